@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — headline measurement of the hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`, or — when
     WORLD_SIZE is not set — bench.py starts its N ranks itself the same way; it exits non-zero rather than fall back to
     the single-GPU headline when N GPUs are not there or WORLD_SIZE disagrees with --gpus)
@@ -10,9 +10,11 @@ Metric (BASELINE.json): soft-min pairs/s at N=M=1e6, D=3, fp32 (+ Sinkhorn wall-
 A *pair* is one evaluation of exp(h_j - C(x_i,y_j)/eps) inside one soft-min reduction.
 
 * N = 1 (the headline): one "step" = one ``glhip_softmin_fwd`` launch over one synthetic problem of 1e6 x 1e6 points
-  in 3D (1e12 pairs), inputs resident in HBM.  Next to it, outside the timed region: the other reductions of the hot
-  path timed with HIP events (``kernels``), the end-to-end losses of the BASELINE configs (``sinkhorn_wallclock``) and
-  the CPU baseline (``cpu_baseline``).
+  in 3D (1e12 pairs), inputs resident in HBM.  A plain run does only that: set-up, W warm-up steps, K timed steps, the
+  outputs (``--dump-outputs``), the line.  With ``--full``, next to it and outside the timed region: the bf16 x 3 layout
+  of the same launch and the PMC traffic (``roofline``), the other reductions of the hot path timed with HIP events
+  (``kernels``), the end-to-end losses of the BASELINE configs (``sinkhorn_wallclock``), the CPU baseline
+  (``cpu_baseline``), ``sharded_batch_reference`` and ``shard_curve``.
 * N > 1: BASELINE configs[3] — the batch of B = 256 problems of 4096 x 4096 bf16 points, sharded over the ranks by
   ``geomloss_amd.distributed.ShardedSamplesLoss`` (one process per GPU, explicit ``diameter``, no data-path
   collective); one step = one whole batched Sinkhorn loss (44 soft-min reductions per problem, fused four to a launch)
@@ -24,12 +26,16 @@ A *pair* is one evaluation of exp(h_j - C(x_i,y_j)/eps) inside one soft-min redu
   peak = 256 CU x 4 SIMD x 2.4 GHz x 64 pairs / 10 cycles = 1.573e13 pairs/s.  ``achieved`` = pairs per launch /
   mean launch duration measured here with HIP events on the launch stream.  The dense-equivalent HBM figure that
   BASELINE.json asks for (4 algorithmic bytes per pair) is kept in ``hbm_dense_equivalent``; it
-  exceeds 1 because the kernel never streams that matrix.  ``traffic`` = HBM bytes per launch of the dominant kernel from two
+  exceeds 1 because the kernel never streams that matrix.  ``traffic`` (``--full``) = HBM bytes per launch of the dominant kernel from two
   rocprofv3 PMC passes that this process runs over a minimal copy of its own command (``measure_traffic``; null if the
   profiler is not there); the builder's fuller PMC summary of the same command stays under ``builder_pmc`` with its source.
-* cpu_baseline (rank 0, N = 1): PyTorch-CPU port of the reference's tensorized Sinkhorn
+* cpu_baseline (rank 0, N = 1, ``--full``): PyTorch-CPU port of the reference's tensorized Sinkhorn
   (oracle/tensorized_torch.py, pinned to the reference by tests/test_oracle_golden.py::test_torch_port_matches_reference)
   on BASELINE configs[0] exactly (N=M=2000, 2D, fp32) and at N=M=5000 3D.
+
+``--dump-outputs DIR``: after the timed steps, what the timed path returned in its last step goes to ``DIR/<name>.npy``
+(N = 1: ``softmin.npy``, the soft-min of every one of the 1e6 points, float32; N > 1: ``loss_sum.npy``, float64, on rank 0).
+The inputs are drawn from fixed seeds, so two builds run with the same arguments can be compared output for output.
 
 Rank 0 prints ONE JSON line on stdout; everything else goes to stderr.
 """
@@ -85,6 +91,18 @@ def emit(obj):
     out = _JSON_OUT if _JSON_OUT is not None else sys.stdout
     out.write(json.dumps(obj) + "\n")
     out.flush()
+
+
+def dump_outputs(directory, arrays):
+    """``--dump-outputs``: one ``<name>.npy`` per array (float32 / float64 as computed) in ``directory``."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(directory, name + ".npy"), a)
+    log(f"[bench] outputs of the last step written to {directory}: {', '.join(sorted(arrays))}")
 
 
 def make_problem(n, dev, seed):
@@ -444,11 +462,13 @@ def run_headline(args, dev):
     t0 = time.perf_counter()
     for k in range(args.steps):
         starts[k].record()               # same stream as the launch (torch's current stream)
-        hip.softmin_fwd_raw(x, y, h, eps, 2, flags=HEADLINE_FLAGS)
+        out = hip.softmin_fwd_raw(x, y, h, eps, 2, flags=HEADLINE_FLAGS)
         stops[k].record()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     kernel_ms = sum(a.elapsed_time(b) for a, b in zip(starts, stops)) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"softmin": out})
 
     pairs_per_launch = float(n) * n
     value = pairs_per_launch * args.steps / elapsed
@@ -498,7 +518,7 @@ def run_headline(args, dev):
             "builder_pmc": builder_pmc,
         },
     }
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         ms3 = event_ms(lambda: hip.softmin_fwd_raw(x, y, h, eps, 2), 3)
         res["roofline"]["bf16x3_layout"] = {"kernel_ms": ms3, "kernel_pairs_per_s": pairs_per_launch / (ms3 * 1e-3),
                                             "note": "the same launch without GLHIP_FLAG_F16X2: softmin_fwd_x32_kernel, three bf16 pieces per "
@@ -549,6 +569,8 @@ def run_sharded(args, dev, rank, world):
         total = loss(x, y)          # local batched loss + scalar all-reduce (RCCL over xGMI)
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss_sum": total.double()})
     t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = t.item()
@@ -653,8 +675,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--points", type=int, default=1_000_000, help="N = M of the soft-min workload (N = 1)")
     ap.add_argument("--batch", type=int, default=256, help="global batch of the sharded workload (N > 1)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the side legs (traffic, kernels, cpu_baseline, wall-clocks)")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 PMC passes that measure roofline.traffic")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: also run the side legs after the timed steps (bf16 x 3 layout, traffic, kernels, cpu_baseline, "
+                         "wall-clocks, shard curve); a plain run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy")
+    ap.add_argument("--no-extras", action="store_true", help="skip the side legs even under --full (traffic, kernels, cpu_baseline, wall-clocks)")
+    ap.add_argument("--no-traffic", action="store_true", help="under --full, skip the two rocprofv3 PMC passes that measure roofline.traffic")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for a 1-GPU dry run)")
     ap.add_argument("--force-sharded", action="store_true",
                     help="run the N>1 (batch-sharded) leg even with one rank: exercises process-group init + the RCCL all-reduce on a 1-GPU box")
@@ -665,6 +692,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.single_device and args.backend == "nccl":
         ap.error("--single-device puts every rank on cuda:0, which RCCL refuses: add --backend gloo")
 

@@ -1,46 +1,65 @@
-"""The reference's OWN test file for ``ot.solve_sample`` (/root/reference/tests/test_ot_solve_sample.py: Diracs drawn by
-hypothesis over library / dtype / device / batch shape, checked by the reference's check_ot_result.py), run without touching a
-line of it, against ``geomloss_amd.ot`` on the HIP kernels — through the import shim of tests/refshim/ (``geomloss.ot`` ->
-``geomloss_amd.ot``; ``pytest_check`` stub).
+"""The reference's Dirac test of ``ot.solve_sample`` (one point on each side, drawn by its hypothesis strategy over library / dtype /
+weights), replayed from the draws recorded in tests/golden/reference_diracs_ot.npz (tests/golden/make_golden_ot_diracs.py): the
+reference tree is not part of this repository, so the drawn inputs and expected answers travel instead.
 
-Where it can run.  It needs BOTH the reference tree (read-only, present in the build container only — reference sources may not
-be copied into this repository) and a GPU (``geomloss_amd.ot`` has no CPU path).  The build container has no GPU and the GPU
-boxes have no reference tree, so in the driver's two test runs the GPU half is skipped; what runs everywhere the reference tree
-exists is the collection half (the shim resolves every import of the reference's test package).  The same closed forms are
-restated in tests/test_ot_gpu.py, which does run on the GPU box.
+* CPU: every recorded draw is an un-batched call, its arguments bind to ``geomloss_amd.ot.solve_sample``, and the result class
+  exposes every field that is compared.
+* GPU: every draw through ``geomloss_amd.ot.solve_sample`` on the HIP kernels; each returned field keeps the library and dtype of
+  the inputs and the shape of the expected answer, and the values pass ``conftest.reference_accepts``.
 """
-import os
-import subprocess
-import sys
+import inspect
 
+import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.environ.get("GEOMLOSS_REFERENCE", "/root/reference")
-REF_TEST = os.path.join(REF, "tests", "test_ot_solve_sample.py")
-needs_reference = pytest.mark.skipif(not os.path.exists(REF_TEST), reason="the reference tree is not on this machine")
+from conftest import reference_accepts, reference_dirac_cases
+from geomloss_amd import ot
+
+FIELDS = ("value", "plan", "potential_a", "potential_b", "marginal_a", "marginal_b")
 
 
-def _pytest_on_reference(scratch, *extra):
-    # nothing may be written into the reference tree: no bytecode, no pytest cache, hypothesis' example database elsewhere;
-    # `-c /dev/null`: the reference's pyproject.toml asks for the pytest-cov plugin, which is not installed here
-    env = dict(os.environ, GEOMLOSS_REFERENCE_SRC=os.path.join(REF, "src"), PYTHONDONTWRITEBYTECODE="1",
-               HYPOTHESIS_STORAGE_DIRECTORY=os.path.join(str(scratch), "hypothesis"),
-               PYTHONPATH=os.pathsep.join([os.path.join(ROOT, "tests", "refshim"), ROOT, os.environ.get("PYTHONPATH", "")]))
-    cmd = [sys.executable, "-m", "pytest", REF_TEST, "-q", "-c", os.devnull, "-p", "no:cacheprovider", "--rootdir", REF, *extra]
-    return subprocess.run(cmd, capture_output=True, text=True, timeout=1200, env=env, cwd=str(scratch))
+def _solver_kwargs(c):
+    return dict(a=c.get("a"), b=c.get("b"), cost="sqeuclidean", reg=float(c["reg"]), unbalanced=None, max_iter=int(c["max_iter"]),
+                method=str(c["method"]))
 
 
-@needs_reference
-def test_reference_test_file_collects_against_geomloss_amd(tmp_path):
-    out = _pytest_on_reference(tmp_path, "--collect-only")
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-2000:]
-    assert "test_correct_values_diracs" in out.stdout
+def test_reference_test_file_collects_against_geomloss_amd():
+    cases = reference_dirac_cases()
+    assert len(cases) == 60
+    sig = inspect.signature(ot.solve_sample)
+    for c in cases:
+        assert c["X_a"].ndim == 2 and c["X_b"].ndim == 2
+        assert str(c["library"]) in ("numpy", "torch") and str(c["dtype"]) in ("float32", "float64")
+        sig.bind(c["X_a"], c["X_b"], **_solver_kwargs(c))
+        assert {k[5:] for k in c if k.startswith("want_")} <= set(FIELDS)
+    for k in FIELDS + ("a_to_b", "b_to_a"):
+        assert hasattr(ot.OTResultSample, k), k
 
 
-@needs_reference
 @pytest.mark.gpu
-def test_reference_test_file_passes_unmodified(cuda, tmp_path):
-    out = _pytest_on_reference(tmp_path)
-    assert out.returncode == 0, out.stdout[-4000:] + out.stderr[-2000:]
-    assert "passed" in out.stdout
+def test_reference_test_file_passes_unmodified(cuda):
+    import torch
+
+    for i, c in enumerate(reference_dirac_cases()):
+        lib, dtype = str(c["library"]), str(c["dtype"])
+
+        def cast(v):
+            if v is None:
+                return None
+            v = np.asarray(v).astype(dtype)
+            return torch.from_numpy(v).to(cuda) if lib == "torch" else v
+        kw = dict(_solver_kwargs(c), a=cast(c.get("a")), b=cast(c.get("b")))
+        res = ot.solve_sample(cast(c["X_a"]), cast(c["X_b"]), **kw)
+        got = {}
+        for k in FIELDS:
+            v = getattr(res, k)
+            if lib == "torch":
+                assert isinstance(v, torch.Tensor) and v.device == cuda, (i, k)
+                v = v.cpu().numpy()
+            v = np.asarray(v)
+            assert str(v.dtype) == dtype, (i, k, v.dtype)
+            got[k] = v
+        want = {k[5:]: c[k] for k in c if k.startswith("want_")}
+        for k, w in want.items():
+            assert got[k].shape == np.shape(w), (i, k, got[k].shape, np.shape(w))
+        assert reference_accepts(got, want, float(c["atol"]), float(c["rtol"])) == [], i

@@ -8,6 +8,7 @@ set -u
 TAG=${1:-r02}
 mkdir -p gpurun_out
 STATUS=gpurun_out/final_measure_$TAG.status
+OUT=$(dirname "$STATUS")      # the directory every leg writes into
 : > $STATUS
 FAIL=0
 
@@ -31,7 +32,7 @@ leg() {   # leg <name> <output file | -> <timeout s> <command...>     (SKIP="nam
     fi
 }
 
-leg bench gpurun_out/bench_$TAG.json 900 python bench.py --steps 20 --warmup 5
+leg bench "$OUT/bench_$TAG.json" 900 python bench.py --full --steps 20 --warmup 5     # with the side legs
 leg profile_gpu - 900 bash tools/profile_gpu.sh $TAG                    # kernel trace + PMC passes of the headline command
 leg summarize_profile - 200 python tools/summarize_profile.py gpurun_out/prof_$TAG $TAG
 cp profiles/${TAG}_kernel_trace_stats.txt profiles/${TAG}_pmc_softmin.json gpurun_out/ 2>/dev/null      # (written under profiles/ on the box: only gpurun_out/ comes back)
