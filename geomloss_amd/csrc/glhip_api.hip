@@ -105,15 +105,18 @@ int glhip_softmin_fwd(const void* x, const void* y, const float* h, float* out, 
     if (p != 1 && p != 2) return fail(GLHIP_EUNSUPPORTED, "glhip_softmin_fwd: p must be 1 or 2 (got %d)", p);
     const Ranges rg{ranges_i, slices_i, redranges_j};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (p == 1 && autosort_applies(B, N, M, D, n_ranges, flags)) {      // glhip_autosort.h: compact row blocks -> distances on the matrix cores
+    // glhip_autosort.h: p = 1 — compact row blocks -> distances on the matrix cores; p = 2 — only the column blocks that can change a
+    // float32 result (exact block pruning)
+    if ((p == 1 || prune_applies(N, M)) && autosort_applies(B, N, M, D, n_ranges, flags)) {
         AutoSort a;
         const int C = (N + kSortSlab - 1) / kSortSlab;
-        rc = autosort_prepare(a, x, y, N, M, D, in_dtype, workspace, workspace_bytes, glhip_workspace_bytes(1, N, M, D, C), st);
+        rc = autosort_prepare(a, x, y, N, M, D, in_dtype, workspace, workspace_bytes, glhip_workspace_bytes(1, N, M, D, C), st, p == 1);
         if (rc) return rc;
         if (a.on) {
             gather_f32(h, a.perm_y, a.col0, M, st);
+            if (p == 2) prune_ranges(a.xs, a.ys, a.col0, nullptr, 0.f, N, M, D, in_dtype, eps, a.ranges_i, a.slices_i, a.red, a.blocks, st);
             rc = glhip_softmin_fwd(a.xs, a.ys, a.col0, a.out, 1, N, M, D, eps, p, in_dtype, a.ranges_i, a.slices_i, a.red, a.C, a.inner_ws,
-                                   a.inner_bytes, flags | GLHIP_FLAG_MFMA_DIST | GLHIP_FLAG_NO_SORT, stream);
+                                   a.inner_bytes, flags | (p == 1 ? GLHIP_FLAG_MFMA_DIST : 0) | GLHIP_FLAG_NO_SORT, stream);
             if (rc) return rc;
             scatter_f32(a.out, a.perm_x, out, N, st);
             return check_launch("glhip_softmin_fwd");
@@ -139,17 +142,20 @@ int glhip_sinkhorn_step(const void* x, const void* y, const float* logw, const f
     if (p != 1 && p != 2) return fail(GLHIP_EUNSUPPORTED, "glhip_sinkhorn_step: p must be 1 or 2 (got %d)", p);
     const Ranges rg{ranges_i, slices_i, redranges_j};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (p == 1 && autosort_applies(B, N, M, D, n_ranges, flags)) {      // as glhip_softmin_fwd; the potentials travel with their clouds
+    if ((p == 1 || prune_applies(N, M)) && autosort_applies(B, N, M, D, n_ranges, flags)) {   // as glhip_softmin_fwd; the potentials travel with their clouds
         AutoSort a;
         const int C = (N + kSortSlab - 1) / kSortSlab;
-        rc = autosort_prepare(a, x, y, N, M, D, in_dtype, workspace, workspace_bytes, glhip_workspace_bytes(1, N, M, D, C), st);
+        rc = autosort_prepare(a, x, y, N, M, D, in_dtype, workspace, workspace_bytes, glhip_workspace_bytes(1, N, M, D, C), st, p == 1);
         if (rc) return rc;
         if (a.on) {
             gather_f32(logw, a.perm_y, a.col0, M, st);
             if (pot) gather_f32(pot, a.perm_y, a.col1, M, st);
             if (prev) gather_f32(prev, a.perm_x, a.row0, N, st);
+            // (the bound takes the column vector the kernels form: logw + pot / eps)
+            if (p == 2) prune_ranges(a.xs, a.ys, a.col0, pot ? a.col1 : nullptr, 1.0f / eps, N, M, D, in_dtype, eps, a.ranges_i, a.slices_i, a.red, a.blocks, st);
             rc = glhip_sinkhorn_step(a.xs, a.ys, a.col0, pot ? a.col1 : nullptr, prev ? a.row0 : nullptr, a.out, 1, N, M, D, eps, damping, p, in_dtype,
-                                     a.ranges_i, a.slices_i, a.red, a.C, a.inner_ws, a.inner_bytes, flags | GLHIP_FLAG_MFMA_DIST | GLHIP_FLAG_NO_SORT, stream);
+                                     a.ranges_i, a.slices_i, a.red, a.C, a.inner_ws, a.inner_bytes,
+                                     flags | (p == 1 ? GLHIP_FLAG_MFMA_DIST : 0) | GLHIP_FLAG_NO_SORT, stream);
             if (rc) return rc;
             scatter_f32(a.out, a.perm_x, out, N, st);
             return check_launch("glhip_sinkhorn_step");

@@ -8,7 +8,7 @@
 //   bounding box -> voxel edge (~256 rows per voxel; columns: 512) -> boustrophedon path index of every point as the sort key ->
 //   rocPRIM radix sort -> gathered clouds and column / row vectors -> the block-sparse launch "every slab of 256 rows x all columns"
 //   with GLHIP_FLAG_MFMA_DIST -> results scattered back to the caller's row order.
-// Conditions: B = 1, dense, D <= 3, N >= 65536, N M >= 5e8, neither GLHIP_FLAG_NO_MFMA / _DIRECT nor GLHIP_FLAG_NO_SORT, and a
+// Conditions: B = 1, dense, D <= 3, N >= 65536, N M >= 5e8 (p = 2: >= 1e11, prune_applies), neither GLHIP_FLAG_NO_MFMA / _DIRECT nor GLHIP_FLAG_NO_SORT, and a
 // workspace of glhip_workspace_bytes(...) (smaller: the generic kernel, as before).  Two sorts of ~0.5 ms against ~200 ms.
 #pragma once
 
@@ -23,6 +23,47 @@ constexpr int kSortSlab = 256;        // rows per row block = the row tile of th
 constexpr int kSortColChunks = 8;     // column intervals per slab: something for the column splits to split
 constexpr int kSortRowsPerVoxel = 256;
 
+// p = 2 soft-min / half-step (round 7): the sorted launch keeps only the column blocks that can matter in float32.
+//   T: kPruneColBlock consecutive sorted columns; R: a slab of kSortSlab sorted rows; h_j the dual value of column j (logw + pot / eps
+//   for the half-step).  With boxes of R and T and dmin / dmax their smallest / largest distance,
+//     Mlb(R) = max_T [hmax(T) - dmax(R,T)^2 / (2 eps)]        <= max_j [h_j - |x_i - y_j|^2 / (2 eps)] for every row i of R,
+//   and T is kept iff hmax(T) - dmin(R,T)^2 / (2 eps) >= Mlb(R) - L, L = ln M + 26 ln 2 + kPruneMarginNats.  Every term of a dropped
+//   block is below e^(Mlb - L) <= 2^-26 e^-margin / M times the row's largest term, so all of them together are below 2^-26 of the row
+//   sum: the output -eps log(sum) moves by less than eps 2^-26, under one float32 ulp of it.  The bound is evaluated in float64 from
+//   the exact float32 box corners; the margin (1 nat) covers the exponent error of the f16 x 2 layout on the dropped terms and on the
+//   row maximum (2^-21 of up to ~2.6e5 log2 units: 0.09 nat each) and the float32 rounding of logw + pot / eps.
+//   Special values keep the dense launch's behaviour: a column block with a non-finite coordinate or a NaN dual value is kept by every
+//   slab (and left out of Mlb); a slab with a non-finite coordinate or a non-finite Mlb (all h = -inf, h = +inf, ...) keeps everything;
+//   a block whose dual values are all -inf may go.
+//   Kept blocks become column intervals per slab: at most kPruneRuns runs (a slab with more closes its smallest gaps: more work,
+//   never less), cut on a grid of pieces so that the column splits of the inner launch, which take a slab's intervals round robin,
+//   get even shares even when nothing prunes.
+constexpr int kPruneColBlock = 256;   // columns per column block T (a multiple of 32)
+constexpr int kPruneRuns = 160;       // runs of kept blocks per slab (the bench problem: mean 66, max 143 at 256 columns per block)
+constexpr int kPruneGrid = 64;        // pieces a whole row of column blocks is cut into, at most
+constexpr double kPruneMarginNats = 1.0;
+
+struct PrunePlan {
+    int nT;    // column blocks
+    int PB;    // column blocks per grid piece
+    int S;     // interval slots per slab
+};
+inline PrunePlan prune_plan(int M) {
+    PrunePlan p;
+    p.nT = (M + kPruneColBlock - 1) / kPruneColBlock;
+    p.PB = (p.nT + kPruneGrid - 1) / kPruneGrid;
+    p.PB = p.PB > 64 ? p.PB : 64;                  // pieces of at least 16384 columns
+    p.S = kPruneRuns + (p.nT + p.PB - 1) / p.PB;   // runs + grid cuts inside them
+    return p;
+}
+// From 1e11 pairs on: the two sorts, the bound and the scatter cost ~1 ms per call, and the online loss at N = M = 1e5 (1e10 pairs per
+// half-step, ~0.8 ms each dense) went from 34.4 to 46.8 ms with every call pruned.  Interval slots address red[2 q] with an int.
+constexpr double kPruneMinPairs = 1e11;
+inline bool prune_applies(int N, int M) {
+    const long C = (N + kSortSlab - 1) / kSortSlab;
+    return (double)N * M >= kPruneMinPairs && C * (long)prune_plan(M).S * 2 < (1L << 31) - 1;
+}
+
 inline size_t as_align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // implemented in glhip_cluster.hip (rocPRIM lives there)
@@ -32,6 +73,10 @@ int compact_sort(const void* z, int n, int D, int in_dtype, int rows_per_voxel, 
 void gather_f32(const float* src, const int32_t* perm, float* dst, int n, hipStream_t st);       // dst[k] = src[perm[k]]
 void scatter_f32(const float* src, const int32_t* perm, float* dst, int n, hipStream_t st, int width = 1);      // dst[perm[k], :] = src[k, :]
 void slab_ranges(int N, int M, int32_t* ranges_i, int32_t* slices_i, int32_t* red, hipStream_t st);
+size_t prune_blocks_bytes(int M);
+// the kept column intervals of every slab of the sorted clouds xs (N, D), ys (M, D) for the column vector h (+ pot * pot_scale)
+void prune_ranges(const void* xs, const void* ys, const float* h, const float* pot, float pot_scale, int N, int M, int D, int in_dtype,
+                  float eps, int32_t* ranges_i, int32_t* slices_i, int32_t* red, void* blocks, hipStream_t st);
 
 inline bool autosort_applies(int B, int N, int M, int D, int n_ranges, int flags) {
     return B == 1 && n_ranges == 0 && D <= 3 && N >= 65536 && (double)N * M >= 5e8 &&
@@ -45,6 +90,7 @@ struct AutoSort {
     void *xs = nullptr, *ys = nullptr;
     float *col0 = nullptr, *col1 = nullptr, *row0 = nullptr, *out = nullptr;      // gathered per-column / per-row vectors, sorted output
     float* out_rows = nullptr;              // (N, D) sorted output (row gradients)
+    void* blocks = nullptr;                 // per-column-block boxes and dual maxima (pruned p = 2 launches)
     void* inner_ws = nullptr;
     size_t inner_bytes = 0;
 };
@@ -53,16 +99,18 @@ struct AutoSort {
 inline size_t autosort_bytes(int N, int M, int D) {
     const int C = (N + kSortSlab - 1) / kSortSlab;
     const int L = N > M ? N : M;
+    const size_t slots = (size_t)(kSortColChunks > prune_plan(M).S ? kSortColChunks : prune_plan(M).S);   // interval slots per slab
     return as_align256((size_t)N * 4) + as_align256((size_t)M * 4) + as_align256((size_t)N * D * 4) + as_align256((size_t)M * D * 4) +
            2 * as_align256((size_t)M * 4) + 2 * as_align256((size_t)N * 4) + as_align256((size_t)N * D * 4) + as_align256((size_t)C * 8) +
            as_align256((size_t)C * 4) +
-           as_align256((size_t)C * kSortColChunks * 8) + compact_sort_scratch_bytes(L);
+           as_align256((size_t)C * slots * 8) + as_align256(prune_blocks_bytes(M)) + compact_sort_scratch_bytes(L);
 }
 
 // Sorts both clouds into the workspace; `a.on` stays false when the workspace is too small for the sorted call plus `inner_min`
-// bytes of scratch for the launch itself (the caller then runs the generic kernel).
+// bytes of scratch for the launch itself (the caller then runs the generic kernel).  slabs = false: the caller fills the ranges
+// itself (prune_ranges) once its column vector is gathered.
 inline int autosort_prepare(AutoSort& a, const void* x, const void* y, int N, int M, int D, int in_dtype, void* workspace,
-                            size_t workspace_bytes, size_t inner_min, hipStream_t st) {
+                            size_t workspace_bytes, size_t inner_min, hipStream_t st, bool slabs = true) {
     const size_t need = autosort_bytes(N, M, D);
     if (!workspace || workspace_bytes < need + inner_min) return 0;
     char* w = static_cast<char*>(workspace);
@@ -80,7 +128,9 @@ inline int autosort_prepare(AutoSort& a, const void* x, const void* y, int N, in
     a.out_rows = reinterpret_cast<float*>(take((size_t)N * D * 4));
     a.ranges_i = reinterpret_cast<int32_t*>(take((size_t)a.C * 8));
     a.slices_i = reinterpret_cast<int32_t*>(take((size_t)a.C * 4));
-    a.red = reinterpret_cast<int32_t*>(take((size_t)a.C * kSortColChunks * 8));
+    const size_t slots = (size_t)(kSortColChunks > prune_plan(M).S ? kSortColChunks : prune_plan(M).S);
+    a.red = reinterpret_cast<int32_t*>(take((size_t)a.C * slots * 8));
+    a.blocks = take(prune_blocks_bytes(M));
     const int L = N > M ? N : M;
     const size_t sb = compact_sort_scratch_bytes(L);
     void* scratch = take(sb);
@@ -88,7 +138,7 @@ inline int autosort_prepare(AutoSort& a, const void* x, const void* y, int N, in
     if (rc) return rc;
     rc = compact_sort(y, M, D, in_dtype, 2 * kSortRowsPerVoxel, a.perm_y, a.ys, scratch, sb, st);
     if (rc) return rc;
-    slab_ranges(N, M, a.ranges_i, a.slices_i, a.red, st);
+    if (slabs) slab_ranges(N, M, a.ranges_i, a.slices_i, a.red, st);
     a.inner_ws = w + off;
     a.inner_bytes = workspace_bytes - off;
     a.on = true;

@@ -6,6 +6,7 @@
 // helpers with torch tensor ops (dozens of small launches, two host round trips each, and 1.2 s of lazily loaded torch code
 // objects on the first call).  Here: a handful of launches on the caller's stream, no host round trip inside the library,
 // deterministic results (fixed-order float64 sums, no atomics on floating-point data).
+#include <cmath>
 #include <cstring>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -362,6 +363,198 @@ __global__ void __launch_bounds__(256) slab_ranges_kernel(int N, int M, int C, i
     }
 }
 
+// ---- exact block pruning of the sorted p = 2 launch (glhip_autosort.h: the bound and why it is exact) ------------------------------
+
+struct ColBlock {           // one block of kPruneColBlock sorted columns
+    float lo[3];
+    float hmax;             // largest dual value of the block (-inf: all -inf)
+    float hi[3];
+    int special;            // a non-finite coordinate or a NaN dual value: kept by every slab, left out of Mlb
+};
+
+// one wavefront per column block; lane l takes columns l, l + 64, ...
+template <typename T>
+__global__ void __launch_bounds__(256) prune_blocks_kernel(const T* __restrict__ ys, const float* __restrict__ h, const float* __restrict__ pot,
+                                                           float pot_scale, int M, int D, int nT, ColBlock* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= nT) return;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    float hm = -INFINITY;
+    int bad = 0;
+    const int j0 = t * kPruneColBlock, j1 = min(M, j0 + kPruneColBlock);
+    for (int j = j0 + lane; j < j1; j += 64) {
+        for (int d = 0; d < D; ++d) {
+            const float v = to_f32<T>(ys[(long)j * D + d]);
+            bad |= !__builtin_isfinite(v);
+            lo[d] = fminf(lo[d], v);
+            hi[d] = fmaxf(hi[d], v);
+        }
+        const float hv = pot ? __builtin_fmaf(pot[j], pot_scale, h[j]) : h[j];     // as the half-step forms it (glhip_softmin_ops.h)
+        bad |= __builtin_isnan(hv);
+        hm = fmaxf(hm, hv);
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        for (int d = 0; d < D; ++d) {
+            lo[d] = fminf(lo[d], __shfl_xor(lo[d], off, 64));
+            hi[d] = fmaxf(hi[d], __shfl_xor(hi[d], off, 64));
+        }
+        hm = fmaxf(hm, __shfl_xor(hm, off, 64));
+        bad |= __shfl_xor(bad, off, 64);
+    }
+    if (lane == 0) {
+        ColBlock b;
+        for (int d = 0; d < 3; ++d) {
+            b.lo[d] = d < D ? lo[d] : 0.f;
+            b.hi[d] = d < D ? hi[d] : 0.f;
+        }
+        b.hmax = hm;
+        b.special = bad;
+        out[t] = b;
+    }
+}
+
+// squared distances between two boxes, smallest and largest, in float64 (exact float32 corners in, 1e-16 relative error out)
+__device__ __forceinline__ void box_d2(const double (&rlo)[3], const double (&rhi)[3], const ColBlock& b, int D, double& dmin2, double& dmax2) {
+    dmin2 = 0.0;
+    dmax2 = 0.0;
+    for (int d = 0; d < D; ++d) {
+        const double blo = b.lo[d], bhi = b.hi[d];
+        const double gap = fmax(fmax(blo - rhi[d], rlo[d] - bhi), 0.0);
+        const double far = fmax(bhi - rlo[d], rhi[d] - blo);
+        dmin2 = fma(gap, gap, dmin2);
+        dmax2 = fma(far, far, dmax2);
+    }
+}
+
+// inclusive scan of one int per thread over a 256-thread workgroup (MAX: maximum, else sum); `buf` holds 256 ints of LDS
+template <bool MAX>
+__device__ __forceinline__ int block_scan256(int v, int* buf) {
+    const int t = threadIdx.x;
+    buf[t] = v;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+        const int o = t >= off ? buf[t - off] : (MAX ? INT_MIN : 0);
+        __syncthreads();
+        v = MAX ? max(v, o) : v + o;
+        buf[t] = v;
+        __syncthreads();
+    }
+    return v;
+}
+
+// One workgroup per slab of kSortSlab sorted rows: its box, Mlb, then the kept blocks as column intervals in its S slots of `red`
+// (unused slots: empty intervals, which the kernels skip).  A piece starts at a kept block that opens a run (the gap to the previous
+// kept block is >= g blocks) or that sits on the piece grid (a multiple of PB).  g = 1 unless the slab has more than kPruneRuns runs;
+// then g is the smallest gap length that leaves at most kPruneRuns runs (gaps shorter than g are closed).
+template <typename T>
+__global__ void __launch_bounds__(256) prune_slabs_kernel(const T* __restrict__ xs, int N, int M, int D, const ColBlock* __restrict__ blocks,
+                                                          int nT, int PB, int S, double inv2eps, double L, int32_t* __restrict__ ranges_i,
+                                                          int32_t* __restrict__ slices_i, int32_t* __restrict__ red) {
+    __shared__ int buf[256];
+    __shared__ float wlo[4][3], whi[4][3];
+    __shared__ double wm[4];
+    const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r0 = k * kSortSlab, r1 = min(N, r0 + kSortSlab);
+    if (tid == 0) {
+        ranges_i[2 * k] = r0;
+        ranges_i[2 * k + 1] = r1;
+        slices_i[k] = (k + 1) * S;
+    }
+    // the slab's box
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    int bad = 0;
+    if (r0 + tid < r1) {
+        for (int d = 0; d < D; ++d) {
+            const float v = to_f32<T>(xs[(long)(r0 + tid) * D + d]);
+            bad |= !__builtin_isfinite(v);
+            lo[d] = v;
+            hi[d] = v;
+        }
+    }
+    for (int d = 0; d < D; ++d) {
+        for (int off = 32; off > 0; off >>= 1) {
+            lo[d] = fminf(lo[d], __shfl_xor(lo[d], off, 64));
+            hi[d] = fmaxf(hi[d], __shfl_xor(hi[d], off, 64));
+        }
+        if (lane == 0) { wlo[wave][d] = lo[d]; whi[wave][d] = hi[d]; }
+    }
+    bad = __syncthreads_or(bad);
+    double rlo[3] = {0.0, 0.0, 0.0}, rhi[3] = {0.0, 0.0, 0.0};
+    for (int d = 0; d < D; ++d) {
+        rlo[d] = fminf(fminf(wlo[0][d], wlo[1][d]), fminf(wlo[2][d], wlo[3][d]));
+        rhi[d] = fmaxf(fmaxf(whi[0][d], whi[1][d]), fmaxf(whi[2][d], whi[3][d]));
+    }
+    // Mlb: a lower bound on the largest exponent of every row of the slab
+    double mlb = -INFINITY;
+    if (!bad) {
+        for (int t = tid; t < nT; t += 256) {
+            const ColBlock b = blocks[t];
+            if (b.special) continue;
+            double dmin2, dmax2;
+            box_d2(rlo, rhi, b, D, dmin2, dmax2);
+            mlb = fmax(mlb, (double)b.hmax - dmax2 * inv2eps);
+        }
+        for (int off = 32; off > 0; off >>= 1) mlb = fmax(mlb, __shfl_xor(mlb, off, 64));
+        if (lane == 0) wm[wave] = mlb;
+        __syncthreads();
+        mlb = fmax(fmax(wm[0], wm[1]), fmax(wm[2], wm[3]));
+    }
+    const bool keep_all = bad || !__builtin_isfinite(mlb);
+    const double thr = mlb - L;
+    auto kept = [&](int t) {
+        if (keep_all) return true;
+        const ColBlock b = blocks[t];
+        if (b.special) return true;
+        double dmin2, dmax2;
+        box_d2(rlo, rhi, b, D, dmin2, dmax2);
+        return (double)b.hmax - dmin2 * inv2eps >= thr;
+    };
+    // one walk over the blocks: the number of runs for gap length g, and (EMIT) the pieces written out
+    int32_t* slots = red + 2 * (long)k * S;
+    auto walk = [&](int g, bool emit) {
+        int carry = -1, runs = 0, pieces = 0;
+        for (int c0 = 0; c0 < nT; c0 += 256) {
+            const int t = c0 + tid;
+            const bool kp = t < nT && kept(t);
+            block_scan256<true>(kp ? t : -1, buf);      // buf[t]: the last kept block of the chunk up to t
+            const int prev = max(carry, tid > 0 ? buf[tid - 1] : -1);
+            const int last = buf[255];
+            const bool run = kp && (prev < 0 || t - prev - 1 >= g);
+            const bool start = run || (kp && t % PB == 0);
+            runs += __syncthreads_count(run);             // (also: every read of buf is done before the next scan writes it)
+            carry = max(carry, last);
+            if (emit) {
+                const int idx = pieces + block_scan256<false>(start ? 1 : 0, buf) - 1;
+                if (start && idx < S) {
+                    slots[2 * idx] = t * kPruneColBlock;
+                    if (idx > 0) slots[2 * idx - 1] = min(M, (run ? prev + 1 : t) * kPruneColBlock);
+                }
+                pieces += __syncthreads_count(start);
+            }
+        }
+        if (emit) {
+            const int n = min(pieces, S);
+            if (tid == 0 && n > 0) slots[2 * n - 1] = min(M, (carry + 1) * kPruneColBlock);
+            for (int q = n + tid; q < S; q += 256) {
+                slots[2 * q] = 0;
+                slots[2 * q + 1] = 0;
+            }
+        }
+        return runs;
+    };
+    int g = 1;
+    if (walk(1, false) > kPruneRuns) {
+        int lo_g = 1, hi_g = nT;   // walk(nT) has one run
+        while (hi_g - lo_g > 1) {
+            const int mid = lo_g + (hi_g - lo_g) / 2;
+            if (walk(mid, false) > kPruneRuns) lo_g = mid; else hi_g = mid;
+        }
+        g = hi_g;
+    }
+    walk(g, true);
+}
+
 size_t sort64_temp_bytes(int n) {
     size_t bytes = 0;
     uint64_t* k = nullptr;
@@ -420,6 +613,28 @@ void scatter_f32(const float* src, const int32_t* perm, float* dst, int n, hipSt
 void slab_ranges(int N, int M, int32_t* ranges_i, int32_t* slices_i, int32_t* red, hipStream_t st) {
     const int C = (N + kSortSlab - 1) / kSortSlab;
     hipLaunchKernelGGL(slab_ranges_kernel, dim3((C + 255) / 256), dim3(256), 0, st, N, M, C, ranges_i, slices_i, red);
+}
+
+size_t prune_blocks_bytes(int M) { return (size_t)prune_plan(M).nT * sizeof(ColBlock); }
+
+void prune_ranges(const void* xs, const void* ys, const float* h, const float* pot, float pot_scale, int N, int M, int D, int in_dtype,
+                  float eps, int32_t* ranges_i, int32_t* slices_i, int32_t* red, void* blocks_, hipStream_t st) {
+    const PrunePlan pp = prune_plan(M);
+    const int C = (N + kSortSlab - 1) / kSortSlab;
+    ColBlock* blocks = static_cast<ColBlock*>(blocks_);
+    const double inv2eps = 0.5 / (double)eps;
+    const double L = std::log((double)M) + 26.0 * std::log(2.0) + kPruneMarginNats;
+    if (in_dtype == GLHIP_F32) {
+        hipLaunchKernelGGL(prune_blocks_kernel<float>, dim3((pp.nT + 3) / 4), dim3(256), 0, st, static_cast<const float*>(ys), h, pot, pot_scale, M, D,
+                           pp.nT, blocks);
+        hipLaunchKernelGGL(prune_slabs_kernel<float>, dim3(C), dim3(256), 0, st, static_cast<const float*>(xs), N, M, D, blocks, pp.nT, pp.PB, pp.S,
+                           inv2eps, L, ranges_i, slices_i, red);
+    } else {
+        hipLaunchKernelGGL(prune_blocks_kernel<bf16_t>, dim3((pp.nT + 3) / 4), dim3(256), 0, st, static_cast<const bf16_t*>(ys), h, pot, pot_scale, M,
+                           D, pp.nT, blocks);
+        hipLaunchKernelGGL(prune_slabs_kernel<bf16_t>, dim3(C), dim3(256), 0, st, static_cast<const bf16_t*>(xs), N, M, D, blocks, pp.nT, pp.PB,
+                           pp.S, inv2eps, L, ranges_i, slices_i, red);
+    }
 }
 
 }  // namespace glhip

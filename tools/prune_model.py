@@ -1,0 +1,130 @@
+#!/usr/bin/env python
+"""CPU model of the exact block pruning of big dense p = 2 soft-min launches (csrc/glhip_autosort.h, glhip_cluster.hip).
+
+Restates in NumPy what the library does on the device: both clouds voxel-sorted along a boustrophedon path (compact_sort), rows cut
+into slabs of 256, columns into blocks of 256, the float64 bound
+
+    Mlb(R) = max_T [hmax(T) - dmax(R,T)^2 / (2 eps)],   keep T iff hmax(T) - dmin(R,T)^2 / (2 eps) >= Mlb(R) - (ln M + 26 ln 2 + 1),
+
+and counts the kept pairs and the runs of kept blocks per slab.  ``check_dropped`` verifies on the points themselves that no dropped
+block holds a term above Mlb(R) - L for any row of the slab (tests/test_prune_model.py).
+
+    python tools/prune_model.py [--n 1000000] [--eps 0.0025]     (the bench problem: bench.make_problem(n, seed=1000))
+"""
+
+import argparse
+import math
+
+import numpy as np
+
+SLAB, BLOCK, RUNS, MARGIN = 256, 256, 160, 1.0
+
+
+def compact_order(z, rows_per_voxel):
+    """glhip_cluster.hip: voxel_kernel + path_keys_kernel + a stable radix sort of the keys"""
+    z = np.asarray(z, np.float32)
+    n, D = z.shape
+    lo, hi = z.min(0), z.max(0)
+    ext = (hi - lo).astype(np.float32)
+    emax = float(ext.max())
+    live = ext > np.float32(1e-6) * np.float32(max(emax, 1e-30))
+    vol = np.float32(np.prod(ext[live])) if live.any() else np.float32(1.0)
+    voxel = np.float32(np.power(np.float32(vol * np.float32(rows_per_voxel) / np.float32(n)), np.float32(1.0 / max(int(live.sum()), 1))))
+    voxel = np.float32(max(voxel, np.float32(emax / 2**20), np.float32(1e-30)))
+    qmin = np.floor(lo / voxel).astype(np.int64)
+    e = np.floor((lo + ext) / voxel).astype(np.int64) - qmin + 1
+    path = np.zeros(n, np.uint64)
+    for d in range(D):
+        q = np.clip(np.floor(z[:, d] / voxel).astype(np.int64) - qmin[d], 0, e[d] - 1)
+        c = np.where(path & np.uint64(1), e[d] - 1 - q, q).astype(np.uint64)
+        path = path * np.uint64(e[d]) + c
+    return np.argsort(path, kind="stable")
+
+
+def boxes(z, size):
+    n = z.shape[0]
+    k = (n + size - 1) // size
+    pad = np.full((k * size - n, z.shape[1]), np.nan, z.dtype)
+    zz = np.concatenate([z, pad]).reshape(k, size, -1)
+    return np.nanmin(zz, 1).astype(np.float64), np.nanmax(zz, 1).astype(np.float64)
+
+
+def plan(xs, ys, h, eps):
+    """keep (C, nT) bool, Mlb (C,), L — for finite inputs (the special values are the device's business, tested on the GPU)"""
+    M = ys.shape[0]
+    rlo, rhi = boxes(xs, SLAB)
+    blo, bhi = boxes(ys, BLOCK)
+    nT = blo.shape[0]
+    hp = np.concatenate([h.astype(np.float64), np.full(nT * BLOCK - M, -np.inf)]).reshape(nT, BLOCK)
+    hmax = hp.max(1)
+    L = math.log(M) + 26 * math.log(2) + MARGIN
+    keep = np.zeros((rlo.shape[0], nT), bool)
+    mlb = np.zeros(rlo.shape[0])
+    for c0 in range(0, rlo.shape[0], 256):
+        a, b = rlo[c0:c0 + 256, None], rhi[c0:c0 + 256, None]
+        gap = np.maximum(np.maximum(blo[None] - b, a - bhi[None]), 0.0)
+        far = np.maximum(bhi[None] - a, b - blo[None])
+        dmin2, dmax2 = (gap**2).sum(-1), (far**2).sum(-1)
+        m = (hmax[None] - dmax2 / (2 * eps)).max(1)
+        mlb[c0:c0 + 256] = m
+        keep[c0:c0 + 256] = hmax[None] - dmin2 / (2 * eps) >= (m - L)[:, None]
+    return keep, mlb, L
+
+
+def runs_per_slab(keep):
+    k = keep.astype(np.int8)
+    return (np.diff(np.concatenate([np.zeros((k.shape[0], 1), np.int8), k], 1), axis=1) == 1).sum(1)
+
+
+def kept_pairs(keep, N, M):
+    rows = np.full(keep.shape[0], SLAB)
+    rows[-1] = N - SLAB * (keep.shape[0] - 1)
+    cols = np.full(keep.shape[1], BLOCK)
+    cols[-1] = M - BLOCK * (keep.shape[1] - 1)
+    return float(rows @ keep.astype(np.float64) @ cols)
+
+
+def check_dropped(xs, ys, h, eps, keep, mlb, L, slabs):
+    """largest (term - (Mlb - L)) over the dropped blocks of the given slabs, exact float64 terms; < 0 means the bound held"""
+    worst = -np.inf
+    for c in slabs:
+        xr = xs[c * SLAB:(c + 1) * SLAB].astype(np.float64)
+        cols = np.concatenate([np.arange(t * BLOCK, min((t + 1) * BLOCK, ys.shape[0])) for t in np.flatnonzero(~keep[c])] or [np.zeros(0, int)])
+        if cols.size == 0:
+            continue
+        d2 = ((xr[:, None, :] - ys[cols].astype(np.float64)[None]) ** 2).sum(-1)
+        terms = h[cols].astype(np.float64)[None] - d2 / (2 * eps)
+        worst = max(worst, float(terms.max() - (mlb[c] - L)))
+    return worst
+
+
+def bench_problem(n, seed=1000):
+    """bench.make_problem(n, seed) without torch's device copy (same generator calls, same values)"""
+    import torch
+
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    x = torch.rand(n, 3, generator=g)
+    y = torch.rand(n, 3, generator=g)
+    eps = 0.05**2
+    h = torch.full((n,), -math.log(n)) + 0.01 * torch.randn(n, generator=g) / eps
+    return x.numpy(), y.numpy(), h.numpy(), eps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=1000000)
+    ap.add_argument("--eps", type=float, nargs="*", default=[0.01**2, 0.05**2, 0.2**2, 1.0])
+    a = ap.parse_args()
+    x, y, h, _ = bench_problem(a.n)
+    px, py = compact_order(x, 256), compact_order(y, 512)
+    xs, ys, hs = x[px], y[py], h[py]
+    for eps in a.eps:
+        keep, mlb, L = plan(xs, ys, hs, eps)
+        r = runs_per_slab(keep)
+        frac = kept_pairs(keep, a.n, a.n) / (float(a.n) * a.n)
+        print(f"n = {a.n}  eps = {eps:.4g}: L = {L:.2f} nats, kept pairs {frac:.4f}, kept blocks per slab {keep.sum(1).mean():.0f} of {keep.shape[1]}, "
+              f"runs per slab mean {r.mean():.1f} max {r.max()}, slabs over {RUNS} runs {(r > RUNS).sum()}", flush=True)
+
+
+if __name__ == "__main__":
+    main()
