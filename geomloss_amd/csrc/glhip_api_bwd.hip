@@ -60,9 +60,10 @@ int glhip_cmin_fwd(const void* x, const void* y, const float* g, float* out, int
     auto run = [&](auto tag) {
         using T = decltype(tag);
         const CminParams<T> prm{static_cast<const T*>(x), static_cast<const T*>(y), g, out};
-#define GL_CMIN(DD, PP) launch_mapreduce<HardMinOp<DD, PP, 2, T>>(prm, rg, n_ranges, B, N, M, sc.ws, sc.bytes, sc.allow_split, st, sc.cb)
-        if (p == 2) { if (D == 1) GL_CMIN(1, 2); else if (D == 2) GL_CMIN(2, 2); else GL_CMIN(3, 2); }
-        else        { if (D == 1) GL_CMIN(1, 1); else if (D == 2) GL_CMIN(2, 1); else GL_CMIN(3, 1); }
+#define GL_CMIN(DD) \
+    if (p == 2) launch_mapreduce<HardMinOp<DD, 2, 2, T>>(prm, rg, n_ranges, B, N, M, sc.ws, sc.bytes, sc.allow_split, st, sc.cb); \
+    else launch_mapreduce<HardMinOp<DD, 1, 2, T>>(prm, rg, n_ranges, B, N, M, sc.ws, sc.bytes, sc.allow_split, st, sc.cb)
+        GLHIP_D3_DISPATCH(D, GL_CMIN)
 #undef GL_CMIN
     };
     if (in_dtype == GLHIP_F32) run(float{}); else run(bf16_t{});

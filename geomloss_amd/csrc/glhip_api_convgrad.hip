@@ -68,10 +68,11 @@ int glhip_kernel_conv_fwd_grad(int kind, const void* x, const void* y, const flo
 #define GL_XD(DD) launch_gauss_grad_t32<DD, true, T>(prm, blur, rg, n_ranges, B, N, M, sc, st)
                 GLHIP_XD_DISPATCH(D, GL_XD)
 #undef GL_XD
+            } else {
+#define GL_D(DD) launch_gauss_fwdgrad<DD, T>(prm, blur, rg, n_ranges, B, N, M, sc, st)
+                GLHIP_D3_DISPATCH(D, GL_D)
+#undef GL_D
             }
-            else if (D == 1) launch_gauss_fwdgrad<1, T>(prm, blur, rg, n_ranges, B, N, M, sc, st);
-            else if (D == 2) launch_gauss_fwdgrad<2, T>(prm, blur, rg, n_ranges, B, N, M, sc, st);
-            else launch_gauss_fwdgrad<3, T>(prm, blur, rg, n_ranges, B, N, M, sc, st);
         } else if (kind == GLHIP_LAPLACIAN) {   // same scales as conv_typed (glhip_launch.h)
             prm.t = kLog2e / blur;
             prm.gscale = -1.0f / blur;

@@ -3,7 +3,7 @@
 // derivation of the bf16 x 3 layout; the f16 x 2 one is described below.
 #pragma once
 
-#include "glhip_softmin_xdl.h"
+#include "glhip_mfma_common.h"
 
 namespace glhip {
 

@@ -23,6 +23,8 @@
 //   store_partial / merge_row.
 #pragma once
 
+#include <type_traits>
+
 #include "glhip_common.h"
 
 namespace glhip {
@@ -316,33 +318,79 @@ static inline Ranges with_row_chunks(const Ranges& rg, int n_ranges, int N, int 
     return out;
 }
 
+// The column-split mechanics of a row-tiled reduction launch (this file's kernel and the matrix-core kernels of glhip_launch.h):
+// row-chunk table, split workspace, SplitInfo, grid, main launch, merge launch.  Every policy stays with the launcher: between
+// construction and launch() it sets sp.n_splits (and sp.gather / sp.share), may move a dense launch to the XCD-aware 1-D grid
+// (take_xcd) and may place pre-packed columns at packed_offset().  launch() hands the main kernel's launch to a callable
+// main(std::integral_constant<bool, SPARSE>, grid, ranges), then queues merge_kernel<MergeOp, SPARSE> when the columns are split.
+struct SplitLaunch {
+    Ranges rg;                  // the caller's ranges: what the merge kernel reads
+    Ranges rgc;                 // what the main kernel reads: block-sparse launches with a row-chunk table get it here
+    int n_ranges, B, N, M;
+    int gx;                     // dense launches: row blocks per batch item
+    unsigned chunk_grid = 0;    // block-sparse launches: grid.x (one workgroup per row chunk, or per row block without a table)
+    long row_blocks;            // what the split rules count: row blocks (not chunks) of block-sparse launches
+    long per_split;             // bytes of workspace per column split
+    long fit;                   // column splits the workspace holds
+    SplitInfo sp;
+
+    // `rows`: rows per workgroup of the main kernel; `partial`: floats per row and split (MergeOp::kPartial)
+    SplitLaunch(const Ranges& ranges, int n_ranges_, int B_, int N_, int M_, int rows, int partial, void* workspace, size_t bytes,
+                const ChunkBuf& cb, hipStream_t stream, int share = 0)
+        : rg(ranges), n_ranges(n_ranges_), B(B_), N(N_), M(M_), gx((N_ + rows - 1) / rows) {
+        rgc = n_ranges > 0 ? with_row_chunks(rg, n_ranges, N, rows, cb, stream, chunk_grid, share) : rg;
+        row_blocks = n_ranges > 0 ? (long)n_ranges : (long)B * gx;
+        per_split = (long)B * N * partial * sizeof(float);
+        fit = (workspace && per_split > 0) ? (long)(bytes / per_split) : 0;
+        sp.n_splits = 1;
+        sp.workspace = static_cast<float*>(workspace);
+        sp.split_stride = (long)B * N * partial;
+        sp.xcd_grid_x = 0;
+        sp.xcd_blocks = 0;
+    }
+
+    // dense launches with room for 8 splits and enough columns for them may run on the XCD-aware 1-D grid (workgroup_coords) ...
+    bool xcd_eligible(bool allow_split) const { return n_ranges == 0 && allow_split && fit >= 8 && M >= 65536; }
+    // ... with the launcher's `nx` splits, when the grid fits: returns whether it was taken
+    bool take_xcd(int nx) {
+        if ((long)gx * B * nx >= (1L << 31)) return false;
+        sp.n_splits = nx;
+        sp.xcd_grid_x = gx;
+        sp.xcd_blocks = gx * B;
+        return true;
+    }
+    // byte offset in the workspace of what a launch places behind its split partials (pre-packed columns)
+    size_t packed_offset() const { return (((size_t)(sp.n_splits > 1 ? sp.n_splits : 0) * per_split) + 255) & ~(size_t)255; }
+
+    template <class MergeOp, class F>
+    void launch(F&& main, const typename MergeOp::Params& mprm, hipStream_t stream) const {
+        if (n_ranges > 0) launch_sparse<MergeOp>(main, mprm, stream);
+        else launch_dense<MergeOp>(main, mprm, stream);
+    }
+    // (launchers whose kernels exist in one mode only call these directly: the other mode is not instantiated)
+    template <class MergeOp, class F>
+    void launch_sparse(F&& main, const typename MergeOp::Params& mprm, hipStream_t stream) const {
+        main(std::true_type{}, dim3(chunk_grid, 1, sp.n_splits), rgc);
+        if (sp.n_splits > 1) hipLaunchKernelGGL((merge_kernel<MergeOp, true>), dim3(n_ranges, 1, 1), dim3(kBlock), 0, stream, mprm, rg, N, sp);
+    }
+    template <class MergeOp, class F>
+    void launch_dense(F&& main, const typename MergeOp::Params& mprm, hipStream_t stream) const {
+        constexpr int kMergeRows = kBlock * MergeOp::kRows;
+        main(std::false_type{}, sp.xcd_grid_x > 0 ? dim3((unsigned)((long)gx * B * sp.n_splits), 1, 1) : dim3(gx, B, sp.n_splits), rg);
+        if (sp.n_splits > 1)
+            hipLaunchKernelGGL((merge_kernel<MergeOp, false>), dim3((N + kMergeRows - 1) / kMergeRows, B, 1), dim3(kBlock), 0, stream, mprm, rg, N, sp);
+    }
+};
+
 template <class Op>
 static inline void launch_mapreduce(const typename Op::Params& prm, const Ranges& rg, int n_ranges, int B, int N,
                                     int M, void* workspace, size_t workspace_bytes, bool allow_split,
                                     hipStream_t stream, const ChunkBuf& cb = ChunkBuf()) {
-    const int rows_per_block = kBlock * Op::kRows;
-    unsigned chunk_grid = 0;
-    const Ranges rgc = n_ranges > 0 ? with_row_chunks(rg, n_ranges, N, rows_per_block, cb, stream, chunk_grid) : rg;
-    const long row_blocks = n_ranges > 0 ? (long)n_ranges : (long)B * ((N + rows_per_block - 1) / rows_per_block);
-    const long per_split = (long)B * N * Op::kPartial * sizeof(float);
-    const long fit = (workspace && per_split > 0) ? (long)(workspace_bytes / per_split) : 0;
-    SplitInfo sp;
-    sp.n_splits = (allow_split && fit >= 2) ? choose_splits(row_blocks, M, n_ranges, fit) : 1;
-    sp.workspace = static_cast<float*>(workspace);
-    sp.split_stride = (long)B * N * Op::kPartial;
-    sp.xcd_grid_x = 0;
-    sp.xcd_blocks = 0;
-    if (n_ranges > 0) {
-        dim3 grid(chunk_grid, 1, sp.n_splits);
-        hipLaunchKernelGGL((mapreduce_kernel<Op, true>), grid, dim3(kBlock), 0, stream, prm, rgc, N, M, sp);
-        if (sp.n_splits > 1)
-            hipLaunchKernelGGL((merge_kernel<Op, true>), dim3(n_ranges, 1, 1), dim3(kBlock), 0, stream, prm, rg, N, sp);
-    } else {
-        dim3 grid((N + rows_per_block - 1) / rows_per_block, B, sp.n_splits);
-        hipLaunchKernelGGL((mapreduce_kernel<Op, false>), grid, dim3(kBlock), 0, stream, prm, rg, N, M, sp);
-        if (sp.n_splits > 1)
-            hipLaunchKernelGGL((merge_kernel<Op, false>), dim3(grid.x, B, 1), dim3(kBlock), 0, stream, prm, rg, N, sp);
-    }
+    SplitLaunch sl(rg, n_ranges, B, N, M, kBlock * Op::kRows, Op::kPartial, workspace, workspace_bytes, cb, stream);
+    sl.sp.n_splits = (allow_split && sl.fit >= 2) ? choose_splits(sl.row_blocks, M, n_ranges, sl.fit) : 1;
+    sl.launch<Op>([&](auto sparse, dim3 grid, const Ranges& r) {
+        hipLaunchKernelGGL((mapreduce_kernel<Op, decltype(sparse)::value>), grid, dim3(kBlock), 0, stream, prm, r, N, M, sl.sp);
+    }, prm, stream);
 }
 
 }  // namespace glhip

@@ -1,11 +1,11 @@
 // glhip_softmin_x32.h — soft-min forward (p = 2, D <= 3), bf16x3 exponents on v_mfma_f32_32x32x16_bf16.
 //
-// Same arithmetic as glhip_softmin_xdl.h (every fp32 operand = 3 exact bf16 pieces, 8 products per coordinate),
-// different tiling, chosen from measurements on MI355X (tools/ubench/overlap.hip, profiles/r01_ubench_pipes.txt):
+// bf16 x 3 arithmetic (glhip_mfma_common.h: every fp32 operand = 3 exact bf16 pieces, 8 products per coordinate)
+// on a tiling chosen from measurements on MI355X (tools/ubench/overlap.hip, profiles/r01_ubench_pipes.txt):
 // beside exp2-bound VALU work a 16x16x32 MFMA still costs ~6 issue cycles per 256 exponents, a 32x32x16 MFMA
 // costs ~0 per 1024 — the matrix pipe time itself hides completely.  So:
 //   * one MFMA pair (K = 2 x 16) produces a 32 x 32 block of exponents;
-//   * the block is TRANSPOSED with respect to the 16x16 kernel: the MFMA "A" rows are 32 columns y_j (from LDS),
+//   * the block is TRANSPOSED with respect to a 16x16 tiling: the MFMA "A" rows are 32 columns y_j (from LDS),
 //     the MFMA "B" columns are 32 rows x_i (in registers).  In the result lane l owns row i = l % 32 and its 16
 //     registers are 16 different columns, so the row sum is 15 adds inside the lane + one add into ONE running
 //     register (not a 4- or 16-register tile), the running max is one value per lane, and the final merge of a
@@ -15,7 +15,7 @@
 //       block d < D : y side [y1,y2,y1,y3,y1,y2,y3,y2]   x side [a1,a1,a2,a1,a3,a2,a2,a3]
 //       block 3     : y side [H1,H2,H3, 1, 1, 1, 0, 0]   x side [ 1, 1, 1,n1,n2,n3, 0, 0]     n = -running max
 //     and C = 0 (an inline constant: no accumulator-input registers at all).
-// Lazy max, speculative tile pass, tile-end check, exact redo, column splits and the merge are as in the 16x16 kernel.
+// Lazy max, speculative tile pass, tile-end check and exact redo: glhip_mfma_common.h; column splits and the merge: glhip_mapreduce.h.
 #pragma once
 
 #include "glhip_klayout.h"

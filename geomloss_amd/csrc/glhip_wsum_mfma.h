@@ -9,9 +9,12 @@
 //   WS_GAUSS_FWDGRAD : product AND its row gradient in one pass — S0 is the product itself: out_i = S0,
 //                    dout_i/dx_i = -(1/blur^2) (xt_i S0 - S1).  Used by the autograd forward when x requires gradients, so that
 //                    the backward pass of a kernel norm is elementwise (fwd + bwd of the gaussian MMD: 3 + 2 reductions -> 3).
-// Exponents are <= 0 by construction, so there is no running max.  Same wave / LDS layout and the same
-// bf16 x 3 exponent MFMA as the forward soft-min (glhip_softmin_xdl.h): lane l holds D rows 4*(l/16)+r and
-// column l%16 of each 16-column group.
+// Exponents are <= 0 by construction, so there is no running max.  They come from the bf16 x 3 split of
+// glhip_mfma_common.h on v_mfma_f32_16x16x32_bf16, K layout (4 blocks of 8 slots):
+//   block d < D : A = [a1,a1,a2,a1,a3,a2,a2,a3] of a_id,  B = [y1,y2,y1,y3,y1,y2,y3,y2] of yt_jd
+//   block 3     : A = [1,1,1,0,0,0,0,0],                  B = [H1,H2,H3,0,0,0,0,0]      (H_j split the same way)
+// Lane l holds K-block l/16 of row / column l%16, so one 16-byte LDS record per (column, K-block) is the B operand
+// as is; in the result lane l holds D rows 4*(l/16)+r and column l%16 of each 16-column group.
 // q is staged as tileQ[c][G][j] = float4 over the 4 column groups of super-group G: the 4 lanes that share a
 // column read the same 16 bytes (broadcast), the 16 columns are contiguous (conflict-free).
 //
@@ -21,7 +24,7 @@
 // (GLHIP_FLAG_NO_MFMA) and are what laplacian / energy / p = 1 always use.
 #pragma once
 
-#include "glhip_softmin_xdl.h"
+#include "glhip_mfma_common.h"
 
 namespace glhip {
 
@@ -66,10 +69,10 @@ template <int MODE, int D, typename T, bool SPARSE, int RT = kMfmaRT, int NW = 4
 __global__ void __launch_bounds__(NW * 64)
 wsum_mfma_kernel(WsumParams<T> prm, Ranges rg, int N, int M, SplitInfo sp) {
     static_assert(RT * NW * 16 == kMfmaRowsPerBlock, "256 rows per workgroup");
-    constexpr int kMfmaRT = RT, kMfmaRowsPerWave = RT * 16, kBlock = NW * 64;      // (shadow the 4 x 4 constants of glhip_softmin_mfma.h)
+    constexpr int kMfmaRT = RT, kMfmaRowsPerWave = RT * 16, kBlock = NW * 64;      // (shadow the 4 x 4 constants of glhip_mfma_common.h)
     constexpr int NQ = WsumShape<MODE, D>::kNQ;
     constexpr int NA = WsumShape<MODE, D>::kNA;
-    __shared__ uint4 tileX[(kTileX / 16) * 64];          // bf16 x 3 B operands, as in softmin_fwd_xdl_kernel
+    __shared__ uint4 tileX[(kTileX / 16) * 64];          // bf16 x 3 B operands: [column group][lane = kblock*16 + j]
     __shared__ f32x4 tileQ[NQ * (kTileX / 64) * 16];
 
     const int tid = threadIdx.x;

@@ -63,11 +63,10 @@ extern "C" {
                                  instead of the per-workgroup-centred expansion. Slower, tighter. */
 #define GLHIP_FLAG_NO_MFMA 2  /* p=2 softmin / gaussian: form the exponents on the VALU instead of the matrix cores */
 #define GLHIP_FLAG_NO_SPLIT 4 /* never split the columns of a row over several workgroups (ignore the workspace) */
-#define GLHIP_FLAG_F32_MFMA 8 /* p=2 softmin forward: fp32 MFMA (v_mfma_f32_16x16x4_f32) instead of the bf16x3 split.  A/B only: compiled in
-                                 with `make AB=1`; the shipped library runs its default kernel (same results to rounding) */
+#define GLHIP_FLAG_F32_MFMA 8 /* accepted for compatibility (the fp32-MFMA tiling of the p=2 softmin forward served A/B runs only and is
+                                 gone): the forward runs its default kernel; big dense F16X2 forwards with D <= 3 stay on the bf16x3 kernel */
 #define GLHIP_FLAG_XDL16 16   /* gaussian product: bf16x3 on 16x16x32 MFMAs (the previous tiling) instead of 32x32x16 — the tiling of the
-                                 gradient kernels, see GLHIP_FLAG_GRAD_FAMILY.  p=2 softmin forward: that tiling with `make AB=1` only
-                                 (A/B; the shipped library runs its default kernel) */
+                                 gradient kernels, see GLHIP_FLAG_GRAD_FAMILY.  p=2 softmin forward: as GLHIP_FLAG_F32_MFMA */
 #define GLHIP_FLAG_GRAD_FAMILY GLHIP_FLAG_XDL16 /* kernel products: round like the product of glhip_kernel_conv_fwd_grad of the same
                                  kind — gaussian: the 16x16x32 tiling above; laplacian / energy: explicit differences with |.| = m rsq(m)
                                  (bit-identical to that product).  For the other two terms of a kernel norm whose gradient is on. */
