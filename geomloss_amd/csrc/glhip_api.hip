@@ -12,7 +12,18 @@ extern "C" {
 int glhip_version(void) { return GLHIP_VERSION; }
 
 size_t glhip_workspace_bytes(int B, int N, int M, int D, int n_ranges) {
-    if (B <= 0 || N <= 0 || M <= 0 || D < 1 || D > kXdMaxD) return 0;   // the generic-D kernels (D > 16) do not split
+    if (B <= 0 || N <= 0 || M <= 0 || D < 1 || D > kXkMaxD) return 0;   // the generic-D kernels do not split
+    if (D > kXdMaxD) {   // 17 <= D <= 4095 (glhip_softmin_xk.h): split partials of 2 floats per row — what launch_xk_l takes, nothing else
+        int nf = choose_splits(n_ranges > 0 ? n_ranges : (long)B * ((N + kXkRows - 1) / kXkRows), M, n_ranges, 1L << 30);
+        if (n_ranges == 0 && M >= 65536) {
+            const int nx = xcd_splits((long)B * ((N + kXkRows - 1) / kXkRows), M, kXkSlots, 32);
+            nf = nf > nx ? nf : nx;
+            nf = nf > 8 ? nf : 8;
+        }
+        size_t bytes = (size_t)(nf < 2 ? 0 : nf) * (size_t)B * (size_t)N * 2 * sizeof(float);
+        if (n_ranges > 0) bytes += chunk_table_bytes(n_ranges, N, 64);
+        return bytes;
+    }
     if (D > 3) {   // 4 <= D <= 16 (glhip_softmin_xd.h): split partials of 2 floats per row (+ packed columns on big dense launches)
         const int ns128 = choose_splits(n_ranges > 0 ? n_ranges : (long)B * ((N + 127) / 128), M, n_ranges, 1L << 30);
         int nf = ns128;
@@ -93,6 +104,21 @@ size_t glhip_workspace_bytes(int B, int N, int M, int D, int n_ranges) {
 
 const char* glhip_last_error(void) { return g_err; }
 
+// big dense D <= 3 launches that sort their clouds first (glhip_autosort.h): p = 1 — compact row blocks -> distances on the matrix
+// cores; p = 2 — only the column blocks that can change a float32 result (exact block pruning)
+static bool softmin_sorts(int B, int N, int M, int D, int p, int n_ranges, int flags) {
+    return (p == 1 || prune_applies(N, M)) && autosort_applies(B, N, M, D, n_ranges, flags);
+}
+
+int glhip_softmin_fwd_family(int B, long N, long M, int D, int p, int dtype, int flags, int n_ranges) {
+    if (B < 0 || N < 0 || M < 0 || N > 0x7fffffffL || M > 0x7fffffffL || D < 1 || n_ranges < 0 || (p != 1 && p != 2) ||
+        (dtype != GLHIP_F32 && dtype != GLHIP_BF16))
+        return GLHIP_EINVAL;
+    if (softmin_sorts(B, (int)N, (int)M, D, p, n_ranges, flags))   // the inner launch: slabs of kSortSlab sorted rows as row blocks
+        return softmin_fwd_family(1, N, M, D, p, flags | (p == 1 ? GLHIP_FLAG_MFMA_DIST : 0) | GLHIP_FLAG_NO_SORT, (int)((N + kSortSlab - 1) / kSortSlab));
+    return softmin_fwd_family(B, N, M, D, p, flags, n_ranges);
+}
+
 int glhip_softmin_fwd(const void* x, const void* y, const float* h, float* out, int B, int N, int M, int D,
                       float eps, int p, int in_dtype, const int32_t* ranges_i, const int32_t* slices_i,
                       const int32_t* redranges_j, int n_ranges, void* workspace, size_t workspace_bytes, int flags,
@@ -105,9 +131,7 @@ int glhip_softmin_fwd(const void* x, const void* y, const float* h, float* out, 
     if (p != 1 && p != 2) return fail(GLHIP_EUNSUPPORTED, "glhip_softmin_fwd: p must be 1 or 2 (got %d)", p);
     const Ranges rg{ranges_i, slices_i, redranges_j};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    // glhip_autosort.h: p = 1 — compact row blocks -> distances on the matrix cores; p = 2 — only the column blocks that can change a
-    // float32 result (exact block pruning)
-    if ((p == 1 || prune_applies(N, M)) && autosort_applies(B, N, M, D, n_ranges, flags)) {
+    if (softmin_sorts(B, N, M, D, p, n_ranges, flags)) {
         AutoSort a;
         const int C = (N + kSortSlab - 1) / kSortSlab;
         rc = autosort_prepare(a, x, y, N, M, D, in_dtype, workspace, workspace_bytes, glhip_workspace_bytes(1, N, M, D, C), st, p == 1);
@@ -142,7 +166,7 @@ int glhip_sinkhorn_step(const void* x, const void* y, const float* logw, const f
     if (p != 1 && p != 2) return fail(GLHIP_EUNSUPPORTED, "glhip_sinkhorn_step: p must be 1 or 2 (got %d)", p);
     const Ranges rg{ranges_i, slices_i, redranges_j};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if ((p == 1 || prune_applies(N, M)) && autosort_applies(B, N, M, D, n_ranges, flags)) {   // as glhip_softmin_fwd; the potentials travel with their clouds
+    if (softmin_sorts(B, N, M, D, p, n_ranges, flags)) {   // as glhip_softmin_fwd; the potentials travel with their clouds
         AutoSort a;
         const int C = (N + kSortSlab - 1) / kSortSlab;
         rc = autosort_prepare(a, x, y, N, M, D, in_dtype, workspace, workspace_bytes, glhip_workspace_bytes(1, N, M, D, C), st, p == 1);

@@ -4,6 +4,15 @@
 
 extern "C" {
 
+int glhip_kernel_conv_fwd_family(int kind, int B, long N, long M, int D, int dtype, int flags, int n_ranges) {
+    if (B < 0 || N < 0 || M < 0 || N > 0x7fffffffL || M > 0x7fffffffL || D < 1 || n_ranges < 0 || kind < GLHIP_GAUSSIAN || kind > GLHIP_ENERGY ||
+        (dtype != GLHIP_F32 && dtype != GLHIP_BF16))
+        return GLHIP_EINVAL;
+    if (kind != GLHIP_GAUSSIAN && autosort_applies(B, (int)N, (int)M, D, n_ranges, flags))   // the inner launch over slabs of sorted rows
+        return conv_fwd_family(kind, 1, D, flags | GLHIP_FLAG_MFMA_DIST | GLHIP_FLAG_NO_SORT, (int)((N + kSortSlab - 1) / kSortSlab));
+    return conv_fwd_family(kind, B, D, flags, n_ranges);
+}
+
 int glhip_kernel_conv_fwd(int kind, const void* x, const void* y, const float* v, float* out, int B, int N, int M,
                           int D, float blur, int in_dtype, const int32_t* ranges_i, const int32_t* slices_i,
                           const int32_t* redranges_j, int n_ranges, void* workspace, size_t workspace_bytes,

@@ -5,6 +5,10 @@
 // The (kJT x kDC) slab of y is staged in LDS and read back with broadcast ds_read_b128; each thread
 // keeps kJT partial squared distances in VGPRs.  Cost is ~2 VALU ops per (pair, dimension): this is
 // the slow path, the library is tuned for D <= 3.
+//
+// Gradients (BWD) in any dimension: a thread accumulates kGenericGradPass = 64 output coordinates in registers, so the
+// coordinates are swept in ceil(D / 64) passes; every pass walks all columns again and recomputes the squared distances and the
+// weights (D <= 64: one pass, as before).  A capability, not a fast path: ~(2 + 2 ceil(D / 64)) VALU ops per (pair, dimension).
 #pragma once
 
 #include "glhip_common.h"
@@ -13,7 +17,7 @@ namespace glhip {
 
 constexpr int kJT = 16;   // columns per generic tile
 constexpr int kDC = 16;   // feature dimensions per chunk
-constexpr int kGenericMaxGradD = 64;
+constexpr int kGenericGradPass = 64;   // output coordinates of a gradient row held in registers per pass
 
 enum GenericMode { GM_SOFTMIN_P2 = 0, GM_SOFTMIN_P1 = 1, GM_GAUSS = 2, GM_LAPLACE = 3, GM_ENERGY = 4 };
 
@@ -71,126 +75,132 @@ generic_kernel(GenericParams<T> p, Ranges rg, int N, int M, int D) {
         const T* xi = p.x + ((long)b * N + i) * D;
         float m = kNegBig, ssum = 0.f, accv = 0.f;
         float lse2 = 0.f;
-        float gacc[BWD ? kGenericMaxGradD : 1];
-        if (BWD) {
-#pragma unroll
-            for (int d = 0; d < kGenericMaxGradD; ++d) gacc[d] = 0.f;
-            if (SOFTMIN) lse2 = p.fwd[(long)b * N + i] / p.out_scale;
-        }
+        float gacc[BWD ? kGenericGradPass : 1];
+        if (BWD && SOFTMIN) lse2 = p.fwd[(long)b * N + i] / p.out_scale;
+        const int npass = BWD ? (D + kGenericGradPass - 1) / kGenericGradPass : 1;
 
-        for (int q = q_begin; q < q_end; ++q) {
-            const int js = SPARSE ? rg.redranges_j[2 * q] : 0;
-            const int je = SPARSE ? rg.redranges_j[2 * q + 1] : M;
-            for (int j0 = js; j0 < je; j0 += kJT) {
-                float d2[kJT];
+        for (int pass = 0; pass < npass; ++pass) {
+            const int dbase = pass * kGenericGradPass;      // gradients: this pass owns output coordinates [dbase, dbase + 64)
+            if (BWD) {
 #pragma unroll
-                for (int jj = 0; jj < kJT; ++jj) d2[jj] = 0.f;
-                float sj[kJT];
+                for (int d = 0; d < kGenericGradPass; ++d) gacc[d] = 0.f;
+                ssum = 0.f;
+            }
 
-                for (int ch = 0; ch < nchunks; ++ch) {
-                    const int d0 = ch * kDC;
-                    __syncthreads();
-                    {
-                        const int jj = tid / kDC, dd = tid % kDC;
-                        const int j = j0 + jj, d = d0 + dd;
-                        ytile[jj][dd] = (j < je && d < D) ? to_f32<T>(p.y[((long)b * M + j) * D + d]) : 0.f;
-                        if (ch == 0 && tid < kJT) {
-                            const int jt = j0 + tid;
-                            float sv = SOFTMIN ? kNegBig : 0.f;
-                            if (jt < je) sv = SOFTMIN ? p.s[(long)b * M + jt] * kLog2e : p.s[(long)b * M + jt];
-                            stile[tid] = sv;
-                        }
-                    }
-                    __syncthreads();
-                    float xd[kDC];
+            for (int q = q_begin; q < q_end; ++q) {
+                const int js = SPARSE ? rg.redranges_j[2 * q] : 0;
+                const int je = SPARSE ? rg.redranges_j[2 * q + 1] : M;
+                for (int j0 = js; j0 < je; j0 += kJT) {
+                    float d2[kJT];
 #pragma unroll
-                    for (int dd = 0; dd < kDC; ++dd) xd[dd] = (d0 + dd < D) ? to_f32<T>(xi[d0 + dd]) : 0.f;
-#pragma unroll
-                    for (int jj = 0; jj < kJT; ++jj) {
-#pragma unroll
-                        for (int dd = 0; dd < kDC; ++dd) {
-                            const float df = xd[dd] - ytile[jj][dd];
-                            d2[jj] = __builtin_fmaf(df, df, d2[jj]);
-                        }
-                    }
-                    if (ch == 0) {
-#pragma unroll
-                        for (int jj = 0; jj < kJT; ++jj) sj[jj] = stile[jj];
-                    }
-                }
+                    for (int jj = 0; jj < kJT; ++jj) d2[jj] = 0.f;
+                    float sj[kJT];
 
-                if (!BWD) {
-                    if (SOFTMIN) {
-                        float u[kJT];
-#pragma unroll
-                        for (int jj = 0; jj < kJT; ++jj) u[jj] = generic_value<MODE>(d2[jj], sj[jj], p.dscale, p.clamp2);
-                        float cm = u[0];
-#pragma unroll
-                        for (int jj = 1; jj < kJT; ++jj) cm = fmaxf(cm, u[jj]);
-                        const float mn = fmaxf(m, cm);
-                        ssum *= fast_exp2(m - mn);
-                        m = mn;
-#pragma unroll
-                        for (int jj = 0; jj < kJT; ++jj) ssum += fast_exp2(u[jj] - mn);
-                    } else {
-#pragma unroll
-                        for (int jj = 0; jj < kJT; ++jj)
-                            accv = __builtin_fmaf(generic_value<MODE>(d2[jj], 0.f, p.dscale, p.clamp2), sj[jj], accv);
-                    }
-                } else {
-                    // direction weights w_j, then a second sweep over the feature chunks
-                    float w[kJT];
-#pragma unroll
-                    for (int jj = 0; jj < kJT; ++jj) {
-                        const float rs = (d2[jj] > p.clamp2) ? fast_rsq(d2[jj]) : 0.f;
-                        if (SOFTMIN) {
-                            const float pij = fast_exp2(generic_value<MODE>(d2[jj], sj[jj], p.dscale, p.clamp2) - lse2);
-                            ssum += pij;
-                            w[jj] = (MODE == GM_SOFTMIN_P2) ? pij : pij * rs;
-                        } else if (MODE == GM_GAUSS) {
-                            w[jj] = sj[jj] * generic_value<MODE>(d2[jj], 0.f, p.dscale, p.clamp2);
-                        } else if (MODE == GM_LAPLACE) {
-                            w[jj] = sj[jj] * rs * generic_value<MODE>(d2[jj], 0.f, p.dscale, p.clamp2);
-                        } else {
-                            w[jj] = sj[jj] * rs;
-                        }
-                    }
-#pragma unroll
-                    for (int ch = 0; ch < kGenericMaxGradD / kDC; ++ch) {
+                    for (int ch = 0; ch < nchunks; ++ch) {
                         const int d0 = ch * kDC;
-                        if (d0 < D) {
-                            if (nchunks > 1) {   // the slab in LDS is the last chunk: restage
-                                __syncthreads();
-                                const int jj = tid / kDC, dd = tid % kDC;
-                                const int j = j0 + jj, d = d0 + dd;
-                                ytile[jj][dd] = (j < je && d < D) ? to_f32<T>(p.y[((long)b * M + j) * D + d]) : 0.f;
-                                __syncthreads();
+                        __syncthreads();
+                        {
+                            const int jj = tid / kDC, dd = tid % kDC;
+                            const int j = j0 + jj, d = d0 + dd;
+                            ytile[jj][dd] = (j < je && d < D) ? to_f32<T>(p.y[((long)b * M + j) * D + d]) : 0.f;
+                            if (ch == 0 && tid < kJT) {
+                                const int jt = j0 + tid;
+                                float sv = SOFTMIN ? kNegBig : 0.f;
+                                if (jt < je) sv = SOFTMIN ? p.s[(long)b * M + jt] * kLog2e : p.s[(long)b * M + jt];
+                                stile[tid] = sv;
                             }
+                        }
+                        __syncthreads();
+                        float xd[kDC];
+#pragma unroll
+                        for (int dd = 0; dd < kDC; ++dd) xd[dd] = (d0 + dd < D) ? to_f32<T>(xi[d0 + dd]) : 0.f;
+#pragma unroll
+                        for (int jj = 0; jj < kJT; ++jj) {
 #pragma unroll
                             for (int dd = 0; dd < kDC; ++dd) {
-                                const float xv = (d0 + dd < D) ? to_f32<T>(xi[d0 + dd]) : 0.f;
-                                float a = gacc[d0 + dd];
+                                const float df = xd[dd] - ytile[jj][dd];
+                                d2[jj] = __builtin_fmaf(df, df, d2[jj]);
+                            }
+                        }
+                        if (ch == 0) {
 #pragma unroll
-                                for (int jj = 0; jj < kJT; ++jj) a = __builtin_fmaf(w[jj], xv - ytile[jj][dd], a);
-                                gacc[d0 + dd] = a;
+                            for (int jj = 0; jj < kJT; ++jj) sj[jj] = stile[jj];
+                        }
+                    }
+
+                    if (!BWD) {
+                        if (SOFTMIN) {
+                            float u[kJT];
+#pragma unroll
+                            for (int jj = 0; jj < kJT; ++jj) u[jj] = generic_value<MODE>(d2[jj], sj[jj], p.dscale, p.clamp2);
+                            float cm = u[0];
+#pragma unroll
+                            for (int jj = 1; jj < kJT; ++jj) cm = fmaxf(cm, u[jj]);
+                            const float mn = fmaxf(m, cm);
+                            ssum *= fast_exp2(m - mn);
+                            m = mn;
+#pragma unroll
+                            for (int jj = 0; jj < kJT; ++jj) ssum += fast_exp2(u[jj] - mn);
+                        } else {
+#pragma unroll
+                            for (int jj = 0; jj < kJT; ++jj)
+                                accv = __builtin_fmaf(generic_value<MODE>(d2[jj], 0.f, p.dscale, p.clamp2), sj[jj], accv);
+                        }
+                    } else {
+                        // direction weights w_j, then a second sweep over the feature chunks
+                        float w[kJT];
+#pragma unroll
+                        for (int jj = 0; jj < kJT; ++jj) {
+                            const float rs = (d2[jj] > p.clamp2) ? fast_rsq(d2[jj]) : 0.f;
+                            if (SOFTMIN) {
+                                const float pij = fast_exp2(generic_value<MODE>(d2[jj], sj[jj], p.dscale, p.clamp2) - lse2);
+                                ssum += pij;
+                                w[jj] = (MODE == GM_SOFTMIN_P2) ? pij : pij * rs;
+                            } else if (MODE == GM_GAUSS) {
+                                w[jj] = sj[jj] * generic_value<MODE>(d2[jj], 0.f, p.dscale, p.clamp2);
+                            } else if (MODE == GM_LAPLACE) {
+                                w[jj] = sj[jj] * rs * generic_value<MODE>(d2[jj], 0.f, p.dscale, p.clamp2);
+                            } else {
+                                w[jj] = sj[jj] * rs;
+                            }
+                        }
+#pragma unroll
+                        for (int ch = 0; ch < kGenericGradPass / kDC; ++ch) {
+                            const int d0 = dbase + ch * kDC;
+                            if (d0 < D) {
+                                if (nchunks > 1) {   // the slab in LDS is the last chunk: restage
+                                    __syncthreads();
+                                    const int jj = tid / kDC, dd = tid % kDC;
+                                    const int j = j0 + jj, d = d0 + dd;
+                                    ytile[jj][dd] = (j < je && d < D) ? to_f32<T>(p.y[((long)b * M + j) * D + d]) : 0.f;
+                                    __syncthreads();
+                                }
+#pragma unroll
+                                for (int dd = 0; dd < kDC; ++dd) {
+                                    const float xv = (d0 + dd < D) ? to_f32<T>(xi[d0 + dd]) : 0.f;
+                                    float a = gacc[ch * kDC + dd];
+#pragma unroll
+                                    for (int jj = 0; jj < kJT; ++jj) a = __builtin_fmaf(w[jj], xv - ytile[jj][dd], a);
+                                    gacc[ch * kDC + dd] = a;
+                                }
                             }
                         }
                     }
                 }
             }
-        }
 
-        const int irow = row0 + tid;
-        if (irow < row_end) {
-            if (!BWD) {
-                p.out[(long)b * N + irow] = SOFTMIN ? p.out_scale * (m + fast_log2(ssum)) : accv;
-            } else {
-                float f = p.g[(long)b * N + irow];
-                if (SOFTMIN) f *= (ssum > 0.f) ? 1.0f / ssum : 0.f;
-                else f *= p.gscale;
+            const int irow = row0 + tid;
+            if (irow < row_end) {
+                if (!BWD) {
+                    p.out[(long)b * N + irow] = SOFTMIN ? p.out_scale * (m + fast_log2(ssum)) : accv;
+                } else {
+                    float f = p.g[(long)b * N + irow];
+                    if (SOFTMIN) f *= (ssum > 0.f) ? 1.0f / ssum : 0.f;
+                    else f *= p.gscale;
 #pragma unroll
-                for (int d = 0; d < kGenericMaxGradD; ++d)
-                    if (d < D) p.gx[((long)b * N + irow) * D + d] = f * gacc[d];
+                    for (int d = 0; d < kGenericGradPass; ++d)
+                        if (dbase + d < D) p.gx[((long)b * N + irow) * D + dbase + d] = f * gacc[d];
+                }
             }
         }
     }

@@ -100,6 +100,15 @@ __device__ __forceinline__ uint32_t xd_slot(int slot, const uint32_t (&sc)[3], c
     return cp[d][piece];
 }
 
+// Which piece sits in K slot t of a coordinate item, as xd_slot / xd_record_of lay them out (for kernels that build their records from
+// run-time coordinates, glhip_softmin_xk.h): bf16 x 3, t = 0..5: [a1,a1,a2,a1,a3,a2] | [y1,y2,y1,y3,y1,y2]; f16 x 2, t = 0..2:
+// [a_hi,a_hi,a_lo] | [y_hi,y_lo,y_hi]
+template <bool XSIDE, int L>
+__device__ __forceinline__ constexpr int xd_piece_at(int t) {
+    if (L == XL_F16X2) return XSIDE ? (t == 2 ? 1 : 0) : (t == 1 ? 1 : 0);
+    return XSIDE ? (t == 2 ? 1 : (t == 4 ? 2 : (t == 5 ? 1 : 0))) : (t == 1 ? 1 : (t == 3 ? 2 : (t == 5 ? 1 : 0)));
+}
+
 // The same from the float values themselves, splitting what the record needs when it needs it (a record touches the scalar and
 // at most three coordinates): for the row pass of the kernels, where 3 (D + 1) live piece registers next to RT x NM finished
 // operands pushed D = 16 over 128 VGPRs.

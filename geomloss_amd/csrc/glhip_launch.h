@@ -17,6 +17,7 @@
 #include "glhip_dist_x32.h"
 #include "glhip_dist_grad_x32.h"
 #include "glhip_softmin_xd.h"
+#include "glhip_softmin_xk.h"
 #include "glhip_wsum_t32.h"
 #include "glhip_dist_xd.h"
 
@@ -406,6 +407,42 @@ void launch_xd(const SoftminParams<T>& prm, const typename MergeOp::Params& mprm
     else launch_xd_l<MODE, D, T, MergeOp, XL_BF16X3>(prm, mprm, rg, n_ranges, B, N, M, sc, st);
 }
 
+// ---- 17 <= D <= 4095 on the matrix cores (glhip_softmin_xk.h): the same two operators with D as a run-time argument.  Column splits,
+// the XCD-aware grid of big dense launches, row chunks of block-sparse launches and the merge kernels as above (the merge operators
+// do not look at the coordinates: they are instantiated for D = 1); tiles are staged on the fly, there is no pre-packed copy, so
+// the workspace holds split partials only and a launch without one runs unsplit.
+constexpr long kXkSlots = 256 * 2;    // resident 8-wave workgroups (78.75 KiB of LDS, <= 128 VGPRs)
+
+template <int MODE, typename T, class MergeOp, int L>
+void launch_xk_l(const SoftminParams<T>& prm, const typename MergeOp::Params& mprm, const Ranges& rg, int n_ranges, int B, int N, int M, int D,
+                 const Scratch& sc, hipStream_t st) {
+    constexpr int kPart = MODE == XD_SOFTMIN ? 2 : 1;
+    static_assert(MergeOp::kPartial == kPart, "partial formats differ");
+    SplitLaunch sl(rg, n_ranges, B, N, M, kXkRows, kPart, sc.ws, sc.bytes, sc.cb, st);
+    sl.sp.n_splits = (sc.allow_split && sl.fit >= 2) ? choose_splits(sl.row_blocks, M, n_ranges, sl.fit) : 1;
+    sl.sp.gather = (n_ranges > 0 && N / n_ranges < 128) ? 1 : 0;   // small clusters: gathered tiles, as in launch_softmin_mfma_nw
+    if (sl.xcd_eligible(sc.allow_split)) sl.take_xcd(xcd_splits(sl.row_blocks, M, kXkSlots, sl.fit));   // one column split per XCD at a time
+    sl.launch<MergeOp>([&](auto sparse, dim3 grid, const Ranges& r) {
+        hipLaunchKernelGGL((xk_fwd_kernel<MODE, T, decltype(sparse)::value, L>), grid, dim3(kXkThreads), 0, st, prm, r, N, M, D, sl.sp);
+    }, mprm, st);
+}
+
+// ... in the K layout the call asks for
+template <int MODE, typename T, class MergeOp>
+void launch_xk(const SoftminParams<T>& prm, const typename MergeOp::Params& mprm, const Ranges& rg, int n_ranges, int B, int N, int M, int D,
+               const Scratch& sc, hipStream_t st) {
+    if (sc.h2) launch_xk_l<MODE, T, MergeOp, XL_F16X2>(prm, mprm, rg, n_ranges, B, N, M, D, sc, st);
+    else launch_xk_l<MODE, T, MergeOp, XL_BF16X3>(prm, mprm, rg, n_ranges, B, N, M, D, sc, st);
+}
+
+// Which matrix-core forward family serves a p = 2 soft-min / half-step / gaussian product in dimension D > 3 under `flags`
+// (GLHIP_FLAG_NO_MFMA / _DIRECT: none — the generic kernel)
+inline int highd_p2_family(int D, int flags) {
+    if (flags & (GLHIP_FLAG_NO_MFMA | GLHIP_FLAG_DIRECT)) return GLHIP_FAMILY_GENERIC;
+    if (D <= kXdMaxD) return GLHIP_FAMILY_XD;
+    return D <= kXkMaxD ? GLHIP_FAMILY_XK : GLHIP_FAMILY_GENERIC;
+}
+
 // distance reductions for 4 <= D <= 16, dense launches (glhip_dist_xd.h): soft-min p = 1 / fused half-step, laplacian and energy products
 // 256-row workgroups of the distance kernels on a few thousand points are a handful (N = 1000: 4 per problem): launches with fewer than
 // 512 workgroups split their columns down to 128 per split, up to 32 splits and what the workspace holds
@@ -489,6 +526,34 @@ void launch_gauss_grad_t32(const ConvParams<T>& prm, float blur, const Ranges& r
 
 inline bool use_mfma_dist(int flags, int n_ranges, int B, int D) {
     return (flags & GLHIP_FLAG_MFMA_DIST) != 0 && n_ranges > 0 && B == 1 && D <= 3;
+}
+
+// The kernel family of a soft-min forward / fused half-step launch (GLHIP_FAMILY_*, include/glhip.h): THE predicate of
+// softmin_typed<false> below, and what glhip_softmin_fwd_family reports.  Host arithmetic only.
+inline int softmin_fwd_family(int B, long N, long M, int D, int p, int flags, int n_ranges) {
+    if (D <= 3) {
+        if (p == 1 && use_mfma_dist(flags, n_ranges, B, D)) return GLHIP_FAMILY_DIST;
+        const bool direct = (flags & GLHIP_FLAG_DIRECT) != 0, mfma = (flags & GLHIP_FLAG_NO_MFMA) == 0;
+        // GLHIP_FLAG_F16X2, big dense launches: the kernel of glhip_softmin_xd.h instantiated for D <= 3 (see softmin_typed)
+        const bool ab_flag = (flags & (GLHIP_FLAG_F32_MFMA | GLHIP_FLAG_XDL16)) != 0;
+        if (p == 2 && (flags & GLHIP_FLAG_F16X2) && !direct && mfma && !ab_flag && n_ranges == 0 && M >= 65536 && (double)B * N * M >= 5e8)
+            return GLHIP_FAMILY_XD;
+        return (p == 2 && !direct && mfma) ? GLHIP_FAMILY_X32 : GLHIP_FAMILY_VALU;
+    }
+    if (p == 1) return (D <= kXdMaxD && n_ranges == 0 && !(flags & (GLHIP_FLAG_NO_MFMA | GLHIP_FLAG_DIRECT))) ? GLHIP_FAMILY_DIST : GLHIP_FAMILY_GENERIC;
+    return highd_p2_family(D, flags);
+}
+
+// ... and of a kernel product (glhip_kernel_conv_fwd): THE predicate of conv_typed<false> below, reported by glhip_kernel_conv_fwd_family.
+// GLHIP_FAMILY_X32 stands for the matrix-core gaussian product of D <= 3 (glhip_wsum_x32.h / glhip_wsum_mfma.h).
+inline int conv_fwd_family(int kind, int B, int D, int flags, int n_ranges) {
+    if (D <= 3) {
+        if (kind == GLHIP_GAUSSIAN) return (flags & GLHIP_FLAG_NO_MFMA) ? GLHIP_FAMILY_VALU : GLHIP_FAMILY_X32;
+        return use_mfma_dist(flags, n_ranges, B, D) ? GLHIP_FAMILY_DIST : GLHIP_FAMILY_VALU;
+    }
+    if (kind != GLHIP_GAUSSIAN)      // laplacian / energy: distances on the matrix cores, dense launches of D <= 16
+        return (D <= kXdMaxD && n_ranges == 0 && !(flags & GLHIP_FLAG_NO_MFMA)) ? GLHIP_FAMILY_DIST : GLHIP_FAMILY_GENERIC;
+    return highd_p2_family(D, flags & ~GLHIP_FLAG_DIRECT);      // (_DIRECT means nothing to a kernel product)
 }
 
 template <int D, bool BWD, typename T>
@@ -723,13 +788,14 @@ int softmin_typed(const void* x, const void* y, const float* h, float* out, cons
                   const Scratch& sc, int flags, hipStream_t st, const StepArgs& step = StepArgs()) {
     const float s2 = kLog2e / eps;
     const float out_scale = -eps * kLn2;
+    const int fam = BWD ? -1 : softmin_fwd_family(B, N, M, D, p, flags, n_ranges);      // forward launches: the family decides
     if (D <= 3) {
         const bool direct = (flags & GLHIP_FLAG_DIRECT) != 0;
-        const bool mfma = (flags & GLHIP_FLAG_NO_MFMA) == 0;
+        const bool mfma = BWD ? (flags & GLHIP_FLAG_NO_MFMA) == 0 : fam == GLHIP_FAMILY_X32;
         SoftminParams<T> prm = make_softmin_params<T>(x, y, h, out, eps, p, step.pot, step.prev, step.alpha, step.beta);
         prm.fwd = fwd; prm.g = g; prm.gx = gx; prm.shift2 = step.shift2;
         if constexpr (!BWD) {
-            if (p == 1 && use_mfma_dist(flags, n_ranges, B, D)) {
+            if (fam == GLHIP_FAMILY_DIST) {
 #define GL_D(DD) launch_dist<DM_SOFTMIN_P1, DD, T, SoftminFwdOp<DD, 1, true, 1, T>>(dist_params(prm), prm, rg, n_ranges, N, M, sc, st)
                 GLHIP_D3_DISPATCH(D, GL_D)
 #undef GL_D
@@ -745,8 +811,7 @@ int softmin_typed(const void* x, const void* y, const float* h, float* out, cons
             // (mid-size launches, 16384 <= M < 65536, through this kernel with pre-packed columns and a free split count: 0.164 -> 0.191 ms
             // at N = M = 4e4, 0.242 -> 0.250 at 5e4, round 6: they stay on the x32 kernel)
             // GLHIP_FLAG_F32_MFMA / GLHIP_FLAG_XDL16 keep these launches on the x32 kernel too.
-            const bool ab_flag = (flags & (GLHIP_FLAG_F32_MFMA | GLHIP_FLAG_XDL16)) != 0;
-            if (p == 2 && sc.h2 && !direct && mfma && !ab_flag && n_ranges == 0 && M >= 65536 && (double)B * N * M >= 5e8) {
+            if (fam == GLHIP_FAMILY_XD) {
 #define GL_D(DD) launch_xd_l<XD_SOFTMIN, DD, T, SoftminFwdOp<DD, 2, false, 1, T>, XL_F16X2>(prm, prm, rg, n_ranges, B, N, M, sc, st)
                 GLHIP_D3_DISPATCH(D, GL_D)
 #undef GL_D
@@ -758,7 +823,7 @@ int softmin_typed(const void* x, const void* y, const float* h, float* out, cons
 #undef GL_D
     } else {
         if constexpr (!BWD) {
-            if (p == 1 && D <= kXdMaxD && n_ranges == 0 && !(flags & (GLHIP_FLAG_NO_MFMA | GLHIP_FLAG_DIRECT))) {   // distances on the matrix cores
+            if (fam == GLHIP_FAMILY_DIST) {   // p = 1, D <= 16, dense: distances on the matrix cores
                 const SoftminParams<T> mprm = make_softmin_params<T>(x, y, h, out, eps, 1, step.pot, step.prev, step.alpha, step.beta);
                 const DistParams<T> dp = dist_params(mprm);
 #define GL_XD(DD) launch_dist_xd<DM_SOFTMIN_P1, DD, T, SoftminFwdOp<DD, 1, true, 1, T>>(dp, mprm, B, N, M, sc, st)
@@ -766,11 +831,16 @@ int softmin_typed(const void* x, const void* y, const float* h, float* out, cons
 #undef GL_XD
                 return GLHIP_OK;
             }
-            if (p == 2 && D <= kXdMaxD && !(flags & (GLHIP_FLAG_NO_MFMA | GLHIP_FLAG_DIRECT))) {   // 4 <= D <= 16: matrix cores
+            if (fam == GLHIP_FAMILY_XD) {   // p = 2, 4 <= D <= 16: matrix cores
                 SoftminParams<T> prm = make_softmin_params<T>(x, y, h, out, eps, 2, step.pot, step.prev, step.alpha, step.beta);
 #define GL_XD(DD) launch_xd<XD_SOFTMIN, DD, T, SoftminFwdOp<DD, 2, false, 1, T>>(prm, prm, rg, n_ranges, B, N, M, sc, st)
                 GLHIP_XD_DISPATCH(D, GL_XD)
 #undef GL_XD
+                return GLHIP_OK;
+            }
+            if (fam == GLHIP_FAMILY_XK) {   // p = 2, 17 <= D <= 4095: matrix cores, K-chunked (glhip_softmin_xk.h)
+                SoftminParams<T> prm = make_softmin_params<T>(x, y, h, out, eps, 2, step.pot, step.prev, step.alpha, step.beta);
+                launch_xk<XD_SOFTMIN, T, SoftminFwdOp<1, 2, false, 1, T>>(prm, prm, rg, n_ranges, B, N, M, D, sc, st);
                 return GLHIP_OK;
             }
         } else {
@@ -794,11 +864,8 @@ int softmin_typed(const void* x, const void* y, const float* h, float* out, cons
             }
         }
         if (step.pot || step.prev || step.alpha != 1.f)
-            return fail(GLHIP_EUNSUPPORTED, "glhip_sinkhorn_step: no fused kernel for D=%d, p=%d, flags=%d (D <= 16, p = 2 on the matrix "
-                                            "cores only): use glhip_softmin_fwd", D, p, flags);
-        if (BWD && D > kGenericMaxGradD)
-            return fail(GLHIP_EUNSUPPORTED, "softmin_bwd_x: D=%d > %d is not supported by the generic gradient kernel",
-                        D, kGenericMaxGradD);
+            return fail(GLHIP_EUNSUPPORTED, "glhip_sinkhorn_step: no fused kernel for D=%d, p=%d, flags=%d (D > 3: the matrix-core kernels only — "
+                                            "p = 2 up to D = 4095, dense p = 1 up to D = 16): use glhip_softmin_fwd", D, p, flags);
         GenericParams<T> prm;
         prm.x = static_cast<const T*>(x);
         prm.y = static_cast<const T*>(y);
@@ -860,6 +927,7 @@ template <bool BWD, typename T>
 int conv_typed(int kind, const void* x, const void* y, const float* v, float* out, const float* g, float* gx,
                int B, int N, int M, int D, float blur, const Ranges& rg, int n_ranges, const Scratch& sc,
                int flags, hipStream_t st) {
+    const int kfam = BWD ? -1 : conv_fwd_family(kind, B, D, flags, n_ranges);      // products: the family decides
     if (D <= 3) {
         ConvParams<T> prm;
         prm.x = static_cast<const T*>(x);
@@ -872,7 +940,7 @@ int conv_typed(int kind, const void* x, const void* y, const float* v, float* ou
             prm.t = std::sqrt(0.5f * kLog2e) / blur;
             prm.gscale = -1.0f / (prm.t * blur * blur);
             prm.clamp2 = 0.f;
-            if ((flags & GLHIP_FLAG_NO_MFMA) == 0) {
+            if (BWD ? (flags & GLHIP_FLAG_NO_MFMA) == 0 : kfam == GLHIP_FAMILY_X32) {
                 const bool x32 = (flags & GLHIP_FLAG_XDL16) == 0;
 #define GL_D(DD) launch_gauss_mfma<DD, BWD, T>(prm, blur, rg, n_ranges, B, N, M, sc, x32, st)
                 GLHIP_D3_DISPATCH(D, GL_D)
@@ -885,7 +953,7 @@ int conv_typed(int kind, const void* x, const void* y, const float* v, float* ou
             prm.gscale = -1.0f / blur;
             prm.clamp2 = 1e-8f * kLog2e * kLog2e;   // the reference clamps |x/blur - y/blur|^2
             if constexpr (!BWD) {
-                if (use_mfma_dist(flags, n_ranges, B, D)) {      // GRAD_FAMILY: |.| = m rsq(m), as the product of glhip_dist_grad_x32.h
+                if (kfam == GLHIP_FAMILY_DIST) {      // GRAD_FAMILY: |.| = m rsq(m), as the product of glhip_dist_grad_x32.h
                     const DistParams<T> dp = dist_params(prm);
                     const bool fam = (flags & GLHIP_FLAG_GRAD_FAMILY) != 0;
 #define GL_DIST(DD) \
@@ -911,7 +979,7 @@ int conv_typed(int kind, const void* x, const void* y, const float* v, float* ou
             prm.gscale = -1.0f;
             prm.clamp2 = 1e-8f;
             if constexpr (!BWD) {
-                if (use_mfma_dist(flags, n_ranges, B, D)) {
+                if (kfam == GLHIP_FAMILY_DIST) {
                     const DistParams<T> dp = dist_params(prm);
                     const bool fam = (flags & GLHIP_FLAG_GRAD_FAMILY) != 0;
 #define GL_DIST(DD) \
@@ -935,7 +1003,7 @@ int conv_typed(int kind, const void* x, const void* y, const float* v, float* ou
         }
     } else {
         if constexpr (!BWD) {
-            if (kind != GLHIP_GAUSSIAN && D <= kXdMaxD && n_ranges == 0 && !(flags & GLHIP_FLAG_NO_MFMA)) {   // laplacian / energy: distances on the matrix cores
+            if (kind != GLHIP_GAUSSIAN && kfam == GLHIP_FAMILY_DIST) {   // laplacian / energy, dense, D <= 16: distances on the matrix cores
                 const bool lap = kind == GLHIP_LAPLACIAN;
                 const float t = lap ? kLog2e / blur : 1.0f;
                 ConvParams<T> mprm;
@@ -949,7 +1017,16 @@ int conv_typed(int kind, const void* x, const void* y, const float* v, float* ou
 #undef GL_XD
                 return GLHIP_OK;
             }
-            if (kind == GLHIP_GAUSSIAN && D <= kXdMaxD && !(flags & GLHIP_FLAG_NO_MFMA)) {   // 4 <= D <= 16: matrix cores
+            const int gfam = kind == GLHIP_GAUSSIAN ? kfam : GLHIP_FAMILY_GENERIC;
+            if (gfam == GLHIP_FAMILY_XK) {   // 17 <= D <= 4095: matrix cores, K-chunked (glhip_softmin_xk.h); exponent and operands as below
+                const SoftminParams<T> prm = make_softmin_params<T>(x, y, v, out, blur * blur, 2, nullptr, nullptr, 1.f, 0.f);
+                ConvParams<T> mprm;
+                mprm.x = prm.x; mprm.y = prm.y; mprm.v = v; mprm.out = out; mprm.g = nullptr; mprm.gx = nullptr;
+                mprm.t = 1.f; mprm.gscale = 0.f; mprm.clamp2 = 0.f;
+                launch_xk<XD_GAUSS, T, ConvOp<GLHIP_GAUSSIAN, 1, 1, T, 0>>(prm, mprm, rg, n_ranges, B, N, M, D, sc, st);
+                return GLHIP_OK;
+            }
+            if (gfam == GLHIP_FAMILY_XD) {   // 4 <= D <= 16: matrix cores
                 // the gaussian exponent -|x-y|^2 / (2 blur^2) is the soft-min's with eps = blur^2 and h = 0; `h` carries v
                 const SoftminParams<T> prm = make_softmin_params<T>(x, y, v, out, blur * blur, 2, nullptr, nullptr, 1.f, 0.f);
                 ConvParams<T> mprm;
@@ -987,9 +1064,6 @@ int conv_typed(int kind, const void* x, const void* y, const float* v, float* ou
                 return GLHIP_OK;
             }
         }
-        if (BWD && D > kGenericMaxGradD)
-            return fail(GLHIP_EUNSUPPORTED, "kernel_conv_bwd_x: D=%d > %d is not supported by the generic gradient kernel",
-                        D, kGenericMaxGradD);
         GenericParams<T> prm;
         prm.x = static_cast<const T*>(x);
         prm.y = static_cast<const T*>(y);

@@ -25,7 +25,12 @@ FLAG_DIRECT, FLAG_NO_MFMA, FLAG_NO_SPLIT, FLAG_F32_MFMA, FLAG_XDL16, FLAG_PREPAC
 FLAG_F16X2 = 256                # exponents from two f16 pieces per coordinate; the caller vouches for the range (glhip.h)
 FLAG_NO_SORT = 512              # big dense distance reductions: do not voxel-sort the clouds inside the library (glhip.h)
 FLAG_GRAD_FAMILY = FLAG_XDL16   # kernel products rounded like the product-and-gradient kernel of the same kind (glhip.h)
-XD_MAX_DIM = 16                 # p = 2 soft-min forward / half-step and gaussian product run on the matrix cores up to this dimension
+XD_MAX_DIM = 16                 # the fused four-softmin iteration / annealing / extrapolation, the one-pass value + gradient and the matrix-core
+                                # gradients stop at this dimension (glhip_softmin_xd.h, glhip_wsum_t32.h)
+MFMA_FWD_MAX_DIM = 4095         # p = 2 soft-min forward / half-step and gaussian product run on the matrix cores up to this dimension
+                                # (17 ... 4095: the K-chunked kernel of glhip_softmin_xk.h; kept in step with the library by tests/test_anyd_kernels_gpu.py)
+# kernel families reported by softmin_fwd_family (GLHIP_FAMILY_* of glhip.h)
+FAMILY_VALU, FAMILY_X32, FAMILY_XD, FAMILY_XK, FAMILY_DIST, FAMILY_GENERIC = 0, 1, 2, 3, 4, 5
 
 # every symbol include/glhip.h declares, with its ctypes signature
 _c_int, _c_float, _vp, _c_size = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
@@ -36,6 +41,8 @@ SIGNATURES = {
     "glhip_version": (_c_int, []),
     "glhip_last_error": (ctypes.c_char_p, []),
     "glhip_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "glhip_softmin_fwd_family": (_c_int, [_c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int, _c_int]),
+    "glhip_kernel_conv_fwd_family": (_c_int, [_c_int, _c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int]),
     "glhip_softmin_fwd": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int, _c_int]
                           + _RANGES + _TAIL),
     "glhip_sinkhorn_step": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_float,
@@ -1072,7 +1079,9 @@ def softmin(eps, x, y, h, p=2, ranges=None, flags=0):
 
 
 def fused_step_applies(D, p=2, flags=0, sparse=False):
-    """Whether ``glhip_sinkhorn_step`` has a kernel for clouds of dimension D: every operator for D <= 3; for 4 <= D <= XD_MAX_DIM
+    """Whether one of the kernels of D <= XD_MAX_DIM = 16 serves ``glhip_sinkhorn_step`` for clouds of dimension D (always False
+    beyond: the fused half-step of 17 <= D <= 4095 is a different kernel — ask :func:`half_step_applies`, which the drivers do, for
+    "is the half-step ONE launch"): every operator for D <= 3; for 4 <= D <= XD_MAX_DIM
     the matrix-core kernels — p = 2 (glhip_softmin_xd.h), and since round 5 p = 1 on DENSE launches (glhip_dist_xd.h; ``sparse``:
     the launch carries block-sparse ranges) — which GLHIP_FLAG_NO_MFMA / GLHIP_FLAG_DIRECT switch off: the generic-dimension
     kernel those flags fall back to has no fused half-step."""
@@ -1083,10 +1092,37 @@ def fused_step_applies(D, p=2, flags=0, sparse=False):
     return p == 2 or (p == 1 and not sparse)
 
 
+def half_step_applies(D, p=2, flags=0, sparse=False):
+    """Whether :func:`sinkhorn_step` runs as ONE ``glhip_sinkhorn_step`` launch: wherever :func:`fused_step_applies` (the kernels of
+    D <= 16), and for p = 2 clouds of 17 <= D <= MFMA_FWD_MAX_DIM on the K-chunked matrix-core kernel (glhip_softmin_xk.h), which
+    GLHIP_FLAG_NO_MFMA / GLHIP_FLAG_DIRECT switch off like the others."""
+    if fused_step_applies(D, p, flags, sparse):
+        return True
+    return p == 2 and XD_MAX_DIM < D <= MFMA_FWD_MAX_DIM and not ((int(flags) | ENV_FLAGS) & (FLAG_NO_MFMA | FLAG_DIRECT))
+
+
+def softmin_fwd_family(B, N, M, D, p=2, dtype=F32, flags=0, n_ranges=0):
+    """The kernel family (FAMILY_*) ``glhip_softmin_fwd`` / ``glhip_sinkhorn_step`` select for a launch of this shape: the library's own
+    predicate (``glhip_softmin_fwd_family``), host arithmetic only — no device is touched."""
+    fam = load_library().glhip_softmin_fwd_family(int(B), int(N), int(M), int(D), int(p), int(dtype), int(flags), int(n_ranges))
+    if fam < 0:
+        raise ValueError(f"glhip_softmin_fwd_family: bad arguments B={B} N={N} M={M} D={D} p={p} dtype={dtype} n_ranges={n_ranges}")
+    return fam
+
+
+def kernel_conv_fwd_family(kind, B, N, M, D, dtype=F32, flags=0, n_ranges=0):
+    """The same for the kernel products of ``glhip_kernel_conv_fwd`` (``glhip_kernel_conv_fwd_family``); ``kind``: a name or a code."""
+    fam = load_library().glhip_kernel_conv_fwd_family(int(KERNEL_KINDS.get(kind, kind)), int(B), int(N), int(M), int(D), int(dtype), int(flags),
+                                                      int(n_ranges))
+    if fam < 0:
+        raise ValueError(f"glhip_kernel_conv_fwd_family: bad arguments kind={kind} B={B} N={N} M={M} D={D} dtype={dtype} n_ranges={n_ranges}")
+    return fam
+
+
 def sinkhorn_step(eps, x, y, logw, pot, prev, damping, p=2, ranges=None, flags=0):
     """One non-differentiable half-step of the Sinkhorn loop on the GPU: (prev + damping * softmin(eps, C, logw + pot/eps)) / 2,
-    or damping * softmin(...) when prev is None — ONE launch where :func:`fused_step_applies`, the soft-min kernel followed by
-    torch arithmetic elsewhere (D > 16, block-sparse p = 1 in D > 3, D > 3 under GLHIP_FLAG_NO_MFMA / GLHIP_FLAG_DIRECT).
+    or damping * softmin(...) when prev is None — ONE launch where :func:`half_step_applies`, the soft-min kernel followed by
+    torch arithmetic elsewhere (p = 1 in D > 16, D > 4095, block-sparse p = 1 in D > 3, D > 3 under GLHIP_FLAG_NO_MFMA / GLHIP_FLAG_DIRECT).
 
     x: (N,D)|(B,N,D), y: (M,D)|(B,M,D); logw, pot: (M,)|(B,M) (pot may be None); prev: (N,)|(B,N) or None.
     Returns fp32 (N,)|(B,N).  Used by the drivers inside the no-grad part of ``sinkhorn_loop``."""
@@ -1098,7 +1134,7 @@ def sinkhorn_step(eps, x, y, logw, pot, prev, damping, p=2, ranges=None, flags=0
         pv = None if prev is None else prev.detach().double().contiguous().reshape(B, -1)
         out = sinkhorn_step_raw(xb, yb.double(), lw, pt, pv, eps, damping, p, ranges, 0)
         return out if batched else out.view(-1)
-    if not fused_step_applies(x.shape[-1], p, flags, ranges is not None) or is_f64(x):
+    if not half_step_applies(x.shape[-1], p, flags, ranges is not None) or is_f64(x):
         with torch.no_grad():
             h = _vec(logw, x) if pot is None else _vec(logw, x) + _vec(pot, x).reshape(logw.shape) / eps
             ft = damping * softmin(eps, x.detach(), y.detach(), h, p=p, ranges=ranges, flags=flags)

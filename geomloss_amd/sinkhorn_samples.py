@@ -124,7 +124,9 @@ class _HipSoftmin:
         """Tells the soft-min how wide the clouds ARE (the diagonal of their bounding box, or an upper bound of it; None: unknown),
         so that it can ask for the f16 x 2 exponent layout (GLHIP_FLAG_F16X2: about half the matrix instructions and LDS bytes of
         the default bf16 x 3 one) where the exponents fit f16's range: terms of size log2(e) extent^2 / eps must stay below ~2.6e5,
-        i.e. eps >= 2e-5 extent^2 with a factor 3 of headroom.  The extent is always MEASURED on the data: a ``diameter=`` given by
+        i.e. eps >= 2e-5 extent^2 with a factor 3 of headroom.  The rule bounds EXPONENTS, so it holds in every dimension the layout
+        serves (up to 4095): extent^2 already grows with D, log2(e) extent^2 / eps <= 7.2e4 stays inside the floor kH2Floor = -5e5, and
+        the scaled coordinates sqrt(log2(e) / eps) |x - c| <= 270 inside f16's 65504.  The extent is always MEASURED on the data: a ``diameter=`` given by
         the caller only parametrises the schedule (``_legacy/sinkhorn_divergence.py:154-163``) and may understate the clouds, so
         it is never used here (round 5 trusted it with a factor 15 and returned inf / nan on understated values).
         p = 2 only; GEOMLOSS_HIP_F16X2=0 keeps bf16 x 3.
@@ -147,7 +149,7 @@ class _HipSoftmin:
     def step(self, eps, C, log_w, pot, damping, prev):
         x, y = C[0], C[1]
         ranges = C[4] if self.multiscale else None
-        if not hip.fused_step_applies(x.shape[-1], self.p, 0, ranges is not None):  # no fused kernel on the generic-dimension path (incl. D > 3 under NO_MFMA / DIRECT)
+        if not hip.half_step_applies(x.shape[-1], self.p, 0, ranges is not None):  # no fused kernel on the generic-dimension path (incl. D > 3 under NO_MFMA / DIRECT)
             ft = damping * self(eps, C, log_w if pot is None else log_w + pot / eps)
             return ft if prev is None else 0.5 * (prev + ft)
         flat = (lambda t: None if t is None else t.reshape(-1)) if x.dim() == 2 else (lambda t: t)

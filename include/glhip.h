@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 120 /* 0.1.20 */
+#define GLHIP_VERSION 121 /* 0.1.21 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
@@ -79,13 +79,14 @@ extern "C" {
                                   (sum of squared block sizes / N <= 64): launch 2-wavefront workgroups over 256-column tiles.  A hint: results
                                   do not depend on it.  The caller knows the block sizes (glhip_block_ranges_kept_pairs returns the sum). */
 
-#define GLHIP_FLAG_F16X2 256 /* p = 2 soft-min (forward, half-step, gradient) and gaussian product / gradient, 4 <= D <= 16 (and the D <= 3
-                                  soft-min forward): form the exponents from TWO f16 pieces per coordinate (3 products, v_mfma_f32_32x32x16_f16)
+#define GLHIP_FLAG_F16X2 256 /* p = 2 soft-min (forward, half-step, gradient) and gaussian product / gradient, 4 <= D <= 16, the D <= 3
+                                  soft-min forward, and (version 121) the soft-min forward / half-step / gaussian product of 17 <= D <= 4095: form the exponents from TWO f16 pieces per coordinate (3 products, v_mfma_f32_32x32x16_f16)
                                   instead of three bf16 pieces (6 products) — about half the matrix instructions and LDS bytes.  Cross terms
                                   good to ~2^-21 relative instead of 2^-24 (csrc/glhip_softmin_xd.h).  THE CALLER VOUCHES FOR THE RANGE: every
                                   exponent term (log2(e) h_j, |x - y|^2 / (2 eps ln 2)) must stay below ~2.6e5 in magnitude, i.e. roughly
-                                  (cloud diameter)^2 / eps < 3e5; beyond that f16 overflows and the results are inf / nan.  Ignored by kernels
-                                  without that layout (p = 1, laplacian, energy, D > 16, float64). */
+                                  (cloud diameter)^2 / eps < 3e5; beyond that f16 overflows and the results are inf / nan.  The bound is on the
+                                  exponents, so it is the same in every dimension (diameter^2 grows like D on a unit cube).  Ignored by kernels
+                                  without that layout (p = 1, laplacian, energy, the gradients of D > 16, D > 4095, float64). */
 
 #define GLHIP_FLAG_NO_SORT 512 /* p = 1 soft-min / half-step, laplacian and energy products: big dense launches (B = 1, D <= 3, N >= 65536,
                                   N M >= 5e8, a workspace of glhip_workspace_bytes) sort both clouds into the workspace themselves — voxel sort along a
@@ -119,6 +120,16 @@ extern "C" {
 #define GLHIP_EUNSUPPORTED (-2) /* valid request this build has no kernel for */
 #define GLHIP_ELAUNCH (-3)      /* hipGetLastError() after the launch was not hipSuccess */
 
+/* kernel families of the soft-min forward / fused half-step (glhip_softmin_fwd_family) and of the kernel products (glhip_kernel_conv_fwd_family) */
+#define GLHIP_FAMILY_VALU 0    /* D <= 3 on the VALU map-reduce skeleton (glhip_mapreduce.h): p = 1, GLHIP_FLAG_DIRECT / _NO_MFMA */
+#define GLHIP_FAMILY_X32 1     /* p = 2, D <= 3: matrix cores, glhip_softmin_x32.h */
+#define GLHIP_FAMILY_XD 2      /* p = 2, 4 <= D <= 16 (and big dense GLHIP_FLAG_F16X2 launches of D <= 3): matrix cores, glhip_softmin_xd.h */
+#define GLHIP_FAMILY_XK 3      /* p = 2, 17 <= D <= 4095: matrix cores, K-chunked, D a run-time argument, glhip_softmin_xk.h */
+#define GLHIP_FAMILY_DIST 4    /* p = 1 with the squared distances on the matrix cores: glhip_dist_x32.h (block-sparse, D <= 3,
+                                  GLHIP_FLAG_MFMA_DIST) / glhip_dist_xd.h (dense, 4 <= D <= 16) */
+#define GLHIP_FAMILY_GENERIC 5 /* D > 3 on the one-thread-per-row kernel of glhip_generic.h: p = 1 block-sparse or D > 16, p = 2 with D > 4095
+                                  or under GLHIP_FLAG_NO_MFMA / _DIRECT */
+
 int glhip_version(void);
 const char* glhip_last_error(void);
 
@@ -131,9 +142,24 @@ const char* glhip_last_error(void);
  * copy instead of recomputing.  glhip_workspace_bytes returns a size that lets every entry point use its
  * preferred plan for the given problem (208 MB at B = 1, N = M = 1e6, D = 3); smaller buffers are used as
  * far as they go.  The buffer must stay alive until the work queued on `stream` has run; its contents
- * are scratch.
+ * are scratch.  17 <= D <= 4095 (version 121; 0 before): the column-split partials of the forward kernels (2 floats per row and
+ * split, up to 32 splits) — those kernels stage their operands on the fly and keep nothing else there; the gradients of D > 16 and
+ * every launch of D > 4095 use no workspace.
  */
 size_t glhip_workspace_bytes(int B, int N, int M, int D, int n_ranges);
+
+/*
+ * Which kernel family (GLHIP_FAMILY_*) glhip_softmin_fwd / glhip_sinkhorn_step select for a launch of this shape: the predicate the
+ * launch itself evaluates, exposed so that tests and callers can see the choice.  Host arithmetic only: no device, no stream, no
+ * launch.  For the big dense D <= 3 launches that sort their clouds first (see GLHIP_FLAG_NO_SORT) it reports the family of the
+ * inner block-sparse launch, which assumes a workspace of glhip_workspace_bytes.  Returns GLHIP_EINVAL for sizes, p or dtype the
+ * entry points reject.
+ */
+int glhip_softmin_fwd_family(int B, long N, long M, int D, int p, int dtype, int flags, int n_ranges);
+/* ... and the same for the products of glhip_kernel_conv_fwd.  Gaussian: _X32 (D <= 3; here the matrix-core product of glhip_wsum_x32.h /
+ * glhip_wsum_mfma.h), _XD, _XK, or _VALU / _GENERIC under GLHIP_FLAG_NO_MFMA and beyond D = 4095; laplacian / energy: _DIST where the
+ * squared distances come from the matrix cores, _VALU / _GENERIC elsewhere. */
+int glhip_kernel_conv_fwd_family(int kind, int B, long N, long M, int D, int dtype, int flags, int n_ranges);
 
 /*
  * Soft-C-transform  out[b,i] = -eps * log sum_j exp( h[b,j] - C(x[b,i], y[b,j]) / eps ),
@@ -147,10 +173,10 @@ size_t glhip_workspace_bytes(int B, int N, int M, int D, int n_ranges);
  *
  *   x (B,N,D)  y (B,M,D)  h (B,M) fp32  out (B,N) fp32
  *
- * Kernels by (p, D): p = 2 on the matrix cores for D <= 16 (glhip_softmin_x32.h / _xd.h; GLHIP_FLAG_F16X2 selects the two-piece f16
- * layout); p = 1 on the matrix cores for block-sparse launches of D <= 3 with GLHIP_FLAG_MFMA_DIST (glhip_dist_x32.h) and, since
+ * Kernels by (p, D): p = 2 on the matrix cores for D <= 4095 (glhip_softmin_x32.h / _xd.h up to D = 16, the K-chunked glhip_softmin_xk.h
+ * from D = 17 on, version 121; GLHIP_FLAG_F16X2 selects the two-piece f16 layout); p = 1 on the matrix cores for block-sparse launches of D <= 3 with GLHIP_FLAG_MFMA_DIST (glhip_dist_x32.h) and, since
  * round 5, for every DENSE launch of 4 <= D <= 16 (glhip_dist_xd.h: squared distances from the MFMA chain, pairs closer than 1/16 of
- * their offset from the cloud's centre re-evaluated exactly); everything else (D > 16, block-sparse p = 1 in D > 3, GLHIP_FLAG_NO_MFMA /
+ * their offset from the cloud's centre re-evaluated exactly); everything else (p = 1 in D > 16, p = 2 in D > 4095, block-sparse p = 1 in D > 3, GLHIP_FLAG_NO_MFMA /
  * GLHIP_FLAG_DIRECT) on explicit differences.
  * Accuracy of the matrix-core distances (p = 1; laplacian / energy products): the squared distance of a pair carries ~2^-23 t^2 R^2
  * (t = log2(e) / eps, R = offset of the pair from the centre the launch subtracts), so the EXPONENT of a pair just above the near-pair
@@ -166,8 +192,8 @@ int glhip_softmin_fwd(const void* x, const void* y, const float* h, float* out,
                       void* workspace, size_t workspace_bytes, int flags, void* stream);
 
 /*
- * One fused half-step of the symmetric Sinkhorn iteration (every kernel of D <= 3; p = 2 for D <= 16; p = 1 on dense launches for
- * D <= 16; GLHIP_EUNSUPPORTED elsewhere — compose glhip_softmin_fwd):
+ * One fused half-step of the symmetric Sinkhorn iteration (every kernel of D <= 3; p = 2 for D <= 4095 (D > 16: version 121); p = 1 on
+ * dense launches for D <= 16; GLHIP_EUNSUPPORTED elsewhere — compose glhip_softmin_fwd):
  *   t_i   = soft-min(eps, C(x,y), logw + pot / eps)_i          (pot == NULL: logw alone, the initialisation)
  *   out_i = damping * t_i                                       (prev == NULL)
  *   out_i = (prev_i + damping * t_i) / 2                        (prev != NULL; out must not alias prev)
@@ -280,6 +306,9 @@ int glhip_lse_lines_bwd(const float* h, const float* lse, const float* grad_out,
  *   recomputed row sum, as autograd's logsumexp backward does).
  * Replaces: the symbolic KeOps `Grad` of the generic_logsumexp above.
  * (p = 1, dense, 4 <= D <= 16: glhip_dist_xd.h since round 5 — distances from the MFMA chain, near pairs from the points themselves.)
+ * D > 16: the one-thread-per-row kernel of glhip_generic.h, in ANY dimension (version 121; D <= 64 before): 64 output coordinates
+ * per pass over the columns, ceil(D / 64) passes.  The same holds for glhip_kernel_conv_bwd_x.  A matrix-core gradient for D > 16
+ * (the weighted sums sum_j w_ij y_j as a second MFMA product) is not part of the library yet.
  *   out = the saved forward result (B,N);  grad_out (B,N) fp32;  grad_x (B,N,D) fp32.
  */
 int glhip_softmin_bwd_x(const void* x, const void* y, const float* h,
@@ -298,7 +327,7 @@ int glhip_softmin_bwd_x(const void* x, const void* y, const float* h,
  *   The transposed product K^T @ a (:135-137) is the same call with x and y swapped.
  *
  *   v (B,M) fp32, out (B,N) fp32.
- *   gaussian: matrix cores for D <= 16; laplacian / energy: matrix-core distances for block-sparse D <= 3 launches with
+ *   gaussian: matrix cores for D <= 4095 (glhip_softmin_xk.h from D = 17 on, version 121); laplacian / energy: matrix-core distances for block-sparse D <= 3 launches with
  *   GLHIP_FLAG_MFMA_DIST and for dense launches of 4 <= D <= 16 (glhip_dist_xd.h, round 5); explicit differences elsewhere.
  */
 int glhip_kernel_conv_fwd(int kind, const void* x, const void* y, const float* v, float* out,
