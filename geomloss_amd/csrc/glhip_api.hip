@@ -110,6 +110,25 @@ static bool softmin_sorts(int B, int N, int M, int D, int p, int n_ranges, int f
     return (p == 1 || prune_applies(N, M)) && autosort_applies(B, N, M, D, n_ranges, flags);
 }
 
+// The inner launch of a sorted call: the block-sparse launch over the slabs of the sorted clouds, on the rest of the workspace.  p = 2:
+// with the records of the second pruning level (glhip_softmin_x32.h), which only this path hands to a kernel.
+static int sorted_inner(const AutoSort& a, const void* x, const float* h, int N, int M, int D, float eps, int p, int in_dtype, int flags,
+                        hipStream_t st, const StepArgs& step = StepArgs()) {
+    const int inner = flags | (p == 1 ? GLHIP_FLAG_MFMA_DIST : 0) | GLHIP_FLAG_NO_SORT;
+    Scratch sc = make_scratch(a.inner_ws, a.inner_bytes, inner, a.C, N);
+    if (p == 2) {
+        sc.l2.groups = static_cast<const GroupBox*>(a.groups);
+        sc.l2.home = a.home;
+        sc.l2.centre_x = x;
+        sc.l2.n_groups = (M + 31) / 32;
+        sc.l2.L2 = (float)(prune_L(M) * 1.4426950408889634);
+    }
+    const Ranges rg{a.ranges_i, a.slices_i, a.red};
+    return (in_dtype == GLHIP_F32)
+               ? softmin_typed<false, float>(a.xs, a.ys, h, a.out, nullptr, nullptr, nullptr, 1, N, M, D, eps, p, rg, a.C, sc, inner, st, step)
+               : softmin_typed<false, bf16_t>(a.xs, a.ys, h, a.out, nullptr, nullptr, nullptr, 1, N, M, D, eps, p, rg, a.C, sc, inner, st, step);
+}
+
 int glhip_softmin_fwd_family(int B, long N, long M, int D, int p, int dtype, int flags, int n_ranges) {
     if (B < 0 || N < 0 || M < 0 || N > 0x7fffffffL || M > 0x7fffffffL || D < 1 || n_ranges < 0 || (p != 1 && p != 2) ||
         (dtype != GLHIP_F32 && dtype != GLHIP_BF16))
@@ -138,9 +157,9 @@ int glhip_softmin_fwd(const void* x, const void* y, const float* h, float* out, 
         if (rc) return rc;
         if (a.on) {
             gather_f32(h, a.perm_y, a.col0, M, st);
-            if (p == 2) prune_ranges(a.xs, a.ys, a.col0, nullptr, 0.f, N, M, D, in_dtype, eps, a.ranges_i, a.slices_i, a.red, a.blocks, st);
-            rc = glhip_softmin_fwd(a.xs, a.ys, a.col0, a.out, 1, N, M, D, eps, p, in_dtype, a.ranges_i, a.slices_i, a.red, a.C, a.inner_ws,
-                                   a.inner_bytes, flags | (p == 1 ? GLHIP_FLAG_MFMA_DIST : 0) | GLHIP_FLAG_NO_SORT, stream);
+            if (p == 2)
+                prune_ranges(a.xs, a.ys, a.col0, nullptr, 0.f, N, M, D, in_dtype, eps, a.ranges_i, a.slices_i, a.red, a.blocks, a.groups, a.home, st);
+            rc = sorted_inner(a, x, a.col0, N, M, D, eps, p, in_dtype, flags, st);
             if (rc) return rc;
             scatter_f32(a.out, a.perm_x, out, N, st);
             return check_launch("glhip_softmin_fwd");
@@ -176,10 +195,15 @@ int glhip_sinkhorn_step(const void* x, const void* y, const float* logw, const f
             if (pot) gather_f32(pot, a.perm_y, a.col1, M, st);
             if (prev) gather_f32(prev, a.perm_x, a.row0, N, st);
             // (the bound takes the column vector the kernels form: logw + pot / eps)
-            if (p == 2) prune_ranges(a.xs, a.ys, a.col0, pot ? a.col1 : nullptr, 1.0f / eps, N, M, D, in_dtype, eps, a.ranges_i, a.slices_i, a.red, a.blocks, st);
-            rc = glhip_sinkhorn_step(a.xs, a.ys, a.col0, pot ? a.col1 : nullptr, prev ? a.row0 : nullptr, a.out, 1, N, M, D, eps, damping, p, in_dtype,
-                                     a.ranges_i, a.slices_i, a.red, a.C, a.inner_ws, a.inner_bytes,
-                                     flags | (p == 1 ? GLHIP_FLAG_MFMA_DIST : 0) | GLHIP_FLAG_NO_SORT, stream);
+            if (p == 2)
+                prune_ranges(a.xs, a.ys, a.col0, pot ? a.col1 : nullptr, 1.0f / eps, N, M, D, in_dtype, eps, a.ranges_i, a.slices_i, a.red, a.blocks,
+                             a.groups, a.home, st);
+            StepArgs inner_step;
+            inner_step.pot = pot ? a.col1 : nullptr;
+            inner_step.prev = prev ? a.row0 : nullptr;
+            inner_step.alpha = prev ? 0.5f * damping : damping;
+            inner_step.beta = prev ? 0.5f : 0.f;
+            rc = sorted_inner(a, x, a.col0, N, M, D, eps, p, in_dtype, flags, st, inner_step);
             if (rc) return rc;
             scatter_f32(a.out, a.perm_x, out, N, st);
             return check_launch("glhip_sinkhorn_step");

@@ -5,7 +5,8 @@
 // so a caller binding glhip_softmin_fwd(p = 1) through INTEGRATION.md's stub — the `lse_genred("Norm2(X-Y)")` call site,
 // _legacy/sinkhorn_samples.py:316-334 — got the generic explicit-difference kernel: 346 ms instead of 191 at N = M = 1e6.
 // Now the entry points do it behind the ABI, inside the caller's workspace and on the caller's stream, without a host round trip:
-//   bounding box -> voxel edge (~256 rows per voxel; columns: 512) -> boustrophedon path index of every point as the sort key ->
+//   bounding box -> voxel edge (~256 rows per voxel; columns: 512; the pruned p = 2 call: 256 / 256 and a minor key, below) ->
+//   boustrophedon path index of every point as the sort key ->
 //   rocPRIM radix sort -> gathered clouds and column / row vectors -> the block-sparse launch "every slab of 256 rows x all columns"
 //   with GLHIP_FLAG_MFMA_DIST -> results scattered back to the caller's row order.
 // Conditions: B = 1, dense, D <= 3, N >= 65536, N M >= 5e8 (p = 2: >= 1e11, prune_applies), neither GLHIP_FLAG_NO_MFMA / _DIRECT nor GLHIP_FLAG_NO_SORT, and a
@@ -14,6 +15,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 
@@ -38,7 +40,15 @@ constexpr int kSortRowsPerVoxel = 256;
 //   Kept blocks become column intervals per slab: at most kPruneRuns runs (a slab with more closes its smallest gaps: more work,
 //   never less), cut on a grid of pieces so that the column splits of the inner launch, which take a slab's intervals round robin,
 //   get even shares even when nothing prunes.
-constexpr int kPruneColBlock = 256;   // columns per column block T (a multiple of 32)
+//   Second level (round 9; the test and its exactness argument: glhip_softmin_x32.h, P2): inside the kept intervals every wavefront of
+//   the reducing kernel skips the groups of 32 columns that cannot matter to its own 32 rows, against its rows' running maxima seeded
+//   with their exact maxima over the slab's HOME BLOCK — the block that attains Mlb(R), always kept (its dmin <= its dmax).  For it
+//   prune_blocks_kernel also writes one record per aligned group of 32 sorted columns (intervals start on multiples of kPruneColBlock,
+//   so a tile's group g is a global group) and prune_slabs_kernel the home block of every slab (-1: a slab that keeps everything, for
+//   lack of a finite bound or because every block passes it — no second level, no cost of it, for such a slab).  The sorted p = 2 call orders both clouds in voxels of kSortRowsPerVoxel
+//   points with a minor key of sub-voxels of ~32 points (prune_sort_sub), so that 32 consecutive points are compact; the distance
+//   launches (p = 1, laplacian, energy) keep the order they had.
+constexpr int kPruneColBlock = 256;   // columns per column block T (a multiple of 64)
 constexpr int kPruneRuns = 160;       // runs of kept blocks per slab (the bench problem: mean 66, max 143 at 256 columns per block)
 constexpr int kPruneGrid = 64;        // pieces a whole row of column blocks is cut into, at most
 constexpr double kPruneMarginNats = 1.0;
@@ -68,15 +78,22 @@ inline size_t as_align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // implemented in glhip_cluster.hip (rocPRIM lives there)
 size_t compact_sort_scratch_bytes(int n);
+// sub > 1: inside a voxel, points are ordered by sub-voxel of edge voxel / sub (the minor key of path_keys_kernel)
 int compact_sort(const void* z, int n, int D, int in_dtype, int rows_per_voxel, int32_t* perm, void* z_sorted, void* scratch,
-                 size_t scratch_bytes, hipStream_t st);
+                 size_t scratch_bytes, hipStream_t st, int sub = 1);
 void gather_f32(const float* src, const int32_t* perm, float* dst, int n, hipStream_t st);       // dst[k] = src[perm[k]]
 void scatter_f32(const float* src, const int32_t* perm, float* dst, int n, hipStream_t st, int width = 1);      // dst[perm[k], :] = src[k, :]
 void slab_ranges(int N, int M, int32_t* ranges_i, int32_t* slices_i, int32_t* red, hipStream_t st);
 size_t prune_blocks_bytes(int M);
-// the kept column intervals of every slab of the sorted clouds xs (N, D), ys (M, D) for the column vector h (+ pot * pot_scale)
+size_t prune_groups_bytes(int M);
+// the kept column intervals of every slab of the sorted clouds xs (N, D), ys (M, D) for the column vector h (+ pot * pot_scale); for the
+// second level: the records of the groups of 32 columns (`groups`, prune_groups_bytes) and every slab's home block (`home`, C ints)
 void prune_ranges(const void* xs, const void* ys, const float* h, const float* pot, float pot_scale, int N, int M, int D, int in_dtype,
-                  float eps, int32_t* ranges_i, int32_t* slices_i, int32_t* red, void* blocks, hipStream_t st);
+                  float eps, int32_t* ranges_i, int32_t* slices_i, int32_t* red, void* blocks, void* groups, int32_t* home, hipStream_t st);
+// L of the bound in nats
+inline double prune_L(int M) { return std::log((double)M) + 26.0 * 0.6931471805599453 + kPruneMarginNats; }
+// sub-voxels per axis of the sorted p = 2 call: sub^D ~ 8 sub-voxels of ~32 points in a voxel of kSortRowsPerVoxel
+inline int prune_sort_sub(int D) { return D >= 3 ? 2 : (D == 2 ? 3 : 8); }
 
 inline bool autosort_applies(int B, int N, int M, int D, int n_ranges, int flags) {
     return B == 1 && n_ranges == 0 && D <= 3 && N >= 65536 && (double)N * M >= 5e8 &&
@@ -91,6 +108,8 @@ struct AutoSort {
     float *col0 = nullptr, *col1 = nullptr, *row0 = nullptr, *out = nullptr;      // gathered per-column / per-row vectors, sorted output
     float* out_rows = nullptr;              // (N, D) sorted output (row gradients)
     void* blocks = nullptr;                 // per-column-block boxes and dual maxima (pruned p = 2 launches)
+    void* groups = nullptr;                 // the same per group of 32 columns, and every slab's home block: the second level
+    int32_t* home = nullptr;
     void* inner_ws = nullptr;
     size_t inner_bytes = 0;
 };
@@ -103,7 +122,8 @@ inline size_t autosort_bytes(int N, int M, int D) {
     return as_align256((size_t)N * 4) + as_align256((size_t)M * 4) + as_align256((size_t)N * D * 4) + as_align256((size_t)M * D * 4) +
            2 * as_align256((size_t)M * 4) + 2 * as_align256((size_t)N * 4) + as_align256((size_t)N * D * 4) + as_align256((size_t)C * 8) +
            as_align256((size_t)C * 4) +
-           as_align256((size_t)C * slots * 8) + as_align256(prune_blocks_bytes(M)) + compact_sort_scratch_bytes(L);
+           as_align256((size_t)C * slots * 8) + as_align256(prune_blocks_bytes(M)) + as_align256(prune_groups_bytes(M)) +
+           as_align256((size_t)C * 4) + compact_sort_scratch_bytes(L);
 }
 
 // Sorts both clouds into the workspace; `a.on` stays false when the workspace is too small for the sorted call plus `inner_min`
@@ -131,12 +151,16 @@ inline int autosort_prepare(AutoSort& a, const void* x, const void* y, int N, in
     const size_t slots = (size_t)(kSortColChunks > prune_plan(M).S ? kSortColChunks : prune_plan(M).S);
     a.red = reinterpret_cast<int32_t*>(take((size_t)a.C * slots * 8));
     a.blocks = take(prune_blocks_bytes(M));
+    a.groups = take(prune_groups_bytes(M));
+    a.home = reinterpret_cast<int32_t*>(take((size_t)a.C * 4));
     const int L = N > M ? N : M;
     const size_t sb = compact_sort_scratch_bytes(L);
     void* scratch = take(sb);
-    int rc = compact_sort(x, N, D, in_dtype, kSortRowsPerVoxel, a.perm_x, a.xs, scratch, sb, st);
+    // (slabs = false is the pruned p = 2 call: both clouds in voxels of kSortRowsPerVoxel points, compact sub-voxels inside)
+    int rc = compact_sort(x, N, D, in_dtype, kSortRowsPerVoxel, a.perm_x, a.xs, scratch, sb, st, slabs ? 1 : prune_sort_sub(D));
     if (rc) return rc;
-    rc = compact_sort(y, M, D, in_dtype, 2 * kSortRowsPerVoxel, a.perm_y, a.ys, scratch, sb, st);
+    rc = compact_sort(y, M, D, in_dtype, slabs ? 2 * kSortRowsPerVoxel : kSortRowsPerVoxel, a.perm_y, a.ys, scratch, sb, st,
+                      slabs ? 1 : prune_sort_sub(D));
     if (rc) return rc;
     if (slabs) slab_ranges(N, M, a.ranges_i, a.slices_i, a.red, st);
     a.inner_ws = w + off;

@@ -310,22 +310,32 @@ __global__ void voxel_kernel(SortHead* head, int n, int D, int rows_per_voxel) {
 
 // sort key = index of the point's voxel along a boustrophedon path through the voxel grid (the scan direction of an axis flips each
 // time the path index of the axes before it advances): voxels that follow each other in the order are face neighbours in space, so
-// ANY run of consecutive rows of the sorted cloud is spatially compact (hip.py:_serpentine did this on the cluster list)
+// ANY run of consecutive rows of the sorted cloud is spatially compact (hip.py:_serpentine did this on the cluster list).
+// sub > 1 (the sorted p = 2 launches): a minor key orders the points INSIDE a voxel by sub-voxel of edge voxel / sub, along the same
+// kind of path, so that a run of ~rows_per_voxel / sub^D consecutive points (a 32-row wavefront tile, a group of 32 columns) has a
+// sub-voxel's box instead of the whole voxel's; the voxel order itself, which the slab x block bound sees, is unchanged.
 template <typename T>
-__global__ void __launch_bounds__(256) path_keys_kernel(const T* __restrict__ x, int n, int D, const SortHead* __restrict__ head,
+__global__ void __launch_bounds__(256) path_keys_kernel(const T* __restrict__ x, int n, int D, const SortHead* __restrict__ head, int sub,
                                                         uint64_t* __restrict__ keys, int32_t* __restrict__ idx) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float voxel = head->voxel;
-    uint64_t path = 0;
+    uint64_t path = 0, minor = 0, cells = 1;
     for (int d = 0; d < D; ++d) {
         const int e = head->ext[d];
-        int q = (int)floorf(to_f32<T>(x[i * D + d]) / voxel) - head->qmin[d];
+        const float f = to_f32<T>(x[i * D + d]) / voxel, fl = floorf(f);
+        int q = (int)fl - head->qmin[d];
         q = q < 0 ? 0 : (q >= e ? e - 1 : q);
         const int c = (path & 1) ? e - 1 - q : q;
         path = path * (uint64_t)e + (uint64_t)c;
+        if (sub > 1) {
+            int r = (int)((f - fl) * (float)sub);
+            r = r > 0 ? (r >= sub ? sub - 1 : r) : 0;      // (NaN: 0)
+            minor = minor * (uint64_t)sub + (uint64_t)((minor & 1) ? sub - 1 - r : r);
+            cells *= (uint64_t)sub;
+        }
     }
-    keys[i] = path;
+    keys[i] = path * cells + minor;      // path < 2^60 (at most 2^20 voxels along an axis), cells <= 9
     idx[i] = (int32_t)i;
 }
 
@@ -371,45 +381,77 @@ struct ColBlock {           // one block of kPruneColBlock sorted columns
     float hi[3];
     int special;            // a non-finite coordinate or a NaN dual value: kept by every slab, left out of Mlb
 };
+static_assert(kHomeCols == kPruneColBlock && kPruneColBlock % 64 == 0 && sizeof(GroupBox) == 32, "block / group records");
 
-// one wavefront per column block; lane l takes columns l, l + 64, ...
+// one wavefront per column block; in step k lanes 0-31 take the block's group 2 k of 32 columns and lanes 32-63 group 2 k + 1: the
+// same pass writes the record of every group (the second level of the bound, glhip_softmin_x32.h) and the block's own
 template <typename T>
 __global__ void __launch_bounds__(256) prune_blocks_kernel(const T* __restrict__ ys, const float* __restrict__ h, const float* __restrict__ pot,
-                                                           float pot_scale, int M, int D, int nT, ColBlock* __restrict__ out) {
+                                                           float pot_scale, int M, int D, int nT, ColBlock* __restrict__ out,
+                                                           GroupBox* __restrict__ groups) {
     const int lane = threadIdx.x & 63;
     const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (t >= nT) return;
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    float hm = -INFINITY;
-    int bad = 0;
+    float blo[3] = {INFINITY, INFINITY, INFINITY}, bhi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    float bhm = -INFINITY;
+    int bbad = 0;
     const int j0 = t * kPruneColBlock, j1 = min(M, j0 + kPruneColBlock);
-    for (int j = j0 + lane; j < j1; j += 64) {
-        for (int d = 0; d < D; ++d) {
-            const float v = to_f32<T>(ys[(long)j * D + d]);
-            bad |= !__builtin_isfinite(v);
-            lo[d] = fminf(lo[d], v);
-            hi[d] = fmaxf(hi[d], v);
+    for (int k = 0; k < kPruneColBlock / 64; ++k) {
+        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        float hm = -INFINITY;
+        int bad = 0;
+        const int j = j0 + 64 * k + lane;
+        if (j < j1) {
+            for (int d = 0; d < D; ++d) {
+                const float v = to_f32<T>(ys[(long)j * D + d]);
+                bad |= !__builtin_isfinite(v);
+                lo[d] = v;
+                hi[d] = v;
+            }
+            const float hv = pot ? __builtin_fmaf(pot[j], pot_scale, h[j]) : h[j];     // as the half-step forms it (glhip_softmin_ops.h)
+            bad |= __builtin_isnan(hv);
+            hm = fmaxf(hm, hv);      // (drops a NaN: the mark carries it)
         }
-        const float hv = pot ? __builtin_fmaf(pot[j], pot_scale, h[j]) : h[j];     // as the half-step forms it (glhip_softmin_ops.h)
-        bad |= __builtin_isnan(hv);
-        hm = fmaxf(hm, hv);
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        for (int d = 0; d < D; ++d) {
-            lo[d] = fminf(lo[d], __shfl_xor(lo[d], off, 64));
-            hi[d] = fmaxf(hi[d], __shfl_xor(hi[d], off, 64));
+        for (int off = 16; off > 0; off >>= 1) {
+            for (int d = 0; d < D; ++d) {
+                lo[d] = fminf(lo[d], __shfl_xor(lo[d], off, 64));
+                hi[d] = fmaxf(hi[d], __shfl_xor(hi[d], off, 64));
+            }
+            hm = fmaxf(hm, __shfl_xor(hm, off, 64));
+            bad |= __shfl_xor(bad, off, 64);
         }
-        hm = fmaxf(hm, __shfl_xor(hm, off, 64));
-        bad |= __shfl_xor(bad, off, 64);
+        const int g0 = j0 + 64 * k + (lane & 32);      // first column of this half's group
+        if ((lane & 31) == 0 && g0 < j1) {
+            GroupBox b;
+            for (int d = 0; d < 3; ++d) {
+                b.lohi[d][0] = d < D ? lo[d] : 0.f;
+                b.lohi[d][1] = d < D ? hi[d] : 0.f;
+            }
+            b.hmax = hm;
+            b.special = bad;
+            groups[g0 >> 5] = b;
+        }
+        for (int d = 0; d < D; ++d) {
+            blo[d] = fminf(blo[d], lo[d]);
+            bhi[d] = fmaxf(bhi[d], hi[d]);
+        }
+        bhm = fmaxf(bhm, hm);
+        bbad |= bad;
     }
+    for (int d = 0; d < D; ++d) {
+        blo[d] = fminf(blo[d], __shfl_xor(blo[d], 32, 64));
+        bhi[d] = fmaxf(bhi[d], __shfl_xor(bhi[d], 32, 64));
+    }
+    bhm = fmaxf(bhm, __shfl_xor(bhm, 32, 64));
+    bbad |= __shfl_xor(bbad, 32, 64);
     if (lane == 0) {
         ColBlock b;
         for (int d = 0; d < 3; ++d) {
-            b.lo[d] = d < D ? lo[d] : 0.f;
-            b.hi[d] = d < D ? hi[d] : 0.f;
+            b.lo[d] = d < D ? blo[d] : 0.f;
+            b.hi[d] = d < D ? bhi[d] : 0.f;
         }
-        b.hmax = hm;
-        b.special = bad;
+        b.hmax = bhm;
+        b.special = bbad;
         out[t] = b;
     }
 }
@@ -450,10 +492,11 @@ __device__ __forceinline__ int block_scan256(int v, int* buf) {
 template <typename T>
 __global__ void __launch_bounds__(256) prune_slabs_kernel(const T* __restrict__ xs, int N, int M, int D, const ColBlock* __restrict__ blocks,
                                                           int nT, int PB, int S, double inv2eps, double L, int32_t* __restrict__ ranges_i,
-                                                          int32_t* __restrict__ slices_i, int32_t* __restrict__ red) {
+                                                          int32_t* __restrict__ slices_i, int32_t* __restrict__ red, int32_t* __restrict__ home) {
     __shared__ int buf[256];
     __shared__ float wlo[4][3], whi[4][3];
     __shared__ double wm[4];
+    __shared__ int wb[4];
     const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r0 = k * kSortSlab, r1 = min(N, r0 + kSortSlab);
     if (tid == 0) {
@@ -486,19 +529,31 @@ __global__ void __launch_bounds__(256) prune_slabs_kernel(const T* __restrict__ 
         rhi[d] = fmaxf(fmaxf(whi[0][d], whi[1][d]), fmaxf(whi[2][d], whi[3][d]));
     }
     // Mlb: a lower bound on the largest exponent of every row of the slab
+    // ... and the block that attains it: the slab's home block (the first of them)
     double mlb = -INFINITY;
+    int best = -1;
     if (!bad) {
         for (int t = tid; t < nT; t += 256) {
             const ColBlock b = blocks[t];
             if (b.special) continue;
             double dmin2, dmax2;
             box_d2(rlo, rhi, b, D, dmin2, dmax2);
-            mlb = fmax(mlb, (double)b.hmax - dmax2 * inv2eps);
+            const double v = (double)b.hmax - dmax2 * inv2eps;
+            if (v > mlb) { mlb = v; best = t; }      // (t ascends: the first block of a tie stays)
         }
-        for (int off = 32; off > 0; off >>= 1) mlb = fmax(mlb, __shfl_xor(mlb, off, 64));
-        if (lane == 0) wm[wave] = mlb;
+        auto take = [&](double v, int t) {
+            if (t >= 0 && (v > mlb || (v == mlb && (best < 0 || t < best)))) { mlb = v; best = t; }
+        };
+        for (int off = 32; off > 0; off >>= 1) {
+            const double v = __shfl_xor(mlb, off, 64);
+            const int t = __shfl_xor(best, off, 64);
+            take(v, t);
+        }
+        if (lane == 0) { wm[wave] = mlb; wb[wave] = best; }
         __syncthreads();
-        mlb = fmax(fmax(wm[0], wm[1]), fmax(wm[2], wm[3]));
+        mlb = -INFINITY;
+        best = -1;
+        for (int w = 0; w < 4; ++w) take(wm[w], wb[w]);
     }
     const bool keep_all = bad || !__builtin_isfinite(mlb);
     const double thr = mlb - L;
@@ -510,6 +565,15 @@ __global__ void __launch_bounds__(256) prune_slabs_kernel(const T* __restrict__ 
         box_d2(rlo, rhi, b, D, dmin2, dmax2);
         return (double)b.hmax - dmin2 * inv2eps >= thr;
     };
+    // No second level where it has nothing to win: a slab without a bound, and a slab whose bound keeps every block (large eps: the
+    // finer test would pass nearly every group as well, and costs ~2 % of the sweep)
+    {
+        int all = 1;
+        if (!keep_all)
+            for (int t = tid; t < nT && all; t += 256) all = kept(t) ? 1 : 0;
+        all = __syncthreads_and(all);
+        if (tid == 0) home[k] = (keep_all || all) ? -1 : best;
+    }
     // one walk over the blocks: the number of runs for gap length g, and (EMIT) the pieces written out
     int32_t* slots = red + 2 * (long)k * S;
     auto walk = [&](int g, bool emit) {
@@ -566,8 +630,8 @@ size_t sort64_temp_bytes(int n) {
 }
 
 template <typename T>
-int compact_sort_typed(const void* z_, int n, int D, int rows_per_voxel, int32_t* perm, void* z_sorted, void* scratch, size_t scratch_bytes,
-                       hipStream_t st) {
+int compact_sort_typed(const void* z_, int n, int D, int rows_per_voxel, int sub, int32_t* perm, void* z_sorted, void* scratch,
+                       size_t scratch_bytes, hipStream_t st) {
     const T* z = static_cast<const T*>(z_);
     char* ws = static_cast<char*>(scratch);
     SortHead* head = reinterpret_cast<SortHead*>(ws);
@@ -581,7 +645,7 @@ int compact_sort_typed(const void* z_, int n, int D, int rows_per_voxel, int32_t
     hipLaunchKernelGGL(sort_head_init_kernel, dim3(1), dim3(64), 0, st, head);
     hipLaunchKernelGGL((bbox_kernel<T>), dim3(blocks < 512 ? blocks : 512), dim3(256), 0, st, z, n, D, head);
     hipLaunchKernelGGL(voxel_kernel, dim3(1), dim3(64), 0, st, head, n, D, rows_per_voxel);
-    hipLaunchKernelGGL((path_keys_kernel<T>), dim3(blocks), dim3(256), 0, st, z, n, D, head, keys_in, idx_in);
+    hipLaunchKernelGGL((path_keys_kernel<T>), dim3(blocks), dim3(256), 0, st, z, n, D, head, sub, keys_in, idx_in);
     if (rocprim::radix_sort_pairs(ws + off, temp, keys_in, keys_out, idx_in, perm, (size_t)n, 0u, 64u, st) != hipSuccess)
         return fail(GLHIP_ELAUNCH, "compact_sort: radix sort failed: %s", hipGetErrorString(hipGetLastError()));
     hipLaunchKernelGGL((gather_points_kernel<T>), dim3(blocks), dim3(256), 0, st, z, perm, n, D, static_cast<T*>(z_sorted));
@@ -597,9 +661,9 @@ size_t compact_sort_scratch_bytes(int n) {
 }
 
 int compact_sort(const void* z, int n, int D, int in_dtype, int rows_per_voxel, int32_t* perm, void* z_sorted, void* scratch,
-                 size_t scratch_bytes, hipStream_t st) {
-    return in_dtype == GLHIP_F32 ? compact_sort_typed<float>(z, n, D, rows_per_voxel, perm, z_sorted, scratch, scratch_bytes, st)
-                                 : compact_sort_typed<bf16_t>(z, n, D, rows_per_voxel, perm, z_sorted, scratch, scratch_bytes, st);
+                 size_t scratch_bytes, hipStream_t st, int sub) {
+    return in_dtype == GLHIP_F32 ? compact_sort_typed<float>(z, n, D, rows_per_voxel, sub, perm, z_sorted, scratch, scratch_bytes, st)
+                                 : compact_sort_typed<bf16_t>(z, n, D, rows_per_voxel, sub, perm, z_sorted, scratch, scratch_bytes, st);
 }
 
 void gather_f32(const float* src, const int32_t* perm, float* dst, int n, hipStream_t st) {
@@ -616,24 +680,26 @@ void slab_ranges(int N, int M, int32_t* ranges_i, int32_t* slices_i, int32_t* re
 }
 
 size_t prune_blocks_bytes(int M) { return (size_t)prune_plan(M).nT * sizeof(ColBlock); }
+size_t prune_groups_bytes(int M) { return (size_t)((M + 31) / 32) * sizeof(GroupBox); }
 
 void prune_ranges(const void* xs, const void* ys, const float* h, const float* pot, float pot_scale, int N, int M, int D, int in_dtype,
-                  float eps, int32_t* ranges_i, int32_t* slices_i, int32_t* red, void* blocks_, hipStream_t st) {
+                  float eps, int32_t* ranges_i, int32_t* slices_i, int32_t* red, void* blocks_, void* groups_, int32_t* home, hipStream_t st) {
     const PrunePlan pp = prune_plan(M);
     const int C = (N + kSortSlab - 1) / kSortSlab;
     ColBlock* blocks = static_cast<ColBlock*>(blocks_);
+    GroupBox* groups = static_cast<GroupBox*>(groups_);
     const double inv2eps = 0.5 / (double)eps;
-    const double L = std::log((double)M) + 26.0 * std::log(2.0) + kPruneMarginNats;
+    const double L = prune_L(M);
     if (in_dtype == GLHIP_F32) {
         hipLaunchKernelGGL(prune_blocks_kernel<float>, dim3((pp.nT + 3) / 4), dim3(256), 0, st, static_cast<const float*>(ys), h, pot, pot_scale, M, D,
-                           pp.nT, blocks);
+                           pp.nT, blocks, groups);
         hipLaunchKernelGGL(prune_slabs_kernel<float>, dim3(C), dim3(256), 0, st, static_cast<const float*>(xs), N, M, D, blocks, pp.nT, pp.PB, pp.S,
-                           inv2eps, L, ranges_i, slices_i, red);
+                           inv2eps, L, ranges_i, slices_i, red, home);
     } else {
         hipLaunchKernelGGL(prune_blocks_kernel<bf16_t>, dim3((pp.nT + 3) / 4), dim3(256), 0, st, static_cast<const bf16_t*>(ys), h, pot, pot_scale, M,
-                           D, pp.nT, blocks);
+                           D, pp.nT, blocks, groups);
         hipLaunchKernelGGL(prune_slabs_kernel<bf16_t>, dim3(C), dim3(256), 0, st, static_cast<const bf16_t*>(xs), N, M, D, blocks, pp.nT, pp.PB,
-                           pp.S, inv2eps, L, ranges_i, slices_i, red);
+                           pp.S, inv2eps, L, ranges_i, slices_i, red, home);
     }
 }
 

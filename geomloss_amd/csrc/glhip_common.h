@@ -42,6 +42,22 @@ struct Ranges {
     const int32_t* chunks;
 };
 
+// Second, in-kernel level of the exact pruning of sorted p = 2 launches (glhip_autosort.h; the test itself: glhip_softmin_x32.h).
+struct GroupBox {           // one aligned group of 32 sorted columns, as four 8-byte parts: the test reads one part per lane
+    float lohi[3][2];       // box corners, (lo, hi) per coordinate (0, 0 beyond D)
+    float hmax;             // largest dual value of the group (-inf: all -inf)
+    int special;            // a non-finite coordinate or a NaN dual value: never skipped
+};
+constexpr int kHomeCols = 256;      // columns of a slab's home block (= kPruneColBlock)
+struct Level2 {
+    const GroupBox* groups = nullptr;   // ceil(M / 32) records
+    const int32_t* home = nullptr;      // per row block (slab): the column block that attains Mlb, -1: no second level for this slab
+    const void* centre_x = nullptr;     // the caller's UNSORTED rows (N, D): launch_centre reads them, so the sorted launch expands its
+                                        // exponents around the very centre of the dense launch of the same call
+    int n_groups = 0;
+    float L2 = 0.f;                     // L of the bound, in log2 units
+};
+
 // One LDS record per column point: D coordinates (already centred / scaled) + one scalar.
 template <int D> struct alignas(16) Rec { float c[4]; };            // D = 2, 3
 template <> struct alignas(8) Rec<1> { float c[2]; };

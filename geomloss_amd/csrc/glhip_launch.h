@@ -48,6 +48,7 @@ struct Scratch {
     bool small_rows;    // GLHIP_FLAG_SMALL_ROW_BLOCKS
     bool h2;            // GLHIP_FLAG_F16X2: exponents from f16 x 2 pieces (glhip_softmin_xd.h) where a kernel has that layout
     ChunkBuf cb;        // block-sparse launches: room for the row-chunk table, carved off the front of the workspace
+    Level2 l2;          // the sorted p = 2 launches of glhip_softmin_fwd / glhip_sinkhorn_step: second pruning level (glhip_softmin_x32.h)
     // pre-packed column records pay for their extra launch from ~5e8 pairs on; they live in the workspace, which
     // GLHIP_FLAG_NO_SPLIT tells us to leave alone
     bool prepack(double pairs) const { return ws && (force_pre || (allow_split && pairs >= prepack_min_pairs())); }
@@ -62,7 +63,7 @@ struct Scratch {
 // columns as before.
 Scratch make_scratch(void* workspace, size_t bytes, int flags, int n_ranges, int N) {
     Scratch sc{workspace, bytes, (flags & GLHIP_FLAG_NO_SPLIT) == 0, (flags & GLHIP_FLAG_PREPACK) != 0,
-               (flags & GLHIP_FLAG_SMALL_ROW_BLOCKS) != 0, (flags & GLHIP_FLAG_F16X2) != 0, ChunkBuf()};
+               (flags & GLHIP_FLAG_SMALL_ROW_BLOCKS) != 0, (flags & GLHIP_FLAG_F16X2) != 0, ChunkBuf(), Level2()};
     if (n_ranges > 0 && workspace) {
         // 64-row workgroups (GLHIP_FLAG_SMALL_ROW_BLOCKS) cut a cluster into twice as many chunks: their table is sized for 64-row tiles
         // (glhip_workspace_bytes reserves that much for every block-sparse call); with less workspace, the 128-row table.
@@ -131,7 +132,11 @@ void launch_softmin_mfma_nw(const SoftminParams<T>& prm, const Ranges& rg, int n
     // block-sparse: one workgroup per row chunk of kRowsPerBlock rows (build_row_chunks_kernel)
     // 4 wavefronts on the 32x32x16 kernel, f16 x 2 layout: chunks of whole groups of 4 row tiles, leftover row tiles carried (glhip_softmin_x32.h)
     // (profiles/r06_carried_tiles_ab.txt)
-    const int share = (NW == 4 && L == XL_F16X2 && n_ranges > 0) ? 1 : 0;
+    // the second pruning level rides on the workgroup shape the sorted launches get (launch_softmin_mfma): f16 x 2 on 4 wavefronts,
+    // bf16 x 3 on 8; its kernel carries no leftover tiles (slabs of 256 rows are whole chunks)
+    constexpr bool kP2Shape = (L == XL_F16X2) ? NW == 4 : NW == 8;
+    const bool p2 = kP2Shape && n_ranges > 0 && sc.l2.groups && sc.l2.home && sc.l2.centre_x;
+    const int share = (NW == 4 && L == XL_F16X2 && n_ranges > 0 && !p2) ? 1 : 0;
     // the number of column splits is still derived from the number of row BLOCKS: deriving it from the (larger) chunk count
     // gives fewer, longer-lived workgroups and measured 3 % slower on uniform clusters (multiscale at 1e6: 258 vs 250 ms)
     SplitLaunch sl(rg, n_ranges, B, N, M, kRowsPerBlock, 2, sc.ws, sc.bytes, sc.cb, st, share);
@@ -153,13 +158,22 @@ void launch_softmin_mfma_nw(const SoftminParams<T>& prm, const Ranges& rg, int n
     PackedCols pk{nullptr, (long)((M + 31) / 32) * (32 * NR)};
     const size_t packed_bytes = (size_t)B * (size_t)pk.stride * sizeof(uint4);   // either layout fits
     const bool pre = sc.prepack((double)B * N * M) && sc.bytes >= sl.packed_offset() + packed_bytes;
+    const bool use_p2 = pre && p2 && !sl.sp.gather;
     if (pre) {
         pk.rec = reinterpret_cast<uint4*>(static_cast<char*>(sc.ws) + sl.packed_offset());
-        if (n_ranges > 0) hipLaunchKernelGGL((pack_columns_kernel<D, T, false, L>), dim3((M + kBlock - 1) / kBlock, B, 1), dim3(kBlock), 0, st, prm, N, M, pk);
+        SoftminParams<T> pprm = prm;      // (the pack kernel reads the rows for the launch's centre only: the one the main kernel takes)
+        if (use_p2) pprm.x = static_cast<const T*>(sc.l2.centre_x);
+        if (n_ranges > 0) hipLaunchKernelGGL((pack_columns_kernel<D, T, false, L>), dim3((M + kBlock - 1) / kBlock, B, 1), dim3(kBlock), 0, st, pprm, N, M, pk);
         else hipLaunchKernelGGL((pack_columns_kernel<D, T, true, L>), dim3((M + 31 + kBlock) / kBlock, B, 1), dim3(kBlock), 0, st, prm, N, M, pk);
     }
     auto main_kernel = [&](auto sparse, dim3 grid, const Ranges& r) {
         constexpr bool SP = decltype(sparse)::value;
+        if constexpr (SP && kP2Shape) {
+            if (use_p2) {
+                hipLaunchKernelGGL((softmin_fwd_x32_p2_kernel<D, T, NW, L>), grid, dim3(NW * 64), 0, st, prm, r, N, M, sl.sp, pk, sc.l2);
+                return;
+            }
+        }
         if (pre) hipLaunchKernelGGL((softmin_fwd_x32_kernel<D, T, SP, 1, NW, true, L>), grid, dim3(NW * 64), 0, st, prm, r, N, M, sl.sp, pk);
         else hipLaunchKernelGGL((softmin_fwd_x32_kernel<D, T, SP, 1, NW, false, L>), grid, dim3(NW * 64), 0, st, prm, r, N, M, sl.sp, PackedCols{nullptr, 0});
     };

@@ -219,10 +219,53 @@ constexpr int fwd_tile(int NW) { return NW == 2 ? 256 : kTileX; }
 
 // The work of one workgroup: row block bx of batch item b, column split `split`.  tileX: kTile * 4 records of LDS,
 // [column group of 32][K block][column], one 16-byte record per (column, K block).
-template <int D, typename T, bool SPARSE, int RT, int NW, bool PRE, int L = XL_BF16X3>
+//
+// P2: the second, finer level of the exact pruning of sorted p = 2 launches (glhip_autosort.h has the first: slabs of 256 rows x blocks
+// of 256 columns, as column intervals).  Inside the kept intervals a wavefront skips whole groups of 32 columns (one MFMA block: 1024
+// exponentials) that cannot matter to any of its 32 rows:
+//   * seed: before the sweep every wavefront takes the EXACT maximum of its rows' exponents over the slab's home block (Level2::home,
+//     the block that attains Mlb: 8 groups, MFMA + max, no exponentials) and starts its running maximum there.  The lazy running
+//     maximum alone is whatever the first 32 columns gave and may sit tens of nats under the row's largest exponent; the seed is an
+//     exponent the row really has, within a few nats of the largest.  The sums over those columns are taken when the sweep reaches them.
+//   * test: per tile, the lanes read the records of the tile's (up to 16) groups (box corners, largest dual value:
+//     prune_blocks_kernel) — lane g + 16 d the (lo, hi) pair of coordinate d of group g, lane g + 48 its dual maximum, so the record costs
+//     two registers while the tile is staged — and bound the group's exponents from above for the wavefront's row box W (reduced once
+//     per row pass and kept in a few bytes of LDS of the wavefront's own):
+//         ub(G) = hmax(G) log2 e - s2 / 2 dmin(W, G)^2      against      thr = min over the rows of (m_i - s2 / 2 |x_i - c|^2) - L log2 e,
+//     m_i - s2 / 2 |x_i - c|^2 being row i's running maximum as a full exponent.  A ballot of "not (ub < thr)" is the mask the group loops
+//     (speculative pass and exact redo alike) walk; thr is recomputed where the running maxima change (seed, redo).
+//   * exactness: m_i never exceeds row i's largest exponent, so every term of a skipped group is below e^-L times a term the row has —
+//     the argument of glhip_autosort.h with the row's own maximum in the place of Mlb; both levels together drop at most M terms of a
+//     row, each under 2^-26 e^-margin / M of its largest: under 2^-26 e^-1 of the row sum.
+//   * rounding: ub and thr are float32 (the first level is float64).  Each side is a difference of two products formed with at most
+//     8 roundings: relative error <= 2^-21 of each product.  Exponents reach ~2.6e5 log2 units under the f16 x 2 contract, where that
+//     is 0.12 log2 units per product — not something to take out of the 1-nat margin, which already pays for the layouts' own error on
+//     the row maximum (0.09 nat).  It is added as explicit slack on the keep side instead: ub is raised by kP2Slack (|hmax log2 e| +
+//     s2 / 2 dmin^2) and every row's exponent lowered by kP2Slack (|m_i| + s2 / 2 |x_i - c|^2), kP2Slack = 2^-20 (twice the bound).
+//   * special values: a group with a non-finite coordinate or a NaN dual value is marked and never skipped; a slab with a non-finite
+//     coordinate or without a finite Mlb has home = -1: no seed, no test, the code path of the first level alone.  So has a slab whose
+//     first level keeps every block (large eps): the test would pass nearly every group and cost ~2 % of the sweep.  The skip is the
+//     comparison `ub < thr` being TRUE: a NaN on either side keeps the group; a row whose running maximum is not finite sets
+//     thr = -inf for its wavefront.
+//   * centre: the sorted launch expands its exponents around launch_centre of the caller's UNSORTED rows (Level2::centre_x), the centre
+//     of the dense launch of the same call: pruned and dense results differ by the summation order alone (~1e-8 at the headline law),
+//     and non-finite coordinates, whose NaN / infinity pattern depends on the side of the centre a row lies on, give the same pattern.
+//   Launches without Level2 (P2 = false: everything but the sorted p = 2 path) compile to what they were.
+constexpr float kP2Slack = 9.5367431640625e-7f;      // 2^-20
+
+__device__ __forceinline__ float wave_min_uniform(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off, 64));
+    return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v)));
+}
+__device__ __forceinline__ float wave_max_uniform(float v) { return -wave_min_uniform(-v); }
+
+template <int D, typename T, bool SPARSE, int RT, int NW, bool PRE, int L = XL_BF16X3, bool P2 = false>
 __device__ __forceinline__ void softmin_fwd_x32_body(const SoftminParams<T>& prm, const Ranges& rg, int N, int M,
                                                      const SplitInfo& sp, const PackedCols& pk, int bx, int b, int split,
-                                                     uint4* tileX) {
+                                                     uint4* tileX, const Level2& l2 = Level2(), float2* wbox = nullptr) {
+    static_assert(!P2 || (SPARSE && PRE && RT == 1), "the second pruning level serves the sorted launches: block-sparse, pre-packed columns");
+    static_assert(!P2 || fwd_tile(NW) == 512, "the test reads the records of a tile's 16 groups with 4 lanes each");
     constexpr int kRowsPerWave = RT * 32;
     constexpr int kRowsPerBlock = NW * kRowsPerWave;
     constexpr int kThreads = NW * 64;
@@ -237,7 +280,8 @@ __device__ __forceinline__ void softmin_fwd_x32_body(const SoftminParams<T>& prm
     // build_row_chunks_kernel): every wavefront reduces its own row tile against all the column groups of a tile and the leftover
     // row tile against every 4th group — 1.25 row tiles of work per wavefront, none of them idle.  (Up to 3 leftover tiles per
     // workgroup were tried: 22-25 more VGPRs per slot, 150 in all, 3 waves per SIMD.)
-    constexpr int XS = (SPARSE && RT == 1 && NW == 4 && L == XL_F16X2) ? 1 : 0;      // (bf16 x 3: 94 -> 122 VGPRs and spills; left alone)
+    // (P2: slabs of 256 rows are two whole chunks — nothing to carry but the cloud's last rows; the slot's registers serve the test)
+    constexpr int XS = (SPARSE && RT == 1 && NW == 4 && L == XL_F16X2 && !P2) ? 1 : 0;      // (bf16 x 3: 94 -> 122 VGPRs and spills; left alone)
     constexpr int NS = RT + XS;                     // row-tile slots of a wavefront: [0, RT) its own, [RT, NS) the shared leftovers
 
     const int tid = threadIdx.x;
@@ -272,13 +316,18 @@ __device__ __forceinline__ void softmin_fwd_x32_body(const SoftminParams<T>& prm
         }
     }
     const int nx = XS > 0 ? (xe - xb + 31) >> 5 : 0;      // leftover row tiles of this workgroup (wave-uniform; > 0 only beside a full chunk)
+    int home = -1;      // P2: the home column block of this workgroup's slab (workgroup-uniform); -1: first level only
+    if constexpr (P2) {
+        // a tile's group g is the global group (j0 >> 5) + g only while a tile is one piece of one interval
+        if (row_begin < row_end && !sp.gather) home = l2.home[(rg.chunks && rg.chunks[0] >= 0) ? rg.chunks[1 + 3 * bx] : bx];
+    }
 
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const uint4 kOnes = uint4{0x3F803F80u, 0x00003F80u, 0u, 0u};   // [1,1,1,0,...]: block 3 with n = 0
 
     for (int row0 = row_begin; row0 < row_end; row0 += kRowsPerBlock) {
         float centre[D];
-        if (PRE) launch_centre<D, T>(prm.x, b, N, centre);
+        if (PRE) launch_centre<D, T>(P2 ? static_cast<const T*>(l2.centre_x) : prm.x, b, N, centre);
         else load_point<D, T>(prm.x, (long)b * N + row0, centre);
 
         // block-sparse: the wavefront -> rows assignment is rotated by the chunk index (the empty slots of successive partial chunks
@@ -330,6 +379,35 @@ __device__ __forceinline__ void softmin_fwd_x32_body(const SoftminParams<T>& prm
         }
         const bool wave_active = wave_row0 < row_end;
         bool first_group = true, first_shared = true;
+        // P2: the wavefront's row box (in LDS, wbox[wavefront][coordinate] = (lo, hi): only this wavefront reads it) and the threshold of the test
+        float thr = -INFINITY;
+        const int part = lane >> 4;      // which 8 bytes of a group's record this lane reads
+        if constexpr (P2) {
+            if (home >= 0 && wave_active) {
+                float xi[D];
+                load_point<D, T>(prm.x, (long)b * N + min(wave_row0 + l31, row_end - 1), xi);
+#pragma unroll
+                for (int d = 0; d < D; ++d) {
+                    const float lo = wave_min_uniform(xi[d]), hi = wave_max_uniform(xi[d]);
+                    if (lane == d) wbox[wave * 4 + d] = float2{lo, hi};
+                }
+                if (lane >= D && lane < 4) wbox[wave * 4 + lane] = float2{0.f, 0.f};
+            }
+        }
+        auto row_threshold = [&]() {      // from the running maxima as they stand (rare: the rows are loaded again)
+            float xi[D];
+            load_point<D, T>(prm.x, (long)b * N + min(wave_row0 + l31, row_end - 1), xi);
+            float n2 = 0.f;
+#pragma unroll
+            for (int d = 0; d < D; ++d) {
+                const float xt = xi[d] - centre[d];
+                n2 = __builtin_fmaf(xt, xt, n2);
+            }
+            const float rowoff = 0.5f * prm.s2 * n2;      // m - rowoff: the running maximum as a full exponent (write_row)
+            const float full = m[0] - rowoff;
+            const float low = __builtin_isfinite(full) ? full - kP2Slack * (__builtin_fabsf(m[0]) + rowoff) : -INFINITY;
+            return wave_min_uniform(low) - l2.L2;
+        };
 
         // PRE: the records of the next tile are fetched into registers while the current tile is consumed
         u32x4 pre[kPer];
@@ -366,6 +444,40 @@ __device__ __forceinline__ void softmin_fwd_x32_body(const SoftminParams<T>& prm
                 for (int kb = 0; kb < NR; ++kb) pre[k * NR + kb] = col[kb];
             }
         };
+        if constexpr (P2) {
+            if (home >= 0) {      // (workgroup-uniform) exact row maxima over the home block: where the running maxima start
+                const int hj0 = home * kHomeCols, hn = min(kHomeCols, M - hj0);
+                __syncthreads();                                  // (a previous row pass may still be reading the tile buffer)
+                for (int t = tid; t < kHomeCols; t += kThreads) {
+                    const bool real = t < hn;
+                    const u32x4* col = reinterpret_cast<const u32x4*>(pk.rec + ((long)b * M + hj0 + (real ? t : 0)) * NR);
+                    u32x4* dst = reinterpret_cast<u32x4*>(&tileX[(t >> 5) * GS + (t & 31)]);
+#pragma unroll
+                    for (int kb = 0; kb < NR; ++kb) dst[kb * 32] = real ? col[kb] : neutral[kb];
+                }
+                __syncthreads();
+                if (wave_active) {
+                    float um = kFloor;
+                    for (int G = 0; G < kHomeCols / 32; ++G) {      // (n = 0 so far: plain exponents)
+                        f32x16 u;
+                        if constexpr (H2) {
+                            u = mfma_h32(tileX[G * GS + rec0], Xlo[0], zero16);
+                        } else {
+                            u = mfma_x32(tileX[G * GS + rec0], Xlo[0], zero16);
+                            u = mfma_x32(tileX[G * GS + 64 + rec0], Xhi[0], u);
+                        }
+                        um = fmaxf(um, max16(u));
+                    }
+                    um = fmaxf(um, __shfl_xor(um, 32, 64));
+                    m[0] = um;
+                    if constexpr (H2) Xlo[0] = select_u4(half == 0, xd_with_n<L>(Xlo[0], -um), Xlo[0]);
+                    else if (half) Xhi[0] = pack_negmax(um);
+                    first_group = false;
+                    thr = row_threshold();
+                }
+            }
+        }
+
         if (GATHER) {
             if (cur.q < q_end) {
                 gnext = gather_tile<kCols, kThreads, kTile>(rg, M, q_end, split, ns, cur, tid, gcols, gn, pieces);
@@ -378,6 +490,11 @@ __device__ __forceinline__ void softmin_fwd_x32_body(const SoftminParams<T>& prm
         while (cur.q < q_end) {
             {
                 const int j0 = cur.j0;
+                // P2: the records of this tile's groups, asked for before the barriers and the staging
+                float2 gb = float2{0.f, 0.f};
+                if constexpr (P2) {
+                    if (home >= 0) gb = reinterpret_cast<const float2*>(l2.groups + min((j0 >> 5) + (lane & 15), l2.n_groups - 1))[part];
+                }
                 if (GATHER_NOW) gnext = gather_tile<kCols, kThreads, kTile>(rg, M, q_end, split, ns, cur, tid, gcols, gn, pieces);
                 const int n = (GATHER || GATHER_NOW) ? gn : min(kTile, cur.je - j0);
                 const int npad = (n + 31) & ~31;
@@ -434,6 +551,22 @@ __device__ __forceinline__ void softmin_fwd_x32_body(const SoftminParams<T>& prm
 
                 const int nG = npad / 32;
                 int G0 = cpart;
+                unsigned long long keep = ~0ull;      // P2: the groups of this tile that may matter to this wavefront's rows
+                if constexpr (P2) {
+                    if (home >= 0 && (j0 & 31) == 0) {
+                        // parts 0-2: the squared gap of one coordinate (beyond D both boxes are 0: no gap); part 3 adds nothing
+                        const float2 wb = wbox[wave * 4 + part];
+                        const float gap = part < 3 ? fmaxf(fmaxf(gb.x - wb.y, wb.x - gb.y), 0.f) : 0.f;
+                        float d2 = gap * gap;
+                        d2 += __shfl_xor(d2, 16, 64);
+                        d2 += __shfl_xor(d2, 32, 64);
+                        const float hmax = __shfl(gb.x, 48 + (lane & 15), 64);
+                        const int special = __shfl(__float_as_int(gb.y), 48 + (lane & 15), 64);
+                        const float hm2 = hmax * kLog2e, q = 0.5f * prm.s2 * d2;
+                        const float ub = (hm2 - q) + kP2Slack * (fminf(__builtin_fabsf(hm2), 3.0e38f) + q);
+                        keep = __ballot(lane >= nG || special != 0 || !(ub < thr));
+                    }
+                }
                 // one 32 x 32 block of exponents: column group G against row tile rt (`plain`: with n = 0, for the exact maxima)
                 auto block = [&](int G, int rt, bool plain) -> f32x16 {
                     if constexpr (H2) {
@@ -485,9 +618,17 @@ __device__ __forceinline__ void softmin_fwd_x32_body(const SoftminParams<T>& prm
                 float stmp[NS];
 #pragma unroll
                 for (int rt = 0; rt < NS; ++rt) stmp[rt] = 0.f;
-                for (int G = G0; G < nG; G += cs) {
+                // P2, a slab under test: this wavefront's groups G0, G0 + cs, ... < nG that passed, as a bit set (scalar loop control); slabs
+                // without a second level keep the counted loop, whose LDS reads the compiler pipelines across groups (bf16 x 3: 4 % of the sweep)
+                if (P2 && home >= 0) {
+                    const unsigned long long lanes = cs == 1 ? ~0ull : (cs == 2 ? 0x5555555555555555ull : 0x1111111111111111ull) << cpart;
+                    keep &= lanes & ((1ull << nG) - 1ull) & ~((1ull << G0) - 1ull);
+                    for (unsigned long long todo = keep; todo; todo &= todo - 1ull) stmp[0] += sum_exp2_16(block(__builtin_ctzll(todo), 0, false));
+                } else {
+                    for (int G = G0; G < nG; G += cs) {
 #pragma unroll
-                    for (int rt = 0; rt < RT; ++rt) stmp[rt] += sum_exp2_16(block(G, rt, false));
+                        for (int rt = 0; rt < RT; ++rt) stmp[rt] += sum_exp2_16(block(G, rt, false));
+                    }
                 }
                 if (XS > 0 && nx > 0 && !first_shared) {
                     for (int G = GX0; G < nG; G += 4) {
@@ -504,9 +645,13 @@ __device__ __forceinline__ void softmin_fwd_x32_body(const SoftminParams<T>& prm
                 for (int rt = 1; rt < NS; ++rt) smax = fmaxf(smax, stmp[rt]);
                 if (__any(!(smax < kSumThr))) {
                     // a term far above the lazy max arrived (or inf / NaN): redo the tile with exact per-group maxima
-                    for (int G = G0; G < nG; G += cs) {
+                    if (P2 && home >= 0) {
+                        for (unsigned long long todo = keep; todo; todo &= todo - 1ull) group_exact(__builtin_ctzll(todo), 0);
+                    } else {
+                        for (int G = G0; G < nG; G += cs) {
 #pragma unroll
-                        for (int rt = 0; rt < RT; ++rt) group_exact(G, rt);
+                            for (int rt = 0; rt < RT; ++rt) group_exact(G, rt);
+                        }
                     }
                     if (XS > 0 && nx > 0 && !first_shared) {
                         for (int G = GX0; G < nG; G += 4) {
@@ -518,6 +663,9 @@ __device__ __forceinline__ void softmin_fwd_x32_body(const SoftminParams<T>& prm
 #pragma unroll
                     for (int rt = 0; rt < NS; ++rt)      // (a leftover slot that has seen no group yet keeps n = 0 for its first, exact one)
                         if (rt < RT || (rt - RT < nx && !first_shared)) set_max(rt, m[rt]);
+                    if constexpr (P2) {
+                        if (home >= 0) thr = row_threshold();
+                    }
                 } else {
 #pragma unroll
                     for (int rt = 0; rt < NS; ++rt) ssum[rt] += stmp[rt];
@@ -615,6 +763,21 @@ softmin_fwd_x32_kernel(SoftminParams<T> prm, Ranges rg, int N, int M, SplitInfo 
     int bx, b, split;
     workgroup_coords(sp, bx, b, split);
     softmin_fwd_x32_body<D, T, SPARSE, RT, NW, PRE, L>(prm, rg, N, M, sp, pk, bx, b, split, tileX);
+}
+
+// the sorted p = 2 launches: block-sparse, pre-packed columns, with the second pruning level (P2 above)
+// Occupancy as without P2: 5 wavefronts per SIMD for the 4-wavefront f16 x 2 kernel (96 VGPRs, no scratch), 6 for the 8-wavefront
+// bf16 x 3 one — three workgroups per CU; at 5 (two workgroups) it measured 101 against 88 ms where nothing prunes.  The bound of 80
+// VGPRs costs that kernel 32-60 bytes of scratch per lane (D = 3: 32-40): written in the prologue, read back in the seed pass, once
+// per tile in the test and in the epilogue, never inside the group loops (profiles/r09_kernel_resources.txt).
+template <int D, typename T, int NW, int L>
+__global__ void __launch_bounds__(NW * 64, NW == 4 ? 5 : (NW == 8 ? 6 : 1))
+softmin_fwd_x32_p2_kernel(SoftminParams<T> prm, Ranges rg, int N, int M, SplitInfo sp, PackedCols pk, Level2 l2) {
+    __shared__ uint4 tileX[fwd_tile(NW) * X32Layout<L>::NR];
+    __shared__ float2 wbox[NW * 4];
+    int bx, b, split;
+    workgroup_coords(sp, bx, b, split);
+    softmin_fwd_x32_body<D, T, true, 1, NW, true, L, true>(prm, rg, N, M, sp, pk, bx, b, split, tileX, l2, wbox);
 }
 
 // Up to four independent dense reductions in ONE launch — the four soft-mins of a Sinkhorn iteration

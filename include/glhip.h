@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 121 /* 0.1.21 */
+#define GLHIP_VERSION 122 /* 0.1.22 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
@@ -102,7 +102,12 @@ extern "C" {
                                   1-nat margin covers the f16 x 2 exponent error).  Non-finite inputs behave as in the dense launch (their
                                   blocks / slabs keep everything).  The kept blocks run on the block-sparse kernel (either exponent layout),
                                   results return in the caller's order, with no host synchronisation.  Headline law at 1e6 x 1e6
-                                  (eps = 0.05^2): 36 % of the pairs kept, 81 -> 35 ms.  Here this flag means the dense xd / x32 launch. */
+                                  (eps = 0.05^2): 36 % of the pairs kept, 81 -> 35 ms.  Version 122: a second level of the same bound inside
+                                  the reducing kernel — every wavefront skips the groups of 32 columns that cannot matter to its own 32 rows,
+                                  against their running maxima seeded with exact maxima over the slab's best block (csrc/glhip_softmin_x32.h,
+                                  P2); both clouds are ordered in voxels of 256 points with compact sub-voxels inside.  Same guarantee (both
+                                  levels together drop < 2^-26 of a row sum); headline law: 35 -> 24 ms (profiles/r09_*).
+                                  Here this flag means the dense xd / x32 launch. */
 
 /* Environment variables read ONCE per process by the library itself (test / tuning knobs; everything else is an argument):
  *   GLHIP_FWD_NW = 2 | 4 | 8  force the workgroup height (wavefronts) of the soft-min forward kernels instead of the size heuristic

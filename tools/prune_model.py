@@ -9,7 +9,13 @@ into slabs of 256, columns into blocks of 256, the float64 bound
 and counts the kept pairs and the runs of kept blocks per slab.  ``check_dropped`` verifies on the points themselves that no dropped
 block holds a term above Mlb(R) - L for any row of the slab (tests/test_prune_model.py).
 
-    python tools/prune_model.py [--n 1000000] [--eps 0.0025]     (the bench problem: bench.make_problem(n, seed=1000))
+The second level (csrc/glhip_softmin_x32.h, P2) is modelled by ``level2``: inside the kept blocks, every 32-row wavefront tile tests
+every group of 32 columns against its rows' exact maxima over the slab's home block (the block that attains Mlb) and evaluates only
+the groups that pass; ``compact_order2`` is the order of the sorted p = 2 call (voxels of 256 points for both clouds, a minor key of
+sub-voxels inside).  ``level2`` also verifies on the points themselves that no skipped pair holds a term above its row's true
+maximum - L.  The model's test is exact arithmetic; the kernel's float32 test keeps a little more (its slack is on the keep side).
+
+    python tools/prune_model.py [--n 1000000] [--eps 0.0025] [--slabs 40]     (the bench problem: bench.make_problem(n, seed=1000))
 """
 
 import argparse
@@ -39,6 +45,38 @@ def compact_order(z, rows_per_voxel):
         c = np.where(path & np.uint64(1), e[d] - 1 - q, q).astype(np.uint64)
         path = path * np.uint64(e[d]) + c
     return np.argsort(path, kind="stable")
+
+
+def compact_order2(z, rows_per_voxel, sub):
+    """compact_order with the minor key of path_keys_kernel (sub > 1): inside a voxel, sub-voxels of edge voxel / sub along a
+    boustrophedon path of their own"""
+    z = np.asarray(z, np.float32)
+    n, D = z.shape
+    lo, hi = z.min(0), z.max(0)
+    ext = (hi - lo).astype(np.float32)
+    emax = float(ext.max())
+    live = ext > np.float32(1e-6) * np.float32(max(emax, 1e-30))
+    vol = np.float32(np.prod(ext[live])) if live.any() else np.float32(1.0)
+    voxel = np.float32(np.power(np.float32(vol * np.float32(rows_per_voxel) / np.float32(n)), np.float32(1.0 / max(int(live.sum()), 1))))
+    voxel = np.float32(max(voxel, np.float32(emax / 2**20), np.float32(1e-30)))
+    qmin = np.floor(lo / voxel).astype(np.int64)
+    e = np.floor((lo + ext) / voxel).astype(np.int64) - qmin + 1
+    path = np.zeros(n, np.uint64)
+    minor = np.zeros(n, np.uint64)
+    for d in range(D):
+        f = (z[:, d] / voxel).astype(np.float32)
+        fl = np.floor(f)
+        q = np.clip(fl.astype(np.int64) - qmin[d], 0, e[d] - 1)
+        c = np.where(path & np.uint64(1), e[d] - 1 - q, q).astype(np.uint64)
+        path = path * np.uint64(e[d]) + c
+        r = np.clip(((f - fl) * np.float32(sub)).astype(np.int64), 0, sub - 1)
+        minor = minor * np.uint64(sub) + np.where(minor & np.uint64(1), sub - 1 - r, r).astype(np.uint64)
+    return np.argsort(path * np.uint64(sub**D) + minor, kind="stable")
+
+
+def sort_sub(D):
+    """glhip_autosort.h: prune_sort_sub"""
+    return 2 if D >= 3 else (3 if D == 2 else 8)
 
 
 def boxes(z, size):
@@ -98,6 +136,52 @@ def check_dropped(xs, ys, h, eps, keep, mlb, L, slabs):
     return worst
 
 
+TILE, GROUP = 32, 32
+
+
+def level2(xs, ys, h, eps, keep, L, slabs, check=False):
+    """The second level on the given slabs.  Returns (pairs whose exponential is evaluated, pairs kept by the first level, worst), where
+    worst (check=True) is the largest (term - (true row maximum - L)) over the pairs the second level skips, exact float64; < 0 means
+    the bound held.  The running maximum of a row is modelled by its seed (the kernel's only rises)."""
+    M, D = ys.shape
+    x64, y64, h64 = xs.astype(np.float64), ys.astype(np.float64), h.astype(np.float64)
+    rlo, rhi = boxes(xs, SLAB)
+    blo, bhi = boxes(ys, BLOCK)
+    glo, ghi = boxes(ys, GROUP)
+    nT, nG = blo.shape[0], glo.shape[0]
+    hmax = np.concatenate([h64, np.full(nT * BLOCK - M, -np.inf)]).reshape(nT, BLOCK).max(1)
+    ghmax = np.concatenate([h64, np.full(nG * GROUP - M, -np.inf)]).reshape(nG, GROUP).max(1)
+    gcols = np.minimum(GROUP, M - GROUP * np.arange(nG))
+    evaluated = kept1 = 0.0
+    worst = -np.inf
+    for c in slabs:
+        far = np.maximum(bhi - rlo[c], rhi[c] - blo)
+        home = int(np.argmax(hmax - (far**2).sum(-1) / (2 * eps)))
+        hc = np.arange(home * BLOCK, min(M, (home + 1) * BLOCK))
+        groups = np.concatenate([np.arange(t * (BLOCK // GROUP), min(nG, (t + 1) * (BLOCK // GROUP))) for t in np.flatnonzero(keep[c])])
+        r1 = min(xs.shape[0], (c + 1) * SLAB)
+        for w0 in range(c * SLAB, r1, TILE):
+            xr = x64[w0:min(w0 + TILE, r1)]
+            seed = (h64[hc][None] - ((xr[:, None, :] - y64[hc][None]) ** 2).sum(-1) / (2 * eps)).max(1)
+            thr = seed.min() - L
+            wlo, whi = xr.min(0), xr.max(0)
+            gap = np.maximum(np.maximum(glo[groups] - whi, wlo - ghi[groups]), 0.0)
+            k2 = ghmax[groups] - (gap**2).sum(-1) / (2 * eps) >= thr
+            evaluated += float(gcols[groups][k2].sum()) * xr.shape[0]
+            kept1 += float(gcols[groups].sum()) * xr.shape[0]
+            if check:
+                true_max = np.full(xr.shape[0], -np.inf)
+                for j0 in range(0, M, 65536):
+                    yy, hh = y64[j0:j0 + 65536], h64[j0:j0 + 65536]
+                    true_max = np.maximum(true_max, (hh[None] - ((xr[:, None, :] - yy[None]) ** 2).sum(-1) / (2 * eps)).max(1))
+                gone = groups[~k2]
+                if gone.size:
+                    cols = np.concatenate([np.arange(g * GROUP, min(M, (g + 1) * GROUP)) for g in gone])
+                    terms = h64[cols][None] - ((xr[:, None, :] - y64[cols][None]) ** 2).sum(-1) / (2 * eps)
+                    worst = max(worst, float((terms - (true_max - L)[:, None]).max()))
+    return evaluated, kept1, worst
+
+
 def bench_problem(n, seed=1000):
     """bench.make_problem(n, seed) without torch's device copy (same generator calls, same values)"""
     import torch
@@ -114,6 +198,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1000000)
     ap.add_argument("--eps", type=float, nargs="*", default=[0.01**2, 0.05**2, 0.2**2, 1.0])
+    ap.add_argument("--slabs", type=int, default=40, help="slabs sampled for the second level (0: first level only)")
     a = ap.parse_args()
     x, y, h, _ = bench_problem(a.n)
     px, py = compact_order(x, 256), compact_order(y, 512)
@@ -124,6 +209,22 @@ def main():
         frac = kept_pairs(keep, a.n, a.n) / (float(a.n) * a.n)
         print(f"n = {a.n}  eps = {eps:.4g}: L = {L:.2f} nats, kept pairs {frac:.4f}, kept blocks per slab {keep.sum(1).mean():.0f} of {keep.shape[1]}, "
               f"runs per slab mean {r.mean():.1f} max {r.max()}, slabs over {RUNS} runs {(r > RUNS).sum()}", flush=True)
+    if a.slabs <= 0:
+        return
+    # the sorted p = 2 call: voxels of 256 points for both clouds; with and without the minor key
+    for sub in (1, sort_sub(3)):
+        px, py = compact_order2(x, 256, sub), compact_order2(y, 256, sub)
+        xs, ys, hs = x[px], y[py], h[py]
+        C = (a.n + SLAB - 1) // SLAB
+        slabs = np.unique(np.linspace(0, C - 1, a.slabs).astype(int))
+        rows = float(sum(min(a.n, (c + 1) * SLAB) - c * SLAB for c in slabs))
+        for eps in a.eps:
+            keep, mlb, L = plan(xs, ys, hs, eps)
+            r = runs_per_slab(keep)
+            ev, k1, _ = level2(xs, ys, hs, eps, keep, L, slabs)
+            print(f"two levels, voxels 256 / 256, sub {sub}: n = {a.n}  eps = {eps:.4g}: first level keeps {kept_pairs(keep, a.n, a.n) / (float(a.n) * a.n):.4f} "
+                  f"(runs per slab mean {r.mean():.1f} max {r.max()}); on {len(slabs)} slabs: first level {k1 / (rows * a.n):.4f}, "
+                  f"evaluated after the second {ev / (rows * a.n):.4f}", flush=True)
 
 
 if __name__ == "__main__":
