@@ -119,6 +119,7 @@ static int sorted_inner(const AutoSort& a, const void* x, const float* h, int N,
     if (p == 2) {
         sc.l2.groups = static_cast<const GroupBox*>(a.groups);
         sc.l2.home = a.home;
+        sc.l2.t2 = a.t2;
         sc.l2.centre_x = x;
         sc.l2.n_groups = (M + 31) / 32;
         sc.l2.L2 = (float)(prune_L(M) * 1.4426950408889634);
@@ -158,7 +159,7 @@ int glhip_softmin_fwd(const void* x, const void* y, const float* h, float* out, 
         if (a.on) {
             gather_f32(h, a.perm_y, a.col0, M, st);
             if (p == 2)
-                prune_ranges(a.xs, a.ys, a.col0, nullptr, 0.f, N, M, D, in_dtype, eps, a.ranges_i, a.slices_i, a.red, a.blocks, a.groups, a.home, st);
+                prune_ranges(a.xs, a.ys, a.col0, nullptr, 0.f, N, M, D, in_dtype, eps, a.ranges_i, a.slices_i, a.red, a.blocks, a.groups, a.home, a.t2, a.mlb, a.t1, st);
             rc = sorted_inner(a, x, a.col0, N, M, D, eps, p, in_dtype, flags, st);
             if (rc) return rc;
             scatter_f32(a.out, a.perm_x, out, N, st);
@@ -197,7 +198,7 @@ int glhip_sinkhorn_step(const void* x, const void* y, const float* logw, const f
             // (the bound takes the column vector the kernels form: logw + pot / eps)
             if (p == 2)
                 prune_ranges(a.xs, a.ys, a.col0, pot ? a.col1 : nullptr, 1.0f / eps, N, M, D, in_dtype, eps, a.ranges_i, a.slices_i, a.red, a.blocks,
-                             a.groups, a.home, st);
+                             a.groups, a.home, a.t2, a.mlb, a.t1, st);
             StepArgs inner_step;
             inner_step.pot = pot ? a.col1 : nullptr;
             inner_step.prev = prev ? a.row0 : nullptr;
@@ -219,6 +220,40 @@ int glhip_sinkhorn_step(const void* x, const void* y, const float* logw, const f
              ? softmin_typed<false, float>(x, y, logw, out, nullptr, nullptr, nullptr, B, N, M, D, eps, p, rg, n_ranges, sc, flags, st, step)
              : softmin_typed<false, bf16_t>(x, y, logw, out, nullptr, nullptr, nullptr, B, N, M, D, eps, p, rg, n_ranges, sc, flags, st, step);
     return rc ? rc : check_launch("glhip_sinkhorn_step");
+}
+
+int glhip_prune_inspect_slots(int M) { return M > 0 ? prune_plan(M).S : GLHIP_EINVAL; }
+
+int glhip_prune_inspect(const void* x, const void* y, const float* logw, const float* pot, int N, int M, int D, float eps, int in_dtype,
+                        int32_t* perm_x, int32_t* perm_y, double* mlb, double* t1, int32_t* home, int32_t* intervals, float* t2,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "glhip_prune_inspect";
+    int rc = check_common(fn, x, y, logw, 1, N, M, D, in_dtype, nullptr, nullptr, nullptr, 0);
+    if (rc) return rc;
+    if (!(eps > 0.f)) return fail(GLHIP_EINVAL, "%s: eps must be > 0", fn);
+    if (!softmin_sorts(1, N, M, D, 2, 0, 0))
+        return fail(GLHIP_EUNSUPPORTED, "%s: a p = 2 call of this shape is not pruned (N = %d, M = %d, D = %d)", fn, N, M, D);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    AutoSort a;
+    const int C = (N + kSortSlab - 1) / kSortSlab;
+    rc = autosort_prepare(a, x, y, N, M, D, in_dtype, workspace, workspace_bytes, glhip_workspace_bytes(1, N, M, D, C), st, false);
+    if (rc) return rc;
+    if (!a.on) return fail(GLHIP_EINVAL, "%s: needs a workspace of glhip_workspace_bytes(1, N, M, D, 0)", fn);
+    gather_f32(logw, a.perm_y, a.col0, M, st);
+    if (pot) gather_f32(pot, a.perm_y, a.col1, M, st);
+    // -inf marks the thresholds of the tiles no kernel writes (slabs without a home block)
+    if (hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a.t2), (int)0xFF800000u, (size_t)((N + 31) / 32), st) != hipSuccess)
+        return fail(GLHIP_ELAUNCH, "%s: memset failed: %s", fn, hipGetErrorString(hipGetLastError()));
+    prune_ranges(a.xs, a.ys, a.col0, pot ? a.col1 : nullptr, 1.0f / eps, N, M, D, in_dtype, eps, a.ranges_i, a.slices_i, a.red, a.blocks, a.groups,
+                 a.home, a.t2, a.mlb, a.t1, st);
+    auto copy = [&](void* dst, const void* src, size_t bytes) {
+        return !dst || hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st) == hipSuccess;
+    };
+    const bool ok = copy(perm_x, a.perm_x, (size_t)N * 4) && copy(perm_y, a.perm_y, (size_t)M * 4) && copy(mlb, a.mlb, (size_t)C * 8) &&
+                    copy(t1, a.t1, (size_t)C * 8) && copy(home, a.home, (size_t)C * 4) &&
+                    copy(intervals, a.red, (size_t)C * prune_plan(M).S * 8) && copy(t2, a.t2, (size_t)((N + 31) / 32) * 4);
+    if (!ok) return fail(GLHIP_ELAUNCH, "%s: copy failed: %s", fn, hipGetErrorString(hipGetLastError()));
+    return check_launch(fn);
 }
 
 int glhip_sinkhorn_iter4(const void* x, const void* y, const float* a_log, const float* b_log, const float* f_ba,

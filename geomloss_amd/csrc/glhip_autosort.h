@@ -48,10 +48,39 @@ constexpr int kSortRowsPerVoxel = 256;
 //   lack of a finite bound or because every block passes it — no second level, no cost of it, for such a slab).  The sorted p = 2 call orders both clouds in voxels of kSortRowsPerVoxel
 //   points with a minor key of sub-voxels of ~32 points (prune_sort_sub), so that 32 consecutive points are compact; the distance
 //   launches (p = 1, laplacian, energy) keep the order they had.
+//   Mass rule (round 10).  Both tests above pay ln M of their L for the case that all M columns sit exactly at the threshold.  What the
+//   guarantee needs is that the SUM of everything dropped stays under 2^-26 of the row sum, and that sum is bounded from the records:
+//   with lse(S) = log sum_{j in S} e^(h_j) and pen(A, S) = dmin(A, S)^2 / (2 eps), the terms of a set S of columns sum to at most
+//   e^(lse(S) - pen(A, S)) for every row in the box A.  The 2^-26 is split three ways, each piece with its own proof:
+//     first level, 2^-26 / e of e^Mlb(R): a block T has the key k(T) = lse(T) - pen(R, T); prune_slabs_kernel finds the largest threshold
+//       t1(R) such that the masses e^(k(T) - Mlb(R)) of the blocks with k(T) < t1 sum to at most the budget, and keeps T iff k(T) >= t1(R)
+//       (or T is special, or the slab keeps everything).  Mlb and the home block are what they were: Mlb is a term the row really has.
+//     second level, term rule, 2^-26 / e: the kernel's test against the rows' running maxima, unchanged (at most M terms, each under
+//       e^-L of the row's largest).  The group records hold lse(G) in the place of hmax(G): lse >= hmax, the test stays valid.
+//     second level, mass rule, 2^-26 (1 - 2 / e) of e^ms(W), ms(W) the smallest of the exact largest exponents of the tile's 32 rows
+//       over the home block (each of them a term its row really has): prune_tiles_kernel finds, over the groups inside the slab's
+//       emitted intervals, the largest t2(W) such that the masses e^(k(W, G) - ms(W)) of the groups with k(W, G) = lse(G) - pen(W, G)
+//       < t2 sum to at most the budget; the kernel's threshold is max(term rule's, t2(W)).
+//   Thresholds come from histograms, not sorts: kPruneBuckets buckets of kPruneBucketNats from the term rule's threshold (Mlb - L,
+//   ms - L) up, each holding the actual mass of its keys; keys below the range share an underflow bucket that is always counted (and
+//   can never exceed a budget by itself: glhip_cluster.hip, prune_first_kept), keys above it are never dropped; the threshold is the
+//   lower edge of the first bucket at which the running sum passes the budget.  Rounding: the first level and t2 are float64 from the
+//   exact float32 corners; lse is a float32 rounded UP (kPruneLseSlack); t2 is stored in log2 units as a float32 rounded toward minus
+//   infinity; the kernel's ub carries its slack on the keep side.  Special blocks and groups are never dropped and enter no sum; a
+//   slab with home = -1 gets no threshold work; a tile without a finite seed gets t2 = -inf.  The thresholds live in the sort scratch.
+//   Headline law at 1e6: tools/prune_model.py, profiles/r10_*.
 constexpr int kPruneColBlock = 256;   // columns per column block T (a multiple of 64)
-constexpr int kPruneRuns = 160;       // runs of kept blocks per slab (the bench problem: mean 66, max 143 at 256 columns per block)
+constexpr int kPruneRuns = 160;       // runs of kept blocks per slab (the bench problem under the mass rule: mean 71, max 175 — 8 of 3907 slabs
+                                      // close their one-block gaps, 0.01 % more kept pairs: profiles/r10_prune_model.txt)
 constexpr int kPruneGrid = 64;        // pieces a whole row of column blocks is cut into, at most
 constexpr double kPruneMarginNats = 1.0;
+// The mass rule (round 10): thresholds are found on histograms of the keys, kPruneBuckets buckets of kPruneBucketNats starting at the
+// classic threshold.  28 nats cover ln M + 4 for every M an int holds (ln 2^31 = 21.5).  The budgets: the row sum may lose 2^-26 in
+// all — 2^-26 / e by the first level, 2^-26 / e by the term rule of the second, the rest by the mass rule of the second.
+constexpr int kPruneBuckets = 112;
+constexpr double kPruneBucketNats = 0.25;
+constexpr double kPruneBudget1 = 1.4901161193847656e-08 / 2.718281828459045;                  // 2^-26 / e
+constexpr double kPruneBudget2 = 1.4901161193847656e-08 * (1.0 - 2.0 / 2.718281828459045);    // 2^-26 (1 - 2 / e)
 
 struct PrunePlan {
     int nT;    // column blocks
@@ -87,9 +116,11 @@ void slab_ranges(int N, int M, int32_t* ranges_i, int32_t* slices_i, int32_t* re
 size_t prune_blocks_bytes(int M);
 size_t prune_groups_bytes(int M);
 // the kept column intervals of every slab of the sorted clouds xs (N, D), ys (M, D) for the column vector h (+ pot * pot_scale); for the
-// second level: the records of the groups of 32 columns (`groups`, prune_groups_bytes) and every slab's home block (`home`, C ints)
+// second level: the records of the groups of 32 columns (`groups`, prune_groups_bytes), every slab's home block (`home`, C ints) and the
+// mass-rule threshold of every tile of 32 rows (`t2`, ceil(N / 32) floats); for glhip_prune_inspect: every slab's Mlb and t1 (C doubles each)
 void prune_ranges(const void* xs, const void* ys, const float* h, const float* pot, float pot_scale, int N, int M, int D, int in_dtype,
-                  float eps, int32_t* ranges_i, int32_t* slices_i, int32_t* red, void* blocks, void* groups, int32_t* home, hipStream_t st);
+                  float eps, int32_t* ranges_i, int32_t* slices_i, int32_t* red, void* blocks, void* groups, int32_t* home, float* t2,
+                  double* mlb, double* t1, hipStream_t st);
 // L of the bound in nats
 inline double prune_L(int M) { return std::log((double)M) + 26.0 * 0.6931471805599453 + kPruneMarginNats; }
 // sub-voxels per axis of the sorted p = 2 call: sub^D ~ 8 sub-voxels of ~32 points in a voxel of kSortRowsPerVoxel
@@ -110,6 +141,8 @@ struct AutoSort {
     void* blocks = nullptr;                 // per-column-block boxes and dual maxima (pruned p = 2 launches)
     void* groups = nullptr;                 // the same per group of 32 columns, and every slab's home block: the second level
     int32_t* home = nullptr;
+    float* t2 = nullptr;                    // per tile of 32 rows: the second level's mass-rule threshold; per slab: Mlb and the first
+    double *mlb = nullptr, *t1 = nullptr;   // level's threshold.  All three live in the sort scratch, dead once both sorts have run
     void* inner_ws = nullptr;
     size_t inner_bytes = 0;
 };
@@ -163,6 +196,10 @@ inline int autosort_prepare(AutoSort& a, const void* x, const void* y, int N, in
                       slabs ? 1 : prune_sort_sub(D));
     if (rc) return rc;
     if (slabs) slab_ranges(N, M, a.ranges_i, a.slices_i, a.red, st);
+    // (the scratch holds 20 bytes per point of the larger cloud and more: N / 8 + 16 C bytes fit many times over)
+    a.mlb = reinterpret_cast<double*>(scratch);
+    a.t1 = a.mlb + a.C;
+    a.t2 = reinterpret_cast<float*>(a.t1 + a.C);
     a.inner_ws = w + off;
     a.inner_bytes = workspace_bytes - off;
     a.on = true;

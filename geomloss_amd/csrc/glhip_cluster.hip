@@ -379,8 +379,16 @@ struct ColBlock {           // one block of kPruneColBlock sorted columns
     float lo[3];
     float hmax;             // largest dual value of the block (-inf: all -inf)
     float hi[3];
-    int special;            // a non-finite coordinate or a NaN dual value: kept by every slab, left out of Mlb
+    float lse;              // log sum exp of the block's dual values, rounded up; NaN marks a SPECIAL block (a non-finite coordinate or a
+                            // NaN dual value): kept by every slab, left out of Mlb and of every sum
 };
+// lse in float32, rounded up.  The sum of up to 256 terms e^(h - hmax) in [0, 1] is a tree of float32 adds 8 deep over expf values good to
+// 2 ulp: under 1e-6 relative, so under 1e-6 in the logarithm; logf of a value in [1, 256] is good to 2 ulp of 5.6: 1e-6; the final add
+// rounds by 2^-24 |lse|.  The block's value is formed from the eight rounded-up group values in the same way, once more.  Slack
+// 2^-20 (|lse| + 8): 16 ulp of the value plus 7.6e-6, several times the sum of those.
+constexpr float kPruneLseSlack = 9.5367431640625e-7f;      // 2^-20
+__device__ __forceinline__ float lse_up(float v) { return v + kPruneLseSlack * (__builtin_fabsf(v) + 8.f); }
+
 static_assert(kHomeCols == kPruneColBlock && kPruneColBlock % 64 == 0 && sizeof(GroupBox) == 32, "block / group records");
 
 // one wavefront per column block; in step k lanes 0-31 take the block's group 2 k of 32 columns and lanes 32-63 group 2 k + 1: the
@@ -394,11 +402,13 @@ __global__ void __launch_bounds__(256) prune_blocks_kernel(const T* __restrict__
     if (t >= nT) return;
     float blo[3] = {INFINITY, INFINITY, INFINITY}, bhi[3] = {-INFINITY, -INFINITY, -INFINITY};
     float bhm = -INFINITY;
+    float gls[kPruneColBlock / 64];      // the values of this half's groups
     int bbad = 0;
     const int j0 = t * kPruneColBlock, j1 = min(M, j0 + kPruneColBlock);
+#pragma unroll
     for (int k = 0; k < kPruneColBlock / 64; ++k) {
         float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        float hm = -INFINITY;
+        float hm = -INFINITY, hv = -INFINITY;
         int bad = 0;
         const int j = j0 + 64 * k + lane;
         if (j < j1) {
@@ -408,7 +418,7 @@ __global__ void __launch_bounds__(256) prune_blocks_kernel(const T* __restrict__
                 lo[d] = v;
                 hi[d] = v;
             }
-            const float hv = pot ? __builtin_fmaf(pot[j], pot_scale, h[j]) : h[j];     // as the half-step forms it (glhip_softmin_ops.h)
+            hv = pot ? __builtin_fmaf(pot[j], pot_scale, h[j]) : h[j];     // as the half-step forms it (glhip_softmin_ops.h)
             bad |= __builtin_isnan(hv);
             hm = fmaxf(hm, hv);      // (drops a NaN: the mark carries it)
         }
@@ -420,6 +430,11 @@ __global__ void __launch_bounds__(256) prune_blocks_kernel(const T* __restrict__
             hm = fmaxf(hm, __shfl_xor(hm, off, 64));
             bad |= __shfl_xor(bad, off, 64);
         }
+        // the group's log sum exp around its maximum (a NaN or -inf value adds nothing; hm = +-inf stands for itself)
+        float se = (__builtin_isfinite(hm) && hv > -INFINITY) ? expf(hv - hm) : 0.f;
+        for (int off = 16; off > 0; off >>= 1) se += __shfl_xor(se, off, 64);
+        const float gl = __builtin_isfinite(hm) ? lse_up(hm + logf(se)) : hm;
+        gls[k] = gl;
         const int g0 = j0 + 64 * k + (lane & 32);      // first column of this half's group
         if ((lane & 31) == 0 && g0 < j1) {
             GroupBox b;
@@ -427,7 +442,7 @@ __global__ void __launch_bounds__(256) prune_blocks_kernel(const T* __restrict__
                 b.lohi[d][0] = d < D ? lo[d] : 0.f;
                 b.lohi[d][1] = d < D ? hi[d] : 0.f;
             }
-            b.hmax = hm;
+            b.lse = gl;
             b.special = bad;
             groups[g0 >> 5] = b;
         }
@@ -444,6 +459,18 @@ __global__ void __launch_bounds__(256) prune_blocks_kernel(const T* __restrict__
     }
     bhm = fmaxf(bhm, __shfl_xor(bhm, 32, 64));
     bbad |= __shfl_xor(bbad, 32, 64);
+    float gm = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < kPruneColBlock / 64; ++k) gm = fmaxf(gm, gls[k]);
+    gm = fmaxf(gm, __shfl_xor(gm, 32, 64));
+    float blse = gm;
+    if (__builtin_isfinite(gm)) {
+        float se = 0.f;
+#pragma unroll
+        for (int k = 0; k < kPruneColBlock / 64; ++k) se += expf(gls[k] - gm);      // (an empty or all -inf group: e^-inf = 0)
+        se += __shfl_xor(se, 32, 64);
+        blse = lse_up(gm + logf(se));
+    }
     if (lane == 0) {
         ColBlock b;
         for (int d = 0; d < 3; ++d) {
@@ -451,7 +478,7 @@ __global__ void __launch_bounds__(256) prune_blocks_kernel(const T* __restrict__
             b.hi[d] = d < D ? bhi[d] : 0.f;
         }
         b.hmax = bhm;
-        b.special = bbad;
+        b.lse = bbad ? NAN : blse;
         out[t] = b;
     }
 }
@@ -485,6 +512,27 @@ __device__ __forceinline__ int block_scan256(int v, int* buf) {
     return v;
 }
 
+// The bucket of a key for a histogram that starts at `lo`: -1 below it (the underflow bucket, always dropped), kPruneBuckets above its
+// range (never dropped).  A NaN key counts as above the range.
+__device__ __forceinline__ int prune_bucket(double key, double lo) {
+    const double d = (key - lo) * (1.0 / kPruneBucketNats);
+    if (d < 0.0) return -1;
+    return d < (double)kPruneBuckets ? (int)d : kPruneBuckets;
+}
+// The first bucket that is kept: buckets are dropped from the bottom while the dropped mass (the underflow bucket first) stays within the
+// budget.  The underflow bucket alone cannot exceed it: every key in it has a mass below e^-L = 2^-26 e^-1 / M, and it holds at most
+// ceil(M / 256) blocks (first level, budget 2^-26 e^-1) or ceil(M / 32) groups (second level, budget 2^-26 (1 - 2 / e) > 2^-26 e^-1 / 16)
+// — so bucket 0 is always a valid answer.
+__device__ __forceinline__ int prune_first_kept(const double* hist, double under, double budget) {
+    double s = under;
+    int b = 0;
+    for (; b < kPruneBuckets; ++b) {
+        if (s + hist[b] > budget) break;
+        s += hist[b];
+    }
+    return b;
+}
+
 // One workgroup per slab of kSortSlab sorted rows: its box, Mlb, then the kept blocks as column intervals in its S slots of `red`
 // (unused slots: empty intervals, which the kernels skip).  A piece starts at a kept block that opens a run (the gap to the previous
 // kept block is >= g blocks) or that sits on the piece grid (a multiple of PB).  g = 1 unless the slab has more than kPruneRuns runs;
@@ -492,8 +540,11 @@ __device__ __forceinline__ int block_scan256(int v, int* buf) {
 template <typename T>
 __global__ void __launch_bounds__(256) prune_slabs_kernel(const T* __restrict__ xs, int N, int M, int D, const ColBlock* __restrict__ blocks,
                                                           int nT, int PB, int S, double inv2eps, double L, int32_t* __restrict__ ranges_i,
-                                                          int32_t* __restrict__ slices_i, int32_t* __restrict__ red, int32_t* __restrict__ home) {
+                                                          int32_t* __restrict__ slices_i, int32_t* __restrict__ red, int32_t* __restrict__ home,
+                                                          double* __restrict__ mlb_out, double* __restrict__ t1_out) {
     __shared__ int buf[256];
+    __shared__ double hist[kPruneBuckets + 1];      // (the last entry: the underflow bucket)
+    __shared__ int first_kept;
     __shared__ float wlo[4][3], whi[4][3];
     __shared__ double wm[4];
     __shared__ int wb[4];
@@ -535,7 +586,7 @@ __global__ void __launch_bounds__(256) prune_slabs_kernel(const T* __restrict__ 
     if (!bad) {
         for (int t = tid; t < nT; t += 256) {
             const ColBlock b = blocks[t];
-            if (b.special) continue;
+            if (__builtin_isnan(b.lse)) continue;
             double dmin2, dmax2;
             box_d2(rlo, rhi, b, D, dmin2, dmax2);
             const double v = (double)b.hmax - dmax2 * inv2eps;
@@ -556,14 +607,39 @@ __global__ void __launch_bounds__(256) prune_slabs_kernel(const T* __restrict__ 
         for (int w = 0; w < 4; ++w) take(wm[w], wb[w]);
     }
     const bool keep_all = bad || !__builtin_isfinite(mlb);
-    const double thr = mlb - L;
+    // The mass rule (glhip_autosort.h): a histogram of the keys k(T) = lse(T) - dmin(R,T)^2 / (2 eps) above the classic threshold Mlb - L,
+    // every bucket holding the mass e^(k(T) - Mlb) of its blocks
+    const double lo_key = mlb - L;
+    auto block_key = [&](const ColBlock& b) {
+        double dmin2, dmax2;
+        box_d2(rlo, rhi, b, D, dmin2, dmax2);
+        return (double)b.lse - dmin2 * inv2eps;
+    };
+    for (int q = tid; q <= kPruneBuckets; q += 256) hist[q] = 0.0;
+    __syncthreads();
+    if (!keep_all) {
+        for (int t = tid; t < nT; t += 256) {
+            const ColBlock b = blocks[t];
+            if (__builtin_isnan(b.lse)) continue;
+            const double key = block_key(b);
+            const int q = prune_bucket(key, lo_key);
+            const double mass = exp(key - mlb);
+            if (q < kPruneBuckets && mass > 0.0) atomicAdd(&hist[q < 0 ? kPruneBuckets : q], mass);
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        first_kept = keep_all ? 0 : prune_first_kept(hist, hist[kPruneBuckets], kPruneBudget1);
+        mlb_out[k] = mlb;
+        t1_out[k] = keep_all ? -INFINITY : lo_key + first_kept * kPruneBucketNats;
+    }
+    __syncthreads();
+    const int fk = first_kept;
     auto kept = [&](int t) {
         if (keep_all) return true;
         const ColBlock b = blocks[t];
-        if (b.special) return true;
-        double dmin2, dmax2;
-        box_d2(rlo, rhi, b, D, dmin2, dmax2);
-        return (double)b.hmax - dmin2 * inv2eps >= thr;
+        if (__builtin_isnan(b.lse)) return true;
+        return prune_bucket(block_key(b), lo_key) >= fk;
     };
     // No second level where it has nothing to win: a slab without a bound, and a slab whose bound keeps every block (large eps: the
     // finer test would pass nearly every group as well, and costs ~2 % of the sweep)
@@ -617,6 +693,122 @@ __global__ void __launch_bounds__(256) prune_slabs_kernel(const T* __restrict__ 
         g = hi_g;
     }
     walk(g, true);
+}
+
+// The mass rule of the second level (glhip_autosort.h).  One workgroup per slab with a home block, after prune_slabs_kernel: for each of
+// the slab's 8 tiles W of 32 rows, the seed ms(W) — the smallest over the tile's rows of the row's exact largest exponent over the home
+// block, float64 from the points themselves — then one histogram per tile of the keys k(W, G) = lse(G) - dmin(W,G)^2 / (2 eps) of the
+// groups G inside the slab's emitted intervals, starting at ms(W) - L, and from it the threshold t2(W): written in log2 units, the
+// reducing kernel's, as a float32 rounded toward minus infinity.  Thread = row for the seeds, thread = group for the histograms.
+static_assert(kPruneRuns + kPruneGrid <= 256 && kSortSlab == 256, "one thread per interval slot / per row");
+template <typename T>
+__global__ void __launch_bounds__(256) prune_tiles_kernel(const T* __restrict__ xs, const T* __restrict__ ys, const float* __restrict__ h,
+                                                          const float* __restrict__ pot, float pot_scale, int N, int M, int D,
+                                                          const GroupBox* __restrict__ groups, const int32_t* __restrict__ red, int S,
+                                                          const int32_t* __restrict__ home, double inv2eps, double L, float* __restrict__ t2) {
+    constexpr int kTiles = kSortSlab / 32;
+    __shared__ int buf[256];
+    __shared__ int first_group[256];
+    __shared__ double hy[kPruneColBlock][3], hh[kPruneColBlock];
+    __shared__ float tlo[kTiles][3], thi[kTiles][3];
+    __shared__ double ms[kTiles];
+    __shared__ double hist[kTiles][kPruneBuckets + 1];      // (the last entry: the underflow bucket)
+    const int k = blockIdx.x, tid = threadIdx.x, w = tid >> 5;
+    const int hb = home[k];
+    if (hb < 0) return;      // no second level for this slab: nobody reads its thresholds
+    const int r0 = k * kSortSlab, r1 = min(N, r0 + kSortSlab);
+    // the home block's columns
+    {
+        const int j = hb * kPruneColBlock + tid;
+        const bool real = j < M;
+        for (int d = 0; d < 3; ++d) hy[tid][d] = (real && d < D) ? (double)to_f32<T>(ys[(long)j * D + d]) : 0.0;
+        hh[tid] = real ? (double)(pot ? __builtin_fmaf(pot[j], pot_scale, h[j]) : h[j]) : -INFINITY;
+    }
+    for (int q = tid; q < kTiles * (kPruneBuckets + 1); q += 256) (&hist[0][0])[q] = 0.0;
+    // this thread's row, its tile's box and seed
+    const bool row = r0 + tid < r1;
+    float x[3] = {0.f, 0.f, 0.f};
+    if (row)
+        for (int d = 0; d < D; ++d) x[d] = to_f32<T>(xs[(long)(r0 + tid) * D + d]);
+    for (int d = 0; d < 3; ++d) {
+        float lo = row ? x[d] : INFINITY, hi = row ? x[d] : -INFINITY;
+        for (int off = 16; off > 0; off >>= 1) {
+            lo = fminf(lo, __shfl_xor(lo, off, 64));
+            hi = fmaxf(hi, __shfl_xor(hi, off, 64));
+        }
+        if ((tid & 31) == 0) { tlo[w][d] = lo; thi[w][d] = hi; }
+    }
+    __syncthreads();
+    {
+        double seed = -INFINITY;
+        const double xd[3] = {(double)x[0], (double)x[1], (double)x[2]};
+        for (int j = 0; j < kPruneColBlock; ++j) {
+            double d2 = 0.0;
+            for (int d = 0; d < 3; ++d) {
+                const double t = xd[d] - hy[j][d];
+                d2 = fma(t, t, d2);
+            }
+            seed = fmax(seed, hh[j] - d2 * inv2eps);      // (a padding column: -inf)
+        }
+        // the tile's smallest seed; a seed that is not finite (none should be: the home block attains a finite Mlb) turns the rule off
+        int ok = !row || __builtin_isfinite(seed);
+        double v = row ? seed : INFINITY;
+        for (int off = 16; off > 0; off >>= 1) {
+            v = fmin(v, __shfl_xor(v, off, 64));
+            ok &= __shfl_xor(ok, off, 64);
+        }
+        if ((tid & 31) == 0) ms[w] = (ok && r0 + 32 * w < r1) ? v : NAN;      // NaN: no rows, or no finite seed
+    }
+    // the groups of the emitted intervals, numbered through: first_group[q] = groups before interval q
+    const int32_t* slots = red + 2 * (long)k * S;
+    int j0 = 0, ng = 0;
+    if (tid < S) {
+        j0 = slots[2 * tid];
+        ng = (max(slots[2 * tid + 1], j0) - j0 + 31) >> 5;      // (intervals start on multiples of kPruneColBlock)
+    }
+    const int incl = block_scan256<false>(ng, buf);
+    first_group[tid] = incl - ng;
+    const int total = buf[255];
+    __syncthreads();
+    double under[kTiles];
+    for (int c = 0; c < kTiles; ++c) under[c] = 0.0;
+    for (int f = tid; f < total; f += 256) {
+        int q = 0;      // the last slot with first_group <= f (empty slots share their successor's value and are passed over)
+        for (int step = 128; step > 0; step >>= 1)
+            if (q + step < 256 && first_group[q + step] <= f) q += step;
+        const int g = (slots[2 * q] >> 5) + (f - first_group[q]);
+        const GroupBox b = groups[g];
+        if (b.special) continue;
+        for (int c = 0; c < kTiles; ++c) {
+            const double m = ms[c];
+            if (!(m == m)) continue;
+            double dmin2 = 0.0;
+            for (int d = 0; d < 3; ++d) {
+                const double gap = fmax(fmax((double)b.lohi[d][0] - (double)thi[c][d], (double)tlo[c][d] - (double)b.lohi[d][1]), 0.0);
+                dmin2 = fma(gap, gap, dmin2);
+            }
+            const double key = (double)b.lse - dmin2 * inv2eps;
+            const int bk = prune_bucket(key, m - L);
+            if (bk >= kPruneBuckets) continue;
+            const double mass = exp(key - m);
+            if (bk < 0) under[c] += mass;
+            else if (mass > 0.0) atomicAdd(&hist[c][bk], mass);
+        }
+    }
+    for (int c = 0; c < kTiles; ++c)
+        if (under[c] > 0.0) atomicAdd(&hist[c][kPruneBuckets], under[c]);
+    __syncthreads();
+    if (tid < kTiles && r0 + 32 * tid < r1) {
+        const double m = ms[tid];
+        float out = -INFINITY;
+        if (m == m) {
+            const int fk = prune_first_kept(hist[tid], hist[tid][kPruneBuckets], kPruneBudget2);
+            const double v = (m - L + fk * kPruneBucketNats) * 1.4426950408889634;
+            out = (float)v;
+            if ((double)out > v) out = nextafterf(out, -INFINITY);
+        }
+        t2[(r0 >> 5) + tid] = out;
+    }
 }
 
 size_t sort64_temp_bytes(int n) {
@@ -683,7 +875,8 @@ size_t prune_blocks_bytes(int M) { return (size_t)prune_plan(M).nT * sizeof(ColB
 size_t prune_groups_bytes(int M) { return (size_t)((M + 31) / 32) * sizeof(GroupBox); }
 
 void prune_ranges(const void* xs, const void* ys, const float* h, const float* pot, float pot_scale, int N, int M, int D, int in_dtype,
-                  float eps, int32_t* ranges_i, int32_t* slices_i, int32_t* red, void* blocks_, void* groups_, int32_t* home, hipStream_t st) {
+                  float eps, int32_t* ranges_i, int32_t* slices_i, int32_t* red, void* blocks_, void* groups_, int32_t* home, float* t2,
+                  double* mlb, double* t1, hipStream_t st) {
     const PrunePlan pp = prune_plan(M);
     const int C = (N + kSortSlab - 1) / kSortSlab;
     ColBlock* blocks = static_cast<ColBlock*>(blocks_);
@@ -694,12 +887,16 @@ void prune_ranges(const void* xs, const void* ys, const float* h, const float* p
         hipLaunchKernelGGL(prune_blocks_kernel<float>, dim3((pp.nT + 3) / 4), dim3(256), 0, st, static_cast<const float*>(ys), h, pot, pot_scale, M, D,
                            pp.nT, blocks, groups);
         hipLaunchKernelGGL(prune_slabs_kernel<float>, dim3(C), dim3(256), 0, st, static_cast<const float*>(xs), N, M, D, blocks, pp.nT, pp.PB, pp.S,
-                           inv2eps, L, ranges_i, slices_i, red, home);
+                           inv2eps, L, ranges_i, slices_i, red, home, mlb, t1);
+        hipLaunchKernelGGL(prune_tiles_kernel<float>, dim3(C), dim3(256), 0, st, static_cast<const float*>(xs), static_cast<const float*>(ys), h, pot,
+                           pot_scale, N, M, D, groups, red, pp.S, home, inv2eps, L, t2);
     } else {
         hipLaunchKernelGGL(prune_blocks_kernel<bf16_t>, dim3((pp.nT + 3) / 4), dim3(256), 0, st, static_cast<const bf16_t*>(ys), h, pot, pot_scale, M,
                            D, pp.nT, blocks, groups);
         hipLaunchKernelGGL(prune_slabs_kernel<bf16_t>, dim3(C), dim3(256), 0, st, static_cast<const bf16_t*>(xs), N, M, D, blocks, pp.nT, pp.PB,
-                           pp.S, inv2eps, L, ranges_i, slices_i, red, home);
+                           pp.S, inv2eps, L, ranges_i, slices_i, red, home, mlb, t1);
+        hipLaunchKernelGGL(prune_tiles_kernel<bf16_t>, dim3(C), dim3(256), 0, st, static_cast<const bf16_t*>(xs), static_cast<const bf16_t*>(ys), h,
+                           pot, pot_scale, N, M, D, groups, red, pp.S, home, inv2eps, L, t2);
     }
 }
 

@@ -45,8 +45,8 @@ struct Ranges {
 // Second, in-kernel level of the exact pruning of sorted p = 2 launches (glhip_autosort.h; the test itself: glhip_softmin_x32.h).
 struct GroupBox {           // one aligned group of 32 sorted columns, as four 8-byte parts: the test reads one part per lane
     float lohi[3][2];       // box corners, (lo, hi) per coordinate (0, 0 beyond D)
-    float hmax;             // largest dual value of the group (-inf: all -inf)
-    int special;            // a non-finite coordinate or a NaN dual value: never skipped
+    float lse;              // log sum exp of the group's dual values, rounded up (>= the largest of them; -inf: all -inf)
+    int special;            // a non-finite coordinate or a NaN dual value: never skipped, left out of every sum
 };
 constexpr int kHomeCols = 256;      // columns of a slab's home block (= kPruneColBlock)
 struct Level2 {
@@ -56,6 +56,8 @@ struct Level2 {
                                         // exponents around the very centre of the dense launch of the same call
     int n_groups = 0;
     float L2 = 0.f;                     // L of the bound, in log2 units
+    const float* t2 = nullptr;          // per tile of 32 sorted rows: the threshold of the mass rule, in log2 units (prune_tiles_kernel); read
+                                        // only by slabs with a home block
 };
 
 // One LDS record per column point: D coordinates (already centred / scaled) + one scalar.

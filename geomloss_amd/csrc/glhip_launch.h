@@ -135,7 +135,7 @@ void launch_softmin_mfma_nw(const SoftminParams<T>& prm, const Ranges& rg, int n
     // the second pruning level rides on the workgroup shape the sorted launches get (launch_softmin_mfma): f16 x 2 on 4 wavefronts,
     // bf16 x 3 on 8; its kernel carries no leftover tiles (slabs of 256 rows are whole chunks)
     constexpr bool kP2Shape = (L == XL_F16X2) ? NW == 4 : NW == 8;
-    const bool p2 = kP2Shape && n_ranges > 0 && sc.l2.groups && sc.l2.home && sc.l2.centre_x;
+    const bool p2 = kP2Shape && n_ranges > 0 && sc.l2.groups && sc.l2.home && sc.l2.centre_x && sc.l2.t2;
     const int share = (NW == 4 && L == XL_F16X2 && n_ranges > 0 && !p2) ? 1 : 0;
     // the number of column splits is still derived from the number of row BLOCKS: deriving it from the (larger) chunk count
     // gives fewer, longer-lived workgroups and measured 3 % slower on uniform clusters (multiscale at 1e6: 258 vs 250 ms)

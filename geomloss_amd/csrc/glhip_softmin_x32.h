@@ -250,6 +250,10 @@ constexpr int fwd_tile(int NW) { return NW == 2 ? 256 : kTileX; }
 //   * centre: the sorted launch expands its exponents around launch_centre of the caller's UNSORTED rows (Level2::centre_x), the centre
 //     of the dense launch of the same call: pruned and dense results differ by the summation order alone (~1e-8 at the headline law),
 //     and non-finite coordinates, whose NaN / infinity pattern depends on the side of the centre a row lies on, give the same pattern.
+//   * mass rule (round 10; the argument: glhip_autosort.h): the records hold lse(G) >= hmax(G) in the place of hmax(G) — the test above
+//     stays valid, a little more conservative — and thr is the larger of the term rule's threshold above and Level2::t2 of the
+//     wavefront's tile of 32 rows (prune_tiles_kernel: groups whose keys lie under it hold, together, under 2^-26 (1 - 2 / e) of a term
+//     every row of the tile has).  Taken where thr is set (seed, redo): the group loops are what they were.
 //   Launches without Level2 (P2 = false: everything but the sorted p = 2 path) compile to what they were.
 constexpr float kP2Slack = 9.5367431640625e-7f;      // 2^-20
 
@@ -473,7 +477,7 @@ __device__ __forceinline__ void softmin_fwd_x32_body(const SoftminParams<T>& prm
                     if constexpr (H2) Xlo[0] = select_u4(half == 0, xd_with_n<L>(Xlo[0], -um), Xlo[0]);
                     else if (half) Xhi[0] = pack_negmax(um);
                     first_group = false;
-                    thr = row_threshold();
+                    thr = fmaxf(row_threshold(), l2.t2[wave_row0 >> 5]);
                 }
             }
         }
@@ -664,7 +668,7 @@ __device__ __forceinline__ void softmin_fwd_x32_body(const SoftminParams<T>& prm
                     for (int rt = 0; rt < NS; ++rt)      // (a leftover slot that has seen no group yet keeps n = 0 for its first, exact one)
                         if (rt < RT || (rt - RT < nx && !first_shared)) set_max(rt, m[rt]);
                     if constexpr (P2) {
-                        if (home >= 0) thr = row_threshold();
+                        if (home >= 0) thr = fmaxf(row_threshold(), l2.t2[wave_row0 >> 5]);
                     }
                 } else {
 #pragma unroll

@@ -43,6 +43,8 @@ SIGNATURES = {
     "glhip_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "glhip_softmin_fwd_family": (_c_int, [_c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int, _c_int]),
     "glhip_kernel_conv_fwd_family": (_c_int, [_c_int, _c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int]),
+    "glhip_prune_inspect_slots": (_c_int, [_c_int]),
+    "glhip_prune_inspect": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_float, _c_int] + [_vp] * 7 + [_vp, _c_size, _vp]),
     "glhip_softmin_fwd": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int, _c_int]
                           + _RANGES + _TAIL),
     "glhip_sinkhorn_step": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_float,

@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 122 /* 0.1.22 */
+#define GLHIP_VERSION 123 /* 0.1.23 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
@@ -107,6 +107,12 @@ extern "C" {
                                   against their running maxima seeded with exact maxima over the slab's best block (csrc/glhip_softmin_x32.h,
                                   P2); both clouds are ordered in voxels of 256 points with compact sub-voxels inside.  Same guarantee (both
                                   levels together drop < 2^-26 of a row sum); headline law: 35 -> 24 ms (profiles/r09_*).
+                                  Version 123: both levels drop by the SUM of what they drop instead of by single terms.  The terms of a
+                                  set S of columns sum to at most e^(lse(S) - dmin(box, S)^2 / (2 eps)) for every row of the box; per slab
+                                  (blocks of 256 columns) and per tile of 32 rows (groups of 32 columns) the largest threshold on that key
+                                  is taken whose dropped masses stay within a budget — 2^-26 / e, and 2^-26 (1 - 2 / e) beside the 2^-26 / e
+                                  of the term rule — found on 0.25-nat histograms in float64 (csrc/glhip_autosort.h).  Same guarantee:
+                                  a row loses < 2^-26 of its sum.  glhip_prune_inspect shows the thresholds (profiles/r10_*).
                                   Here this flag means the dense xd / x32 launch. */
 
 /* Environment variables read ONCE per process by the library itself (test / tuning knobs; everything else is an argument):
@@ -165,6 +171,26 @@ int glhip_softmin_fwd_family(int B, long N, long M, int D, int p, int dtype, int
  * glhip_wsum_mfma.h), _XD, _XK, or _VALU / _GENERIC under GLHIP_FLAG_NO_MFMA and beyond D = 4095; laplacian / energy: _DIST where the
  * squared distances come from the matrix cores, _VALU / _GENERIC elsewhere. */
 int glhip_kernel_conv_fwd_family(int kind, int B, long N, long M, int D, int dtype, int flags, int n_ranges);
+
+/*
+ * What the exact pruning of a big dense p = 2 call decides (version 123): runs the sort and the bounds of glhip_softmin_fwd (pot = NULL,
+ * logw = h) or glhip_sinkhorn_step (the column vector is fma(pot, 1 / eps, logw)) on `stream` and copies the records into the caller's
+ * DEVICE buffers; it launches no reduction.  The mass dropped by the pruning is below one ulp of the output by design, so no output can
+ * tell a correct budget from a generous one: the thresholds themselves are checkable here.  With C = ceil(N / 256) slabs of sorted rows
+ * and S = glhip_prune_inspect_slots(M) interval slots per slab (any output may be NULL):
+ *   perm_x (N), perm_y (M)   sorted position -> caller's index
+ *   mlb, t1 (C doubles)      per slab: Mlb and the first level's key threshold, in nats (t1 = -inf: the slab keeps everything)
+ *   home (C)                 per slab: the home column block, -1: no second level
+ *   intervals (C S 2)        per slab: S (begin, end) pairs of sorted columns; unused slots are empty
+ *   t2 (ceil(N / 32) floats) per tile of 32 sorted rows: the second level's mass threshold, in log2 units as the kernel compares it
+ *                            (-inf: not written — home = -1 — or no finite seed)
+ * GLHIP_EUNSUPPORTED for shapes the p = 2 call does not prune (see GLHIP_FLAG_NO_SORT); GLHIP_EINVAL for a workspace below
+ * glhip_workspace_bytes(1, N, M, D, 0).
+ */
+int glhip_prune_inspect_slots(int M);
+int glhip_prune_inspect(const void* x, const void* y, const float* logw, const float* pot, int N, int M, int D, float eps, int in_dtype,
+                        int32_t* perm_x, int32_t* perm_y, double* mlb, double* t1, int32_t* home, int32_t* intervals, float* t2,
+                        void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * Soft-C-transform  out[b,i] = -eps * log sum_j exp( h[b,j] - C(x[b,i], y[b,j]) / eps ),

@@ -182,6 +182,171 @@ def level2(xs, ys, h, eps, keep, L, slabs, check=False):
     return evaluated, kept1, worst
 
 
+# ---- the mass rule (glhip_autosort.h, round 10): thresholds by dropped mass, found on histograms of the keys ----------------------------
+
+BUCKETS, BUCKET_NATS = 112, 0.25                 # kPruneBuckets, kPruneBucketNats
+BUDGET1 = 2.0**-26 / math.e                      # first level, relative to e^Mlb(R)
+BUDGET2 = 2.0**-26 * (1.0 - 2.0 / math.e)        # second level's mass rule, relative to e^ms(W)
+LSE_SLACK = np.float32(2.0**-20)                 # kPruneLseSlack
+LOG2E = 1.4426950408889634
+
+
+def inv2eps_of(eps):
+    """the device's 0.5 / (double)eps of the float32 eps it is handed"""
+    return 0.5 / float(np.float32(eps))
+
+
+def lse_up(hp):
+    """prune_blocks_kernel: log sum exp of every row of hp (padding: -inf) as a float32 rounded up by the kernel's slack (the model
+    sums in float64; the device's float32 sum differs by far less than the slack)"""
+    m = hp.max(1)
+    fin = np.isfinite(m)
+    with np.errstate(invalid="ignore", over="ignore"):
+        s = np.exp(hp - np.where(fin, m, 0.0)[:, None]).sum(1)
+        v = np.where(fin, m + np.log(np.where(fin, s, 1.0)), m).astype(np.float32)
+        up = (v + LSE_SLACK * (np.abs(v) + np.float32(8.0))).astype(np.float32)
+    return np.where(fin, up, v).astype(np.float64)
+
+
+def group_block_lse(h, M):
+    """(lse per group of 32, lse per block of 256): the block's value is formed from its groups' rounded-up values, as on the device"""
+    nG, nT = (M + GROUP - 1) // GROUP, (M + BLOCK - 1) // BLOCK
+    g = lse_up(np.concatenate([h.astype(np.float64), np.full(nG * GROUP - M, -np.inf)]).reshape(nG, GROUP))
+    per = BLOCK // GROUP
+    b = lse_up(np.concatenate([g, np.full(nT * per - nG, -np.inf)]).reshape(nT, per))
+    return g, b
+
+
+def bucket_of(key, lo):
+    """prune_bucket: -1 below the histogram, BUCKETS above its range (never dropped)"""
+    d = (key - lo) * (1.0 / BUCKET_NATS)
+    with np.errstate(invalid="ignore"):
+        return np.where(d < 0.0, -1, np.where(d < BUCKETS, np.floor(np.where(d < BUCKETS, d, 0.0)), BUCKETS)).astype(np.int64)
+
+
+def first_kept(hist, under, budget):
+    """prune_first_kept over the last axis: the first bucket whose mass would take the dropped sum past the budget"""
+    over = under[..., None] + np.cumsum(hist, -1) > budget
+    return np.where(over.any(-1), over.argmax(-1), BUCKETS)
+
+
+def plan_mass(xs, ys, h, eps):
+    """The first level under the mass rule: keep (C, nT) bool, Mlb (C,), t1 (C,), L — for finite inputs.  A slab that keeps every
+    block is what the device calls home = -1."""
+    M = ys.shape[0]
+    rlo, rhi = boxes(xs, SLAB)
+    blo, bhi = boxes(ys, BLOCK)
+    nT = blo.shape[0]
+    hmax = np.concatenate([h.astype(np.float64), np.full(nT * BLOCK - M, -np.inf)]).reshape(nT, BLOCK).max(1)
+    _, blse = group_block_lse(h, M)
+    L = math.log(M) + 26 * math.log(2) + MARGIN
+    i2e = inv2eps_of(eps)
+    C = rlo.shape[0]
+    keep = np.zeros((C, nT), bool)
+    mlb, t1 = np.zeros(C), np.zeros(C)
+    for c0 in range(0, C, 256):
+        a, b = rlo[c0:c0 + 256, None], rhi[c0:c0 + 256, None]
+        gap = np.maximum(np.maximum(blo[None] - b, a - bhi[None]), 0.0)
+        far = np.maximum(bhi[None] - a, b - blo[None])
+        dmin2, dmax2 = (gap**2).sum(-1), (far**2).sum(-1)
+        m = (hmax[None] - dmax2 * i2e).max(1)
+        key = blse[None] - dmin2 * i2e
+        lo = (m - L)[:, None]
+        bk = bucket_of(key, lo)
+        with np.errstate(over="ignore"):      # (keys above the range: never dropped, their mass is not used)
+            mass = np.exp(key - m[:, None])
+        n = m.shape[0]
+        flat = (np.arange(n)[:, None] * (BUCKETS + 2) + bk + 1).ravel()
+        hist = np.bincount(flat, weights=mass.ravel(), minlength=n * (BUCKETS + 2)).reshape(n, BUCKETS + 2)
+        fk = first_kept(hist[:, 1:BUCKETS + 1], hist[:, 0], BUDGET1)
+        mlb[c0:c0 + 256] = m
+        t1[c0:c0 + 256] = m - L + fk * BUCKET_NATS
+        keep[c0:c0 + 256] = bk >= fk[:, None]
+    return keep, mlb, t1, L
+
+
+def t2_as_stored(t2_nats):
+    """the device's record: log2 units, float32 rounded toward minus infinity"""
+    v = np.asarray(t2_nats, np.float64) * LOG2E
+    f = v.astype(np.float32)
+    return np.where(f.astype(np.float64) > v, np.nextafter(f, np.float32(-np.inf)), f).astype(np.float32)
+
+
+def intervals_of(keep_row):
+    """the column intervals of the kept blocks of one slab (without gap closing: at most RUNS runs)"""
+    k = np.concatenate([[0], keep_row.astype(np.int8), [0]])
+    d = np.diff(k)
+    return [(int(a) * BLOCK, int(b) * BLOCK) for a, b in zip(np.flatnonzero(d == 1), np.flatnonzero(d == -1))]
+
+
+def level2_mass(xs, ys, h, eps, keep, L, slabs, intervals=None):
+    """The second level under the mass rule on the given slabs.  intervals: {slab: [(j0, je), ...]} to walk the device's emitted
+    intervals instead of the runs of kept blocks.  Returns (pairs evaluated, pairs kept by the first level, per slab a dict with
+    home, groups (the groups walked), ms, t2 (nats) per tile and skip (tiles, groups) bool).  A group is evaluated iff its key
+    lse(G) - pen(W, G) lies in a bucket from the tile's first kept one on; the kernel's term rule, thr = ms - L against the same key,
+    is bucket >= 0."""
+    N, M = xs.shape[0], ys.shape[0]
+    x64, y64, h64 = xs.astype(np.float64), ys.astype(np.float64), h.astype(np.float64)
+    rlo, rhi = boxes(xs, SLAB)
+    blo, bhi = boxes(ys, BLOCK)
+    glo, ghi = boxes(ys, GROUP)
+    nT, nG = blo.shape[0], glo.shape[0]
+    hmax = np.concatenate([h64, np.full(nT * BLOCK - M, -np.inf)]).reshape(nT, BLOCK).max(1)
+    glse, _ = group_block_lse(h, M)
+    gcols = np.minimum(GROUP, M - GROUP * np.arange(nG))
+    i2e = inv2eps_of(eps)
+    evaluated = kept1 = 0.0
+    out = {}
+    for c in slabs:
+        far = np.maximum(bhi - rlo[c], rhi[c] - blo)
+        home = int(np.argmax(hmax - (far**2).sum(-1) * i2e))
+        hc = np.arange(home * BLOCK, min(M, (home + 1) * BLOCK))
+        iv = intervals[c] if intervals is not None else intervals_of(keep[c])
+        groups = np.concatenate([np.arange(j0 // GROUP, (min(je, M) + GROUP - 1) // GROUP) for j0, je in iv if je > j0])
+        r1 = min(N, (c + 1) * SLAB)
+        ms, t2, skip = [], [], []
+        for w0 in range(c * SLAB, r1, TILE):
+            xr = x64[w0:min(w0 + TILE, r1)]
+            seed = (h64[hc][None] - ((xr[:, None, :] - y64[hc][None]) ** 2).sum(-1) * i2e).max(1)
+            m = seed.min()
+            wlo, whi = xr.min(0), xr.max(0)
+            gap = np.maximum(np.maximum(glo[groups] - whi, wlo - ghi[groups]), 0.0)
+            key = glse[groups] - (gap**2).sum(-1) * i2e
+            bk = bucket_of(key, m - L)
+            with np.errstate(over="ignore"):
+                hist = np.bincount(bk + 1, weights=np.exp(key - m), minlength=BUCKETS + 2)
+            fk = int(first_kept(hist[1:BUCKETS + 1], hist[0], BUDGET2))
+            ms.append(m)
+            t2.append(m - L + fk * BUCKET_NATS)
+            skip.append(bk < fk)
+            evaluated += float(gcols[groups][bk >= fk].sum()) * xr.shape[0]
+            kept1 += float(gcols[groups].sum()) * xr.shape[0]
+        out[c] = dict(home=home, groups=groups, ms=np.array(ms), t2=np.array(t2), skip=np.array(skip))
+    return evaluated, kept1, out
+
+
+def dropped_share(xs, ys, h, eps, keep_row, rec, c):
+    """On the points themselves, float64: for every row of slab c, the share of its true sum held by the columns the first level
+    drops (keep_row) plus the columns of the groups the second level skips for the row's tile (rec: level2_mass's record)."""
+    N, M = xs.shape[0], ys.shape[0]
+    r0, r1 = c * SLAB, min(N, (c + 1) * SLAB)
+    xr = xs[r0:r1].astype(np.float64)
+    terms = np.empty((r1 - r0, M))
+    for j0 in range(0, M, 65536):
+        yy = ys[j0:j0 + 65536].astype(np.float64)
+        terms[:, j0:j0 + 65536] = h[j0:j0 + 65536].astype(np.float64)[None] - ((xr[:, None, :] - yy[None]) ** 2).sum(-1) / (2 * float(np.float32(eps)))
+    e = np.exp(terms - terms.max(1)[:, None])
+    gone1 = np.repeat(~keep_row, BLOCK)[:M]
+    share = np.zeros(r1 - r0)
+    for t in range((r1 - r0 + TILE - 1) // TILE):
+        gone = gone1.copy()
+        for g in rec["groups"][rec["skip"][t]]:
+            gone[g * GROUP:(g + 1) * GROUP] = True
+        rows = slice(t * TILE, min((t + 1) * TILE, r1 - r0))
+        share[rows] = e[rows][:, gone].sum(1) / e[rows].sum(1)
+    return share
+
+
 def bench_problem(n, seed=1000):
     """bench.make_problem(n, seed) without torch's device copy (same generator calls, same values)"""
     import torch
@@ -225,6 +390,14 @@ def main():
             print(f"two levels, voxels 256 / 256, sub {sub}: n = {a.n}  eps = {eps:.4g}: first level keeps {kept_pairs(keep, a.n, a.n) / (float(a.n) * a.n):.4f} "
                   f"(runs per slab mean {r.mean():.1f} max {r.max()}); on {len(slabs)} slabs: first level {k1 / (rows * a.n):.4f}, "
                   f"evaluated after the second {ev / (rows * a.n):.4f}", flush=True)
+            if sub == 1:
+                continue
+            keep, mlb, t1, L = plan_mass(xs, ys, hs, eps)
+            r = runs_per_slab(keep)
+            ev, k1, _ = level2_mass(xs, ys, hs, eps, keep, L, slabs)
+            print(f"mass rule,  voxels 256 / 256, sub {sub}: n = {a.n}  eps = {eps:.4g}: first level keeps {kept_pairs(keep, a.n, a.n) / (float(a.n) * a.n):.4f} "
+                  f"(runs per slab mean {r.mean():.1f} max {r.max()}, slabs over {RUNS} runs {(r > RUNS).sum()}); on {len(slabs)} slabs: "
+                  f"first level {k1 / (rows * a.n):.4f}, evaluated after the second {ev / (rows * a.n):.4f}", flush=True)
 
 
 if __name__ == "__main__":
