@@ -21,5 +21,7 @@ from . import hip
 from .wasserstein_barycenter_images import ImagesBarycenter  # noqa: E402
 from . import sinkhorn_divergence  # noqa: E402
 from . import ot  # noqa: E402  (`from geomloss import ot`: ot.solve_sample on the same kernels)
+from . import transport  # noqa: E402  (apply_plan / barycentric_map for the potentials of the legacy API)
+from .transport import apply_plan, barycentric_map  # noqa: E402
 
-__all__ = ["SamplesLoss", "ImagesBarycenter", "sinkhorn_divergence", "hip", "ot"]
+__all__ = ["SamplesLoss", "ImagesBarycenter", "sinkhorn_divergence", "hip", "ot", "transport", "apply_plan", "barycentric_map"]

@@ -55,6 +55,8 @@ SIGNATURES = {
     "glhip_sinkhorn_extrapolate4": (_c_int, [_vp] * 14 + [_c_int] * 6 + [_c_float, _c_float, _c_int, _c_int] + _TAIL),
     "glhip_softmin_bwd_x": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int,
                                      _c_int] + _RANGES + _TAIL),
+    "glhip_plan_apply_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "glhip_plan_apply": (_c_int, [_vp] * 7 + [_c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int, _c_int] + _RANGES + _TAIL),
     "glhip_kernel_conv_fwd": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int]
                               + _RANGES + _TAIL),
     "glhip_kernel_conv_bwd_x": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float,
@@ -345,6 +347,30 @@ def softmin_bwd_x_raw(x, y, h, out, grad_out, eps, p=2, ranges=None, flags=0):
                                      *_range_args(ranges, B), *ws_args, int(flags), _stream(x))
     _check(rc, lib)
     return gx
+
+
+def plan_apply_raw(x, y, h, fwd, feat, eps, flags=0, want_mass=False, p=2, ranges=None, workspace=True):
+    """The plan of a p = 2 soft-min applied to features (``glhip_plan_apply``): x (B,N,D), y (B,M,D) fp32|bf16, h (B,M), fwd (B,N) the
+    saved soft-min, feat (B,M,V) fp32 -> (B,N,V) fp32 row-normalised averages [, (B,N) recomputed row masses].  ``workspace=False``
+    passes no workspace: the launch runs without column splits (same results up to summation order)."""
+    lib = load_library()
+    B, N, D = x.shape
+    M, V = y.shape[1], feat.shape[2]
+    if is_f64(x):
+        raise NotImplementedError("glhip_plan_apply: float64 clouds are not supported (cast to float32)")
+    if tuple(feat.shape[:2]) != (B, M) or tuple(h.shape) != (B, M) or tuple(fwd.shape) != (B, N):
+        raise ValueError(f"glhip_plan_apply: expected h {(B, M)}, fwd {(B, N)}, feat {(B, M, 'V')}; got {tuple(h.shape)}, "
+                         f"{tuple(fwd.shape)}, {tuple(feat.shape)}")
+    out = torch.empty((B, N, V), dtype=torch.float32, device=x.device)
+    mass = torch.empty((B, N), dtype=torch.float32, device=x.device) if want_mass else None
+    with torch.cuda.device(x.device):
+        nbytes = int(lib.glhip_plan_apply_workspace_bytes(B, N, M, D, V)) if workspace else 0
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+        rc = lib.glhip_plan_apply(x.data_ptr(), y.data_ptr(), h.data_ptr(), fwd.data_ptr(), feat.data_ptr(), out.data_ptr(),
+                                  None if mass is None else mass.data_ptr(), B, N, M, D, V, float(eps), int(p), _dtype_code(x),
+                                  *_range_args(ranges, B), None if ws is None else ws.data_ptr(), nbytes, int(flags), _stream(x))
+    _check(rc, lib)
+    return (out, mass) if want_mass else out
 
 
 def softmin_fwd_grad_raw(x, y, h, guess, margin, eps, ranges=None, flags=0):
@@ -1078,6 +1104,50 @@ ENV_FLAGS = int(os.environ.get("GEOMLOSS_HIP_FLAGS", "0"))
 def softmin(eps, x, y, h, p=2, ranges=None, flags=0):
     """Soft-C-transform on the GPU.  x: (N,D)|(B,N,D), y: (M,D)|(B,M,D), h: (M,)|(B,M) -> (N,)|(B,N) fp32."""
     return _Softmin.apply(x, y, h, float(eps), int(p), ranges, int(flags) | ENV_FLAGS)
+
+
+def plan_apply_applies(x, p=2, ranges=None):
+    """Whether :func:`plan_apply` serves clouds like ``x``: p = 2, dense, D <= XD_MAX_DIM, float32 / bfloat16 compute."""
+    return p == 2 and ranges is None and x.shape[-1] <= XD_MAX_DIM and x.dtype != torch.float64
+
+
+def plan_apply(eps, x, y, h, feat, fwd=None, flags=0, p=2, ranges=None):
+    """Row-normalised application of the plan of a p = 2 soft-min to a feature matrix on the matrix cores (``glhip_plan_apply``):
+
+        out[i, v] = sum_j w_ij feat[j, v] / sum_j w_ij,     w_ij = exp(h_j - |x_i - y_j|^2 / (2 eps) + fwd_i / eps)
+
+    x: (N,D)|(B,N,D), y: (M,D)|(B,M,D), h: (M,)|(B,M), feat: (M,V)|(B,M,V)|(M,) -> (N,V)|(B,N,V)|(N,) fp32.  ``fwd`` is
+    ``softmin(eps, x, y, h)`` for the same arguments; it is computed here when not given.  The unnormalised product is
+    ``exp(-fwd / eps)[..., None] * out``.  Cost: one sweep over the N x M pairs per pass, each worth about four soft-min reductions
+    whatever it carries; a pass takes up to 128 feature columns for D <= 4, 64 for 5 <= D <= 11 and 32 beyond, and a remainder of
+    a single column is a whole pass: V = 129 at D = 3 costs two.  Inside the kernel the weights are taken relative to the largest one
+    of their row, and ``out`` is divided by the recomputed row sum: ``fwd`` only centres the exponents (an error of a few units of
+    ``eps`` in it costs no accuracy in ``out``; it must be close enough for the exponents to stay in range), and one-hot plan rows
+    return their features bit for bit.  NOT an autograd function: it runs under ``torch.no_grad()`` and returns a tensor without
+    ``grad_fn``.  float64 clouds, p = 1, D > 16 and block-sparse ranges raise ``NotImplementedError``."""
+    D = x.shape[-1]
+    if x.dtype == torch.float64 or y.dtype == torch.float64:
+        raise NotImplementedError("geomloss_amd.hip.plan_apply: float64 clouds are not supported (cast to float32)")
+    if p != 2 or D > XD_MAX_DIM or ranges is not None:
+        raise NotImplementedError(f"geomloss_amd.hip.plan_apply: only p = 2, D <= {XD_MAX_DIM}, dense plans (got p = {p}, D = {D}, "
+                                  f"ranges {'given' if ranges is not None else 'None'})")
+    batched = x.dim() == 3
+    lead = tuple(y.shape[:-1])
+    vector = feat.dim() == len(lead)
+    if tuple(feat.shape[:len(lead)]) != lead or feat.dim() not in (len(lead), len(lead) + 1):
+        raise ValueError(f"geomloss_amd.hip.plan_apply: expected features of shape {lead} or {lead + ('V',)}, got {tuple(feat.shape)}")
+    with torch.no_grad():
+        xb, yb, hb, _ = _as_batched(_points(x.detach(), "x"), _points(y.detach(), "y"), _f32(h))
+        if yb.dtype != xb.dtype:
+            yb = yb.to(xb.dtype)
+        B, M = yb.shape[0], yb.shape[1]
+        fb = _f32(feat).to(xb.device).reshape(B, M, -1)
+        flags = int(flags) | ENV_FLAGS
+        fwd_b = softmin_fwd_raw(xb, yb, hb, eps, 2, None, flags) if fwd is None else _f32(fwd).reshape(B, -1)
+        out = plan_apply_raw(xb, yb, hb, fwd_b, fb, float(eps), flags)
+    if not batched:
+        out = out[0]
+    return out[..., 0] if vector else out
 
 
 def fused_step_applies(D, p=2, flags=0, sparse=False):

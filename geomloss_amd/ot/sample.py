@@ -215,6 +215,11 @@ def solve_sample_batch(*args, **kwargs):
 #  results
 # ---------------------------------------------------------------------------------------------------------------------
 
+# columns from which `plan_operator @ S` goes through hip.plan_apply: one forward reduction + an application worth ~4 of them
+# (measured, profiles/plan_apply.txt) against the 2 V forward reductions of the log-domain loop
+PLAN_APPLY_MIN_COLUMNS = 3
+
+
 class LinearOperator:
     """Matrix-free linear map with a transpose (``_ot_result.py:7-160``): ``op @ v``, ``op.T``, ``op.shape``."""
 
@@ -320,10 +325,21 @@ class OTResultSample:
         return d * a[:, None] * b[None, :]
 
     def _apply_density(self, rows, cols, f_rows, g_cols, s):
-        """sum_j exp((f_i + g_j - C_ij)/eps) s_jv for s (M, V), through soft-min reductions in the log domain: positive and
-        negative parts of every column of s are reduced separately, so no exponential of a raw potential is ever formed."""
+        """sum_j exp((f_i + g_j - C_ij)/eps) s_jv for s (M, V).  Where ``hip.plan_apply`` applies (fp32 / bf16 compute, D <= 16): the
+        row-normalised average of s under the plan, times the row sums known from one forward reduction — from
+        ``PLAN_APPLY_MIN_COLUMNS`` columns on.  Otherwise, and for one or two columns, through soft-min reductions in the log domain: positive and negative parts of every column of s
+        are reduced separately.  Either way no exponential of a raw potential is ever formed."""
         eps = self._reg
         s = s.to(device=rows.device, dtype=torch.float32)
+        # One forward reduction + one matrix-core application of the plan (hip.plan_apply) wherever that kernel serves the clouds and
+        # is the cheaper route.  An application costs about four forward reductions whatever the width (up to 32 columns), the
+        # log-domain loop below at most 2 V of them: one or two columns stay on the loop (a single nonnegative column — what
+        # marginal_a / marginal_b send — is ONE forward reduction there, V = 1 with mixed signs two, V = 2 at most four).
+        if s.shape[1] >= PLAN_APPLY_MIN_COLUMNS and hip.plan_apply_applies(rows):
+            h = (g_cols / eps).detach()
+            fwd = hip.softmin(eps / 2, rows.detach(), cols.detach(), h)      # the library's C = |x - y|^2 / 2 against the solver's |x - y|^2
+            avg = hip.plan_apply(eps / 2, rows.detach(), cols.detach(), h, s, fwd=fwd)
+            return ((f_rows - 2.0 * fwd) / eps).exp()[:, None] * avg
         out = torch.zeros((rows.shape[0], s.shape[1]), dtype=torch.float32, device=rows.device)
         for v in range(s.shape[1]):
             for sign in (1.0, -1.0):

@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 123 /* 0.1.23 */
+#define GLHIP_VERSION 124 /* 0.1.24 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
@@ -338,8 +338,9 @@ int glhip_lse_lines_bwd(const float* h, const float* lse, const float* grad_out,
  * Replaces: the symbolic KeOps `Grad` of the generic_logsumexp above.
  * (p = 1, dense, 4 <= D <= 16: glhip_dist_xd.h since round 5 — distances from the MFMA chain, near pairs from the points themselves.)
  * D > 16: the one-thread-per-row kernel of glhip_generic.h, in ANY dimension (version 121; D <= 64 before): 64 output coordinates
- * per pass over the columns, ceil(D / 64) passes.  The same holds for glhip_kernel_conv_bwd_x.  A matrix-core gradient for D > 16
- * (the weighted sums sum_j w_ij y_j as a second MFMA product) is not part of the library yet.
+ * per pass over the columns, ceil(D / 64) passes.  The same holds for glhip_kernel_conv_bwd_x.  The weighted sums sum_j w_ij q_j as
+ * a second MFMA product over all 32 MFMA rows live in glhip_plan_apply below (glhip_plan_apply.h, version 124: any number of feature
+ * columns, D <= 16); the D > 16 gradient does not use that product yet and stays on the one-thread-per-row kernel.
  *   out = the saved forward result (B,N);  grad_out (B,N) fp32;  grad_x (B,N,D) fp32.
  */
 int glhip_softmin_bwd_x(const void* x, const void* y, const float* h,
@@ -348,6 +349,39 @@ int glhip_softmin_bwd_x(const void* x, const void* y, const float* h,
                         const int32_t* ranges_i, const int32_t* slices_i,
                         const int32_t* redranges_j, int n_ranges,
                         void* workspace, size_t workspace_bytes, int flags, void* stream);
+
+/*
+ * Application of the transport plan of a p = 2 soft-min to a feature matrix (version 124; glhip_plan_apply.h).  With
+ * C_ij = |x_i - y_j|^2 / 2 and fwd (B,N) the saved result of glhip_softmin_fwd for the same x, y, h, eps:
+ *   w_ij       = exp( h_j - C_ij/eps + fwd_i/eps )
+ *   mass_i     = sum_j w_ij                                   (= 1 up to rounding)
+ *   out[b,i,v] = sum_j w_ij feat[b,j,v] / mass_i              (0 where mass_i == 0: a row whose columns all carry h = -inf; either layout)
+ * Dividing by the recomputed mass cancels the common-mode error of a row's exponents, as in glhip_softmin_bwd_x; a caller that wants
+ * the unnormalised product multiplies by exp(-fwd_i / eps), which the forward gives exactly.
+ * Replaces: `P @ S` on the reference's symbolic plans (ot/_implementations/sample.py lazy_plan / plan_operator / density_operator).
+ *   feat (B,M,V) row-major fp32, V >= 1 any size;  out (B,N,V) fp32;  mass (B,N) fp32 or NULL;  x, y fp32 or bf16.
+ *   One pass over the columns per 128 features for D <= 4, per 64 for 5 <= D <= 11, per 32 beyond (a remainder is a pass of its own): the exponent block and the two f16 pieces of its 16
+ *   weights per lane are shared by up to four chunks of 32 features, each a second MFMA product (three piece products = six MFMAs per
+ *   chunk, fresh accumulator per 32 columns); features are split into two f16 pieces under a power-of-two scale per column and tile,
+ *   found on the device.  Inside the kernel the weights are taken relative to the running maximum of their row (fwd centres the
+ *   exponents and scales `mass`; an inaccurate fwd costs no accuracy in `out`), so the largest weight of a row is exact and a one-hot
+ *   plan row returns its features bit for bit.  Rounding of the product: <= 2e-7 of sum_j w_ij |feat_jv| (tools/plan_apply_model.py), next to the ~1e-6 the
+ *   exponents leave.
+ *   Supported: p == 2, 1 <= D <= 16, dense launches (n_ranges == 0), any B; anything else returns GLHIP_EUNSUPPORTED (the range
+ *   arguments are there so that block-sparse plans can follow without an ABI change).  N == 0, M == 0, V == 0: nothing is launched
+ *   (M == 0 or a zero-size feat with N > 0: out and mass are zeroed).
+ *   flags: GLHIP_FLAG_F16X2 (exponents from f16 x 2 pieces, under that flag's range contract), GLHIP_FLAG_NO_SPLIT; others are ignored.
+ *   Workspace: glhip_plan_apply_workspace_bytes holds the (sums, mass, row maximum) partials of the column splits the launch would like,
+ *   and never asks for more than 1 GiB (big launches have row blocks enough and split little); NULL or short means fewer or
+ *   no splits — the same results up to summation order.
+ */
+size_t glhip_plan_apply_workspace_bytes(int B, int N, int M, int D, int V);
+
+int glhip_plan_apply(const void* x, const void* y, const float* h, const float* fwd, const float* feat,
+                     float* out, float* mass,
+                     int B, int N, int M, int D, int V, float eps, int p, int in_dtype,
+                     const int32_t* ranges_i, const int32_t* slices_i, const int32_t* redranges_j, int n_ranges,
+                     void* workspace, size_t workspace_bytes, int flags, void* stream);
 
 /*
  * Kernel-matrix × vector product  out[b,i] = sum_j k(x[b,i], y[b,j]) * v[b,j].

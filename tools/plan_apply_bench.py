@@ -1,0 +1,88 @@
+"""GPU box: the transport plan applied to feature matrices, timed with HIP events — ``plan_operator @ S`` of an ``ot.solve_sample``
+result and the raw ``glhip_plan_apply`` launch, D = 3, N = M = --n (default 2e5), V in {1 mixed-sign, 2, 3, 32, 128}; optionally one
+V = 32 product at --big (1e6: 3 calls after 1).  Medians over --launches calls after --warmup warm-up calls, with the spread
+(max - min) / median.
+
+    python tools/plan_apply_bench.py                 # one forward reduction + one matrix-core application per product
+    python tools/plan_apply_bench.py --legacy        # the log-domain path for every width: 2 V forward reductions per product.  Copied
+                                                     # into a checkout of a commit without glhip_plan_apply, this is how that commit is timed
+
+The solve itself is not timed: the potentials are a few Sinkhorn iterations at a moderate temperature, enough for a well-formed plan."""
+import argparse
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+from geomloss_amd import hip, ot  # noqa: E402
+
+
+def timed(fn, launches, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(launches):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    med = statistics.median(ms)
+    return med, min(ms), (max(ms) - min(ms)) / med
+
+
+def features(n, V, g, dev):
+    return torch.randn(n, V, generator=g).to(dev)      # standard normal: every column changes sign
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=200_000)
+    ap.add_argument("--big", type=int, default=0, help="one more V = 32 product at this N = M (1e6), 3 calls")
+    ap.add_argument("--launches", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--widths", type=int, nargs="*", default=[1, 2, 3, 32, 128])
+    ap.add_argument("--legacy", action="store_true", help="log-domain path: 2 V forward reductions per product")
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    lib = hip.load_library()
+    if args.legacy:
+        hip.plan_apply_applies = lambda *a, **k: False
+    mode = ("log-domain path (2 V forward reductions)" if args.legacy
+            else "glhip_plan_apply (1 forward reduction + 1 application) from 3 columns on, log-domain path below")
+    print(f"# libgeomloss_hip {lib.glhip_version()}; {mode}; D = 3, float32; median (min, spread) of {args.launches} calls after "
+          f"{args.warmup} (N = M = --big: 3 after 1); {torch.cuda.get_device_name(0)}")
+
+    def run(n, widths, launches, warmup):
+        g = torch.Generator().manual_seed(n)
+        x, y = torch.rand(n, 3, generator=g).to(dev), torch.rand(n, 3, generator=g).to(dev)
+        res = ot.solve_sample(x, y, reg=0.05**2 * 2, max_iter=5)
+        op = res.plan_operator
+        for V in widths:
+            S = features(n, V, g, dev)
+            med, lo, spread = timed(lambda: op @ S, launches, warmup)
+            print(f"plan_operator @ S   N=M={n:8d} V={V:4d}  {med:10.3f} ms (min {lo:10.3f}, spread {spread:5.1%})", flush=True)
+        if args.legacy:
+            return
+        eps = 0.05**2
+        xb, yb = x[None].contiguous(), y[None].contiguous()
+        hb = (torch.randn(1, n, generator=g) * 2).to(dev)
+        fwd = hip.softmin_fwd_raw(xb, yb, hb, eps, 2, None, 0)
+        med, lo, spread = timed(lambda: hip.softmin_fwd_raw(xb, yb, hb, eps, 2, None, 0), launches, warmup)
+        print(f"glhip_softmin_fwd   N=M={n:8d}         {med:10.3f} ms (min {lo:10.3f}, spread {spread:5.1%})", flush=True)
+        for V in widths:
+            S = features(n, V, g, dev)[None].contiguous()
+            med, lo, spread = timed(lambda: hip.plan_apply_raw(xb, yb, hb, fwd, S, eps, 0), launches, warmup)
+            print(f"glhip_plan_apply    N=M={n:8d} V={V:4d}  {med:10.3f} ms (min {lo:10.3f}, spread {spread:5.1%})", flush=True)
+
+    run(args.n, args.widths, args.launches, args.warmup)
+    if args.big:
+        run(args.big, [32], 3, 1)
+    torch.cuda.synchronize()
+
+
+if __name__ == "__main__":
+    main()
