@@ -6,16 +6,6 @@ namespace {
 
 constexpr size_t kPlanMaxWorkspace = (size_t)1 << 30;      // glhip_plan_apply_workspace_bytes never asks for more than 1 GiB (glhip.h)
 
-// THE split policy of a pass, shared by the launcher and by the sizing call: the rule of every split launch (choose_splits), or — dense
-// launches with room for 8 splits over >= 65536 columns (SplitLaunch::xcd_eligible) — the XCD-aware grid with xcd_splits.
-// `fit`: splits the workspace holds; `slots`: resident workgroups of the kernel shape.
-struct PlanSplits { int n; bool xcd; };
-inline PlanSplits plan_splits(long row_blocks, int M, long fit, bool allow_split, long slots) {
-    if (!allow_split || fit < 2) return PlanSplits{1, false};
-    if (fit >= 8 && M >= 65536) return PlanSplits{xcd_splits(row_blocks, M, slots, fit), true};
-    return PlanSplits{choose_splits(row_blocks, M, 0, fit), false};
-}
-
 template <int D, typename T, int NCH, int L>
 void launch_plan_pass(const PlanParams<T>& prm, int B, int N, int M, const Scratch& sc, hipStream_t st) {
     const Ranges none{nullptr, nullptr, nullptr, nullptr};

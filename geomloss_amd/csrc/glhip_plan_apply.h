@@ -368,7 +368,8 @@ plan_apply_kernel(PlanParams<T> prm, int N, int M, SplitInfo sp) {
 
 // Combines the column splits of a pass: one thread per (row, feature).  The partials of a row are nv sums, the mass — both relative
 // to 2^m of their split — and m: the splits are brought to the largest m (factor exactly 1 for the split that holds it), added and divided.
-__global__ void __launch_bounds__(kBlock)
+// (static: two translation units launch it — glhip_api_plan.hip and glhip_api_plan_xk.hip — as with build_row_chunks_kernel)
+static __global__ void __launch_bounds__(kBlock)
 plan_merge_kernel(float* __restrict__ out, float* __restrict__ mass, long rows, int V, int v0, int nv, SplitInfo sp) {
     const long id = (long)blockIdx.x * kBlock + threadIdx.x;
     if (id >= rows * nv) return;

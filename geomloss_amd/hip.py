@@ -29,6 +29,7 @@ XD_MAX_DIM = 16                 # the fused four-softmin iteration / annealing /
                                 # gradients stop at this dimension (glhip_softmin_xd.h, glhip_wsum_t32.h)
 MFMA_FWD_MAX_DIM = 4095         # p = 2 soft-min forward / half-step and gaussian product run on the matrix cores up to this dimension
                                 # (17 ... 4095: the K-chunked kernel of glhip_softmin_xk.h; kept in step with the library by tests/test_anyd_kernels_gpu.py)
+PLAN_MAX_DIM = 4095             # plan_apply_nd applies p = 2 transport plans to features up to this dimension (17 ... 4095: glhip_plan_apply_xk.h)
 # kernel families reported by softmin_fwd_family (GLHIP_FAMILY_* of glhip.h)
 FAMILY_VALU, FAMILY_X32, FAMILY_XD, FAMILY_XK, FAMILY_DIST, FAMILY_GENERIC = 0, 1, 2, 3, 4, 5
 
@@ -57,6 +58,10 @@ SIGNATURES = {
                                      _c_int] + _RANGES + _TAIL),
     "glhip_plan_apply_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "glhip_plan_apply": (_c_int, [_vp] * 7 + [_c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int, _c_int] + _RANGES + _TAIL),
+    "glhip_plan_apply_nd_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "glhip_plan_apply_nd_family": (_c_int, [_c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int]),
+    "glhip_plan_apply_nd_pass_width": (_c_int, [_c_int]),
+    "glhip_plan_apply_nd": (_c_int, [_vp] * 7 + [_c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int, _c_int] + _RANGES + _TAIL),
     "glhip_kernel_conv_fwd": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int]
                               + _RANGES + _TAIL),
     "glhip_kernel_conv_bwd_x": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float,
@@ -349,28 +354,40 @@ def softmin_bwd_x_raw(x, y, h, out, grad_out, eps, p=2, ranges=None, flags=0):
     return gx
 
 
-def plan_apply_raw(x, y, h, fwd, feat, eps, flags=0, want_mass=False, p=2, ranges=None, workspace=True):
-    """The plan of a p = 2 soft-min applied to features (``glhip_plan_apply``): x (B,N,D), y (B,M,D) fp32|bf16, h (B,M), fwd (B,N) the
-    saved soft-min, feat (B,M,V) fp32 -> (B,N,V) fp32 row-normalised averages [, (B,N) recomputed row masses].  ``workspace=False``
-    passes no workspace: the launch runs without column splits (same results up to summation order)."""
+def _plan_apply_call(entry, x, y, h, fwd, feat, eps, flags, want_mass, p, ranges, workspace):
+    """``glhip_plan_apply`` (D <= 16) or ``glhip_plan_apply_nd`` (D <= 4095) with its own workspace sizing call."""
     lib = load_library()
     B, N, D = x.shape
     M, V = y.shape[1], feat.shape[2]
     if is_f64(x):
-        raise NotImplementedError("glhip_plan_apply: float64 clouds are not supported (cast to float32)")
+        raise NotImplementedError(f"{entry}: float64 clouds are not supported (cast to float32)")
     if tuple(feat.shape[:2]) != (B, M) or tuple(h.shape) != (B, M) or tuple(fwd.shape) != (B, N):
-        raise ValueError(f"glhip_plan_apply: expected h {(B, M)}, fwd {(B, N)}, feat {(B, M, 'V')}; got {tuple(h.shape)}, "
+        raise ValueError(f"{entry}: expected h {(B, M)}, fwd {(B, N)}, feat {(B, M, 'V')}; got {tuple(h.shape)}, "
                          f"{tuple(fwd.shape)}, {tuple(feat.shape)}")
     out = torch.empty((B, N, V), dtype=torch.float32, device=x.device)
     mass = torch.empty((B, N), dtype=torch.float32, device=x.device) if want_mass else None
     with torch.cuda.device(x.device):
-        nbytes = int(lib.glhip_plan_apply_workspace_bytes(B, N, M, D, V)) if workspace else 0
+        nbytes = int(getattr(lib, entry + "_workspace_bytes")(B, N, M, D, V)) if workspace else 0
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
-        rc = lib.glhip_plan_apply(x.data_ptr(), y.data_ptr(), h.data_ptr(), fwd.data_ptr(), feat.data_ptr(), out.data_ptr(),
-                                  None if mass is None else mass.data_ptr(), B, N, M, D, V, float(eps), int(p), _dtype_code(x),
-                                  *_range_args(ranges, B), None if ws is None else ws.data_ptr(), nbytes, int(flags), _stream(x))
+        rc = getattr(lib, entry)(x.data_ptr(), y.data_ptr(), h.data_ptr(), fwd.data_ptr(), feat.data_ptr(), out.data_ptr(),
+                                 None if mass is None else mass.data_ptr(), B, N, M, D, V, float(eps), int(p), _dtype_code(x),
+                                 *_range_args(ranges, B), None if ws is None else ws.data_ptr(), nbytes, int(flags), _stream(x))
     _check(rc, lib)
     return (out, mass) if want_mass else out
+
+
+def plan_apply_raw(x, y, h, fwd, feat, eps, flags=0, want_mass=False, p=2, ranges=None, workspace=True):
+    """The plan of a p = 2 soft-min applied to features (``glhip_plan_apply``, D <= 16 — this contract stays; any D <= 4095:
+    :func:`plan_apply_nd_raw`): x (B,N,D), y (B,M,D) fp32|bf16, h (B,M), fwd (B,N) the
+    saved soft-min, feat (B,M,V) fp32 -> (B,N,V) fp32 row-normalised averages [, (B,N) recomputed row masses].  ``workspace=False``
+    passes no workspace: the launch runs without column splits (same results up to summation order)."""
+    return _plan_apply_call("glhip_plan_apply", x, y, h, fwd, feat, eps, flags, want_mass, p, ranges, workspace)
+
+
+def plan_apply_nd_raw(x, y, h, fwd, feat, eps, flags=0, want_mass=False, p=2, ranges=None, workspace=True):
+    """:func:`plan_apply_raw` for any D <= PLAN_MAX_DIM (``glhip_plan_apply_nd``): D <= 16 is the very launch of ``glhip_plan_apply``,
+    17 <= D <= 4095 the K-chunked kernel of glhip_plan_apply_xk.h."""
+    return _plan_apply_call("glhip_plan_apply_nd", x, y, h, fwd, feat, eps, flags, want_mass, p, ranges, workspace)
 
 
 def softmin_fwd_grad_raw(x, y, h, guess, margin, eps, ranges=None, flags=0):
@@ -1111,6 +1128,51 @@ def plan_apply_applies(x, p=2, ranges=None):
     return p == 2 and ranges is None and x.shape[-1] <= XD_MAX_DIM and x.dtype != torch.float64
 
 
+def plan_apply_nd_applies(x, p=2, ranges=None):
+    """Whether :func:`plan_apply_nd` serves clouds like ``x``: p = 2, dense, D <= PLAN_MAX_DIM, float32 / bfloat16 compute."""
+    return p == 2 and ranges is None and x.shape[-1] <= PLAN_MAX_DIM and x.dtype != torch.float64
+
+
+def plan_apply_nd_family(B, N, M, D, V, p=2, dtype=torch.float32, flags=0, n_ranges=0):
+    """The kernel family (FAMILY_XD for D <= 16, FAMILY_XK for 17 <= D <= PLAN_MAX_DIM) that ``glhip_plan_apply_nd`` selects: the
+    predicate the launch itself evaluates, host arithmetic only.  Raises ``NotImplementedError`` for valid requests without a
+    kernel and ``ValueError`` for what the entry point rejects."""
+    lib = load_library()
+    code = {torch.float32: 0, torch.bfloat16: 1}.get(dtype, -1)
+    fam = int(lib.glhip_plan_apply_nd_family(int(B), int(N), int(M), int(D), int(V), int(p), code, int(flags), int(n_ranges)))
+    if fam == -2:
+        raise NotImplementedError(f"glhip_plan_apply_nd: no kernel for p = {p}, D = {D}, n_ranges = {n_ranges}")
+    if fam < 0:
+        raise ValueError(f"glhip_plan_apply_nd_family: bad arguments {(B, N, M, D, V, p, dtype, flags, n_ranges)}")
+    return fam
+
+
+def _plan_apply(name, raw, max_dim, eps, x, y, h, feat, fwd, flags, p, ranges):
+    D = x.shape[-1]
+    if x.dtype == torch.float64 or y.dtype == torch.float64:
+        raise NotImplementedError(f"geomloss_amd.hip.{name}: float64 clouds are not supported (cast to float32)")
+    if p != 2 or D > max_dim or ranges is not None:
+        raise NotImplementedError(f"geomloss_amd.hip.{name}: only p = 2, D <= {max_dim}, dense plans (got p = {p}, D = {D}, "
+                                  f"ranges {'given' if ranges is not None else 'None'})")
+    batched = x.dim() == 3
+    lead = tuple(y.shape[:-1])
+    vector = feat.dim() == len(lead)
+    if tuple(feat.shape[:len(lead)]) != lead or feat.dim() not in (len(lead), len(lead) + 1):
+        raise ValueError(f"geomloss_amd.hip.{name}: expected features of shape {lead} or {lead + ('V',)}, got {tuple(feat.shape)}")
+    with torch.no_grad():
+        xb, yb, hb, _ = _as_batched(_points(x.detach(), "x"), _points(y.detach(), "y"), _f32(h))
+        if yb.dtype != xb.dtype:
+            yb = yb.to(xb.dtype)
+        B, M = yb.shape[0], yb.shape[1]
+        fb = _f32(feat).to(xb.device).reshape(B, M, -1)
+        flags = int(flags) | ENV_FLAGS
+        fwd_b = softmin_fwd_raw(xb, yb, hb, eps, 2, None, flags) if fwd is None else _f32(fwd).reshape(B, -1)
+        out = raw(xb, yb, hb, fwd_b, fb, float(eps), flags)
+    if not batched:
+        out = out[0]
+    return out[..., 0] if vector else out
+
+
 def plan_apply(eps, x, y, h, feat, fwd=None, flags=0, p=2, ranges=None):
     """Row-normalised application of the plan of a p = 2 soft-min to a feature matrix on the matrix cores (``glhip_plan_apply``):
 
@@ -1124,30 +1186,18 @@ def plan_apply(eps, x, y, h, feat, fwd=None, flags=0, p=2, ranges=None):
     of their row, and ``out`` is divided by the recomputed row sum: ``fwd`` only centres the exponents (an error of a few units of
     ``eps`` in it costs no accuracy in ``out``; it must be close enough for the exponents to stay in range), and one-hot plan rows
     return their features bit for bit.  NOT an autograd function: it runs under ``torch.no_grad()`` and returns a tensor without
-    ``grad_fn``.  float64 clouds, p = 1, D > 16 and block-sparse ranges raise ``NotImplementedError``."""
-    D = x.shape[-1]
-    if x.dtype == torch.float64 or y.dtype == torch.float64:
-        raise NotImplementedError("geomloss_amd.hip.plan_apply: float64 clouds are not supported (cast to float32)")
-    if p != 2 or D > XD_MAX_DIM or ranges is not None:
-        raise NotImplementedError(f"geomloss_amd.hip.plan_apply: only p = 2, D <= {XD_MAX_DIM}, dense plans (got p = {p}, D = {D}, "
-                                  f"ranges {'given' if ranges is not None else 'None'})")
-    batched = x.dim() == 3
-    lead = tuple(y.shape[:-1])
-    vector = feat.dim() == len(lead)
-    if tuple(feat.shape[:len(lead)]) != lead or feat.dim() not in (len(lead), len(lead) + 1):
-        raise ValueError(f"geomloss_amd.hip.plan_apply: expected features of shape {lead} or {lead + ('V',)}, got {tuple(feat.shape)}")
-    with torch.no_grad():
-        xb, yb, hb, _ = _as_batched(_points(x.detach(), "x"), _points(y.detach(), "y"), _f32(h))
-        if yb.dtype != xb.dtype:
-            yb = yb.to(xb.dtype)
-        B, M = yb.shape[0], yb.shape[1]
-        fb = _f32(feat).to(xb.device).reshape(B, M, -1)
-        flags = int(flags) | ENV_FLAGS
-        fwd_b = softmin_fwd_raw(xb, yb, hb, eps, 2, None, flags) if fwd is None else _f32(fwd).reshape(B, -1)
-        out = plan_apply_raw(xb, yb, hb, fwd_b, fb, float(eps), flags)
-    if not batched:
-        out = out[0]
-    return out[..., 0] if vector else out
+    ``grad_fn``.  float64 clouds, p = 1, D > 16 and block-sparse ranges raise ``NotImplementedError``; :func:`plan_apply_nd` is the
+    same function for any D <= PLAN_MAX_DIM = 4095."""
+    return _plan_apply("plan_apply", plan_apply_raw, XD_MAX_DIM, eps, x, y, h, feat, fwd, flags, p, ranges)
+
+
+def plan_apply_nd(eps, x, y, h, feat, fwd=None, flags=0, p=2, ranges=None):
+    """:func:`plan_apply` for clouds of any dimension D <= PLAN_MAX_DIM = 4095 (``glhip_plan_apply_nd``).  D <= 16 runs the very
+    launch of :func:`plan_apply`; for 17 <= D <= 4095 the exponent blocks come from the K-chunked kernel of the forward reduction
+    of these dimensions (glhip_plan_apply_xk.h) and a pass carries up to 64 feature columns.  Same shapes, same semantics
+    (row-normalised, one-hot rows bit for bit, rows without mass give 0), not an autograd function.  float64 clouds, p = 1,
+    D > 4095 and block-sparse ranges raise ``NotImplementedError``."""
+    return _plan_apply("plan_apply_nd", plan_apply_nd_raw, PLAN_MAX_DIM, eps, x, y, h, feat, fwd, flags, p, ranges)
 
 
 def fused_step_applies(D, p=2, flags=0, sparse=False):

@@ -215,9 +215,15 @@ def solve_sample_batch(*args, **kwargs):
 #  results
 # ---------------------------------------------------------------------------------------------------------------------
 
-# columns from which `plan_operator @ S` goes through hip.plan_apply: one forward reduction + an application worth ~4 of them
+# columns from which `plan_operator @ S` goes through hip.plan_apply_nd: one forward reduction + an application worth ~4 of them
 # (measured, profiles/plan_apply.txt) against the 2 V forward reductions of the log-domain loop
 PLAN_APPLY_MIN_COLUMNS = 3
+# ... and for clouds of 17 <= D <= 4095 (glhip_plan_apply_xk.h).  NOT MEASURED yet: no timing of that kernel exists.  The value is the
+# conservative one its cost model allows: a pass issues NM + 6 NCH MFMAs per block where a forward issues NM >= 7, on one workgroup per
+# CU instead of two, and a pass worth more than ~15 forward reductions would mean the kernel does not follow that model — so one
+# forward + one pass is at most ~16 forwards, what the loop spends on 8 mixed-sign columns.  To be lowered to the smallest V at which
+# `tools/plan_apply_bench.py --dims 32 64 128` shows the new route ahead of `--legacy`.
+PLAN_APPLY_ND_MIN_COLUMNS = 8
 
 
 class LinearOperator:
@@ -325,20 +331,22 @@ class OTResultSample:
         return d * a[:, None] * b[None, :]
 
     def _apply_density(self, rows, cols, f_rows, g_cols, s):
-        """sum_j exp((f_i + g_j - C_ij)/eps) s_jv for s (M, V).  Where ``hip.plan_apply`` applies (fp32 / bf16 compute, D <= 16): the
+        """sum_j exp((f_i + g_j - C_ij)/eps) s_jv for s (M, V).  Where ``hip.plan_apply_nd`` applies (fp32 / bf16 compute, D <= 4095): the
         row-normalised average of s under the plan, times the row sums known from one forward reduction — from
-        ``PLAN_APPLY_MIN_COLUMNS`` columns on.  Otherwise, and for one or two columns, through soft-min reductions in the log domain: positive and negative parts of every column of s
+        ``PLAN_APPLY_MIN_COLUMNS`` columns on (D <= 16; ``PLAN_APPLY_ND_MIN_COLUMNS`` beyond).  Otherwise, and below those widths, through soft-min reductions in the log domain: positive and negative parts of every column of s
         are reduced separately.  Either way no exponential of a raw potential is ever formed."""
         eps = self._reg
         s = s.to(device=rows.device, dtype=torch.float32)
-        # One forward reduction + one matrix-core application of the plan (hip.plan_apply) wherever that kernel serves the clouds and
-        # is the cheaper route.  An application costs about four forward reductions whatever the width (up to 32 columns), the
-        # log-domain loop below at most 2 V of them: one or two columns stay on the loop (a single nonnegative column — what
-        # marginal_a / marginal_b send — is ONE forward reduction there, V = 1 with mixed signs two, V = 2 at most four).
-        if s.shape[1] >= PLAN_APPLY_MIN_COLUMNS and hip.plan_apply_applies(rows):
+        # One forward reduction + one matrix-core application of the plan (hip.plan_apply_nd) wherever that kernel serves the clouds and
+        # is the cheaper route.  For D <= 16 an application costs about four forward reductions whatever the width (up to 32 columns),
+        # the log-domain loop below at most 2 V of them: one or two columns stay on the loop (a single nonnegative column — what
+        # marginal_a / marginal_b send — is ONE forward reduction there, V = 1 with mixed signs two, V = 2 at most four).  For D >= 17
+        # the cost of an application is not measured yet: the threshold is the conservative one explained at its definition.
+        min_columns = PLAN_APPLY_MIN_COLUMNS if rows.shape[-1] <= hip.XD_MAX_DIM else PLAN_APPLY_ND_MIN_COLUMNS
+        if s.shape[1] >= min_columns and hip.plan_apply_nd_applies(rows):
             h = (g_cols / eps).detach()
             fwd = hip.softmin(eps / 2, rows.detach(), cols.detach(), h)      # the library's C = |x - y|^2 / 2 against the solver's |x - y|^2
-            avg = hip.plan_apply(eps / 2, rows.detach(), cols.detach(), h, s, fwd=fwd)
+            avg = hip.plan_apply_nd(eps / 2, rows.detach(), cols.detach(), h, s, fwd=fwd)
             return ((f_rows - 2.0 * fwd) / eps).exp()[:, None] * avg
         out = torch.zeros((rows.shape[0], s.shape[1]), dtype=torch.float32, device=rows.device)
         for v in range(s.shape[1]):

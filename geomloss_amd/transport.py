@@ -5,9 +5,10 @@
     P_ij = a_i b_j exp((F_i + G_j - |x_i - y_j|^2 / 2) / blur^2)
 
 without ever forming it.  The functions below push features through that plan — labels, colours, the barycentric map — with one
-soft-min reduction and one matrix-core application of the plan (:func:`geomloss_amd.hip.plan_apply`), at any N, M the solver itself
-handles.  GPU tensors only, like the ``online`` backend; p = 2, D <= 16, float32 / bfloat16 clouds.  Nothing here is recorded by
-autograd.
+soft-min reduction and one matrix-core application of the plan (:func:`geomloss_amd.hip.plan_apply_nd`), at any N, M the solver
+itself handles.  GPU tensors only, like the ``online`` backend; p = 2, float32 / bfloat16 clouds of dimension D <= 4095: D <= 16 on
+the kernel with resident operands (up to 128 feature columns per pass), 17 <= D <= 4095 — principal components, embeddings — on the
+K-chunked kernel (64 per pass); beyond, ``NotImplementedError``.  Nothing here is recorded by autograd.
 """
 
 import math
@@ -39,7 +40,7 @@ def apply_plan(x, y, F, G, feat, blur, a=None, b=None, transpose=False):
         Gf = G.detach().float().reshape(y.shape[:-1])
         h = _log_weights(b, Gf, M) + Gf / eps
         fwd = hip.softmin(eps, x.detach(), y.detach(), h)              # sum_j b_j exp((G_j - C_ij) / eps) = exp(-fwd_i / eps)
-        avg = hip.plan_apply(eps, x, y, h, feat, fwd=fwd)
+        avg = hip.plan_apply_nd(eps, x, y, h, feat, fwd=fwd)
         rows = (_log_weights(a, Ff, N) + (Ff - fwd) / eps).exp()       # sum_j P_ij
         return rows * avg if avg.dim() == rows.dim() else rows.unsqueeze(-1) * avg
 
@@ -52,4 +53,4 @@ def barycentric_map(x, y, F, G, blur, b=None):
     with torch.no_grad():
         Gf = G.detach().float().reshape(y.shape[:-1])
         h = _log_weights(b, Gf, y.shape[-2]) + Gf / eps
-        return hip.plan_apply(eps, x, y, h, y.detach().float())
+        return hip.plan_apply_nd(eps, x, y, h, y.detach().float())

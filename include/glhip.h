@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 124 /* 0.1.24 */
+#define GLHIP_VERSION 125 /* 0.1.25 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
@@ -340,7 +340,9 @@ int glhip_lse_lines_bwd(const float* h, const float* lse, const float* grad_out,
  * D > 16: the one-thread-per-row kernel of glhip_generic.h, in ANY dimension (version 121; D <= 64 before): 64 output coordinates
  * per pass over the columns, ceil(D / 64) passes.  The same holds for glhip_kernel_conv_bwd_x.  The weighted sums sum_j w_ij q_j as
  * a second MFMA product over all 32 MFMA rows live in glhip_plan_apply below (glhip_plan_apply.h, version 124: any number of feature
- * columns, D <= 16); the D > 16 gradient does not use that product yet and stays on the one-thread-per-row kernel.
+ * columns, D <= 16) and, for 17 <= D <= 4095, in glhip_plan_apply_nd (glhip_plan_apply_xk.h, version 125); the D > 16 gradient does
+ * not use that product yet and stays on the one-thread-per-row kernel (its 5e-6 test bound is met by explicit differences; whether the
+ * MFMA chain's exponents meet it is measured by tests/test_plan_apply_nd_gpu.py).
  *   out = the saved forward result (B,N);  grad_out (B,N) fp32;  grad_x (B,N,D) fp32.
  */
 int glhip_softmin_bwd_x(const void* x, const void* y, const float* h,
@@ -367,9 +369,10 @@ int glhip_softmin_bwd_x(const void* x, const void* y, const float* h,
  *   exponents and scales `mass`; an inaccurate fwd costs no accuracy in `out`), so the largest weight of a row is exact and a one-hot
  *   plan row returns its features bit for bit.  Rounding of the product: <= 2e-7 of sum_j w_ij |feat_jv| (tools/plan_apply_model.py), next to the ~1e-6 the
  *   exponents leave.
- *   Supported: p == 2, 1 <= D <= 16, dense launches (n_ranges == 0), any B; anything else returns GLHIP_EUNSUPPORTED (the range
+ *   Supported: p == 2, 1 <= D <= 16 (this contract stays: D >= 17 goes through glhip_plan_apply_nd below), dense launches
+ *   (n_ranges == 0), any B; anything else returns GLHIP_EUNSUPPORTED (the range
  *   arguments are there so that block-sparse plans can follow without an ABI change).  N == 0, M == 0, V == 0: nothing is launched
- *   (M == 0 or a zero-size feat with N > 0: out and mass are zeroed).
+ *   (M == 0 with N > 0: out and mass are zeroed; V == 0: out is empty and mass is left as it is — glhip_plan_apply_nd zeroes it).
  *   flags: GLHIP_FLAG_F16X2 (exponents from f16 x 2 pieces, under that flag's range contract), GLHIP_FLAG_NO_SPLIT; others are ignored.
  *   Workspace: glhip_plan_apply_workspace_bytes holds the (sums, mass, row maximum) partials of the column splits the launch would like,
  *   and never asks for more than 1 GiB (big launches have row blocks enough and split little); NULL or short means fewer or
@@ -382,6 +385,35 @@ int glhip_plan_apply(const void* x, const void* y, const float* h, const float* 
                      int B, int N, int M, int D, int V, float eps, int p, int in_dtype,
                      const int32_t* ranges_i, const int32_t* slices_i, const int32_t* redranges_j, int n_ranges,
                      void* workspace, size_t workspace_bytes, int flags, void* stream);
+
+/*
+ * The same application in any dimension up to 4095 (version 125).  glhip_plan_apply and glhip_plan_apply_workspace_bytes keep their
+ * D <= 16 contract (D = 17 returns GLHIP_EUNSUPPORTED there); these symbols take the same argument lists with the same meaning:
+ *   1 <= D <= 16:     forwards to glhip_plan_apply — the very same launch, bit-identical results.
+ *   17 <= D <= 4095:  xk_plan_kernel (glhip_plan_apply_xk.h): the K-chunked exponent blocks of the forward kernel of these dimensions
+ *                     (glhip_softmin_xk.h: 256 x 128 blocks, stages of 6 MFMAs, operands split on the fly, both layouts, float32 and
+ *                     bfloat16 clouds), handed after the last stage of a column tile to the second MFMA product of glhip_plan_apply.h.
+ *                     One pass over the columns per 64 features (a remainder is a pass of its own).  Same semantics: out = 0 and
+ *                     mass = 0 for a row whose columns all carry h = -inf, in either layout; a one-hot plan row returns its features
+ *                     bit for bit; M == 0 or V == 0 with N > 0 zeroes out and mass; N == 0 launches nothing.
+ *   p != 2, block-sparse ranges (n_ranges > 0) and D > 4095 return GLHIP_EUNSUPPORTED.
+ * glhip_plan_apply_nd_workspace_bytes holds the split partials only and never asks for more than 1 GiB; NULL or a short buffer means
+ * fewer or no splits, with the same results up to summation order.
+ * glhip_plan_apply_nd_family: host arithmetic only, the predicate the launch itself evaluates — GLHIP_FAMILY_XD for D <= 16,
+ * GLHIP_FAMILY_XK for 17 <= D <= 4095, GLHIP_EUNSUPPORTED for valid requests without a kernel (p = 1, ranges, D > 4095),
+ * GLHIP_EINVAL for what the entry point rejects (negative sizes, D < 1, bad p or dtype).  `flags` does not change the family.
+ * glhip_plan_apply_nd_pass_width: feature columns one pass over the columns carries — 128 / 64 / 32 for D <= 4 / <= 11 / <= 16,
+ * 64 for 17 <= D <= 4095, 0 for a dimension without a kernel.
+ * Not routed through this product (yet): glhip_softmin_bwd_x of D > 16, see above.
+ */
+size_t glhip_plan_apply_nd_workspace_bytes(int B, int N, int M, int D, int V);
+int glhip_plan_apply_nd_family(int B, long N, long M, int D, int V, int p, int dtype, int flags, int n_ranges);
+int glhip_plan_apply_nd_pass_width(int D);
+int glhip_plan_apply_nd(const void* x, const void* y, const float* h, const float* fwd, const float* feat,
+                        float* out, float* mass,
+                        int B, int N, int M, int D, int V, float eps, int p, int in_dtype,
+                        const int32_t* ranges_i, const int32_t* slices_i, const int32_t* redranges_j, int n_ranges,
+                        void* workspace, size_t workspace_bytes, int flags, void* stream);
 
 /*
  * Kernel-matrix × vector product  out[b,i] = sum_j k(x[b,i], y[b,j]) * v[b,j].
