@@ -1,6 +1,11 @@
 // glhip_api_bwd.hip — C-ABI part 2: the soft-min gradient and the hard C-transform of point clouds.
 #include "glhip_launch.h"
 
+namespace glhip {      // glhip_api_grad_xk.hip: the GLHIP_FLAG_XK_GRAD route (xk_grad_kernel, glhip_softmin_grad_xk.h)
+int softmin_grad_xk_launch(const void* x, const void* y, const float* h, const float* fwd, const float* g, float* gx, int B, int N, int M,
+                           int D, float eps, int in_dtype, void* workspace, size_t workspace_bytes, int flags, hipStream_t st);
+}
+
 extern "C" {
 
 int glhip_softmin_bwd_x(const void* x, const void* y, const float* h, const float* out, const float* grad_out,
@@ -15,6 +20,10 @@ int glhip_softmin_bwd_x(const void* x, const void* y, const float* h, const floa
     if (p != 1 && p != 2) return fail(GLHIP_EUNSUPPORTED, "glhip_softmin_bwd_x: p must be 1 or 2 (got %d)", p);
     const Ranges rg{ranges_i, slices_i, redranges_j};
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if (glhip_softmin_bwd_x_uses_plan(B, N, M, D, p, in_dtype, flags, n_ranges) == 1) {      // GLHIP_FLAG_XK_GRAD: p = 2, 17 <= D <= 4095, dense
+        rc = softmin_grad_xk_launch(x, y, h, out, grad_out, grad_x, B, N, M, D, eps, in_dtype, workspace, workspace_bytes, flags, st);
+        return rc ? rc : check_launch("glhip_softmin_bwd_x");
+    }
     const Scratch sc = make_scratch(workspace, workspace_bytes, flags, n_ranges, N);
     rc = (in_dtype == GLHIP_F32)
              ? softmin_typed<true, float>(x, y, h, nullptr, out, grad_out, grad_x, B, N, M, D, eps, p, rg, n_ranges, sc, flags, st)

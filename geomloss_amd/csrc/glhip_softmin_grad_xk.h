@@ -1,73 +1,50 @@
-// glhip_plan_apply_xk.h — the transport plan of a p = 2 soft-min applied to a feature matrix on the matrix cores, 17 <= D <= 4095:
+// glhip_softmin_grad_xk.h — the gradient of a p = 2 soft-min with respect to the row points on the matrix cores, 17 <= D <= 4095:
 //
-//     out[i][v] = sum_j w_ij feat[j][v] / sum_j w_ij,      w_ij = 2^( u_ij + C_i ),  u_ij = H_j + s xt_i.yt_j,  C_i = r_i - fwd_i / out_scale
+//     grad_x[i][d] = g_i ( x_i[d] - sum_j w_ij y_j[d] / sum_j w_ij ),      w_ij as in glhip_plan_apply_xk.h
 //
-// glhip_plan_apply.h keeps the x-side operands of the whole exponent in registers and is templated on D <= 16.  Here D is a RUN-TIME
-// argument and the kernel is the union of two that the tree already has:
+// i.e. the transport plan applied to the column cloud itself.  xk_grad_kernel is xk_plan_kernel (glhip_plan_apply_xk.h) with three
+// differences; everything else — the exponent half, the weights relative to the running row maximum times 2^kWqShift, the mass from
+// the fp32 weights, the two f16 pieces under a power-of-two scale per feature column and tile, six MFMAs per chunk into a fresh
+// accumulator per 32-column block, the meeting of the two column halves — is that kernel's, restated.
 //
-//   exponent half = xk_fwd_kernel (glhip_softmin_xk.h), MODE soft-min: the 256 x 128 block of 8 wavefronts as 4 x 2, K stages of 6
-//   MFMAs, points centred on the first row of the row block and split on the fly (xk_pack_half, xk_norms, glhip_klayout.h), padded
-//   columns at -1e30 (f16 x 2: the floor), both layouts.  That kernel calls mfma(Y, X, acc): after the last stage lane (half, i) of a
-//   wavefront holds, for each of its 2 x 2 blocks, row i for the 16 columns col(half, r) = 8 (r / 4) + 4 half + r % 4 —
-//   the layout plan_apply_kernel feeds to its second product as the B operand.
+//   features   feature c of a pass that starts at coordinate v0 is to_f32(y[j][v0 + c]) - to_f32(centre[v0 + c]), read in the cloud's
+//              dtype: no feat pointer, no fp32 copy of a bf16 cloud.  centre = the first row of the row block, which the exponent half
+//              centres on already.  Centred features keep x_i - ybar_i free of cancellation for clouds far from the origin: both
+//              terms of the epilogue are of the size of the cloud's diameter.
+//   epilogue   unsplit launches write grad_x[b][i][v0 + c] = g_i ((x_i[c] - centre[c]) - s / w); 0 for a row without mass (w == 0).
+//              The division stays a division: a one-hot plan row gives x_i - y_j exactly.
+//   splits     partials (sums of nv centred features, mass, m) as in the plan kernels; xk_grad_merge_kernel brings the splits to the
+//              largest m, adds, divides and applies the same epilogue — the centre row of row i is (i / kXkRows) kXkRows of its batch item.
 //
-//   plan half = the discipline of plan_apply_kernel (glhip_plan_apply.h), after the last K stage of a column tile, block by block:
-//   C_i joins the exponents on the VALU, together with a per-column mask (0, or -inf for padded columns and columns with h = -inf:
-//   they weigh exactly 0 in either layout, whatever the staging put in their H slot and whatever fwd_i is); weights relative to the
-//   running maximum of their row times 2^kWqShift; the mass from the unsplit fp32 weights; weights in two f16 pieces; six
-//   v_mfma_f32_32x32x16_f16 per chunk of 32 features against A operands staged in LDS (two f16 pieces under a power-of-two scale per
-//   feature column and tile: plan_scale_exponent); a fresh accumulator per 32-column block, folded into the running sums with one
-//   v_fma_f32 per register; a new row maximum rescales the running sums and the mass.  The largest weight of a row is 2^13 exactly:
-//   a one-hot plan row returns its features bit for bit.
+// A pass covers 64 coordinates (NCH = 2), a remainder of <= 32 runs as NCH = 1: ceil(D / 64) passes, each with its own exponent half.
+//   registers / LDS / scratch (gfx950, tools/kernel_resources.py, profiles/softmin_grad_xk.txt): see that file; 0 bytes of scratch in
+//   all eight instantiations, LDS as xk_plan_kernel (95.1 / 111.5 KiB).
 //
-// Feature staging costs no barrier of its own: a tile's features are loaded and their maxima taken (ds_max_u32) between the first
-// two barriers of the tile, scaled, split and written to LDS between the second and the third — the barriers xk_fwd_kernel has for
-// the column indices and norms.  The two column halves of a workgroup (wc = 0, 1) carry separate (sums, mass, m) for the same rows
-// and meet in LDS after the last tile ([feature][row] in the stage buffer), as (m, s) do in xk_fwd_kernel.  Column splits: the
-// partial format of plan_apply_kernel — (sums[nv], mass, m) — and its plan_merge_kernel, unchanged.
-//
-// Chunks per pass: NCH = 1 or 2 chunks of 32 features, i.e. up to 64 features per pass (launch); wider feature matrices take
-// further passes, a remainder is a pass of its own.  A wavefront carries 2 row tiles x NCH accumulators of 16 registers next to its
-// 64 registers of exponents; four chunks would need 128 + 64 before any operand and 130 KiB for the meeting of the halves.
-// One workgroup per CU: __launch_bounds__(512, 2).
-//   registers / LDS / scratch (gfx950, tools/kernel_resources.py, profiles/plan_apply_nd.txt), float32 and bfloat16 clouds:
-//     NCH = 1, both layouts:  200 VGPRs, 95.1 KiB of LDS (97 408 B), 0 bytes of scratch
-//     NCH = 2, both layouts:  256 VGPRs, 111.5 KiB of LDS (114 176 B), 0 bytes of scratch
-//     LDS: 78.75 KiB of xk_fwd_kernel + 16 KiB of feature pieces per chunk + 384 B per chunk of maxima and inverse scales
-//
-// Cost model: per 32 x 32 block NM >= 7 MFMAs of exponent (NM = ceil((6 + kPer D) / 16)) + 6 NCH MFMAs of product + ~50 VALU
-// instructions of exponentials and piece conversions shared by the chunks + 16 NCH v_fma_f32.  The staging of the exponent half
-// (the splitting of 384 points per stage) is what a pass shares with a forward reduction, and it dominates both.
-//
-// Kept in step by hand: the stage loop below (the split of the points into records and the six K chunks of MFMAs) restates the body of
-// xk_fwd_kernel, which may not change with this kernel; only xk_pack_half, xk_norms and the layout constants are shared code.  It
-// leaves out that kernel's sched_barrier between the two half groups of f16 x 2 (there for a 128-VGPR budget this kernel does not
-// have).  Follow-up: one __forceinline__ stage helper for both kernels, with tools/kernel_resources.py showing xk_fwd_kernel unchanged.
-//
-// glhip_softmin_bwd_x of 17 <= D <= 4095 — g_i (x_i - sum_j P_ij y_j) is a plan application too — runs xk_grad_kernel
-// (glhip_softmin_grad_xk.h) under GLHIP_FLAG_XK_GRAD: a copy of this body with the centred column cloud as its features and the
-// gradient's epilogue; this kernel and its resources are untouched by it.  Out of scope here: block-sparse plans, p = 1, float64
-// clouds and autograd through the application.
+// Kept in step by hand: this body duplicates xk_plan_kernel's (a mode parameter there would have to leave the resources of its eight
+// instantiations untouched; a copy does so by construction), whose stage loop in turn restates xk_fwd_kernel's.
 #pragma once
 
-#include "glhip_plan_apply.h"
-#include "glhip_softmin_xk.h"
+#include "glhip_plan_apply_xk.h"
 
 namespace glhip {
 
-constexpr int kXkPlanMaxChunks = 2;                      // feature chunks per pass
-
-template <int NCH>
-struct XkPlanLds {
-    XkLds xk;                                            // the exponent half (xk.v: the column mask, 0 or -inf)
-    uint4 q[(kXkCols / 32) * NCH * 4 * 64];              // feature A operands: [group][chunk][piece][instruction][lane = 32 h + c] x 8 f16
-    uint32_t fmax[2][32 * NCH];                          // largest |f| bit pattern per feature, tiles of even / odd index
-    __attribute__((aligned(16))) float inv[32 * NCH];    // 2^-13 / scale of the current tile, per feature
+template <typename T>
+struct XkGradParams {
+    const T* x;           // (B,N,D)
+    const T* y;           // (B,M,D)
+    const float* h;       // (B,M)
+    const float* fwd;     // (B,N): the saved soft-min
+    const float* g;       // (B,N): the incoming gradient
+    float* gx;            // (B,N,D)
+    float s2;             // log2(e) / eps
+    float out_scale;      // -eps ln 2: LSE2_i = fwd_i / out_scale
+    int v0;               // first coordinate of this pass
+    int nv;               // coordinates of this pass, <= 32 NCH
 };
 
 template <typename T, int NCH, int L>
 __global__ void __launch_bounds__(kXkThreads, 2)
-xk_plan_kernel(PlanParams<T> prm, int N, int M, int D, SplitInfo sp) {
+xk_grad_kernel(XkGradParams<T> prm, int N, int M, int D, SplitInfo sp) {
     constexpr bool H2 = (L == XL_F16X2);
     constexpr int kItems = H2 ? 8 : 4;                        // items (coordinates) of a 24-slot group
     constexpr int kLead = H2 ? 2 : 1;                         // items taken by the scalar item
@@ -140,19 +117,20 @@ xk_plan_kernel(PlanParams<T> prm, int N, int M, int D, SplitInfo sp) {
         const int col = (tid < n) ? j0 + tid : -1;            // this thread's column (tid < kXkCols), -1 = padding
         __syncthreads();                                      // the previous tile (and the row scalars) are settled
         if (tid < kXkCols) lds.xk.idx[kXkRows + tid] = col;
-        // features: item (column quad cq, feature c of the pass) — c runs fastest, so the loads of a wavefront are contiguous runs of
-        // feat rows (plan_apply_kernel)
+        // features = the centred coordinates v0 .. v0 + nv - 1 of the tile's columns: item (column quad cq, coordinate c of the pass) —
+        // c runs fastest, so the loads of a wavefront are contiguous runs of y rows
         float fv[kFItems][4];
 #pragma unroll
         for (int k = 0; k < kFItems; ++k) {
             const int it = tid + k * kXkThreads;
             const int cq = it / VC, c = it - cq * VC;
             const int t = cq << 2;
+            const float cen = (c < prm.nv) ? to_f32<T>(centre[prm.v0 + c]) : 0.f;
             uint32_t mx = 0u;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 float f = 0.f;
-                if (t + q < n && c < prm.nv) f = prm.feat[((long)b * M + j0 + t + q) * prm.V + prm.v0 + c];
+                if (t + q < n && c < prm.nv) f = to_f32<T>(yb[(long)(j0 + t + q) * D + prm.v0 + c]) - cen;
                 fv[k][q] = f;
                 mx = max(mx, __float_as_uint(f) & 0x7FFFFFFFu);
             }
@@ -375,8 +353,10 @@ xk_plan_kernel(PlanParams<T> prm, int N, int M, int D, SplitInfo sp) {
         const float rs1 = fast_exp2(m[rt] - mn), rs2 = fast_exp2(m2 - mn);
         const float w = __builtin_fmaf(mrg[VC * kXkRows + r_local], rs2, mass[rt] * rs1);
         const long idx = (long)b * N + i;
-        float* orow = prm.out + idx * prm.V + prm.v0;
+        const T* xrow = xb + (long)i * D + prm.v0;
+        float* orow = prm.gx + idx * D + prm.v0;
         float* part = sp.workspace + split * sp.split_stride + idx * (prm.nv + 2);
+        const float gi = (ns == 1) ? prm.g[idx] : 0.f;
 #pragma unroll
         for (int ch = 0; ch < NCH; ++ch) {
 #pragma unroll
@@ -384,20 +364,46 @@ xk_plan_kernel(PlanParams<T> prm, int N, int M, int D, SplitInfo sp) {
                 const int c = 32 * ch + (r & 3) + 8 * (r >> 2) + 4 * half;
                 if (c < prm.nv) {
                     const float s = __builtin_fmaf(mrg[c * kXkRows + r_local], rs2, pacc[rt][ch][r] * rs1);
-                    if (ns == 1) orow[c] = (w > 0.f) ? s / w : 0.f;      // a division: exact where the quotient is
-                    else part[c] = s;
+                    if (ns == 1) {      // g_i ((x_i - centre) - ybar_i): a division, exact where the quotient is; a row without mass gets 0
+                        const float xc = to_f32<T>(xrow[c]) - to_f32<T>(centre[prm.v0 + c]);
+                        orow[c] = (w > 0.f) ? gi * (xc - s / w) : 0.f;
+                    } else {
+                        part[c] = s;
+                    }
                 }
             }
         }
-        if (half == 0) {
-            if (ns > 1) {
-                part[prm.nv] = w;
-                part[prm.nv + 1] = mn;
-            } else if (prm.mass && prm.v0 == 0) {
-                prm.mass[idx] = w * fast_exp2(mn);
-            }
+        if (half == 0 && ns > 1) {
+            part[prm.nv] = w;
+            part[prm.nv + 1] = mn;
         }
     }
+}
+
+// Combines the column splits of a gradient pass: one thread per (row, coordinate).  The partials of a row are nv sums of centred
+// coordinates and the mass — both relative to 2^m of their split — and m (plan_merge_kernel's format): brought to the largest m, added,
+// divided, and put through the epilogue of xk_grad_kernel.
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+xk_grad_merge_kernel(XkGradParams<T> prm, int N, int D, long rows, SplitInfo sp) {
+    const long id = (long)blockIdx.x * kBlock + threadIdx.x;
+    const int nv = prm.nv;
+    if (id >= rows * nv) return;
+    const long row = id / nv;
+    const int c = (int)(id - row * nv);
+    const float* part = sp.workspace + row * (nv + 2);
+    float mx = kMinusHuge;
+    for (int k = 0; k < sp.n_splits; ++k) mx = fmaxf(mx, part[k * sp.split_stride + nv + 1]);
+    float s = 0.f, w = 0.f;
+    for (int k = 0; k < sp.n_splits; ++k) {
+        const float rs = fast_exp2(part[k * sp.split_stride + nv + 1] - mx);
+        s = __builtin_fmaf(part[k * sp.split_stride + c], rs, s);
+        w = __builtin_fmaf(part[k * sp.split_stride + nv], rs, w);
+    }
+    const long i = row % N;
+    const long crow = row - i + (i / kXkRows) * kXkRows;      // the first row of the row block, within the batch item
+    const float xc = to_f32<T>(prm.x[row * D + prm.v0 + c]) - to_f32<T>(prm.x[crow * D + prm.v0 + c]);
+    prm.gx[row * D + prm.v0 + c] = (w > 0.f) ? prm.g[row] * (xc - s / w) : 0.f;
 }
 
 }  // namespace glhip

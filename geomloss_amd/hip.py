@@ -24,6 +24,7 @@ F32, BF16 = 0, 1
 FLAG_DIRECT, FLAG_NO_MFMA, FLAG_NO_SPLIT, FLAG_F32_MFMA, FLAG_XDL16, FLAG_PREPACK, FLAG_MFMA_DIST, FLAG_SMALL_ROW_BLOCKS = 1, 2, 4, 8, 16, 32, 64, 128
 FLAG_F16X2 = 256                # exponents from two f16 pieces per coordinate; the caller vouches for the range (glhip.h)
 FLAG_NO_SORT = 512              # big dense distance reductions: do not voxel-sort the clouds inside the library (glhip.h)
+FLAG_XK_GRAD = 1024             # glhip_softmin_bwd_x: the p = 2 gradient of 17 <= D <= 4095 on the matrix cores (glhip_softmin_grad_xk.h)
 FLAG_GRAD_FAMILY = FLAG_XDL16   # kernel products rounded like the product-and-gradient kernel of the same kind (glhip.h)
 XD_MAX_DIM = 16                 # the fused four-softmin iteration / annealing / extrapolation, the one-pass value + gradient and the matrix-core
                                 # gradients stop at this dimension (glhip_softmin_xd.h, glhip_wsum_t32.h)
@@ -56,6 +57,8 @@ SIGNATURES = {
     "glhip_sinkhorn_extrapolate4": (_c_int, [_vp] * 14 + [_c_int] * 6 + [_c_float, _c_float, _c_int, _c_int] + _TAIL),
     "glhip_softmin_bwd_x": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int,
                                      _c_int] + _RANGES + _TAIL),
+    "glhip_softmin_bwd_x_uses_plan": (_c_int, [_c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int, _c_int]),
+    "glhip_softmin_bwd_x_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "glhip_plan_apply_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "glhip_plan_apply": (_c_int, [_vp] * 7 + [_c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int, _c_int] + _RANGES + _TAIL),
     "glhip_plan_apply_nd_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
@@ -333,7 +336,18 @@ def sinkhorn_extrapolate4_raw(x, y, xc, yc, a_log_c, b_log_c, pots, eps, damping
     return tuple(outs)
 
 
-def softmin_bwd_x_raw(x, y, h, out, grad_out, eps, p=2, ranges=None, flags=0):
+def softmin_bwd_x_uses_plan(B, N, M, D, p=2, dtype=F32, flags=0, n_ranges=0):
+    """Whether ``glhip_softmin_bwd_x`` runs the matrix-core gradient of 17 <= D <= 4095 for this launch (``FLAG_XK_GRAD``): the
+    library's own predicate (host arithmetic, no GPU).  1 / 0, or ``ValueError`` for arguments the entry point rejects."""
+    lib = load_library()
+    r = int(lib.glhip_softmin_bwd_x_uses_plan(int(B), int(N), int(M), int(D), int(p), int(dtype), int(flags), int(n_ranges)))
+    if r < 0:
+        raise ValueError(f"glhip_softmin_bwd_x_uses_plan: bad argument (B {B}, N {N}, M {M}, D {D}, p {p}, dtype {dtype}, n_ranges {n_ranges})")
+    return r
+
+
+def softmin_bwd_x_raw(x, y, h, out, grad_out, eps, p=2, ranges=None, flags=0, workspace=True):
+    """``workspace=False``: launch without one (no column splits) — tests only."""
     lib = load_library()
     B, N, D = x.shape
     M = y.shape[1]
@@ -345,8 +359,17 @@ def softmin_bwd_x_raw(x, y, h, out, grad_out, eps, p=2, ranges=None, flags=0):
         _check(rc, lib)
         return gx
     gx = torch.empty((B, N, D), dtype=torch.float32, device=x.device)
+    n_ranges = 0 if ranges is None else int(ranges.ranges_i.shape[0])
     with torch.cuda.device(x.device):
-        ws, ws_args = _workspace(lib, x, B, N, M, D, ranges)
+        if lib.glhip_softmin_bwd_x_uses_plan(B, N, M, D, int(p), _dtype_code(x), int(flags), n_ranges) == 1:
+            # the matrix-core gradient sizes its own split partials (glhip_softmin_bwd_x_workspace_bytes)
+            nbytes = int(lib.glhip_softmin_bwd_x_workspace_bytes(B, N, M, D, int(flags))) if workspace else 0
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+            ws_args = (None if ws is None else ws.data_ptr(), nbytes)
+        elif workspace:
+            ws, ws_args = _workspace(lib, x, B, N, M, D, ranges)
+        else:
+            ws, ws_args = None, (None, 0)
         rc = lib.glhip_softmin_bwd_x(x.data_ptr(), y.data_ptr(), h.data_ptr(), out.data_ptr(), grad_out.data_ptr(),
                                      gx.data_ptr(), B, N, M, D, float(eps), int(p), _dtype_code(x),
                                      *_range_args(ranges, B), *ws_args, int(flags), _stream(x))

@@ -139,7 +139,10 @@ class _HipSoftmin:
             self.h2_min_eps = 2e-5 * float(extent) ** 2
 
     def _flags(self, eps):
-        return hip.FLAG_F16X2 if eps >= self.h2_min_eps else 0
+        # FLAG_XK_GRAD: the backward of dense p = 2 soft-mins of 17 <= D <= 4095 on the matrix cores (glhip_softmin_grad_xk.h); the
+        # library ignores it everywhere else — every forward launch, D <= 16, the block-sparse fine level of the two-scale backend
+        xk = hip.FLAG_XK_GRAD if (self.p == 2 and _XK_GRAD) else 0
+        return xk | (hip.FLAG_F16X2 if eps >= self.h2_min_eps else 0)
 
     def __call__(self, eps, C, h):
         if self.multiscale:
@@ -245,6 +248,7 @@ class _HipSoftmin:
 _graph_mode = os.environ.get("GEOMLOSS_HIP_GRAPH", "0") == "1"
 _COARSE_F64_MIN_PAIRS = float(os.environ.get("GEOMLOSS_HIP_COARSE_F64_MIN_PAIRS", "1e11"))   # two-scale losses: float64 coarse level from here on
 _F16X2 = os.environ.get("GEOMLOSS_HIP_F16X2", "1") != "0"      # f16 x 2 exponents where the temperature allows (_HipSoftmin.set_range)
+_XK_GRAD = os.environ.get("GEOMLOSS_HIP_XK_GRAD", "1") != "0"  # matrix-core soft-min gradient of 17 <= D <= 4095 (_HipSoftmin._flags)
 _anneal_in_library = True   # the iterations of a level queued by one library call (tests switch it off to compare with one call per iteration)
 _fuse_iterations = True   # one launch per Sinkhorn iteration (small / mid-size clouds); set_iteration_fusion(False): four half-steps
 # ... up to this many pairs per soft-min; bigger problems fill the GPU with one soft-min per launch (pre-packed columns, XCD grids)

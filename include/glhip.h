@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 125 /* 0.1.25 */
+#define GLHIP_VERSION 126 /* 0.1.26 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
@@ -86,7 +86,15 @@ extern "C" {
                                   exponent term (log2(e) h_j, |x - y|^2 / (2 eps ln 2)) must stay below ~2.6e5 in magnitude, i.e. roughly
                                   (cloud diameter)^2 / eps < 3e5; beyond that f16 overflows and the results are inf / nan.  The bound is on the
                                   exponents, so it is the same in every dimension (diameter^2 grows like D on a unit cube).  Ignored by kernels
-                                  without that layout (p = 1, laplacian, energy, the gradients of D > 16, D > 4095, float64). */
+                                  without that layout (p = 1, laplacian, energy, the gradients of D > 16 other than GLHIP_FLAG_XK_GRAD, D > 4095, float64). */
+
+#define GLHIP_FLAG_XK_GRAD 1024 /* glhip_softmin_bwd_x only (version 126): the gradient of p == 2, 17 <= D <= 4095, dense launches (n_ranges == 0),
+                                  B <= 65535, without GLHIP_FLAG_NO_MFMA / _DIRECT runs xk_grad_kernel (csrc/glhip_softmin_grad_xk.h): the K-chunked
+                                  plan application of glhip_plan_apply_nd with the centred column cloud as its features, ceil(D / 64) passes.
+                                  glhip_softmin_bwd_x_uses_plan is the predicate.  Ignored everywhere else — every other entry point, p = 1,
+                                  D <= 16, D > 4095, block-sparse ranges, the float64 symbols: those launches are the ones version 125 makes,
+                                  bit for bit.  Without the flag nothing changes: the one-thread-per-row kernel of glhip_generic.h.
+                                  GLHIP_FLAG_F16X2 selects the exponent layout of the new kernel, under that flag's range contract. */
 
 #define GLHIP_FLAG_NO_SORT 512 /* p = 1 soft-min / half-step, laplacian and energy products: big dense launches (B = 1, D <= 3, N >= 65536,
                                   N M >= 5e8, a workspace of glhip_workspace_bytes) sort both clouds into the workspace themselves — voxel sort along a
@@ -340,9 +348,20 @@ int glhip_lse_lines_bwd(const float* h, const float* lse, const float* grad_out,
  * D > 16: the one-thread-per-row kernel of glhip_generic.h, in ANY dimension (version 121; D <= 64 before): 64 output coordinates
  * per pass over the columns, ceil(D / 64) passes.  The same holds for glhip_kernel_conv_bwd_x.  The weighted sums sum_j w_ij q_j as
  * a second MFMA product over all 32 MFMA rows live in glhip_plan_apply below (glhip_plan_apply.h, version 124: any number of feature
- * columns, D <= 16) and, for 17 <= D <= 4095, in glhip_plan_apply_nd (glhip_plan_apply_xk.h, version 125); the D > 16 gradient does
- * not use that product yet and stays on the one-thread-per-row kernel (its 5e-6 test bound is met by explicit differences; whether the
- * MFMA chain's exponents meet it is measured by tests/test_plan_apply_nd_gpu.py).
+ * columns, D <= 16) and, for 17 <= D <= 4095, in glhip_plan_apply_nd (glhip_plan_apply_xk.h, version 125).
+ * GLHIP_FLAG_XK_GRAD (version 126) routes the p = 2 gradient of 17 <= D <= 4095 through that product: xk_grad_kernel
+ * (glhip_softmin_grad_xk.h) takes the column cloud itself, centred on the first row of each 256-row block, as its features and writes
+ * g_i ((x_i - centre) - sum_j P_ij (y_j - centre)) — 64 coordinates per pass, ceil(D / 64) passes, float32 and bfloat16 clouds, both
+ * exponent layouts; a row without mass gets 0; a one-hot plan row gives g_i (x_i - y_j) with an exact difference.  The flag is opt-in
+ * at this level: the default stays the one-thread-per-row kernel, whose explicit differences meet 5e-6 at eps = 0.3 where the
+ * exponents of a long MFMA chain are bounded by 4 x the error of plain float32 arithmetic instead (DESIGN section 4 has the measured
+ * figures of both routes).
+ *   glhip_softmin_bwd_x_uses_plan: host arithmetic only, the very predicate the launch evaluates — 1: xk_grad_kernel; 0: the launch
+ *   of version 125; GLHIP_EINVAL: negative sizes, D < 1, a bad p or dtype.
+ *   glhip_softmin_bwd_x_workspace_bytes: the split partials of the widest pass of the new route (sums of <= 64 centred coordinates,
+ *   mass, row maximum per row and split), never more than 1 GiB, 0 where the predicate is 0 (those launches size their workspace
+ *   with glhip_workspace_bytes, which does not change) or under GLHIP_FLAG_NO_SPLIT.  NULL or a short workspace: fewer or no splits,
+ *   the same results up to summation order.  N == 0 or B == 0 launches nothing; M == 0 zeroes grad_x.
  *   out = the saved forward result (B,N);  grad_out (B,N) fp32;  grad_x (B,N,D) fp32.
  */
 int glhip_softmin_bwd_x(const void* x, const void* y, const float* h,
@@ -351,6 +370,8 @@ int glhip_softmin_bwd_x(const void* x, const void* y, const float* h,
                         const int32_t* ranges_i, const int32_t* slices_i,
                         const int32_t* redranges_j, int n_ranges,
                         void* workspace, size_t workspace_bytes, int flags, void* stream);
+int glhip_softmin_bwd_x_uses_plan(int B, long N, long M, int D, int p, int dtype, int flags, int n_ranges);
+size_t glhip_softmin_bwd_x_workspace_bytes(int B, int N, int M, int D, int flags);
 
 /*
  * Application of the transport plan of a p = 2 soft-min to a feature matrix (version 124; glhip_plan_apply.h).  With
@@ -404,7 +425,7 @@ int glhip_plan_apply(const void* x, const void* y, const float* h, const float* 
  * GLHIP_EINVAL for what the entry point rejects (negative sizes, D < 1, bad p or dtype).  `flags` does not change the family.
  * glhip_plan_apply_nd_pass_width: feature columns one pass over the columns carries — 128 / 64 / 32 for D <= 4 / <= 11 / <= 16,
  * 64 for 17 <= D <= 4095, 0 for a dimension without a kernel.
- * Not routed through this product (yet): glhip_softmin_bwd_x of D > 16, see above.
+ * glhip_softmin_bwd_x of 17 <= D <= 4095 runs a gradient mode of this product under GLHIP_FLAG_XK_GRAD (version 126), see above.
  */
 size_t glhip_plan_apply_nd_workspace_bytes(int B, int N, int M, int D, int V);
 int glhip_plan_apply_nd_family(int B, long N, long M, int D, int V, int p, int dtype, int flags, int n_ranges);
