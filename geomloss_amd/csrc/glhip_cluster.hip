@@ -18,6 +18,7 @@
 #include "glhip_autosort.h"
 #include "glhip_common.h"
 #include "glhip_error.h"
+#include "glhip_prune_words.h"
 
 using namespace glhip;
 
@@ -537,6 +538,10 @@ __device__ __forceinline__ int prune_first_kept(const double* hist, double under
 // (unused slots: empty intervals, which the kernels skip).  A piece starts at a kept block that opens a run (the gap to the previous
 // kept block is >= g blocks) or that sits on the piece grid (a multiple of PB).  g = 1 unless the slab has more than kPruneRuns runs;
 // then g is the smallest gap length that leaves at most kPruneRuns runs (gaps shorter than g are closed).
+// kept(t) is evaluated once per block, into a bit set in LDS (up to 64 x kPruneMaskWords = 65536 blocks; beyond that every walk evaluates it
+// again, as all of them did before).  For g = 1 — all but a handful of slabs — runs are counted and pieces written from
+// the 64-bit words (glhip_prune_words.h): one prefix sum over the workgroup instead of two per 256 blocks (~1100 barriers per slab at M = 1e6).
+constexpr int kPruneMaskWords = 1024;      // 65536 blocks = 16.7e6 columns: 8 KB
 template <typename T>
 __global__ void __launch_bounds__(256) prune_slabs_kernel(const T* __restrict__ xs, int N, int M, int D, const ColBlock* __restrict__ blocks,
                                                           int nT, int PB, int S, double inv2eps, double L, int32_t* __restrict__ ranges_i,
@@ -545,6 +550,7 @@ __global__ void __launch_bounds__(256) prune_slabs_kernel(const T* __restrict__ 
     __shared__ int buf[256];
     __shared__ double hist[kPruneBuckets + 1];      // (the last entry: the underflow bucket)
     __shared__ int first_kept;
+    __shared__ unsigned long long mask[kPruneMaskWords];
     __shared__ float wlo[4][3], whi[4][3];
     __shared__ double wm[4];
     __shared__ int wb[4];
@@ -643,20 +649,31 @@ __global__ void __launch_bounds__(256) prune_slabs_kernel(const T* __restrict__ 
     };
     // No second level where it has nothing to win: a slab without a bound, and a slab whose bound keeps every block (large eps: the
     // finer test would pass nearly every group as well, and costs ~2 % of the sweep)
+    const int nW = (nT + 63) >> 6;
+    const bool masked = nW <= kPruneMaskWords;
     {
         int all = 1;
-        if (!keep_all)
+        if (masked) {      // one word per wavefront and step
+            for (int w = wave; w < nW; w += 4) {
+                const int t = 64 * w + lane;
+                const unsigned long long m = __ballot(t < nT && kept(t));
+                if (lane == 0) mask[w] = m;
+                all &= m == (nT - 64 * w >= 64 ? ~0ull : (1ull << (nT - 64 * w)) - 1ull);
+            }
+        } else if (!keep_all) {
             for (int t = tid; t < nT && all; t += 256) all = kept(t) ? 1 : 0;
-        all = __syncthreads_and(all);
+        }
+        all = __syncthreads_and(all);      // (also: the bit set is written)
         if (tid == 0) home[k] = (keep_all || all) ? -1 : best;
     }
+    auto kept_at = [&](int t) { return masked ? ((mask[t >> 6] >> (t & 63)) & 1ull) != 0 : kept(t); };
     // one walk over the blocks: the number of runs for gap length g, and (EMIT) the pieces written out
     int32_t* slots = red + 2 * (long)k * S;
     auto walk = [&](int g, bool emit) {
         int carry = -1, runs = 0, pieces = 0;
         for (int c0 = 0; c0 < nT; c0 += 256) {
             const int t = c0 + tid;
-            const bool kp = t < nT && kept(t);
+            const bool kp = t < nT && kept_at(t);
             block_scan256<true>(kp ? t : -1, buf);      // buf[t]: the last kept block of the chunk up to t
             const int prev = max(carry, tid > 0 ? buf[tid - 1] : -1);
             const int last = buf[255];
@@ -683,8 +700,29 @@ __global__ void __launch_bounds__(256) prune_slabs_kernel(const T* __restrict__ 
         }
         return runs;
     };
+    // g = 1 on the bit set (glhip_prune_words.h): thread i owns the words [i wpt, (i + 1) wpt)
+    const int wpt = (nW + 255) / 256, w0 = min(nW, tid * wpt), w1 = min(nW, w0 + wpt);
+    int runs1 = 0;
+    if (masked) {
+        int nrun, nstart;
+        prune_count_words(mask, w0, w1, PB, nrun, nstart);
+        block_scan256<false>(nrun, buf);
+        runs1 = buf[255];
+        __syncthreads();
+        if (runs1 <= kPruneRuns) {      // (workgroup-uniform)
+            const int base = block_scan256<false>(nstart, buf) - nstart;
+            const int n = min(buf[255], S);
+            prune_emit_words(mask, w0, w1, base, PB, S, kPruneColBlock, M, slots);
+            if (tid == 0 && n > 0) prune_emit_last(mask, nW, n, kPruneColBlock, M, slots);
+            for (int q = n + tid; q < S; q += 256) {
+                slots[2 * q] = 0;
+                slots[2 * q + 1] = 0;
+            }
+            return;
+        }
+    }
     int g = 1;
-    if (walk(1, false) > kPruneRuns) {
+    if ((masked ? runs1 : walk(1, false)) > kPruneRuns) {
         int lo_g = 1, hi_g = nT;   // walk(nT) has one run
         while (hi_g - lo_g > 1) {
             const int mid = lo_g + (hi_g - lo_g) / 2;

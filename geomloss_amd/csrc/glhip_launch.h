@@ -156,14 +156,17 @@ void launch_softmin_mfma_nw(const SoftminParams<T>& prm, const Ranges& rg, int n
     // Dense launches of the x32 kernel with enough work to pay for one more (tiny) launch split the columns into
     // bf16x3 MFMA records ONCE, in workspace behind the split partials, instead of once per workgroup.
     PackedCols pk{nullptr, (long)((M + 31) / 32) * (32 * NR)};
-    const size_t packed_bytes = (size_t)B * (size_t)pk.stride * sizeof(uint4);   // either layout fits
+    const size_t packed_bytes = (size_t)B * (size_t)pk.stride * sizeof(uint4);   // either layout fits: ceil(M / 32) whole groups hold the M records-of-NR of [M][NR]
     const bool pre = sc.prepack((double)B * N * M) && sc.bytes >= sl.packed_offset() + packed_bytes;
     const bool use_p2 = pre && p2 && !sl.sp.gather;
     if (pre) {
         pk.rec = reinterpret_cast<uint4*>(static_cast<char*>(sc.ws) + sl.packed_offset());
         SoftminParams<T> pprm = prm;      // (the pack kernel reads the rows for the launch's centre only: the one the main kernel takes)
         if (use_p2) pprm.x = static_cast<const T*>(sc.l2.centre_x);
-        if (n_ranges > 0) hipLaunchKernelGGL((pack_columns_kernel<D, T, false, L>), dim3((M + kBlock - 1) / kBlock, B, 1), dim3(kBlock), 0, st, pprm, N, M, pk);
+        // the sorted p = 2 launch on the f16 x 2 layout reads group-major columns, like the dense one (its intervals are whole blocks of
+        // 256 sorted columns: softmin_fwd_x32_body, GSRC); the other block-sparse launches gather theirs from [M][NR]
+        if (use_p2 && L == XL_F16X2) hipLaunchKernelGGL((pack_columns_kernel<D, T, true, L>), dim3((M + 31 + kBlock) / kBlock, B, 1), dim3(kBlock), 0, st, pprm, N, M, pk);
+        else if (n_ranges > 0) hipLaunchKernelGGL((pack_columns_kernel<D, T, false, L>), dim3((M + kBlock - 1) / kBlock, B, 1), dim3(kBlock), 0, st, pprm, N, M, pk);
         else hipLaunchKernelGGL((pack_columns_kernel<D, T, true, L>), dim3((M + 31 + kBlock) / kBlock, B, 1), dim3(kBlock), 0, st, prm, N, M, pk);
     }
     auto main_kernel = [&](auto sparse, dim3 grid, const Ranges& r) {

@@ -110,9 +110,9 @@ __device__ __forceinline__ void pack_column(const SoftminParams<T>& prm, long co
 // cluster-sorted clouds (block-sparse mode) the per-workgroup centre of the on-the-fly path is more accurate, the global one
 // has the accuracy of the dense launches (absolute error of a potential ~ 2^-24 diam^2, independent of eps).
 struct PackedCols {
-    uint4* rec;     // dense launches (GROUPED): [B][ceil(M/32)][NR K blocks][32 columns] (NR = 4, or 2 in the f16 x 2 layout) — the LDS tile layout, so a tile
+    uint4* rec;     // dense launches and the sorted p = 2 launch on the f16 x 2 layout (GROUPED): [B][ceil(M/32)][NR K blocks][32 columns] (NR = 4, or 2 in the f16 x 2 layout) — the LDS tile layout, so a tile
                     //   (which starts on a group boundary there) is staged by a linear, fully coalesced copy;
-                    // block-sparse launches: [M][4 K blocks] — tiles start at arbitrary columns
+                    // the other block-sparse launches: [M][NR K blocks] — tiles start at arbitrary columns
     long stride;    // GROUPED: records per batch item = ceil(M/32) * 32 NR
 };
 
@@ -277,6 +277,16 @@ __device__ __forceinline__ void softmin_fwd_x32_body(const SoftminParams<T>& prm
     constexpr int NR = X32Layout<L>::NR;            // records per column
     constexpr bool H2 = (L == XL_F16X2);
     constexpr int GS = 32 * NR;                     // records per column group of 32
+    // Grouped source: the packed columns are group-major ([group of 32][K block][column], the LDS tile layout: PackedCols), every tile
+    // starts on a group boundary and is staged by a linear copy.  True for the dense pre-packed launches and for the sorted p = 2
+    // launch (P2) on the f16 x 2 layout.  Precondition of the latter: its column intervals start on multiples of 32 and end on
+    // multiples of 32 or at M — they are whole column blocks of kPruneColBlock sorted columns (glhip_cluster.hip: kPruneColBlock % 64
+    // == 0), one piece per tile (the host launches P2 without SplitInfo::gather only).  The pack kernel has written neutral columns
+    // into the cloud's last group.  The bf16 x 3 P2 kernel keeps [M][NR] and the gathered tile: it is held to 80 VGPRs (6 wavefronts
+    // per SIMD) and already spills; the grouped fetch — four records 8 KB apart per thread instead of one column's four adjacent
+    // ones — holds three more loop-invariant registers, i.e. more scratch (profiles/headline_overheads.txt, section 4).
+    constexpr bool GSRC = PRE && (!SPARSE || (P2 && H2));
+    static_assert(!P2 || (kHomeCols % 32 == 0 && kTile % 32 == 0), "P2 tiles and home blocks are whole groups of 32 columns");
     constexpr int kPer = (kTile * NR) / kThreads;   // PRE: records one thread moves per tile
     static_assert((kTile * NR) % kThreads == 0, "tile / workgroup shape");
     constexpr float kFloor = H2 ? kH2Floor : kMinusHuge;      // the running maximum of a row that has seen no mass yet
@@ -322,7 +332,7 @@ __device__ __forceinline__ void softmin_fwd_x32_body(const SoftminParams<T>& prm
     const int nx = XS > 0 ? (xe - xb + 31) >> 5 : 0;      // leftover row tiles of this workgroup (wave-uniform; > 0 only beside a full chunk)
     int home = -1;      // P2: the home column block of this workgroup's slab (workgroup-uniform); -1: first level only
     if constexpr (P2) {
-        // a tile's group g is the global group (j0 >> 5) + g only while a tile is one piece of one interval
+        // (a tile's group g is the global group (j0 >> 5) + g only while a tile is one piece of one interval)
         if (row_begin < row_end && !sp.gather) home = l2.home[(rg.chunks && rg.chunks[0] >= 0) ? rg.chunks[1 + 3 * bx] : bx];
     }
 
@@ -428,14 +438,14 @@ __device__ __forceinline__ void softmin_fwd_x32_body(const SoftminParams<T>& prm
             }
         }
         auto tile_src = [&](int j0) {   // first record of the tile starting at column j0 in the packed buffer
-            return SPARSE ? pk.rec + ((long)b * M + j0) * NR : pk.rec + b * pk.stride + (long)(j0 >> 5) * GS;
+            return GSRC ? pk.rec + b * pk.stride + (long)(j0 >> 5) * GS : pk.rec + ((long)b * M + j0) * NR;
         };
         TileCursor cur;
         cur.q = q_begin + (SPARSE ? split : 0);
         cur.j0 = cur.je = 0;
         open_interval<SPARSE, PRE>(rg, M, q_end, split, ns, cur);
         const int pieces = sp.gather ? kTile : 1;
-        constexpr bool GATHER = SPARSE && PRE;   // pre-packed: the gathered tile is fetched into registers one tile ahead
+        constexpr bool GATHER = SPARSE && PRE && !GSRC;   // pre-packed, [M][NR]: the gathered tile is fetched into registers one tile ahead
         constexpr bool GATHER_NOW = SPARSE && !PRE;   // packed on the fly: gathered when it is staged
         constexpr int kCols = kPer / NR;         // columns a thread moves per tile
         int gcols[kCols], gn = 0;                // GATHER: the columns behind `pre`, and how many real ones the fetched tile holds
@@ -450,19 +460,26 @@ __device__ __forceinline__ void softmin_fwd_x32_body(const SoftminParams<T>& prm
         };
         if constexpr (P2) {
             if (home >= 0) {      // (workgroup-uniform) exact row maxima over the home block: where the running maxima start
-                const int hj0 = home * kHomeCols, hn = min(kHomeCols, M - hj0);
+                // GSRC: the cloud's last block may hold fewer than 8 groups, and only the groups it has are staged and read (workgroup-
+                // uniform; a group of neutral columns alone never raised a maximum above the floor)
+                const int hj0 = home * kHomeCols, hn = min(kHomeCols, M - hj0), hg = GSRC ? (hn + 31) >> 5 : kHomeCols / 32;
                 __syncthreads();                                  // (a previous row pass may still be reading the tile buffer)
-                for (int t = tid; t < kHomeCols; t += kThreads) {
-                    const bool real = t < hn;
-                    const u32x4* col = reinterpret_cast<const u32x4*>(pk.rec + ((long)b * M + hj0 + (real ? t : 0)) * NR);
-                    u32x4* dst = reinterpret_cast<u32x4*>(&tileX[(t >> 5) * GS + (t & 31)]);
+                if constexpr (GSRC) {
+                    const uint4* hsrc = tile_src(hj0);
+                    for (int r = tid; r < hg * GS; r += kThreads) *reinterpret_cast<u32x4*>(&tileX[r]) = *reinterpret_cast<const u32x4*>(hsrc + r);
+                } else {
+                    for (int t = tid; t < kHomeCols; t += kThreads) {
+                        const bool real = t < hn;
+                        const u32x4* col = reinterpret_cast<const u32x4*>(pk.rec + ((long)b * M + hj0 + (real ? t : 0)) * NR);
+                        u32x4* dst = reinterpret_cast<u32x4*>(&tileX[(t >> 5) * GS + (t & 31)]);
 #pragma unroll
-                    for (int kb = 0; kb < NR; ++kb) dst[kb * 32] = real ? col[kb] : neutral[kb];
+                        for (int kb = 0; kb < NR; ++kb) dst[kb * 32] = real ? col[kb] : neutral[kb];
+                    }
                 }
                 __syncthreads();
                 if (wave_active) {
                     float um = kFloor;
-                    for (int G = 0; G < kHomeCols / 32; ++G) {      // (n = 0 so far: plain exponents)
+                    for (int G = 0; G < hg; ++G) {      // (n = 0 so far: plain exponents)
                         f32x16 u;
                         if constexpr (H2) {
                             u = mfma_h32(tileX[G * GS + rec0], Xlo[0], zero16);
@@ -488,7 +505,7 @@ __device__ __forceinline__ void softmin_fwd_x32_body(const SoftminParams<T>& prm
                 fetch_gathered();
             }
         } else if (PRE && cur.q < q_end) {
-            fetch_records<kPer, kThreads, !SPARSE, NR>(pre, tile_src(cur.j0), min(kTile, cur.je - cur.j0), tid);
+            fetch_records<kPer, kThreads, GSRC, NR>(pre, tile_src(cur.j0), min(kTile, cur.je - cur.j0), tid);
         }
 
         while (cur.q < q_end) {
@@ -513,7 +530,7 @@ __device__ __forceinline__ void softmin_fwd_x32_body(const SoftminParams<T>& prm
                     }
                 }
                 __syncthreads();
-                if (PRE && !SPARSE) {
+                if (GSRC) {
 #pragma unroll
                     for (int k = 0; k < kPer; ++k) {
                         const int r = tid + k * kThreads;
@@ -538,7 +555,7 @@ __device__ __forceinline__ void softmin_fwd_x32_body(const SoftminParams<T>& prm
                     }
                 } else if (PRE) {
                     if (nxt.q < q_end)
-                        fetch_records<kPer, kThreads, !SPARSE, NR>(pre, tile_src(nxt.j0), min(kTile, nxt.je - nxt.j0), tid);
+                        fetch_records<kPer, kThreads, GSRC, NR>(pre, tile_src(nxt.j0), min(kTile, nxt.je - nxt.j0), tid);
                 } else if (GATHER_NOW) {
 #pragma unroll
                     for (int k = 0; k < kCols; ++k) {
@@ -557,7 +574,7 @@ __device__ __forceinline__ void softmin_fwd_x32_body(const SoftminParams<T>& prm
                 int G0 = cpart;
                 unsigned long long keep = ~0ull;      // P2: the groups of this tile that may matter to this wavefront's rows
                 if constexpr (P2) {
-                    if (home >= 0 && (j0 & 31) == 0) {
+                    if (home >= 0 && (GSRC || (j0 & 31) == 0)) {      // (the tile's group g is the global group (j0 >> 5) + g)
                         // parts 0-2: the squared gap of one coordinate (beyond D both boxes are 0: no gap); part 3 adds nothing
                         const float2 wb = wbox[wave * 4 + part];
                         const float gap = part < 3 ? fmaxf(fmaxf(gb.x - wb.y, wb.x - gb.y), 0.f) : 0.f;

@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 126 /* 0.1.26 */
+#define GLHIP_VERSION 127 /* 0.1.27 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
