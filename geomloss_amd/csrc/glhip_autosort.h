@@ -7,7 +7,7 @@
 // Now the entry points do it behind the ABI, inside the caller's workspace and on the caller's stream, without a host round trip:
 //   bounding box -> voxel edge (~256 rows per voxel; columns: 512; the pruned p = 2 call: 256 / 256 and a minor key, below) ->
 //   boustrophedon path index of every point as the sort key ->
-//   rocPRIM radix sort -> gathered clouds and column / row vectors -> the block-sparse launch "every slab of 256 rows x all columns"
+//   rocPRIM radix sort (-> the pruned p = 2 call: balanced cells inside blocks of 1024, below) -> gathered clouds and column / row vectors -> the block-sparse launch "every slab of 256 rows x all columns"
 //   with GLHIP_FLAG_MFMA_DIST -> results scattered back to the caller's row order.
 // Conditions: B = 1, dense, D <= 3, N >= 65536, N M >= 5e8 (p = 2: >= 1e11, prune_applies), neither GLHIP_FLAG_NO_MFMA / _DIRECT nor GLHIP_FLAG_NO_SORT, and a
 // workspace of glhip_workspace_bytes(...) (smaller: the generic kernel, as before).  Two sorts of ~0.5 ms against ~200 ms.
@@ -48,6 +48,17 @@ constexpr int kSortRowsPerVoxel = 256;
 //   lack of a finite bound or because every block passes it — no second level, no cost of it, for such a slab).  The sorted p = 2 call orders both clouds in voxels of kSortRowsPerVoxel
 //   points with a minor key of sub-voxels of ~32 points (prune_sort_sub), so that 32 consecutive points are compact; the distance
 //   launches (p = 1, laplacian, energy) keep the order they had.
+//   Balanced cells (library 128).  Voxels and sub-voxels hold 256 and 32 points on average, with Poisson counts: an ALIGNED run of exactly
+//   256 (32) sorted points — what both levels put a box around — usually straddles two of them, and its box is up to twice the size
+//   it could be.  So after the radix sort the sorted p = 2 call splits every whole aligned block of kBalanceBlock = 1024 positions
+//   of the path order like a k-d tree (balance_kernel, glhip_cluster.hip; the rules: glhip_balance.h): five levels with segments of
+//   1024, 512, 256, 128 and 64 points, each segment sorted by (coordinate on the axis of its largest finite extent — ties: the lowest
+//   axis — in an order where -inf < ... < +inf < NaN, position the point had in the block).  The result: cells of exactly 512, 256,
+//   128, 64 and 32 points, every one the half of a median cut, which slabs, column blocks, row tiles and column groups are aligned to.
+//   The order is a function of the input alone; the set of points of every block of 1024 is what the path order put there, so the
+//   voxel path still decides which blocks are neighbours; the last n mod 1024 points keep the path order (the minor key orders them).
+//   The pruning is exact for any order: the order only decides how much is kept.  Bench problem at 1e6, eps = 0.05^2 (tools/prune_model.py,
+//   profiles/balanced_order_model.txt): kept by the first level 0.262 -> 0.227 of the blocks, evaluated after the second 0.155 -> 0.134 (device counter: 0.158 -> 0.140).
 //   Mass rule (round 10).  Both tests above pay ln M of their L for the case that all M columns sit exactly at the threshold.  What the
 //   guarantee needs is that the SUM of everything dropped stays under 2^-26 of the row sum, and that sum is bounded from the records:
 //   with lse(S) = log sum_{j in S} e^(h_j) and pen(A, S) = dmin(A, S)^2 / (2 eps), the terms of a set S of columns sum to at most
@@ -71,7 +82,10 @@ constexpr int kSortRowsPerVoxel = 256;
 //   Headline law at 1e6: tools/prune_model.py, profiles/r10_*.
 constexpr int kPruneColBlock = 256;   // columns per column block T (a multiple of 64)
 constexpr int kPruneRuns = 160;       // runs of kept blocks per slab (the bench problem under the mass rule: mean 71, max 175 — 8 of 3907 slabs
-                                      // close their one-block gaps, 0.01 % more kept pairs: profiles/r10_prune_model.txt)
+                                      // close their one-block gaps, 0.01 % more kept pairs: profiles/r10_prune_model.txt; with balanced
+                                      // cells: profiles/balanced_order_model.txt)
+constexpr int kBalanceBlock = 1024;   // positions of the path order that are balanced together (a multiple of kSortSlab and kPruneColBlock)
+constexpr int kBalanceLeaf = 32;      // points of the smallest cell: the row tile of a wavefront, the column group
 constexpr int kPruneGrid = 64;        // pieces a whole row of column blocks is cut into, at most
 constexpr double kPruneMarginNats = 1.0;
 // The mass rule (round 10): thresholds are found on histograms of the keys, kPruneBuckets buckets of kPruneBucketNats starting at the
@@ -107,7 +121,8 @@ inline size_t as_align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // implemented in glhip_cluster.hip (rocPRIM lives there)
 size_t compact_sort_scratch_bytes(int n);
-// sub > 1: inside a voxel, points are ordered by sub-voxel of edge voxel / sub (the minor key of path_keys_kernel)
+// sub > 1: inside a voxel, points are ordered by sub-voxel of edge voxel / sub (the minor key of path_keys_kernel), then every whole
+// block of kBalanceBlock positions is split into balanced cells (balance_kernel)
 int compact_sort(const void* z, int n, int D, int in_dtype, int rows_per_voxel, int32_t* perm, void* z_sorted, void* scratch,
                  size_t scratch_bytes, hipStream_t st, int sub = 1);
 void gather_f32(const float* src, const int32_t* perm, float* dst, int n, hipStream_t st);       // dst[k] = src[perm[k]]

@@ -16,6 +16,7 @@
 #include <cstdint>
 
 #include "glhip_autosort.h"
+#include "glhip_balance.h"
 #include "glhip_common.h"
 #include "glhip_error.h"
 #include "glhip_prune_words.h"
@@ -315,6 +316,9 @@ __global__ void voxel_kernel(SortHead* head, int n, int D, int rows_per_voxel) {
 // sub > 1 (the sorted p = 2 launches): a minor key orders the points INSIDE a voxel by sub-voxel of edge voxel / sub, along the same
 // kind of path, so that a run of ~rows_per_voxel / sub^D consecutive points (a 32-row wavefront tile, a group of 32 columns) has a
 // sub-voxel's box instead of the whole voxel's; the voxel order itself, which the slab x block bound sees, is unchanged.
+// With sub > 1 this path order is not the final one: balance_kernel reorders the points inside every whole aligned block of
+// kBalanceBlock positions into median-cut cells (glhip_autosort.h: balanced cells); the path decides which points share a block,
+// and it alone orders the last n mod kBalanceBlock points.
 template <typename T>
 __global__ void __launch_bounds__(256) path_keys_kernel(const T* __restrict__ x, int n, int D, const SortHead* __restrict__ head, int sub,
                                                         uint64_t* __restrict__ keys, int32_t* __restrict__ idx) {
@@ -338,6 +342,74 @@ __global__ void __launch_bounds__(256) path_keys_kernel(const T* __restrict__ x,
     }
     keys[i] = path * cells + minor;      // path < 2^60 (at most 2^20 voxels along an axis), cells <= 9
     idx[i] = (int32_t)i;
+}
+
+// The balancing pass of the sorted p = 2 call (glhip_autosort.h: balanced cells; the rules: glhip_balance.h).  One workgroup per whole
+// aligned block of kBalanceBlock positions of `perm`, one point per thread, in place: the block's points and indices go to LDS, five
+// levels sort every segment (1024, 512, ..., 64 positions) by (coordinate on the segment's longest axis, incoming position), and the
+// indices come back in the new order.  The sort is a bitonic network on the words of balance_word, one word per thread in a register:
+// partners less than a wavefront apart meet by shuffle, the others through LDS (20 of the 185 steps).  The words of a segment are
+// distinct, so the order is a function of the block's points alone.
+static_assert(kBalanceBlock == 1024 && kBalanceLeaf == 32, "one point per thread of a 1024-thread workgroup; segments down to one wavefront");
+template <typename T>
+__global__ void __launch_bounds__(kBalanceBlock) balance_kernel(const T* __restrict__ z, int D, int32_t* __restrict__ perm) {
+    __shared__ float pts[3][kBalanceBlock];
+    __shared__ int32_t src[kBalanceBlock];
+    __shared__ unsigned long long words[kBalanceBlock];
+    __shared__ float wlo[kBalanceBlock / 64][3], whi[kBalanceBlock / 64][3];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long base = (long)blockIdx.x * kBalanceBlock;
+    {
+        const int32_t j = perm[base + tid];
+        src[tid] = j;
+        for (int d = 0; d < 3; ++d) pts[d][tid] = d < D ? to_f32<T>(z[(long)j * D + d]) : 0.f;
+    }
+    __syncthreads();
+    int p = tid;      // the incoming position of the point that sits at position tid now
+    for (int seg = kBalanceBlock; seg >= 2 * kBalanceLeaf; seg >>= 1) {
+        // the extents of this thread's segment: per wavefront by shuffle, then over the segment's wavefronts
+        float lo[3], hi[3];      // (an axis beyond D: no finite value, it loses to every other)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            lo[d] = INFINITY;
+            hi[d] = -INFINITY;
+            if (d < D) balance_extent_add(pts[d][p], lo[d], hi[d]);
+            for (int off = 32; off > 0; off >>= 1) {
+                lo[d] = fminf(lo[d], __shfl_xor(lo[d], off, 64));
+                hi[d] = fmaxf(hi[d], __shfl_xor(hi[d], off, 64));
+            }
+            if (lane == 0) { wlo[wave][d] = lo[d]; whi[wave][d] = hi[d]; }
+        }
+        __syncthreads();
+        const int waves = seg >> 6, w0 = wave & ~(waves - 1);
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            for (int w = w0; w < w0 + waves; ++w) {
+                lo[d] = fminf(lo[d], wlo[w][d]);
+                hi[d] = fmaxf(hi[d], whi[w][d]);
+            }
+        }
+        const int axis = balance_axis(lo, hi, 3);
+        unsigned long long v = balance_word(balance_key(pts[axis][p]), (unsigned)p);
+        for (int k = 2; k <= seg; k <<= 1) {
+            for (int j = k >> 1; j > 0; j >>= 1) {
+                unsigned long long o;
+                if (j >= 64) {      // (uniform over the workgroup)
+                    __syncthreads();      // every read of the step before is done (and, first, every read of wlo / whi)
+                    words[tid] = v;
+                    __syncthreads();
+                    o = words[tid ^ j];
+                } else {
+                    const unsigned ol = __shfl_xor((unsigned)v, j, 64), oh = __shfl_xor((unsigned)(v >> 32), j, 64);
+                    o = ((unsigned long long)oh << 32) | ol;
+                }
+                v = (balance_keeps_min(tid, j, k, seg) == (o < v)) ? o : v;
+            }
+        }
+        p = (int)(unsigned)v;
+        __syncthreads();      // wlo / whi and words are free for the next level
+    }
+    perm[base + tid] = src[p];
 }
 
 template <typename T>
@@ -878,6 +950,9 @@ int compact_sort_typed(const void* z_, int n, int D, int rows_per_voxel, int sub
     hipLaunchKernelGGL((path_keys_kernel<T>), dim3(blocks), dim3(256), 0, st, z, n, D, head, sub, keys_in, idx_in);
     if (rocprim::radix_sort_pairs(ws + off, temp, keys_in, keys_out, idx_in, perm, (size_t)n, 0u, 64u, st) != hipSuccess)
         return fail(GLHIP_ELAUNCH, "compact_sort: radix sort failed: %s", hipGetErrorString(hipGetLastError()));
+    // the sorted p = 2 call: balanced cells inside every whole block of kBalanceBlock positions; the partial last block keeps the path order
+    if (sub > 1 && n >= kBalanceBlock)
+        hipLaunchKernelGGL((balance_kernel<T>), dim3(n / kBalanceBlock), dim3(kBalanceBlock), 0, st, z, D, perm);
     hipLaunchKernelGGL((gather_points_kernel<T>), dim3(blocks), dim3(256), 0, st, z, perm, n, D, static_cast<T*>(z_sorted));
     return GLHIP_OK;
 }

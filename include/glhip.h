@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 127 /* 0.1.27 */
+#define GLHIP_VERSION 128 /* 0.1.28 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
@@ -121,6 +121,11 @@ extern "C" {
                                   is taken whose dropped masses stay within a budget — 2^-26 / e, and 2^-26 (1 - 2 / e) beside the 2^-26 / e
                                   of the term rule — found on 0.25-nat histograms in float64 (csrc/glhip_autosort.h).  Same guarantee:
                                   a row loses < 2^-26 of its sum.  glhip_prune_inspect shows the thresholds (profiles/r10_*).
+                                  Version 128: balanced cells.  After the radix sort, every whole aligned block of 1024 positions of both
+                                  sorted clouds is split by median cuts along the longest axis into cells of exactly 512, 256, 128, 64 and
+                                  32 points (csrc/glhip_balance.h), which the slabs, blocks, tiles and groups of both levels are aligned
+                                  to: their boxes no longer straddle two voxels.  The guarantee does not depend on the order; perm_x / perm_y
+                                  of glhip_prune_inspect show it.  The last N mod 1024 (M mod 1024) points keep the path order.
                                   Here this flag means the dense xd / x32 launch. */
 
 /* Environment variables read ONCE per process by the library itself (test / tuning knobs; everything else is an argument):

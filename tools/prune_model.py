@@ -79,6 +79,71 @@ def sort_sub(D):
     return 2 if D >= 3 else (3 if D == 2 else 8)
 
 
+def order_key(v):
+    """glhip_balance.h: balance_key — the order-preserving image of float32 values as uint32: -inf < ... < -0 < +0 < ... < +inf < NaN
+    (every NaN, either sign, is one value)"""
+    b = np.ascontiguousarray(v, np.float32).view(np.uint32)
+    k = np.where(b & np.uint32(0x80000000), ~b, b | np.uint32(0x80000000))
+    return np.where((b & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000), np.uint32(0xFFFFFFFF), k).astype(np.uint32)
+
+
+def balance_axes(p):
+    """glhip_balance.h: balance_axis for segments p (segments, points, D): the axis of the largest extent over the finite values
+    (float32; ties: the lowest axis; an axis without a finite value loses to every other; none at all: axis 0)"""
+    fin = np.isfinite(p)
+    lo = np.where(fin, p, np.float32(np.inf)).min(1)
+    hi = np.where(fin, p, np.float32(-np.inf)).max(1)
+    with np.errstate(over="ignore", invalid="ignore"):
+        ext = np.where(lo <= hi, (hi - lo).astype(np.float32), np.float32(-1.0))
+    return ext.argmax(1)      # (the first of equal maxima)
+
+
+def balanced_order(z, perm, block=1024, leaf=32):
+    """glhip_cluster.hip: balance_kernel, on the order `perm` of the cloud z (float32 values; a bf16 cloud: its values as float32).
+    Every whole aligned block of `block` positions is split like a k-d tree: levels with segments of block, block / 2, ..., 2 leaf
+    points, each segment sorted by (order_key of the coordinate on the segment's own axis, position the point had in the block).
+    The last n mod block positions are left as they are.  Returns the new order."""
+    z = np.asarray(z, np.float32)
+    perm = np.asarray(perm)
+    nb = perm.shape[0] // block
+    out = perm.copy()
+    if nb == 0:
+        return out
+    head = perm[:nb * block].reshape(nb, block)
+    pos = np.broadcast_to(np.arange(block, dtype=np.uint64), (nb, block)).copy()      # incoming position of the point at each place
+    seg = block
+    while seg >= 2 * leaf:
+        ps = pos.reshape(-1, seg)
+        first = (np.arange(ps.shape[0]) * seg // block)[:, None]                      # the segment's block
+        pts = z[head[first, ps.astype(np.int64)]]                                     # (segments, seg, D)
+        axis = balance_axes(pts)
+        key = order_key(np.take_along_axis(pts, axis[:, None, None], 2)[:, :, 0])
+        word = (key.astype(np.uint64) << np.uint64(32)) | ps
+        pos = np.take_along_axis(ps, np.argsort(word, 1), 1).reshape(nb, block)       # (no two words of a segment are equal)
+        seg //= 2
+    out[:nb * block] = np.take_along_axis(head, pos.astype(np.int64), 1).ravel()
+    return out
+
+
+def closed_gaps(keep_row, runs=None):
+    """prune_slabs_kernel's gap closing on the kept blocks of one slab: with more than `runs` runs, the gaps shorter than g — the
+    smallest g that leaves at most `runs` runs — are closed.  Returns the row with the closed gaps kept."""
+    runs = RUNS if runs is None else runs
+    t = np.flatnonzero(keep_row)
+    if t.size == 0:
+        return keep_row.copy()
+    gaps = np.diff(t) - 1
+    real = np.sort(gaps[gaps > 0])[::-1]
+    if real.size + 1 <= runs:
+        return keep_row.copy()
+    g = int(real[runs - 1]) + 1       # at most runs - 1 gaps of at least g blocks stay open
+    out = keep_row.copy()
+    for a, n in zip(t[:-1], gaps):
+        if 0 < n < g:
+            out[a + 1:a + 1 + n] = True
+    return out
+
+
 def boxes(z, size):
     n = z.shape[0]
     k = (n + size - 1) // size
@@ -359,13 +424,50 @@ def bench_problem(n, seed=1000):
     return x.numpy(), y.numpy(), h.numpy(), eps
 
 
+def tiles_of(keep_row, width=512):
+    """column tiles of `width` columns the reducing kernel stages for one slab: every run of kept blocks is walked in whole tiles"""
+    k = np.concatenate([[0], keep_row.astype(np.int8), [0]])
+    d = np.diff(k)
+    return int(sum(-(-(int(b) - int(a)) * BLOCK // width) for a, b in zip(np.flatnonzero(d == 1), np.flatnonzero(d == -1))))
+
+
+def balanced_lines(x, y, h, n, eps_list, n_slabs):
+    """The mass rule on today's order of the sorted p = 2 call and on the balanced one (balanced_order): first level, runs, gap closing,
+    tiles, and the second level on a sample of slabs scaled to all of them by the first-level fraction."""
+    sub = sort_sub(x.shape[1])
+    px, py = compact_order2(x, 256, sub), compact_order2(y, 256, sub)
+    C = (n + SLAB - 1) // SLAB
+    slabs = np.arange(5, C, max(1, (C - 5) // n_slabs)) if n_slabs > 0 and C > 5 else np.zeros(0, int)
+    rows = float(sum(min(n, (c + 1) * SLAB) - c * SLAB for c in slabs))
+    for eps in eps_list:
+        for name, qx, qy in (("path order", px, py), ("balanced 1024", balanced_order(x, px), balanced_order(y, py))):
+            xs, ys, hs = x[qx], y[qy], h[qy]
+            keep, mlb, t1, L = plan_mass(xs, ys, hs, eps)
+            r = runs_per_slab(keep)
+            closed = keep.copy()
+            for c in np.flatnonzero(r > RUNS):
+                closed[c] = closed_gaps(keep[c])
+            first = kept_pairs(closed, n, n) / (float(n) * n)
+            line = (f"{name}: n = {n}  eps = {eps:.4g}: first level keeps {kept_pairs(keep, n, n) / (float(n) * n):.4f}, runs per slab mean "
+                    f"{r.mean():.1f} max {r.max()}, slabs over {RUNS} runs {(r > RUNS).sum()}, kept blocks {int(keep.sum())} + {int(closed.sum() - keep.sum())} "
+                    f"by gap closing, 512-column tiles {sum(tiles_of(closed[c]) for c in range(C))}")
+            if len(slabs):
+                ev, k1, _ = level2_mass(xs, ys, hs, eps, closed, L, slabs)
+                line += (f"; on {len(slabs)} slabs: first level {k1 / (rows * n):.4f}, evaluated after the second {ev / (rows * n):.4f}, "
+                         f"scaled to all slabs {ev / k1 * first:.4f}")
+            print(line, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--balanced", action="store_true", help="only the lines that compare the path order with the balanced one")
     ap.add_argument("--n", type=int, default=1000000)
     ap.add_argument("--eps", type=float, nargs="*", default=[0.01**2, 0.05**2, 0.2**2, 1.0])
     ap.add_argument("--slabs", type=int, default=40, help="slabs sampled for the second level (0: first level only)")
     a = ap.parse_args()
     x, y, h, _ = bench_problem(a.n)
+    if a.balanced:
+        return balanced_lines(x, y, h, a.n, a.eps, a.slabs)
     px, py = compact_order(x, 256), compact_order(y, 512)
     xs, ys, hs = x[px], y[py], h[py]
     for eps in a.eps:
@@ -398,6 +500,7 @@ def main():
             print(f"mass rule,  voxels 256 / 256, sub {sub}: n = {a.n}  eps = {eps:.4g}: first level keeps {kept_pairs(keep, a.n, a.n) / (float(a.n) * a.n):.4f} "
                   f"(runs per slab mean {r.mean():.1f} max {r.max()}, slabs over {RUNS} runs {(r > RUNS).sum()}); on {len(slabs)} slabs: "
                   f"first level {k1 / (rows * a.n):.4f}, evaluated after the second {ev / (rows * a.n):.4f}", flush=True)
+    balanced_lines(x, y, h, a.n, a.eps, a.slabs)
 
 
 if __name__ == "__main__":
