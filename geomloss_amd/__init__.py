@@ -22,6 +22,7 @@ from .wasserstein_barycenter_images import ImagesBarycenter  # noqa: E402
 from . import sinkhorn_divergence  # noqa: E402
 from . import ot  # noqa: E402  (`from geomloss import ot`: ot.solve_sample on the same kernels)
 from . import transport  # noqa: E402  (apply_plan / barycentric_map for the potentials of the legacy API)
-from .transport import apply_plan, barycentric_map  # noqa: E402
+from .transport import apply_plan, barycentric_map, plan_argmax  # noqa: E402
+from .cluster import kmeans  # noqa: E402  (cluster labels in any dimension for the "multiscale" backend)
 
-__all__ = ["SamplesLoss", "ImagesBarycenter", "sinkhorn_divergence", "hip", "ot", "transport", "apply_plan", "barycentric_map"]
+__all__ = ["SamplesLoss", "ImagesBarycenter", "sinkhorn_divergence", "hip", "ot", "transport", "apply_plan", "barycentric_map", "plan_argmax", "kmeans"]

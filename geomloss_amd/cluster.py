@@ -10,6 +10,9 @@ the sorted cloud, and a boolean cluster-cluster mask becomes CSR-like lists of c
 One deliberate difference: ``from_matrix`` merges column intervals that are adjacent in memory
 (consecutive kept clusters), so the kernels stream fewer, longer tiles.  The reduced set of
 (i, j) pairs is unchanged.
+
+:func:`kmeans` produces cluster labels in any dimension (the reference's tutorial recipe for D > 3, where there is no cubic grid),
+for the 6-argument call form of ``SamplesLoss``.
 """
 
 import torch
@@ -69,6 +72,65 @@ def _cluster_ranges_centroids(x, lab, weights, min_weight, perm):
     w_c = seg[0]
     cents = (seg[1:] / w_c.clamp_min(min_weight)).t().contiguous()
     return ranges, cents.to(x.dtype), w_c.to(wdtype)
+
+
+def kmeans_update(x, labels, centroids, weights=None):
+    """One centroid update of Lloyd's algorithm: every centroid moves to the (weighted) mean of the points labelled with it; a
+    cluster that received no point (or no weight) keeps its row of ``centroids``.  Sorted segment sums
+    (:func:`cluster_ranges_centroids`): no float atomics, the same inputs give the same centroids bit for bit.
+    x (N,D), labels (N,) integers in [0, K), centroids (K,D) fp32 -> (K,D) fp32."""
+    with torch.no_grad():
+        K = centroids.shape[0]
+        _, cents, w_c = cluster_ranges_centroids(x.detach().float(), labels, weights)
+        C = cents.shape[0]                                   # max label + 1 <= K: the trailing clusters may be empty
+        if C > K:
+            raise ValueError(f"kmeans_update: label {C - 1} with {K} centroids")
+        new = centroids.clone()
+        new[:C] = torch.where((w_c > 0).unsqueeze(1), cents, centroids[:C])
+        return new
+
+
+def kmeans(x, K, n_iter=10, init=None, weights=None, generator=None):
+    """Lloyd's K-means on a GPU cloud, the reference's recipe for cluster labels in dimension D > 3
+    (``examples/sinkhorn_multiscale/plot_optimal_transport_cluster.py:154-187``, a KeOps ``generic_argmin`` loop): ``n_iter`` times,
+    assign every point to its nearest centroid (:func:`geomloss_amd.hip.argmin`, on the matrix cores, nothing of size N x K is
+    stored), then move every centroid to the mean of its points.
+
+    x (N,D) fp32 | bf16 on a GPU, 1 <= D <= 4095; returns ``(labels, centroids)``: int32 (N,) and fp32 (K,D).  As in the
+    tutorial, the labels are those of the last assignment and the centroids have been updated once more since.  The labels go
+    straight into ``SamplesLoss("sinkhorn", backend="multiscale", cluster_scale=...)(labels_x, a, x, labels_y, b, y)``.
+
+    ``init=None``: K distinct points of ``x`` drawn with ``generator`` (the tutorial's ``randperm(N)[:K]``); ``init`` (K,D): start
+    from these centroids.  ``weights`` (N,): weighted means.  ``n_iter=0`` only assigns.
+    Differences with the tutorial: the centroid update is deterministic (sorted segment sums in float64 instead of
+    ``bincount(weights=)`` float atomics: two runs are bit-identical), ties between centroids go to the smallest index, and a
+    cluster that receives no point keeps its previous centroid where the tutorial's 0 / 0 gives NaN.  Not recorded by autograd."""
+    from . import hip
+    with torch.no_grad():
+        x = x.detach()
+        if x.dim() != 2:
+            raise ValueError(f"geomloss_amd.kmeans: expected an (N, D) cloud, got {tuple(x.shape)}")
+        N, D = x.shape
+        K = int(K)
+        if init is None:
+            if not 1 <= K <= N:
+                raise ValueError(f"geomloss_amd.kmeans: K = {K} centroids cannot be drawn from {N} points")
+            dev = x.device if generator is None else generator.device
+            c = x[torch.randperm(N, generator=generator, device=dev)[:K].to(x.device)].float()
+        else:
+            c = init.detach().to(device=x.device, dtype=torch.float32).clone()
+            if tuple(c.shape) != (K, D):
+                raise ValueError(f"geomloss_amd.kmeans: init should have shape {(K, D)}, got {tuple(c.shape)}")
+        w = None if weights is None else weights.detach().reshape(-1).to(x.device)
+        if w is not None and w.shape[0] != N:
+            raise ValueError(f"geomloss_amd.kmeans: expected {N} weights, got {w.shape[0]}")
+        labels = None
+        for _ in range(int(n_iter)):
+            labels = hip.argmin(x, c)
+            c = kmeans_update(x, labels, c, w)
+        if labels is None:
+            labels = hip.argmin(x, c)
+        return labels.int(), c
 
 
 def sort_clusters(x, lab):

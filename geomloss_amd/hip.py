@@ -30,6 +30,7 @@ XD_MAX_DIM = 16                 # the fused four-softmin iteration / annealing /
                                 # gradients stop at this dimension (glhip_softmin_xd.h, glhip_wsum_t32.h)
 MFMA_FWD_MAX_DIM = 4095         # p = 2 soft-min forward / half-step and gaussian product run on the matrix cores up to this dimension
                                 # (17 ... 4095: the K-chunked kernel of glhip_softmin_xk.h; kept in step with the library by tests/test_anyd_kernels_gpu.py)
+ARGMIN_MAX_DIM = 4095           # argmin takes p = 2 clouds of every dimension up to this one (glhip_argmin_xk.h)
 PLAN_MAX_DIM = 4095             # plan_apply_nd applies p = 2 transport plans to features up to this dimension (17 ... 4095: glhip_plan_apply_xk.h)
 # kernel families reported by softmin_fwd_family (GLHIP_FAMILY_* of glhip.h)
 FAMILY_VALU, FAMILY_X32, FAMILY_XD, FAMILY_XK, FAMILY_DIST, FAMILY_GENERIC = 0, 1, 2, 3, 4, 5
@@ -81,6 +82,9 @@ SIGNATURES = {
     "glhip_lse_lines_bwd": (_c_int, [_vp, _vp, _vp, _vp, ctypes.c_long, _c_int, _c_float, _c_int, _vp]),
     "glhip_cmin_fwd": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int] + _RANGES + _TAIL),
     "glhip_max_lines_fwd": (_c_int, [_vp, _vp, ctypes.c_long, _c_int, _c_float, _c_int, _vp]),
+    "glhip_argmin_supported": (_c_int, [_c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int]),
+    "glhip_argmin_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int]),
+    "glhip_argmin": (_c_int, [_vp] * 5 + [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int] + _RANGES + _TAIL),
     "glhip_cluster_workspace_bytes": (_c_size, [_c_int, _c_int]),
     "glhip_grid_cluster": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_float, _c_float] + [_vp] * 7 + [_vp, _c_size, _vp]),
     "glhip_block_ranges": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float] + [_vp] * 6
@@ -1565,6 +1569,58 @@ def cmin(x, y, g, p=2, ranges=None, flags=0):
                                 *_range_args(ranges, B), *ws_args, int(flags) | ENV_FLAGS, _stream(xb))
     _check(rc, lib)
     return out if batched else out.view(-1)
+
+
+def argmin_supported(B, N, M, D, p=2, dtype=F32, n_ranges=0):
+    """Whether ``glhip_argmin`` serves a launch of this shape (p = 2, dense, 1 <= D <= ARGMIN_MAX_DIM, fp32 / bf16 clouds): the
+    predicate the launch itself evaluates (``glhip_argmin_supported``), host arithmetic only — no device is touched.  Raises
+    ``ValueError`` for what the entry point rejects (negative sizes, D < 1, a bad p or dtype)."""
+    ok = int(load_library().glhip_argmin_supported(int(B), int(N), int(M), int(D), int(p), int(dtype), int(n_ranges)))
+    if ok < 0:
+        raise ValueError(f"glhip_argmin_supported: bad arguments B={B} N={N} M={M} D={D} p={p} dtype={dtype} n_ranges={n_ranges}")
+    return bool(ok)
+
+
+def argmin(x, y, g=None, return_value=False, flags=0, p=2):
+    """Arg-reduction on the matrix cores (``glhip_argmin``): ``argmin_j [|x_i - y_j|^2 / 2 - g_j]`` — the nearest column for
+    ``g = None``, what KeOps' ``generic_argmin("SqDist(x,y)", ...)`` returns in the reference's K-means recipe; the column a plan row
+    sends most of its mass to for g = dual potential + eps log weight.
+    x: (N,D)|(B,N,D), y: (M,D)|(B,M,D), g: (M,)|(B,M)|None -> int32 (N,)|(B,N); with ``return_value`` also the fp32 minima.
+    Ties go to the smallest index; ``g_j = -inf`` excludes column j; a row without an admissible column (M = 0, every g = -inf) gets
+    index -1 and value +inf.  Not recorded by autograd.  float64 clouds, p != 2 and D > ARGMIN_MAX_DIM = 4095 raise
+    ``NotImplementedError``; block-sparse ranges, k > 1 neighbours and p = 1 are out of scope."""
+    if x.dtype == torch.float64 or y.dtype == torch.float64:
+        raise NotImplementedError("geomloss_amd.hip.argmin: float64 clouds are not supported (cast to float32)")
+    D = x.shape[-1]
+    if p != 2 or D > ARGMIN_MAX_DIM:
+        raise NotImplementedError(f"geomloss_amd.hip.argmin: only p = 2, D <= {ARGMIN_MAX_DIM} (got p = {p}, D = {D})")
+    lib = load_library()
+    with torch.no_grad():
+        xp, yp = _points(x.detach(), "x"), _points(y.detach(), "y")
+        if g is not None and g.numel() != yp.numel() // max(D, 1):
+            raise ValueError(f"geomloss_amd.hip.argmin: expected one dual value per column, {tuple(y.shape[:-1])}, got {tuple(g.shape)}")
+        gv = _f32(g).to(xp.device) if g is not None else torch.empty(yp.shape[:-1], dtype=torch.float32, device=xp.device)
+        xb, yb, _, batched = _as_batched(xp, yp, gv.new_empty(xp.shape[0] if xp.dim() == 3 else 1))      # (g may be empty: reshaped below)
+        gb = gv.reshape(yb.shape[:2])
+        if yb.dtype != xb.dtype:
+            yb = yb.to(xb.dtype)
+        if yb.shape[0] != xb.shape[0] or yb.shape[2] != D:
+            raise ValueError(f"geomloss_amd.hip.argmin: clouds of shapes {tuple(x.shape)} and {tuple(y.shape)} do not go together")
+        B, N, _ = xb.shape
+        M = yb.shape[1]
+        index = torch.empty((B, N), dtype=torch.int32, device=xb.device)
+        value = torch.empty((B, N), dtype=torch.float32, device=xb.device) if return_value else None
+        with torch.cuda.device(xb.device):
+            nbytes = int(lib.glhip_argmin_workspace_bytes(B, N, M, D))
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=xb.device) if nbytes else None
+            rc = lib.glhip_argmin(xb.data_ptr(), yb.data_ptr(), gb.data_ptr() if g is not None else None, index.data_ptr(),
+                                  value.data_ptr() if return_value else None, B, N, M, D, int(p), _dtype_code(xb), *_NO_RANGES,
+                                  ctypes.c_void_p(ws.data_ptr()) if nbytes else None, nbytes, int(flags) | ENV_FLAGS, _stream(xb))
+        _check(rc, lib)
+    if not batched:
+        index = index.view(-1)
+        value = value.view(-1) if return_value else None
+    return (index, value) if return_value else index
 
 
 def max_lines(g, step, p=2):

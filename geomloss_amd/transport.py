@@ -9,6 +9,9 @@ soft-min reduction and one matrix-core application of the plan (:func:`geomloss_
 itself handles.  GPU tensors only, like the ``online`` backend; p = 2, float32 / bfloat16 clouds of dimension D <= 4095: D <= 16 on
 the kernel with resident operands (up to 128 feature columns per pass), 17 <= D <= 4095 — principal components, embeddings — on the
 K-chunked kernel (64 per pass); beyond, ``NotImplementedError``.  Nothing here is recorded by autograd.
+
+:func:`plan_argmax` gives the hard correspondence instead of an average: the column that receives most of a row's mass, one
+arg-reduction (:func:`geomloss_amd.hip.argmin`), same clouds and dimensions.
 """
 
 import math
@@ -17,7 +20,7 @@ import torch
 
 from . import hip
 
-__all__ = ["apply_plan", "barycentric_map"]
+__all__ = ["apply_plan", "barycentric_map", "plan_argmax"]
 
 
 def _log_weights(w, like, count):
@@ -54,3 +57,14 @@ def barycentric_map(x, y, F, G, blur, b=None):
         Gf = G.detach().float().reshape(y.shape[:-1])
         h = _log_weights(b, Gf, y.shape[-2]) + Gf / eps
         return hip.plan_apply_nd(eps, x, y, h, y.detach().float())
+
+
+def plan_argmax(x, y, F, G, blur, b=None):
+    """``argmax_j P_ij`` int32 (N,)|(B,N): the column that receives most of the mass of row i — a hard correspondence where
+    :func:`barycentric_map` gives an average.  It is ``argmin_j [|x_i - y_j|^2 / 2 - G_j - blur^2 log b_j]``
+    (:func:`geomloss_amd.hip.argmin`); columns of zero weight are never returned, ties go to the smallest index.  Like the
+    barycentric map it does not depend on ``a`` or ``F``; ``F`` is accepted so that the call reads like :func:`apply_plan`."""
+    eps = float(blur) ** 2
+    with torch.no_grad():
+        Gf = G.detach().float().reshape(y.shape[:-1])
+        return hip.argmin(x, y, Gf + eps * _log_weights(b, Gf, y.shape[-2]))

@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 128 /* 0.1.28 */
+#define GLHIP_VERSION 129 /* 0.1.29 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
@@ -531,6 +531,34 @@ int glhip_cmin_fwd(const void* x, const void* y, const float* g, float* out, int
                    const int32_t* ranges_i, const int32_t* slices_i, const int32_t* redranges_j, int n_ranges,
                    void* workspace, size_t workspace_bytes, int flags, void* stream);
 int glhip_max_lines_fwd(const float* g, float* out, long R, int N, float step, int p, void* stream);
+/*
+ * Arg-reduction (version 129; glhip_argmin_xk.h): for every row the column of the smallest dual-shifted cost,
+ *   index[b,i] = argmin_j [ |x[b,i] - y[b,j]|^2 / 2 - g[b,j] ],   value[b,i] = that minimum.
+ * Replaces: KeOps' generic_argmin("SqDist(x,y)", ...) of the reference's K-means recipe
+ * (examples/sinkhorn_multiscale/plot_optimal_transport_cluster.py:151-191) with g = NULL, and gives the hard correspondences of a
+ * transport plan with g = dual potential + eps log weight.
+ *   x (B,N,D), y (B,M,D) fp32 | bf16;  g (B,M) fp32 or NULL (= 0: nearest neighbour);  index (B,N) int32;  value (B,N) fp32 or NULL.
+ *   Supported: p == 2, 1 <= D <= 4095, dense launches (n_ranges == 0), any B <= 65535; p = 1, D > 4095 and block-sparse ranges return
+ *   GLHIP_EUNSUPPORTED (the range arguments are there so that block-sparse launches can follow without an ABI change).
+ *   The kernel is the staging and MFMA chain of the forward reduction of 17 <= D <= 4095 (glhip_softmin_xk.h: 256 x 128 blocks, bf16 x 3
+ *   pieces split on the fly, points centred per row block) for every D from 1, with a compare-and-select epilogue.
+ *   Ties go to the smallest column index, whatever the number of column splits: exact duplicates among the columns return the first
+ *   copy.  g[b,j] = -inf marks a column that cannot be chosen; a row without an admissible column (M == 0, every g = -inf) gets
+ *   index -1 and value +inf.  N == 0 or B == 0 launches nothing.
+ *   Accuracy: the exponents of glhip_softmin_xk.h with s = 1 — the cost of the returned column exceeds the true minimum by at most
+ *   2 (NM + 5) 2^-24 (diam^2 + max |g|), NM = ceil((6 + 6 D) / 16), and value is within that of the minimum.
+ *   flags: GLHIP_FLAG_NO_SPLIT; GLHIP_FLAG_F16X2 is accepted and ignored (bf16 x 3 only: no range precondition); others are ignored.
+ *   Workspace: glhip_argmin_workspace_bytes holds the (exponent, index) partials of the column splits the launch would like; NULL or
+ *   short means fewer or no splits, with the same results index for index.
+ * glhip_argmin_supported: host arithmetic only, the predicate the launch itself evaluates — 1 / 0, GLHIP_EINVAL for what the entry
+ * point rejects (negative sizes, D < 1, a bad p or dtype).
+ */
+int glhip_argmin_supported(int B, long N, long M, int D, int p, int dtype, int n_ranges);
+size_t glhip_argmin_workspace_bytes(int B, int N, int M, int D);
+int glhip_argmin(const void* x, const void* y, const float* g, int32_t* index, float* value,
+                 int B, int N, int M, int D, int p, int in_dtype,
+                 const int32_t* ranges_i, const int32_t* slices_i, const int32_t* redranges_j, int n_ranges,
+                 void* workspace, size_t workspace_bytes, int flags, void* stream);
 /*
  * The cluster pyramid of the two-scale ("multiscale") backends, on the device.
  *
