@@ -106,12 +106,16 @@ def test_softmin_batched_and_bf16(cuda):
 
 
 def test_softmin_translation_robust(cuda):
-    """Clouds far from the origin: the per-workgroup re-centring keeps the expanded form accurate."""
-    x, y, h = _clouds(5, 600, 700, 3, offset=1000.0)
-    eps = 0.05**2
-    ref = oracle_c.softmin(eps, x, y, h, 2)
-    out = hip.softmin(eps, _t(x, cuda), _t(y, cuda), _t(h, cuda)).cpu().numpy()
-    assert np.abs(out - ref).max() < 1e-5   # potentials are O(1): absolute tolerance
+    """Clouds far from the origin: the per-workgroup re-centring keeps the expanded form accurate — on both K layouts and on pre-packed
+    columns; D = 8 and D = 40 (eps scaled with D, as everywhere in the suite): kernels that centre on the first row of a block."""
+    for D in (3, 8, 40):
+        x, y, h = _clouds(5, 600, 700, D, offset=1000.0)
+        eps = 0.05**2 * D / 3
+        ref = oracle_c.softmin(eps, x, y, h, 2)
+        for flags in (0, hip.FLAG_F16X2, hip.FLAG_PREPACK):
+            out = hip.softmin(eps, _t(x, cuda), _t(y, cuda), _t(h, cuda), flags=flags).cpu().numpy()
+            print(f"translation D={D} flags={flags}: err {np.abs(out - ref).max():.3e}")
+            assert np.abs(out - ref).max() < 1e-5, (D, flags)   # potentials are O(1): absolute tolerance
 
 
 def test_softmin_rescale_branch_and_infinities(cuda):
@@ -124,18 +128,19 @@ def test_softmin_rescale_branch_and_infinities(cuda):
     h[6] = -100000.0
     eps = 0.05**2
     ref = oracle_c.softmin(eps, x, y, h, 2)
-    for flags in (0, 8, hip.FLAG_NO_MFMA, hip.FLAG_NO_SPLIT):
+    # (GLHIP_FLAG_F16X2: what SamplesLoss selects by default for D <= 3; in its range here: |H| <= 5000, exponents floored at -5e5)
+    for flags in (0, 8, hip.FLAG_NO_MFMA, hip.FLAG_NO_SPLIT, hip.FLAG_F16X2, hip.FLAG_F16X2 | hip.FLAG_NO_SPLIT):
         out = hip.softmin(eps, _t(x, cuda), _t(y, cuda), _t(h, cuda), flags=flags).cpu().numpy()
-        assert np.isfinite(out).all() and np.abs(out - ref).max() < 1.2e-6 + 2e-6 * np.abs(ref).max()
+        assert np.isfinite(out).all() and np.abs(out - ref).max() < 1.2e-6 + 2e-6 * np.abs(ref).max(), flags
     # lazy-max stress for the matrix-core path: exponents climbing by ~70 (base 2) every 64 columns (so every
     # LDS tile overflows its speculative pass and is redone exactly), then a cliff, then one late spike
     h2 = (np.arange(M) // 64 * 48.0).astype(np.float32)
     h2[M // 2:] -= 3000.0
     h2[-3] = 5000.0
     ref2 = oracle_c.softmin(eps, x, y, h2, 2)
-    for flags in (0, 8, hip.FLAG_NO_MFMA):
+    for flags in (0, 8, hip.FLAG_NO_MFMA, hip.FLAG_F16X2, hip.FLAG_F16X2 | hip.FLAG_NO_SPLIT):
         out2 = hip.softmin(eps, _t(x, cuda), _t(y, cuda), _t(h2, cuda), flags=flags).cpu().numpy()
-        assert np.isfinite(out2).all() and relerr(out2, ref2) < 2e-6
+        assert np.isfinite(out2).all() and relerr(out2, ref2) < 2e-6, flags
 
 
 def _random_ranges(rng, N, M, ci, cj, density, dev):
