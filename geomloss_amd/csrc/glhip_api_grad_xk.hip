@@ -1,5 +1,5 @@
 // glhip_api_grad_xk.hip — C-ABI part 10: the p = 2 soft-min gradient of 17 <= D <= 4095 on the matrix cores (GLHIP_FLAG_XK_GRAD):
-// xk_grad_kernel of glhip_softmin_grad_xk.h, launched by glhip_softmin_bwd_x (glhip_api_bwd.hip) where glhip_softmin_bwd_x_uses_plan
+// xk_plan_kernel on XkGradParams (glhip_softmin_grad_xk.h), launched by glhip_softmin_bwd_x (glhip_api_bwd.hip) where glhip_softmin_bwd_x_uses_plan
 // says so.  A translation unit of its own: the parallel build does not get longer.
 #include "glhip_launch.h"
 #include "glhip_softmin_grad_xk.h"
@@ -27,7 +27,7 @@ void launch_xk_grad_pass(const XkGradParams<T>& prm, int B, int N, int M, int D,
     if (!(ps.xcd && sl.take_xcd(ps.n)))      // (a grid beyond 2^31 workgroups stays on the plain 3-D grid)
         sl.sp.n_splits = ps.xcd ? choose_splits(sl.row_blocks, M, 0, sl.fit) : ps.n;
     const dim3 grid = sl.sp.xcd_grid_x > 0 ? dim3((unsigned)((long)sl.gx * B * sl.sp.n_splits), 1, 1) : dim3(sl.gx, B, sl.sp.n_splits);
-    hipLaunchKernelGGL((xk_grad_kernel<T, NCH, L>), grid, dim3(kXkThreads), 0, st, prm, N, M, D, sl.sp);
+    hipLaunchKernelGGL((xk_plan_kernel<T, NCH, L, XkGradParams<T>>), grid, dim3(kXkThreads), 0, st, prm, N, M, D, sl.sp);
     if (sl.sp.n_splits > 1) {
         const long rows = (long)B * N, items = rows * prm.nv;
         hipLaunchKernelGGL((xk_grad_merge_kernel<T>), dim3((unsigned)((items + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, prm, N, D, rows, sl.sp);

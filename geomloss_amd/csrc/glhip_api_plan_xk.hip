@@ -34,7 +34,7 @@ void launch_xk_plan_pass(const PlanParams<T>& prm, int B, int N, int M, int D, c
     if (!(ps.xcd && sl.take_xcd(ps.n)))      // (a grid beyond 2^31 workgroups stays on the plain 3-D grid)
         sl.sp.n_splits = ps.xcd ? choose_splits(sl.row_blocks, M, 0, sl.fit) : ps.n;
     const dim3 grid = sl.sp.xcd_grid_x > 0 ? dim3((unsigned)((long)sl.gx * B * sl.sp.n_splits), 1, 1) : dim3(sl.gx, B, sl.sp.n_splits);
-    hipLaunchKernelGGL((xk_plan_kernel<T, NCH, L>), grid, dim3(kXkThreads), 0, st, prm, N, M, D, sl.sp);
+    hipLaunchKernelGGL((xk_plan_kernel<T, NCH, L, PlanParams<T>>), grid, dim3(kXkThreads), 0, st, prm, N, M, D, sl.sp);
     if (sl.sp.n_splits > 1) {
         const long rows = (long)B * N, items = rows * prm.nv;
         hipLaunchKernelGGL(plan_merge_kernel, dim3((unsigned)((items + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, prm.out, prm.mass, rows,

@@ -4,9 +4,9 @@
 // generic_argmin("SqDist(x,y)") of the reference's K-means recipe (g = 0) and gives the hard correspondences of a transport plan
 // (g = dual potential + eps log weight).
 //
-// It is the staging and the MFMA chain of xk_fwd_kernel (glhip_softmin_xk.h) with another epilogue: the same 256 rows x 128 columns
-// per workgroup, 8 wavefronts as 4 x 2, stages of 6 K chunks, points centred on the first row of the row block, split into bf16 x 3
-// pieces on the fly.  The bf16 x 3 layout only: it has no range precondition.  s = 1, row scalar 0, column scalar
+// It is the staging and the MFMA chain of xk_fwd_kernel (glhip_softmin_xk.h: xk_exponent_blocks, called with scales of 1) with another
+// epilogue: the same 256 rows x 128 columns per workgroup, 8 wavefronts as 4 x 2, stages of 6 K chunks, points centred on the first
+// row of the row block, split into bf16 x 3 pieces on the fly.  The bf16 x 3 layout only: it has no range precondition.  s = 1, row scalar 0, column scalar
 // H_j = g_j - |yt_j|^2 / 2: the exponent block u_ij = H_j + xt_i . yt_j is largest where the cost |xt_i|^2 / 2 - u_ij is smallest.
 // kXkMinD = 17 is where the soft-min dispatch hands over to this family, not a limit of the packing: xk_num_mfma / xk_num_groups
 // count the scalar item plus D coordinates from D = 1 (one MFMA, one group), and slots past the last coordinate are zero.
@@ -46,8 +46,6 @@ template <typename T>
 __global__ void __launch_bounds__(kXkThreads, 4)
 argmin_xk_kernel(ArgminParams<T> prm, int N, int M, int D, SplitInfo sp) {
     constexpr int L = XL_BF16X3;
-    constexpr int kItems = 4;                                 // items (coordinates) of a 24-slot group
-    constexpr int kLead = 1;                                  // items taken by the scalar item
     __shared__ XkLds lds;
 
     int bx, b, split;
@@ -104,69 +102,7 @@ argmin_xk_kernel(ArgminParams<T> prm, int N, int M, int D, SplitInfo sp) {
 
             const bool wave_on = wave_rows && wc * kXkCG < ncg;
             f32x16 acc[kXkRT][kXkCG];
-#pragma unroll
-            for (int rt = 0; rt < kXkRT; ++rt)
-#pragma unroll
-                for (int cg = 0; cg < kXkCG; ++cg)
-#pragma unroll
-                    for (int k = 0; k < 16; ++k) acc[rt][cg][k] = 0.f;
-
-            const int npts = nr32 + ncg * 32;
-            for (int g0 = 0; g0 < NG; g0 += kXkStageGroups) {
-                __syncthreads();                              // the previous stage is consumed (first stage: the scalars are written)
-                // ---- split: work item = (point, group of the stage); the groups of a point on neighbouring lanes ----
-                for (int t = tid; t < npts * kXkStageGroups; t += kXkThreads) {
-                    const int pt = t / kXkStageGroups, gi = t % kXkStageGroups;
-                    const int g = g0 + gi;
-                    if (g >= NG) continue;
-                    const bool isrow = pt < nr32;
-                    const int slot = isrow ? pt : kXkRows + (pt - nr32);
-                    const int i = lds.idx[slot];
-                    const T* p = (isrow ? xb : yb) + (long)max(i, 0) * D;
-                    const int d0 = kItems * g - kLead;
-                    const float sc = lds.scal[slot];
-                    uint32_t w[2][6];
-                    auto half_group = [&](auto hsel) {          // items d0 + 2 HALF, d0 + 2 HALF + 1 of the point -> six dwords
-                        constexpr int HALF = decltype(hsel)::value;
-                        float val[kItems / 2];
-#pragma unroll
-                        for (int q = 0; q < kItems / 2; ++q) {
-                            const int d = d0 + HALF * (kItems / 2) + q;
-                            val[q] = (d >= 0 && d < D && i >= 0) ? to_f32<T>(p[d]) - to_f32<T>(centre[d]) : 0.f;
-                        }
-                        if (isrow) xk_pack_half<true, L, HALF>(g == 0, sc, val, w[HALF]);
-                        else xk_pack_half<false, L, HALF>(g == 0, sc, val, w[HALF]);
-                    };
-                    half_group(std::integral_constant<int, 0>{});
-                    half_group(std::integral_constant<int, 1>{});
-                    const uint4 rec[3] = {uint4{w[0][0], w[0][1], w[0][2], w[0][3]}, uint4{w[0][4], w[0][5], w[1][0], w[1][1]},
-                                          uint4{w[1][2], w[1][3], w[1][4], w[1][5]}};
-                    uint4* dst = &lds.buf[((slot >> 5) * kXkStageRecs + 3 * gi) * kXkRecStride + (slot & 31)];
-#pragma unroll
-                    for (int r = 0; r < 3; ++r) dst[r * kXkRecStride] = rec[r];
-                }
-                __syncthreads();
-                // ---- multiply: K chunk c of the stage = records 2 c (lane half 0) and 2 c + 1 (half 1) ----
-                if (wave_on) {
-                    const int nch = min(kXkStageChunks, NM - (g0 / kXkStageGroups) * kXkStageChunks);
-                    const uint4* rbase = &lds.buf[((wr * kXkRT) * kXkStageRecs + half) * kXkRecStride + l31];
-                    const uint4* cbase = &lds.buf[((kXkRows / 32 + wc * kXkCG) * kXkStageRecs + half) * kXkRecStride + l31];
-#pragma unroll
-                    for (int c = 0; c < kXkStageChunks; ++c) {
-                        if (c < nch) {
-                            uint4 X[kXkRT], Y[kXkCG];
-#pragma unroll
-                            for (int rt = 0; rt < kXkRT; ++rt) X[rt] = rbase[(rt * kXkStageRecs + 2 * c) * kXkRecStride];
-#pragma unroll
-                            for (int cg = 0; cg < kXkCG; ++cg) Y[cg] = cbase[(cg * kXkStageRecs + 2 * c) * kXkRecStride];
-#pragma unroll
-                            for (int rt = 0; rt < kXkRT; ++rt)
-#pragma unroll
-                                for (int cg = 0; cg < kXkCG; ++cg) acc[rt][cg] = mfma_x32(Y[cg], X[rt], acc[rt][cg]);
-                        }
-                    }
-                }
-            }
+            xk_exponent_blocks<T, L, false>(lds, xb, yb, centre, D, NM, NG, nr32, ncg, 1.0f, 1.0f, wave_on, wr, wc, half, l31, tid, acc);
             if (!wave_on) return;
 
             // ---- epilogue: the best exponent of this wavefront's 2 x 2 blocks per row, columns in ascending order, strict compare

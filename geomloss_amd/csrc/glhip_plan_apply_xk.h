@@ -30,24 +30,25 @@
 // further passes, a remainder is a pass of its own.  A wavefront carries 2 row tiles x NCH accumulators of 16 registers next to its
 // 64 registers of exponents; four chunks would need 128 + 64 before any operand and 130 KiB for the meeting of the halves.
 // One workgroup per CU: __launch_bounds__(512, 2).
-//   registers / LDS / scratch (gfx950, tools/kernel_resources.py, profiles/plan_apply_nd.txt), float32 and bfloat16 clouds:
-//     NCH = 1, both layouts:  200 VGPRs, 95.1 KiB of LDS (97 408 B), 0 bytes of scratch
-//     NCH = 2, both layouts:  256 VGPRs, 111.5 KiB of LDS (114 176 B), 0 bytes of scratch
+//   registers / LDS / scratch (gfx950, tools/kernel_resources.py, profiles/xk_shared_stage.txt), float32 and bfloat16 clouds, plan and
+//   gradient:
+//     NCH = 1, both layouts:  199 VGPRs, 95.1 KiB of LDS (97 408 B), 0 bytes of scratch
+//     NCH = 2, both layouts:  252-256 VGPRs, 111.5 KiB of LDS (114 176 B), 0 bytes of scratch
 //     LDS: 78.75 KiB of xk_fwd_kernel + 16 KiB of feature pieces per chunk + 384 B per chunk of maxima and inverse scales
 //
 // Cost model: per 32 x 32 block NM >= 7 MFMAs of exponent (NM = ceil((6 + kPer D) / 16)) + 6 NCH MFMAs of product + ~50 VALU
 // instructions of exponentials and piece conversions shared by the chunks + 16 NCH v_fma_f32.  The staging of the exponent half
 // (the splitting of 384 points per stage) is what a pass shares with a forward reduction, and it dominates both.
 //
-// Kept in step by hand: the stage loop below (the split of the points into records and the six K chunks of MFMAs) restates the body of
-// xk_fwd_kernel, which may not change with this kernel; only xk_pack_half, xk_norms and the layout constants are shared code.  It
-// leaves out that kernel's sched_barrier between the two half groups of f16 x 2 (there for a 128-VGPR budget this kernel does not
-// have).  Follow-up: one __forceinline__ stage helper for both kernels, with tools/kernel_resources.py showing xk_fwd_kernel unchanged.
+// The exponent half is xk_exponent_blocks (glhip_softmin_xk.h), the stage loop xk_fwd_kernel runs, without that kernel's sched_barrier
+// between the two half groups of f16 x 2 (there for a 128-VGPR budget this kernel does not have).
 //
-// glhip_softmin_bwd_x of 17 <= D <= 4095 — g_i (x_i - sum_j P_ij y_j) is a plan application too — runs xk_grad_kernel
-// (glhip_softmin_grad_xk.h) under GLHIP_FLAG_XK_GRAD: a copy of this body with the centred column cloud as its features and the
-// gradient's epilogue; this kernel and its resources are untouched by it.  Out of scope here: block-sparse plans, p = 1, float64
-// clouds and autograd through the application.
+// glhip_softmin_bwd_x of 17 <= D <= 4095 — g_i (x_i - sum_j P_ij y_j) is a plan application too — runs this kernel under
+// GLHIP_FLAG_XK_GRAD, instantiated on XkGradParams (glhip_softmin_grad_xk.h): the centred column cloud as its features and the
+// gradient's epilogue, chosen with `if constexpr` at four sites.  The two must stay ONE __global__ template: the same body as a
+// __device__ __forceinline__ function behind two thin __global__ wrappers cost 30 VGPRs at NCH = 1 and spilled 112-180 bytes per lane
+// at NCH = 2 (profiles/xk_shared_stage.txt).  Out of scope here: block-sparse plans, p = 1, float64 clouds and autograd through the
+// application.
 #pragma once
 
 #include "glhip_plan_apply.h"
@@ -65,12 +66,13 @@ struct XkPlanLds {
     __attribute__((aligned(16))) float inv[32 * NCH];    // 2^-13 / scale of the current tile, per feature
 };
 
-template <typename T, int NCH, int L>
+// P = PlanParams<T>: the plan applied to prm.feat.  P = XkGradParams<T> (glhip_softmin_grad_xk.h): the gradient with respect to the row
+// points — the same body at four sites marked GRAD: the feature load, the output row, the unsplit epilogue and the mass output.
+template <typename T, int NCH, int L, typename P>
 __global__ void __launch_bounds__(kXkThreads, 2)
-xk_plan_kernel(PlanParams<T> prm, int N, int M, int D, SplitInfo sp) {
+xk_plan_kernel(P prm, int N, int M, int D, SplitInfo sp) {
+    constexpr bool GRAD = !std::is_same<P, PlanParams<T>>::value;
     constexpr bool H2 = (L == XL_F16X2);
-    constexpr int kItems = H2 ? 8 : 4;                        // items (coordinates) of a 24-slot group
-    constexpr int kLead = H2 ? 2 : 1;                         // items taken by the scalar item
     constexpr int VC = 32 * NCH;
     constexpr int kQRecs = NCH * 4 * 64;                      // feature records per column group
     constexpr int kFItems = (kXkCols / 4) * VC / kXkThreads;  // (column quad, feature) items per thread and tile: 2, 4
@@ -141,18 +143,23 @@ xk_plan_kernel(PlanParams<T> prm, int N, int M, int D, SplitInfo sp) {
         __syncthreads();                                      // the previous tile (and the row scalars) are settled
         if (tid < kXkCols) lds.xk.idx[kXkRows + tid] = col;
         // features: item (column quad cq, feature c of the pass) — c runs fastest, so the loads of a wavefront are contiguous runs of
-        // feat rows (plan_apply_kernel)
+        // feat rows (plan_apply_kernel).  GRAD: the centred coordinates v0 .. v0 + nv - 1 of the tile's columns, runs of y rows
         float fv[kFItems][4];
 #pragma unroll
         for (int k = 0; k < kFItems; ++k) {
             const int it = tid + k * kXkThreads;
             const int cq = it / VC, c = it - cq * VC;
             const int t = cq << 2;
+            float cen = 0.f;
+            if constexpr (GRAD) cen = (c < prm.nv) ? to_f32<T>(centre[prm.v0 + c]) : 0.f;
             uint32_t mx = 0u;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 float f = 0.f;
-                if (t + q < n && c < prm.nv) f = prm.feat[((long)b * M + j0 + t + q) * prm.V + prm.v0 + c];
+                if (t + q < n && c < prm.nv) {
+                    if constexpr (GRAD) f = to_f32<T>(yb[(long)(j0 + t + q) * D + prm.v0 + c]) - cen;
+                    else f = prm.feat[((long)b * M + j0 + t + q) * prm.V + prm.v0 + c];
+                }
                 fv[k][q] = f;
                 mx = max(mx, __float_as_uint(f) & 0x7FFFFFFFu);
             }
@@ -200,69 +207,7 @@ xk_plan_kernel(PlanParams<T> prm, int N, int M, int D, SplitInfo sp) {
 
         const bool wave_on = wave_rows && wc * kXkCG < ncg;
         f32x16 acc[kXkRT][kXkCG];
-#pragma unroll
-        for (int rt = 0; rt < kXkRT; ++rt)
-#pragma unroll
-            for (int cg = 0; cg < kXkCG; ++cg) acc[rt][cg] = zero16;
-
-        const int npts = nr32 + ncg * 32;
-        for (int g0 = 0; g0 < NG; g0 += kXkStageGroups) {
-            __syncthreads();                                  // the previous stage is consumed (first stage: the scalars are written)
-            // ---- split: work item = (point, group of the stage), as xk_fwd_kernel ----
-            for (int t = tid; t < npts * kXkStageGroups; t += kXkThreads) {
-                const int pt = t / kXkStageGroups, gi = t % kXkStageGroups;
-                const int g = g0 + gi;
-                if (g >= NG) continue;
-                const bool isrow = pt < nr32;
-                const int slot = isrow ? pt : kXkRows + (pt - nr32);
-                const int i = lds.xk.idx[slot];
-                const T* p = (isrow ? xb : yb) + (long)max(i, 0) * D;
-                const float scale = isrow ? xscale : yscale;
-                const int d0 = kItems * g - kLead;
-                const float sc = lds.xk.scal[slot];
-                uint32_t w[2][6];
-                auto half_group = [&](auto hsel) {            // items d0 + kItems / 2 * HALF ... of the point -> six dwords
-                    constexpr int HALF = decltype(hsel)::value;
-                    float val[kItems / 2];
-#pragma unroll
-                    for (int q = 0; q < kItems / 2; ++q) {
-                        const int d = d0 + HALF * (kItems / 2) + q;
-                        val[q] = (d >= 0 && d < D && i >= 0) ? (to_f32<T>(p[d]) - to_f32<T>(centre[d])) * scale : 0.f;
-                    }
-                    if (isrow) xk_pack_half<true, L, HALF>(g == 0, sc, val, w[HALF]);
-                    else xk_pack_half<false, L, HALF>(g == 0, sc, val, w[HALF]);
-                };
-                half_group(std::integral_constant<int, 0>{});
-                half_group(std::integral_constant<int, 1>{});
-                const uint4 rec[3] = {uint4{w[0][0], w[0][1], w[0][2], w[0][3]}, uint4{w[0][4], w[0][5], w[1][0], w[1][1]},
-                                      uint4{w[1][2], w[1][3], w[1][4], w[1][5]}};
-                uint4* dst = &lds.xk.buf[((slot >> 5) * kXkStageRecs + 3 * gi) * kXkRecStride + (slot & 31)];
-#pragma unroll
-                for (int r = 0; r < 3; ++r) dst[r * kXkRecStride] = rec[r];
-            }
-            __syncthreads();
-            // ---- multiply: K chunk c of the stage = records 2 c (lane half 0) and 2 c + 1 (half 1) ----
-            if (wave_on) {
-                const int nch = min(kXkStageChunks, NM - (g0 / kXkStageGroups) * kXkStageChunks);
-                const uint4* rbase = &lds.xk.buf[((wr * kXkRT) * kXkStageRecs + half) * kXkRecStride + l31];
-                const uint4* cbase = &lds.xk.buf[((kXkRows / 32 + wc * kXkCG) * kXkStageRecs + half) * kXkRecStride + l31];
-#pragma unroll
-                for (int c = 0; c < kXkStageChunks; ++c) {
-                    if (c < nch) {
-                        uint4 X[kXkRT], Y[kXkCG];
-#pragma unroll
-                        for (int rt = 0; rt < kXkRT; ++rt) X[rt] = rbase[(rt * kXkStageRecs + 2 * c) * kXkRecStride];
-#pragma unroll
-                        for (int cg = 0; cg < kXkCG; ++cg) Y[cg] = cbase[(cg * kXkStageRecs + 2 * c) * kXkRecStride];
-#pragma unroll
-                        for (int rt = 0; rt < kXkRT; ++rt)
-#pragma unroll
-                            for (int cg = 0; cg < kXkCG; ++cg)
-                                acc[rt][cg] = H2 ? mfma_h32(Y[cg], X[rt], acc[rt][cg]) : mfma_x32(Y[cg], X[rt], acc[rt][cg]);
-                    }
-                }
-            }
-        }
+        xk_exponent_blocks<T, L, false>(lds.xk, xb, yb, centre, D, NM, NG, nr32, ncg, xscale, yscale, wave_on, wr, wc, half, l31, tid, acc);
         if (!wave_on) continue;
 
         // ---- plan half: the weights of this wavefront's 2 x 2 blocks times the tile's features (column groups >= ncg were not packed) ----
@@ -375,7 +320,14 @@ xk_plan_kernel(PlanParams<T> prm, int N, int M, int D, SplitInfo sp) {
         const float rs1 = fast_exp2(m[rt] - mn), rs2 = fast_exp2(m2 - mn);
         const float w = __builtin_fmaf(mrg[VC * kXkRows + r_local], rs2, mass[rt] * rs1);
         const long idx = (long)b * N + i;
-        float* orow = prm.out + idx * prm.V + prm.v0;
+        float* orow;
+        float gi = 0.f;                                       // GRAD: the incoming gradient of the row
+        if constexpr (GRAD) {
+            orow = prm.gx + idx * D + prm.v0;
+            if (ns == 1) gi = prm.g[idx];
+        } else {
+            orow = prm.out + idx * prm.V + prm.v0;
+        }
         float* part = sp.workspace + split * sp.split_stride + idx * (prm.nv + 2);
 #pragma unroll
         for (int ch = 0; ch < NCH; ++ch) {
@@ -384,8 +336,14 @@ xk_plan_kernel(PlanParams<T> prm, int N, int M, int D, SplitInfo sp) {
                 const int c = 32 * ch + (r & 3) + 8 * (r >> 2) + 4 * half;
                 if (c < prm.nv) {
                     const float s = __builtin_fmaf(mrg[c * kXkRows + r_local], rs2, pacc[rt][ch][r] * rs1);
-                    if (ns == 1) orow[c] = (w > 0.f) ? s / w : 0.f;      // a division: exact where the quotient is
-                    else part[c] = s;
+                    if (ns > 1) {
+                        part[c] = s;
+                    } else if constexpr (GRAD) {      // g_i ((x_i - centre) - ybar_i); a row without mass gets 0
+                        const float xc = to_f32<T>(xb[(long)i * D + prm.v0 + c]) - to_f32<T>(centre[prm.v0 + c]);
+                        orow[c] = (w > 0.f) ? gi * (xc - s / w) : 0.f;
+                    } else {
+                        orow[c] = (w > 0.f) ? s / w : 0.f;      // a division: exact where the quotient is
+                    }
                 }
             }
         }
@@ -393,8 +351,8 @@ xk_plan_kernel(PlanParams<T> prm, int N, int M, int D, SplitInfo sp) {
             if (ns > 1) {
                 part[prm.nv] = w;
                 part[prm.nv + 1] = mn;
-            } else if (prm.mass && prm.v0 == 0) {
-                prm.mass[idx] = w * fast_exp2(mn);
+            } else if constexpr (!GRAD) {
+                if (prm.mass && prm.v0 == 0) prm.mass[idx] = w * fast_exp2(mn);
             }
         }
     }

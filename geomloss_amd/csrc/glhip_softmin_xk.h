@@ -15,6 +15,7 @@
 //   one point x one GROUP of 3 records = 24 slots = 4 coordinates (8 on f16 x 2): every coordinate is loaded and split once —
 //   barrier, 6 K chunks of MFMAs, barrier.  The rows are re-split for every column tile (the price of staging on the fly: 384
 //   points split per 32768 pairs and stage); a second resident workgroup per CU overlaps its MFMAs with this one's VALU work.
+//   (xk_exponent_blocks below: the one stage loop of this kernel, xk_plan_kernel and argmin_xk_kernel.)
 //   LDS: 12 point groups x 12 records x 33 (32 + 1 pad: the 3-record groups of a point land on different banks) x 16 B = 74.25 KiB
 //   + 4.5 KiB of indices / scalars = 78.75 KiB: two workgroups per CU (157.5 of 160 KiB), 4 wavefronts per SIMD (<= 128 VGPRs).
 //
@@ -145,13 +146,98 @@ __device__ __forceinline__ void xk_norms(const T* __restrict__ pts, const T* __r
     }
 }
 
+// The exponent blocks of one column tile: zeroes a wavefront's 2 x 2 accumulators and sweeps the K dimension in stages.  The ONE stage
+// loop of the D > 16 kernels (xk_fwd_kernel, xk_plan_kernel, argmin_xk_kernel); the caller has written lds.idx and lds.scal of the
+// nr32 row slots and of the ncg * 32 column slots of the tile (no barrier needed after: the first stage starts with one).
+//   split     all 512 threads; a work item is (point, 24-slot group of the stage), the groups of a point on neighbouring lanes.  The
+//             coordinates of the group — kItems of them, less the kLead items the scalar item takes in group 0 — are loaded, centred,
+//             scaled (xscale for rows, yscale for columns; argmin passes 1), split by xk_pack_half and written as three records.
+//             SCHED puts a sched_barrier between the two half groups of f16 x 2: eight coordinates in flight at once cost xk_fwd_kernel
+//             its 128-VGPR budget; the other kernels have no such budget and leave it out.
+//   multiply  wavefronts with wave_on; K chunk c of the stage = records 2 c (lane half 0) and 2 c + 1 (half 1): 2 + 2 ds_read_b128 for
+//             the 4 MFMAs of a chunk, mfma(Y, X, acc) — lane (half, i) ends up with row i for the columns 8 (r / 4) + 4 half + r % 4.
+// Keep this a __forceinline__ function called from a __global__ body.  Moving a whole kernel BODY into a device function behind thin
+// __global__ wrappers was tried for xk_plan_kernel: +30 VGPRs at NCH = 1 and 112-180 bytes of scratch per lane at NCH = 2.
+template <typename T, int L, bool SCHED>
+__device__ __forceinline__ void xk_exponent_blocks(XkLds& lds, const T* __restrict__ xb, const T* __restrict__ yb, const T* __restrict__ centre,
+                                                   int D, int NM, int NG, int nr32, int ncg, float xscale, float yscale, bool wave_on, int wr,
+                                                   int wc, int half, int l31, int tid, f32x16 (&acc)[kXkRT][kXkCG]) {
+    constexpr bool H2 = (L == XL_F16X2);
+    constexpr int kItems = H2 ? 8 : 4;                        // items (coordinates) of a 24-slot group
+    constexpr int kLead = H2 ? 2 : 1;                         // items taken by the scalar item
+#pragma unroll
+    for (int rt = 0; rt < kXkRT; ++rt)
+#pragma unroll
+        for (int cg = 0; cg < kXkCG; ++cg)
+#pragma unroll
+            for (int k = 0; k < 16; ++k) acc[rt][cg][k] = 0.f;
+
+    const int npts = nr32 + ncg * 32;
+    for (int g0 = 0; g0 < NG; g0 += kXkStageGroups) {
+        __syncthreads();                                      // the previous stage is consumed (first stage: the scalars are written)
+        // ---- split ----
+        for (int t = tid; t < npts * kXkStageGroups; t += kXkThreads) {
+            const int pt = t / kXkStageGroups, gi = t % kXkStageGroups;
+            const int g = g0 + gi;
+            if (g >= NG) continue;
+            const bool isrow = pt < nr32;
+            const int slot = isrow ? pt : kXkRows + (pt - nr32);
+            const int i = lds.idx[slot];
+            const T* p = (isrow ? xb : yb) + (long)max(i, 0) * D;
+            const float scale = isrow ? xscale : yscale;
+            const int d0 = kItems * g - kLead;
+            const float sc = lds.scal[slot];
+            uint32_t w[2][6];
+            auto half_group = [&](auto hsel) {                // items d0 + kItems / 2 * HALF ... of the point -> six dwords
+                constexpr int HALF = decltype(hsel)::value;
+                float val[kItems / 2];
+#pragma unroll
+                for (int q = 0; q < kItems / 2; ++q) {
+                    const int d = d0 + HALF * (kItems / 2) + q;
+                    val[q] = (d >= 0 && d < D && i >= 0) ? (to_f32<T>(p[d]) - to_f32<T>(centre[d])) * scale : 0.f;
+                }
+                if (isrow) xk_pack_half<true, L, HALF>(g == 0, sc, val, w[HALF]);
+                else xk_pack_half<false, L, HALF>(g == 0, sc, val, w[HALF]);
+            };
+            half_group(std::integral_constant<int, 0>{});
+            if (SCHED && H2) __builtin_amdgcn_sched_barrier(0);
+            half_group(std::integral_constant<int, 1>{});
+            const uint4 rec[3] = {uint4{w[0][0], w[0][1], w[0][2], w[0][3]}, uint4{w[0][4], w[0][5], w[1][0], w[1][1]},
+                                  uint4{w[1][2], w[1][3], w[1][4], w[1][5]}};
+            uint4* dst = &lds.buf[((slot >> 5) * kXkStageRecs + 3 * gi) * kXkRecStride + (slot & 31)];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) dst[r * kXkRecStride] = rec[r];
+        }
+        __syncthreads();
+        // ---- multiply ----
+        if (wave_on) {
+            const int nch = min(kXkStageChunks, NM - (g0 / kXkStageGroups) * kXkStageChunks);
+            const uint4* rbase = &lds.buf[((wr * kXkRT) * kXkStageRecs + half) * kXkRecStride + l31];
+            const uint4* cbase = &lds.buf[((kXkRows / 32 + wc * kXkCG) * kXkStageRecs + half) * kXkRecStride + l31];
+#pragma unroll
+            for (int c = 0; c < kXkStageChunks; ++c) {
+                if (c < nch) {
+                    uint4 X[kXkRT], Y[kXkCG];
+#pragma unroll
+                    for (int rt = 0; rt < kXkRT; ++rt) X[rt] = rbase[(rt * kXkStageRecs + 2 * c) * kXkRecStride];
+#pragma unroll
+                    for (int cg = 0; cg < kXkCG; ++cg) Y[cg] = cbase[(cg * kXkStageRecs + 2 * c) * kXkRecStride];
+#pragma unroll
+                    for (int rt = 0; rt < kXkRT; ++rt)
+#pragma unroll
+                        for (int cg = 0; cg < kXkCG; ++cg)
+                            acc[rt][cg] = H2 ? mfma_h32(Y[cg], X[rt], acc[rt][cg]) : mfma_x32(Y[cg], X[rt], acc[rt][cg]);
+                }
+            }
+        }
+    }
+}
+
 template <int MODE, typename T, bool SPARSE, int L>
 __global__ void __launch_bounds__(kXkThreads, 4)
 xk_fwd_kernel(SoftminParams<T> prm, Ranges rg, int N, int M, int D, SplitInfo sp) {
     constexpr bool H2 = (L == XL_F16X2);
     constexpr float kFloor = H2 ? kH2Floor : kMinusHuge;      // the running maximum of a row that has seen no mass yet
-    constexpr int kItems = H2 ? 8 : 4;                        // items (coordinates) of a 24-slot group
-    constexpr int kLead = H2 ? 2 : 1;                         // items taken by the scalar item
     __shared__ XkLds lds;
 
     int bx, b, split;
@@ -218,72 +304,7 @@ xk_fwd_kernel(SoftminParams<T> prm, Ranges rg, int N, int M, int D, SplitInfo sp
 
             const bool wave_on = wave_rows && wc * kXkCG < ncg;
             f32x16 acc[kXkRT][kXkCG];
-#pragma unroll
-            for (int rt = 0; rt < kXkRT; ++rt)
-#pragma unroll
-                for (int cg = 0; cg < kXkCG; ++cg)
-#pragma unroll
-                    for (int k = 0; k < 16; ++k) acc[rt][cg][k] = 0.f;
-
-            const int npts = nr32 + ncg * 32;
-            for (int g0 = 0; g0 < NG; g0 += kXkStageGroups) {
-                __syncthreads();                              // the previous stage is consumed (first stage: the scalars are written)
-                // ---- split: work item = (point, group of the stage); the groups of a point on neighbouring lanes ----
-                for (int t = tid; t < npts * kXkStageGroups; t += kXkThreads) {
-                    const int pt = t / kXkStageGroups, gi = t % kXkStageGroups;
-                    const int g = g0 + gi;
-                    if (g >= NG) continue;
-                    const bool isrow = pt < nr32;
-                    const int slot = isrow ? pt : kXkRows + (pt - nr32);
-                    const int i = lds.idx[slot];
-                    const T* p = (isrow ? xb : yb) + (long)max(i, 0) * D;
-                    const float scale = isrow ? xscale : yscale;
-                    const int d0 = kItems * g - kLead;
-                    const float sc = lds.scal[slot];
-                    uint32_t w[2][6];
-                    auto half_group = [&](auto hsel) {          // items d0 + kItems / 2 * HALF ... of the point -> six dwords
-                        constexpr int HALF = decltype(hsel)::value;
-                        float val[kItems / 2];
-#pragma unroll
-                        for (int q = 0; q < kItems / 2; ++q) {
-                            const int d = d0 + HALF * (kItems / 2) + q;
-                            val[q] = (d >= 0 && d < D && i >= 0) ? (to_f32<T>(p[d]) - to_f32<T>(centre[d])) * scale : 0.f;
-                        }
-                        if (isrow) xk_pack_half<true, L, HALF>(g == 0, sc, val, w[HALF]);
-                        else xk_pack_half<false, L, HALF>(g == 0, sc, val, w[HALF]);
-                    };
-                    half_group(std::integral_constant<int, 0>{});
-                    if (H2) __builtin_amdgcn_sched_barrier(0);      // eight coordinates in flight at once cost the f16 x 2 kernels their 128-VGPR budget
-                    half_group(std::integral_constant<int, 1>{});
-                    const uint4 rec[3] = {uint4{w[0][0], w[0][1], w[0][2], w[0][3]}, uint4{w[0][4], w[0][5], w[1][0], w[1][1]},
-                                          uint4{w[1][2], w[1][3], w[1][4], w[1][5]}};
-                    uint4* dst = &lds.buf[((slot >> 5) * kXkStageRecs + 3 * gi) * kXkRecStride + (slot & 31)];
-#pragma unroll
-                    for (int r = 0; r < 3; ++r) dst[r * kXkRecStride] = rec[r];
-                }
-                __syncthreads();
-                // ---- multiply: K chunk c of the stage = records 2 c (lane half 0) and 2 c + 1 (half 1) ----
-                if (wave_on) {
-                    const int nch = min(kXkStageChunks, NM - (g0 / kXkStageGroups) * kXkStageChunks);
-                    const uint4* rbase = &lds.buf[((wr * kXkRT) * kXkStageRecs + half) * kXkRecStride + l31];
-                    const uint4* cbase = &lds.buf[((kXkRows / 32 + wc * kXkCG) * kXkStageRecs + half) * kXkRecStride + l31];
-#pragma unroll
-                    for (int c = 0; c < kXkStageChunks; ++c) {
-                        if (c < nch) {
-                            uint4 X[kXkRT], Y[kXkCG];
-#pragma unroll
-                            for (int rt = 0; rt < kXkRT; ++rt) X[rt] = rbase[(rt * kXkStageRecs + 2 * c) * kXkRecStride];
-#pragma unroll
-                            for (int cg = 0; cg < kXkCG; ++cg) Y[cg] = cbase[(cg * kXkStageRecs + 2 * c) * kXkRecStride];
-#pragma unroll
-                            for (int rt = 0; rt < kXkRT; ++rt)
-#pragma unroll
-                                for (int cg = 0; cg < kXkCG; ++cg)
-                                    acc[rt][cg] = H2 ? mfma_h32(Y[cg], X[rt], acc[rt][cg]) : mfma_x32(Y[cg], X[rt], acc[rt][cg]);
-                        }
-                    }
-                }
-            }
+            xk_exponent_blocks<T, L, true>(lds, xb, yb, centre, D, NM, NG, nr32, ncg, xscale, yscale, wave_on, wr, wc, half, l31, tid, acc);
             if (!wave_on) return;
 
             // ---- epilogue: the exponents of this wavefront's 2 x 2 blocks join the row sums (column groups >= ncg were not packed) ----

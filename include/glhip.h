@@ -89,7 +89,7 @@ extern "C" {
                                   without that layout (p = 1, laplacian, energy, the gradients of D > 16 other than GLHIP_FLAG_XK_GRAD, D > 4095, float64). */
 
 #define GLHIP_FLAG_XK_GRAD 1024 /* glhip_softmin_bwd_x only (version 126): the gradient of p == 2, 17 <= D <= 4095, dense launches (n_ranges == 0),
-                                  B <= 65535, without GLHIP_FLAG_NO_MFMA / _DIRECT runs xk_grad_kernel (csrc/glhip_softmin_grad_xk.h): the K-chunked
+                                  B <= 65535, without GLHIP_FLAG_NO_MFMA / _DIRECT runs xk_plan_kernel on XkGradParams (csrc/glhip_softmin_grad_xk.h): the K-chunked
                                   plan application of glhip_plan_apply_nd with the centred column cloud as its features, ceil(D / 64) passes.
                                   glhip_softmin_bwd_x_uses_plan is the predicate.  Ignored everywhere else — every other entry point, p = 1,
                                   D <= 16, D > 4095, block-sparse ranges, the float64 symbols: those launches are the ones version 125 makes,
@@ -354,14 +354,14 @@ int glhip_lse_lines_bwd(const float* h, const float* lse, const float* grad_out,
  * per pass over the columns, ceil(D / 64) passes.  The same holds for glhip_kernel_conv_bwd_x.  The weighted sums sum_j w_ij q_j as
  * a second MFMA product over all 32 MFMA rows live in glhip_plan_apply below (glhip_plan_apply.h, version 124: any number of feature
  * columns, D <= 16) and, for 17 <= D <= 4095, in glhip_plan_apply_nd (glhip_plan_apply_xk.h, version 125).
- * GLHIP_FLAG_XK_GRAD (version 126) routes the p = 2 gradient of 17 <= D <= 4095 through that product: xk_grad_kernel
- * (glhip_softmin_grad_xk.h) takes the column cloud itself, centred on the first row of each 256-row block, as its features and writes
+ * GLHIP_FLAG_XK_GRAD (version 126) routes the p = 2 gradient of 17 <= D <= 4095 through that product: xk_plan_kernel on
+ * XkGradParams (glhip_plan_apply_xk.h, glhip_softmin_grad_xk.h) takes the column cloud itself, centred on the first row of each 256-row block, as its features and writes
  * g_i ((x_i - centre) - sum_j P_ij (y_j - centre)) — 64 coordinates per pass, ceil(D / 64) passes, float32 and bfloat16 clouds, both
  * exponent layouts; a row without mass gets 0; a one-hot plan row gives g_i (x_i - y_j) with an exact difference.  The flag is opt-in
  * at this level: the default stays the one-thread-per-row kernel, whose explicit differences meet 5e-6 at eps = 0.3 where the
  * exponents of a long MFMA chain are bounded by 4 x the error of plain float32 arithmetic instead (DESIGN section 4 has the measured
  * figures of both routes).
- *   glhip_softmin_bwd_x_uses_plan: host arithmetic only, the very predicate the launch evaluates — 1: xk_grad_kernel; 0: the launch
+ *   glhip_softmin_bwd_x_uses_plan: host arithmetic only, the very predicate the launch evaluates — 1: that kernel; 0: the launch
  *   of version 125; GLHIP_EINVAL: negative sizes, D < 1, a bad p or dtype.
  *   glhip_softmin_bwd_x_workspace_bytes: the split partials of the widest pass of the new route (sums of <= 64 centred coordinates,
  *   mass, row maximum per row and split), never more than 1 GiB, 0 where the predicate is 0 (those launches size their workspace
