@@ -2,6 +2,11 @@
 #include "glhip_autosort.h"
 #include "glhip_launch.h"
 
+namespace glhip {      // glhip_api_convgrad_xk.hip: the GLHIP_FLAG_XK_GRAD route (xk_plan_kernel on XkGaussGradParams, glhip_gauss_grad_xk.h)
+int gauss_grad_xk_launch(const void* x, const void* y, const float* v, const float* g, float* out, float* gx, int B, int N, int M, int D,
+                         float blur, int in_dtype, void* workspace, size_t workspace_bytes, int flags, hipStream_t st);
+}
+
 extern "C" {
 
 int glhip_kernel_conv_bwd_x(int kind, const void* x, const void* y, const float* v, const float* g, float* grad_x,
@@ -16,6 +21,10 @@ int glhip_kernel_conv_bwd_x(int kind, const void* x, const void* y, const float*
     if (kind != GLHIP_ENERGY && !(blur > 0.f)) return fail(GLHIP_EINVAL, "glhip_kernel_conv_bwd_x: blur must be > 0");
     const Ranges rg{ranges_i, slices_i, redranges_j};
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if (glhip_kernel_conv_grad_uses_xk(kind, B, N, M, D, in_dtype, flags, n_ranges) == 1) {      // GLHIP_FLAG_XK_GRAD: gaussian, 17 <= D <= 4095, dense
+        rc = gauss_grad_xk_launch(x, y, v, g, nullptr, grad_x, B, N, M, D, blur, in_dtype, workspace, workspace_bytes, flags, st);
+        return rc ? rc : check_launch("glhip_kernel_conv_bwd_x");
+    }
     const Scratch sc = make_scratch(workspace, workspace_bytes, flags, n_ranges, N);
     rc = (in_dtype == GLHIP_F32)
              ? conv_typed<true, float>(kind, x, y, v, nullptr, g, grad_x, B, N, M, D, blur, rg, n_ranges, sc, flags, st)
@@ -31,12 +40,19 @@ int glhip_kernel_conv_fwd_grad(int kind, const void* x, const void* y, const flo
     if (rc) return rc;
     if (kind < GLHIP_GAUSSIAN || kind > GLHIP_ENERGY)
         return fail(GLHIP_EINVAL, "glhip_kernel_conv_fwd_grad: unknown kernel id %d", kind);
-    if (D > 3 && !(kind == GLHIP_GAUSSIAN && D <= kXdMaxD && !(flags & GLHIP_FLAG_NO_MFMA)))
-        return fail(GLHIP_EUNSUPPORTED, "glhip_kernel_conv_fwd_grad: D <= 3 (gaussian on the matrix cores: D <= 16) only (got kind %d, "
-                                        "D %d, flags %d): call glhip_kernel_conv_fwd + glhip_kernel_conv_bwd_x", kind, D, flags);
+    const bool xk = glhip_kernel_conv_grad_uses_xk(kind, B, N, M, D, in_dtype, flags, n_ranges) == 1;      // GLHIP_FLAG_XK_GRAD
+    if (D > 3 && !xk && !(kind == GLHIP_GAUSSIAN && D <= kXdMaxD && !(flags & GLHIP_FLAG_NO_MFMA)))
+        return fail(GLHIP_EUNSUPPORTED, "glhip_kernel_conv_fwd_grad: D <= 3 (gaussian on the matrix cores: D <= 16; 17 <= D <= 4095 "
+                                        "under GLHIP_FLAG_XK_GRAD) only (got kind %d, D %d, flags %d): call glhip_kernel_conv_fwd + "
+                                        "glhip_kernel_conv_bwd_x", kind, D, flags);
     if (B == 0 || N == 0) return GLHIP_OK;
     if (!out || !grad_unit) return fail(GLHIP_EINVAL, "glhip_kernel_conv_fwd_grad: NULL out / grad_unit");
     if (kind != GLHIP_ENERGY && !(blur > 0.f)) return fail(GLHIP_EINVAL, "glhip_kernel_conv_fwd_grad: blur must be > 0");
+    if (xk) {      // gaussian, 17 <= D <= 4095, dense: the passes of glhip_gauss_grad_xk.h
+        rc = gauss_grad_xk_launch(x, y, v, nullptr, out, grad_unit, B, N, M, D, blur, in_dtype, workspace, workspace_bytes, flags,
+                                  static_cast<hipStream_t>(stream));
+        return rc ? rc : check_launch("glhip_kernel_conv_fwd_grad");
+    }
     const Ranges rg{ranges_i, slices_i, redranges_j};
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (kind != GLHIP_GAUSSIAN && autosort_applies(B, N, M, D, n_ranges, flags)) {      // as glhip_kernel_conv_fwd (glhip_autosort.h)

@@ -34,6 +34,7 @@
 //   gradient:
 //     NCH = 1, both layouts:  199 VGPRs, 95.1 KiB of LDS (97 408 B), 0 bytes of scratch
 //     NCH = 2, both layouts:  252-256 VGPRs, 111.5 KiB of LDS (114 176 B), 0 bytes of scratch
+//     gaussian gradient (profiles/gauss_grad_xk.txt):  207 / 253-256 VGPRs, the same LDS, 0 bytes of scratch
 //     LDS: 78.75 KiB of xk_fwd_kernel + 16 KiB of feature pieces per chunk + 384 B per chunk of maxima and inverse scales
 //
 // Cost model: per 32 x 32 block NM >= 7 MFMAs of exponent (NM = ceil((6 + kPer D) / 16)) + 6 NCH MFMAs of product + ~50 VALU
@@ -49,6 +50,10 @@
 // __device__ __forceinline__ function behind two thin __global__ wrappers cost 30 VGPRs at NCH = 1 and spilled 112-180 bytes per lane
 // at NCH = 2 (profiles/xk_shared_stage.txt).  Out of scope here: block-sparse plans, p = 1, float64 clouds and autograd through the
 // application.
+//
+// glhip_kernel_conv_bwd_x / glhip_kernel_conv_fwd_grad of the gaussian kernel, 17 <= D <= 4095, are the third instantiation, on
+// XkGaussGradParams (glhip_gauss_grad_xk.h, sites marked GAUSS): the exponents of the gaussian product, features v_j (y_j - centre),
+// the signed mass sum_j w_ij v_j (lds.xk.v carries v_j), and an epilogue that multiplies the sums by 2^m instead of normalising them.
 #pragma once
 
 #include "glhip_plan_apply.h"
@@ -57,6 +62,14 @@
 namespace glhip {
 
 constexpr int kXkPlanMaxChunks = 2;                      // feature chunks per pass
+
+template <typename T> struct XkGaussGradParams;          // glhip_gauss_grad_xk.h
+
+// GAUSS: one entry of the gradient from sums relative to 2^m (e2m = 2^m, gs = g_i / blur^2).  A row that no column reached (e2m == 0)
+// writes 0.  The signed mass w can be 0 where s is not: it is never a test for an empty row.
+__device__ __forceinline__ float xk_gauss_grad_entry(float s, float w, float xc, float e2m, float gs) {
+    return (e2m > 0.f) ? gs * (e2m * __builtin_fmaf(-xc, w, s)) : 0.f;
+}
 
 template <int NCH>
 struct XkPlanLds {
@@ -68,10 +81,13 @@ struct XkPlanLds {
 
 // P = PlanParams<T>: the plan applied to prm.feat.  P = XkGradParams<T> (glhip_softmin_grad_xk.h): the gradient with respect to the row
 // points — the same body at four sites marked GRAD: the feature load, the output row, the unsplit epilogue and the mass output.
+// P = XkGaussGradParams<T> (glhip_gauss_grad_xk.h): the gradient of the gaussian product — GRAD's feature load and output row, and its own
+// arms marked GAUSS: C_i and H_j without dual or forward value, v_j in lds.xk.v, the signed mass and the unnormalised epilogue.
 template <typename T, int NCH, int L, typename P>
 __global__ void __launch_bounds__(kXkThreads, 2)
 xk_plan_kernel(P prm, int N, int M, int D, SplitInfo sp) {
     constexpr bool GRAD = !std::is_same<P, PlanParams<T>>::value;
+    constexpr bool GAUSS = std::is_same<P, XkGaussGradParams<T>>::value;
     constexpr bool H2 = (L == XL_F16X2);
     constexpr int VC = 32 * NCH;
     constexpr int kQRecs = NCH * 4 * 64;                      // feature records per column group
@@ -128,9 +144,13 @@ xk_plan_kernel(P prm, int N, int M, int D, SplitInfo sp) {
         // C_i = r_i - LSE2_i, r_i = -s/2 |xt_i|^2, LSE2_i = fwd_i / out_scale.  fwd_i = +inf is a row without mass; a huge fwd_i (the
         // forward counted its padded columns into such a row) must stay finite here: it meets the -inf of the column mask
         const int i = min(wave_row0 + rt * 32 + l31, row_end - 1);
-        const float fw = prm.fwd[(long)b * N + i];
-        const float c = -0.5f * prm.s2 * lds.xk.n2row[i - row0] - fw / prm.out_scale;
-        cst[rt] = (fw == __builtin_inff()) ? kNegBig : __builtin_fminf(c, -kNegBig);
+        if constexpr (GAUSS) {                                // C_i = r_i: the exponents of the gaussian product
+            cst[rt] = -0.5f * prm.s2 * lds.xk.n2row[i - row0];
+        } else {
+            const float fw = prm.fwd[(long)b * N + i];
+            const float c = -0.5f * prm.s2 * lds.xk.n2row[i - row0] - fw / prm.out_scale;
+            cst[rt] = (fw == __builtin_inff()) ? kNegBig : __builtin_fminf(c, -kNegBig);
+        }
     }
 
     int js, je;
@@ -159,6 +179,7 @@ xk_plan_kernel(P prm, int N, int M, int D, SplitInfo sp) {
                 if (t + q < n && c < prm.nv) {
                     if constexpr (GRAD) f = to_f32<T>(yb[(long)(j0 + t + q) * D + prm.v0 + c]) - cen;
                     else f = prm.feat[((long)b * M + j0 + t + q) * prm.V + prm.v0 + c];
+                    if constexpr (GAUSS) f *= prm.v[(long)b * M + j0 + t + q];      // v_j (y_j - centre)
                 }
                 fv[k][q] = f;
                 mx = max(mx, __float_as_uint(f) & 0x7FFFFFFFu);
@@ -195,7 +216,13 @@ xk_plan_kernel(P prm, int N, int M, int D, SplitInfo sp) {
         __syncthreads();
         if (tid < ncg * 32) {                                 // |yt|^2 -> H_j, and the column's mask
             float H = kNegBig, mask = -__builtin_inff();
-            if (col >= 0) {
+            if constexpr (GAUSS) {                            // lds.xk.v: v_j, 0 for a padded column (its features are 0 too)
+                mask = 0.f;
+                if (col >= 0) {
+                    H = -0.5f * prm.s2 * lds.xk.scal[kXkRows + tid];
+                    mask = prm.v[(long)b * M + col];
+                }
+            } else if (col >= 0) {
                 const float hj = prm.h[(long)b * M + col];
                 H = __builtin_fmaf(-0.5f * prm.s2, lds.xk.scal[kXkRows + tid], hj * kLog2e);
                 if (hj != -__builtin_inff()) mask = 0.f;
@@ -222,11 +249,16 @@ xk_plan_kernel(P prm, int N, int M, int D, SplitInfo sp) {
                 const float* mk = &lds.xk.v[G * 32 + half * 4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const float4 k4 = *reinterpret_cast<const float4*>(mk + q * 8);
-                    u[4 * q + 0] = (acc[rt][cg][4 * q + 0] + cst[rt]) + k4.x;
-                    u[4 * q + 1] = (acc[rt][cg][4 * q + 1] + cst[rt]) + k4.y;
-                    u[4 * q + 2] = (acc[rt][cg][4 * q + 2] + cst[rt]) + k4.z;
-                    u[4 * q + 3] = (acc[rt][cg][4 * q + 3] + cst[rt]) + k4.w;
+                    if constexpr (GAUSS) {                    // no mask: the running maximum is taken over the exponents, never over v
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) u[4 * q + k] = acc[rt][cg][4 * q + k] + cst[rt];
+                    } else {
+                        const float4 k4 = *reinterpret_cast<const float4*>(mk + q * 8);
+                        u[4 * q + 0] = (acc[rt][cg][4 * q + 0] + cst[rt]) + k4.x;
+                        u[4 * q + 1] = (acc[rt][cg][4 * q + 1] + cst[rt]) + k4.y;
+                        u[4 * q + 2] = (acc[rt][cg][4 * q + 2] + cst[rt]) + k4.z;
+                        u[4 * q + 3] = (acc[rt][cg][4 * q + 3] + cst[rt]) + k4.w;
+                    }
                 }
                 // weights relative to the running maximum of the row: w' = 2^13 2^(u - m) <= 8192 whatever fwd is worth, and the largest
                 // weight of a row is 2^13 EXACTLY.  A new maximum rescales the running sums (factor exactly 1 for the rows that keep theirs)
@@ -248,8 +280,14 @@ xk_plan_kernel(P prm, int N, int M, int D, SplitInfo sp) {
 #pragma unroll
                 for (int k = 0; k < 16; k += 2) {      // pairs: one v_cvt_pk_f16_f32 per two high pieces, both read back from it
                     const f32x2_t w = {fast_exp2(u[k] - m[rt]) * (float)(1 << kWqShift), fast_exp2(u[k + 1] - m[rt]) * (float)(1 << kWqShift)};
-                    mass4[rt][k & 3] += w[0];
-                    mass4[rt][(k & 3) + 1] += w[1];
+                    if constexpr (GAUSS) {                    // the signed mass: the unsplit fp32 weights times v_j
+                        const float2 v2 = *reinterpret_cast<const float2*>(mk + (k >> 2) * 8 + (k & 3));
+                        mass4[rt][k & 3] = __builtin_fmaf(w[0], v2.x, mass4[rt][k & 3]);
+                        mass4[rt][(k & 3) + 1] = __builtin_fmaf(w[1], v2.y, mass4[rt][(k & 3) + 1]);
+                    } else {
+                        mass4[rt][k & 3] += w[0];
+                        mass4[rt][(k & 3) + 1] += w[1];
+                    }
                     const f16x2_t hh = __builtin_convertvector(w, f16x2_t);
                     const f32x2_t back = __builtin_convertvector(hh, f32x2_t);
                     const f16x2_t ll = __builtin_convertvector(w - back, f16x2_t);
@@ -322,7 +360,14 @@ xk_plan_kernel(P prm, int N, int M, int D, SplitInfo sp) {
         const long idx = (long)b * N + i;
         float* orow;
         float gi = 0.f;                                       // GRAD: the incoming gradient of the row
-        if constexpr (GRAD) {
+        float e2m = 0.f;                                      // GAUSS: 2^m, and gi = g_i / blur^2
+        if constexpr (GAUSS) {
+            orow = prm.gx + idx * D + prm.v0;
+            if (ns == 1) {
+                gi = prm.g ? prm.g[idx] * prm.gscale : prm.gscale;
+                e2m = fast_exp2(mn);
+            }
+        } else if constexpr (GRAD) {
             orow = prm.gx + idx * D + prm.v0;
             if (ns == 1) gi = prm.g[idx];
         } else {
@@ -338,6 +383,9 @@ xk_plan_kernel(P prm, int N, int M, int D, SplitInfo sp) {
                     const float s = __builtin_fmaf(mrg[c * kXkRows + r_local], rs2, pacc[rt][ch][r] * rs1);
                     if (ns > 1) {
                         part[c] = s;
+                    } else if constexpr (GAUSS) {     // nothing is normalised: g_i / blur^2 2^m (S - xc W); a row no column reached gets 0
+                        const float xc = to_f32<T>(xb[(long)i * D + prm.v0 + c]) - to_f32<T>(centre[prm.v0 + c]);
+                        orow[c] = xk_gauss_grad_entry(s, w, xc, e2m, gi);
                     } else if constexpr (GRAD) {      // g_i ((x_i - centre) - ybar_i); a row without mass gets 0
                         const float xc = to_f32<T>(xb[(long)i * D + prm.v0 + c]) - to_f32<T>(centre[prm.v0 + c]);
                         orow[c] = (w > 0.f) ? gi * (xc - s / w) : 0.f;
@@ -351,6 +399,8 @@ xk_plan_kernel(P prm, int N, int M, int D, SplitInfo sp) {
             if (ns > 1) {
                 part[prm.nv] = w;
                 part[prm.nv + 1] = mn;
+            } else if constexpr (GAUSS) {
+                if (prm.out && prm.v0 == 0) prm.out[idx] = (e2m > 0.f) ? w * e2m : 0.f;
             } else if constexpr (!GRAD) {
                 if (prm.mass && prm.v0 == 0) prm.mass[idx] = w * fast_exp2(mn);
             }

@@ -24,7 +24,8 @@ F32, BF16 = 0, 1
 FLAG_DIRECT, FLAG_NO_MFMA, FLAG_NO_SPLIT, FLAG_F32_MFMA, FLAG_XDL16, FLAG_PREPACK, FLAG_MFMA_DIST, FLAG_SMALL_ROW_BLOCKS = 1, 2, 4, 8, 16, 32, 64, 128
 FLAG_F16X2 = 256                # exponents from two f16 pieces per coordinate; the caller vouches for the range (glhip.h)
 FLAG_NO_SORT = 512              # big dense distance reductions: do not voxel-sort the clouds inside the library (glhip.h)
-FLAG_XK_GRAD = 1024             # glhip_softmin_bwd_x: the p = 2 gradient of 17 <= D <= 4095 on the matrix cores (glhip_softmin_grad_xk.h)
+FLAG_XK_GRAD = 1024             # glhip_softmin_bwd_x: the p = 2 gradient of 17 <= D <= 4095 on the matrix cores (glhip_softmin_grad_xk.h);
+                                # glhip_kernel_conv_bwd_x / _fwd_grad: the gaussian gradient of those dimensions (glhip_gauss_grad_xk.h)
 FLAG_GRAD_FAMILY = FLAG_XDL16   # kernel products rounded like the product-and-gradient kernel of the same kind (glhip.h)
 XD_MAX_DIM = 16                 # the fused four-softmin iteration / annealing / extrapolation, the one-pass value + gradient and the matrix-core
                                 # gradients stop at this dimension (glhip_softmin_xd.h, glhip_wsum_t32.h)
@@ -60,6 +61,8 @@ SIGNATURES = {
                                      _c_int] + _RANGES + _TAIL),
     "glhip_softmin_bwd_x_uses_plan": (_c_int, [_c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int, _c_int]),
     "glhip_softmin_bwd_x_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "glhip_kernel_conv_grad_uses_xk": (_c_int, [_c_int, _c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int]),
+    "glhip_kernel_conv_grad_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "glhip_plan_apply_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "glhip_plan_apply": (_c_int, [_vp] * 7 + [_c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int, _c_int] + _RANGES + _TAIL),
     "glhip_plan_apply_nd_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
@@ -455,7 +458,34 @@ def kernel_conv_fwd_raw(kind, x, y, v, blur, ranges=None, flags=0):
     return out
 
 
-def kernel_conv_bwd_x_raw(kind, x, y, v, g, blur, ranges=None, flags=0):
+def kernel_conv_grad_uses_xk(kind, B, N, M, D, dtype=F32, flags=0, n_ranges=0):
+    """Whether ``glhip_kernel_conv_bwd_x`` / ``glhip_kernel_conv_fwd_grad`` run the matrix-core gaussian gradient of 17 <= D <= 4095 for
+    this launch (``FLAG_XK_GRAD``): the library's own predicate (host arithmetic, no GPU); ``kind``: a name or a code.  1 / 0, or
+    ``ValueError`` for arguments the entry points reject."""
+    lib = load_library()
+    r = int(lib.glhip_kernel_conv_grad_uses_xk(int(KERNEL_KINDS.get(kind, kind)), int(B), int(N), int(M), int(D), int(dtype), int(flags),
+                                               int(n_ranges)))
+    if r < 0:
+        raise ValueError(f"glhip_kernel_conv_grad_uses_xk: bad argument (kind {kind}, B {B}, N {N}, M {M}, D {D}, dtype {dtype}, "
+                         f"n_ranges {n_ranges})")
+    return r
+
+
+def _conv_grad_workspace(lib, kind, x, B, N, M, D, ranges, flags, workspace):
+    """The workspace of a kernel gradient launch: the matrix-core gaussian gradient of 17 <= D <= 4095 sizes its own split partials
+    (``glhip_kernel_conv_grad_workspace_bytes``), every other launch takes ``glhip_workspace_bytes``."""
+    n_ranges = 0 if ranges is None else int(ranges.ranges_i.shape[0])
+    if lib.glhip_kernel_conv_grad_uses_xk(int(kind), B, N, M, D, _dtype_code(x), int(flags), n_ranges) == 1:
+        nbytes = int(lib.glhip_kernel_conv_grad_workspace_bytes(B, N, M, D, int(flags))) if workspace else 0
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+        return ws, (None if ws is None else ws.data_ptr(), nbytes)
+    if workspace:
+        return _workspace(lib, x, B, N, M, D, ranges)
+    return None, (None, 0)
+
+
+def kernel_conv_bwd_x_raw(kind, x, y, v, g, blur, ranges=None, flags=0, workspace=True):
+    """``workspace=False``: launch without one (no column splits) — tests only."""
     lib = load_library()
     B, N, D = x.shape
     M = y.shape[1]
@@ -468,7 +498,7 @@ def kernel_conv_bwd_x_raw(kind, x, y, v, g, blur, ranges=None, flags=0):
         return gx
     gx = torch.empty((B, N, D), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        ws, ws_args = _workspace(lib, x, B, N, M, D, ranges)
+        ws, ws_args = _conv_grad_workspace(lib, kind, x, B, N, M, D, ranges, flags, workspace)
         rc = lib.glhip_kernel_conv_bwd_x(int(kind), x.data_ptr(), y.data_ptr(), v.data_ptr(), g.data_ptr(),
                                          gx.data_ptr(), B, N, M, D, float(blur), _dtype_code(x),
                                          *_range_args(ranges, B), *ws_args, int(flags), _stream(x))
@@ -476,15 +506,17 @@ def kernel_conv_bwd_x_raw(kind, x, y, v, g, blur, ranges=None, flags=0):
     return gx
 
 
-def kernel_conv_fwd_grad_raw(kind, x, y, v, blur, ranges=None, flags=0):
-    """out = K v and d out_i / d x_i in one pass (``glhip_kernel_conv_fwd_grad``; gaussian, D <= 3) -> (B,N), (B,N,D)."""
+def kernel_conv_fwd_grad_raw(kind, x, y, v, blur, ranges=None, flags=0, workspace=True):
+    """out = K v and d out_i / d x_i in one pass (``glhip_kernel_conv_fwd_grad``: every kernel at D <= 3, the gaussian kernel at
+    D <= 16, and at 17 <= D <= 4095 under ``FLAG_XK_GRAD``) -> (B,N), (B,N,D).  ``workspace=False``: launch without one (no column
+    splits) — tests only."""
     lib = load_library()
     B, N, D = x.shape
     M = y.shape[1]
     out = torch.empty((B, N), dtype=torch.float32, device=x.device)
     gu = torch.empty((B, N, D), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        ws, ws_args = _workspace(lib, x, B, N, M, D, ranges)
+        ws, ws_args = _conv_grad_workspace(lib, kind, x, B, N, M, D, ranges, flags, workspace)
         rc = lib.glhip_kernel_conv_fwd_grad(int(kind), x.data_ptr(), y.data_ptr(), v.data_ptr(), out.data_ptr(), gu.data_ptr(),
                                             B, N, M, D, float(blur), _dtype_code(x), *_range_args(ranges, B), *ws_args,
                                             int(flags), _stream(x))
@@ -1353,9 +1385,13 @@ class _KernelConv(torch.autograd.Function):
             return xb, yb, vb, batched, kernel_conv_fwd_raw(kind, xb, yb, vb, blur, ranges, flags), None
         # When x requires gradients, the product and its row gradient come out of ONE reduction: the gradient kernel
         # carries one more accumulator, the product itself.  The backward pass is then elementwise.
-        # (D <= 3: every kernel; 4 <= D <= 16: the gaussian kernel on the matrix cores)
+        # (D <= 3: every kernel; 4 <= D <= 16: the gaussian kernel on the matrix cores; 17 <= D <= 4095: the gaussian kernel where
+        # the caller asked for the matrix-core gradient, FLAG_XK_GRAD)
         fused = (_fuse_kernel_grad and want_unit
-                 and (xb.shape[-1] <= 3 or (kind == GAUSSIAN and xb.shape[-1] <= XD_MAX_DIM and not (flags & FLAG_NO_MFMA))))
+                 and (xb.shape[-1] <= 3 or (kind == GAUSSIAN and xb.shape[-1] <= XD_MAX_DIM and not (flags & FLAG_NO_MFMA))
+                      or load_library().glhip_kernel_conv_grad_uses_xk(int(kind), xb.shape[0], xb.shape[1], yb.shape[1], xb.shape[2],
+                                                                       _dtype_code(xb), int(flags),
+                                                                       0 if ranges is None else int(ranges.ranges_i.shape[0])) == 1))
         # laplacian / energy: squared distances from the matrix cores wherever the row blocks are spatially compact — the voxel
         # clusters of the multiscale backend as they are, large dense launches after the voxel sort the library does itself
         # (csrc/glhip_autosort.h) — for the product, the product + gradient and (GRAD_FAMILY) the companion products of a norm alike

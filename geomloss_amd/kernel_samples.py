@@ -9,6 +9,7 @@ kernel-matrix x vector products with the HIP kernel ``glhip_kernel_conv_fwd`` (d
 and never materialise a matrix.
 """
 
+import os
 from functools import partial
 
 import numpy as np
@@ -182,6 +183,18 @@ def _weights_dtype(points):
     return torch.float64 if points.dtype == torch.float64 else torch.float32
 
 
+# matrix-core gaussian gradient of 17 <= D <= 4095 (glhip_gauss_grad_xk.h): the knob of the soft-min gradient of those dimensions
+# (sinkhorn_samples._XK_GRAD) covers this one too
+_XK_GRAD = os.environ.get("GEOMLOSS_HIP_XK_GRAD", "1") != "0"
+
+
+def _grad_flags(name, pts):
+    """FLAG_XK_GRAD for the gaussian kernel beyond the compiled dimensions: the product-and-gradient reductions of _UnionNorm then run
+    on the matrix cores in dimension 17 ... 4095 (hip.kernel_conv_grad_uses_xk; the library ignores the flag where it does not apply).
+    D <= 16 keeps its default flags."""
+    return hip.FLAG_XK_GRAD if (name == "gaussian" and _XK_GRAD and pts.shape[-1] > hip.XD_MAX_DIM) else 0
+
+
 class _UnionNorm(torch.autograd.Function):
     """1/2 <w, K_zz w> on the union cloud z = (x, y), w = (α, -β), as ONE autograd node.
 
@@ -198,8 +211,9 @@ class _UnionNorm(torch.autograd.Function):
         batch = x.dim() > 2
         z = torch.cat((x, y.to(x.dtype)), dim=-2)
         w = torch.cat((α.to(_weights_dtype(x)), -β.to(_weights_dtype(x))), dim=-1)
-        U_x, unit_x = hip.kernel_conv_with_unit(name, x, z, w, blur, ctx.needs_input_grad[3])
-        U_y, unit_y = hip.kernel_conv_with_unit(name, y, z, w, blur, ctx.needs_input_grad[5])
+        fl = _grad_flags(name, x)
+        U_x, unit_x = hip.kernel_conv_with_unit(name, x, z, w, blur, ctx.needs_input_grad[3], fl)
+        U_y, unit_y = hip.kernel_conv_with_unit(name, y, z, w, blur, ctx.needs_input_grad[5], fl)
         ctx.name, ctx.blur, ctx.units = name, blur, (unit_x, unit_y)
         ctx.save_for_backward(α, x, β, y, U_x, U_y)
         return 0.5 * scal_sum(α, U_x, β, -U_y, batch=batch)
@@ -229,7 +243,7 @@ class _UnionNorm(torch.autograd.Function):
                 g = gl * wt.to(w.dtype)
                 if unit is not None:
                     return (g.unsqueeze(-1) * unit).to(pts.dtype).reshape(pts.shape)
-                return hip.kernel_conv_row_gradient(name, pts, z, w, g, blur).to(pts.dtype)
+                return hip.kernel_conv_row_gradient(name, pts, z, w, g, blur, _grad_flags(name, pts)).to(pts.dtype)
             if ctx.needs_input_grad[3]:
                 gx = rows(x, α, ctx.units[0])
             if ctx.needs_input_grad[5]:

@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 129 /* 0.1.29 */
+#define GLHIP_VERSION 130 /* 0.1.30 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
@@ -88,13 +88,18 @@ extern "C" {
                                   exponents, so it is the same in every dimension (diameter^2 grows like D on a unit cube).  Ignored by kernels
                                   without that layout (p = 1, laplacian, energy, the gradients of D > 16 other than GLHIP_FLAG_XK_GRAD, D > 4095, float64). */
 
-#define GLHIP_FLAG_XK_GRAD 1024 /* glhip_softmin_bwd_x only (version 126): the gradient of p == 2, 17 <= D <= 4095, dense launches (n_ranges == 0),
+#define GLHIP_FLAG_XK_GRAD 1024 /* glhip_softmin_bwd_x (version 126) and, gaussian kind, glhip_kernel_conv_bwd_x / glhip_kernel_conv_fwd_grad
+                                  (version 130, below).  glhip_softmin_bwd_x: the gradient of p == 2, 17 <= D <= 4095, dense launches (n_ranges == 0),
                                   B <= 65535, without GLHIP_FLAG_NO_MFMA / _DIRECT runs xk_plan_kernel on XkGradParams (csrc/glhip_softmin_grad_xk.h): the K-chunked
                                   plan application of glhip_plan_apply_nd with the centred column cloud as its features, ceil(D / 64) passes.
                                   glhip_softmin_bwd_x_uses_plan is the predicate.  Ignored everywhere else — every other entry point, p = 1,
                                   D <= 16, D > 4095, block-sparse ranges, the float64 symbols: those launches are the ones version 125 makes,
                                   bit for bit.  Without the flag nothing changes: the one-thread-per-row kernel of glhip_generic.h.
-                                  GLHIP_FLAG_F16X2 selects the exponent layout of the new kernel, under that flag's range contract. */
+                                  GLHIP_FLAG_F16X2 selects the exponent layout of the new kernel, under that flag's range contract.
+                                  glhip_kernel_conv_bwd_x / glhip_kernel_conv_fwd_grad: the gaussian gradient of 17 <= D <= 4095 under the same
+                                  conditions runs xk_plan_kernel on XkGaussGradParams (csrc/glhip_gauss_grad_xk.h);
+                                  glhip_kernel_conv_grad_uses_xk is the predicate.  Laplacian / energy, D <= 16, D > 4095, block-sparse ranges,
+                                  GLHIP_FLAG_NO_MFMA / _DIRECT and glhip_kernel_conv_fwd ignore the flag, bit for bit. */
 
 #define GLHIP_FLAG_NO_SORT 512 /* p = 1 soft-min / half-step, laplacian and energy products: big dense launches (B = 1, D <= 3, N >= 65536,
                                   N M >= 5e8, a workspace of glhip_workspace_bytes) sort both clouds into the workspace themselves — voxel sort along a
@@ -467,7 +472,21 @@ int glhip_kernel_conv_fwd(int kind, const void* x, const void* y, const float* v
  * The gradient with respect to y is the same call with (x,g) and (y,v) swapped; the gradient
  * with respect to v is glhip_kernel_conv_fwd with x and y swapped and v := g.
  * Replaces: KeOps autograd of the reductions at kernel_samples.py:128-137.
+ * D > 16 runs the one-thread-per-row kernel of glhip_generic.h.  GLHIP_FLAG_XK_GRAD (version 130) routes the GAUSSIAN gradient of
+ * 17 <= D <= 4095, dense launches, B <= 65535, without GLHIP_FLAG_NO_MFMA / _DIRECT, to the matrix cores instead: xk_plan_kernel on
+ * XkGaussGradParams (glhip_gauss_grad_xk.h) — the exponents of the gaussian product, features v_j (y_j - centre), the signed sum
+ * sum_j k_ij v_j, and g_i / blur^2 [ S_i - (x_i - centre) U_i ] at the end; 64 coordinates per pass, float32 and bfloat16 clouds, both
+ * exponent layouts (GLHIP_FLAG_F16X2 under its range contract).  A row that no column reaches writes 0.  The same flag makes
+ * glhip_kernel_conv_fwd_grad below accept those launches.  Opt-in at this level, as for glhip_softmin_bwd_x: the exponents of a long
+ * MFMA chain are bounded by max(5e-6, 4 x the error of plain float32 arithmetic), not by a flat 5e-6.
+ *   glhip_kernel_conv_grad_uses_xk: host arithmetic only, the very predicate both entry points evaluate — 1: that kernel; 0: the launch
+ *   of version 129; GLHIP_EINVAL: a bad kind or dtype, negative sizes, D < 1.
+ *   glhip_kernel_conv_grad_workspace_bytes: the split partials of the widest pass of that route (sums of <= 64 coordinates, signed
+ *   mass, row maximum per row and split), never more than 1 GiB, 0 where the predicate is 0 or under GLHIP_FLAG_NO_SPLIT.  NULL or a
+ *   short workspace: fewer or no splits, the same results up to summation order.  M == 0 zeroes grad_x (and out).
  */
+int glhip_kernel_conv_grad_uses_xk(int kind, int B, long N, long M, int D, int dtype, int flags, int n_ranges);
+size_t glhip_kernel_conv_grad_workspace_bytes(int B, int N, int M, int D, int flags);
 int glhip_kernel_conv_bwd_x(int kind, const void* x, const void* y, const float* v,
                             const float* g, float* grad_x,
                             int B, int N, int M, int D, float blur, int in_dtype,
@@ -511,8 +530,9 @@ int glhip_softmin_fwd_grad(const void* x, const void* y, const float* h, const f
  * gaussian: matrix-core kernel (GLHIP_FLAG_NO_MFMA: explicit differences).  laplacian / energy: explicit differences with
  * |.| = m rsq(m); the product is then bit-identical to glhip_kernel_conv_fwd under GLHIP_FLAG_GRAD_FAMILY, which is what the
  * three terms of one kernel norm are sent to when gradients are on (their rounding must be common to cancel).  Coincident points (inside the 1e-4
- * clamp of utils.py:61) add k(0) v_j to the product and nothing to the gradient.  D > 3: GLHIP_EUNSUPPORTED (call the two
- * entry points above).
+ * clamp of utils.py:61) add k(0) v_j to the product and nothing to the gradient.  D > 3 (gaussian on the matrix cores: D > 16):
+ * GLHIP_EUNSUPPORTED (call the two entry points above) — except, version 130, the gaussian kernel of 17 <= D <= 4095 under
+ * GLHIP_FLAG_XK_GRAD where glhip_kernel_conv_grad_uses_xk is 1: out and grad_unit from the passes of glhip_gauss_grad_xk.h.
  */
 int glhip_kernel_conv_fwd_grad(int kind, const void* x, const void* y, const float* v, float* out, float* grad_unit,
                                int B, int N, int M, int D, float blur, int in_dtype,
