@@ -1,40 +1,26 @@
 // glhip_api_argmin.hip — C-ABI part 11: the arg-reduction glhip_argmin (glhip_argmin_xk.h) with its host-only support query and its
 // workspace sizing.  A translation unit of its own: the parallel build does not get longer.
-#include "glhip_launch.h"
+#include "glhip_launch_plan.h"
 #include "glhip_argmin_xk.h"
 
 namespace {
 
 // THE predicate of glhip_argmin, and what glhip_argmin_supported reports.  Host arithmetic only.
 inline int argmin_supported(int B, long N, long M, int D, int p, int dtype, int n_ranges) {
-    if (B < 0 || N < 0 || M < 0 || N > 0x7fffffffL || M > 0x7fffffffL || D < 1 || n_ranges < 0 || (p != 1 && p != 2) ||
-        (dtype != GLHIP_F32 && dtype != GLHIP_BF16))
-        return GLHIP_EINVAL;
+    if (plan_family_bad_args(B, N, M, D, dtype, n_ranges) || (p != 1 && p != 2)) return GLHIP_EINVAL;
     return (p == 2 && n_ranges == 0 && D <= kXkMaxD && B <= 65535) ? 1 : 0;
 }
 
-// THE split policy, shared by the launcher and the sizing call: the rule of launch_xk_l (glhip_launch.h) — choose_splits, or the
-// XCD-aware grid with xcd_splits for dense launches with room for 8 splits over >= 65536 columns.  `fit`: splits the workspace holds.
-struct ArgminSplits { int n; bool xcd; };
-inline ArgminSplits argmin_splits(long row_blocks, int M, long fit, bool allow_split) {
-    if (!allow_split || fit < 2) return ArgminSplits{1, false};
-    if (fit >= 8 && M >= 65536) return ArgminSplits{xcd_splits(row_blocks, M, kXkSlots, fit), true};
-    return ArgminSplits{choose_splits(row_blocks, M, 0, fit), false};
-}
-
+// The split policy is plan_splits (glhip_launch_plan.h) with the resident workgroups of the forward kernel of 17 <= D <= 4095; the partial of
+// a row is (value, index).
 template <typename T>
 void launch_argmin(const ArgminParams<T>& prm, int B, int N, int M, int D, const Scratch& sc, hipStream_t st) {
-    const Ranges none{nullptr, nullptr, nullptr, nullptr};
-    SplitLaunch sl(none, 0, B, N, M, kXkRows, 2, sc.ws, sc.bytes, sc.cb, st);
-    const ArgminSplits as = argmin_splits(sl.row_blocks, M, sl.fit, sc.allow_split);
-    if (!(as.xcd && sl.take_xcd(as.n)))      // (a grid beyond 2^31 workgroups stays on the plain 3-D grid)
-        sl.sp.n_splits = as.xcd ? choose_splits(sl.row_blocks, M, 0, sl.fit) : as.n;
-    const dim3 grid = sl.sp.xcd_grid_x > 0 ? dim3((unsigned)((long)sl.gx * B * sl.sp.n_splits), 1, 1) : dim3(sl.gx, B, sl.sp.n_splits);
-    hipLaunchKernelGGL((argmin_xk_kernel<T>), grid, dim3(kXkThreads), 0, st, prm, N, M, D, sl.sp);
-    if (sl.sp.n_splits > 1) {
-        const long rows = (long)B * N;
-        hipLaunchKernelGGL(argmin_merge_kernel, dim3((unsigned)((rows + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, prm.index, prm.value, rows, sl.sp);
-    }
+    launch_plan_pass(kXkRows, 2, kXkSlots, B, N, M, sc, st,
+        [&](dim3 grid, const SplitInfo& sp) { hipLaunchKernelGGL((argmin_xk_kernel<T>), grid, dim3(kXkThreads), 0, st, prm, N, M, D, sp); },
+        [&](const SplitInfo& sp) {
+            const long rows = (long)B * N;
+            hipLaunchKernelGGL(argmin_merge_kernel, dim3((unsigned)((rows + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, prm.index, prm.value, rows, sp);
+        });
 }
 
 }  // namespace
@@ -48,7 +34,7 @@ int glhip_argmin_supported(int B, long N, long M, int D, int p, int dtype, int n
 size_t glhip_argmin_workspace_bytes(int B, int N, int M, int D) {
     if (B <= 0 || N <= 0 || M <= 0 || D < 1 || D > kXkMaxD) return 0;
     const long row_blocks = (long)B * ((N + kXkRows - 1) / kXkRows);
-    // room for either rule of argmin_splits (as glhip_workspace_bytes sizes the forward of 17 <= D <= 4095): non-decreasing in M
+    // room for either rule of plan_splits (as glhip_workspace_bytes sizes the forward of 17 <= D <= 4095): non-decreasing in M
     int ns = choose_splits(row_blocks, M, 0, 32);
     if (M >= 65536) {
         const int nx = xcd_splits(row_blocks, M, kXkSlots, 32);

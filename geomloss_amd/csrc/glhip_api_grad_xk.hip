@@ -1,47 +1,16 @@
 // glhip_api_grad_xk.hip — C-ABI part 10: the p = 2 soft-min gradient of 17 <= D <= 4095 on the matrix cores (GLHIP_FLAG_XK_GRAD):
 // xk_plan_kernel on XkGradParams (glhip_softmin_grad_xk.h), launched by glhip_softmin_bwd_x (glhip_api_bwd.hip) where glhip_softmin_bwd_x_uses_plan
 // says so.  A translation unit of its own: the parallel build does not get longer.
-#include "glhip_launch.h"
+#include "glhip_launch_plan.h"
 #include "glhip_softmin_grad_xk.h"
 
 namespace {
 
-constexpr size_t kGradXkMaxWorkspace = (size_t)1 << 30;   // glhip_softmin_bwd_x_workspace_bytes never asks for more than 1 GiB (glhip.h)
-constexpr long kXkGradSlots = 256;                        // resident 8-wave workgroups: one per CU, as xk_plan_kernel
-constexpr int kGradXkWidth = 32 * kXkPlanMaxChunks;       // coordinates per pass
-
 // THE predicate of the GLHIP_FLAG_XK_GRAD route of glhip_softmin_bwd_x, and what glhip_softmin_bwd_x_uses_plan reports.  Host arithmetic only.
 inline int grad_xk_uses_plan(int B, long N, long M, int D, int p, int dtype, int flags, int n_ranges) {
-    if (B < 0 || N < 0 || M < 0 || N > 0x7fffffffL || M > 0x7fffffffL || D < 1 || n_ranges < 0 || (p != 1 && p != 2) ||
-        (dtype != GLHIP_F32 && dtype != GLHIP_BF16))
-        return GLHIP_EINVAL;
+    if (plan_family_bad_args(B, N, M, D, dtype, n_ranges) || (p != 1 && p != 2)) return GLHIP_EINVAL;
     if (!(flags & GLHIP_FLAG_XK_GRAD) || (flags & (GLHIP_FLAG_NO_MFMA | GLHIP_FLAG_DIRECT))) return 0;
     return (p == 2 && D > kXdMaxD && D <= kXkMaxD && n_ranges == 0 && B <= 65535) ? 1 : 0;
-}
-
-template <typename T, int NCH, int L>
-void launch_xk_grad_pass(const XkGradParams<T>& prm, int B, int N, int M, int D, const Scratch& sc, hipStream_t st) {
-    const Ranges none{nullptr, nullptr, nullptr, nullptr};
-    SplitLaunch sl(none, 0, B, N, M, kXkRows, prm.nv + 2, sc.ws, sc.bytes, sc.cb, st);
-    const PlanSplits ps = plan_splits(sl.row_blocks, M, sl.fit, sc.allow_split, kXkGradSlots);
-    if (!(ps.xcd && sl.take_xcd(ps.n)))      // (a grid beyond 2^31 workgroups stays on the plain 3-D grid)
-        sl.sp.n_splits = ps.xcd ? choose_splits(sl.row_blocks, M, 0, sl.fit) : ps.n;
-    const dim3 grid = sl.sp.xcd_grid_x > 0 ? dim3((unsigned)((long)sl.gx * B * sl.sp.n_splits), 1, 1) : dim3(sl.gx, B, sl.sp.n_splits);
-    hipLaunchKernelGGL((xk_plan_kernel<T, NCH, L, XkGradParams<T>>), grid, dim3(kXkThreads), 0, st, prm, N, M, D, sl.sp);
-    if (sl.sp.n_splits > 1) {
-        const long rows = (long)B * N, items = rows * prm.nv;
-        hipLaunchKernelGGL((xk_grad_merge_kernel<T>), dim3((unsigned)((items + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, prm, N, D, rows, sl.sp);
-    }
-}
-
-template <typename T, int L>
-void launch_xk_grad(XkGradParams<T> prm, int B, int N, int M, int D, const Scratch& sc, hipStream_t st) {
-    for (int v0 = 0; v0 < D; v0 += kGradXkWidth) {
-        prm.v0 = v0;
-        prm.nv = D - v0 < kGradXkWidth ? D - v0 : kGradXkWidth;
-        if (prm.nv > 32) launch_xk_grad_pass<T, 2, L>(prm, B, N, M, D, sc, st);
-        else launch_xk_grad_pass<T, 1, L>(prm, B, N, M, D, sc, st);
-    }
 }
 
 }  // namespace
@@ -59,8 +28,7 @@ int softmin_grad_xk_launch(const void* x, const void* y, const float* h, const f
     auto run = [&](auto tag) {
         using T = decltype(tag);
         const XkGradParams<T> prm{static_cast<const T*>(x), static_cast<const T*>(y), h, fwd, g, gx, kLog2e / eps, -eps * kLn2, 0, 0};
-        if (sc.h2) launch_xk_grad<T, XL_F16X2>(prm, B, N, M, D, sc, st);
-        else launch_xk_grad<T, XL_BF16X3>(prm, B, N, M, D, sc, st);
+        launch_xk_plan_passes(prm, D, B, N, M, D, sc, st);
     };
     if (in_dtype == GLHIP_F32) run(float{}); else run(bf16_t{});
     return GLHIP_OK;
@@ -77,13 +45,7 @@ int glhip_softmin_bwd_x_uses_plan(int B, long N, long M, int D, int p, int dtype
 size_t glhip_softmin_bwd_x_workspace_bytes(int B, int N, int M, int D, int flags) {
     if (B <= 0 || N <= 0 || M <= 0 || (flags & GLHIP_FLAG_NO_SPLIT)) return 0;
     if (grad_xk_uses_plan(B, N, M, D, 2, GLHIP_F32, flags, 0) != 1) return 0;
-    const int nv = D < kGradXkWidth ? D : kGradXkWidth;      // the widest pass
-    const size_t per_split = (size_t)B * N * (nv + 2) * sizeof(float);
-    const long row_blocks = (long)B * ((N + kXkRows - 1) / kXkRows);
-    long fit = (long)(kGradXkMaxWorkspace / per_split);
-    fit = fit < 32 ? fit : 32;
-    const int ns = plan_splits(row_blocks, M, fit, true, kXkGradSlots).n;
-    return ns >= 2 ? (size_t)ns * per_split : 0;
+    return plan_pass_workspace_bytes(B, N, M, kXkRows, D < kXkPlanWidth ? D : kXkPlanWidth, {kXkPlanSlots});
 }
 
 }  // extern "C"

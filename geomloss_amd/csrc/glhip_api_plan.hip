@@ -1,28 +1,19 @@
 // glhip_api_plan.hip — C-ABI part 8: the transport plan of a p = 2 soft-min applied to a feature matrix (glhip_plan_apply.h).
-#include "glhip_launch.h"
-#include "glhip_plan_apply.h"
+#include "glhip_launch_plan.h"
 
 namespace {
 
-constexpr size_t kPlanMaxWorkspace = (size_t)1 << 30;      // glhip_plan_apply_workspace_bytes never asks for more than 1 GiB (glhip.h)
-
 template <int D, typename T, int NCH, int L>
-void launch_plan_pass(const PlanParams<T>& prm, int B, int N, int M, const Scratch& sc, hipStream_t st) {
-    const Ranges none{nullptr, nullptr, nullptr, nullptr};
-    SplitLaunch sl(none, 0, B, N, M, kPlanRows, prm.nv + 2, sc.ws, sc.bytes, sc.cb, st);
+void launch_plan_d_pass(const PlanParams<T>& prm, int B, int N, int M, const Scratch& sc, hipStream_t st) {
     constexpr long kSlots = 256L * (PlanShape<D, NCH, L>::template waves<T>() / 2);      // resident 8-wave workgroups (PlanShape::waves)
-    const PlanSplits ps = plan_splits(sl.row_blocks, M, sl.fit, sc.allow_split, kSlots);
-    if (!(ps.xcd && sl.take_xcd(ps.n)))      // (a grid beyond 2^31 workgroups stays on the plain 3-D grid)
-        sl.sp.n_splits = ps.xcd ? choose_splits(sl.row_blocks, M, 0, sl.fit) : ps.n;
-    const dim3 grid = sl.sp.xcd_grid_x > 0 ? dim3((unsigned)((long)sl.gx * B * sl.sp.n_splits), 1, 1) : dim3(sl.gx, B, sl.sp.n_splits);
-    hipLaunchKernelGGL((plan_apply_kernel<D, T, NCH, L>), grid, dim3(kPlanNW * 64), 0, st, prm, N, M, sl.sp);
-    if (sl.sp.n_splits > 1) {      // run-time width: one merge kernel for every chunk count (glhip_plan_apply.h)
-        const long rows = (long)B * N, items = rows * prm.nv;
-        hipLaunchKernelGGL(plan_merge_kernel, dim3((unsigned)((items + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, prm.out, prm.mass, rows,
-                           prm.V, prm.v0, prm.nv, sl.sp);
-    }
+    launch_plan_pass(kPlanRows, prm.nv + 2, kSlots, B, N, M, sc, st,
+        [&](dim3 grid, const SplitInfo& sp) {
+            hipLaunchKernelGGL((plan_apply_kernel<D, T, NCH, L>), grid, dim3(kPlanNW * 64), 0, st, prm, N, M, sp);
+        },
+        [&](const SplitInfo& sp) { launch_plan_merge(prm, B, N, D, sp, st); });
 }
 
+// (a loop of its own, not launch_xk_plan_passes: the pass width and the chunk counts depend on D)
 template <int D, typename T, int L>
 void launch_plan_d(PlanParams<T> prm, int B, int N, int M, int V, const Scratch& sc, hipStream_t st) {
     constexpr int kMax = PlanShape<D, 1, L>::kMaxChunks;       // passes of up to 128 (64) features
@@ -30,12 +21,12 @@ void launch_plan_d(PlanParams<T> prm, int B, int N, int M, int V, const Scratch&
         prm.v0 = v0;
         prm.nv = V - v0 < 32 * kMax ? V - v0 : 32 * kMax;
         if constexpr (kMax == 4) {
-            if (prm.nv > 64) { launch_plan_pass<D, T, 4, L>(prm, B, N, M, sc, st); continue; }
+            if (prm.nv > 64) { launch_plan_d_pass<D, T, 4, L>(prm, B, N, M, sc, st); continue; }
         }
         if constexpr (kMax >= 2) {
-            if (prm.nv > 32) { launch_plan_pass<D, T, 2, L>(prm, B, N, M, sc, st); continue; }
+            if (prm.nv > 32) { launch_plan_d_pass<D, T, 2, L>(prm, B, N, M, sc, st); continue; }
         }
-        launch_plan_pass<D, T, 1, L>(prm, B, N, M, sc, st);
+        launch_plan_d_pass<D, T, 1, L>(prm, B, N, M, sc, st);
     }
 }
 
@@ -59,15 +50,8 @@ extern "C" {
 
 size_t glhip_plan_apply_workspace_bytes(int B, int N, int M, int D, int V) {
     if (B <= 0 || N <= 0 || M <= 0 || D < 1 || V <= 0) return 0;
-    const int nv = V < 32 * kPlanMaxChunks ? V : 32 * kPlanMaxChunks;      // the widest pass any dimension takes
-    const size_t per_split = (size_t)B * N * (nv + 2) * sizeof(float);
-    const long row_blocks = (long)B * ((N + kPlanRows - 1) / kPlanRows);
-    long fit = (long)(kPlanMaxWorkspace / per_split);
-    fit = fit < 32 ? fit : 32;
-    // what the launcher would take with that much room, for either number of resident workgroups a kernel shape has
-    const int a = plan_splits(row_blocks, M, fit, true, 256).n, b = plan_splits(row_blocks, M, fit, true, 512).n;
-    const int ns = a > b ? a : b;
-    return ns >= 2 ? (size_t)ns * per_split : 0;
+    // the widest pass any dimension takes, for either number of resident workgroups a kernel shape has
+    return plan_pass_workspace_bytes(B, N, M, kPlanRows, V < 32 * kPlanMaxChunks ? V : 32 * kPlanMaxChunks, {256, 512});
 }
 
 int glhip_plan_apply(const void* x, const void* y, const float* h, const float* fwd, const float* feat, float* out, float* mass,

@@ -1,56 +1,23 @@
 // glhip_api_plan_xk.hip — C-ABI part 9: plan application in any dimension up to 4095.  1 <= D <= 16 forwards to glhip_plan_apply
 // (glhip_api_plan.hip); 17 <= D <= 4095 runs xk_plan_kernel (glhip_plan_apply_xk.h).  A translation unit of its own: the parallel
 // build does not get longer.
-#include "glhip_launch.h"
-#include "glhip_plan_apply_xk.h"
+#include "glhip_launch_plan.h"
 
 namespace {
-
-constexpr size_t kPlanNdMaxWorkspace = (size_t)1 << 30;   // glhip_plan_apply_nd_workspace_bytes never asks for more than 1 GiB (glhip.h)
-constexpr long kXkPlanSlots = 256;                        // resident 8-wave workgroups: one per CU (glhip_plan_apply_xk.h)
 
 static_assert(PlanShape<4, 1, XL_BF16X3>::kMaxChunks == 4 && PlanShape<5, 1, XL_BF16X3>::kMaxChunks == 2 &&
               PlanShape<11, 1, XL_BF16X3>::kMaxChunks == 2 && PlanShape<12, 1, XL_BF16X3>::kMaxChunks == 1,
               "plan_nd_pass_width restates PlanShape::kMaxChunks");
 inline int plan_nd_pass_width(int D) {
     if (D <= kXdMaxD) return D <= 4 ? 128 : (D <= 11 ? 64 : 32);
-    return 32 * kXkPlanMaxChunks;
+    return kXkPlanWidth;
 }
 
 // THE predicate of glhip_plan_apply_nd, and what glhip_plan_apply_nd_family reports.  Host arithmetic only.
 inline int plan_nd_family(int B, long N, long M, int D, int V, int p, int dtype, int n_ranges) {
-    if (B < 0 || N < 0 || M < 0 || N > 0x7fffffffL || M > 0x7fffffffL || D < 1 || V < 0 || n_ranges < 0 || (p != 1 && p != 2) ||
-        (dtype != GLHIP_F32 && dtype != GLHIP_BF16))
-        return GLHIP_EINVAL;
+    if (plan_family_bad_args(B, N, M, D, dtype, n_ranges) || V < 0 || (p != 1 && p != 2)) return GLHIP_EINVAL;
     if (p != 2 || n_ranges > 0 || D > kXkMaxD || B > 65535) return GLHIP_EUNSUPPORTED;
     return D <= kXdMaxD ? GLHIP_FAMILY_XD : GLHIP_FAMILY_XK;
-}
-
-template <typename T, int NCH, int L>
-void launch_xk_plan_pass(const PlanParams<T>& prm, int B, int N, int M, int D, const Scratch& sc, hipStream_t st) {
-    const Ranges none{nullptr, nullptr, nullptr, nullptr};
-    SplitLaunch sl(none, 0, B, N, M, kXkRows, prm.nv + 2, sc.ws, sc.bytes, sc.cb, st);
-    const PlanSplits ps = plan_splits(sl.row_blocks, M, sl.fit, sc.allow_split, kXkPlanSlots);
-    if (!(ps.xcd && sl.take_xcd(ps.n)))      // (a grid beyond 2^31 workgroups stays on the plain 3-D grid)
-        sl.sp.n_splits = ps.xcd ? choose_splits(sl.row_blocks, M, 0, sl.fit) : ps.n;
-    const dim3 grid = sl.sp.xcd_grid_x > 0 ? dim3((unsigned)((long)sl.gx * B * sl.sp.n_splits), 1, 1) : dim3(sl.gx, B, sl.sp.n_splits);
-    hipLaunchKernelGGL((xk_plan_kernel<T, NCH, L, PlanParams<T>>), grid, dim3(kXkThreads), 0, st, prm, N, M, D, sl.sp);
-    if (sl.sp.n_splits > 1) {
-        const long rows = (long)B * N, items = rows * prm.nv;
-        hipLaunchKernelGGL(plan_merge_kernel, dim3((unsigned)((items + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, prm.out, prm.mass, rows,
-                           prm.V, prm.v0, prm.nv, sl.sp);
-    }
-}
-
-template <typename T, int L>
-void launch_xk_plan(PlanParams<T> prm, int B, int N, int M, int D, int V, const Scratch& sc, hipStream_t st) {
-    constexpr int kWidth = 32 * kXkPlanMaxChunks;
-    for (int v0 = 0; v0 < V; v0 += kWidth) {
-        prm.v0 = v0;
-        prm.nv = V - v0 < kWidth ? V - v0 : kWidth;
-        if (prm.nv > 32) launch_xk_plan_pass<T, 2, L>(prm, B, N, M, D, sc, st);
-        else launch_xk_plan_pass<T, 1, L>(prm, B, N, M, D, sc, st);
-    }
 }
 
 }  // namespace
@@ -67,14 +34,7 @@ int glhip_plan_apply_nd_pass_width(int D) { return (D < 1 || D > kXkMaxD) ? 0 : 
 size_t glhip_plan_apply_nd_workspace_bytes(int B, int N, int M, int D, int V) {
     if (B <= 0 || N <= 0 || M <= 0 || D < 1 || D > kXkMaxD || V <= 0) return 0;
     if (D <= kXdMaxD) return glhip_plan_apply_workspace_bytes(B, N, M, D, V);
-    const int width = plan_nd_pass_width(D);
-    const int nv = V < width ? V : width;      // the widest pass
-    const size_t per_split = (size_t)B * N * (nv + 2) * sizeof(float);
-    const long row_blocks = (long)B * ((N + kXkRows - 1) / kXkRows);
-    long fit = (long)(kPlanNdMaxWorkspace / per_split);
-    fit = fit < 32 ? fit : 32;
-    const int ns = plan_splits(row_blocks, M, fit, true, kXkPlanSlots).n;
-    return ns >= 2 ? (size_t)ns * per_split : 0;
+    return plan_pass_workspace_bytes(B, N, M, kXkRows, V < kXkPlanWidth ? V : kXkPlanWidth, {kXkPlanSlots});
 }
 
 int glhip_plan_apply_nd(const void* x, const void* y, const float* h, const float* fwd, const float* feat, float* out, float* mass,
@@ -109,8 +69,7 @@ int glhip_plan_apply_nd(const void* x, const void* y, const float* h, const floa
         using T = decltype(tag);
         const PlanParams<T> prm{static_cast<const T*>(x), static_cast<const T*>(y), h, fwd, feat, out, mass,
                                 kLog2e / eps, -eps * kLn2, V, 0, 0};
-        if (sc.h2) launch_xk_plan<T, XL_F16X2>(prm, B, N, M, D, V, sc, st);
-        else launch_xk_plan<T, XL_BF16X3>(prm, B, N, M, D, V, sc, st);
+        launch_xk_plan_passes(prm, V, B, N, M, D, sc, st);
     };
     if (in_dtype == GLHIP_F32) run(float{}); else run(bf16_t{});
     return check_launch("glhip_plan_apply_nd");

@@ -19,8 +19,8 @@
 //              writes out_i = 2^m W on the pass with v0 == 0.
 //   empty rows W can be exactly 0 while S is not (two columns of weights +v and -v at equal distance), so a row is empty only when no
 //              column reached it: 2^m == 0 (m still at its initial value, or the power underflowed).  Such a row writes 0, never NaN.
-//   splits     partials (S[nv], W, m) per split as xk_grad_merge_kernel's; xk_gauss_grad_merge_kernel brings the splits to the largest
-//              m, adds them and applies the same epilogue with the centre row (i / kXkRows) kXkRows.
+//   splits     partials (S[nv], W, m) per split as the soft-min gradient's; plan_merge_kernel brings the splits to the largest
+//              m and adds them, plan_merge_store below applies the same epilogue with the centre row (i / kXkRows) kXkRows.
 //
 // Passes of 64 coordinates (NCH = 2), a remainder of <= 32 as NCH = 1, as the soft-min gradient.
 //   registers / LDS / scratch (gfx950, tools/kernel_resources.py, profiles/gauss_grad_xk.txt): 0 bytes of scratch in all eight
@@ -45,24 +45,10 @@ struct XkGaussGradParams {
     int nv;               // coordinates of this pass, <= 32 NCH
 };
 
-// Combines the column splits of a gaussian gradient pass: one thread per (row, coordinate), the format of xk_grad_merge_kernel.
+// The gaussian gradient's end of plan_merge_kernel (glhip_plan_apply.h): the merged sums S of coordinate c and W of a row, both relative
+// to 2^mx, put through the unnormalised epilogue of xk_plan_kernel.
 template <typename T>
-__global__ void __launch_bounds__(kBlock)
-xk_gauss_grad_merge_kernel(XkGaussGradParams<T> prm, int N, int D, long rows, SplitInfo sp) {
-    const long id = (long)blockIdx.x * kBlock + threadIdx.x;
-    const int nv = prm.nv;
-    if (id >= rows * nv) return;
-    const long row = id / nv;
-    const int c = (int)(id - row * nv);
-    const float* part = sp.workspace + row * (nv + 2);
-    float mx = kMinusHuge;
-    for (int k = 0; k < sp.n_splits; ++k) mx = fmaxf(mx, part[k * sp.split_stride + nv + 1]);
-    float s = 0.f, w = 0.f;
-    for (int k = 0; k < sp.n_splits; ++k) {
-        const float rs = fast_exp2(part[k * sp.split_stride + nv + 1] - mx);
-        s = __builtin_fmaf(part[k * sp.split_stride + c], rs, s);
-        w = __builtin_fmaf(part[k * sp.split_stride + nv], rs, w);
-    }
+__device__ __forceinline__ void plan_merge_store(const XkGaussGradParams<T>& prm, int N, int D, long row, int c, float s, float w, float mx) {
     const long i = row % N;
     const long crow = row - i + (i / kXkRows) * kXkRows;      // the first row of the row block, within the batch item
     const float xc = to_f32<T>(prm.x[row * D + prm.v0 + c]) - to_f32<T>(prm.x[crow * D + prm.v0 + c]);

@@ -452,15 +452,7 @@ void launch_xk(const SoftminParams<T>& prm, const typename MergeOp::Params& mprm
     else launch_xk_l<MODE, T, MergeOp, XL_BF16X3>(prm, mprm, rg, n_ranges, B, N, M, D, sc, st);
 }
 
-// Plan application (glhip_plan_apply.h, glhip_plan_apply_xk.h).  THE split policy of a pass, shared by the launchers and by the sizing calls: the rule of every split launch (choose_splits), or — dense
-// launches with room for 8 splits over >= 65536 columns (SplitLaunch::xcd_eligible) — the XCD-aware grid with xcd_splits.
-// `fit`: splits the workspace holds; `slots`: resident workgroups of the kernel shape.
-struct PlanSplits { int n; bool xcd; };
-inline PlanSplits plan_splits(long row_blocks, int M, long fit, bool allow_split, long slots) {
-    if (!allow_split || fit < 2) return PlanSplits{1, false};
-    if (fit >= 8 && M >= 65536) return PlanSplits{xcd_splits(row_blocks, M, slots, fit), true};
-    return PlanSplits{choose_splits(row_blocks, M, 0, fit), false};
-}
+// (plan application, the D > 16 gradients and argmin: glhip_launch_plan.h)
 
 // Which matrix-core forward family serves a p = 2 soft-min / half-step / gaussian product in dimension D > 3 under `flags`
 // (GLHIP_FLAG_NO_MFMA / _DIRECT: none — the generic kernel)

@@ -366,12 +366,22 @@ plan_apply_kernel(PlanParams<T> prm, int N, int M, SplitInfo sp) {
     }
 }
 
-// Combines the column splits of a pass: one thread per (row, feature).  The partials of a row are nv sums, the mass — both relative
-// to 2^m of their split — and m: the splits are brought to the largest m (factor exactly 1 for the split that holds it), added and divided.
-// (static: two translation units launch it — glhip_api_plan.hip and glhip_api_plan_xk.hip — as with build_row_chunks_kernel)
-static __global__ void __launch_bounds__(kBlock)
-plan_merge_kernel(float* __restrict__ out, float* __restrict__ mass, long rows, int V, int v0, int nv, SplitInfo sp) {
+// The plan's end of plan_merge_kernel: entry c of the pass in row `row` from the merged sum s and mass w, both relative to 2^mx — divided.
+template <typename T>
+__device__ __forceinline__ void plan_merge_store(const PlanParams<T>& prm, int, int, long row, int c, float s, float w, float mx) {
+    prm.out[row * prm.V + prm.v0 + c] = (w > 0.f) ? s / w : 0.f;
+    if (c == 0 && prm.v0 == 0 && prm.mass) prm.mass[row] = w * fast_exp2(mx);
+}
+
+// Combines the column splits of a pass of plan_apply_kernel or of xk_plan_kernel (glhip_plan_apply_xk.h) on the parameter struct P: one
+// thread per (row, feature).  The partials of a row are nv sums, the mass — both relative to 2^m of their split — and m: the splits are
+// brought to the largest m (factor exactly 1 for the split that holds it) and added; plan_merge_store(prm, N, D, ...), overloaded next
+// to each parameter struct, puts the sums through the epilogue of its kernel.
+template <class P>
+__global__ void __launch_bounds__(kBlock)
+plan_merge_kernel(P prm, int N, int D, long rows, SplitInfo sp) {
     const long id = (long)blockIdx.x * kBlock + threadIdx.x;
+    const int nv = prm.nv;
     if (id >= rows * nv) return;
     const long row = id / nv;
     const int c = (int)(id - row * nv);
@@ -384,8 +394,7 @@ plan_merge_kernel(float* __restrict__ out, float* __restrict__ mass, long rows, 
         s = __builtin_fmaf(part[k * sp.split_stride + c], rs, s);
         w = __builtin_fmaf(part[k * sp.split_stride + nv], rs, w);
     }
-    out[row * V + v0 + c] = (w > 0.f) ? s / w : 0.f;
-    if (c == 0 && v0 == 0 && mass) mass[row] = w * fast_exp2(mx);
+    plan_merge_store(prm, N, D, row, c, s, w, mx);
 }
 
 }  // namespace glhip
