@@ -9,8 +9,8 @@ int glhip_kernel_conv_fwd_family(int kind, int B, long N, long M, int D, int dty
         (dtype != GLHIP_F32 && dtype != GLHIP_BF16))
         return GLHIP_EINVAL;
     if (kind != GLHIP_GAUSSIAN && autosort_applies(B, (int)N, (int)M, D, n_ranges, flags))   // the inner launch over slabs of sorted rows
-        return conv_fwd_family(kind, 1, D, flags | GLHIP_FLAG_MFMA_DIST | GLHIP_FLAG_NO_SORT, (int)((N + kSortSlab - 1) / kSortSlab));
-    return conv_fwd_family(kind, B, D, flags, n_ranges);
+        return conv_family(kind, 0, 1, D, flags | GLHIP_FLAG_MFMA_DIST | GLHIP_FLAG_NO_SORT, (int)((N + kSortSlab - 1) / kSortSlab));
+    return conv_family(kind, 0, B, D, flags, n_ranges);
 }
 
 int glhip_kernel_conv_fwd(int kind, const void* x, const void* y, const float* v, float* out, int B, int N, int M,
@@ -25,26 +25,20 @@ int glhip_kernel_conv_fwd(int kind, const void* x, const void* y, const float* v
     if (kind != GLHIP_ENERGY && !(blur > 0.f)) return fail(GLHIP_EINVAL, "glhip_kernel_conv_fwd: blur must be > 0");
     const Ranges rg{ranges_i, slices_i, redranges_j};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    // laplacian / energy, big dense launches: sorted clouds -> distances on the matrix cores (glhip_autosort.h).  GLHIP_FLAG_GRAD_FAMILY
-    // travels with the inner launch: glhip_kernel_conv_fwd_grad sorts the same way, so the two still round alike.
+    // laplacian / energy, big dense launches: sorted clouds -> distances on the matrix cores (autosort_conv, glhip_autosort.h)
     if (kind != GLHIP_GAUSSIAN && autosort_applies(B, N, M, D, n_ranges, flags)) {
-        AutoSort a;
-        const int C = (N + kSortSlab - 1) / kSortSlab;
-        rc = autosort_prepare(a, x, y, N, M, D, in_dtype, workspace, workspace_bytes, glhip_workspace_bytes(1, N, M, D, C), st);
-        if (rc) return rc;
-        if (a.on) {
-            gather_f32(v, a.perm_y, a.col0, M, st);
-            rc = glhip_kernel_conv_fwd(kind, a.xs, a.ys, a.col0, a.out, 1, N, M, D, blur, in_dtype, a.ranges_i, a.slices_i, a.red, a.C, a.inner_ws,
-                                       a.inner_bytes, flags | GLHIP_FLAG_MFMA_DIST | GLHIP_FLAG_NO_SORT, stream);
-            if (rc) return rc;
-            scatter_f32(a.out, a.perm_x, out, N, st);
-            return check_launch("glhip_kernel_conv_fwd");
-        }
+        bool ran;
+        rc = autosort_conv("glhip_kernel_conv_fwd", x, y, v, out, nullptr, N, M, D, in_dtype, workspace, workspace_bytes, flags, st, &ran,
+                           [&](const AutoSort& a, int inner_flags) {
+                               return glhip_kernel_conv_fwd(kind, a.xs, a.ys, a.col0, a.out, 1, N, M, D, blur, in_dtype, a.ranges_i, a.slices_i, a.red,
+                                                            a.C, a.inner_ws, a.inner_bytes, inner_flags, stream);
+                           });
+        if (rc || ran) return rc;
     }
     const Scratch sc = make_scratch(workspace, workspace_bytes, flags, n_ranges, N);
     rc = (in_dtype == GLHIP_F32)
-             ? conv_typed<false, float>(kind, x, y, v, out, nullptr, nullptr, B, N, M, D, blur, rg, n_ranges, sc, flags, st)
-             : conv_typed<false, bf16_t>(kind, x, y, v, out, nullptr, nullptr, B, N, M, D, blur, rg, n_ranges, sc, flags, st);
+             ? conv_typed<0, float>(kind, x, y, v, out, nullptr, nullptr, B, N, M, D, blur, rg, n_ranges, sc, flags, st)
+             : conv_typed<0, bf16_t>(kind, x, y, v, out, nullptr, nullptr, B, N, M, D, blur, rg, n_ranges, sc, flags, st);
     return rc ? rc : check_launch("glhip_kernel_conv_fwd");
 }
 

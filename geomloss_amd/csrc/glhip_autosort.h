@@ -19,6 +19,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "glhip_error.h"
+
 namespace glhip {
 
 constexpr int kSortSlab = 256;        // rows per row block = the row tile of the distance kernel (8 wavefronts x 32 rows)
@@ -219,6 +221,28 @@ inline int autosort_prepare(AutoSort& a, const void* x, const void* y, int N, in
     a.inner_bytes = workspace_bytes - off;
     a.on = true;
     return 0;
+}
+
+// The sorted call of a laplacian / energy kernel product (glhip_kernel_conv_fwd, glhip_kernel_conv_fwd_grad) where autosort_applies: both
+// clouds sorted into the workspace, v gathered, `inner(a, flags)` — the entry point itself on the sorted clouds, block-sparse over the
+// slabs, writing a.out (and a.out_rows) — and the product (and the rows of `rows_out`, where given) scattered back to the caller's order.
+// GLHIP_FLAG_GRAD_FAMILY travels with the inner flags: both entry points sort the same way, so the two still round alike.
+// *ran stays false when the workspace is too small: the caller launches on the clouds as they are.
+template <class Inner>
+int autosort_conv(const char* fn, const void* x, const void* y, const float* v, float* out, float* rows_out, int N, int M, int D,
+                  int in_dtype, void* workspace, size_t workspace_bytes, int flags, hipStream_t st, bool* ran, Inner inner) {
+    AutoSort a;
+    *ran = false;
+    const int C = (N + kSortSlab - 1) / kSortSlab;
+    int rc = autosort_prepare(a, x, y, N, M, D, in_dtype, workspace, workspace_bytes, glhip_workspace_bytes(1, N, M, D, C), st);
+    if (rc || !a.on) return rc;
+    *ran = true;
+    gather_f32(v, a.perm_y, a.col0, M, st);
+    rc = inner(a, flags | GLHIP_FLAG_MFMA_DIST | GLHIP_FLAG_NO_SORT);
+    if (rc) return rc;
+    scatter_f32(a.out, a.perm_x, out, N, st);
+    if (rows_out) scatter_f32(a.out_rows, a.perm_x, rows_out, N, st, D);
+    return check_launch(fn);
 }
 
 }  // namespace glhip

@@ -1,6 +1,12 @@
 // glhip_launch.h — host side shared by the translation units of libgeomloss_hip.so: argument checks, scratch layout, kernel
 // selection and launch templates.  Everything lives in an anonymous namespace on purpose: each .hip file includes this header and
 // instantiates only the templates its entry points use (forward / gradient / kernel-product kernels compile in parallel).
+//
+// Which kernel runs is a host predicate per entry-point family, stated once and switched on by the body that launches:
+//   soft-min forward / half-step   softmin_fwd_family -> softmin_typed<false>      (reported by glhip_softmin_fwd_family)
+//   kernel products, three modes   conv_family        -> conv_typed<MODE>          (mode 0 reported by glhip_kernel_conv_fwd_family)
+// Parameters come from one builder each (make_softmin_params, make_conv_params: the only place that names the scales of a kernel
+// kind); the one-thread-per-row fallback of both bodies is launch_generic.  The plan family: glhip_launch_plan.h.
 #pragma once
 
 #include <cmath>
@@ -563,16 +569,23 @@ inline int softmin_fwd_family(int B, long N, long M, int D, int p, int flags, in
     return highd_p2_family(D, flags);
 }
 
-// ... and of a kernel product (glhip_kernel_conv_fwd): THE predicate of conv_typed<false> below, reported by glhip_kernel_conv_fwd_family.
-// GLHIP_FAMILY_X32 stands for the matrix-core gaussian product of D <= 3 (glhip_wsum_x32.h / glhip_wsum_mfma.h).
-inline int conv_fwd_family(int kind, int B, int D, int flags, int n_ranges) {
+// ... and of a kernel product: THE predicate of conv_typed<MODE> below.  `mode` is ConvOp's MODE: 0 product (glhip_kernel_conv_fwd; what
+// glhip_kernel_conv_fwd_family reports), 1 gradient (glhip_kernel_conv_bwd_x), 2 product and unit gradient (glhip_kernel_conv_fwd_grad,
+// which has no generic kernel: GLHIP_EUNSUPPORTED where the others say GLHIP_FAMILY_GENERIC).  The gaussian gradients of 17 <= D <= 4095
+// under GLHIP_FLAG_XK_GRAD are a predicate of their own, asked first (glhip_kernel_conv_grad_uses_xk, glhip_api_convgrad_xk.hip).
+// Gaussian: GLHIP_FAMILY_X32 stands for the matrix-core kernels of D <= 3 (glhip_wsum_x32.h / glhip_wsum_mfma.h), GLHIP_FAMILY_XD in
+// modes 1 and 2 for the transposed kernel of 4 <= D <= 16 (glhip_wsum_t32.h).
+inline int conv_family(int kind, int mode, int B, int D, int flags, int n_ranges) {
+    const bool mfma = !(flags & GLHIP_FLAG_NO_MFMA);
     if (D <= 3) {
-        if (kind == GLHIP_GAUSSIAN) return (flags & GLHIP_FLAG_NO_MFMA) ? GLHIP_FAMILY_VALU : GLHIP_FAMILY_X32;
+        if (kind == GLHIP_GAUSSIAN) return mfma ? GLHIP_FAMILY_X32 : GLHIP_FAMILY_VALU;
         return use_mfma_dist(flags, n_ranges, B, D) ? GLHIP_FAMILY_DIST : GLHIP_FAMILY_VALU;
     }
+    const int none = mode == 2 ? GLHIP_EUNSUPPORTED : GLHIP_FAMILY_GENERIC;
     if (kind != GLHIP_GAUSSIAN)      // laplacian / energy: distances on the matrix cores, dense launches of D <= 16
-        return (D <= kXdMaxD && n_ranges == 0 && !(flags & GLHIP_FLAG_NO_MFMA)) ? GLHIP_FAMILY_DIST : GLHIP_FAMILY_GENERIC;
-    return highd_p2_family(D, flags & ~GLHIP_FLAG_DIRECT);      // (_DIRECT means nothing to a kernel product)
+        return (mode != 2 && D <= kXdMaxD && n_ranges == 0 && mfma) ? GLHIP_FAMILY_DIST : none;
+    if (mode == 0) return highd_p2_family(D, flags & ~GLHIP_FLAG_DIRECT);      // (_DIRECT means nothing to a kernel product)
+    return (D <= kXdMaxD && mfma) ? GLHIP_FAMILY_XD : none;
 }
 
 template <int D, bool BWD, typename T>
@@ -611,6 +624,31 @@ SoftminParams<T> make_softmin_params(const void* x, const void* y, const float* 
     prm.beta = beta;
     prm.shift2 = 0.f;
     return prm;
+}
+
+// The parameters of a kernel product / its gradient: the one place that names the scales of a kind (glhip_kconv_ops.h).  `t` scales the
+// coordinates into base-2 units, `gscale` takes the direction sum of the scaled coordinates back to d/dx, `clamp2` = 1e-8 t^2 floors the
+// scaled squared distance under a square root.  A route that reads only some of the fields (a forward merge: `out`) gets them all.
+template <typename T>
+ConvParams<T> make_conv_params(int kind, const void* x, const void* y, const float* v, float* out, const float* g, float* gx, float blur) {
+    ConvParams<T> prm{static_cast<const T*>(x), static_cast<const T*>(y), v, out, g, gx, 1.0f, -1.0f, 1e-8f};      // energy
+    if (kind == GLHIP_GAUSSIAN) {
+        prm.t = std::sqrt(0.5f * kLog2e) / blur;
+        prm.gscale = -1.0f / (prm.t * blur * blur);
+        prm.clamp2 = 0.f;
+    } else if (kind == GLHIP_LAPLACIAN) {
+        prm.t = kLog2e / blur;
+        prm.gscale = -1.0f / blur;
+        prm.clamp2 = 1e-8f * kLog2e * kLog2e;   // the reference clamps |x/blur - y/blur|^2
+    }
+    return prm;
+}
+
+// the one-thread-per-row kernel of glhip_generic.h: one workgroup per row range (block-sparse) or per kBlock rows of a problem
+template <int GM, bool BWD, typename T>
+void launch_generic(const GenericParams<T>& prm, const Ranges& rg, int n_ranges, int B, int N, int M, int D, hipStream_t st) {
+    if (n_ranges > 0) hipLaunchKernelGGL((generic_kernel<GM, BWD, true, T>), dim3(n_ranges, 1, 1), dim3(kBlock), 0, st, prm, rg, N, M, D);
+    else hipLaunchKernelGGL((generic_kernel<GM, BWD, false, T>), dim3((N + kBlock - 1) / kBlock, B, 1), dim3(kBlock), 0, st, prm, rg, N, M, D);
 }
 
 // glhip_sinkhorn_iter4: `count` dense reductions in one launch of a multi kernel + one merge launch.  What the three launchers share:
@@ -885,25 +923,9 @@ int softmin_typed(const void* x, const void* y, const float* h, float* out, cons
         if (step.pot || step.prev || step.alpha != 1.f)
             return fail(GLHIP_EUNSUPPORTED, "glhip_sinkhorn_step: no fused kernel for D=%d, p=%d, flags=%d (D > 3: the matrix-core kernels only — "
                                             "p = 2 up to D = 4095, dense p = 1 up to D = 16): use glhip_softmin_fwd", D, p, flags);
-        GenericParams<T> prm;
-        prm.x = static_cast<const T*>(x);
-        prm.y = static_cast<const T*>(y);
-        prm.s = h;
-        prm.out = out;
-        prm.fwd = fwd;
-        prm.g = g;
-        prm.gx = gx;
-        prm.dscale = (p == 1) ? s2 : 0.5f * s2;
-        prm.out_scale = out_scale;
-        prm.gscale = 1.f;
-        prm.clamp2 = 1e-8f;
-        const bool sp = n_ranges > 0;
-        dim3 grid(sp ? n_ranges : (N + kBlock - 1) / kBlock, sp ? 1 : B, 1);
-#define GL_LAUNCH(MODE, SP) \
-    hipLaunchKernelGGL((generic_kernel<MODE, BWD, SP, T>), grid, dim3(kBlock), 0, st, prm, rg, N, M, D)
-        if (p == 2) { if (sp) GL_LAUNCH(GM_SOFTMIN_P2, true); else GL_LAUNCH(GM_SOFTMIN_P2, false); }
-        else        { if (sp) GL_LAUNCH(GM_SOFTMIN_P1, true); else GL_LAUNCH(GM_SOFTMIN_P1, false); }
-#undef GL_LAUNCH
+        const GenericParams<T> prm{static_cast<const T*>(x), static_cast<const T*>(y), h, out, fwd, g, gx, (p == 1) ? s2 : 0.5f * s2, out_scale, 1.f, 1e-8f};
+        if (p == 2) launch_generic<GM_SOFTMIN_P2, BWD, T>(prm, rg, n_ranges, B, N, M, D, st);
+        else launch_generic<GM_SOFTMIN_P1, BWD, T>(prm, rg, n_ranges, B, N, M, D, st);
     }
     return GLHIP_OK;
 }
@@ -942,176 +964,102 @@ void launch_gauss_fwdgrad(const ConvParams<T>& prm, float blur, const Ranges& rg
     launch_wsum<WS_GAUSS_FWDGRAD, D, T, GaussFwdGradMerge<D, T>>(gauss_wsum_params(prm, blur), prm, rg, n_ranges, B, N, M, sc, false, st);
 }
 
-template <bool BWD, typename T>
+// the distance kernels' mode (glhip_dist_x32.h, glhip_dist_xd.h) of a laplacian / energy kernel
+template <int KIND> constexpr int kConvDistMode = KIND == GLHIP_LAPLACIAN ? DM_LAPLACIAN : DM_ENERGY;
+
+// laplacian / energy on the family conv_family chose, GLHIP_FAMILY_GENERIC aside
+template <int KIND, int MODE, typename T>
+void launch_conv_dist_kind(int fam, const ConvParams<T>& prm, const Ranges& rg, int n_ranges, int B, int N, int M, int D, const Scratch& sc,
+                           int flags, hipStream_t st) {
+    constexpr int DM = kConvDistMode<KIND>;
+    const bool grad_family = (flags & GLHIP_FLAG_GRAD_FAMILY) != 0;      // products rounded like MODE 2: |.| = m rsq(m) (glhip_kconv_ops.h)
+    if (fam == GLHIP_FAMILY_VALU) {
+        if constexpr (MODE == 0) {
+            if (grad_family) { launch_conv_d<KIND, 3, T>(prm, rg, n_ranges, B, N, M, D, sc, st); return; }
+        }
+        launch_conv_d<KIND, MODE, T>(prm, rg, n_ranges, B, N, M, D, sc, st);
+    } else if (D <= 3) {      // GLHIP_FAMILY_DIST, block-sparse (use_mfma_dist)
+        if constexpr (MODE == 0) {
+            const DistParams<T> dp = dist_params(prm);
+#define GL_DIST(DD) \
+    if (grad_family) launch_dist<DM, DD, T, ConvOp<KIND, DD, 1, T, 0>, true>(dp, prm, rg, n_ranges, N, M, sc, st); \
+    else launch_dist<DM, DD, T, ConvOp<KIND, DD, 1, T, 0>, false>(dp, prm, rg, n_ranges, N, M, sc, st)
+            GLHIP_D3_DISPATCH(D, GL_DIST)
+#undef GL_DIST
+        } else {
+            launch_dist_grad_d<KIND, MODE == 2 ? DG_FWDGRAD : DG_BWD, T>(prm, rg, n_ranges, N, M, D, sc, st);
+        }
+    } else if constexpr (MODE == 0) {      // GLHIP_FAMILY_DIST, dense, 4 <= D <= 16 (glhip_dist_xd.h)
+        const DistParams<T> dp = dist_params(prm);
+#define GL_XD(DD) launch_dist_xd<DM, DD, T, ConvOp<KIND, DD, 1, T, 0>>(dp, prm, B, N, M, sc, st)
+        GLHIP_XD_DISPATCH(D, GL_XD)
+#undef GL_XD
+    } else if constexpr (MODE == 1) {
+        const DistXdGradParams<T> gp{dist_params(prm), nullptr, prm.g, prm.gx, prm.gscale};
+#define GL_XD(DD) launch_dist_xd_grad<DM, DD, T, ConvOp<KIND, DD, 1, T, 1>>(gp, prm, B, N, M, sc, st)
+        GLHIP_XD_DISPATCH(D, GL_XD)
+#undef GL_XD
+    }
+}
+
+// The body of the three kernel-product entry points: MODE 0 glhip_kernel_conv_fwd (g, gx NULL), 1 glhip_kernel_conv_bwd_x (out NULL),
+// 2 glhip_kernel_conv_fwd_grad (g NULL).  A switch on conv_family; `if constexpr (MODE ...)` where a translation unit must not
+// instantiate the other modes' kernels.
+template <int MODE, typename T>
 int conv_typed(int kind, const void* x, const void* y, const float* v, float* out, const float* g, float* gx,
                int B, int N, int M, int D, float blur, const Ranges& rg, int n_ranges, const Scratch& sc,
                int flags, hipStream_t st) {
-    const int kfam = BWD ? -1 : conv_fwd_family(kind, B, D, flags, n_ranges);      // products: the family decides
-    if (D <= 3) {
-        ConvParams<T> prm;
-        prm.x = static_cast<const T*>(x);
-        prm.y = static_cast<const T*>(y);
-        prm.v = v;
-        prm.out = out;
-        prm.g = g;
-        prm.gx = gx;
-        if (kind == GLHIP_GAUSSIAN) {
-            prm.t = std::sqrt(0.5f * kLog2e) / blur;
-            prm.gscale = -1.0f / (prm.t * blur * blur);
-            prm.clamp2 = 0.f;
-            if (BWD ? (flags & GLHIP_FLAG_NO_MFMA) == 0 : kfam == GLHIP_FAMILY_X32) {
-                const bool x32 = (flags & GLHIP_FLAG_XDL16) == 0;
-#define GL_D(DD) launch_gauss_mfma<DD, BWD, T>(prm, blur, rg, n_ranges, B, N, M, sc, x32, st)
-                GLHIP_D3_DISPATCH(D, GL_D)
+    const int fam = conv_family(kind, MODE, B, D, flags, n_ranges);
+    const ConvParams<T> prm = make_conv_params<T>(kind, x, y, v, out, g, gx, blur);
+    if (fam == GLHIP_FAMILY_GENERIC) {
+        if constexpr (MODE != 2) {      // unscaled coordinates: the scales sit on the distance, the clamp is the reference's own 1e-8
+            GenericParams<T> gp{prm.x, prm.y, v, out, nullptr, g, gx, 1.f, 1.f, -1.0f, 1e-8f};      // energy
+            if (kind == GLHIP_GAUSSIAN) {
+                gp.dscale = 0.5f * kLog2e / (blur * blur);
+                gp.gscale = -1.0f / (blur * blur);
+                launch_generic<GM_GAUSS, MODE == 1, T>(gp, rg, n_ranges, B, N, M, D, st);
+            } else if (kind == GLHIP_LAPLACIAN) {
+                gp.dscale = kLog2e / blur;
+                gp.gscale = -1.0f / blur;
+                gp.clamp2 = 1e-8f * blur * blur;
+                launch_generic<GM_LAPLACE, MODE == 1, T>(gp, rg, n_ranges, B, N, M, D, st);
+            } else {
+                launch_generic<GM_ENERGY, MODE == 1, T>(gp, rg, n_ranges, B, N, M, D, st);
+            }
+        }
+    } else if (fam == GLHIP_EUNSUPPORTED) {      // MODE 2 only; the entry point has said so with a message
+        return fam;
+    } else if (kind == GLHIP_LAPLACIAN) {
+        launch_conv_dist_kind<GLHIP_LAPLACIAN, MODE, T>(fam, prm, rg, n_ranges, B, N, M, D, sc, flags, st);
+    } else if (kind == GLHIP_ENERGY) {
+        launch_conv_dist_kind<GLHIP_ENERGY, MODE, T>(fam, prm, rg, n_ranges, B, N, M, D, sc, flags, st);
+    } else if (fam == GLHIP_FAMILY_VALU) {      // gaussian from here on
+        launch_conv_d<GLHIP_GAUSSIAN, MODE, T>(prm, rg, n_ranges, B, N, M, D, sc, st);
+    } else if (fam == GLHIP_FAMILY_X32) {       // D <= 3 on the matrix cores
+        if constexpr (MODE == 2) {
+#define GL_D(DD) launch_gauss_fwdgrad<DD, T>(prm, blur, rg, n_ranges, B, N, M, sc, st)
+            GLHIP_D3_DISPATCH(D, GL_D)
 #undef GL_D
-            } else {
-                launch_conv_d<GLHIP_GAUSSIAN, BWD, T>(prm, rg, n_ranges, B, N, M, D, sc, st);
-            }
-        } else if (kind == GLHIP_LAPLACIAN) {
-            prm.t = kLog2e / blur;
-            prm.gscale = -1.0f / blur;
-            prm.clamp2 = 1e-8f * kLog2e * kLog2e;   // the reference clamps |x/blur - y/blur|^2
-            if constexpr (!BWD) {
-                if (kfam == GLHIP_FAMILY_DIST) {      // GRAD_FAMILY: |.| = m rsq(m), as the product of glhip_dist_grad_x32.h
-                    const DistParams<T> dp = dist_params(prm);
-                    const bool fam = (flags & GLHIP_FLAG_GRAD_FAMILY) != 0;
-#define GL_DIST(DD) \
-    if (fam) launch_dist<DM_LAPLACIAN, DD, T, ConvOp<GLHIP_LAPLACIAN, DD, 1, T, false>, true>(dp, prm, rg, n_ranges, N, M, sc, st); \
-    else launch_dist<DM_LAPLACIAN, DD, T, ConvOp<GLHIP_LAPLACIAN, DD, 1, T, false>, false>(dp, prm, rg, n_ranges, N, M, sc, st)
-                    GLHIP_D3_DISPATCH(D, GL_DIST)
-#undef GL_DIST
-                    return GLHIP_OK;
-                }
-                if (flags & GLHIP_FLAG_GRAD_FAMILY) {   // rounded like the product-and-gradient kernel (glhip_kconv_ops.h, MODE 3)
-                    launch_conv_d<GLHIP_LAPLACIAN, 3, T>(prm, rg, n_ranges, B, N, M, D, sc, st);
-                    return GLHIP_OK;
-                }
-            } else {
-                if (use_mfma_dist(flags, n_ranges, B, D)) {
-                    launch_dist_grad_d<GLHIP_LAPLACIAN, DG_BWD, T>(prm, rg, n_ranges, N, M, D, sc, st);
-                    return GLHIP_OK;
-                }
-            }
-            launch_conv_d<GLHIP_LAPLACIAN, BWD, T>(prm, rg, n_ranges, B, N, M, D, sc, st);
         } else {
-            prm.t = 1.0f;
-            prm.gscale = -1.0f;
-            prm.clamp2 = 1e-8f;
-            if constexpr (!BWD) {
-                if (kfam == GLHIP_FAMILY_DIST) {
-                    const DistParams<T> dp = dist_params(prm);
-                    const bool fam = (flags & GLHIP_FLAG_GRAD_FAMILY) != 0;
-#define GL_DIST(DD) \
-    if (fam) launch_dist<DM_ENERGY, DD, T, ConvOp<GLHIP_ENERGY, DD, 1, T, false>, true>(dp, prm, rg, n_ranges, N, M, sc, st); \
-    else launch_dist<DM_ENERGY, DD, T, ConvOp<GLHIP_ENERGY, DD, 1, T, false>, false>(dp, prm, rg, n_ranges, N, M, sc, st)
-                    GLHIP_D3_DISPATCH(D, GL_DIST)
-#undef GL_DIST
-                    return GLHIP_OK;
-                }
-                if (flags & GLHIP_FLAG_GRAD_FAMILY) {   // rounded like the product-and-gradient kernel (glhip_kconv_ops.h, MODE 3)
-                    launch_conv_d<GLHIP_ENERGY, 3, T>(prm, rg, n_ranges, B, N, M, D, sc, st);
-                    return GLHIP_OK;
-                }
-            } else {
-                if (use_mfma_dist(flags, n_ranges, B, D)) {
-                    launch_dist_grad_d<GLHIP_ENERGY, DG_BWD, T>(prm, rg, n_ranges, N, M, D, sc, st);
-                    return GLHIP_OK;
-                }
-            }
-            launch_conv_d<GLHIP_ENERGY, BWD, T>(prm, rg, n_ranges, B, N, M, D, sc, st);
+            const bool x32 = (flags & GLHIP_FLAG_XDL16) == 0;
+#define GL_D(DD) launch_gauss_mfma<DD, MODE == 1, T>(prm, blur, rg, n_ranges, B, N, M, sc, x32, st)
+            GLHIP_D3_DISPATCH(D, GL_D)
+#undef GL_D
         }
-    } else {
-        if constexpr (!BWD) {
-            if (kind != GLHIP_GAUSSIAN && kfam == GLHIP_FAMILY_DIST) {   // laplacian / energy, dense, D <= 16: distances on the matrix cores
-                const bool lap = kind == GLHIP_LAPLACIAN;
-                const float t = lap ? kLog2e / blur : 1.0f;
-                ConvParams<T> mprm;
-                mprm.x = static_cast<const T*>(x); mprm.y = static_cast<const T*>(y); mprm.v = v; mprm.out = out; mprm.g = nullptr; mprm.gx = nullptr;
-                mprm.t = t; mprm.gscale = 0.f; mprm.clamp2 = 1e-8f * (lap ? kLog2e * kLog2e : 1.f);
-                const DistParams<T> dp = dist_params(mprm);
-#define GL_XD(DD) \
-    if (lap) launch_dist_xd<DM_LAPLACIAN, DD, T, ConvOp<GLHIP_LAPLACIAN, DD, 1, T, 0>>(dp, mprm, B, N, M, sc, st); \
-    else launch_dist_xd<DM_ENERGY, DD, T, ConvOp<GLHIP_ENERGY, DD, 1, T, 0>>(dp, mprm, B, N, M, sc, st)
-                GLHIP_XD_DISPATCH(D, GL_XD)
-#undef GL_XD
-                return GLHIP_OK;
-            }
-            const int gfam = kind == GLHIP_GAUSSIAN ? kfam : GLHIP_FAMILY_GENERIC;
-            if (gfam == GLHIP_FAMILY_XK) {   // 17 <= D <= 4095: matrix cores, K-chunked (glhip_softmin_xk.h); exponent and operands as below
-                const SoftminParams<T> prm = make_softmin_params<T>(x, y, v, out, blur * blur, 2, nullptr, nullptr, 1.f, 0.f);
-                ConvParams<T> mprm;
-                mprm.x = prm.x; mprm.y = prm.y; mprm.v = v; mprm.out = out; mprm.g = nullptr; mprm.gx = nullptr;
-                mprm.t = 1.f; mprm.gscale = 0.f; mprm.clamp2 = 0.f;
-                launch_xk<XD_GAUSS, T, ConvOp<GLHIP_GAUSSIAN, 1, 1, T, 0>>(prm, mprm, rg, n_ranges, B, N, M, D, sc, st);
-                return GLHIP_OK;
-            }
-            if (gfam == GLHIP_FAMILY_XD) {   // 4 <= D <= 16: matrix cores
-                // the gaussian exponent -|x-y|^2 / (2 blur^2) is the soft-min's with eps = blur^2 and h = 0; `h` carries v
-                const SoftminParams<T> prm = make_softmin_params<T>(x, y, v, out, blur * blur, 2, nullptr, nullptr, 1.f, 0.f);
-                ConvParams<T> mprm;
-                mprm.x = prm.x; mprm.y = prm.y; mprm.v = v; mprm.out = out; mprm.g = nullptr; mprm.gx = nullptr;
-                mprm.t = 1.f; mprm.gscale = 0.f; mprm.clamp2 = 0.f;
-#define GL_XD(DD) launch_xd<XD_GAUSS, DD, T, ConvOp<GLHIP_GAUSSIAN, DD, 1, T, 0>>(prm, mprm, rg, n_ranges, B, N, M, sc, st)
-                GLHIP_XD_DISPATCH(D, GL_XD)
-#undef GL_XD
-                return GLHIP_OK;
-            }
+    } else if constexpr (MODE == 0) {           // 4 <= D <= 16 (glhip_softmin_xd.h) and 17 <= D <= 4095 (K-chunked, glhip_softmin_xk.h)
+        // the gaussian exponent -|x-y|^2 / (2 blur^2) is the soft-min's with eps = blur^2 and h = 0; `h` carries v; the merge takes prm
+        const SoftminParams<T> sprm = make_softmin_params<T>(x, y, v, out, blur * blur, 2, nullptr, nullptr, 1.f, 0.f);
+        if (fam == GLHIP_FAMILY_XK) {
+            launch_xk<XD_GAUSS, T, ConvOp<GLHIP_GAUSSIAN, 1, 1, T, 0>>(sprm, prm, rg, n_ranges, B, N, M, D, sc, st);
         } else {
-            if (kind != GLHIP_GAUSSIAN && D <= kXdMaxD && n_ranges == 0 && !(flags & GLHIP_FLAG_NO_MFMA)) {   // laplacian / energy gradients, dense
-                const bool lap = kind == GLHIP_LAPLACIAN;
-                const float t = lap ? kLog2e / blur : 1.0f;
-                ConvParams<T> mprm;
-                mprm.x = static_cast<const T*>(x); mprm.y = static_cast<const T*>(y); mprm.v = v; mprm.out = nullptr; mprm.g = g; mprm.gx = gx;
-                mprm.t = t; mprm.gscale = lap ? -1.0f / blur : -1.0f; mprm.clamp2 = 1e-8f * (lap ? kLog2e * kLog2e : 1.f);
-                const DistXdGradParams<T> gp{dist_params(mprm), nullptr, g, gx, mprm.gscale};
-#define GL_XD(DD) \
-    if (lap) launch_dist_xd_grad<DM_LAPLACIAN, DD, T, ConvOp<GLHIP_LAPLACIAN, DD, 1, T, 1>>(gp, mprm, B, N, M, sc, st); \
-    else launch_dist_xd_grad<DM_ENERGY, DD, T, ConvOp<GLHIP_ENERGY, DD, 1, T, 1>>(gp, mprm, B, N, M, sc, st)
-                GLHIP_XD_DISPATCH(D, GL_XD)
+#define GL_XD(DD) launch_xd<XD_GAUSS, DD, T, ConvOp<GLHIP_GAUSSIAN, DD, 1, T, 0>>(sprm, prm, rg, n_ranges, B, N, M, sc, st)
+            GLHIP_XD_DISPATCH(D, GL_XD)
 #undef GL_XD
-                return GLHIP_OK;
-            }
-            if (kind == GLHIP_GAUSSIAN && D <= kXdMaxD && !(flags & GLHIP_FLAG_NO_MFMA)) {   // gaussian gradient, 4 <= D <= 16
-                ConvParams<T> prm;
-                prm.x = static_cast<const T*>(x); prm.y = static_cast<const T*>(y); prm.v = v; prm.out = out; prm.g = g; prm.gx = gx;
-                prm.t = std::sqrt(0.5f * kLog2e) / blur;
-                prm.gscale = -1.0f / (prm.t * blur * blur);
-                prm.clamp2 = 0.f;
-#define GL_XD(DD) launch_gauss_grad_t32<DD, false, T>(prm, blur, rg, n_ranges, B, N, M, sc, st)
-                GLHIP_XD_DISPATCH(D, GL_XD)
+        }
+    } else {                                    // 4 <= D <= 16: the transposed 32x32x16 kernel (glhip_wsum_t32.h)
+#define GL_XD(DD) launch_gauss_grad_t32<DD, MODE == 2, T>(prm, blur, rg, n_ranges, B, N, M, sc, st)
+        GLHIP_XD_DISPATCH(D, GL_XD)
 #undef GL_XD
-                return GLHIP_OK;
-            }
-        }
-        GenericParams<T> prm;
-        prm.x = static_cast<const T*>(x);
-        prm.y = static_cast<const T*>(y);
-        prm.s = v;
-        prm.out = out;
-        prm.fwd = nullptr;
-        prm.g = g;
-        prm.gx = gx;
-        prm.out_scale = 1.f;
-        prm.clamp2 = 1e-8f;
-        const bool sp = n_ranges > 0;
-        dim3 grid(sp ? n_ranges : (N + kBlock - 1) / kBlock, sp ? 1 : B, 1);
-#define GL_LAUNCH(MODE, SP) \
-    hipLaunchKernelGGL((generic_kernel<MODE, BWD, SP, T>), grid, dim3(kBlock), 0, st, prm, rg, N, M, D)
-        if (kind == GLHIP_GAUSSIAN) {
-            prm.dscale = 0.5f * kLog2e / (blur * blur);
-            prm.gscale = -1.0f / (blur * blur);
-            if (sp) GL_LAUNCH(GM_GAUSS, true); else GL_LAUNCH(GM_GAUSS, false);
-        } else if (kind == GLHIP_LAPLACIAN) {
-            prm.dscale = kLog2e / blur;
-            prm.gscale = -1.0f / blur;
-            prm.clamp2 = 1e-8f * blur * blur;
-            if (sp) GL_LAUNCH(GM_LAPLACE, true); else GL_LAUNCH(GM_LAPLACE, false);
-        } else {
-            prm.dscale = 1.f;
-            prm.gscale = -1.0f;
-            if (sp) GL_LAUNCH(GM_ENERGY, true); else GL_LAUNCH(GM_ENERGY, false);
-        }
-#undef GL_LAUNCH
     }
     return GLHIP_OK;
 }
