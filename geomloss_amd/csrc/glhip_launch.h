@@ -26,6 +26,7 @@
 #include "glhip_softmin_xk.h"
 #include "glhip_wsum_t32.h"
 #include "glhip_dist_xd.h"
+#include "glhip_dist_xk.h"
 
 using namespace glhip;
 
@@ -458,6 +459,20 @@ void launch_xk(const SoftminParams<T>& prm, const typename MergeOp::Params& mprm
     else launch_xk_l<MODE, T, MergeOp, XL_BF16X3>(prm, mprm, rg, n_ranges, B, N, M, D, sc, st);
 }
 
+// ... and the distance reductions of the same dimensions (glhip_dist_xk.h, GLHIP_FLAG_XK_DIST): p = 1 soft-min / fused half-step, laplacian
+// and energy products, dense and batched launches, bf16 x 3 only.  Splits, XCD rule and merge as launch_xk_l.
+template <int MODE, typename T, class MergeOp>
+void launch_xk_dist(const DistParams<T>& prm, const typename MergeOp::Params& mprm, int B, int N, int M, int D, const Scratch& sc,
+                    hipStream_t st) {
+    static_assert(MergeOp::kPartial == (MODE == DM_SOFTMIN_P1 ? 2 : 1), "partial formats differ");
+    SplitLaunch sl(Ranges{nullptr, nullptr, nullptr, nullptr}, 0, B, N, M, kXkRows, MergeOp::kPartial, sc.ws, sc.bytes, sc.cb, st);
+    sl.sp.n_splits = (sc.allow_split && sl.fit >= 2) ? choose_splits(sl.row_blocks, M, 0, sl.fit) : 1;
+    if (sl.xcd_eligible(sc.allow_split)) sl.take_xcd(xcd_splits(sl.row_blocks, M, kXkSlots, sl.fit));   // one column split per XCD at a time
+    sl.launch_dense<MergeOp>([&](auto, dim3 grid, const Ranges&) {
+        hipLaunchKernelGGL((xk_dist_kernel<MODE, T>), grid, dim3(kXkThreads), 0, st, prm, N, M, D, sl.sp);
+    }, mprm, st);
+}
+
 // (plan application, the D > 16 gradients and argmin: glhip_launch_plan.h)
 
 // Which matrix-core forward family serves a p = 2 soft-min / half-step / gaussian product in dimension D > 3 under `flags`
@@ -466,6 +481,13 @@ inline int highd_p2_family(int D, int flags) {
     if (flags & (GLHIP_FLAG_NO_MFMA | GLHIP_FLAG_DIRECT)) return GLHIP_FAMILY_GENERIC;
     if (D <= kXdMaxD) return GLHIP_FAMILY_XD;
     return D <= kXkMaxD ? GLHIP_FAMILY_XK : GLHIP_FAMILY_GENERIC;
+}
+
+// ... and a distance reduction (p = 1 soft-min / half-step, laplacian / energy product) in dimension D > 3: glhip_dist_xd.h up to D = 16,
+// glhip_dist_xk.h for 17 <= D <= 4095 on the caller's word (GLHIP_FLAG_XK_DIST); dense launches only
+inline bool highd_dist_applies(int B, int D, int flags, int n_ranges) {
+    if (n_ranges != 0 || (flags & (GLHIP_FLAG_NO_MFMA | GLHIP_FLAG_DIRECT))) return false;
+    return D <= kXdMaxD || ((flags & GLHIP_FLAG_XK_DIST) && D <= kXkMaxD && B <= 65535);
 }
 
 // distance reductions for 4 <= D <= 16, dense launches (glhip_dist_xd.h): soft-min p = 1 / fused half-step, laplacian and energy products
@@ -565,7 +587,7 @@ inline int softmin_fwd_family(int B, long N, long M, int D, int p, int flags, in
             return GLHIP_FAMILY_XD;
         return (p == 2 && !direct && mfma) ? GLHIP_FAMILY_X32 : GLHIP_FAMILY_VALU;
     }
-    if (p == 1) return (D <= kXdMaxD && n_ranges == 0 && !(flags & (GLHIP_FLAG_NO_MFMA | GLHIP_FLAG_DIRECT))) ? GLHIP_FAMILY_DIST : GLHIP_FAMILY_GENERIC;
+    if (p == 1) return highd_dist_applies(B, D, flags, n_ranges) ? GLHIP_FAMILY_DIST : GLHIP_FAMILY_GENERIC;
     return highd_p2_family(D, flags);
 }
 
@@ -582,8 +604,11 @@ inline int conv_family(int kind, int mode, int B, int D, int flags, int n_ranges
         return use_mfma_dist(flags, n_ranges, B, D) ? GLHIP_FAMILY_DIST : GLHIP_FAMILY_VALU;
     }
     const int none = mode == 2 ? GLHIP_EUNSUPPORTED : GLHIP_FAMILY_GENERIC;
-    if (kind != GLHIP_GAUSSIAN)      // laplacian / energy: distances on the matrix cores, dense launches of D <= 16
-        return (mode != 2 && D <= kXdMaxD && n_ranges == 0 && mfma) ? GLHIP_FAMILY_DIST : none;
+    if (kind != GLHIP_GAUSSIAN) {    // laplacian / energy: distances on the matrix cores, dense launches of D <= 16 ...
+        if (mode != 2 && D <= kXdMaxD && n_ranges == 0 && mfma) return GLHIP_FAMILY_DIST;
+        // ... and the product of 17 <= D <= 4095 under GLHIP_FLAG_XK_DIST (glhip_dist_xk.h); its gradients stay generic
+        return (mode == 0 && D > kXdMaxD && highd_dist_applies(B, D, flags, n_ranges)) ? GLHIP_FAMILY_DIST : none;
+    }
     if (mode == 0) return highd_p2_family(D, flags & ~GLHIP_FLAG_DIRECT);      // (_DIRECT means nothing to a kernel product)
     return (D <= kXdMaxD && mfma) ? GLHIP_FAMILY_XD : none;
 }
@@ -880,9 +905,13 @@ int softmin_typed(const void* x, const void* y, const float* h, float* out, cons
 #undef GL_D
     } else {
         if constexpr (!BWD) {
-            if (fam == GLHIP_FAMILY_DIST) {   // p = 1, D <= 16, dense: distances on the matrix cores
+            if (fam == GLHIP_FAMILY_DIST) {   // p = 1, dense: distances on the matrix cores
                 const SoftminParams<T> mprm = make_softmin_params<T>(x, y, h, out, eps, 1, step.pot, step.prev, step.alpha, step.beta);
                 const DistParams<T> dp = dist_params(mprm);
+                if (D > kXdMaxD) {            // 17 <= D <= 4095, GLHIP_FLAG_XK_DIST: K-chunked (glhip_dist_xk.h)
+                    launch_xk_dist<DM_SOFTMIN_P1, T, SoftminFwdOp<1, 1, true, 1, T>>(dp, mprm, B, N, M, D, sc, st);
+                    return GLHIP_OK;
+                }
 #define GL_XD(DD) launch_dist_xd<DM_SOFTMIN_P1, DD, T, SoftminFwdOp<DD, 1, true, 1, T>>(dp, mprm, B, N, M, sc, st)
                 GLHIP_XD_DISPATCH(D, GL_XD)
 #undef GL_XD
@@ -922,7 +951,7 @@ int softmin_typed(const void* x, const void* y, const float* h, float* out, cons
         }
         if (step.pot || step.prev || step.alpha != 1.f)
             return fail(GLHIP_EUNSUPPORTED, "glhip_sinkhorn_step: no fused kernel for D=%d, p=%d, flags=%d (D > 3: the matrix-core kernels only — "
-                                            "p = 2 up to D = 4095, dense p = 1 up to D = 16): use glhip_softmin_fwd", D, p, flags);
+                                            "p = 2 up to D = 4095, dense p = 1 up to D = 16, and up to D = 4095 under GLHIP_FLAG_XK_DIST): use glhip_softmin_fwd", D, p, flags);
         const GenericParams<T> prm{static_cast<const T*>(x), static_cast<const T*>(y), h, out, fwd, g, gx, (p == 1) ? s2 : 0.5f * s2, out_scale, 1.f, 1e-8f};
         if (p == 2) launch_generic<GM_SOFTMIN_P2, BWD, T>(prm, rg, n_ranges, B, N, M, D, st);
         else launch_generic<GM_SOFTMIN_P1, BWD, T>(prm, rg, n_ranges, B, N, M, D, st);
@@ -989,8 +1018,12 @@ void launch_conv_dist_kind(int fam, const ConvParams<T>& prm, const Ranges& rg, 
         } else {
             launch_dist_grad_d<KIND, MODE == 2 ? DG_FWDGRAD : DG_BWD, T>(prm, rg, n_ranges, N, M, D, sc, st);
         }
-    } else if constexpr (MODE == 0) {      // GLHIP_FAMILY_DIST, dense, 4 <= D <= 16 (glhip_dist_xd.h)
+    } else if constexpr (MODE == 0) {      // GLHIP_FAMILY_DIST, dense: 4 <= D <= 16 (glhip_dist_xd.h), beyond K-chunked (glhip_dist_xk.h)
         const DistParams<T> dp = dist_params(prm);
+        if (D > kXdMaxD) {
+            launch_xk_dist<DM, T, ConvOp<KIND, 1, 1, T, 0>>(dp, prm, B, N, M, D, sc, st);
+            return;
+        }
 #define GL_XD(DD) launch_dist_xd<DM, DD, T, ConvOp<KIND, DD, 1, T, 0>>(dp, prm, B, N, M, sc, st)
         GLHIP_XD_DISPATCH(D, GL_XD)
 #undef GL_XD

@@ -26,11 +26,14 @@ FLAG_F16X2 = 256                # exponents from two f16 pieces per coordinate; 
 FLAG_NO_SORT = 512              # big dense distance reductions: do not voxel-sort the clouds inside the library (glhip.h)
 FLAG_XK_GRAD = 1024             # glhip_softmin_bwd_x: the p = 2 gradient of 17 <= D <= 4095 on the matrix cores (glhip_softmin_grad_xk.h);
                                 # glhip_kernel_conv_bwd_x / _fwd_grad: the gaussian gradient of those dimensions (glhip_gauss_grad_xk.h)
+FLAG_XK_DIST = 2048             # p = 1 soft-min / half-step, laplacian and energy products of 17 <= D <= 4095, dense launches: squared distances
+                                # from the K-chunked matrix-core chain (glhip_dist_xk.h); opt-in, the gradients stay on the generic kernel
 FLAG_GRAD_FAMILY = FLAG_XDL16   # kernel products rounded like the product-and-gradient kernel of the same kind (glhip.h)
 XD_MAX_DIM = 16                 # the fused four-softmin iteration / annealing / extrapolation, the one-pass value + gradient and the matrix-core
                                 # gradients stop at this dimension (glhip_softmin_xd.h, glhip_wsum_t32.h)
 MFMA_FWD_MAX_DIM = 4095         # p = 2 soft-min forward / half-step and gaussian product run on the matrix cores up to this dimension
                                 # (17 ... 4095: the K-chunked kernel of glhip_softmin_xk.h; kept in step with the library by tests/test_anyd_kernels_gpu.py)
+DIST_XK_MAX_DIM = 4095          # ... and under FLAG_XK_DIST the p = 1 soft-min / half-step and the laplacian / energy products too (glhip_dist_xk.h)
 ARGMIN_MAX_DIM = 4095           # argmin takes p = 2 clouds of every dimension up to this one (glhip_argmin_xk.h)
 PLAN_MAX_DIM = 4095             # plan_apply_nd applies p = 2 transport plans to features up to this dimension (17 ... 4095: glhip_plan_apply_xk.h)
 # kernel families reported by softmin_fwd_family (GLHIP_FAMILY_* of glhip.h)
@@ -1276,10 +1279,16 @@ def fused_step_applies(D, p=2, flags=0, sparse=False):
 def half_step_applies(D, p=2, flags=0, sparse=False):
     """Whether :func:`sinkhorn_step` runs as ONE ``glhip_sinkhorn_step`` launch: wherever :func:`fused_step_applies` (the kernels of
     D <= 16), and for p = 2 clouds of 17 <= D <= MFMA_FWD_MAX_DIM on the K-chunked matrix-core kernel (glhip_softmin_xk.h), which
-    GLHIP_FLAG_NO_MFMA / GLHIP_FLAG_DIRECT switch off like the others."""
+    GLHIP_FLAG_NO_MFMA / GLHIP_FLAG_DIRECT switch off like the others; under ``FLAG_XK_DIST`` also for p = 1 clouds of
+    17 <= D <= DIST_XK_MAX_DIM on DENSE launches (glhip_dist_xk.h), with the same two flags switching it off."""
     if fused_step_applies(D, p, flags, sparse):
         return True
-    return p == 2 and XD_MAX_DIM < D <= MFMA_FWD_MAX_DIM and not ((int(flags) | ENV_FLAGS) & (FLAG_NO_MFMA | FLAG_DIRECT))
+    flags = int(flags) | ENV_FLAGS
+    if flags & (FLAG_NO_MFMA | FLAG_DIRECT):
+        return False
+    if p == 1:
+        return bool(flags & FLAG_XK_DIST) and not sparse and XD_MAX_DIM < D <= DIST_XK_MAX_DIM
+    return p == 2 and XD_MAX_DIM < D <= MFMA_FWD_MAX_DIM
 
 
 def softmin_fwd_family(B, N, M, D, p=2, dtype=F32, flags=0, n_ranges=0):
@@ -1303,7 +1312,7 @@ def kernel_conv_fwd_family(kind, B, N, M, D, dtype=F32, flags=0, n_ranges=0):
 def sinkhorn_step(eps, x, y, logw, pot, prev, damping, p=2, ranges=None, flags=0):
     """One non-differentiable half-step of the Sinkhorn loop on the GPU: (prev + damping * softmin(eps, C, logw + pot/eps)) / 2,
     or damping * softmin(...) when prev is None — ONE launch where :func:`half_step_applies`, the soft-min kernel followed by
-    torch arithmetic elsewhere (p = 1 in D > 16, D > 4095, block-sparse p = 1 in D > 3, D > 3 under GLHIP_FLAG_NO_MFMA / GLHIP_FLAG_DIRECT).
+    torch arithmetic elsewhere (p = 1 in D > 16 without ``FLAG_XK_DIST``, D > 4095, block-sparse p = 1 in D > 3, D > 3 under GLHIP_FLAG_NO_MFMA / GLHIP_FLAG_DIRECT).
 
     x: (N,D)|(B,N,D), y: (M,D)|(B,M,D); logw, pot: (M,)|(B,M) (pot may be None); prev: (N,)|(B,N) or None.
     Returns fp32 (N,)|(B,N).  Used by the drivers inside the no-grad part of ``sinkhorn_loop``."""

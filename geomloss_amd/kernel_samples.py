@@ -195,6 +195,17 @@ def _grad_flags(name, pts):
     return hip.FLAG_XK_GRAD if (name == "gaussian" and _XK_GRAD and pts.shape[-1] > hip.XD_MAX_DIM) else 0
 
 
+# matrix-core laplacian / energy PRODUCT of 17 <= D <= 4095 (glhip_dist_xk.h); the knob of the p = 1 soft-min of those dimensions
+# (sinkhorn_samples._XK_DIST) covers this one too.  Their gradients stay on the one-thread-per-row kernel.
+_XK_DIST = os.environ.get("GEOMLOSS_HIP_XK_DIST", "1") != "0"
+
+
+def _fwd_flags(name, pts):
+    """FLAG_XK_DIST for the forward products of the laplacian / energy kernels beyond the compiled dimensions (the library ignores the
+    flag where it does not apply: the gradients, D > 4095, float64).  D <= 16 keeps its default flags."""
+    return hip.FLAG_XK_DIST if (name in ("laplacian", "energy") and _XK_DIST and pts.shape[-1] > hip.XD_MAX_DIM) else 0
+
+
 class _UnionNorm(torch.autograd.Function):
     """1/2 <w, K_zz w> on the union cloud z = (x, y), w = (α, -β), as ONE autograd node.
 
@@ -211,7 +222,7 @@ class _UnionNorm(torch.autograd.Function):
         batch = x.dim() > 2
         z = torch.cat((x, y.to(x.dtype)), dim=-2)
         w = torch.cat((α.to(_weights_dtype(x)), -β.to(_weights_dtype(x))), dim=-1)
-        fl = _grad_flags(name, x)
+        fl = _grad_flags(name, x) | _fwd_flags(name, x)
         U_x, unit_x = hip.kernel_conv_with_unit(name, x, z, w, blur, ctx.needs_input_grad[3], fl)
         U_y, unit_y = hip.kernel_conv_with_unit(name, y, z, w, blur, ctx.needs_input_grad[5], fl)
         ctx.name, ctx.blur, ctx.units = name, blur, (unit_x, unit_y)
@@ -288,15 +299,17 @@ def _kernel_loss_union(α, x, β, y, blur, name, potentials):
     if not potentials:
         if _takes_no_gradient(α, x, β, y):
             with torch.no_grad():
-                U_x, U_y = hip.kernel_conv(name, x, z, w, blur), hip.kernel_conv(name, y, z, w, blur)
+                fl = _fwd_flags(name, x)
+                U_x, U_y = hip.kernel_conv(name, x, z, w, blur, flags=fl), hip.kernel_conv(name, y, z, w, blur, flags=fl)
                 return 0.5 * scal_sum(α, U_x, β, -U_y, batch=batch)
         return _UnionNorm.apply(name, 1.0 if blur is None else float(blur), α, x, β, y)
 
     # potentials (``:139-141``) that nobody differentiates (kernel_loss sends the others to the four products of the reference):
     # rows of x, rows of y of the same signed product
     with torch.no_grad():
-        U_x = hip.kernel_conv(name, x, z, w, blur)      # (k*α - k*β)(x_i)
-        U_y = hip.kernel_conv(name, y, z, w, blur)      # (k*α - k*β)(y_j)
+        fl = _fwd_flags(name, x)
+        U_x = hip.kernel_conv(name, x, z, w, blur, flags=fl)      # (k*α - k*β)(x_i)
+        U_y = hip.kernel_conv(name, y, z, w, blur, flags=fl)      # (k*α - k*β)(y_j)
     return U_x, -U_y
 
 

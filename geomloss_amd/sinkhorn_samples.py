@@ -142,6 +142,9 @@ class _HipSoftmin:
         # FLAG_XK_GRAD: the backward of dense p = 2 soft-mins of 17 <= D <= 4095 on the matrix cores (glhip_softmin_grad_xk.h); the
         # library ignores it everywhere else — every forward launch, D <= 16, the block-sparse fine level of the two-scale backend
         xk = hip.FLAG_XK_GRAD if (self.p == 2 and _XK_GRAD) else 0
+        # FLAG_XK_DIST: the forward / fused half-step of dense p = 1 soft-mins of 17 <= D <= 4095 with the distances on the matrix cores
+        # (glhip_dist_xk.h); ignored likewise everywhere else — D <= 16, block-sparse levels, the backward, the fused iterations
+        xk |= hip.FLAG_XK_DIST if (self.p == 1 and _XK_DIST) else 0
         return xk | (hip.FLAG_F16X2 if eps >= self.h2_min_eps else 0)
 
     def __call__(self, eps, C, h):
@@ -152,7 +155,7 @@ class _HipSoftmin:
     def step(self, eps, C, log_w, pot, damping, prev):
         x, y = C[0], C[1]
         ranges = C[4] if self.multiscale else None
-        if not hip.half_step_applies(x.shape[-1], self.p, 0, ranges is not None):  # no fused kernel on the generic-dimension path (incl. D > 3 under NO_MFMA / DIRECT)
+        if not hip.half_step_applies(x.shape[-1], self.p, self._flags(eps), ranges is not None):  # no fused kernel on the generic-dimension path (incl. D > 3 under NO_MFMA / DIRECT)
             ft = damping * self(eps, C, log_w if pot is None else log_w + pot / eps)
             return ft if prev is None else 0.5 * (prev + ft)
         flat = (lambda t: None if t is None else t.reshape(-1)) if x.dim() == 2 else (lambda t: t)
@@ -249,6 +252,7 @@ _graph_mode = os.environ.get("GEOMLOSS_HIP_GRAPH", "0") == "1"
 _COARSE_F64_MIN_PAIRS = float(os.environ.get("GEOMLOSS_HIP_COARSE_F64_MIN_PAIRS", "1e11"))   # two-scale losses: float64 coarse level from here on
 _F16X2 = os.environ.get("GEOMLOSS_HIP_F16X2", "1") != "0"      # f16 x 2 exponents where the temperature allows (_HipSoftmin.set_range)
 _XK_GRAD = os.environ.get("GEOMLOSS_HIP_XK_GRAD", "1") != "0"  # matrix-core soft-min gradient of 17 <= D <= 4095 (_HipSoftmin._flags)
+_XK_DIST = os.environ.get("GEOMLOSS_HIP_XK_DIST", "1") != "0"  # matrix-core p = 1 soft-min / half-step of 17 <= D <= 4095 (_HipSoftmin._flags)
 _anneal_in_library = True   # the iterations of a level queued by one library call (tests switch it off to compare with one call per iteration)
 _fuse_iterations = True   # one launch per Sinkhorn iteration (small / mid-size clouds); set_iteration_fusion(False): four half-steps
 # ... up to this many pairs per soft-min; bigger problems fill the GPU with one soft-min per launch (pre-packed columns, XCD grids)

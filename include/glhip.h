@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 130 /* 0.1.30 */
+#define GLHIP_VERSION 131 /* 0.1.31 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
@@ -86,7 +86,7 @@ extern "C" {
                                   exponent term (log2(e) h_j, |x - y|^2 / (2 eps ln 2)) must stay below ~2.6e5 in magnitude, i.e. roughly
                                   (cloud diameter)^2 / eps < 3e5; beyond that f16 overflows and the results are inf / nan.  The bound is on the
                                   exponents, so it is the same in every dimension (diameter^2 grows like D on a unit cube).  Ignored by kernels
-                                  without that layout (p = 1, laplacian, energy, the gradients of D > 16 other than GLHIP_FLAG_XK_GRAD, D > 4095, float64). */
+                                  without that layout (p = 1, laplacian, energy — GLHIP_FLAG_XK_DIST included: bf16 x 3 only —, the gradients of D > 16 other than GLHIP_FLAG_XK_GRAD, D > 4095, float64). */
 
 #define GLHIP_FLAG_XK_GRAD 1024 /* glhip_softmin_bwd_x (version 126) and, gaussian kind, glhip_kernel_conv_bwd_x / glhip_kernel_conv_fwd_grad
                                   (version 130, below).  glhip_softmin_bwd_x: the gradient of p == 2, 17 <= D <= 4095, dense launches (n_ranges == 0),
@@ -100,6 +100,19 @@ extern "C" {
                                   conditions runs xk_plan_kernel on XkGaussGradParams (csrc/glhip_gauss_grad_xk.h);
                                   glhip_kernel_conv_grad_uses_xk is the predicate.  Laplacian / energy, D <= 16, D > 4095, block-sparse ranges,
                                   GLHIP_FLAG_NO_MFMA / _DIRECT and glhip_kernel_conv_fwd ignore the flag, bit for bit. */
+
+#define GLHIP_FLAG_XK_DIST 2048 /* version 131.  glhip_softmin_fwd / glhip_sinkhorn_step with p == 1 and glhip_kernel_conv_fwd of the laplacian /
+                                  energy kinds: 17 <= D <= 4095, dense launches (n_ranges == 0), B <= 65535, without GLHIP_FLAG_NO_MFMA / _DIRECT
+                                  run xk_dist_kernel (csrc/glhip_dist_xk.h): the squared distances from the K-chunked matrix-core chain of
+                                  glhip_softmin_xk.h (bf16 x 3 pieces only; GLHIP_FLAG_F16X2 is ignored), centred on the first row of each block of 256
+                                  rows, near pairs (d^2 < max(guard |xs_i|^2, 4 clamp^2), GLHIP_DIST_GUARD) re-evaluated on explicit differences.
+                                  The family predicates report GLHIP_FAMILY_DIST there, and glhip_sinkhorn_step with p == 1 runs as ONE fused
+                                  launch instead of returning GLHIP_EUNSUPPORTED.  Opt-in: without the flag every launch is the one version 130
+                                  makes, bit for bit (the one-thread-per-row kernel of glhip_generic.h).  Ignored, bit for bit, by p == 2, the
+                                  gaussian kind, D <= 16, D > 4095, block-sparse ranges, the gradients (glhip_kernel_conv_bwd_x /
+                                  glhip_kernel_conv_fwd_grad / glhip_softmin_bwd_x), the float64 symbols and glhip_sinkhorn_iter4 / _anneal /
+                                  _extrapolate4.  Workspace: glhip_workspace_bytes as it is (2 floats per row and split for D > 16 is what the
+                                  soft-min takes; the products take 1). */
 
 #define GLHIP_FLAG_NO_SORT 512 /* p = 1 soft-min / half-step, laplacian and energy products: big dense launches (B = 1, D <= 3, N >= 65536,
                                   N M >= 5e8, a workspace of glhip_workspace_bytes) sort both clouds into the workspace themselves — voxel sort along a
@@ -154,10 +167,11 @@ extern "C" {
 #define GLHIP_FAMILY_X32 1     /* p = 2, D <= 3: matrix cores, glhip_softmin_x32.h */
 #define GLHIP_FAMILY_XD 2      /* p = 2, 4 <= D <= 16 (and big dense GLHIP_FLAG_F16X2 launches of D <= 3): matrix cores, glhip_softmin_xd.h */
 #define GLHIP_FAMILY_XK 3      /* p = 2, 17 <= D <= 4095: matrix cores, K-chunked, D a run-time argument, glhip_softmin_xk.h */
-#define GLHIP_FAMILY_DIST 4    /* p = 1 with the squared distances on the matrix cores: glhip_dist_x32.h (block-sparse, D <= 3,
-                                  GLHIP_FLAG_MFMA_DIST) / glhip_dist_xd.h (dense, 4 <= D <= 16) */
-#define GLHIP_FAMILY_GENERIC 5 /* D > 3 on the one-thread-per-row kernel of glhip_generic.h: p = 1 block-sparse or D > 16, p = 2 with D > 4095
-                                  or under GLHIP_FLAG_NO_MFMA / _DIRECT */
+#define GLHIP_FAMILY_DIST 4    /* p = 1 / laplacian / energy with the squared distances on the matrix cores: glhip_dist_x32.h (block-sparse, D <= 3,
+                                  GLHIP_FLAG_MFMA_DIST) / glhip_dist_xd.h (dense, 4 <= D <= 16) / glhip_dist_xk.h (dense, 17 <= D <= 4095,
+                                  GLHIP_FLAG_XK_DIST) */
+#define GLHIP_FAMILY_GENERIC 5 /* D > 3 on the one-thread-per-row kernel of glhip_generic.h: p = 1 block-sparse, D > 16 without
+                                  GLHIP_FLAG_XK_DIST or D > 4095; p = 2 with D > 4095 or under GLHIP_FLAG_NO_MFMA / _DIRECT */
 
 int glhip_version(void);
 const char* glhip_last_error(void);
@@ -225,7 +239,7 @@ int glhip_prune_inspect(const void* x, const void* y, const float* logw, const f
  * Kernels by (p, D): p = 2 on the matrix cores for D <= 4095 (glhip_softmin_x32.h / _xd.h up to D = 16, the K-chunked glhip_softmin_xk.h
  * from D = 17 on, version 121; GLHIP_FLAG_F16X2 selects the two-piece f16 layout); p = 1 on the matrix cores for block-sparse launches of D <= 3 with GLHIP_FLAG_MFMA_DIST (glhip_dist_x32.h) and, since
  * round 5, for every DENSE launch of 4 <= D <= 16 (glhip_dist_xd.h: squared distances from the MFMA chain, pairs closer than 1/16 of
- * their offset from the cloud's centre re-evaluated exactly); everything else (p = 1 in D > 16, p = 2 in D > 4095, block-sparse p = 1 in D > 3, GLHIP_FLAG_NO_MFMA /
+ * their offset from the cloud's centre re-evaluated exactly); everything else (p = 1 in D > 16 without GLHIP_FLAG_XK_DIST, p = 2 in D > 4095, block-sparse p = 1 in D > 3, GLHIP_FLAG_NO_MFMA /
  * GLHIP_FLAG_DIRECT) on explicit differences.
  * Accuracy of the matrix-core distances (p = 1; laplacian / energy products): the squared distance of a pair carries ~2^-23 t^2 R^2
  * (t = log2(e) / eps, R = offset of the pair from the centre the launch subtracts), so the EXPONENT of a pair just above the near-pair
@@ -242,7 +256,7 @@ int glhip_softmin_fwd(const void* x, const void* y, const float* h, float* out,
 
 /*
  * One fused half-step of the symmetric Sinkhorn iteration (every kernel of D <= 3; p = 2 for D <= 4095 (D > 16: version 121); p = 1 on
- * dense launches for D <= 16; GLHIP_EUNSUPPORTED elsewhere — compose glhip_softmin_fwd):
+ * dense launches for D <= 16 and, under GLHIP_FLAG_XK_DIST (version 131), for D <= 4095; GLHIP_EUNSUPPORTED elsewhere — compose glhip_softmin_fwd):
  *   t_i   = soft-min(eps, C(x,y), logw + pot / eps)_i          (pot == NULL: logw alone, the initialisation)
  *   out_i = damping * t_i                                       (prev == NULL)
  *   out_i = (prev_i + damping * t_i) / 2                        (prev != NULL; out must not alias prev)
