@@ -4,6 +4,9 @@
 namespace glhip {      // glhip_api_grad_xk.hip: the GLHIP_FLAG_XK_GRAD route (xk_plan_kernel on XkGradParams, glhip_softmin_grad_xk.h)
 int softmin_grad_xk_launch(const void* x, const void* y, const float* h, const float* fwd, const float* g, float* gx, int B, int N, int M,
                            int D, float eps, int in_dtype, void* workspace, size_t workspace_bytes, int flags, hipStream_t st);
+// glhip_api_distgrad_xk.hip: the GLHIP_FLAG_XK_DIST_GRAD route (xk_dist_grad_kernel, glhip_dist_grad_xk.h)
+int dist_grad_xk_launch(int op, const void* x, const void* y, const float* s, const float* g, float* out, float* gx, int B, int N, int M, int D,
+                        float scale, int in_dtype, void* workspace, size_t workspace_bytes, int flags, hipStream_t st);
 }
 
 extern "C" {
@@ -22,6 +25,10 @@ int glhip_softmin_bwd_x(const void* x, const void* y, const float* h, const floa
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (glhip_softmin_bwd_x_uses_plan(B, N, M, D, p, in_dtype, flags, n_ranges) == 1) {      // GLHIP_FLAG_XK_GRAD: p = 2, 17 <= D <= 4095, dense
         rc = softmin_grad_xk_launch(x, y, h, out, grad_out, grad_x, B, N, M, D, eps, in_dtype, workspace, workspace_bytes, flags, st);
+        return rc ? rc : check_launch("glhip_softmin_bwd_x");
+    }
+    if (p == 1 && glhip_dist_grad_uses_xk(GLHIP_DIST_GRAD_SOFTMIN_P1, B, N, M, D, in_dtype, flags, n_ranges) == 1) {      // GLHIP_FLAG_XK_DIST_GRAD: p = 1, 17 <= D <= 4095, dense
+        rc = dist_grad_xk_launch(GLHIP_DIST_GRAD_SOFTMIN_P1, x, y, h, grad_out, nullptr, grad_x, B, N, M, D, eps, in_dtype, workspace, workspace_bytes, flags, st);
         return rc ? rc : check_launch("glhip_softmin_bwd_x");
     }
     const Scratch sc = make_scratch(workspace, workspace_bytes, flags, n_ranges, N);

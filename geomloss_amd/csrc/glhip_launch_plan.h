@@ -2,6 +2,8 @@
 // shares their split policy: ONE pass launcher, ONE pass loop over xk_plan_kernel (glhip_plan_apply_xk.h), ONE sizing rule and ONE
 // argument prologue for glhip_api_plan.hip, glhip_api_plan_xk.hip, glhip_api_grad_xk.hip, glhip_api_convgrad_xk.hip and glhip_api_argmin.hip.
 // What the launcher takes and what the sizing calls promise must agree exactly: both read plan_splits and the constants below.
+// glhip_api_distgrad_xk.hip (xk_dist_grad_kernel, glhip_dist_grad_xk.h) uses launch_plan_pass, launch_plan_merge and the sizing rule with a
+// pass loop of its own: its passes are 32 coordinates wide, and launch_xk_plan_passes below stays the loop of xk_plan_kernel alone.
 #pragma once
 
 #include <initializer_list>

@@ -28,6 +28,9 @@ FLAG_XK_GRAD = 1024             # glhip_softmin_bwd_x: the p = 2 gradient of 17 
                                 # glhip_kernel_conv_bwd_x / _fwd_grad: the gaussian gradient of those dimensions (glhip_gauss_grad_xk.h)
 FLAG_XK_DIST = 2048             # p = 1 soft-min / half-step, laplacian and energy products of 17 <= D <= 4095, dense launches: squared distances
                                 # from the K-chunked matrix-core chain (glhip_dist_xk.h); opt-in, the gradients stay on the generic kernel
+FLAG_XK_DIST_GRAD = 4096        # the p = 1 soft-min, laplacian and energy row gradients of 17 <= D <= 4095, dense launches, on the matrix cores
+                                # (glhip_dist_grad_xk.h); glhip_kernel_conv_fwd_grad takes those kinds under it
+DIST_GRAD_OPS = {"softmin_p1": 0, "laplacian": 1, "energy": 2}      # ops of glhip_dist_grad_uses_xk (GLHIP_DIST_GRAD_*)
 FLAG_GRAD_FAMILY = FLAG_XDL16   # kernel products rounded like the product-and-gradient kernel of the same kind (glhip.h)
 XD_MAX_DIM = 16                 # the fused four-softmin iteration / annealing / extrapolation, the one-pass value + gradient and the matrix-core
                                 # gradients stop at this dimension (glhip_softmin_xd.h, glhip_wsum_t32.h)
@@ -66,6 +69,9 @@ SIGNATURES = {
     "glhip_softmin_bwd_x_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "glhip_kernel_conv_grad_uses_xk": (_c_int, [_c_int, _c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int]),
     "glhip_kernel_conv_grad_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "glhip_dist_grad_uses_xk": (_c_int, [_c_int, _c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int]),
+    "glhip_dist_grad_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "glhip_dist_grad_pass_width": (_c_int, []),
     "glhip_plan_apply_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "glhip_plan_apply": (_c_int, [_vp] * 7 + [_c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int, _c_int] + _RANGES + _TAIL),
     "glhip_plan_apply_nd_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
@@ -356,6 +362,24 @@ def softmin_bwd_x_uses_plan(B, N, M, D, p=2, dtype=F32, flags=0, n_ranges=0):
     return r
 
 
+def dist_grad_uses_xk(op, B, N, M, D, dtype=F32, flags=0, n_ranges=0):
+    """Whether ``glhip_softmin_bwd_x`` with p = 1 (``op`` "softmin_p1") resp. ``glhip_kernel_conv_bwd_x`` / ``glhip_kernel_conv_fwd_grad``
+    (``op`` "laplacian" / "energy", or a kernel kind code) run the matrix-core distance gradient of 17 <= D <= 4095 for this launch
+    (``FLAG_XK_DIST_GRAD``): the library's own predicate (host arithmetic, no GPU).  1 / 0, or ``ValueError`` for bad arguments."""
+    lib = load_library()
+    r = int(lib.glhip_dist_grad_uses_xk(int(DIST_GRAD_OPS.get(op, op)), int(B), int(N), int(M), int(D), int(dtype), int(flags), int(n_ranges)))
+    if r < 0:
+        raise ValueError(f"glhip_dist_grad_uses_xk: bad argument (op {op}, B {B}, N {N}, M {M}, D {D}, dtype {dtype}, n_ranges {n_ranges})")
+    return r
+
+
+def _dist_grad_workspace(lib, x, B, N, M, D, flags, workspace):
+    """The split partials of the matrix-core distance gradient (``glhip_dist_grad_workspace_bytes``)."""
+    nbytes = int(lib.glhip_dist_grad_workspace_bytes(B, N, M, D, int(flags))) if workspace else 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+    return ws, (None if ws is None else ws.data_ptr(), nbytes)
+
+
 def softmin_bwd_x_raw(x, y, h, out, grad_out, eps, p=2, ranges=None, flags=0, workspace=True):
     """``workspace=False``: launch without one (no column splits) — tests only."""
     lib = load_library()
@@ -376,6 +400,8 @@ def softmin_bwd_x_raw(x, y, h, out, grad_out, eps, p=2, ranges=None, flags=0, wo
             nbytes = int(lib.glhip_softmin_bwd_x_workspace_bytes(B, N, M, D, int(flags))) if workspace else 0
             ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
             ws_args = (None if ws is None else ws.data_ptr(), nbytes)
+        elif int(p) == 1 and lib.glhip_dist_grad_uses_xk(0, B, N, M, D, _dtype_code(x), int(flags), n_ranges) == 1:
+            ws, ws_args = _dist_grad_workspace(lib, x, B, N, M, D, flags, workspace)
         elif workspace:
             ws, ws_args = _workspace(lib, x, B, N, M, D, ranges)
         else:
@@ -482,6 +508,8 @@ def _conv_grad_workspace(lib, kind, x, B, N, M, D, ranges, flags, workspace):
         nbytes = int(lib.glhip_kernel_conv_grad_workspace_bytes(B, N, M, D, int(flags))) if workspace else 0
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
         return ws, (None if ws is None else ws.data_ptr(), nbytes)
+    if int(kind) in (LAPLACIAN, ENERGY) and lib.glhip_dist_grad_uses_xk(int(kind), B, N, M, D, _dtype_code(x), int(flags), n_ranges) == 1:
+        return _dist_grad_workspace(lib, x, B, N, M, D, flags, workspace)      # (the ops of the two kinds are their kind codes)
     if workspace:
         return _workspace(lib, x, B, N, M, D, ranges)
     return None, (None, 0)
@@ -511,7 +539,8 @@ def kernel_conv_bwd_x_raw(kind, x, y, v, g, blur, ranges=None, flags=0, workspac
 
 def kernel_conv_fwd_grad_raw(kind, x, y, v, blur, ranges=None, flags=0, workspace=True):
     """out = K v and d out_i / d x_i in one pass (``glhip_kernel_conv_fwd_grad``: every kernel at D <= 3, the gaussian kernel at
-    D <= 16, and at 17 <= D <= 4095 under ``FLAG_XK_GRAD``) -> (B,N), (B,N,D).  ``workspace=False``: launch without one (no column
+    D <= 16, and at 17 <= D <= 4095 under ``FLAG_XK_GRAD``; the laplacian and energy kernels at 17 <= D <= 4095 under
+    ``FLAG_XK_DIST_GRAD``) -> (B,N), (B,N,D).  ``workspace=False``: launch without one (no column
     splits) — tests only."""
     lib = load_library()
     B, N, D = x.shape
@@ -1395,12 +1424,12 @@ class _KernelConv(torch.autograd.Function):
         # When x requires gradients, the product and its row gradient come out of ONE reduction: the gradient kernel
         # carries one more accumulator, the product itself.  The backward pass is then elementwise.
         # (D <= 3: every kernel; 4 <= D <= 16: the gaussian kernel on the matrix cores; 17 <= D <= 4095: the gaussian kernel where
-        # the caller asked for the matrix-core gradient, FLAG_XK_GRAD)
+        # the caller asked for the matrix-core gradient, FLAG_XK_GRAD; the laplacian and energy kernels there under FLAG_XK_DIST_GRAD)
+        launch = (xb.shape[0], xb.shape[1], yb.shape[1], xb.shape[2], _dtype_code(xb), int(flags), 0 if ranges is None else int(ranges.ranges_i.shape[0]))
         fused = (_fuse_kernel_grad and want_unit
                  and (xb.shape[-1] <= 3 or (kind == GAUSSIAN and xb.shape[-1] <= XD_MAX_DIM and not (flags & FLAG_NO_MFMA))
-                      or load_library().glhip_kernel_conv_grad_uses_xk(int(kind), xb.shape[0], xb.shape[1], yb.shape[1], xb.shape[2],
-                                                                       _dtype_code(xb), int(flags),
-                                                                       0 if ranges is None else int(ranges.ranges_i.shape[0])) == 1))
+                      or load_library().glhip_kernel_conv_grad_uses_xk(int(kind), *launch) == 1
+                      or (int(kind) in (LAPLACIAN, ENERGY) and load_library().glhip_dist_grad_uses_xk(int(kind), *launch) == 1)))
         # laplacian / energy: squared distances from the matrix cores wherever the row blocks are spatially compact — the voxel
         # clusters of the multiscale backend as they are, large dense launches after the voxel sort the library does itself
         # (csrc/glhip_autosort.h) — for the product, the product + gradient and (GRAD_FAMILY) the companion products of a norm alike

@@ -188,15 +188,23 @@ def _weights_dtype(points):
 _XK_GRAD = os.environ.get("GEOMLOSS_HIP_XK_GRAD", "1") != "0"
 
 
+# kinds whose row gradient of 17 <= D <= 4095 takes the matrix-core distance gradient (glhip_dist_grad_xk.h, FLAG_XK_DIST_GRAD) by default
+_XK_DIST_GRAD_KINDS = ("laplacian", "energy")
+
+
 def _grad_flags(name, pts):
-    """FLAG_XK_GRAD for the gaussian kernel beyond the compiled dimensions: the product-and-gradient reductions of _UnionNorm then run
-    on the matrix cores in dimension 17 ... 4095 (hip.kernel_conv_grad_uses_xk; the library ignores the flag where it does not apply).
-    D <= 16 keeps its default flags."""
-    return hip.FLAG_XK_GRAD if (name == "gaussian" and _XK_GRAD and pts.shape[-1] > hip.XD_MAX_DIM) else 0
+    """FLAG_XK_GRAD for the gaussian kernel, FLAG_XK_DIST_GRAD for the laplacian and energy kernels, beyond the compiled dimensions: the
+    product-and-gradient reductions of _UnionNorm then run on the matrix cores in dimension 17 ... 4095 (hip.kernel_conv_grad_uses_xk,
+    hip.dist_grad_uses_xk; the library ignores the flags where they do not apply).  D <= 16 keeps its default flags."""
+    if not _XK_GRAD or pts.shape[-1] <= hip.XD_MAX_DIM:
+        return 0
+    if name == "gaussian":
+        return hip.FLAG_XK_GRAD
+    return hip.FLAG_XK_DIST_GRAD if name in _XK_DIST_GRAD_KINDS else 0
 
 
 # matrix-core laplacian / energy PRODUCT of 17 <= D <= 4095 (glhip_dist_xk.h); the knob of the p = 1 soft-min of those dimensions
-# (sinkhorn_samples._XK_DIST) covers this one too.  Their gradients stay on the one-thread-per-row kernel.
+# (sinkhorn_samples._XK_DIST) covers this one too.  (Their gradients: _grad_flags.)
 _XK_DIST = os.environ.get("GEOMLOSS_HIP_XK_DIST", "1") != "0"
 
 

@@ -145,6 +145,9 @@ class _HipSoftmin:
         # FLAG_XK_DIST: the forward / fused half-step of dense p = 1 soft-mins of 17 <= D <= 4095 with the distances on the matrix cores
         # (glhip_dist_xk.h); ignored likewise everywhere else — D <= 16, block-sparse levels, the backward, the fused iterations
         xk |= hip.FLAG_XK_DIST if (self.p == 1 and _XK_DIST) else 0
+        # FLAG_XK_DIST_GRAD: the backward of dense p = 1 soft-mins of 17 <= D <= 4095 on the matrix cores (glhip_dist_grad_xk.h); ignored
+        # everywhere else — every forward launch, p = 2, D <= 16, block-sparse levels.  Under the knob of the other D > 16 gradients
+        xk |= hip.FLAG_XK_DIST_GRAD if (self.p == 1 and _XK_GRAD and _XK_DIST_GRAD_P1) else 0
         return xk | (hip.FLAG_F16X2 if eps >= self.h2_min_eps else 0)
 
     def __call__(self, eps, C, h):
@@ -253,6 +256,7 @@ _COARSE_F64_MIN_PAIRS = float(os.environ.get("GEOMLOSS_HIP_COARSE_F64_MIN_PAIRS"
 _F16X2 = os.environ.get("GEOMLOSS_HIP_F16X2", "1") != "0"      # f16 x 2 exponents where the temperature allows (_HipSoftmin.set_range)
 _XK_GRAD = os.environ.get("GEOMLOSS_HIP_XK_GRAD", "1") != "0"  # matrix-core soft-min gradient of 17 <= D <= 4095 (_HipSoftmin._flags)
 _XK_DIST = os.environ.get("GEOMLOSS_HIP_XK_DIST", "1") != "0"  # matrix-core p = 1 soft-min / half-step of 17 <= D <= 4095 (_HipSoftmin._flags)
+_XK_DIST_GRAD_P1 = True     # matrix-core p = 1 soft-min GRADIENT of 17 <= D <= 4095 (glhip_dist_grad_xk.h) on by default, under _XK_GRAD's knob
 _anneal_in_library = True   # the iterations of a level queued by one library call (tests switch it off to compare with one call per iteration)
 _fuse_iterations = True   # one launch per Sinkhorn iteration (small / mid-size clouds); set_iteration_fusion(False): four half-steps
 # ... up to this many pairs per soft-min; bigger problems fill the GPU with one soft-min per launch (pre-packed columns, XCD grids)

@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 131 /* 0.1.31 */
+#define GLHIP_VERSION 132 /* 0.1.32 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
@@ -113,6 +113,23 @@ extern "C" {
                                   glhip_kernel_conv_fwd_grad / glhip_softmin_bwd_x), the float64 symbols and glhip_sinkhorn_iter4 / _anneal /
                                   _extrapolate4.  Workspace: glhip_workspace_bytes as it is (2 floats per row and split for D > 16 is what the
                                   soft-min takes; the products take 1). */
+
+#define GLHIP_FLAG_XK_DIST_GRAD 4096 /* version 132.  The row gradients of the distance reductions: glhip_softmin_bwd_x with p == 1 and
+                                  glhip_kernel_conv_bwd_x / glhip_kernel_conv_fwd_grad of the laplacian / energy kinds, 17 <= D <= 4095, dense
+                                  launches (n_ranges == 0), B <= 65535, without GLHIP_FLAG_NO_MFMA / _DIRECT run xk_dist_grad_kernel
+                                  (csrc/glhip_dist_grad_xk.h): the exact squared distances of xk_dist_kernel (bf16 x 3 only, near pairs repaired
+                                  and added on explicit differences) and the K-chunked product of xk_plan_kernel against the centred column
+                                  cloud, in passes of glhip_dist_grad_pass_width() coordinates.  The p = 1 gradient normalises itself from the
+                                  same launch (the saved forward value is not read).  glhip_kernel_conv_fwd_grad stops being GLHIP_EUNSUPPORTED
+                                  for those kinds.  glhip_dist_grad_uses_xk is the predicate, glhip_dist_grad_workspace_bytes the sizing call.
+                                  Opt-in: without the flag every launch of every entry point is the one version 131 makes, bit for bit.
+                                  Ignored, bit for bit, by p == 2, the gaussian kind, D <= 16, D > 4095, block-sparse ranges, every forward and
+                                  the float64 symbols.  GLHIP_FLAG_XK_GRAD is a different bit: its predicates stay 0 for these gradients. */
+
+/* ops of glhip_dist_grad_uses_xk */
+#define GLHIP_DIST_GRAD_SOFTMIN_P1 0 /* glhip_softmin_bwd_x, p == 1 */
+#define GLHIP_DIST_GRAD_LAPLACIAN 1  /* glhip_kernel_conv_bwd_x / glhip_kernel_conv_fwd_grad, GLHIP_LAPLACIAN */
+#define GLHIP_DIST_GRAD_ENERGY 2     /* ... GLHIP_ENERGY */
 
 #define GLHIP_FLAG_NO_SORT 512 /* p = 1 soft-min / half-step, laplacian and energy products: big dense launches (B = 1, D <= 3, N >= 65536,
                                   N M >= 5e8, a workspace of glhip_workspace_bytes) sort both clouds into the workspace themselves — voxel sort along a
@@ -499,6 +516,17 @@ int glhip_kernel_conv_fwd(int kind, const void* x, const void* y, const float* v
  *   mass, row maximum per row and split), never more than 1 GiB, 0 where the predicate is 0 or under GLHIP_FLAG_NO_SPLIT.  NULL or a
  *   short workspace: fewer or no splits, the same results up to summation order.  M == 0 zeroes grad_x (and out).
  */
+/* GLHIP_FLAG_XK_DIST_GRAD (version 132): the predicate, the workspace and the pass width of xk_dist_grad_kernel (glhip_dist_grad_xk.h).
+ *   glhip_dist_grad_uses_xk: host arithmetic only, the very predicate glhip_softmin_bwd_x (op GLHIP_DIST_GRAD_SOFTMIN_P1, asked for p == 1) and
+ *   glhip_kernel_conv_bwd_x / glhip_kernel_conv_fwd_grad (laplacian, energy) evaluate — 1: that kernel (dense, 17 <= D <= 4095, B <= 65535, the
+ *   flag set, neither GLHIP_FLAG_NO_MFMA nor _DIRECT); 0: the launch of version 131; GLHIP_EINVAL: a bad op or dtype, negative sizes, D < 1.
+ *   glhip_dist_grad_workspace_bytes: the split partials of the widest pass (the direction sums of <= glhip_dist_grad_pass_width()
+ *   coordinates, one scalar — the normaliser Z, or the product — and the row maximum per row and split), never more than 1 GiB, 0 where the
+ *   predicate is 0 or under GLHIP_FLAG_NO_SPLIT.  NULL or a short workspace: fewer or no splits.  M == 0 zeroes grad_x (and out).
+ *   Results are bit-identical run to run.  Pairs inside the clamp (|x - y|^2 <= 1e-8 in the kernel's units) get no direction. */
+int glhip_dist_grad_uses_xk(int op, int B, long N, long M, int D, int dtype, int flags, int n_ranges);
+size_t glhip_dist_grad_workspace_bytes(int B, int N, int M, int D, int flags);
+int glhip_dist_grad_pass_width(void);
 int glhip_kernel_conv_grad_uses_xk(int kind, int B, long N, long M, int D, int dtype, int flags, int n_ranges);
 size_t glhip_kernel_conv_grad_workspace_bytes(int B, int N, int M, int D, int flags);
 int glhip_kernel_conv_bwd_x(int kind, const void* x, const void* y, const float* v,
