@@ -1,13 +1,6 @@
 // glhip_api_bwd.hip — C-ABI part 2: the soft-min gradient and the hard C-transform of point clouds.
+#include "glhip_grad_xk.h"
 #include "glhip_launch.h"
-
-namespace glhip {      // glhip_api_grad_xk.hip: the GLHIP_FLAG_XK_GRAD route (xk_plan_kernel on XkGradParams, glhip_softmin_grad_xk.h)
-int softmin_grad_xk_launch(const void* x, const void* y, const float* h, const float* fwd, const float* g, float* gx, int B, int N, int M,
-                           int D, float eps, int in_dtype, void* workspace, size_t workspace_bytes, int flags, hipStream_t st);
-// glhip_api_distgrad_xk.hip: the GLHIP_FLAG_XK_DIST_GRAD route (xk_dist_grad_kernel, glhip_dist_grad_xk.h)
-int dist_grad_xk_launch(int op, const void* x, const void* y, const float* s, const float* g, float* out, float* gx, int B, int N, int M, int D,
-                        float scale, int in_dtype, void* workspace, size_t workspace_bytes, int flags, hipStream_t st);
-}
 
 extern "C" {
 

@@ -1,14 +1,7 @@
 // glhip_api_convgrad.hip — C-ABI part 4: gradients of the kernel products.
 #include "glhip_autosort.h"
+#include "glhip_grad_xk.h"
 #include "glhip_launch.h"
-
-namespace glhip {      // glhip_api_convgrad_xk.hip: the GLHIP_FLAG_XK_GRAD route (xk_plan_kernel on XkGaussGradParams, glhip_gauss_grad_xk.h)
-int gauss_grad_xk_launch(const void* x, const void* y, const float* v, const float* g, float* out, float* gx, int B, int N, int M, int D,
-                         float blur, int in_dtype, void* workspace, size_t workspace_bytes, int flags, hipStream_t st);
-// glhip_api_distgrad_xk.hip: the GLHIP_FLAG_XK_DIST_GRAD route (xk_dist_grad_kernel, glhip_dist_grad_xk.h)
-int dist_grad_xk_launch(int op, const void* x, const void* y, const float* s, const float* g, float* out, float* gx, int B, int N, int M, int D,
-                        float scale, int in_dtype, void* workspace, size_t workspace_bytes, int flags, hipStream_t st);
-}
 
 namespace {
 // laplacian / energy, 17 <= D <= 4095, dense, under GLHIP_FLAG_XK_DIST_GRAD: the op of glhip_dist_grad_uses_xk, or -1

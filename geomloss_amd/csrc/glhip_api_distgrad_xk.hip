@@ -2,6 +2,7 @@
 // (GLHIP_FLAG_XK_DIST_GRAD): xk_dist_grad_kernel (glhip_dist_grad_xk.h), launched by glhip_softmin_bwd_x with p = 1 (glhip_api_bwd.hip) and
 // by glhip_kernel_conv_bwd_x / glhip_kernel_conv_fwd_grad of the laplacian and energy kernels (glhip_api_convgrad.hip) where
 // glhip_dist_grad_uses_xk says so.  A translation unit of its own: the parallel build does not get longer.
+#include "glhip_grad_xk.h"
 #include "glhip_launch_plan.h"
 #include "glhip_dist_grad_xk.h"
 
@@ -12,30 +13,19 @@ constexpr int kXkDistGradWidth = 32 * glhip::kXkDistGradChunks;      // coordina
 // THE predicate of the GLHIP_FLAG_XK_DIST_GRAD route, and what glhip_dist_grad_uses_xk reports.  Host arithmetic only.
 inline int dist_grad_uses_xk(int op, int B, long N, long M, int D, int dtype, int flags, int n_ranges) {
     if (op < GLHIP_DIST_GRAD_SOFTMIN_P1 || op > GLHIP_DIST_GRAD_ENERGY || plan_family_bad_args(B, N, M, D, dtype, n_ranges)) return GLHIP_EINVAL;
-    if (!(flags & GLHIP_FLAG_XK_DIST_GRAD) || (flags & (GLHIP_FLAG_NO_MFMA | GLHIP_FLAG_DIRECT))) return 0;
-    return (D > kXdMaxD && D <= kXkMaxD && n_ranges == 0 && B <= 65535) ? 1 : 0;
+    return xk_grad_route(GLHIP_FLAG_XK_DIST_GRAD, flags, B, D, n_ranges);
 }
 
-template <int MODE, typename T, int NCH>
-void launch_dist_grad_pass(const XkDistGradParams<MODE, T>& prm, int B, int N, int M, int D, const Scratch& sc, hipStream_t st) {
-    launch_plan_pass(kXkRows, prm.nv + 2, kXkPlanSlots, B, N, M, sc, st,
-        [&](dim3 grid, const SplitInfo& sp) {
-            hipLaunchKernelGGL((xk_dist_grad_kernel<MODE, T, NCH>), grid, dim3(kXkThreads), 0, st, prm, N, M, D, sp);
-        },
-        [&](const SplitInfo& sp) { launch_plan_merge(prm, B, N, D, sp, st); });
-}
-
-// The passes over the D coordinates, kXkDistGradWidth at a time; a pass of <= 32 runs with one chunk
+// The passes over the D coordinates, kXkDistGradWidth at a time: one chunk each
 template <int MODE, typename T>
-void launch_dist_grad_passes(XkDistGradParams<MODE, T> prm, int B, int N, int M, int D, const Scratch& sc, hipStream_t st) {
-    for (int v0 = 0; v0 < D; v0 += kXkDistGradWidth) {
-        prm.v0 = v0;
-        prm.nv = D - v0 < kXkDistGradWidth ? D - v0 : kXkDistGradWidth;
-        if constexpr (kXkDistGradChunks == 2) {
-            if (prm.nv > 32) { launch_dist_grad_pass<MODE, T, 2>(prm, B, N, M, D, sc, st); continue; }
-        }
-        launch_dist_grad_pass<MODE, T, 1>(prm, B, N, M, D, sc, st);
-    }
+void launch_dist_grad_passes(const XkDistGradParams<MODE, T>& prm, int B, int N, int M, int D, const Scratch& sc, hipStream_t st) {
+    launch_plan_passes(prm, D, kXkDistGradWidth, [&](const XkDistGradParams<MODE, T>& pass, int) {
+        launch_plan_pass(kXkRows, pass.nv + 2, kXkPlanSlots, B, N, M, sc, st,
+            [&](dim3 grid, const SplitInfo& sp) {
+                hipLaunchKernelGGL((xk_dist_grad_kernel<MODE, T, kXkDistGradChunks>), grid, dim3(kXkThreads), 0, st, pass, N, M, D, sp);
+            },
+            [&](const SplitInfo& sp) { launch_plan_merge(pass, B, N, D, sp, st); });
+    });
 }
 
 }  // namespace
@@ -47,13 +37,7 @@ namespace glhip {
 // checked the arguments and the predicate, and B, N > 0.
 int dist_grad_xk_launch(int op, const void* x, const void* y, const float* s, const float* g, float* out, float* gx, int B, int N, int M, int D,
                         float scale, int in_dtype, void* workspace, size_t workspace_bytes, int flags, hipStream_t st) {
-    if (M == 0) {      // no columns: empty sums
-        (void)hipMemsetAsync(gx, 0, (size_t)B * N * D * sizeof(float), st);
-        if (out) (void)hipMemsetAsync(out, 0, (size_t)B * N * sizeof(float), st);
-        return GLHIP_OK;
-    }
-    const Scratch sc = make_scratch(workspace, workspace_bytes, flags, 0, N);
-    auto run = [&](auto tag) {
+    return xk_grad_launch(gx, out, B, N, M, D, in_dtype, workspace, workspace_bytes, flags, st, [&](auto tag, const Scratch& sc) {
         using T = decltype(tag);
         const T* xp = static_cast<const T*>(x);
         const T* yp = static_cast<const T*>(y);
@@ -67,9 +51,7 @@ int dist_grad_xk_launch(int op, const void* x, const void* y, const float* s, co
             const ConvParams<T> c = make_conv_params<T>(GLHIP_ENERGY, x, y, s, out, g, gx, scale);
             launch_dist_grad_passes(XkDistGradParams<DM_ENERGY, T>{xp, yp, s, g, gx, out, c.t, c.clamp2, dist_guard(), c.gscale, 0, 0}, B, N, M, D, sc, st);
         }
-    };
-    if (in_dtype == GLHIP_F32) run(float{}); else run(bf16_t{});
-    return GLHIP_OK;
+    });
 }
 
 }  // namespace glhip
@@ -81,9 +63,7 @@ int glhip_dist_grad_uses_xk(int op, int B, long N, long M, int D, int dtype, int
 }
 
 size_t glhip_dist_grad_workspace_bytes(int B, int N, int M, int D, int flags) {
-    if (B <= 0 || N <= 0 || M <= 0 || (flags & GLHIP_FLAG_NO_SPLIT)) return 0;
-    if (dist_grad_uses_xk(GLHIP_DIST_GRAD_SOFTMIN_P1, B, N, M, D, GLHIP_F32, flags, 0) != 1) return 0;
-    return plan_pass_workspace_bytes(B, N, M, kXkRows, D < kXkDistGradWidth ? D : kXkDistGradWidth, {kXkPlanSlots});
+    return xk_grad_workspace_bytes(dist_grad_uses_xk(GLHIP_DIST_GRAD_SOFTMIN_P1, B, N, M, D, GLHIP_F32, flags, 0), B, N, M, D, flags, kXkDistGradWidth);
 }
 
 int glhip_dist_grad_pass_width(void) { return kXkDistGradWidth; }

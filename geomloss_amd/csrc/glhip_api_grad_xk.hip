@@ -1,6 +1,7 @@
 // glhip_api_grad_xk.hip — C-ABI part 10: the p = 2 soft-min gradient of 17 <= D <= 4095 on the matrix cores (GLHIP_FLAG_XK_GRAD):
 // xk_plan_kernel on XkGradParams (glhip_softmin_grad_xk.h), launched by glhip_softmin_bwd_x (glhip_api_bwd.hip) where glhip_softmin_bwd_x_uses_plan
 // says so.  A translation unit of its own: the parallel build does not get longer.
+#include "glhip_grad_xk.h"
 #include "glhip_launch_plan.h"
 #include "glhip_softmin_grad_xk.h"
 
@@ -9,8 +10,7 @@ namespace {
 // THE predicate of the GLHIP_FLAG_XK_GRAD route of glhip_softmin_bwd_x, and what glhip_softmin_bwd_x_uses_plan reports.  Host arithmetic only.
 inline int grad_xk_uses_plan(int B, long N, long M, int D, int p, int dtype, int flags, int n_ranges) {
     if (plan_family_bad_args(B, N, M, D, dtype, n_ranges) || (p != 1 && p != 2)) return GLHIP_EINVAL;
-    if (!(flags & GLHIP_FLAG_XK_GRAD) || (flags & (GLHIP_FLAG_NO_MFMA | GLHIP_FLAG_DIRECT))) return 0;
-    return (p == 2 && D > kXdMaxD && D <= kXkMaxD && n_ranges == 0 && B <= 65535) ? 1 : 0;
+    return p == 2 ? xk_grad_route(GLHIP_FLAG_XK_GRAD, flags, B, D, n_ranges) : 0;
 }
 
 }  // namespace
@@ -20,18 +20,11 @@ namespace glhip {
 // The launch behind glhip_softmin_bwd_x under GLHIP_FLAG_XK_GRAD; the caller has checked the arguments and the predicate, and B, N > 0.
 int softmin_grad_xk_launch(const void* x, const void* y, const float* h, const float* fwd, const float* g, float* gx, int B, int N, int M,
                            int D, float eps, int in_dtype, void* workspace, size_t workspace_bytes, int flags, hipStream_t st) {
-    if (M == 0) {      // no columns: no mass in any row
-        (void)hipMemsetAsync(gx, 0, (size_t)B * N * D * sizeof(float), st);
-        return GLHIP_OK;
-    }
-    const Scratch sc = make_scratch(workspace, workspace_bytes, flags, 0, N);
-    auto run = [&](auto tag) {
+    return xk_grad_launch(gx, nullptr, B, N, M, D, in_dtype, workspace, workspace_bytes, flags, st, [&](auto tag, const Scratch& sc) {
         using T = decltype(tag);
         const XkGradParams<T> prm{static_cast<const T*>(x), static_cast<const T*>(y), h, fwd, g, gx, kLog2e / eps, -eps * kLn2, 0, 0};
         launch_xk_plan_passes(prm, D, B, N, M, D, sc, st);
-    };
-    if (in_dtype == GLHIP_F32) run(float{}); else run(bf16_t{});
-    return GLHIP_OK;
+    });
 }
 
 }  // namespace glhip
@@ -43,9 +36,7 @@ int glhip_softmin_bwd_x_uses_plan(int B, long N, long M, int D, int p, int dtype
 }
 
 size_t glhip_softmin_bwd_x_workspace_bytes(int B, int N, int M, int D, int flags) {
-    if (B <= 0 || N <= 0 || M <= 0 || (flags & GLHIP_FLAG_NO_SPLIT)) return 0;
-    if (grad_xk_uses_plan(B, N, M, D, 2, GLHIP_F32, flags, 0) != 1) return 0;
-    return plan_pass_workspace_bytes(B, N, M, kXkRows, D < kXkPlanWidth ? D : kXkPlanWidth, {kXkPlanSlots});
+    return xk_grad_workspace_bytes(grad_xk_uses_plan(B, N, M, D, 2, GLHIP_F32, flags, 0), B, N, M, D, flags, kXkPlanWidth);
 }
 
 }  // extern "C"

@@ -40,6 +40,10 @@
 //     soft-min p = 1 : 227 VGPRs, 95.1 KiB of LDS (97 408 B), 0 bytes of scratch, 2 waves per SIMD (one workgroup per CU)
 //     laplacian      : 229 VGPRs, the same LDS, 0 bytes of scratch, 2 waves per SIMD
 //     energy         : 231 VGPRs, the same LDS, 0 bytes of scratch, 2 waves per SIMD
+//
+// Shared pieces: the near-pair repair is xk_dist_exact_d2 / xk_dist_patch_near of glhip_dist_xk.h (the owner's patch; the second walk below
+// keeps its structure and uses xk_dist_exact_d2 alone); the plan half calls plan_store_pieces, plan_rescale (with z4 as a second scalar),
+// plan_split_weights and plan_chunk_mfma of glhip_plan_apply.h and the register maps of glhip_klayout.h (profiles/xk_plan_pieces.txt).
 #pragma once
 
 #include "glhip_dist_xk.h"
@@ -92,8 +96,6 @@ xk_dist_grad_kernel(XkDistGradParams<MODE, T> prm, int N, int M, int D, SplitInf
     static_assert(NCH == 1 || NCH == 2, "1 or 2 chunks of 32 coordinates per pass");
     static_assert(kFItems * kXkThreads == (kXkCols / 4) * VC, "whole items per thread");
     static_assert((VC + 2) * kXkRows * sizeof(float) <= sizeof(XkLds::buf), "the column halves meet in the stage buffer");
-    typedef float f32x2_t __attribute__((ext_vector_type(2)));
-    typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
     __shared__ XkPlanLds<NCH> lds;
 
     int bx, b, split;
@@ -182,15 +184,10 @@ xk_dist_grad_kernel(XkDistGradParams<MODE, T> prm, int N, int M, int D, SplitInf
             const int t = cq << 2;
             if (t < ncg * 32) {
                 const float sc = __uint_as_float(plan_scale_exponent(lds.fmax[parity][c]) << 23);
-                const f32x2_t v01 = {fv[k][0] * sc, fv[k][1] * sc}, v23 = {fv[k][2] * sc, fv[k][3] * sc};
-                const f16x2_t h01 = __builtin_convertvector(v01, f16x2_t), h23 = __builtin_convertvector(v23, f16x2_t);
-                const f16x2_t l01 = __builtin_convertvector(v01 - __builtin_convertvector(h01, f32x2_t), f16x2_t);
-                const f16x2_t l23 = __builtin_convertvector(v23 - __builtin_convertvector(h23, f32x2_t), f16x2_t);
                 const int jj = t & 31;
                 const int r = (jj >> 3) << 2, hq = (jj >> 2) & 1;
                 uint2* qb = reinterpret_cast<uint2*>(&lds.q[(t >> 5) * kQRecs + (c >> 5) * (4 * 64) + (r >> 3) * 64 + hq * 32 + (c & 31)]) + ((r & 7) >> 2);
-                qb[0] = uint2{__builtin_bit_cast(uint32_t, h01), __builtin_bit_cast(uint32_t, h23)};
-                qb[256] = uint2{__builtin_bit_cast(uint32_t, l01), __builtin_bit_cast(uint32_t, l23)};
+                plan_store_pieces(fv[k], sc, qb);
             }
         }
         __syncthreads();
@@ -221,31 +218,13 @@ xk_dist_grad_kernel(XkDistGradParams<MODE, T> prm, int N, int M, int D, SplitInf
                 if (G >= ncg) continue;
                 const int cslot0 = G * 32;
                 f32x16& d2 = acc[rt][cg];
-                // ---- near pairs, as xk_dist_kernel: the owner patches its d2 with the exact value (register k of a lane is column
-                // 8 (k / 4) + 4 half + k % 4 of the group)
+                // ---- near pairs, as xk_dist_kernel: the owner patches its d2 with the exact value
                 uint32_t near = 0u;
                 const bool any_near = prm.guard > 0.f && __any(min16(d2) < thr);
                 if (any_near) {
 #pragma unroll
                     for (int k = 15; k >= 0; --k) near = (near << 1) | (d2[k] < thr ? 1u : 0u);
-                    const T* xi = xb + (long)lds.xk.idx[rslot] * D;
-                    uint32_t todo = near;
-                    while (todo != 0u) {
-                        const int k = __builtin_ctz(todo);
-                        todo &= todo - 1u;
-                        const int j = lds.xk.idx[kXkRows + cslot0 + (k >> 2) * 8 + half * 4 + (k & 3)];
-                        if (j >= 0) {
-                            const T* yj = yb + (long)j * D;
-                            float e = 0.f;
-                            for (int d = 0; d < D; ++d) {
-                                const float df = (to_f32<T>(xi[d]) - to_f32<T>(yj[d])) * prm.t;
-                                e = __builtin_fmaf(df, df, e);
-                            }
-                            e = fmaxf(e, prm.clamp2);
-#pragma unroll
-                            for (int kk = 0; kk < 16; ++kk) d2[kk] = (kk == k) ? e : d2[kk];
-                        }
-                    }
+                    xk_dist_patch_near<T>(d2, near, xb + (long)lds.xk.idx[rslot] * D, yb, &lds.xk.idx[kXkRows + cslot0], half, D, prm.t, prm.clamp2);
                 }
                 // ---- u~ = u - 0.5 log2(d2) in place; ds: dist, or -1 for a pair inside the clamp
                 const float* sg = &lds.xk.v[cslot0 + half * 4];
@@ -268,18 +247,7 @@ xk_dist_grad_kernel(XkDistGradParams<MODE, T> prm, int N, int M, int D, SplitInf
                 }
                 float bm = max16(d2);
                 bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
-                if (__any(bm > m[rt])) {                      // lazy: rescale only when the maximum grew (factor exactly 1 for the rows that keep theirs)
-                    const float mn = fmaxf(m[rt], bm);
-                    const float rs = fast_exp2(m[rt] - mn);
-#pragma unroll
-                    for (int ch = 0; ch < NCH; ++ch) {
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) pacc[rt][ch][r] *= rs;
-                    }
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) { mass4[rt][k] *= rs; z4[rt][k] *= rs; }
-                    m[rt] = mn;
-                }
+                plan_rescale(bm, m[rt], pacc[rt], mass4[rt], z4[rt]);      // lazy: only when the maximum grew
                 // ---- the exact direction of the near pairs of the row: both lanes of the row walk the same pairs
                 if (any_near) {
                     const uint32_t other = __shfl_xor(near, 32, 64);
@@ -291,15 +259,11 @@ xk_dist_grad_kernel(XkDistGradParams<MODE, T> prm, int N, int M, int D, SplitInf
                             while (todo != 0u) {
                                 const int k = __builtin_ctz(todo);
                                 todo &= todo - 1u;
-                                const int cs = cslot0 + (k >> 2) * 8 + hs * 4 + (k & 3);
+                                const int cs = cslot0 + reg_column(k, hs);
                                 const int j = lds.xk.idx[kXkRows + cs];
                                 if (j < 0) continue;
                                 const T* yj = yb + (long)j * D;
-                                float e = 0.f;
-                                for (int d = 0; d < D; ++d) {
-                                    const float df = (to_f32<T>(xi[d]) - to_f32<T>(yj[d])) * prm.t;
-                                    e = __builtin_fmaf(df, df, e);
-                                }
+                                const float e = xk_dist_exact_d2<T>(xi, yj, D, prm.t);
                                 if (!(e > prm.clamp2)) continue;      // inside the clamp: no direction
                                 const float sj = lds.xk.v[cs];
                                 const float dist = fast_sqrt(e);
@@ -311,7 +275,7 @@ xk_dist_grad_kernel(XkDistGradParams<MODE, T> prm, int N, int M, int D, SplitInf
                                 for (int ch = 0; ch < NCH; ++ch) {
 #pragma unroll
                                     for (int r = 0; r < 16; ++r) {
-                                        const int c = 32 * ch + (r & 3) + 8 * (r >> 2) + 4 * half;
+                                        const int c = 32 * ch + reg_feature(r, half);
                                         if (c < prm.nv) {     // S -= w (x_i - y_j): T = (x_i - c) W - S gains w (x_i - y_j)
                                             const float dy = to_f32<T>(yj[prm.v0 + c]) - to_f32<T>(xi[prm.v0 + c]);
                                             pacc[rt][ch][r] = __builtin_fmaf(wn, dy, pacc[rt][ch][r]);
@@ -340,31 +304,16 @@ xk_dist_grad_kernel(XkDistGradParams<MODE, T> prm, int N, int M, int D, SplitInf
                             z4[rt][(k & 3) + e] = __builtin_fmaf(w[e], zf, z4[rt][(k & 3) + e]);
                             mass4[rt][(k & 3) + e] += wd[e];
                         } else {
-                            const float vj = sg[(k >> 2) * 8 + (k & 3) + e];
+                            const float vj = sg[reg_column(k + e, 0)];      // (sg carries the lane half)
                             z4[rt][(k & 3) + e] = __builtin_fmaf(w[e] * zf, vj, z4[rt][(k & 3) + e]);
                             mass4[rt][(k & 3) + e] = __builtin_fmaf(wd[e], vj, mass4[rt][(k & 3) + e]);
                         }
                     }
-                    const f16x2_t hh = __builtin_convertvector(wd, f16x2_t);
-                    const f32x2_t back = __builtin_convertvector(hh, f32x2_t);
-                    const f16x2_t ll = __builtin_convertvector(wd - back, f16x2_t);
-                    whi[k >> 3].v[k & 7] = hh[0];
-                    whi[k >> 3].v[(k & 7) + 1] = hh[1];
-                    wlo[k >> 3].v[k & 7] = ll[0];
-                    wlo[k >> 3].v[(k & 7) + 1] = ll[1];
+                    plan_split_weights(wd, k, whi, wlo);
                 }
 #pragma unroll
                 for (int ch = 0; ch < NCH; ++ch) {
-                    const uint4* qg = &lds.q[G * kQRecs + ch * (4 * 64) + lane];      // piece p, instruction I: qg[p * 128 + I * 64]
-                    Pack16h qh0, qh1, ql0, ql1;
-                    qh0.u = qg[0]; qh1.u = qg[64]; ql0.u = qg[128]; ql1.u = qg[192];
-                    // smallest products first: lo hi, hi lo, hi hi
-                    f32x16 t = __builtin_amdgcn_mfma_f32_32x32x16_f16(ql0.v, whi[0].v, zero16, 0, 0, 0);
-                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(ql1.v, whi[1].v, t, 0, 0, 0);
-                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(qh0.v, wlo[0].v, t, 0, 0, 0);
-                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(qh1.v, wlo[1].v, t, 0, 0, 0);
-                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(qh0.v, whi[0].v, t, 0, 0, 0);
-                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(qh1.v, whi[1].v, t, 0, 0, 0);
+                    const f32x16 t = plan_chunk_mfma(&lds.q[G * kQRecs + ch * (4 * 64) + lane], whi, wlo);
                     const float* ig = &lds.inv[ch * 32 + half * 4];
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
@@ -397,7 +346,7 @@ xk_dist_grad_kernel(XkDistGradParams<MODE, T> prm, int N, int M, int D, SplitInf
         for (int ch = 0; ch < NCH; ++ch) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int c = 32 * ch + (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int c = 32 * ch + reg_feature(r, half);
                 float xc = 0.f;
                 if (c < prm.nv) xc = to_f32<T>(xb[(long)i * D + prm.v0 + c]) - to_f32<T>(centre[prm.v0 + c]);
                 pacc[rt][ch][r] = __builtin_fmaf(xc, w, -pacc[rt][ch][r]);
@@ -407,7 +356,7 @@ xk_dist_grad_kernel(XkDistGradParams<MODE, T> prm, int N, int M, int D, SplitInf
 #pragma unroll
             for (int ch = 0; ch < NCH; ++ch) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) mrg[(32 * ch + (r & 3) + 8 * (r >> 2) + 4 * half) * kXkRows + r_local] = pacc[rt][ch][r];
+                for (int r = 0; r < 16; ++r) mrg[(32 * ch + reg_feature(r, half)) * kXkRows + r_local] = pacc[rt][ch][r];
             }
             if (half == 0) {
                 mrg[VC * kXkRows + r_local] = zs[rt];
@@ -435,7 +384,7 @@ xk_dist_grad_kernel(XkDistGradParams<MODE, T> prm, int N, int M, int D, SplitInf
         for (int ch = 0; ch < NCH; ++ch) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int c = 32 * ch + (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int c = 32 * ch + reg_feature(r, half);
                 if (c < prm.nv) {
                     const float s = __builtin_fmaf(mrg[c * kXkRows + r_local], rs2, pacc[rt][ch][r] * rs1);
                     if (ns > 1) part[c] = s;

@@ -19,12 +19,46 @@
 // SoftminFwdOp<1, 1, true, 1, T> / ConvOp<KIND, 1, 1, T, 0>.
 //
 // The first row of a block is its centre: n_i = 0 and d2 = N_j, a float32 chain on explicit differences — exact like a near pair.
+//
+// The near-pair repair is two __device__ __forceinline__ pieces below, xk_dist_exact_d2 and xk_dist_patch_near, shared with
+// xk_dist_grad_kernel (glhip_dist_grad_xk.h); the v_mbcnt re-derivation of the lane stays at this kernel's call site.
 #pragma once
 
 #include "glhip_dist_xd.h"
 #include "glhip_softmin_xk.h"
 
 namespace glhip {
+
+// ---- The near-pair repair, shared with xk_dist_grad_kernel (glhip_dist_grad_xk.h) ----
+
+// t^2 |x_i - y_j|^2 on explicit differences of the points themselves: a run-time loop over D from global memory
+template <typename T>
+__device__ __forceinline__ float xk_dist_exact_d2(const T* xi, const T* yj, int D, float t) {
+    float e = 0.f;
+    for (int d = 0; d < D; ++d) {
+        const float df = (to_f32<T>(xi[d]) - to_f32<T>(yj[d])) * t;
+        e = __builtin_fmaf(df, df, e);
+    }
+    return e;
+}
+
+// The owner of a block's near pairs (mask `near`: bit k = register k of d2, column reg_column(k, half) of the group whose column
+// indices are cidx[0 .. 31], -1 = padding, never re-evaluated) patches its d2 with the exact value, clamped from below: one pair per
+// lane and turn.
+template <typename T>
+__device__ __forceinline__ void xk_dist_patch_near(f32x16& d2, uint32_t near, const T* xi, const T* yb, const int* cidx, int half, int D,
+                                                   float t, float clamp2) {
+    while (near != 0u) {
+        const int k = __builtin_ctz(near);
+        near &= near - 1u;
+        const int j = cidx[reg_column(k, half)];
+        if (j >= 0) {
+            const float e = fmaxf(xk_dist_exact_d2<T>(xi, yb + (long)j * D, D, t), clamp2);
+#pragma unroll
+            for (int kk = 0; kk < 16; ++kk) d2[kk] = (kk == k) ? e : d2[kk];
+        }
+    }
+}
 
 template <int MODE, typename T>
 __global__ void __launch_bounds__(kXkThreads, 4)
@@ -107,7 +141,7 @@ xk_dist_kernel(DistParams<T> prm, int N, int M, int D, SplitInfo sp) {
                 if (cslot0 >= ncg * 32) continue;
                 f32x16& d2 = acc[rt][cg];
                 // near pairs and everything below 4 x the floor of utils.py:61, which only an exact value may decide: one pair per
-                // lane and turn (register k of a lane is column 8 (k / 4) + 4 half + k % 4 of the group)
+                // lane and turn (xk_dist_patch_near)
                 if (prm.guard > 0.f && __any(min16(d2) < thr)) {
                     uint32_t near = 0u;
 #pragma unroll
@@ -118,22 +152,7 @@ xk_dist_kernel(DistParams<T> prm, int N, int M, int D, SplitInfo sp) {
                     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
                     const int nh = ln >> 5;
                     const T* xi = xb + (long)lds.idx[wr * (kXkRT * 32) + rt * 32 + (ln & 31)] * D;
-                    while (near != 0u) {
-                        const int k = __builtin_ctz(near);
-                        near &= near - 1u;
-                        const int j = lds.idx[kXkRows + cslot0 + (k >> 2) * 8 + nh * 4 + (k & 3)];
-                        if (j >= 0) {
-                            const T* yj = yb + (long)j * D;
-                            float e = 0.f;
-                            for (int d = 0; d < D; ++d) {
-                                const float df = (to_f32<T>(xi[d]) - to_f32<T>(yj[d])) * prm.t;
-                                e = __builtin_fmaf(df, df, e);
-                            }
-                            e = fmaxf(e, prm.clamp2);
-#pragma unroll
-                            for (int kk = 0; kk < 16; ++kk) d2[kk] = (kk == k) ? e : d2[kk];
-                        }
-                    }
+                    xk_dist_patch_near<T>(d2, near, xi, yb, &lds.idx[kXkRows + cslot0], nh, D, prm.t, prm.clamp2);
                 }
                 const float* sg = &lds.v[cslot0 + half * 4];
                 float a4[4] = {0.f, 0.f, 0.f, 0.f};

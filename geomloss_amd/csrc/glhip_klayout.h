@@ -9,6 +9,12 @@ namespace glhip {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// The result of a 32 x 32 MFMA: lane (half, i) holds MFMA column i, and its register r the MFMA row (r & 3) + 8 (r >> 2) + 4 half.  One map,
+// read two ways: the kernels that call mfma(Y, X, acc) find there a column of a 32-column group, those whose A operand is a chunk of 32
+// features a feature of the chunk.
+constexpr int reg_column(int k, int half) { return (k >> 2) * 8 + half * 4 + (k & 3); }
+constexpr int reg_feature(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
+
 // K layout of an exponent.
 //   XL_BF16X3 (default): every fp32 operand = three bf16 pieces, six products per coordinate (above).
 //   XL_F16X2  (GLHIP_FLAG_F16X2, round 5): every coordinate = TWO f16 pieces (hi + lo, 22 significant bits, round-to-nearest,

@@ -1,9 +1,8 @@
 // glhip_launch_plan.h — host side of the reductions whose partial per row and column split is (sums[nv], mass, m), and of argmin, which
-// shares their split policy: ONE pass launcher, ONE pass loop over xk_plan_kernel (glhip_plan_apply_xk.h), ONE sizing rule and ONE
-// argument prologue for glhip_api_plan.hip, glhip_api_plan_xk.hip, glhip_api_grad_xk.hip, glhip_api_convgrad_xk.hip and glhip_api_argmin.hip.
+// shares their split policy: ONE pass launcher, ONE pass loop, ONE sizing rule and ONE argument prologue for glhip_api_plan.hip,
+// glhip_api_plan_xk.hip, glhip_api_grad_xk.hip, glhip_api_convgrad_xk.hip, glhip_api_distgrad_xk.hip and glhip_api_argmin.hip; for the three
+// gradient routes of 17 <= D <= 4095 also ONE predicate tail, ONE workspace rule and ONE launch prologue.
 // What the launcher takes and what the sizing calls promise must agree exactly: both read plan_splits and the constants below.
-// glhip_api_distgrad_xk.hip (xk_dist_grad_kernel, glhip_dist_grad_xk.h) uses launch_plan_pass, launch_plan_merge and the sizing rule with a
-// pass loop of its own: its passes are 32 coordinates wide, and launch_xk_plan_passes below stays the loop of xk_plan_kernel alone.
 #pragma once
 
 #include <initializer_list>
@@ -76,21 +75,58 @@ void launch_xk_plan_pass(const P& prm, int B, int N, int M, int D, const Scratch
         [&](const SplitInfo& sp) { launch_plan_merge(prm, B, N, D, sp, st); });
 }
 
-// The passes of xk_plan_kernel over `width` features (the plan: V) or coordinates (the gradients: D), kXkPlanWidth at a time; a pass of
-// <= 32 runs with one chunk.  In the K layout the call asks for.
-template <template <typename> class PP, typename T>
-void launch_xk_plan_passes(PP<T> prm, int width, int B, int N, int M, int D, const Scratch& sc, hipStream_t st) {
-    for (int v0 = 0; v0 < width; v0 += kXkPlanWidth) {
+// THE pass loop: `width` features (the plan: V) or coordinates (the gradients: D), `pass_width` at a time; pass(prm, nch) launches one
+// pass with prm.v0 and prm.nv set, nch = the chunks of 32 it needs.
+template <class P, class Pass>
+void launch_plan_passes(P prm, int width, int pass_width, Pass&& pass) {
+    for (int v0 = 0; v0 < width; v0 += pass_width) {
         prm.v0 = v0;
-        prm.nv = width - v0 < kXkPlanWidth ? width - v0 : kXkPlanWidth;
-        if (prm.nv > 32) {
-            if (sc.h2) launch_xk_plan_pass<T, 2, XL_F16X2>(prm, B, N, M, D, sc, st);
-            else launch_xk_plan_pass<T, 2, XL_BF16X3>(prm, B, N, M, D, sc, st);
-        } else {
-            if (sc.h2) launch_xk_plan_pass<T, 1, XL_F16X2>(prm, B, N, M, D, sc, st);
-            else launch_xk_plan_pass<T, 1, XL_BF16X3>(prm, B, N, M, D, sc, st);
-        }
+        prm.nv = width - v0 < pass_width ? width - v0 : pass_width;
+        pass(prm, (prm.nv + 31) / 32);
     }
+}
+
+// The passes of xk_plan_kernel, kXkPlanWidth at a time; a pass of <= 32 runs with one chunk.  In the K layout the call asks for.
+template <template <typename> class PP, typename T>
+void launch_xk_plan_passes(const PP<T>& prm, int width, int B, int N, int M, int D, const Scratch& sc, hipStream_t st) {
+    launch_plan_passes(prm, width, kXkPlanWidth, [&](const PP<T>& pass, int nch) {
+        if (nch > 1) {
+            if (sc.h2) launch_xk_plan_pass<T, 2, XL_F16X2>(pass, B, N, M, D, sc, st);
+            else launch_xk_plan_pass<T, 2, XL_BF16X3>(pass, B, N, M, D, sc, st);
+        } else {
+            if (sc.h2) launch_xk_plan_pass<T, 1, XL_F16X2>(pass, B, N, M, D, sc, st);
+            else launch_xk_plan_pass<T, 1, XL_BF16X3>(pass, B, N, M, D, sc, st);
+        }
+    });
+}
+
+// ---- The gradient routes of 17 <= D <= 4095 (glhip_api_grad_xk.hip, glhip_api_convgrad_xk.hip, glhip_api_distgrad_xk.hip) ----
+
+// The tail of their predicates, after the arguments are checked: the flag that opts in, none that opts out of the matrix cores, a
+// dimension of the K-chunked kernels, a dense launch within the grid's batch limit.  Host arithmetic only.
+inline int xk_grad_route(int opt_in, int flags, int B, int D, int n_ranges) {
+    if (!(flags & opt_in) || (flags & (GLHIP_FLAG_NO_MFMA | GLHIP_FLAG_DIRECT))) return 0;
+    return (D > kXdMaxD && D <= kXkMaxD && n_ranges == 0 && B <= 65535) ? 1 : 0;
+}
+
+// Their sizing rule: the widest pass carries min(D, pass_width) coordinates; `uses`: what the route's predicate answers for float32 clouds
+inline size_t xk_grad_workspace_bytes(int uses, int B, int N, int M, int D, int flags, int pass_width) {
+    if (B <= 0 || N <= 0 || M <= 0 || (flags & GLHIP_FLAG_NO_SPLIT) || uses != 1) return 0;
+    return plan_pass_workspace_bytes(B, N, M, kXkRows, D < pass_width ? D : pass_width, {kXkPlanSlots});
+}
+
+// Their launch prologue: without columns the sums are empty (gx, and out where wanted, are zeroed); else run(T{}, scratch) on the cloud type
+template <class Run>
+int xk_grad_launch(float* gx, float* out, int B, int N, int M, int D, int in_dtype, void* workspace, size_t workspace_bytes, int flags,
+                   hipStream_t st, Run&& run) {
+    if (M == 0) {
+        (void)hipMemsetAsync(gx, 0, (size_t)B * N * D * sizeof(float), st);
+        if (out) (void)hipMemsetAsync(out, 0, (size_t)B * N * sizeof(float), st);
+        return GLHIP_OK;
+    }
+    const Scratch sc = make_scratch(workspace, workspace_bytes, flags, 0, N);
+    if (in_dtype == GLHIP_F32) run(float{}, sc); else run(bf16_t{}, sc);
+    return GLHIP_OK;
 }
 
 }  // namespace

@@ -48,6 +48,13 @@
 // sums and mass relative to 2^m.  The merge brings the splits to the largest m, adds and divides.  Its width is a RUN-TIME
 // argument (plan_merge_kernel below, one thread per row and feature) — one merge for every chunk count and any V, instead of one
 // MergeOp instantiation per width.
+//
+// Shared pieces (profiles/xk_plan_pieces.txt).  The plan half exists in three __global__ bodies: plan_apply_kernel here, xk_plan_kernel
+// (glhip_plan_apply_xk.h) and xk_dist_grad_kernel (glhip_dist_grad_xk.h).  What they share as __device__ __forceinline__ pieces is defined
+// here — plan_store_pieces (scale, split and store of one staged feature item), plan_rescale (the lazy rescale; this kernel keeps its
+// inline text: the helper costs the four-chunk instantiations 2 VGPRs), plan_split_weights, plan_chunk_mfma (the six MFMAs of a chunk) —
+// next to the register maps reg_column / reg_feature of glhip_klayout.h.  The staging loops, the fold of a fresh accumulator into the running
+// sums and the meeting of the column halves stay in each body: as pieces they moved registers in one kernel or another.
 #pragma once
 
 #include "glhip_softmin_xd.h"
@@ -102,6 +109,68 @@ __device__ __forceinline__ uint32_t plan_scale_exponent(uint32_t max_bits) {
     return (uint32_t)min(max(se, 1), 254 - kWqShift - 1);
 }
 
+// ---- The pieces of the plan half.  plan_apply_kernel below, xk_plan_kernel (glhip_plan_apply_xk.h) and xk_dist_grad_kernel
+// (glhip_dist_grad_xk.h) are three __global__ bodies that call them (plan_rescale: the latter two); each is __device__ __forceinline__
+// and holds no barrier. ----
+
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+
+// Feature c of four consecutive columns — K slots s0 .. s0 + 3 of one lane half and one instruction — under the power-of-two scale sc,
+// in two f16 pieces: the high one at qb, the low one a piece further ([piece][instruction][lane]: 128 records = 256 uint2 per piece)
+__device__ __forceinline__ void plan_store_pieces(const float (&f)[4], float sc, uint2* qb) {
+    const f32x2_t v01 = {f[0] * sc, f[1] * sc}, v23 = {f[2] * sc, f[3] * sc};
+    const f16x2_t h01 = __builtin_convertvector(v01, f16x2_t), h23 = __builtin_convertvector(v23, f16x2_t);
+    const f16x2_t l01 = __builtin_convertvector(v01 - __builtin_convertvector(h01, f32x2_t), f16x2_t);
+    const f16x2_t l23 = __builtin_convertvector(v23 - __builtin_convertvector(h23, f32x2_t), f16x2_t);
+    qb[0] = uint2{__builtin_bit_cast(uint32_t, h01), __builtin_bit_cast(uint32_t, h23)};
+    qb[256] = uint2{__builtin_bit_cast(uint32_t, l01), __builtin_bit_cast(uint32_t, l23)};
+}
+
+// A block whose row maximum bm (the same in both lane halves of a row) passes the running maximum m of some row of the wavefront
+// brings the running sums and every four-register scalar to the new maximum: factor exactly 1 for the rows that keep theirs.
+template <int NCH, class... Scal4>
+__device__ __forceinline__ void plan_rescale(float bm, float& m, f32x16 (&acc)[NCH], Scal4&... scal4) {
+    if (!__any(bm > m)) return;
+    const float mn = fmaxf(m, bm);
+    const float rs = fast_exp2(m - mn);
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[ch][r] *= rs;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) ((scal4[k] *= rs), ...);
+    m = mn;
+}
+
+// Two weights into their two f16 pieces, K slots k and k + 1 of the B operands: one v_cvt_pk_f16_f32 per two high pieces, both read
+// back from it (wsum_t32q_kernel)
+__device__ __forceinline__ void plan_split_weights(f32x2_t w, int k, Pack16h (&whi)[2], Pack16h (&wlo)[2]) {
+    const f16x2_t hh = __builtin_convertvector(w, f16x2_t);
+    const f32x2_t back = __builtin_convertvector(hh, f32x2_t);
+    const f16x2_t ll = __builtin_convertvector(w - back, f16x2_t);
+    whi[k >> 3].v[k & 7] = hh[0];
+    whi[k >> 3].v[(k & 7) + 1] = hh[1];
+    wlo[k >> 3].v[k & 7] = ll[0];
+    wlo[k >> 3].v[(k & 7) + 1] = ll[1];
+}
+
+// One chunk of 32 features times the weights of a 32-column block, into a fresh accumulator: six v_mfma_f32_32x32x16_f16.  qg: this
+// lane's records of the chunk (piece p, instruction I: qg[p * 128 + I * 64]).  The fold into the running sums stays with the caller.
+__device__ __forceinline__ f32x16 plan_chunk_mfma(const uint4* qg, const Pack16h (&whi)[2], const Pack16h (&wlo)[2]) {
+    const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    Pack16h qh0, qh1, ql0, ql1;
+    qh0.u = qg[0]; qh1.u = qg[64]; ql0.u = qg[128]; ql1.u = qg[192];
+    // smallest products first: lo hi, hi lo, hi hi
+    f32x16 t = __builtin_amdgcn_mfma_f32_32x32x16_f16(ql0.v, whi[0].v, zero16, 0, 0, 0);
+    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(ql1.v, whi[1].v, t, 0, 0, 0);
+    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(qh0.v, wlo[0].v, t, 0, 0, 0);
+    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(qh1.v, wlo[1].v, t, 0, 0, 0);
+    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(qh0.v, whi[0].v, t, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(qh1.v, whi[1].v, t, 0, 0, 0);
+}
+
 template <int D, typename T, int NCH, int L>
 __global__ void __launch_bounds__(kPlanNW * 64, (PlanShape<D, NCH, L>::template waves<T>()))
 plan_apply_kernel(PlanParams<T> prm, int N, int M, SplitInfo sp) {
@@ -113,8 +182,6 @@ plan_apply_kernel(PlanParams<T> prm, int N, int M, SplitInfo sp) {
     static_assert(kTileD <= kThreads, "one column per thread");
     static_assert(NCH == 1 || NCH == 2 || NCH == 4, "1, 2 or 4 chunks of 32 features per pass");
     static_assert(kItems * kThreads == (kTileD / 4) * VC, "whole items per thread");
-    typedef float f32x2_t __attribute__((ext_vector_type(2)));
-    typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
     __shared__ uint4 tile[kTileD * NBP];                 // exponent records: [column group of 32][K block][column]
     __shared__ uint4 tileQ[kGroups * S::kQRecs];         // feature A operands: [group][chunk][piece][instruction][lane = 32 h + c] x 8 f16
     __shared__ uint32_t tileMax[2][VC];                  // largest |f| bit pattern per feature, tiles of even / odd index
@@ -259,16 +326,10 @@ plan_apply_kernel(PlanParams<T> prm, int N, int M, SplitInfo sp) {
             const int t = cq << 2;
             if (t < npad) {
                 const float sc = __uint_as_float(plan_scale_exponent(tileMax[parity][c]) << 23);
-                const f32x2_t v01 = {fv[k][0] * sc, fv[k][1] * sc}, v23 = {fv[k][2] * sc, fv[k][3] * sc};
-                const f16x2_t h01 = __builtin_convertvector(v01, f16x2_t), h23 = __builtin_convertvector(v23, f16x2_t);
-                const f16x2_t l01 = __builtin_convertvector(v01 - __builtin_convertvector(h01, f32x2_t), f16x2_t);
-                const f16x2_t l23 = __builtin_convertvector(v23 - __builtin_convertvector(h23, f32x2_t), f16x2_t);
                 const int jj = t & 31;
                 const int r = (jj >> 3) << 2, hq = (jj >> 2) & 1;
                 uint2* qb = reinterpret_cast<uint2*>(&tileQ[(t >> 5) * S::kQRecs + (c >> 5) * (4 * 64) + (r >> 3) * 64 + hq * 32 + (c & 31)]) + ((r & 7) >> 2);
-                // [piece][instruction][lane]: 128 records = 256 uint2 per piece
-                qb[0] = uint2{__builtin_bit_cast(uint32_t, h01), __builtin_bit_cast(uint32_t, h23)};
-                qb[256] = uint2{__builtin_bit_cast(uint32_t, l01), __builtin_bit_cast(uint32_t, l23)};
+                plan_store_pieces(fv[k], sc, qb);
             }
         }
         __syncthreads();
@@ -296,31 +357,16 @@ plan_apply_kernel(PlanParams<T> prm, int N, int M, SplitInfo sp) {
             }
             Pack16h whi[2], wlo[2];
 #pragma unroll
-            for (int k = 0; k < 16; k += 2) {      // pairs: one v_cvt_pk_f16_f32 per two high pieces, both read back from it (wsum_t32q_kernel)
+            for (int k = 0; k < 16; k += 2) {
                 const f32x2_t w = {fast_exp2(u[k] - m) * (float)(1 << kWqShift), fast_exp2(u[k + 1] - m) * (float)(1 << kWqShift)};
                 mass4[k & 3] += w[0];
                 mass4[(k & 3) + 1] += w[1];
-                const f16x2_t hh = __builtin_convertvector(w, f16x2_t);
-                const f32x2_t back = __builtin_convertvector(hh, f32x2_t);
-                const f16x2_t ll = __builtin_convertvector(w - back, f16x2_t);
-                whi[k >> 3].v[k & 7] = hh[0];
-                whi[k >> 3].v[(k & 7) + 1] = hh[1];
-                wlo[k >> 3].v[k & 7] = ll[0];
-                wlo[k >> 3].v[(k & 7) + 1] = ll[1];
+                plan_split_weights(w, k, whi, wlo);
             }
 #pragma unroll
             for (int ch = 0; ch < NCH; ++ch) {
-                const uint4* qg = &tileQ[G * S::kQRecs + ch * (4 * 64) + lane];      // piece p, instruction I: qg[p * 128 + I * 64]
-                Pack16h qh0, qh1, ql0, ql1;
-                qh0.u = qg[0]; qh1.u = qg[64]; ql0.u = qg[128]; ql1.u = qg[192];
-                // smallest products first: lo hi, hi lo, hi hi
-                f32x16 t = __builtin_amdgcn_mfma_f32_32x32x16_f16(ql0.v, whi[0].v, zero16, 0, 0, 0);
-                t = __builtin_amdgcn_mfma_f32_32x32x16_f16(ql1.v, whi[1].v, t, 0, 0, 0);
-                t = __builtin_amdgcn_mfma_f32_32x32x16_f16(qh0.v, wlo[0].v, t, 0, 0, 0);
-                t = __builtin_amdgcn_mfma_f32_32x32x16_f16(qh1.v, wlo[1].v, t, 0, 0, 0);
-                t = __builtin_amdgcn_mfma_f32_32x32x16_f16(qh0.v, whi[0].v, t, 0, 0, 0);
-                t = __builtin_amdgcn_mfma_f32_32x32x16_f16(qh1.v, whi[1].v, t, 0, 0, 0);
-                // register r <-> feature (r & 3) + 8 (r >> 2) + 4 half of the chunk: four broadcast 16-byte reads of the inverse scales
+                const f32x16 t = plan_chunk_mfma(&tileQ[G * S::kQRecs + ch * (4 * 64) + lane], whi, wlo);
+                // register r <-> feature reg_feature(r, half) of the chunk: four broadcast 16-byte reads of the inverse scales
                 const float* ig = &tileInv[ch * 32 + half * 4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -347,7 +393,7 @@ plan_apply_kernel(PlanParams<T> prm, int N, int M, SplitInfo sp) {
             for (int ch = 0; ch < NCH; ++ch) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int c = 32 * ch + (r & 3) + 8 * (r >> 2) + 4 * half;
+                    const int c = 32 * ch + reg_feature(r, half);
                     if (c < prm.nv) {
                         if (ns == 1) orow[c] = (mass > 0.f) ? acc[ch][r] / mass : 0.f;      // a division: exact where the quotient is
                         else part[c] = acc[ch][r];

@@ -54,6 +54,10 @@
 // glhip_kernel_conv_bwd_x / glhip_kernel_conv_fwd_grad of the gaussian kernel, 17 <= D <= 4095, are the third instantiation, on
 // XkGaussGradParams (glhip_gauss_grad_xk.h, sites marked GAUSS): the exponents of the gaussian product, features v_j (y_j - centre),
 // the signed mass sum_j w_ij v_j (lds.xk.v carries v_j), and an epilogue that multiplies the sums by 2^m instead of normalising them.
+//
+// Pieces of the plan half shared with plan_apply_kernel and xk_dist_grad_kernel: plan_store_pieces, plan_rescale, plan_split_weights and
+// plan_chunk_mfma (glhip_plan_apply.h), reg_column / reg_feature (glhip_klayout.h).  Pieces, never bodies: see above and
+// profiles/xk_plan_pieces.txt for what stayed inline here (feature load, staging loop, fold, parking of the wc == 1 half) and why.
 #pragma once
 
 #include "glhip_plan_apply.h"
@@ -95,8 +99,6 @@ xk_plan_kernel(P prm, int N, int M, int D, SplitInfo sp) {
     static_assert(NCH == 1 || NCH == 2, "1 or 2 chunks of 32 features per pass");
     static_assert(kFItems * kXkThreads == (kXkCols / 4) * VC, "whole items per thread");
     static_assert((VC + 2) * kXkRows * sizeof(float) <= sizeof(XkLds::buf), "the column halves meet in the stage buffer");
-    typedef float f32x2_t __attribute__((ext_vector_type(2)));
-    typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
     __shared__ XkPlanLds<NCH> lds;
 
     int bx, b, split;
@@ -201,16 +203,10 @@ xk_plan_kernel(P prm, int N, int M, int D, SplitInfo sp) {
             const int t = cq << 2;
             if (t < ncg * 32) {
                 const float sc = __uint_as_float(plan_scale_exponent(lds.fmax[parity][c]) << 23);
-                const f32x2_t v01 = {fv[k][0] * sc, fv[k][1] * sc}, v23 = {fv[k][2] * sc, fv[k][3] * sc};
-                const f16x2_t h01 = __builtin_convertvector(v01, f16x2_t), h23 = __builtin_convertvector(v23, f16x2_t);
-                const f16x2_t l01 = __builtin_convertvector(v01 - __builtin_convertvector(h01, f32x2_t), f16x2_t);
-                const f16x2_t l23 = __builtin_convertvector(v23 - __builtin_convertvector(h23, f32x2_t), f16x2_t);
                 const int jj = t & 31;
                 const int r = (jj >> 3) << 2, hq = (jj >> 2) & 1;
                 uint2* qb = reinterpret_cast<uint2*>(&lds.q[(t >> 5) * kQRecs + (c >> 5) * (4 * 64) + (r >> 3) * 64 + hq * 32 + (c & 31)]) + ((r & 7) >> 2);
-                // [piece][instruction][lane]: 128 records = 256 uint2 per piece
-                qb[0] = uint2{__builtin_bit_cast(uint32_t, h01), __builtin_bit_cast(uint32_t, h23)};
-                qb[256] = uint2{__builtin_bit_cast(uint32_t, l01), __builtin_bit_cast(uint32_t, l23)};
+                plan_store_pieces(fv[k], sc, qb);
             }
         }
         __syncthreads();
@@ -244,7 +240,7 @@ xk_plan_kernel(P prm, int N, int M, int D, SplitInfo sp) {
             for (int cg = 0; cg < kXkCG; ++cg) {
                 const int G = wc * kXkCG + cg;
                 if (G >= ncg) continue;
-                // register r <-> column 8 (r >> 2) + 4 half + (r & 3) of the group: four broadcast 16-byte reads of the mask
+                // register r <-> column reg_column(r, half) of the group: four broadcast 16-byte reads of the mask
                 f32x16 u;
                 const float* mk = &lds.xk.v[G * 32 + half * 4];
 #pragma unroll
@@ -264,51 +260,25 @@ xk_plan_kernel(P prm, int N, int M, int D, SplitInfo sp) {
                 // weight of a row is 2^13 EXACTLY.  A new maximum rescales the running sums (factor exactly 1 for the rows that keep theirs)
                 float bm = max16(u);
                 bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
-                if (__any(bm > m[rt])) {
-                    const float mn = fmaxf(m[rt], bm);
-                    const float rs = fast_exp2(m[rt] - mn);
-#pragma unroll
-                    for (int ch = 0; ch < NCH; ++ch) {
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) pacc[rt][ch][r] *= rs;
-                    }
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) mass4[rt][k] *= rs;
-                    m[rt] = mn;
-                }
+                plan_rescale(bm, m[rt], pacc[rt], mass4[rt]);
                 Pack16h whi[2], wlo[2];
 #pragma unroll
-                for (int k = 0; k < 16; k += 2) {      // pairs: one v_cvt_pk_f16_f32 per two high pieces, both read back from it
+                for (int k = 0; k < 16; k += 2) {
                     const f32x2_t w = {fast_exp2(u[k] - m[rt]) * (float)(1 << kWqShift), fast_exp2(u[k + 1] - m[rt]) * (float)(1 << kWqShift)};
                     if constexpr (GAUSS) {                    // the signed mass: the unsplit fp32 weights times v_j
-                        const float2 v2 = *reinterpret_cast<const float2*>(mk + (k >> 2) * 8 + (k & 3));
+                        const float2 v2 = *reinterpret_cast<const float2*>(mk + reg_column(k, 0));      // (mk carries the lane half)
                         mass4[rt][k & 3] = __builtin_fmaf(w[0], v2.x, mass4[rt][k & 3]);
                         mass4[rt][(k & 3) + 1] = __builtin_fmaf(w[1], v2.y, mass4[rt][(k & 3) + 1]);
                     } else {
                         mass4[rt][k & 3] += w[0];
                         mass4[rt][(k & 3) + 1] += w[1];
                     }
-                    const f16x2_t hh = __builtin_convertvector(w, f16x2_t);
-                    const f32x2_t back = __builtin_convertvector(hh, f32x2_t);
-                    const f16x2_t ll = __builtin_convertvector(w - back, f16x2_t);
-                    whi[k >> 3].v[k & 7] = hh[0];
-                    whi[k >> 3].v[(k & 7) + 1] = hh[1];
-                    wlo[k >> 3].v[k & 7] = ll[0];
-                    wlo[k >> 3].v[(k & 7) + 1] = ll[1];
+                    plan_split_weights(w, k, whi, wlo);
                 }
 #pragma unroll
                 for (int ch = 0; ch < NCH; ++ch) {
-                    const uint4* qg = &lds.q[G * kQRecs + ch * (4 * 64) + lane];      // piece p, instruction I: qg[p * 128 + I * 64]
-                    Pack16h qh0, qh1, ql0, ql1;
-                    qh0.u = qg[0]; qh1.u = qg[64]; ql0.u = qg[128]; ql1.u = qg[192];
-                    // smallest products first: lo hi, hi lo, hi hi
-                    f32x16 t = __builtin_amdgcn_mfma_f32_32x32x16_f16(ql0.v, whi[0].v, zero16, 0, 0, 0);
-                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(ql1.v, whi[1].v, t, 0, 0, 0);
-                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(qh0.v, wlo[0].v, t, 0, 0, 0);
-                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(qh1.v, wlo[1].v, t, 0, 0, 0);
-                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(qh0.v, whi[0].v, t, 0, 0, 0);
-                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(qh1.v, whi[1].v, t, 0, 0, 0);
-                    // register r <-> feature (r & 3) + 8 (r >> 2) + 4 half of the chunk: four broadcast 16-byte reads of the inverse scales
+                    const f32x16 t = plan_chunk_mfma(&lds.q[G * kQRecs + ch * (4 * 64) + lane], whi, wlo);
+                    // register r <-> feature reg_feature(r, half) of the chunk: four broadcast 16-byte reads of the inverse scales
                     const float* ig = &lds.inv[ch * 32 + half * 4];
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
@@ -337,7 +307,7 @@ xk_plan_kernel(P prm, int N, int M, int D, SplitInfo sp) {
 #pragma unroll
             for (int ch = 0; ch < NCH; ++ch) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) mrg[(32 * ch + (r & 3) + 8 * (r >> 2) + 4 * half) * kXkRows + r_local] = pacc[rt][ch][r];
+                for (int r = 0; r < 16; ++r) mrg[(32 * ch + reg_feature(r, half)) * kXkRows + r_local] = pacc[rt][ch][r];
             }
             if (half == 0) {
                 mrg[VC * kXkRows + r_local] = mass[rt];
@@ -378,7 +348,7 @@ xk_plan_kernel(P prm, int N, int M, int D, SplitInfo sp) {
         for (int ch = 0; ch < NCH; ++ch) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int c = 32 * ch + (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int c = 32 * ch + reg_feature(r, half);
                 if (c < prm.nv) {
                     const float s = __builtin_fmaf(mrg[c * kXkRows + r_local], rs2, pacc[rt][ch][r] * rs1);
                     if (ns > 1) {

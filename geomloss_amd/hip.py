@@ -352,32 +352,50 @@ def sinkhorn_extrapolate4_raw(x, y, xc, yc, a_log_c, b_log_c, pots, eps, damping
     return tuple(outs)
 
 
+def _route_predicate(name, args, shown):
+    """One of the library's route predicates (host arithmetic, no GPU): 1 / 0, or ``ValueError`` for arguments the entry point rejects."""
+    r = int(getattr(load_library(), name)(*(int(a) for a in args)))
+    if r < 0:
+        raise ValueError(f"{name}: bad argument ({shown})")
+    return r
+
+
 def softmin_bwd_x_uses_plan(B, N, M, D, p=2, dtype=F32, flags=0, n_ranges=0):
     """Whether ``glhip_softmin_bwd_x`` runs the matrix-core gradient of 17 <= D <= 4095 for this launch (``FLAG_XK_GRAD``): the
     library's own predicate (host arithmetic, no GPU).  1 / 0, or ``ValueError`` for arguments the entry point rejects."""
-    lib = load_library()
-    r = int(lib.glhip_softmin_bwd_x_uses_plan(int(B), int(N), int(M), int(D), int(p), int(dtype), int(flags), int(n_ranges)))
-    if r < 0:
-        raise ValueError(f"glhip_softmin_bwd_x_uses_plan: bad argument (B {B}, N {N}, M {M}, D {D}, p {p}, dtype {dtype}, n_ranges {n_ranges})")
-    return r
+    return _route_predicate("glhip_softmin_bwd_x_uses_plan", (B, N, M, D, p, dtype, flags, n_ranges),
+                            f"B {B}, N {N}, M {M}, D {D}, p {p}, dtype {dtype}, n_ranges {n_ranges}")
 
 
 def dist_grad_uses_xk(op, B, N, M, D, dtype=F32, flags=0, n_ranges=0):
     """Whether ``glhip_softmin_bwd_x`` with p = 1 (``op`` "softmin_p1") resp. ``glhip_kernel_conv_bwd_x`` / ``glhip_kernel_conv_fwd_grad``
     (``op`` "laplacian" / "energy", or a kernel kind code) run the matrix-core distance gradient of 17 <= D <= 4095 for this launch
     (``FLAG_XK_DIST_GRAD``): the library's own predicate (host arithmetic, no GPU).  1 / 0, or ``ValueError`` for bad arguments."""
-    lib = load_library()
-    r = int(lib.glhip_dist_grad_uses_xk(int(DIST_GRAD_OPS.get(op, op)), int(B), int(N), int(M), int(D), int(dtype), int(flags), int(n_ranges)))
-    if r < 0:
-        raise ValueError(f"glhip_dist_grad_uses_xk: bad argument (op {op}, B {B}, N {N}, M {M}, D {D}, dtype {dtype}, n_ranges {n_ranges})")
-    return r
+    return _route_predicate("glhip_dist_grad_uses_xk", (DIST_GRAD_OPS.get(op, op), B, N, M, D, dtype, flags, n_ranges),
+                            f"op {op}, B {B}, N {N}, M {M}, D {D}, dtype {dtype}, n_ranges {n_ranges}")
 
 
-def _dist_grad_workspace(lib, x, B, N, M, D, flags, workspace):
-    """The split partials of the matrix-core distance gradient (``glhip_dist_grad_workspace_bytes``)."""
-    nbytes = int(lib.glhip_dist_grad_workspace_bytes(B, N, M, D, int(flags))) if workspace else 0
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
-    return ws, (None if ws is None else ws.data_ptr(), nbytes)
+def kernel_conv_grad_uses_xk(kind, B, N, M, D, dtype=F32, flags=0, n_ranges=0):
+    """Whether ``glhip_kernel_conv_bwd_x`` / ``glhip_kernel_conv_fwd_grad`` run the matrix-core gaussian gradient of 17 <= D <= 4095 for
+    this launch (``FLAG_XK_GRAD``): the library's own predicate (host arithmetic, no GPU); ``kind``: a name or a code.  1 / 0, or
+    ``ValueError`` for arguments the entry points reject."""
+    return _route_predicate("glhip_kernel_conv_grad_uses_xk", (KERNEL_KINDS.get(kind, kind), B, N, M, D, dtype, flags, n_ranges),
+                            f"kind {kind}, B {B}, N {N}, M {M}, D {D}, dtype {dtype}, n_ranges {n_ranges}")
+
+
+def _grad_workspace(lib, x, B, N, M, D, ranges, flags, workspace, routes):
+    """The workspace of a gradient launch.  ``routes``: the matrix-core routes of 17 <= D <= 4095 the entry point has, in the order it asks
+    them, as (predicate name, its arguments before the dtype, sizing call name).  The first route whose predicate — the library's own —
+    takes the launch sizes its split partials itself; every other launch takes ``glhip_workspace_bytes``."""
+    n_ranges = 0 if ranges is None else int(ranges.ranges_i.shape[0])
+    for uses, args, sizing in routes:
+        if getattr(lib, uses)(*args, _dtype_code(x), int(flags), n_ranges) == 1:
+            nbytes = int(getattr(lib, sizing)(B, N, M, D, int(flags))) if workspace else 0
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+            return ws, (None if ws is None else ws.data_ptr(), nbytes)
+    if workspace:
+        return _workspace(lib, x, B, N, M, D, ranges)
+    return None, (None, 0)
 
 
 def softmin_bwd_x_raw(x, y, h, out, grad_out, eps, p=2, ranges=None, flags=0, workspace=True):
@@ -393,19 +411,11 @@ def softmin_bwd_x_raw(x, y, h, out, grad_out, eps, p=2, ranges=None, flags=0, wo
         _check(rc, lib)
         return gx
     gx = torch.empty((B, N, D), dtype=torch.float32, device=x.device)
-    n_ranges = 0 if ranges is None else int(ranges.ranges_i.shape[0])
     with torch.cuda.device(x.device):
-        if lib.glhip_softmin_bwd_x_uses_plan(B, N, M, D, int(p), _dtype_code(x), int(flags), n_ranges) == 1:
-            # the matrix-core gradient sizes its own split partials (glhip_softmin_bwd_x_workspace_bytes)
-            nbytes = int(lib.glhip_softmin_bwd_x_workspace_bytes(B, N, M, D, int(flags))) if workspace else 0
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
-            ws_args = (None if ws is None else ws.data_ptr(), nbytes)
-        elif int(p) == 1 and lib.glhip_dist_grad_uses_xk(0, B, N, M, D, _dtype_code(x), int(flags), n_ranges) == 1:
-            ws, ws_args = _dist_grad_workspace(lib, x, B, N, M, D, flags, workspace)
-        elif workspace:
-            ws, ws_args = _workspace(lib, x, B, N, M, D, ranges)
-        else:
-            ws, ws_args = None, (None, 0)
+        routes = [("glhip_softmin_bwd_x_uses_plan", (B, N, M, D, int(p)), "glhip_softmin_bwd_x_workspace_bytes")]
+        if int(p) == 1:
+            routes.append(("glhip_dist_grad_uses_xk", (DIST_GRAD_OPS["softmin_p1"], B, N, M, D), "glhip_dist_grad_workspace_bytes"))
+        ws, ws_args = _grad_workspace(lib, x, B, N, M, D, ranges, flags, workspace, routes)
         rc = lib.glhip_softmin_bwd_x(x.data_ptr(), y.data_ptr(), h.data_ptr(), out.data_ptr(), grad_out.data_ptr(),
                                      gx.data_ptr(), B, N, M, D, float(eps), int(p), _dtype_code(x),
                                      *_range_args(ranges, B), *ws_args, int(flags), _stream(x))
@@ -487,32 +497,13 @@ def kernel_conv_fwd_raw(kind, x, y, v, blur, ranges=None, flags=0):
     return out
 
 
-def kernel_conv_grad_uses_xk(kind, B, N, M, D, dtype=F32, flags=0, n_ranges=0):
-    """Whether ``glhip_kernel_conv_bwd_x`` / ``glhip_kernel_conv_fwd_grad`` run the matrix-core gaussian gradient of 17 <= D <= 4095 for
-    this launch (``FLAG_XK_GRAD``): the library's own predicate (host arithmetic, no GPU); ``kind``: a name or a code.  1 / 0, or
-    ``ValueError`` for arguments the entry points reject."""
-    lib = load_library()
-    r = int(lib.glhip_kernel_conv_grad_uses_xk(int(KERNEL_KINDS.get(kind, kind)), int(B), int(N), int(M), int(D), int(dtype), int(flags),
-                                               int(n_ranges)))
-    if r < 0:
-        raise ValueError(f"glhip_kernel_conv_grad_uses_xk: bad argument (kind {kind}, B {B}, N {N}, M {M}, D {D}, dtype {dtype}, "
-                         f"n_ranges {n_ranges})")
-    return r
-
-
-def _conv_grad_workspace(lib, kind, x, B, N, M, D, ranges, flags, workspace):
-    """The workspace of a kernel gradient launch: the matrix-core gaussian gradient of 17 <= D <= 4095 sizes its own split partials
-    (``glhip_kernel_conv_grad_workspace_bytes``), every other launch takes ``glhip_workspace_bytes``."""
-    n_ranges = 0 if ranges is None else int(ranges.ranges_i.shape[0])
-    if lib.glhip_kernel_conv_grad_uses_xk(int(kind), B, N, M, D, _dtype_code(x), int(flags), n_ranges) == 1:
-        nbytes = int(lib.glhip_kernel_conv_grad_workspace_bytes(B, N, M, D, int(flags))) if workspace else 0
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
-        return ws, (None if ws is None else ws.data_ptr(), nbytes)
-    if int(kind) in (LAPLACIAN, ENERGY) and lib.glhip_dist_grad_uses_xk(int(kind), B, N, M, D, _dtype_code(x), int(flags), n_ranges) == 1:
-        return _dist_grad_workspace(lib, x, B, N, M, D, flags, workspace)      # (the ops of the two kinds are their kind codes)
-    if workspace:
-        return _workspace(lib, x, B, N, M, D, ranges)
-    return None, (None, 0)
+def _conv_grad_routes(kind, B, N, M, D):
+    """The matrix-core routes of ``glhip_kernel_conv_bwd_x`` / ``glhip_kernel_conv_fwd_grad`` (``_grad_workspace``): the gaussian gradient, then
+    the distance gradient of the laplacian and energy kernels (their ops are their kind codes)."""
+    routes = [("glhip_kernel_conv_grad_uses_xk", (int(kind), B, N, M, D), "glhip_kernel_conv_grad_workspace_bytes")]
+    if int(kind) in (LAPLACIAN, ENERGY):
+        routes.append(("glhip_dist_grad_uses_xk", (int(kind), B, N, M, D), "glhip_dist_grad_workspace_bytes"))
+    return routes
 
 
 def kernel_conv_bwd_x_raw(kind, x, y, v, g, blur, ranges=None, flags=0, workspace=True):
@@ -529,7 +520,7 @@ def kernel_conv_bwd_x_raw(kind, x, y, v, g, blur, ranges=None, flags=0, workspac
         return gx
     gx = torch.empty((B, N, D), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        ws, ws_args = _conv_grad_workspace(lib, kind, x, B, N, M, D, ranges, flags, workspace)
+        ws, ws_args = _grad_workspace(lib, x, B, N, M, D, ranges, flags, workspace, _conv_grad_routes(kind, B, N, M, D))
         rc = lib.glhip_kernel_conv_bwd_x(int(kind), x.data_ptr(), y.data_ptr(), v.data_ptr(), g.data_ptr(),
                                          gx.data_ptr(), B, N, M, D, float(blur), _dtype_code(x),
                                          *_range_args(ranges, B), *ws_args, int(flags), _stream(x))
@@ -548,7 +539,7 @@ def kernel_conv_fwd_grad_raw(kind, x, y, v, blur, ranges=None, flags=0, workspac
     out = torch.empty((B, N), dtype=torch.float32, device=x.device)
     gu = torch.empty((B, N, D), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        ws, ws_args = _conv_grad_workspace(lib, kind, x, B, N, M, D, ranges, flags, workspace)
+        ws, ws_args = _grad_workspace(lib, x, B, N, M, D, ranges, flags, workspace, _conv_grad_routes(kind, B, N, M, D))
         rc = lib.glhip_kernel_conv_fwd_grad(int(kind), x.data_ptr(), y.data_ptr(), v.data_ptr(), out.data_ptr(), gu.data_ptr(),
                                             B, N, M, D, float(blur), _dtype_code(x), *_range_args(ranges, B), *ws_args,
                                             int(flags), _stream(x))
