@@ -7,96 +7,24 @@ namespace glhip {
 thread_local char g_err[512] = "";
 }
 
+// XdShape<D>::NBP of the default layout for a run-time D (0 outside 4 <= D <= 16)
+#define GL_NBP(DD) XdShape<DD>::NBP
+static const int kXdNBP[] = {GL_NBP(4), GL_NBP(5), GL_NBP(6), GL_NBP(7), GL_NBP(8), GL_NBP(9), GL_NBP(10), GL_NBP(11), GL_NBP(12), GL_NBP(13), GL_NBP(14), GL_NBP(15), GL_NBP(16)};
+#undef GL_NBP
+static_assert(sizeof kXdNBP / sizeof kXdNBP[0] == kXdMaxD - 3, "one entry per dimension of the xd kernels");
+
 extern "C" {
 
 int glhip_version(void) { return GLHIP_VERSION; }
 
 size_t glhip_workspace_bytes(int B, int N, int M, int D, int n_ranges) {
-    if (B <= 0 || N <= 0 || M <= 0 || D < 1 || D > kXkMaxD) return 0;   // the generic-D kernels do not split
-    if (D > kXdMaxD) {   // 17 <= D <= 4095 (glhip_softmin_xk.h): split partials of 2 floats per row — what launch_xk_l takes, nothing else
-        int nf = choose_splits(n_ranges > 0 ? n_ranges : (long)B * ((N + kXkRows - 1) / kXkRows), M, n_ranges, 1L << 30);
-        if (n_ranges == 0 && M >= 65536) {
-            const int nx = xcd_splits((long)B * ((N + kXkRows - 1) / kXkRows), M, kXkSlots, 32);
-            nf = nf > nx ? nf : nx;
-            nf = nf > 8 ? nf : 8;
-        }
-        size_t bytes = (size_t)(nf < 2 ? 0 : nf) * (size_t)B * (size_t)N * 2 * sizeof(float);
-        if (n_ranges > 0) bytes += chunk_table_bytes(n_ranges, N, 64);
-        return bytes;
-    }
-    if (D > 3) {   // 4 <= D <= 16 (glhip_softmin_xd.h): split partials of 2 floats per row (+ packed columns on big dense launches)
-        const int ns128 = choose_splits(n_ranges > 0 ? n_ranges : (long)B * ((N + 127) / 128), M, n_ranges, 1L << 30);
-        int nf = ns128;
-        if (n_ranges == 0 && M >= 65536) {
-            for (int rows = 256; rows <= 512; rows *= 2) {
-                const int nx = xcd_splits((long)B * ((N + rows - 1) / rows), M, kXdSlots, 32);
-                nf = nf > nx ? nf : nx;
-            }
-        }
-        if (n_ranges == 0) {      // small dense launches of the distance kernels split further (dist_small_launch_splits, glhip_launch.h)
-            const long rb = (long)B * ((N + 255) / 256);
-            if (rb * nf < 512) {
-                long want = (512 + rb - 1) / rb;
-                want = want < M / 128 ? want : M / 128;
-                want = want < 32 ? want : 32;
-                nf = nf > want ? nf : (int)want;
-            }
-        }
-        // forward partials: 2 floats per row and split; gradient kernels (glhip_wsum_t32.h, 256-row blocks): D + 1
-        size_t bytes = (size_t)(nf < 2 ? 0 : nf) * (size_t)B * (size_t)N * 2 * sizeof(float);
-        int ng = choose_splits(n_ranges > 0 ? n_ranges : (long)B * ((N + 255) / 256), M, n_ranges, 1L << 30);
-        if (n_ranges == 0 && M >= 65536) {
-            const int nx = xcd_splits((long)B * ((N + 255) / 256), M, kXdSlots, 32);
-            ng = ng > nx ? ng : nx;
-        }
-        const size_t grad = (size_t)(ng < 2 ? 0 : ng) * (size_t)B * (size_t)N * (size_t)(D + 1) * sizeof(float);
-        if (n_ranges == 0 && M >= 65536 && (double)B * N * M >= 5e8)    // forward, big dense launches: up to 32 splits (one split's records per XCD L2) + the pre-packed column records
-            bytes = (size_t)32 * (size_t)B * (size_t)N * 2 * sizeof(float) + 256 + (size_t)B * (size_t)((M + 31) / 32) * 32 * (size_t)(2 * ((6 * (D + 1) + 15) / 16)) * sizeof(uint4);   // XdShape<D>::NBP records per column
-        bytes = bytes > grad ? bytes : grad;
-        if (n_ranges > 0) bytes += chunk_table_bytes(n_ranges, N, 64);
-        return bytes;
-    }
-    const long row_blocks = n_ranges > 0 ? n_ranges : (long)B * ((N + 2 * kBlock - 1) / (2 * kBlock));
-    const int ns = choose_splits(row_blocks, M, n_ranges, 1L << 30);
-    size_t bytes = ns < 2 ? 0 : (size_t)ns * (size_t)B * (size_t)N * (size_t)(D + 1) * sizeof(float);   // widest partial: D + 1 floats
-    if (n_ranges == 0 && M >= 65536) {   // the XCD-aware grids want 8 splits (widest partial: D + 1 floats per row)
-        const size_t xcd = (size_t)8 * (size_t)B * (size_t)N * (size_t)(D + 1) * sizeof(float);
-        bytes = bytes > xcd ? bytes : xcd;
-    }
-    {
-        // forward: its split partials (2 floats per row) + the packed column records (64 bytes per column, glhip_softmin_x32.h)
-        int nf;
-        if (n_ranges > 0) {
-            nf = ns;
-        } else {
-            const int ns128 = choose_splits((long)B * ((N + 127) / 128), M, 0, 1L << 30), ns256 = choose_splits((long)B * ((N + 255) / 256), M, 0, 1L << 30);
-            nf = ns128 > ns256 ? ns128 : ns256;
-            if (M >= 65536) {
-                const int x128 = xcd_splits_prepacked((long)B * ((N + 127) / 128), M, kFwdSlots, 32), x256 = xcd_splits_prepacked((long)B * ((N + 255) / 256), M, kFwdSlots, 32);
-                const int nx = x128 > x256 ? x128 : x256;
-                nf = nf > nx ? nf : nx;
-            }
-        }
-        const size_t fwd = (size_t)(nf < 2 ? 0 : nf) * (size_t)B * (size_t)N * 2 * sizeof(float) + 256 + (size_t)B * (size_t)((M + 31) / 32) * 2048;
-        bytes = bytes > fwd ? bytes : fwd;
-    }
-    {
-        // weighted-sum kernels (soft-min gradient, gaussian product / gradient): split partials of up to D + 1 floats per row
-        // + packed records + up to 4 q components per column
-        int nw = ns;
-        if (n_ranges == 0 && M >= 65536) {
-            const int nx = xcd_splits_prepacked((long)B * ((N + 255) / 256), M, kFwdSlots, 32);
-            nw = nw > nx ? nw : nx;
-        }
-        const size_t ws = (size_t)(nw < 2 ? 0 : nw) * (size_t)B * (size_t)N * (size_t)(D + 1) * sizeof(float) + 256 +
-                          (size_t)B * (size_t)((M + 31) / 32) * 2048 + (size_t)4 * B * M * sizeof(float);
-        bytes = bytes > ws ? bytes : ws;
-    }
-    if (n_ranges > 0) bytes += chunk_table_bytes(n_ranges, N, 64);   // row-chunk table of block-sparse launches (64-row tiles: the smallest, GLHIP_FLAG_SMALL_ROW_BLOCKS)
-    if (autosort_applies(B, N, M, D, n_ranges, 0)) {
+    // the launches' own splits and packed columns: forward_workspace_bytes (glhip_split_policy.h), with the kernels' record counts
+    const int nr = X32Layout<XL_BF16X3>::NR, nbp = (D > 3 && D <= kXdMaxD) ? kXdNBP[D - 4] : 0;
+    size_t bytes = forward_workspace_bytes(B, N, M, D, n_ranges, nr, nbp);
+    if (bytes > 0 && autosort_applies(B, N, M, D, n_ranges, 0)) {
         // big dense distance reductions (p = 1, laplacian, energy) sort their clouds inside the workspace and run as a block-sparse launch
         // over slabs of 256 rows (glhip_autosort.h): the sorted copies + what that inner launch asks for
-        const size_t sorted = autosort_bytes(N, M, D) + glhip_workspace_bytes(1, N, M, D, (N + kSortSlab - 1) / kSortSlab);
+        const size_t sorted = autosort_bytes(N, M, D) + forward_workspace_bytes(1, N, M, D, (N + kSortSlab - 1) / kSortSlab, nr, nbp);
         bytes = bytes > sorted ? bytes : sorted;
     }
     return bytes;

@@ -11,7 +11,7 @@ inline int argmin_supported(int B, long N, long M, int D, int p, int dtype, int 
     return (p == 2 && n_ranges == 0 && D <= kXkMaxD && B <= 65535) ? 1 : 0;
 }
 
-// The split policy is plan_splits (glhip_launch_plan.h) with the resident workgroups of the forward kernel of 17 <= D <= 4095; the partial of
+// The split policy is plan_splits (glhip_split_policy.h, through launch_plan_pass) with the resident workgroups of the forward kernel of 17 <= D <= 4095; the partial of
 // a row is (value, index).
 template <typename T>
 void launch_argmin(const ArgminParams<T>& prm, int B, int N, int M, int D, const Scratch& sc, hipStream_t st) {

@@ -7,6 +7,9 @@
 //   kernel products, three modes   conv_family        -> conv_typed<MODE>          (mode 0 reported by glhip_kernel_conv_fwd_family)
 // Parameters come from one builder each (make_softmin_params, make_conv_params: the only place that names the scales of a kernel
 // kind); the one-thread-per-row fallback of both bodies is launch_generic.  The plan family: glhip_launch_plan.h.
+// How many column splits a launch takes, whether it moves to the XCD-aware grid and where it places pre-packed columns is decided in
+// glhip_split_policy.h (plain C++, one plan function per policy; glhip_workspace_bytes is assembled from the same pieces): a launcher here
+// builds its SplitPlan, hands it to SplitLaunch::apply and launches.
 #pragma once
 
 #include <cmath>
@@ -56,38 +59,33 @@ struct Scratch {
     bool h2;            // GLHIP_FLAG_F16X2: exponents from f16 x 2 pieces (glhip_softmin_xd.h) where a kernel has that layout
     ChunkBuf cb;        // block-sparse launches: room for the row-chunk table, carved off the front of the workspace
     Level2 l2;          // the sorted p = 2 launches of glhip_softmin_fwd / glhip_sinkhorn_step: second pruning level (glhip_softmin_x32.h)
-    // pre-packed column records pay for their extra launch from ~5e8 pairs on; they live in the workspace, which
-    // GLHIP_FLAG_NO_SPLIT tells us to leave alone
-    bool prepack(double pairs) const { return ws && (force_pre || (allow_split && pairs >= prepack_min_pairs())); }
+    // what the plan functions of glhip_split_policy.h read
+    SplitFlags policy() const { return SplitFlags{ws != nullptr, allow_split, force_pre, prepack_min_pairs()}; }
     static double prepack_min_pairs() {     // tuning knob: GLHIP_PREPACK_MIN (pairs per launch)
-        static const double v = getenv("GLHIP_PREPACK_MIN") ? atof(getenv("GLHIP_PREPACK_MIN")) : 5e8;
+        static const double v = getenv("GLHIP_PREPACK_MIN") ? atof(getenv("GLHIP_PREPACK_MIN")) : kPrepackMinPairs;
         return v;
     }
 };
 
-// Scratch of one API call.  Block-sparse calls reserve the front of the workspace for the row-chunk table (sized for the
-// smallest row tile of the call: 128 rows, 64 under GLHIP_FLAG_SMALL_ROW_BLOCKS); the rest serves the column splits and the packed
-// columns as before.
+// Scratch of one API call.  Block-sparse calls reserve the front of the workspace for the row-chunk table (chunk_table_rows,
+// glhip_split_policy.h); the rest serves the column splits and the packed columns as before.
 Scratch make_scratch(void* workspace, size_t bytes, int flags, int n_ranges, int N) {
     Scratch sc{workspace, bytes, (flags & GLHIP_FLAG_NO_SPLIT) == 0, (flags & GLHIP_FLAG_PREPACK) != 0,
                (flags & GLHIP_FLAG_SMALL_ROW_BLOCKS) != 0, (flags & GLHIP_FLAG_F16X2) != 0, ChunkBuf(), Level2()};
-    if (n_ranges > 0 && workspace) {
-        // 64-row workgroups (GLHIP_FLAG_SMALL_ROW_BLOCKS) cut a cluster into twice as many chunks: their table is sized for 64-row tiles
-        // (glhip_workspace_bytes reserves that much for every block-sparse call); with less workspace, the 128-row table.
-        for (int rows = sc.small_rows ? 64 : 128; rows <= 128; rows *= 2) {
-            const size_t need = chunk_table_bytes(n_ranges, N, rows);
-            if (bytes >= need) {
-                sc.cb.buf = static_cast<int32_t*>(workspace);
-                sc.cb.capacity = (long)n_ranges + N / rows + 1;
-                sc.ws = static_cast<char*>(workspace) + need;
-                sc.bytes = bytes - need;
-                if (sc.bytes == 0) sc.ws = nullptr;
-                break;
-            }
-        }
+    const int rows = (n_ranges > 0 && workspace) ? chunk_table_rows(bytes, n_ranges, N, sc.small_rows) : 0;
+    if (rows > 0) {
+        const size_t need = chunk_table_bytes(n_ranges, N, rows);
+        sc.cb.buf = static_cast<int32_t*>(workspace);
+        sc.cb.capacity = (long)n_ranges + N / rows + 1;
+        sc.ws = static_cast<char*>(workspace) + need;
+        sc.bytes = bytes - need;
+        if (sc.bytes == 0) sc.ws = nullptr;
     }
     return sc;
 }
+
+// the workgroup heights and the last dimension glhip_split_policy.h sizes the workspace with are the kernels' own
+static_assert(kRowsValu2 == 2 * kBlock && kRowsNW8 == kMfmaRowsPerBlock && kRowsXk == kXkRows && kSizedMaxD == kXkMaxD, "glhip_split_policy.h");
 
 // rows per thread: 2 keeps the LDS read rate at half a ds_read_b128 per row-column step while leaving
 // enough workgroups to fill 256 CUs; small problems use 1 to expose more workgroups.
@@ -126,8 +124,6 @@ void launch_softmin_r(const SoftminParams<T>& prm, const Ranges& rg, int n_range
     }
 }
 
-constexpr long kFwdSlots = 256 * 3;   // resident 8-wave workgroups of the forward / gaussian x32 kernels (<= 84 VGPRs, 32 KiB LDS)
-
 // p = 2 forward on the matrix cores: bf16x3 on 32x32x16 MFMAs, transposed blocks (glhip_softmin_x32.h); same partial format /
 // merge kernel as the VALU op.
 template <int D, typename T, int NW, int L = XL_BF16X3>
@@ -144,30 +140,16 @@ void launch_softmin_mfma_nw(const SoftminParams<T>& prm, const Ranges& rg, int n
     constexpr bool kP2Shape = (L == XL_F16X2) ? NW == 4 : NW == 8;
     const bool p2 = kP2Shape && n_ranges > 0 && sc.l2.groups && sc.l2.home && sc.l2.centre_x && sc.l2.t2;
     const int share = (NW == 4 && L == XL_F16X2 && n_ranges > 0 && !p2) ? 1 : 0;
-    // the number of column splits is still derived from the number of row BLOCKS: deriving it from the (larger) chunk count
-    // gives fewer, longer-lived workgroups and measured 3 % slower on uniform clusters (multiscale at 1e6: 258 vs 250 ms)
     SplitLaunch sl(rg, n_ranges, B, N, M, kRowsPerBlock, 2, sc.ws, sc.bytes, sc.cb, st, share);
-    sl.sp.n_splits = (sc.allow_split && sl.fit >= 2) ? choose_splits(sl.row_blocks, M, n_ranges, sl.fit) : 1;
-    // block-sparse: small row clusters come with short column intervals (the reference's cluster_scale rule makes ~2000 clusters
-    // whatever N is) — gather them into full tiles; clusters of hundreds of points already fill theirs
-    sl.sp.gather = (n_ranges > 0 && N / n_ranges < 128) ? 1 : 0;
-    sl.sp.share = (share && sl.rgc.chunks) ? 1 : 0;
-    // 2-wavefront workgroups (small clusters): 12 of them are resident per CU, three times the 4-wavefront case choose_splits is
-    // tuned for — at least 6 splits (two-scale loss at N = 3e4 / 5e4 / 1e5: 2.11 / 3.01 / 5.30 -> 2.08 / 2.96 / 5.21 ms, three runs each)
-    if (NW == 2 && n_ranges > 0 && sc.allow_split && sl.fit >= 6 && sl.sp.n_splits > 1 && sl.sp.n_splits < 6) sl.sp.n_splits = 6;
-    // large dense problem: exactly 8 column splits, one per XCD (see workgroup_coords)
-    if (sl.xcd_eligible(sc.allow_split))
-        sl.take_xcd(sc.prepack((double)B * N * M) ? xcd_splits_prepacked(sl.row_blocks, M, kFwdSlots, sl.fit, NR * 16.0)
-                                                  : xcd_splits(sl.row_blocks, M, kFwdSlots, sl.fit));
-
+    const SplitPlan plan = plan_x32_fwd(sl, sc.policy(), NW, NR, share && sl.rgc.chunks);
+    sl.apply(plan);
     // Dense launches of the x32 kernel with enough work to pay for one more (tiny) launch split the columns into
     // bf16x3 MFMA records ONCE, in workspace behind the split partials, instead of once per workgroup.
-    PackedCols pk{nullptr, (long)((M + 31) / 32) * (32 * NR)};
-    const size_t packed_bytes = (size_t)B * (size_t)pk.stride * sizeof(uint4);   // either layout fits: ceil(M / 32) whole groups hold the M records-of-NR of [M][NR]
-    const bool pre = sc.prepack((double)B * N * M) && sc.bytes >= sl.packed_offset() + packed_bytes;
+    PackedCols pk{nullptr, packed_stride(M, NR)};
+    const bool pre = plan.pre;
     const bool use_p2 = pre && p2 && !sl.sp.gather;
     if (pre) {
-        pk.rec = reinterpret_cast<uint4*>(static_cast<char*>(sc.ws) + sl.packed_offset());
+        pk.rec = sl.packed<uint4>(plan);
         SoftminParams<T> pprm = prm;      // (the pack kernel reads the rows for the launch's centre only: the one the main kernel takes)
         if (use_p2) pprm.x = static_cast<const T*>(sc.l2.centre_x);
         // the sorted p = 2 launch on the f16 x 2 layout reads group-major columns, like the dense one (its intervals are whole blocks of
@@ -250,24 +232,18 @@ void launch_wsum(const WsumParams<T>& prm, const typename MergeOp::Params& mprm,
                  int N, int M, const Scratch& sc, bool x32, hipStream_t st) {
     static_assert(WsumShape<MODE, D>::kPart == MergeOp::kPartial, "partial formats differ");
     constexpr int NQ = WsumShape<MODE, D>::kNQ;
+    constexpr int NR = X32Layout<XL_BF16X3>::NR;
     SplitLaunch sl(rg, n_ranges, B, N, M, kMfmaRowsPerBlock, MergeOp::kPartial, sc.ws, sc.bytes, sc.cb, st);
-    sl.sp.n_splits = (sc.allow_split && sl.fit >= 2) ? choose_splits(sl.row_blocks, M, n_ranges, sl.fit) : 1;
-    if (sl.xcd_eligible(sc.allow_split))   // one column split per XCD (workgroup_coords)
-        sl.take_xcd(!(wsum_uses_x32<MODE>() && x32) ? 8
-                    : sc.prepack((double)B * N * M) ? xcd_splits_prepacked(sl.row_blocks, M, kFwdSlots, sl.fit)
-                                                    : xcd_splits(sl.row_blocks, M, kFwdSlots, sl.fit));
-
+    const SplitPlan plan = plan_wsum(sl, sc.policy(), wsum_uses_x32<MODE>() && x32, NR, NQ);
+    sl.apply(plan);
     // pre-packed column records + q vectors behind the split partials (see launch_softmin_mfma_nw)
-    PackedCols pk{nullptr, (long)((M + 31) / 32) * 128};
+    PackedCols pk{nullptr, packed_stride(M, NR)};
     PackedQ pq{nullptr, (long)B * M};
-    bool pre = false;
+    const bool pre = plan.pre;
     if constexpr (wsum_uses_x32<MODE>()) {
-        const size_t rec_bytes = (size_t)B * (size_t)pk.stride * sizeof(uint4);
-        const size_t off = sl.packed_offset();
-        pre = x32 && sc.prepack((double)B * N * M) && sc.bytes >= off + rec_bytes + (size_t)NQ * B * M * sizeof(float);
         if (pre) {
-            pk.rec = reinterpret_cast<uint4*>(static_cast<char*>(sc.ws) + off);
-            pq.q = reinterpret_cast<float*>(static_cast<char*>(sc.ws) + off + rec_bytes);
+            pk.rec = sl.packed<uint4>(plan);
+            pq.q = sl.packed<float>(plan, packed_cols_bytes(B, M, NR));
             if (n_ranges > 0) hipLaunchKernelGGL((wsum_pack_kernel<MODE, D, T, false>), dim3((M + kBlock - 1) / kBlock, B, 1), dim3(kBlock), 0, st, prm, N, M, pk, pq);
             else hipLaunchKernelGGL((wsum_pack_kernel<MODE, D, T, true>), dim3((M + 31 + kBlock) / kBlock, B, 1), dim3(kBlock), 0, st, prm, N, M, pk, pq);
         }
@@ -312,7 +288,7 @@ template <int MODE, int D, typename T, class MergeOp, bool FAMILY = false>
 void launch_dist(const DistParams<T>& prm, const typename MergeOp::Params& mprm, const Ranges& rg, int n_ranges, int N, int M,
                  const Scratch& sc, hipStream_t st) {
     SplitLaunch sl(rg, n_ranges, 1, N, M, kDistNW * 32, MergeOp::kPartial, sc.ws, sc.bytes, sc.cb, st);
-    sl.sp.n_splits = (sc.allow_split && sl.fit >= 2) ? choose_splits(sl.row_blocks, M, n_ranges, sl.fit) : 1;
+    sl.apply(plan_rule(sl, sc.allow_split));
     sl.launch_sparse<MergeOp>([&](auto, dim3 grid, const Ranges& r) {
         hipLaunchKernelGGL((dist_x32_kernel<MODE, D, T, kDistNW, FAMILY>), grid, dim3(kDistNW * 64), 0, st, prm, r, N, M, sl.sp);
     }, mprm, st);
@@ -325,7 +301,7 @@ void launch_dist_grad(const ConvParams<T>& prm, const Ranges& rg, int n_ranges, 
     using MergeOp = ConvOp<KIND, D, 1, T, GM == DG_FWDGRAD ? 2 : 1>;
     const DistGradParams<T> gp{dist_params(prm), prm.g, prm.gx, prm.gscale};
     SplitLaunch sl(rg, n_ranges, 1, N, M, kDistNW * 32, MergeOp::kPartial, sc.ws, sc.bytes, sc.cb, st);
-    sl.sp.n_splits = (sc.allow_split && sl.fit >= 2) ? choose_splits(sl.row_blocks, M, n_ranges, sl.fit) : 1;
+    sl.apply(plan_rule(sl, sc.allow_split));
     sl.launch_sparse<MergeOp>([&](auto, dim3 grid, const Ranges& r) {
         hipLaunchKernelGGL((dist_grad_x32_kernel<KIND, GM, D, T, kDistNW>), grid, dim3(kDistNW * 64), 0, st, gp, r, N, M, sl.sp);
     }, prm, st);
@@ -341,9 +317,6 @@ void launch_dist_grad_d(const ConvParams<T>& prm, const Ranges& rg, int n_ranges
 // ---- 4 <= D <= 16 on the matrix cores (glhip_softmin_xd.h): soft-min forward / fused half-step (MODE XD_SOFTMIN) and gaussian
 // product (XD_GAUSS).  Column splits, XCD-aware 1-D grid for big dense launches, row chunks for block-sparse ones and the merge
 // kernels are those of the D <= 3 kernels; there is no pre-packed column copy.
-constexpr int kXdMaxD = 16;
-constexpr long kXdSlots = 256 * 2;    // resident 8-wave workgroups (<= 48 KiB of LDS, <= 128 VGPRs)
-
 template <int MODE, int D, typename T, class MergeOp, int RT, int NW, int L>
 void launch_xd_cfg(const SoftminParams<T>& prm, const typename MergeOp::Params& mprm, const Ranges& rg, int n_ranges, int B, int N,
                    int M, const Scratch& sc, hipStream_t st) {
@@ -352,17 +325,16 @@ void launch_xd_cfg(const SoftminParams<T>& prm, const typename MergeOp::Params& 
     static_assert(MergeOp::kPartial == kPart, "partial formats differ");
     constexpr int kRows = RT * NW * 32;
     SplitLaunch sl(rg, n_ranges, B, N, M, kRows, kPart, sc.ws, sc.bytes, sc.cb, st);
-    sl.sp.n_splits = (sc.allow_split && sl.fit >= 2) ? choose_splits(sl.row_blocks, M, n_ranges, sl.fit) : 1;
-    sl.sp.gather = (n_ranges > 0 && N / n_ranges < 128) ? 1 : 0;   // small clusters: gathered tiles, as in launch_softmin_mfma_nw
-    // pre-packed columns (glhip_softmin_xd.h): the records of all columns once, in workspace behind the split partials
-    XdPacked pk{nullptr, (long)((M + 31) / 32) * S::kGroupRecs};
-    const size_t packed_bytes = (size_t)B * (size_t)pk.stride * sizeof(uint4);
-    const long fit_pre = (sc.ws && sc.bytes > packed_bytes + 256) ? (long)((sc.bytes - packed_bytes - 256) / sl.per_split) : 0;
-    const bool pre = NW == 8 && sc.prepack((double)B * N * M) && fit_pre >= 8;      // (A/B knob GLHIP_XD_PRE of rounds 4-5: pre-packed columns won)
-    auto pack = [&]() {
-        pk.rec = reinterpret_cast<uint4*>(static_cast<char*>(sc.ws) + sl.packed_offset());
+    // splits by the rule, by the free-split rule or on the XCD-aware grid; pre-packed columns (glhip_softmin_xd.h): the records of all
+    // columns once, in workspace behind the split partials
+    const SplitPlan plan = plan_xd(sl, sc.policy(), NW, S::NBP);
+    sl.apply(plan);
+    XdPacked pk{nullptr, packed_stride(M, S::NBP)};
+    static_assert(S::kGroupRecs == 32 * S::NBP, "packed_stride counts whole groups of 32 columns");
+    if (plan.pre) {
+        pk.rec = sl.packed<uint4>(plan);
         hipLaunchKernelGGL((xd_pack_kernel<MODE, D, T, L>), dim3((M + 31 + kBlock) / kBlock, B, 1), dim3(kBlock), 0, st, prm, N, M, pk);
-    };
+    }
     auto main_kernel = [&](auto sparse, dim3 grid, const Ranges& r) {
         constexpr bool SP = decltype(sparse)::value;
         if constexpr (NW == 8 && !SP) {
@@ -371,31 +343,7 @@ void launch_xd_cfg(const SoftminParams<T>& prm, const typename MergeOp::Params& 
         hipLaunchKernelGGL((xd_fwd_kernel<MODE, D, T, SP, RT, NW, false, L>), grid, dim3(NW * 64), 0, st, prm, r, N, M, sl.sp, XdPacked{nullptr, 0});
     };
     if constexpr (NW == 8) {
-        // Packed columns that fit every XCD's L2 (<= 3.5 MB: M = 1e5 at 32 bytes per column) need no XCD-aware placement: any number
-        // of splits, on the plain 3-D grid, chosen to fill the chip's rounds of resident workgroups (free_splits).  BASELINE config 2,
-        // online N = M = 1e5: 13 splits instead of 32: 0.937 -> 0.896 ms per soft-min, 35.3 -> 34.2 ms per loss; N = 7e4: 0.489 -> 0.439 ms.
-        // From M = 8192 (below 65536 the launch used to pack its columns per workgroup, on up to 32 splits: raw soft-mins at N = M = 5e4,
-        // D = 4 / 5 / 8: 0.318 / 0.402 / 0.396 -> 0.280 / 0.303 / 0.300 ms).
-        if (n_ranges == 0 && sc.allow_split && pre && M >= 8192 && (double)M * S::NBP * 16.0 <= 3.5e6) {
-            const long gxB = sl.row_blocks;
-            double eff_free = 0.0;
-            const int nf = free_splits(gxB, M, kXdSlots, fit_pre, &eff_free);
-            double eff_x = 0.0;
-            if (M >= 65536) {
-                const int nx8 = xcd_splits_prepacked(gxB, M, kXdSlots, fit_pre, S::NBP * 16.0);
-                eff_x = ((double)gxB * nx8 / (double)kXdSlots) / (double)((gxB * nx8 + kXdSlots - 1) / kXdSlots);
-            }
-            if (nf >= 1 && eff_free > eff_x + 0.02) {
-                sl.sp.n_splits = nf;
-                pack();
-                sl.launch_dense<MergeOp>(main_kernel, mprm, st);
-                return;
-            }
-        }
-    }
-    if (sl.xcd_eligible(sc.allow_split)) {   // one column split per XCD at a time (workgroup_coords)
-        const int nx = pre ? xcd_splits_prepacked(sl.row_blocks, M, kXdSlots, fit_pre, S::NBP * 16.0) : xcd_splits(sl.row_blocks, M, kXdSlots, sl.fit);
-        if (sl.take_xcd(nx) && pre) pack();
+        if (plan.pre) { sl.launch_dense<MergeOp>(main_kernel, mprm, st); return; }      // (pre-packed launches are dense)
     }
     sl.launch<MergeOp>(main_kernel, mprm, st);
 }
@@ -435,17 +383,13 @@ void launch_xd(const SoftminParams<T>& prm, const typename MergeOp::Params& mprm
 // the XCD-aware grid of big dense launches, row chunks of block-sparse launches and the merge kernels as above (the merge operators
 // do not look at the coordinates: they are instantiated for D = 1); tiles are staged on the fly, there is no pre-packed copy, so
 // the workspace holds split partials only and a launch without one runs unsplit.
-constexpr long kXkSlots = 256 * 2;    // resident 8-wave workgroups (78.75 KiB of LDS, <= 128 VGPRs)
-
 template <int MODE, typename T, class MergeOp, int L>
 void launch_xk_l(const SoftminParams<T>& prm, const typename MergeOp::Params& mprm, const Ranges& rg, int n_ranges, int B, int N, int M, int D,
                  const Scratch& sc, hipStream_t st) {
     constexpr int kPart = MODE == XD_SOFTMIN ? 2 : 1;
     static_assert(MergeOp::kPartial == kPart, "partial formats differ");
     SplitLaunch sl(rg, n_ranges, B, N, M, kXkRows, kPart, sc.ws, sc.bytes, sc.cb, st);
-    sl.sp.n_splits = (sc.allow_split && sl.fit >= 2) ? choose_splits(sl.row_blocks, M, n_ranges, sl.fit) : 1;
-    sl.sp.gather = (n_ranges > 0 && N / n_ranges < 128) ? 1 : 0;   // small clusters: gathered tiles, as in launch_softmin_mfma_nw
-    if (sl.xcd_eligible(sc.allow_split)) sl.take_xcd(xcd_splits(sl.row_blocks, M, kXkSlots, sl.fit));   // one column split per XCD at a time
+    sl.apply(plan_rule(sl, sc.allow_split, kXkSlots, false, true));   // small clusters: gathered tiles, as in launch_softmin_mfma_nw
     sl.launch<MergeOp>([&](auto sparse, dim3 grid, const Ranges& r) {
         hipLaunchKernelGGL((xk_fwd_kernel<MODE, T, decltype(sparse)::value, L>), grid, dim3(kXkThreads), 0, st, prm, r, N, M, D, sl.sp);
     }, mprm, st);
@@ -466,8 +410,7 @@ void launch_xk_dist(const DistParams<T>& prm, const typename MergeOp::Params& mp
                     hipStream_t st) {
     static_assert(MergeOp::kPartial == (MODE == DM_SOFTMIN_P1 ? 2 : 1), "partial formats differ");
     SplitLaunch sl(Ranges{nullptr, nullptr, nullptr, nullptr}, 0, B, N, M, kXkRows, MergeOp::kPartial, sc.ws, sc.bytes, sc.cb, st);
-    sl.sp.n_splits = (sc.allow_split && sl.fit >= 2) ? choose_splits(sl.row_blocks, M, 0, sl.fit) : 1;
-    if (sl.xcd_eligible(sc.allow_split)) sl.take_xcd(xcd_splits(sl.row_blocks, M, kXkSlots, sl.fit));   // one column split per XCD at a time
+    sl.apply(plan_rule(sl, sc.allow_split, kXkSlots));
     sl.launch_dense<MergeOp>([&](auto, dim3 grid, const Ranges&) {
         hipLaunchKernelGGL((xk_dist_kernel<MODE, T>), grid, dim3(kXkThreads), 0, st, prm, N, M, D, sl.sp);
     }, mprm, st);
@@ -491,27 +434,13 @@ inline bool highd_dist_applies(int B, int D, int flags, int n_ranges) {
 }
 
 // distance reductions for 4 <= D <= 16, dense launches (glhip_dist_xd.h): soft-min p = 1 / fused half-step, laplacian and energy products
-// 256-row workgroups of the distance kernels on a few thousand points are a handful (N = 1000: 4 per problem): launches with fewer than
-// 512 workgroups split their columns down to 128 per split, up to 32 splits and what the workspace holds
-// (online p = 1 losses at N = 1000 / 2000: 0.53 / 0.49 -> 0.35 / 0.38 ms)
-static inline int dist_small_launch_splits(int n_splits, long row_blocks, int M, long fit, bool allow_split) {
-    constexpr int min_cols = 128;
-    if (!allow_split || row_blocks * n_splits >= 512) return n_splits;
-    long want = (512 + row_blocks - 1) / row_blocks;
-    const long by_cols = M / min_cols;
-    want = want < by_cols ? want : by_cols;
-    want = want < 32 ? want : 32;
-    want = want < fit ? want : fit;
-    return want > n_splits ? (int)want : n_splits;
-}
-
+// (small launches split their columns further: dist_small_launch_splits, glhip_split_policy.h)
 template <int MODE, int D, typename T, class MergeOp>
 void launch_dist_xd(const DistParams<T>& prm, const typename MergeOp::Params& mprm, int B, int N, int M, const Scratch& sc, hipStream_t st) {
     constexpr int NW = 8;
     static_assert(MergeOp::kPartial == (MODE == DM_SOFTMIN_P1 ? 2 : 1), "partial formats differ");
     SplitLaunch sl(Ranges{nullptr, nullptr, nullptr, nullptr}, 0, B, N, M, NW * 32, MergeOp::kPartial, sc.ws, sc.bytes, sc.cb, st);
-    sl.sp.n_splits = (sc.allow_split && sl.fit >= 2) ? choose_splits(sl.row_blocks, M, 0, sl.fit) : 1;
-    sl.sp.n_splits = dist_small_launch_splits(sl.sp.n_splits, sl.row_blocks, M, sl.fit, sc.allow_split);
+    sl.apply(plan_rule(sl, sc.allow_split, 0, true));
     sl.launch_dense<MergeOp>([&](auto, dim3 grid, const Ranges&) {
         hipLaunchKernelGGL((dist_xd_kernel<MODE, D, T, NW>), grid, dim3(NW * 64), 0, st, prm, N, M, sl.sp);
     }, mprm, st);
@@ -524,7 +453,7 @@ void launch_dist_xd_grad(const DistXdGradParams<T>& gp, const typename MergeOp::
     constexpr int NW = 8;
     static_assert(MergeOp::kPartial == (MODE == DM_SOFTMIN_P1 ? D + 1 : D), "partial formats differ");
     SplitLaunch sl(Ranges{nullptr, nullptr, nullptr, nullptr}, 0, B, N, M, NW * 32, MergeOp::kPartial, sc.ws, sc.bytes, sc.cb, st);
-    sl.sp.n_splits = (sc.allow_split && sl.fit >= 2) ? choose_splits(sl.row_blocks, M, 0, sl.fit) : 1;
+    sl.apply(plan_rule(sl, sc.allow_split));
     sl.launch_dense<MergeOp>([&](auto, dim3 grid, const Ranges&) {
         hipLaunchKernelGGL((dist_xd_grad_kernel<MODE, D, T, NW>), grid, dim3(NW * 64), 0, st, gp, N, M, sl.sp);
     }, mprm, st);
@@ -538,8 +467,7 @@ void launch_wsum_t32_rt(const WsumParams<T>& prm, const typename MergeOp::Params
     static_assert(MergeOp::kPartial == ((MODE == WS_GAUSS_BWD) ? D : D + 1), "partial formats differ");
     constexpr int NW = 8 / RT;       // 256 rows per workgroup either way
     SplitLaunch sl(rg, n_ranges, B, N, M, kMfmaRowsPerBlock, MergeOp::kPartial, sc.ws, sc.bytes, sc.cb, st);
-    sl.sp.n_splits = (sc.allow_split && sl.fit >= 2) ? choose_splits(sl.row_blocks, M, n_ranges, sl.fit) : 1;
-    if (sl.xcd_eligible(sc.allow_split)) sl.take_xcd(xcd_splits(sl.row_blocks, M, kXdSlots, sl.fit));
+    sl.apply(plan_rule(sl, sc.allow_split, kXdSlots));
     sl.launch<MergeOp>([&](auto sparse, dim3 grid, const Ranges& r) {
         constexpr bool SP = decltype(sparse)::value;
         if constexpr (WQ) hipLaunchKernelGGL((wsum_t32q_kernel<D, T, SP, NW>), grid, dim3(NW * 64), 0, st, prm, r, N, M, sl.sp);
@@ -677,81 +605,45 @@ void launch_generic(const GenericParams<T>& prm, const Ranges& rg, int n_ranges,
 }
 
 // glhip_sinkhorn_iter4: `count` dense reductions in one launch of a multi kernel + one merge launch.  What the three launchers share:
-// the extent of the problems (widest N, narrowest and widest M, row blocks of `rows`-row workgroups), the split workspace and the merge.
+// the extent of the problems (multi_geom, glhip_split_policy.h), the plan of their kind (plan_multi), the split workspace and the merge.
 template <typename T>
 struct MultiSplit {
-    int maxN = 0, minM, maxM = 0, gx;
-    long row_blocks = 0, fit;
+    SplitGeom g;
+    size_t packed[4] = {0, 0, 0, 0};      // MULTI_X32: where each problem's pre-packed columns go
+    SplitPlan plan;
     SplitInfo sp;
-    MultiSplit(const SoftminMulti<T>& m, int B, int rows, const Scratch& sc) : minM(m.M[0]) {
-        for (int k = 0; k < m.count; ++k) {
-            maxN = m.N[k] > maxN ? m.N[k] : maxN;
-            minM = m.M[k] < minM ? m.M[k] : minM;
-            maxM = m.M[k] > maxM ? m.M[k] : maxM;
-            row_blocks += (long)B * ((m.N[k] + rows - 1) / rows);
-        }
-        gx = (maxN + rows - 1) / rows;
-        const long per_split = (long)m.count * B * maxN * 2 * sizeof(float);
-        fit = sc.ws ? (long)(sc.bytes / per_split) : 0;
-        sp.n_splits = 1;
-        sp.workspace = static_cast<float*>(sc.ws);
-        sp.split_stride = 0;   // per problem, set in the kernels
-        sp.xcd_grid_x = 0;
-        sp.xcd_blocks = 0;
+    // `nr`: records per column of the x32 forward (MULTI_X32)
+    MultiSplit(SoftminMulti<T>& m, int B, int rows, const Scratch& sc, int kind, int nr = 0)
+        : g(multi_geom(m.count, m.N, m.M, B, rows, sc.ws != nullptr, sc.bytes)), plan(plan_multi(g, sc.policy(), kind, m.count, m.N, m.M, nr, packed)),
+          sp{plan.n_splits, static_cast<float*>(sc.ws), 0, 0, 0} {      // (the split stride is per problem, set in the kernels)
+        m.ws_stride = (long)sp.n_splits * B * g.N * 2;      // floats of split workspace per problem
     }
-    // floats of split workspace per problem, once the launcher has chosen sp.n_splits
-    long ws_stride(int B) const { return (long)sp.n_splits * B * maxN * 2; }
+    dim3 grid(int count) const { return dim3(g.gx, g.B, sp.n_splits * count); }
     template <class MergeOp>
-    void merge(const SoftminMulti<T>& m, int B, hipStream_t st) const {
+    void merge(const SoftminMulti<T>& m, hipStream_t st) const {
         if (sp.n_splits > 1)
-            hipLaunchKernelGGL((merge_multi_kernel<MergeOp, T>), dim3((maxN + kBlock - 1) / kBlock, B, m.count), dim3(kBlock), 0, st, m, sp);
+            hipLaunchKernelGGL((merge_multi_kernel<MergeOp, T>), dim3((g.N + kBlock - 1) / kBlock, g.B, m.count), dim3(kBlock), 0, st, m, sp);
     }
 };
 
-// p = 2, D <= 3: the multi launch of the x32 forward kernel
+// p = 2, D <= 3: the multi launch of the x32 forward kernel, with pre-packed columns where they pay (plan_multi)
 template <int D, typename T, int L = XL_BF16X3>
 void launch_iter4(SoftminMulti<T>& m, int B, const Scratch& sc, hipStream_t st) {
     constexpr int NR = X32Layout<L>::NR;
     constexpr int NW = 4;
-    MultiSplit<T> ms(m, B, NW * 32, sc);
-    ms.sp.n_splits = (sc.allow_split && ms.fit >= 2) ? choose_splits(ms.row_blocks, ms.minM, 0, ms.fit) : 1;
-    // ... with at least 3 column tiles per split: a 128-row workgroup that runs one tile of 512 columns is mostly prologue and
-    // epilogue (N = M = 1e4, 19 splits by the rule: 64 us per iteration; 6: 57 us; 2e4: 173 -> 166 us; 5e3 and 3e4: unchanged)
-    if (ms.minM >= 3072 && ms.minM / ms.sp.n_splits < 1536) ms.sp.n_splits = ms.minM / 1536;
-    // ... and none on tiny unbatched problems (rows x columns of one problem up to 5e6, measured): the launch takes as long either
-    // way (N = M = 2000: 17.8 us with 3 splits + merge, 18.1 us with one), and a loop of such launches is bound by the host's launch
-    // rate — the merge kernel is one launch in three
-    constexpr double tiny_pairs = 5e6;
-    if (B == 1 && (double)ms.maxN * ms.maxM <= tiny_pairs) ms.sp.n_splits = 1;
-    m.ws_stride = ms.ws_stride(B);
-    // Pre-packed columns (as in launch_softmin_mfma_nw): with 128-row workgroups every column is split into its bf16 pieces
-    // (maxN / 128) times per problem; one more small launch does it once.  Measured (round 3): B x 4096^2 bf16 with B = 128 / 64 / 32
-    // (the 2- / 4- / 8-GPU shards of configs[3]): 8.65 -> 8.28, 4.54 -> 4.35, 2.43 -> 2.32 ms per loss; N = M = 3e4: 4.07 -> 3.84 ms;
-    // N = M = 1e4 and below: no difference (0.9 ms).
-    double pairs = 0.0;
+    MultiSplit<T> ms(m, B, NW * 32, sc, MULTI_X32, NR);
+    int maxM = 0;
     for (int k = 0; k < m.count; ++k) {
-        pairs += (double)B * m.N[k] * m.M[k];
-        m.pk[k] = PackedCols{nullptr, (long)((m.M[k] + 31) / 32) * (32 * NR)};
+        maxM = m.M[k] > maxM ? m.M[k] : maxM;
+        m.pk[k] = PackedCols{ms.plan.pre ? reinterpret_cast<uint4*>(static_cast<char*>(sc.ws) + ms.packed[k]) : nullptr, packed_stride(m.M[k], NR)};
     }
-    constexpr double pre_min = 1e8;
-    bool pre = sc.ws && sc.allow_split && pairs >= pre_min;
-    if (pre) {
-        size_t off = (((size_t)(ms.sp.n_splits > 1 ? m.count : 0) * (size_t)m.ws_stride * sizeof(float)) + 255) & ~(size_t)255;
-        for (int k = 0; k < m.count && pre; ++k) {
-            const size_t bytes = (size_t)B * (size_t)m.pk[k].stride * sizeof(uint4);
-            if (off + bytes > sc.bytes) { pre = false; break; }
-            m.pk[k].rec = reinterpret_cast<uint4*>(static_cast<char*>(sc.ws) + off);
-            off += (bytes + 255) & ~(size_t)255;
-        }
-    }
-    const dim3 grid(ms.gx, B, ms.sp.n_splits * m.count);
-    if (pre) {
-        hipLaunchKernelGGL((pack_columns_multi_kernel<D, T, L>), dim3((ms.maxM + 31 + kBlock) / kBlock, B, m.count), dim3(kBlock), 0, st, m);
-        hipLaunchKernelGGL((softmin_fwd_x32_multi_kernel<D, T, NW, true, L>), grid, dim3(NW * 64), 0, st, m, ms.sp);
+    if (ms.plan.pre) {
+        hipLaunchKernelGGL((pack_columns_multi_kernel<D, T, L>), dim3((maxM + 31 + kBlock) / kBlock, B, m.count), dim3(kBlock), 0, st, m);
+        hipLaunchKernelGGL((softmin_fwd_x32_multi_kernel<D, T, NW, true, L>), ms.grid(m.count), dim3(NW * 64), 0, st, m, ms.sp);
     } else {
-        hipLaunchKernelGGL((softmin_fwd_x32_multi_kernel<D, T, NW, false, L>), grid, dim3(NW * 64), 0, st, m, ms.sp);
+        hipLaunchKernelGGL((softmin_fwd_x32_multi_kernel<D, T, NW, false, L>), ms.grid(m.count), dim3(NW * 64), 0, st, m, ms.sp);
     }
-    ms.template merge<SoftminFwdOp<D, 2, false, 1, T>>(m, B, st);
+    ms.template merge<SoftminFwdOp<D, 2, false, 1, T>>(m, st);
 }
 
 // the same for 4 <= D <= 16: the multi launch of the xd kernel (glhip_softmin_xd.h), columns packed on the fly, 4 wavefronts x 1 row tile
@@ -759,13 +651,9 @@ template <int D, typename T, int L>
 void launch_iter4_xd(SoftminMulti<T>& m, int B, const Scratch& sc, hipStream_t st) {
     constexpr int NW = 4;
     for (int k = 0; k < m.count; ++k) m.pk[k] = PackedCols{nullptr, 0};
-    MultiSplit<T> ms(m, B, NW * 32, sc);
-    ms.sp.n_splits = (sc.allow_split && ms.fit >= 2) ? choose_splits(ms.row_blocks, ms.minM, 0, ms.fit) : 1;
-    // (no tiny-launch rule as in launch_iter4: N = M = 2000, D = 4 / 16 run 0.35 / 0.42 ms per loss with 3 splits, 0.43 / 0.58 ms with one)
-    // (and more splits than the rule's do not pay either: 7 splits of 256 columns at N = M = 2000 measure like 3 — these loops are host-bound)
-    m.ws_stride = ms.ws_stride(B);
-    hipLaunchKernelGGL((xd_fwd_multi_kernel<D, T, NW, L>), dim3(ms.gx, B, ms.sp.n_splits * m.count), dim3(NW * 64), 0, st, m, ms.sp);
-    ms.template merge<SoftminFwdOp<D, 2, false, 1, T>>(m, B, st);
+    MultiSplit<T> ms(m, B, NW * 32, sc, MULTI_XD);
+    hipLaunchKernelGGL((xd_fwd_multi_kernel<D, T, NW, L>), ms.grid(m.count), dim3(NW * 64), 0, st, m, ms.sp);
+    ms.template merge<SoftminFwdOp<D, 2, false, 1, T>>(m, st);
 }
 
 // p = 1 (round 5): the multi launch of the dense distance kernel (glhip_dist_xd.h), any D <= 16
@@ -779,13 +667,10 @@ void launch_iter4_dist(SoftminMulti<T>& m, int B, const Scratch& sc, hipStream_t
         dm.N[k] = m.N[k];
         dm.M[k] = m.M[k];
     }
-    MultiSplit<T> ms(m, B, NW * 32, sc);
-    ms.sp.n_splits = (sc.allow_split && ms.fit >= 2) ? choose_splits(ms.row_blocks, ms.minM, 0, ms.fit) : 1;
-    // (no tiny-launch rule here: p = 1 at N = M = 2000 runs 0.54 ms per loss with 3 splits, 0.84 ms with one) — the other way round:
-    ms.sp.n_splits = dist_small_launch_splits(ms.sp.n_splits, ms.row_blocks, ms.minM, ms.fit, sc.allow_split);
-    m.ws_stride = dm.ws_stride = ms.ws_stride(B);
-    hipLaunchKernelGGL((dist_xd_multi_kernel<D, T, NW>), dim3(ms.gx, B, ms.sp.n_splits * m.count), dim3(NW * 64), 0, st, dm, ms.sp);
-    ms.template merge<SoftminFwdOp<D, 1, true, 1, T>>(m, B, st);
+    MultiSplit<T> ms(m, B, NW * 32, sc, MULTI_DIST);
+    dm.ws_stride = m.ws_stride;
+    hipLaunchKernelGGL((dist_xd_multi_kernel<D, T, NW>), ms.grid(m.count), dim3(NW * 64), 0, st, dm, ms.sp);
+    ms.template merge<SoftminFwdOp<D, 1, true, 1, T>>(m, st);
 }
 
 // every problem of a SoftminMulti in one launch, on the kernel family of (p, D, layout)

@@ -2,33 +2,20 @@
 // shares their split policy: ONE pass launcher, ONE pass loop, ONE sizing rule and ONE argument prologue for glhip_api_plan.hip,
 // glhip_api_plan_xk.hip, glhip_api_grad_xk.hip, glhip_api_convgrad_xk.hip, glhip_api_distgrad_xk.hip and glhip_api_argmin.hip; for the three
 // gradient routes of 17 <= D <= 4095 also ONE predicate tail, ONE workspace rule and ONE launch prologue.
-// What the launcher takes and what the sizing calls promise must agree exactly: both read plan_splits and the constants below.
+// What the launcher takes and what the sizing calls promise must agree exactly: both read plan_splits, plan_pass_workspace_bytes and the
+// resident-slot constants, which live with every other split rule in glhip_split_policy.h.
 #pragma once
-
-#include <initializer_list>
 
 #include "glhip_launch.h"
 #include "glhip_plan_apply_xk.h"
 
 namespace {
 
-constexpr size_t kPlanMaxWorkspace = (size_t)1 << 30;     // no *_workspace_bytes call of this family asks for more than 1 GiB (glhip.h)
-constexpr long kXkPlanSlots = 256;                        // resident 8-wave workgroups of xk_plan_kernel: one per CU (glhip_plan_apply_xk.h)
 constexpr int kXkPlanWidth = 32 * kXkPlanMaxChunks;       // features / coordinates per pass of xk_plan_kernel
 
 // The EINVAL prologue the predicates of the family share
 inline bool plan_family_bad_args(int B, long N, long M, int D, int dtype, int n_ranges) {
     return B < 0 || N < 0 || M < 0 || N > 0x7fffffffL || M > 0x7fffffffL || D < 1 || n_ranges < 0 || (dtype != GLHIP_F32 && dtype != GLHIP_BF16);
-}
-
-// THE split policy of a pass, shared by the launcher and by the sizing calls: the rule of every split launch (choose_splits), or — dense
-// launches with room for 8 splits over >= 65536 columns (SplitLaunch::xcd_eligible) — the XCD-aware grid with xcd_splits.
-// `fit`: splits the workspace holds; `slots`: resident workgroups of the kernel shape.
-struct PlanSplits { int n; bool xcd; };
-inline PlanSplits plan_splits(long row_blocks, int M, long fit, bool allow_split, long slots) {
-    if (!allow_split || fit < 2) return PlanSplits{1, false};
-    if (fit >= 8 && M >= 65536) return PlanSplits{xcd_splits(row_blocks, M, slots, fit), true};
-    return PlanSplits{choose_splits(row_blocks, M, 0, fit), false};
 }
 
 // One dense pass: `rows` per workgroup, `partial` floats per row and split, `slots` resident workgroups.  main(grid, sp) launches the
@@ -38,25 +25,12 @@ void launch_plan_pass(int rows, int partial, long slots, int B, int N, int M, co
     const Ranges none{nullptr, nullptr, nullptr, nullptr};
     SplitLaunch sl(none, 0, B, N, M, rows, partial, sc.ws, sc.bytes, sc.cb, st);
     const PlanSplits ps = plan_splits(sl.row_blocks, M, sl.fit, sc.allow_split, slots);
-    if (!(ps.xcd && sl.take_xcd(ps.n)))      // (a grid beyond 2^31 workgroups stays on the plain 3-D grid)
-        sl.sp.n_splits = ps.xcd ? choose_splits(sl.row_blocks, M, 0, sl.fit) : ps.n;
+    SplitPlan plan;
+    if (!(ps.xcd && take_xcd(plan, sl, ps.n)))      // (a grid beyond 2^31 workgroups stays on the plain 3-D grid)
+        plan.n_splits = ps.xcd ? choose_splits(sl.row_blocks, M, 0, sl.fit) : ps.n;
+    sl.apply(plan);
     main(sl.sp.xcd_grid_x > 0 ? dim3((unsigned)((long)sl.gx * B * sl.sp.n_splits), 1, 1) : dim3(sl.gx, B, sl.sp.n_splits), sl.sp);
     if (sl.sp.n_splits > 1) merge(sl.sp);
-}
-
-// The workspace of the widest pass (nv sums) of a call: what launch_plan_pass would take with up to 1 GiB, for the largest of the
-// resident-workgroup counts its kernel shapes have; 0 where the pass runs unsplit.
-inline size_t plan_pass_workspace_bytes(int B, int N, int M, int rows, int nv, std::initializer_list<long> slots) {
-    const size_t per_split = (size_t)B * N * (nv + 2) * sizeof(float);
-    const long row_blocks = (long)B * ((N + rows - 1) / rows);
-    long fit = (long)(kPlanMaxWorkspace / per_split);
-    fit = fit < 32 ? fit : 32;
-    int ns = 0;
-    for (long s : slots) {
-        const int n = plan_splits(row_blocks, M, fit, true, s).n;
-        ns = n > ns ? n : ns;
-    }
-    return ns >= 2 ? (size_t)ns * per_split : 0;
 }
 
 // plan_merge_kernel on the parameter struct of the pass: one thread per (row, feature); its width is a run-time argument

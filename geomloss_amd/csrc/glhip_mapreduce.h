@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "glhip_common.h"
+#include "glhip_split_policy.h"
 
 namespace glhip {
 
@@ -235,74 +236,13 @@ merge_kernel(typename Op::Params prm, Ranges rg, int N, SplitInfo sp) {
 
 // ---- host side -------------------------------------------------------------------------------------
 
-// Number of column splits: enough workgroups for >= ~16 rounds over the chip.
-static inline int choose_splits(long row_blocks, int M, int n_ranges, long max_by_workspace) {
-    // dense launches that already fill the chip four times over gain nothing from splits and pay one prologue / epilogue / merge share
-    // per split: B = 256 x 4096 x 4096 (4096 row blocks, 3 splits by the rule below): 17.4 -> 15.9 ms per loss without (round 4)
-    // (short column loops only: with long ones the last partial round of long-lived workgroups is what splits are for)
-    if (n_ranges == 0 && row_blocks >= 4L * 768 && M <= 16384) return 1;
-    const long target = 256L * 4 * 10;   // ~10 rounds of 4 workgroups per CU
-    long ns = (target + row_blocks - 1) / row_blocks;
-    const long by_cols = (n_ranges > 0) ? 8 : (long)M / 512;   // at least 512 columns per split
-    ns = ns < by_cols ? ns : by_cols;
-    ns = ns < 32 ? ns : 32;
-    ns = ns < max_by_workspace ? ns : max_by_workspace;
-    return ns < 1 ? 1 : (int)ns;
-}
-
-// XCD-aware dense launches use a multiple of 8 column splits (split s runs on XCD s % 8).  All workgroups take the
-// same time, so the kernel lasts ceil(workgroups / resident slots) rounds: with 8 splits a 1e5-row problem is 4.07
-// rounds of work spread over 5 (81 %).  Take the smallest multiple of 8 (up to 32) that fills its last round to
-// >= 93 %, else the best one.  `slots` = workgroups resident on the chip (256 CUs x workgroups per CU).
-static inline int xcd_splits(long row_blocks, int M, long slots, long max_by_workspace) {
-    int best = 8;
-    double best_eff = 0.0;
-    for (int ns = 8; ns <= 32; ns += 8) {
-        if (ns > max_by_workspace || (long)M / ns < 2048) break;
-        const double w = (double)row_blocks * ns / (double)slots;
-        const double rounds = (double)((row_blocks * ns + slots - 1) / slots);
-        const double eff = w / rounds;
-        if (eff >= 0.93) return ns;
-        if (eff > best_eff + 0.02) { best_eff = eff; best = ns; }
-    }
-    return best;
-}
-
-// Mid-size dense launches whose packed columns fit the L2 of EVERY XCD at once (<= 3.5 MB: M = 1e5 at 32 bytes per column) need no
-// XCD-aware placement, so the number of splits need not be a multiple of 8: the smallest ns in [4, 32] (>= 2048 columns per split)
-// that fills its last round of resident workgroups to >= 97 %, else the best.  N = M = 1e5, 196 row blocks of 512 rows on 512
-// slots: ns = 32 is 12.25 rounds spread over 13 (0.94) with 6 tiles per workgroup; ns = 13 is 4.98 rounds over 5 with 15 tiles.
-static inline int free_splits(long row_blocks, int M, long slots, long max_by_workspace, double* eff_out) {
-    int best = 0;
-    double best_eff = 0.0;
-    for (int ns = 4; ns <= 32; ++ns) {
-        if (ns > max_by_workspace || (long)M / ns < 2048) break;
-        const double w = (double)row_blocks * ns / (double)slots;
-        const double eff = w / (double)((row_blocks * ns + slots - 1) / slots);
-        if (eff >= 0.97) { best = ns; best_eff = eff; break; }
-        if (eff > best_eff + 0.01) { best_eff = eff; best = ns; }
-    }
-    if (eff_out) *eff_out = best_eff;
-    return best;
-}
-
-// ... and when the columns are pre-packed (64 bytes each), enough splits for one split's records to stay resident in the
-// 4 MB L2 of the XCD that streams them (workgroup_coords runs one split per XCD at a time).
-static inline int xcd_splits_prepacked(long row_blocks, int M, long slots, long max_by_workspace, double bytes_per_column = 64.0) {
-    int ns = xcd_splits(row_blocks, M, slots, max_by_workspace);
-    while (ns + 8 <= 32 && ns + 8 <= max_by_workspace && (double)M / ns * bytes_per_column > 2.5e6) ns += 8;
-    return ns;
-}
+// (the split rules and the arithmetic of a split workspace: glhip_split_policy.h)
 
 // Space reserved at the front of the caller's workspace for the row-chunk table of a block-sparse launch.
 struct ChunkBuf {
     int32_t* buf = nullptr;
     long capacity = 0;      // chunks the table can hold
 };
-
-static inline size_t chunk_table_bytes(int n_ranges, int N, int rows) {
-    return (((size_t)(1 + 3 * ((size_t)n_ranges + (size_t)N / rows + 1)) * sizeof(int32_t)) + 255) & ~(size_t)255;
-}
 
 // Queues build_row_chunks_kernel for a reduction whose workgroups take `rows` rows and returns the ranges to hand to it
 // together with its grid.x; without a reserved table (no workspace) the launch keeps one workgroup per row block.
@@ -318,49 +258,36 @@ static inline Ranges with_row_chunks(const Ranges& rg, int n_ranges, int N, int 
     return out;
 }
 
-// The column-split mechanics of a row-tiled reduction launch (this file's kernel and the matrix-core kernels of glhip_launch.h):
-// row-chunk table, split workspace, SplitInfo, grid, main launch, merge launch.  Every policy stays with the launcher: between
-// construction and launch() it sets sp.n_splits (and sp.gather / sp.share), may move a dense launch to the XCD-aware 1-D grid
-// (take_xcd) and may place pre-packed columns at packed_offset().  launch() hands the main kernel's launch to a callable
+// The column-split mechanics of a row-tiled reduction launch (this file's kernel and the matrix-core kernels of glhip_launch.h): the HIP
+// half of glhip_split_policy.h's SplitGeom — row-chunk table, SplitInfo, grid, main launch, merge launch.  No policy lives here or in a
+// launcher: between construction and launch() the launcher builds a SplitPlan from this geometry (one plan function per policy,
+// glhip_split_policy.h) and hands it to apply().  launch() hands the main kernel's launch to a callable
 // main(std::integral_constant<bool, SPARSE>, grid, ranges), then queues merge_kernel<MergeOp, SPARSE> when the columns are split.
-struct SplitLaunch {
+struct SplitLaunch : SplitGeom {
     Ranges rg;                  // the caller's ranges: what the merge kernel reads
     Ranges rgc;                 // what the main kernel reads: block-sparse launches with a row-chunk table get it here
-    int n_ranges, B, N, M;
-    int gx;                     // dense launches: row blocks per batch item
     unsigned chunk_grid = 0;    // block-sparse launches: grid.x (one workgroup per row chunk, or per row block without a table)
-    long row_blocks;            // what the split rules count: row blocks (not chunks) of block-sparse launches
-    long per_split;             // bytes of workspace per column split
-    long fit;                   // column splits the workspace holds
     SplitInfo sp;
 
     // `rows`: rows per workgroup of the main kernel; `partial`: floats per row and split (MergeOp::kPartial)
-    SplitLaunch(const Ranges& ranges, int n_ranges_, int B_, int N_, int M_, int rows, int partial, void* workspace, size_t bytes,
+    SplitLaunch(const Ranges& ranges, int n_ranges_, int B_, int N_, int M_, int rows, int partial, void* workspace, size_t bytes_,
                 const ChunkBuf& cb, hipStream_t stream, int share = 0)
-        : rg(ranges), n_ranges(n_ranges_), B(B_), N(N_), M(M_), gx((N_ + rows - 1) / rows) {
+        : SplitGeom(n_ranges_, B_, N_, M_, rows, partial, workspace != nullptr, bytes_), rg(ranges),
+          sp{1, static_cast<float*>(workspace), (long)B_ * N_ * partial, 0, 0} {
         rgc = n_ranges > 0 ? with_row_chunks(rg, n_ranges, N, rows, cb, stream, chunk_grid, share) : rg;
-        row_blocks = n_ranges > 0 ? (long)n_ranges : (long)B * gx;
-        per_split = (long)B * N * partial * sizeof(float);
-        fit = (workspace && per_split > 0) ? (long)(bytes / per_split) : 0;
-        sp.n_splits = 1;
-        sp.workspace = static_cast<float*>(workspace);
-        sp.split_stride = (long)B * N * partial;
-        sp.xcd_grid_x = 0;
-        sp.xcd_blocks = 0;
     }
 
-    // dense launches with room for 8 splits and enough columns for them may run on the XCD-aware 1-D grid (workgroup_coords) ...
-    bool xcd_eligible(bool allow_split) const { return n_ranges == 0 && allow_split && fit >= 8 && M >= 65536; }
-    // ... with the launcher's `nx` splits, when the grid fits: returns whether it was taken
-    bool take_xcd(int nx) {
-        if ((long)gx * B * nx >= (1L << 31)) return false;
-        sp.n_splits = nx;
-        sp.xcd_grid_x = gx;
-        sp.xcd_blocks = gx * B;
-        return true;
+    // takes the plan: its splits, its bits, the XCD-aware 1-D grid (workgroup_coords) where it says so
+    void apply(const SplitPlan& p) {
+        sp.n_splits = p.n_splits;
+        sp.gather = p.gather;
+        sp.share = p.share;
+        if (p.xcd) { sp.xcd_grid_x = gx; sp.xcd_blocks = gx * B; }
     }
-    // byte offset in the workspace of what a launch places behind its split partials (pre-packed columns)
-    size_t packed_offset() const { return (((size_t)(sp.n_splits > 1 ? sp.n_splits : 0) * per_split) + 255) & ~(size_t)255; }
+    // where the plan's pre-packed columns go
+    template <class R> R* packed(const SplitPlan& p, size_t behind = 0) const {
+        return reinterpret_cast<R*>(reinterpret_cast<char*>(sp.workspace) + p.packed_offset + behind);
+    }
 
     template <class MergeOp, class F>
     void launch(F&& main, const typename MergeOp::Params& mprm, hipStream_t stream) const {
@@ -387,7 +314,7 @@ static inline void launch_mapreduce(const typename Op::Params& prm, const Ranges
                                     int M, void* workspace, size_t workspace_bytes, bool allow_split,
                                     hipStream_t stream, const ChunkBuf& cb = ChunkBuf()) {
     SplitLaunch sl(rg, n_ranges, B, N, M, kBlock * Op::kRows, Op::kPartial, workspace, workspace_bytes, cb, stream);
-    sl.sp.n_splits = (allow_split && sl.fit >= 2) ? choose_splits(sl.row_blocks, M, n_ranges, sl.fit) : 1;
+    sl.apply(plan_rule(sl, allow_split));
     sl.launch<Op>([&](auto sparse, dim3 grid, const Ranges& r) {
         hipLaunchKernelGGL((mapreduce_kernel<Op, decltype(sparse)::value>), grid, dim3(kBlock), 0, stream, prm, r, N, M, sl.sp);
     }, prm, stream);

@@ -69,7 +69,7 @@ def test_existing_predicates_do_not_see_the_new_bit():
 
 
 def test_workspace():
-    """The sizing call is plan_pass_workspace_bytes (glhip_launch_plan.h) at the shipped pass width: glhip_plan_apply_nd_workspace_bytes
+    """The sizing call is plan_pass_workspace_bytes (glhip_split_policy.h) at the shipped pass width: glhip_plan_apply_nd_workspace_bytes
     is that function of the same 256-row blocks with V features per pass for V <= 64."""
     lib = hip.load_library()
     width = int(lib.glhip_dist_grad_pass_width())

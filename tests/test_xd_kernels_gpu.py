@@ -71,7 +71,7 @@ def test_softmin_fwd_large_launch_paths(cuda, D, N, M):
 @pytest.mark.parametrize("D,N,M", [(3, 33_000, 66_001), (2, 40_000, 100_003), (1, 70_000, 80_000)])
 def test_mid_size_dense_launches_with_a_free_number_of_splits(cuda, D, N, M):
     """f16 x 2 layout, D <= 3, >= 32768 rows, 65536 <= M with all packed columns (32 bytes each) inside one XCD's L2 (<= 3.5 MB): the
-    launch takes the split count that fills the chip's rounds of resident workgroups (glhip_mapreduce.h: free_splits — 23 splits
+    launch takes the split count that fills the chip's rounds of resident workgroups (glhip_split_policy.h: free_splits — 23 splits
     for 65 row blocks of 512 rows here, 13 at N = M = 1e5), not a multiple of 8, on the plain 3-D grid with pre-packed columns.
     Soft-min and fused half-step: sampled rows against the float64 oracle, every row against the bf16 x 3 launch of the same call."""
     x, y, h = _clouds(11 * D + 5, N, M, D)
