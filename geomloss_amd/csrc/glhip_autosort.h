@@ -57,6 +57,9 @@ constexpr int kSortRowsPerVoxel = 256;
 //   1024, 512, 256, 128 and 64 points, each segment sorted by (coordinate on the axis of its largest finite extent — ties: the lowest
 //   axis — in an order where -inf < ... < +inf < NaN, position the point had in the block).  The result: cells of exactly 512, 256,
 //   128, 64 and 32 points, every one the half of a median cut, which slabs, column blocks, row tiles and column groups are aligned to.
+//   (The kernel sorts in full on the last level only.  The words carry the position a point had in the incoming block, so a level
+//   above the last matters through the SET of each half alone, and the first step of a segment's last merge already separates the
+//   halves: glhip_balance.h, balance_step_runs.  The order is the one five full sorts give, position for position.)
 //   The order is a function of the input alone; the set of points of every block of 1024 is what the path order put there, so the
 //   voxel path still decides which blocks are neighbours; the last n mod 1024 points keep the path order (the minor key orders them).
 //   The pruning is exact for any order: the order only decides how much is kept.  Bench problem at 1e6, eps = 0.05^2 (tools/prune_model.py,
@@ -85,7 +88,8 @@ constexpr int kSortRowsPerVoxel = 256;
 constexpr int kPruneColBlock = 256;   // columns per column block T (a multiple of 64)
 constexpr int kPruneRuns = 160;       // runs of kept blocks per slab (the bench problem under the mass rule: mean 71, max 175 — 8 of 3907 slabs
                                       // close their one-block gaps, 0.01 % more kept pairs: profiles/r10_prune_model.txt; with balanced
-                                      // cells: profiles/balanced_order_model.txt)
+                                      // cells: profiles/balanced_order_model.txt — 562 slabs, which take their gap lengths, g and
+                                      // their pieces from the 64-bit words of the kept-block bit set: glhip_prune_words.h)
 constexpr int kBalanceBlock = 1024;   // positions of the path order that are balanced together (a multiple of kSortSlab and kPruneColBlock)
 constexpr int kBalanceLeaf = 32;      // points of the smallest cell: the row tile of a wavefront, the column group
 constexpr int kPruneGrid = 64;        // pieces a whole row of column blocks is cut into, at most

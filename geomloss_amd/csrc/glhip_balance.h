@@ -60,4 +60,12 @@ GLHIP_HD inline bool balance_keeps_min(int i, int j, int k, int seg) {
     return ((i & j) == 0) == ascending;
 }
 
+// Which steps of the network a level runs.  The next level sorts both halves of a segment again, by words that carry the position a
+// point had in the incoming block, not the one it has now: of a level above the last only the SET of each half matters.  Before the
+// last merge (k = seg) the two halves of a segment are sorted, the lower ascending and the upper descending, so the segment is
+// bitonic, and the first step of that merge (j = seg / 2) already leaves the seg / 2 smallest words in the lower half and the others
+// in the upper one; the steps j = seg / 4, ..., 1 would only order each half.  Those are left out (30 of the 185 steps of the five
+// levels, 6 of the 20 that go through LDS); the last level (seg = last_seg) runs all of its steps, it decides the order.
+GLHIP_HD inline bool balance_step_runs(int j, int k, int seg, int last_seg) { return seg == last_seg || k < seg || j == (k >> 1); }
+
 }  // namespace glhip

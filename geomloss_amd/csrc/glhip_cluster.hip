@@ -348,9 +348,39 @@ __global__ void __launch_bounds__(256) path_keys_kernel(const T* __restrict__ x,
 // aligned block of kBalanceBlock positions of `perm`, one point per thread, in place: the block's points and indices go to LDS, five
 // levels sort every segment (1024, 512, ..., 64 positions) by (coordinate on the segment's longest axis, incoming position), and the
 // indices come back in the new order.  The sort is a bitonic network on the words of balance_word, one word per thread in a register:
-// partners less than a wavefront apart meet by shuffle, the others through LDS (20 of the 185 steps).  The words of a segment are
+// partners less than a wavefront apart meet in registers (lane_xor), the others through LDS.  The levels above the last stop their
+// last merge after its first step: it already splits the segment into its lower and upper half, which is all the next level reads
+// of it (balance_step_runs: 155 of the 185 steps of five full sorts run, 14 of the 20 through LDS).  The words of a segment are
 // distinct, so the order is a function of the block's points alone.
 static_assert(kBalanceBlock == 1024 && kBalanceLeaf == 32, "one point per thread of a 1024-thread workgroup; segments down to one wavefront");
+
+// The value of lane (lane ^ j) of the wavefront, j a power of two below 64 that is a constant where this is inlined: a DPP move inside
+// rows of 16 lanes (j = 1, 2: quad_perm; 8: a row rotated by 8; 4: half-row mirror, lane ^ 7, then the quads reversed, lane ^ 3), a
+// swap of 16-lane rows (j = 16) or of the halves (j = 32) of two copies.  All VALU: the network's 141 shuffle steps and the 90
+// extent steps of a block take no LDS cycles (__shfl_xor is a ds_bpermute: 462 of them per wavefront and block).
+template <int CTRL>
+__device__ __forceinline__ unsigned dpp_move(unsigned v) {
+    return (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xF, 0xF, false);
+}
+__device__ __forceinline__ unsigned lane_xor(unsigned v, int j, int lane) {
+    switch (j) {
+        case 1: return dpp_move<0xB1>(v);                       // quad_perm:[1,0,3,2]
+        case 2: return dpp_move<0x4E>(v);                       // quad_perm:[2,3,0,1]
+        case 4: return dpp_move<0x1B>(dpp_move<0x141>(v));      // row_half_mirror, quad_perm:[3,2,1,0]
+        case 8: return dpp_move<0x128>(v);                      // row_ror:8
+        case 16: {      // r[0]: rows 0, 0, 2, 2 of v; r[1]: rows 1, 1, 3, 3
+            const auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false);
+            return (lane & 16) ? r[0] : r[1];
+        }
+        case 32: {      // r[0]: the lower half twice; r[1]: the upper half twice
+            const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+            return (lane & 32) ? r[0] : r[1];
+        }
+        default: return (unsigned)__shfl_xor((int)v, j, 64);
+    }
+}
+__device__ __forceinline__ float lane_xor(float v, int j, int lane) { return __uint_as_float(lane_xor(__float_as_uint(v), j, lane)); }
+
 template <typename T>
 __global__ void __launch_bounds__(kBalanceBlock) balance_kernel(const T* __restrict__ z, int D, int32_t* __restrict__ perm) {
     __shared__ float pts[3][kBalanceBlock];
@@ -366,7 +396,10 @@ __global__ void __launch_bounds__(kBalanceBlock) balance_kernel(const T* __restr
     }
     __syncthreads();
     int p = tid;      // the incoming position of the point that sits at position tid now
-    for (int seg = kBalanceBlock; seg >= 2 * kBalanceLeaf; seg >>= 1) {
+    constexpr int kBalanceBits = 10, kBalanceLevels = 5;      // 1024 = 2^10 positions; segments of 1024 >> 0, ..., 1024 >> 4 = 64
+#pragma unroll
+    for (int lv = 0; lv < kBalanceLevels; ++lv) {
+        const int seg = kBalanceBlock >> lv;
         // the extents of this thread's segment: per wavefront by shuffle, then over the segment's wavefronts
         float lo[3], hi[3];      // (an axis beyond D: no finite value, it loses to every other)
 #pragma unroll
@@ -374,9 +407,10 @@ __global__ void __launch_bounds__(kBalanceBlock) balance_kernel(const T* __restr
             lo[d] = INFINITY;
             hi[d] = -INFINITY;
             if (d < D) balance_extent_add(pts[d][p], lo[d], hi[d]);
-            for (int off = 32; off > 0; off >>= 1) {
-                lo[d] = fminf(lo[d], __shfl_xor(lo[d], off, 64));
-                hi[d] = fmaxf(hi[d], __shfl_xor(hi[d], off, 64));
+#pragma unroll
+            for (int ob = 5; ob >= 0; --ob) {
+                lo[d] = fminf(lo[d], lane_xor(lo[d], 1 << ob, lane));
+                hi[d] = fmaxf(hi[d], lane_xor(hi[d], 1 << ob, lane));
             }
             if (lane == 0) { wlo[wave][d] = lo[d]; whi[wave][d] = hi[d]; }
         }
@@ -391,8 +425,14 @@ __global__ void __launch_bounds__(kBalanceBlock) balance_kernel(const T* __restr
         }
         const int axis = balance_axis(lo, hi, 3);
         unsigned long long v = balance_word(balance_key(pts[axis][p]), (unsigned)p);
-        for (int k = 2; k <= seg; k <<= 1) {
-            for (int j = k >> 1; j > 0; j >>= 1) {
+        // (counted loops that unroll: seg, k and j are constants in every step, so the partner and the direction cost no arithmetic)
+#pragma unroll
+        for (int kb = 1; kb <= kBalanceBits - lv; ++kb) {
+            const int k = 1 << kb;
+#pragma unroll
+            for (int jb = kb - 1; jb >= 0; --jb) {
+                const int j = 1 << jb;
+                if (!balance_step_runs(j, k, seg, 2 * kBalanceLeaf)) break;      // a level above the last: the halves as sets
                 unsigned long long o;
                 if (j >= 64) {      // (uniform over the workgroup)
                     __syncthreads();      // every read of the step before is done (and, first, every read of wlo / whi)
@@ -400,7 +440,7 @@ __global__ void __launch_bounds__(kBalanceBlock) balance_kernel(const T* __restr
                     __syncthreads();
                     o = words[tid ^ j];
                 } else {
-                    const unsigned ol = __shfl_xor((unsigned)v, j, 64), oh = __shfl_xor((unsigned)(v >> 32), j, 64);
+                    const unsigned ol = lane_xor((unsigned)v, j, lane), oh = lane_xor((unsigned)(v >> 32), j, lane);
                     o = ((unsigned long long)oh << 32) | ol;
                 }
                 v = (balance_keeps_min(tid, j, k, seg) == (o < v)) ? o : v;
@@ -613,7 +653,10 @@ __device__ __forceinline__ int prune_first_kept(const double* hist, double under
 // kept(t) is evaluated once per block, into a bit set in LDS (up to 64 x kPruneMaskWords = 65536 blocks; beyond that every walk evaluates it
 // again, as all of them did before).  For g = 1 — all but a handful of slabs — runs are counted and pieces written from
 // the 64-bit words (glhip_prune_words.h): one prefix sum over the workgroup instead of two per 256 blocks (~1100 barriers per slab at M = 1e6).
+// A slab with more runs (one in seven at M = 1e6 with balanced cells) takes its gap lengths from the same words into a list in LDS,
+// finds g on the list and writes its pieces from the words too; only a slab whose bit set or whose gap list does not fit walks the blocks.
 constexpr int kPruneMaskWords = 1024;      // 65536 blocks = 16.7e6 columns: 8 KB
+constexpr int kPruneGaps = 2048;           // gap lengths of a slab with more than kPruneRuns runs: 8 KB
 template <typename T>
 __global__ void __launch_bounds__(256) prune_slabs_kernel(const T* __restrict__ xs, int N, int M, int D, const ColBlock* __restrict__ blocks,
                                                           int nT, int PB, int S, double inv2eps, double L, int32_t* __restrict__ ranges_i,
@@ -623,6 +666,7 @@ __global__ void __launch_bounds__(256) prune_slabs_kernel(const T* __restrict__ 
     __shared__ double hist[kPruneBuckets + 1];      // (the last entry: the underflow bucket)
     __shared__ int first_kept;
     __shared__ unsigned long long mask[kPruneMaskWords];
+    __shared__ int32_t gaps[kPruneGaps];
     __shared__ float wlo[4][3], whi[4][3];
     __shared__ double wm[4];
     __shared__ int wb[4];
@@ -701,8 +745,9 @@ __global__ void __launch_bounds__(256) prune_slabs_kernel(const T* __restrict__ 
             if (__builtin_isnan(b.lse)) continue;
             const double key = block_key(b);
             const int q = prune_bucket(key, lo_key);
+            if (q >= kPruneBuckets) continue;      // above the range: never added, so no exp for it
             const double mass = exp(key - mlb);
-            if (q < kPruneBuckets && mass > 0.0) atomicAdd(&hist[q < 0 ? kPruneBuckets : q], mass);
+            if (mass > 0.0) atomicAdd(&hist[q < 0 ? kPruneBuckets : q], mass);
         }
     }
     __syncthreads();
@@ -776,20 +821,42 @@ __global__ void __launch_bounds__(256) prune_slabs_kernel(const T* __restrict__ 
     const int wpt = (nW + 255) / 256, w0 = min(nW, tid * wpt), w1 = min(nW, w0 + wpt);
     int runs1 = 0;
     if (masked) {
-        int nrun, nstart;
-        prune_count_words(mask, w0, w1, PB, nrun, nstart);
-        block_scan256<false>(nrun, buf);
-        runs1 = buf[255];
-        __syncthreads();
-        if (runs1 <= kPruneRuns) {      // (workgroup-uniform)
+        // the pieces for gap length gw from the words: nstart of them start in this thread's words
+        auto emit_words = [&](int gw, int nstart) {
             const int base = block_scan256<false>(nstart, buf) - nstart;
             const int n = min(buf[255], S);
-            prune_emit_words(mask, w0, w1, base, PB, S, kPruneColBlock, M, slots);
+            prune_emit_words(mask, w0, w1, base, PB, S, kPruneColBlock, M, slots, gw);
             if (tid == 0 && n > 0) prune_emit_last(mask, nW, n, kPruneColBlock, M, slots);
             for (int q = n + tid; q < S; q += 256) {
                 slots[2 * q] = 0;
                 slots[2 * q + 1] = 0;
             }
+        };
+        int nrun, nstart;
+        prune_count_words(mask, w0, w1, PB, nrun, nstart);
+        const int run0 = block_scan256<false>(nrun, buf) - nrun;      // the runs that start before this thread's words
+        runs1 = buf[255];
+        __syncthreads();
+        if (runs1 <= kPruneRuns) {      // (workgroup-uniform)
+            emit_words(1, nstart);
+            return;
+        }
+        // More runs than kPruneRuns: the gap in front of every run but the first, from the words as well, g by bisection over the
+        // gap lengths (one count over the workgroup per step and 256 gaps; the walk pays two scans per step and 256 BLOCKS), and the
+        // pieces from the words again.  A slab with more gaps than the list holds keeps the walk below.
+        if (runs1 - 1 <= kPruneGaps) {
+            const int n_gaps = runs1 - 1;
+            prune_gap_lengths(mask, w0, w1, run0, kPruneGaps, gaps);
+            __syncthreads();
+            int lo_g = 0, hi_g = nT;      // (prune_gap_select, glhip_prune_words.h)
+            while (hi_g - lo_g > 1) {
+                const int mid = lo_g + (hi_g - lo_g) / 2;
+                int c = 0;
+                for (int q0 = 0; q0 < n_gaps; q0 += 256) c += __syncthreads_count(q0 + tid < n_gaps && gaps[q0 + tid] >= mid);
+                if (1 + c > kPruneRuns) lo_g = mid; else hi_g = mid;
+            }
+            prune_count_words(mask, w0, w1, PB, nrun, nstart, hi_g);
+            emit_words(hi_g, nstart);
             return;
         }
     }
@@ -809,7 +876,7 @@ __global__ void __launch_bounds__(256) prune_slabs_kernel(const T* __restrict__ 
 // the slab's 8 tiles W of 32 rows, the seed ms(W) — the smallest over the tile's rows of the row's exact largest exponent over the home
 // block, float64 from the points themselves — then one histogram per tile of the keys k(W, G) = lse(G) - dmin(W,G)^2 / (2 eps) of the
 // groups G inside the slab's emitted intervals, starting at ms(W) - L, and from it the threshold t2(W): written in log2 units, the
-// reducing kernel's, as a float32 rounded toward minus infinity.  Thread = row for the seeds, thread = group for the histograms.
+// reducing kernel's, as a float32 rounded toward minus infinity.  Thread = row for the seeds, thread = (group, tile) for the histograms.
 static_assert(kPruneRuns + kPruneGrid <= 256 && kSortSlab == 256, "one thread per interval slot / per row");
 template <typename T>
 __global__ void __launch_bounds__(256) prune_tiles_kernel(const T* __restrict__ xs, const T* __restrict__ ys, const float* __restrict__ h,
@@ -880,33 +947,54 @@ __global__ void __launch_bounds__(256) prune_tiles_kernel(const T* __restrict__ 
     first_group[tid] = incl - ng;
     const int total = buf[255];
     __syncthreads();
-    double under[kTiles];
-    for (int c = 0; c < kTiles; ++c) under[c] = 0.0;
-    for (int f = tid; f < total; f += 256) {
-        int q = 0;      // the last slot with first_group <= f (empty slots share their successor's value and are passed over)
-        for (int step = 128; step > 0; step >>= 1)
-            if (q + step < 256 && first_group[q + step] <= f) q += step;
-        const int g = (slots[2 * q] >> 5) + (f - first_group[q]);
-        const GroupBox b = groups[g];
-        if (b.special) continue;
-        for (int c = 0; c < kTiles; ++c) {
-            const double m = ms[c];
-            if (!(m == m)) continue;
-            double dmin2 = 0.0;
-            for (int d = 0; d < 3; ++d) {
-                const double gap = fmax(fmax((double)b.lohi[d][0] - (double)thi[c][d], (double)tlo[c][d] - (double)b.lohi[d][1]), 0.0);
-                dmin2 = fma(gap, gap, dmin2);
+    // The groups go through in chunks of 256: thread = group to find the chunk's group numbers, then thread = (group, tile) pair with
+    // the tile in the low bits, 32 groups per pass.  A wavefront's adds of one instruction so go to the 8 histograms, 8 groups each,
+    // not to the few buckets that 64 neighbouring groups share in ONE histogram; a thread keeps one tile's box, seed and underflow
+    // sum in registers, not eight, and the loop over tiles with the inlined exp is gone.
+    const int c = tid & (kTiles - 1), sub = tid / kTiles;
+    const double m = ms[c], lo_key = m - L;
+    double tl[3], th[3];
+    for (int d = 0; d < 3; ++d) {
+        tl[d] = (double)tlo[c][d];
+        th[d] = (double)thi[c][d];
+    }
+    double under = 0.0;
+    for (int f0 = 0; f0 < total; f0 += 256) {
+        const int f = f0 + tid;
+        int g = 0;
+        if (f < total) {
+            int q = 0;      // the last slot with first_group <= f (empty slots share their successor's value and are passed over)
+            for (int step = 128; step > 0; step >>= 1)
+                if (q + step < 256 && first_group[q + step] <= f) q += step;
+            g = (slots[2 * q] >> 5) + (f - first_group[q]);
+        }
+        __syncthreads();      // every read of the chunk before is done (and, first, of the scan)
+        buf[tid] = g;
+        __syncthreads();
+        if (!(m == m)) continue;      // (the barriers above are passed by every thread)
+        const int cnt = min(256, total - f0);
+        for (int s = sub; s < cnt; s += 2 * (256 / kTiles)) {      // two records in flight
+            const int s1 = s + 256 / kTiles;
+            const GroupBox b0 = groups[buf[s]], b1 = groups[buf[min(s1, cnt - 1)]];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const GroupBox& b = u ? b1 : b0;
+                if ((u && s1 >= cnt) || b.special) continue;
+                double dmin2 = 0.0;
+                for (int d = 0; d < 3; ++d) {
+                    const double gap = fmax(fmax((double)b.lohi[d][0] - th[d], tl[d] - (double)b.lohi[d][1]), 0.0);
+                    dmin2 = fma(gap, gap, dmin2);
+                }
+                const double key = (double)b.lse - dmin2 * inv2eps;
+                const int bk = prune_bucket(key, lo_key);
+                if (bk >= kPruneBuckets) continue;
+                const double mass = exp(key - m);
+                if (bk < 0) under += mass;
+                else if (mass > 0.0) atomicAdd(&hist[c][bk], mass);
             }
-            const double key = (double)b.lse - dmin2 * inv2eps;
-            const int bk = prune_bucket(key, m - L);
-            if (bk >= kPruneBuckets) continue;
-            const double mass = exp(key - m);
-            if (bk < 0) under[c] += mass;
-            else if (mass > 0.0) atomicAdd(&hist[c][bk], mass);
         }
     }
-    for (int c = 0; c < kTiles; ++c)
-        if (under[c] > 0.0) atomicAdd(&hist[c][kPruneBuckets], under[c]);
+    if (under > 0.0) atomicAdd(&hist[c][kPruneBuckets], under);
     __syncthreads();
     if (tid < kTiles && r0 + 32 * tid < r1) {
         const double m = ms[tid];

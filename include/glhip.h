@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 132 /* 0.1.32 */
+#define GLHIP_VERSION 133 /* 0.1.33 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
