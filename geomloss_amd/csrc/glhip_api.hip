@@ -40,8 +40,8 @@ static bool softmin_sorts(int B, int N, int M, int D, int p, int n_ranges, int f
 
 // The inner launch of a sorted call: the block-sparse launch over the slabs of the sorted clouds, on the rest of the workspace.  p = 2:
 // with the records of the second pruning level (glhip_softmin_x32.h), which only this path hands to a kernel.
-static int sorted_inner(const AutoSort& a, const void* x, const float* h, int N, int M, int D, float eps, int p, int in_dtype, int flags,
-                        hipStream_t st, const StepArgs& step = StepArgs()) {
+static int sorted_inner(const char* fn, const AutoSort& a, const void* x, const float* h, int N, int M, int D, float eps, int p, int in_dtype,
+                        int flags, hipStream_t st, const StepArgs& step) {
     const int inner = flags | (p == 1 ? GLHIP_FLAG_MFMA_DIST : 0) | GLHIP_FLAG_NO_SORT;
     Scratch sc = make_scratch(a.inner_ws, a.inner_bytes, inner, a.C, N);
     if (p == 2) {
@@ -53,9 +53,8 @@ static int sorted_inner(const AutoSort& a, const void* x, const float* h, int N,
         sc.l2.L2 = (float)(prune_L(M) * 1.4426950408889634);
     }
     const Ranges rg{a.ranges_i, a.slices_i, a.red};
-    return (in_dtype == GLHIP_F32)
-               ? softmin_typed<false, float>(a.xs, a.ys, h, a.out, nullptr, nullptr, nullptr, 1, N, M, D, eps, p, rg, a.C, sc, inner, st, step)
-               : softmin_typed<false, bf16_t>(a.xs, a.ys, h, a.out, nullptr, nullptr, nullptr, 1, N, M, D, eps, p, rg, a.C, sc, inner, st, step);
+    return (in_dtype == GLHIP_F32) ? softmin_fwd_typed<float>(fn, a.xs, a.ys, h, a.out, 1, N, M, D, eps, p, rg, a.C, sc, inner, st, step)
+                                   : softmin_fwd_typed<bf16_t>(fn, a.xs, a.ys, h, a.out, 1, N, M, D, eps, p, rg, a.C, sc, inner, st, step);
 }
 
 int glhip_softmin_fwd_family(int B, long N, long M, int D, int p, int dtype, int flags, int n_ranges) {
@@ -67,87 +66,60 @@ int glhip_softmin_fwd_family(int B, long N, long M, int D, int p, int dtype, int
     return softmin_fwd_family(B, N, M, D, p, flags, n_ranges);
 }
 
-int glhip_softmin_fwd(const void* x, const void* y, const float* h, float* out, int B, int N, int M, int D,
-                      float eps, int p, int in_dtype, const int32_t* ranges_i, const int32_t* slices_i,
-                      const int32_t* redranges_j, int n_ranges, void* workspace, size_t workspace_bytes, int flags,
-                      void* stream) {
-    int rc = check_common("glhip_softmin_fwd", x, y, h, B, N, M, D, in_dtype, ranges_i, slices_i, redranges_j, n_ranges);
+// The body of glhip_sinkhorn_step and of glhip_softmin_fwd, which is the step with pot = prev = NULL and damping = 1.  `fn`: the entry point
+// the caller used, for messages.
+static int softmin_step(const char* fn, const void* x, const void* y, const float* logw, const float* pot, const float* prev, float* out, int B,
+                        int N, int M, int D, float eps, float damping, int p, int in_dtype, const int32_t* ranges_i, const int32_t* slices_i,
+                        const int32_t* redranges_j, int n_ranges, void* workspace, size_t workspace_bytes, int flags, void* stream) {
+    int rc = check_common(fn, x, y, logw, B, N, M, D, in_dtype, ranges_i, slices_i, redranges_j, n_ranges);
     if (rc) return rc;
     if (B == 0 || N == 0) return GLHIP_OK;   // nothing to write
-    if (!out) return fail(GLHIP_EINVAL, "glhip_softmin_fwd: NULL out");
-    if (!(eps > 0.f)) return fail(GLHIP_EINVAL, "glhip_softmin_fwd: eps must be > 0");
-    if (p != 1 && p != 2) return fail(GLHIP_EUNSUPPORTED, "glhip_softmin_fwd: p must be 1 or 2 (got %d)", p);
-    const Ranges rg{ranges_i, slices_i, redranges_j};
+    if (!out) return fail(GLHIP_EINVAL, "%s: NULL out", fn);
+    if (out == prev) return fail(GLHIP_EINVAL, "%s: out must not alias prev (updates are simultaneous)", fn);
+    if (!(eps > 0.f)) return fail(GLHIP_EINVAL, "%s: eps must be > 0", fn);
+    if (p != 1 && p != 2) return fail(GLHIP_EUNSUPPORTED, "%s: p must be 1 or 2 (got %d)", fn, p);
     hipStream_t st = static_cast<hipStream_t>(stream);
+    StepArgs step{pot, prev, prev ? 0.5f * damping : damping, prev ? 0.5f : 0.f};
     if (softmin_sorts(B, N, M, D, p, n_ranges, flags)) {
         AutoSort a;
         const int C = (N + kSortSlab - 1) / kSortSlab;
         rc = autosort_prepare(a, x, y, N, M, D, in_dtype, workspace, workspace_bytes, glhip_workspace_bytes(1, N, M, D, C), st, p == 1);
         if (rc) return rc;
-        if (a.on) {
-            gather_f32(h, a.perm_y, a.col0, M, st);
+        if (a.on) {      // the potentials travel with their clouds
+            gather_f32(logw, a.perm_y, a.col0, M, st);
+            if (pot) { gather_f32(pot, a.perm_y, a.col1, M, st); step.pot = a.col1; }
+            if (prev) { gather_f32(prev, a.perm_x, a.row0, N, st); step.prev = a.row0; }
+            // (the bound takes the column vector the kernels form: logw + pot / eps)
             if (p == 2)
-                prune_ranges(a.xs, a.ys, a.col0, nullptr, 0.f, N, M, D, in_dtype, eps, a.ranges_i, a.slices_i, a.red, a.blocks, a.groups, a.home, a.t2, a.mlb, a.t1, st);
-            rc = sorted_inner(a, x, a.col0, N, M, D, eps, p, in_dtype, flags, st);
+                prune_ranges(a.xs, a.ys, a.col0, step.pot, 1.0f / eps, N, M, D, in_dtype, eps, a.ranges_i, a.slices_i, a.red, a.blocks, a.groups, a.home,
+                             a.t2, a.mlb, a.t1, st);
+            rc = sorted_inner(fn, a, x, a.col0, N, M, D, eps, p, in_dtype, flags, st, step);
             if (rc) return rc;
             scatter_f32(a.out, a.perm_x, out, N, st);
-            return check_launch("glhip_softmin_fwd");
+            return check_launch(fn);
         }
     }
+    const Ranges rg{ranges_i, slices_i, redranges_j};
     const Scratch sc = make_scratch(workspace, workspace_bytes, flags, n_ranges, N);
-    rc = (in_dtype == GLHIP_F32)
-             ? softmin_typed<false, float>(x, y, h, out, nullptr, nullptr, nullptr, B, N, M, D, eps, p, rg, n_ranges, sc, flags, st)
-             : softmin_typed<false, bf16_t>(x, y, h, out, nullptr, nullptr, nullptr, B, N, M, D, eps, p, rg, n_ranges, sc, flags, st);
-    return rc ? rc : check_launch("glhip_softmin_fwd");
+    rc = (in_dtype == GLHIP_F32) ? softmin_fwd_typed<float>(fn, x, y, logw, out, B, N, M, D, eps, p, rg, n_ranges, sc, flags, st, step)
+                                 : softmin_fwd_typed<bf16_t>(fn, x, y, logw, out, B, N, M, D, eps, p, rg, n_ranges, sc, flags, st, step);
+    return rc ? rc : check_launch(fn);
+}
+
+int glhip_softmin_fwd(const void* x, const void* y, const float* h, float* out, int B, int N, int M, int D,
+                      float eps, int p, int in_dtype, const int32_t* ranges_i, const int32_t* slices_i,
+                      const int32_t* redranges_j, int n_ranges, void* workspace, size_t workspace_bytes, int flags,
+                      void* stream) {
+    return softmin_step("glhip_softmin_fwd", x, y, h, nullptr, nullptr, out, B, N, M, D, eps, 1.f, p, in_dtype, ranges_i, slices_i, redranges_j,
+                        n_ranges, workspace, workspace_bytes, flags, stream);
 }
 
 int glhip_sinkhorn_step(const void* x, const void* y, const float* logw, const float* pot, const float* prev,
                         float* out, int B, int N, int M, int D, float eps, float damping, int p, int in_dtype,
                         const int32_t* ranges_i, const int32_t* slices_i, const int32_t* redranges_j, int n_ranges,
                         void* workspace, size_t workspace_bytes, int flags, void* stream) {
-    int rc = check_common("glhip_sinkhorn_step", x, y, logw, B, N, M, D, in_dtype, ranges_i, slices_i, redranges_j, n_ranges);
-    if (rc) return rc;
-    if (B == 0 || N == 0) return GLHIP_OK;   // nothing to write
-    if (!out) return fail(GLHIP_EINVAL, "glhip_sinkhorn_step: NULL out");
-    if (out == prev) return fail(GLHIP_EINVAL, "glhip_sinkhorn_step: out must not alias prev (updates are simultaneous)");
-    if (!(eps > 0.f)) return fail(GLHIP_EINVAL, "glhip_sinkhorn_step: eps must be > 0");
-    if (p != 1 && p != 2) return fail(GLHIP_EUNSUPPORTED, "glhip_sinkhorn_step: p must be 1 or 2 (got %d)", p);
-    const Ranges rg{ranges_i, slices_i, redranges_j};
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (softmin_sorts(B, N, M, D, p, n_ranges, flags)) {   // as glhip_softmin_fwd; the potentials travel with their clouds
-        AutoSort a;
-        const int C = (N + kSortSlab - 1) / kSortSlab;
-        rc = autosort_prepare(a, x, y, N, M, D, in_dtype, workspace, workspace_bytes, glhip_workspace_bytes(1, N, M, D, C), st, p == 1);
-        if (rc) return rc;
-        if (a.on) {
-            gather_f32(logw, a.perm_y, a.col0, M, st);
-            if (pot) gather_f32(pot, a.perm_y, a.col1, M, st);
-            if (prev) gather_f32(prev, a.perm_x, a.row0, N, st);
-            // (the bound takes the column vector the kernels form: logw + pot / eps)
-            if (p == 2)
-                prune_ranges(a.xs, a.ys, a.col0, pot ? a.col1 : nullptr, 1.0f / eps, N, M, D, in_dtype, eps, a.ranges_i, a.slices_i, a.red, a.blocks,
-                             a.groups, a.home, a.t2, a.mlb, a.t1, st);
-            StepArgs inner_step;
-            inner_step.pot = pot ? a.col1 : nullptr;
-            inner_step.prev = prev ? a.row0 : nullptr;
-            inner_step.alpha = prev ? 0.5f * damping : damping;
-            inner_step.beta = prev ? 0.5f : 0.f;
-            rc = sorted_inner(a, x, a.col0, N, M, D, eps, p, in_dtype, flags, st, inner_step);
-            if (rc) return rc;
-            scatter_f32(a.out, a.perm_x, out, N, st);
-            return check_launch("glhip_sinkhorn_step");
-        }
-    }
-    const Scratch sc = make_scratch(workspace, workspace_bytes, flags, n_ranges, N);
-    StepArgs step;
-    step.pot = pot;
-    step.prev = prev;
-    step.alpha = prev ? 0.5f * damping : damping;
-    step.beta = prev ? 0.5f : 0.f;
-    rc = (in_dtype == GLHIP_F32)
-             ? softmin_typed<false, float>(x, y, logw, out, nullptr, nullptr, nullptr, B, N, M, D, eps, p, rg, n_ranges, sc, flags, st, step)
-             : softmin_typed<false, bf16_t>(x, y, logw, out, nullptr, nullptr, nullptr, B, N, M, D, eps, p, rg, n_ranges, sc, flags, st, step);
-    return rc ? rc : check_launch("glhip_sinkhorn_step");
+    return softmin_step("glhip_sinkhorn_step", x, y, logw, pot, prev, out, B, N, M, D, eps, damping, p, in_dtype, ranges_i, slices_i, redranges_j,
+                        n_ranges, workspace, workspace_bytes, flags, stream);
 }
 
 int glhip_prune_inspect_slots(int M) { return M > 0 ? prune_plan(M).S : GLHIP_EINVAL; }

@@ -16,18 +16,17 @@ int glhip_softmin_bwd_x(const void* x, const void* y, const float* h, const floa
     if (p != 1 && p != 2) return fail(GLHIP_EUNSUPPORTED, "glhip_softmin_bwd_x: p must be 1 or 2 (got %d)", p);
     const Ranges rg{ranges_i, slices_i, redranges_j};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (glhip_softmin_bwd_x_uses_plan(B, N, M, D, p, in_dtype, flags, n_ranges) == 1) {      // GLHIP_FLAG_XK_GRAD: p = 2, 17 <= D <= 4095, dense
+    const int fam = softmin_bwd_family(1, B, N, M, D, p, flags, n_ranges);
+    if (fam == GLHIP_FAMILY_XK) {      // GLHIP_FLAG_XK_GRAD: p = 2, 17 <= D <= 4095, dense
         rc = softmin_grad_xk_launch(x, y, h, out, grad_out, grad_x, B, N, M, D, eps, in_dtype, workspace, workspace_bytes, flags, st);
-        return rc ? rc : check_launch("glhip_softmin_bwd_x");
-    }
-    if (p == 1 && glhip_dist_grad_uses_xk(GLHIP_DIST_GRAD_SOFTMIN_P1, B, N, M, D, in_dtype, flags, n_ranges) == 1) {      // GLHIP_FLAG_XK_DIST_GRAD: p = 1, 17 <= D <= 4095, dense
+    } else if (fam == GLHIP_FAMILY_DIST && D > kXdMaxD) {      // GLHIP_FLAG_XK_DIST_GRAD: p = 1, 17 <= D <= 4095, dense
         rc = dist_grad_xk_launch(GLHIP_DIST_GRAD_SOFTMIN_P1, x, y, h, grad_out, nullptr, grad_x, B, N, M, D, eps, in_dtype, workspace, workspace_bytes, flags, st);
-        return rc ? rc : check_launch("glhip_softmin_bwd_x");
+    } else {
+        const Scratch sc = make_scratch(workspace, workspace_bytes, flags, n_ranges, N);
+        rc = (in_dtype == GLHIP_F32)
+                 ? softmin_bwd_typed<float>(fam, x, y, h, nullptr, out, grad_out, grad_x, B, N, M, D, eps, p, rg, n_ranges, sc, flags, st)
+                 : softmin_bwd_typed<bf16_t>(fam, x, y, h, nullptr, out, grad_out, grad_x, B, N, M, D, eps, p, rg, n_ranges, sc, flags, st);
     }
-    const Scratch sc = make_scratch(workspace, workspace_bytes, flags, n_ranges, N);
-    rc = (in_dtype == GLHIP_F32)
-             ? softmin_typed<true, float>(x, y, h, nullptr, out, grad_out, grad_x, B, N, M, D, eps, p, rg, n_ranges, sc, flags, st)
-             : softmin_typed<true, bf16_t>(x, y, h, nullptr, out, grad_out, grad_x, B, N, M, D, eps, p, rg, n_ranges, sc, flags, st);
     return rc ? rc : check_launch("glhip_softmin_bwd_x");
 }
 
@@ -37,7 +36,8 @@ int glhip_softmin_fwd_grad(const void* x, const void* y, const float* h, const f
                            size_t workspace_bytes, int flags, void* stream) {
     int rc = check_common("glhip_softmin_fwd_grad", x, y, h, B, N, M, D, in_dtype, ranges_i, slices_i, redranges_j, n_ranges);
     if (rc) return rc;
-    if (p != 2 || D > kXdMaxD || (flags & (GLHIP_FLAG_NO_MFMA | GLHIP_FLAG_DIRECT)))
+    const int fam = softmin_bwd_family(2, B, N, M, D, p, flags, n_ranges);
+    if (fam == GLHIP_EUNSUPPORTED)
         return fail(GLHIP_EUNSUPPORTED, "glhip_softmin_fwd_grad: only p = 2, D <= 16 on the matrix-core kernels (got p %d, D %d, flags %d): "
                                         "call glhip_softmin_fwd + glhip_softmin_bwd_x", p, D, flags);
     if (B == 0 || N == 0) return GLHIP_OK;
@@ -46,11 +46,10 @@ int glhip_softmin_fwd_grad(const void* x, const void* y, const float* h, const f
     const Ranges rg{ranges_i, slices_i, redranges_j};
     hipStream_t st = static_cast<hipStream_t>(stream);
     const Scratch sc = make_scratch(workspace, workspace_bytes, flags, n_ranges, N);
-    StepArgs step;
-    step.shift2 = margin * kLog2e / eps;      // the guess may be this far (in units of LSE2) below the exact value's upper bound
+    const float shift2 = margin * kLog2e / eps;      // the guess may be this far (in units of LSE2) below the exact value's upper bound
     rc = (in_dtype == GLHIP_F32)
-             ? softmin_typed<true, float>(x, y, h, out, guess, nullptr, grad_unit, B, N, M, D, eps, p, rg, n_ranges, sc, flags, st, step)
-             : softmin_typed<true, bf16_t>(x, y, h, out, guess, nullptr, grad_unit, B, N, M, D, eps, p, rg, n_ranges, sc, flags, st, step);
+             ? softmin_bwd_typed<float>(fam, x, y, h, out, guess, nullptr, grad_unit, B, N, M, D, eps, p, rg, n_ranges, sc, flags, st, shift2)
+             : softmin_bwd_typed<bf16_t>(fam, x, y, h, out, guess, nullptr, grad_unit, B, N, M, D, eps, p, rg, n_ranges, sc, flags, st, shift2);
     return rc ? rc : check_launch("glhip_softmin_fwd_grad");
 }
 

@@ -36,9 +36,10 @@ int glhip_kernel_conv_fwd(int kind, const void* x, const void* y, const float* v
         if (rc || ran) return rc;
     }
     const Scratch sc = make_scratch(workspace, workspace_bytes, flags, n_ranges, N);
+    const int fam = conv_family(kind, 0, B, D, flags, n_ranges);
     rc = (in_dtype == GLHIP_F32)
-             ? conv_typed<0, float>(kind, x, y, v, out, nullptr, nullptr, B, N, M, D, blur, rg, n_ranges, sc, flags, st)
-             : conv_typed<0, bf16_t>(kind, x, y, v, out, nullptr, nullptr, B, N, M, D, blur, rg, n_ranges, sc, flags, st);
+             ? conv_typed<0, float>(fam, kind, x, y, v, out, nullptr, nullptr, B, N, M, D, blur, rg, n_ranges, sc, flags, st)
+             : conv_typed<0, bf16_t>(fam, kind, x, y, v, out, nullptr, nullptr, B, N, M, D, blur, rg, n_ranges, sc, flags, st);
     return rc ? rc : check_launch("glhip_kernel_conv_fwd");
 }
 

@@ -3,15 +3,6 @@
 #include "glhip_grad_xk.h"
 #include "glhip_launch.h"
 
-namespace {
-// laplacian / energy, 17 <= D <= 4095, dense, under GLHIP_FLAG_XK_DIST_GRAD: the op of glhip_dist_grad_uses_xk, or -1
-inline int dist_grad_op(int kind, int B, int N, int M, int D, int in_dtype, int flags, int n_ranges) {
-    if (kind != GLHIP_LAPLACIAN && kind != GLHIP_ENERGY) return -1;
-    const int op = kind == GLHIP_LAPLACIAN ? GLHIP_DIST_GRAD_LAPLACIAN : GLHIP_DIST_GRAD_ENERGY;
-    return glhip_dist_grad_uses_xk(op, B, N, M, D, in_dtype, flags, n_ranges) == 1 ? op : -1;
-}
-}  // namespace
-
 extern "C" {
 
 int glhip_kernel_conv_bwd_x(int kind, const void* x, const void* y, const float* v, const float* g, float* grad_x,
@@ -26,18 +17,17 @@ int glhip_kernel_conv_bwd_x(int kind, const void* x, const void* y, const float*
     if (kind != GLHIP_ENERGY && !(blur > 0.f)) return fail(GLHIP_EINVAL, "glhip_kernel_conv_bwd_x: blur must be > 0");
     const Ranges rg{ranges_i, slices_i, redranges_j};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (glhip_kernel_conv_grad_uses_xk(kind, B, N, M, D, in_dtype, flags, n_ranges) == 1) {      // GLHIP_FLAG_XK_GRAD: gaussian, 17 <= D <= 4095, dense
+    const int fam = conv_family(kind, 1, B, D, flags, n_ranges);
+    if (fam == GLHIP_FAMILY_XK) {      // GLHIP_FLAG_XK_GRAD: gaussian, 17 <= D <= 4095, dense
         rc = gauss_grad_xk_launch(x, y, v, g, nullptr, grad_x, B, N, M, D, blur, in_dtype, workspace, workspace_bytes, flags, st);
-        return rc ? rc : check_launch("glhip_kernel_conv_bwd_x");
+    } else if (fam == GLHIP_FAMILY_DIST && D > kXdMaxD) {      // GLHIP_FLAG_XK_DIST_GRAD: laplacian / energy (the op is the kind), 17 <= D <= 4095, dense
+        rc = dist_grad_xk_launch(kind, x, y, v, g, nullptr, grad_x, B, N, M, D, blur, in_dtype, workspace, workspace_bytes, flags, st);
+    } else {
+        const Scratch sc = make_scratch(workspace, workspace_bytes, flags, n_ranges, N);
+        rc = (in_dtype == GLHIP_F32)
+                 ? conv_typed<1, float>(fam, kind, x, y, v, nullptr, g, grad_x, B, N, M, D, blur, rg, n_ranges, sc, flags, st)
+                 : conv_typed<1, bf16_t>(fam, kind, x, y, v, nullptr, g, grad_x, B, N, M, D, blur, rg, n_ranges, sc, flags, st);
     }
-    if (const int op = dist_grad_op(kind, B, N, M, D, in_dtype, flags, n_ranges); op >= 0) {      // GLHIP_FLAG_XK_DIST_GRAD: laplacian / energy
-        rc = dist_grad_xk_launch(op, x, y, v, g, nullptr, grad_x, B, N, M, D, blur, in_dtype, workspace, workspace_bytes, flags, st);
-        return rc ? rc : check_launch("glhip_kernel_conv_bwd_x");
-    }
-    const Scratch sc = make_scratch(workspace, workspace_bytes, flags, n_ranges, N);
-    rc = (in_dtype == GLHIP_F32)
-             ? conv_typed<1, float>(kind, x, y, v, nullptr, g, grad_x, B, N, M, D, blur, rg, n_ranges, sc, flags, st)
-             : conv_typed<1, bf16_t>(kind, x, y, v, nullptr, g, grad_x, B, N, M, D, blur, rg, n_ranges, sc, flags, st);
     return rc ? rc : check_launch("glhip_kernel_conv_bwd_x");
 }
 
@@ -49,9 +39,8 @@ int glhip_kernel_conv_fwd_grad(int kind, const void* x, const void* y, const flo
     if (rc) return rc;
     if (kind < GLHIP_GAUSSIAN || kind > GLHIP_ENERGY)
         return fail(GLHIP_EINVAL, "glhip_kernel_conv_fwd_grad: unknown kernel id %d", kind);
-    const bool xk = glhip_kernel_conv_grad_uses_xk(kind, B, N, M, D, in_dtype, flags, n_ranges) == 1;      // GLHIP_FLAG_XK_GRAD
-    const int dop = xk ? -1 : dist_grad_op(kind, B, N, M, D, in_dtype, flags, n_ranges);      // GLHIP_FLAG_XK_DIST_GRAD
-    if (!xk && dop < 0 && conv_family(kind, 2, B, D, flags, n_ranges) == GLHIP_EUNSUPPORTED)
+    const int fam = conv_family(kind, 2, B, D, flags, n_ranges);
+    if (fam == GLHIP_EUNSUPPORTED)
         return fail(GLHIP_EUNSUPPORTED, "glhip_kernel_conv_fwd_grad: D <= 3 (gaussian on the matrix cores: D <= 16; 17 <= D <= 4095 "
                                         "under GLHIP_FLAG_XK_GRAD; laplacian / energy of 17 <= D <= 4095 under GLHIP_FLAG_XK_DIST_GRAD) only (got kind %d, D %d, flags %d): call glhip_kernel_conv_fwd + "
                                         "glhip_kernel_conv_bwd_x", kind, D, flags);
@@ -59,12 +48,12 @@ int glhip_kernel_conv_fwd_grad(int kind, const void* x, const void* y, const flo
     if (!out || !grad_unit) return fail(GLHIP_EINVAL, "glhip_kernel_conv_fwd_grad: NULL out / grad_unit");
     if (kind != GLHIP_ENERGY && !(blur > 0.f)) return fail(GLHIP_EINVAL, "glhip_kernel_conv_fwd_grad: blur must be > 0");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (xk) {      // gaussian, 17 <= D <= 4095, dense: the passes of glhip_gauss_grad_xk.h
+    if (fam == GLHIP_FAMILY_XK) {      // GLHIP_FLAG_XK_GRAD: gaussian, 17 <= D <= 4095, dense: the passes of glhip_gauss_grad_xk.h
         rc = gauss_grad_xk_launch(x, y, v, nullptr, out, grad_unit, B, N, M, D, blur, in_dtype, workspace, workspace_bytes, flags, st);
         return rc ? rc : check_launch("glhip_kernel_conv_fwd_grad");
     }
-    if (dop >= 0) {      // laplacian / energy, 17 <= D <= 4095, dense: the passes of glhip_dist_grad_xk.h
-        rc = dist_grad_xk_launch(dop, x, y, v, nullptr, out, grad_unit, B, N, M, D, blur, in_dtype, workspace, workspace_bytes, flags, st);
+    if (fam == GLHIP_FAMILY_DIST && D > kXdMaxD) {      // GLHIP_FLAG_XK_DIST_GRAD: laplacian / energy (the op is the kind): the passes of glhip_dist_grad_xk.h
+        rc = dist_grad_xk_launch(kind, x, y, v, nullptr, out, grad_unit, B, N, M, D, blur, in_dtype, workspace, workspace_bytes, flags, st);
         return rc ? rc : check_launch("glhip_kernel_conv_fwd_grad");
     }
     const Ranges rg{ranges_i, slices_i, redranges_j};
@@ -79,8 +68,8 @@ int glhip_kernel_conv_fwd_grad(int kind, const void* x, const void* y, const flo
     }
     const Scratch sc = make_scratch(workspace, workspace_bytes, flags, n_ranges, N);
     rc = (in_dtype == GLHIP_F32)
-             ? conv_typed<2, float>(kind, x, y, v, out, nullptr, grad_unit, B, N, M, D, blur, rg, n_ranges, sc, flags, st)
-             : conv_typed<2, bf16_t>(kind, x, y, v, out, nullptr, grad_unit, B, N, M, D, blur, rg, n_ranges, sc, flags, st);
+             ? conv_typed<2, float>(fam, kind, x, y, v, out, nullptr, grad_unit, B, N, M, D, blur, rg, n_ranges, sc, flags, st)
+             : conv_typed<2, bf16_t>(fam, kind, x, y, v, out, nullptr, grad_unit, B, N, M, D, blur, rg, n_ranges, sc, flags, st);
     return rc ? rc : check_launch("glhip_kernel_conv_fwd_grad");
 }
 

@@ -1,6 +1,7 @@
 // glhip_grad_xk.h — the launches behind the matrix-core gradient routes of 17 <= D <= 4095, each defined in a translation unit of its own
 // and called by glhip_softmin_bwd_x (glhip_api_bwd.hip) and glhip_kernel_conv_bwd_x / glhip_kernel_conv_fwd_grad (glhip_api_convgrad.hip) where
-// the route's predicate says so.  The caller has checked the arguments and the predicate, and B, N > 0.
+// softmin_bwd_family / conv_family (glhip_family.h) say GLHIP_FAMILY_XK, or GLHIP_FAMILY_DIST beyond D = 16.  The caller has checked the
+// arguments and the family, and B, N > 0.
 #pragma once
 
 #include <cstddef>

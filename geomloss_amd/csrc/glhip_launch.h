@@ -2,11 +2,14 @@
 // selection and launch templates.  Everything lives in an anonymous namespace on purpose: each .hip file includes this header and
 // instantiates only the templates its entry points use (forward / gradient / kernel-product kernels compile in parallel).
 //
-// Which kernel runs is a host predicate per entry-point family, stated once and switched on by the body that launches:
-//   soft-min forward / half-step   softmin_fwd_family -> softmin_typed<false>      (reported by glhip_softmin_fwd_family)
+// Which kernel runs is a host predicate per entry-point family, stated once (glhip_family.h) and switched on by the body that launches:
+//   soft-min forward / half-step   softmin_fwd_family -> softmin_fwd_typed         (reported by glhip_softmin_fwd_family)
+//   soft-min gradient, two modes   softmin_bwd_family -> softmin_bwd_typed         (glhip_softmin_bwd_x_uses_plan / glhip_dist_grad_uses_xk read it)
 //   kernel products, three modes   conv_family        -> conv_typed<MODE>          (mode 0 reported by glhip_kernel_conv_fwd_family)
+// The gradient routes of 17 <= D <= 4095 are arms of the same values; their launches live in translation units of their own
+// (glhip_grad_xk.h) and the entry points call them where the family says GLHIP_FAMILY_XK, or _DIST beyond D = 16.
 // Parameters come from one builder each (make_softmin_params, make_conv_params: the only place that names the scales of a kernel
-// kind); the one-thread-per-row fallback of both bodies is launch_generic.  The plan family: glhip_launch_plan.h.
+// kind); the one-thread-per-row fallback of the three bodies is launch_generic.  The plan family: glhip_launch_plan.h.
 // How many column splits a launch takes, whether it moves to the XCD-aware grid and where it places pre-packed columns is decided in
 // glhip_split_policy.h (plain C++, one plan function per policy; glhip_workspace_bytes is assembled from the same pieces): a launcher here
 // builds its SplitPlan, hands it to SplitLaunch::apply and launches.
@@ -17,6 +20,7 @@
 #include <cstring>
 
 #include "glhip_error.h"
+#include "glhip_family.h"
 #include "glhip_generic.h"
 #include "glhip_kconv_ops.h"
 #include "glhip_softmin_ops.h"
@@ -84,7 +88,7 @@ Scratch make_scratch(void* workspace, size_t bytes, int flags, int n_ranges, int
     return sc;
 }
 
-// the workgroup heights and the last dimension glhip_split_policy.h sizes the workspace with are the kernels' own
+// the workgroup heights and the last dimension glhip_split_policy.h sizes the workspace with (and glhip_family.h routes by) are the kernels' own
 static_assert(kRowsValu2 == 2 * kBlock && kRowsNW8 == kMfmaRowsPerBlock && kRowsXk == kXkRows && kSizedMaxD == kXkMaxD, "glhip_split_policy.h");
 
 // rows per thread: 2 keeps the LDS read rate at half a ds_read_b128 per row-column step while leaving
@@ -418,21 +422,6 @@ void launch_xk_dist(const DistParams<T>& prm, const typename MergeOp::Params& mp
 
 // (plan application, the D > 16 gradients and argmin: glhip_launch_plan.h)
 
-// Which matrix-core forward family serves a p = 2 soft-min / half-step / gaussian product in dimension D > 3 under `flags`
-// (GLHIP_FLAG_NO_MFMA / _DIRECT: none — the generic kernel)
-inline int highd_p2_family(int D, int flags) {
-    if (flags & (GLHIP_FLAG_NO_MFMA | GLHIP_FLAG_DIRECT)) return GLHIP_FAMILY_GENERIC;
-    if (D <= kXdMaxD) return GLHIP_FAMILY_XD;
-    return D <= kXkMaxD ? GLHIP_FAMILY_XK : GLHIP_FAMILY_GENERIC;
-}
-
-// ... and a distance reduction (p = 1 soft-min / half-step, laplacian / energy product) in dimension D > 3: glhip_dist_xd.h up to D = 16,
-// glhip_dist_xk.h for 17 <= D <= 4095 on the caller's word (GLHIP_FLAG_XK_DIST); dense launches only
-inline bool highd_dist_applies(int B, int D, int flags, int n_ranges) {
-    if (n_ranges != 0 || (flags & (GLHIP_FLAG_NO_MFMA | GLHIP_FLAG_DIRECT))) return false;
-    return D <= kXdMaxD || ((flags & GLHIP_FLAG_XK_DIST) && D <= kXkMaxD && B <= 65535);
-}
-
 // distance reductions for 4 <= D <= 16, dense launches (glhip_dist_xd.h): soft-min p = 1 / fused half-step, laplacian and energy products
 // (small launches split their columns further: dist_small_launch_splits, glhip_split_policy.h)
 template <int MODE, int D, typename T, class MergeOp>
@@ -497,60 +486,6 @@ void launch_gauss_grad_t32(const ConvParams<T>& prm, float blur, const Ranges& r
                            hipStream_t st) {
     if constexpr (FWDGRAD) launch_wsum_t32<WS_GAUSS_FWDGRAD, D, T, GaussFwdGradMerge<D, T>>(gauss_wsum_params(prm, blur), prm, rg, n_ranges, B, N, M, sc, st);
     else launch_wsum_t32<WS_GAUSS_BWD, D, T, ConvOp<GLHIP_GAUSSIAN, D, 1, T, 1>>(gauss_wsum_params(prm, blur), prm, rg, n_ranges, B, N, M, sc, st);
-}
-
-inline bool use_mfma_dist(int flags, int n_ranges, int B, int D) {
-    return (flags & GLHIP_FLAG_MFMA_DIST) != 0 && n_ranges > 0 && B == 1 && D <= 3;
-}
-
-// The kernel family of a soft-min forward / fused half-step launch (GLHIP_FAMILY_*, include/glhip.h): THE predicate of
-// softmin_typed<false> below, and what glhip_softmin_fwd_family reports.  Host arithmetic only.
-inline int softmin_fwd_family(int B, long N, long M, int D, int p, int flags, int n_ranges) {
-    if (D <= 3) {
-        if (p == 1 && use_mfma_dist(flags, n_ranges, B, D)) return GLHIP_FAMILY_DIST;
-        const bool direct = (flags & GLHIP_FLAG_DIRECT) != 0, mfma = (flags & GLHIP_FLAG_NO_MFMA) == 0;
-        // GLHIP_FLAG_F16X2, big dense launches: the kernel of glhip_softmin_xd.h instantiated for D <= 3 (see softmin_typed)
-        const bool ab_flag = (flags & (GLHIP_FLAG_F32_MFMA | GLHIP_FLAG_XDL16)) != 0;
-        if (p == 2 && (flags & GLHIP_FLAG_F16X2) && !direct && mfma && !ab_flag && n_ranges == 0 && M >= 65536 && (double)B * N * M >= 5e8)
-            return GLHIP_FAMILY_XD;
-        return (p == 2 && !direct && mfma) ? GLHIP_FAMILY_X32 : GLHIP_FAMILY_VALU;
-    }
-    if (p == 1) return highd_dist_applies(B, D, flags, n_ranges) ? GLHIP_FAMILY_DIST : GLHIP_FAMILY_GENERIC;
-    return highd_p2_family(D, flags);
-}
-
-// ... and of a kernel product: THE predicate of conv_typed<MODE> below.  `mode` is ConvOp's MODE: 0 product (glhip_kernel_conv_fwd; what
-// glhip_kernel_conv_fwd_family reports), 1 gradient (glhip_kernel_conv_bwd_x), 2 product and unit gradient (glhip_kernel_conv_fwd_grad,
-// which has no generic kernel: GLHIP_EUNSUPPORTED where the others say GLHIP_FAMILY_GENERIC).  The gaussian gradients of 17 <= D <= 4095
-// under GLHIP_FLAG_XK_GRAD are a predicate of their own, asked first (glhip_kernel_conv_grad_uses_xk, glhip_api_convgrad_xk.hip).
-// Gaussian: GLHIP_FAMILY_X32 stands for the matrix-core kernels of D <= 3 (glhip_wsum_x32.h / glhip_wsum_mfma.h), GLHIP_FAMILY_XD in
-// modes 1 and 2 for the transposed kernel of 4 <= D <= 16 (glhip_wsum_t32.h).
-inline int conv_family(int kind, int mode, int B, int D, int flags, int n_ranges) {
-    const bool mfma = !(flags & GLHIP_FLAG_NO_MFMA);
-    if (D <= 3) {
-        if (kind == GLHIP_GAUSSIAN) return mfma ? GLHIP_FAMILY_X32 : GLHIP_FAMILY_VALU;
-        return use_mfma_dist(flags, n_ranges, B, D) ? GLHIP_FAMILY_DIST : GLHIP_FAMILY_VALU;
-    }
-    const int none = mode == 2 ? GLHIP_EUNSUPPORTED : GLHIP_FAMILY_GENERIC;
-    if (kind != GLHIP_GAUSSIAN) {    // laplacian / energy: distances on the matrix cores, dense launches of D <= 16 ...
-        if (mode != 2 && D <= kXdMaxD && n_ranges == 0 && mfma) return GLHIP_FAMILY_DIST;
-        // ... and the product of 17 <= D <= 4095 under GLHIP_FLAG_XK_DIST (glhip_dist_xk.h); its gradients stay generic
-        return (mode == 0 && D > kXdMaxD && highd_dist_applies(B, D, flags, n_ranges)) ? GLHIP_FAMILY_DIST : none;
-    }
-    if (mode == 0) return highd_p2_family(D, flags & ~GLHIP_FLAG_DIRECT);      // (_DIRECT means nothing to a kernel product)
-    return (D <= kXdMaxD && mfma) ? GLHIP_FAMILY_XD : none;
-}
-
-template <int D, bool BWD, typename T>
-void launch_softmin_d(const SoftminParams<T>& prm, const Ranges& rg, int n_ranges, int B, int N, int M, int p,
-                      bool direct, bool mfma, const Scratch& sc, hipStream_t st) {
-    if (p == 1) { launch_softmin_r<D, 1, true, BWD, T>(prm, rg, n_ranges, B, N, M, sc, st); return; }
-    if (direct) { launch_softmin_r<D, 2, true, BWD, T>(prm, rg, n_ranges, B, N, M, sc, st); return; }
-    if (!mfma) { launch_softmin_r<D, 2, false, BWD, T>(prm, rg, n_ranges, B, N, M, sc, st); return; }
-    // `if constexpr`: the gradient translation unit does not instantiate the forward kernels, and vice versa
-    // (the soft-min gradient runs on the 16x16x32 kernel only: x32 = false)
-    if constexpr (BWD) launch_wsum<WS_SOFTMIN_BWD, D, T, SoftminBwdOp<D, 2, false, 1, T>>(softmin_wsum_params(prm), prm, rg, n_ranges, B, N, M, sc, false, st);
-    else launch_softmin_mfma<D, T>(prm, rg, n_ranges, B, N, M, sc, st);
 }
 
 template <typename T>
@@ -742,32 +677,54 @@ int extrapolate4_typed(const void* x, const void* y, const void* xc, const void*
     return multi_dispatch<T>(m, B, D, p, sc, st);
 }
 
+// D <= 3 on the VALU skeleton: p = 1, and p = 2 on explicit differences (GLHIP_FLAG_DIRECT) or in the expanded form (GLHIP_FLAG_NO_MFMA)
+template <int D, bool BWD, typename T>
+void launch_softmin_valu(const SoftminParams<T>& prm, const Ranges& rg, int n_ranges, int B, int N, int M, int p, int flags, const Scratch& sc,
+                         hipStream_t st) {
+    if (p == 1) launch_softmin_r<D, 1, true, BWD, T>(prm, rg, n_ranges, B, N, M, sc, st);
+    else if (flags & GLHIP_FLAG_DIRECT) launch_softmin_r<D, 2, true, BWD, T>(prm, rg, n_ranges, B, N, M, sc, st);
+    else launch_softmin_r<D, 2, false, BWD, T>(prm, rg, n_ranges, B, N, M, sc, st);
+}
+
 struct StepArgs {   // fused Sinkhorn half-step; all-default = plain soft-min
     const float* pot = nullptr;
     const float* prev = nullptr;
     float alpha = 1.f, beta = 0.f;
-    float shift2 = 0.f;     // value-and-gradient mode of the gradient kernels
 };
 
-template <bool BWD, typename T>
-int softmin_typed(const void* x, const void* y, const float* h, float* out, const float* fwd, const float* g,
-                  float* gx, int B, int N, int M, int D, float eps, int p, const Ranges& rg, int n_ranges,
-                  const Scratch& sc, int flags, hipStream_t st, const StepArgs& step = StepArgs()) {
-    const float s2 = kLog2e / eps;
-    const float out_scale = -eps * kLn2;
-    const int fam = BWD ? -1 : softmin_fwd_family(B, N, M, D, p, flags, n_ranges);      // forward launches: the family decides
-    if (D <= 3) {
-        const bool direct = (flags & GLHIP_FLAG_DIRECT) != 0;
-        const bool mfma = BWD ? (flags & GLHIP_FLAG_NO_MFMA) == 0 : fam == GLHIP_FAMILY_X32;
-        SoftminParams<T> prm = make_softmin_params<T>(x, y, h, out, eps, p, step.pot, step.prev, step.alpha, step.beta);
-        prm.fwd = fwd; prm.g = g; prm.gx = gx; prm.shift2 = step.shift2;
-        if constexpr (!BWD) {
-            if (fam == GLHIP_FAMILY_DIST) {
-#define GL_D(DD) launch_dist<DM_SOFTMIN_P1, DD, T, SoftminFwdOp<DD, 1, true, 1, T>>(dist_params(prm), prm, rg, n_ranges, N, M, sc, st)
-                GLHIP_D3_DISPATCH(D, GL_D)
+// The body of glhip_softmin_fwd / glhip_sinkhorn_step: a switch on softmin_fwd_family (glhip_family.h).  `fn`: the entry point, for messages.
+template <typename T>
+int softmin_fwd_typed(const char* fn, const void* x, const void* y, const float* h, float* out, int B, int N, int M, int D, float eps, int p,
+                      const Ranges& rg, int n_ranges, const Scratch& sc, int flags, hipStream_t st, const StepArgs& step) {
+    const SoftminParams<T> prm = make_softmin_params<T>(x, y, h, out, eps, p, step.pot, step.prev, step.alpha, step.beta);
+    switch (softmin_fwd_family(B, N, M, D, p, flags, n_ranges)) {
+    case GLHIP_FAMILY_VALU:
+#define GL_D(DD) launch_softmin_valu<DD, false, T>(prm, rg, n_ranges, B, N, M, p, flags, sc, st)
+        GLHIP_D3_DISPATCH(D, GL_D)
 #undef GL_D
-                return GLHIP_OK;
-            }
+        break;
+    case GLHIP_FAMILY_X32:      // p = 2, D <= 3
+#define GL_D(DD) launch_softmin_mfma<DD, T>(prm, rg, n_ranges, B, N, M, sc, st)
+        GLHIP_D3_DISPATCH(D, GL_D)
+#undef GL_D
+        break;
+    case GLHIP_FAMILY_DIST: {   // p = 1: distances on the matrix cores
+        const DistParams<T> dp = dist_params(prm);
+        if (D <= 3) {           // block-sparse (use_mfma_dist)
+#define GL_D(DD) launch_dist<DM_SOFTMIN_P1, DD, T, SoftminFwdOp<DD, 1, true, 1, T>>(dp, prm, rg, n_ranges, N, M, sc, st)
+            GLHIP_D3_DISPATCH(D, GL_D)
+#undef GL_D
+        } else if (D > kXdMaxD) {   // dense, 17 <= D <= 4095, GLHIP_FLAG_XK_DIST: K-chunked (glhip_dist_xk.h)
+            launch_xk_dist<DM_SOFTMIN_P1, T, SoftminFwdOp<1, 1, true, 1, T>>(dp, prm, B, N, M, D, sc, st);
+        } else {                    // dense, 4 <= D <= 16 (glhip_dist_xd.h)
+#define GL_XD(DD) launch_dist_xd<DM_SOFTMIN_P1, DD, T, SoftminFwdOp<DD, 1, true, 1, T>>(dp, prm, B, N, M, sc, st)
+            GLHIP_XD_DISPATCH(D, GL_XD)
+#undef GL_XD
+        }
+        break;
+    }
+    case GLHIP_FAMILY_XD:       // p = 2 on the kernel of glhip_softmin_xd.h
+        if (D <= 3) {
             // GLHIP_FLAG_F16X2, D <= 3: 3 D + 6 <= 15 K slots = ONE v_mfma_f32_32x32x16_f16 per 1024 exponents (bf16 x 3: two), 32 bytes
             // of LDS per column (64) — the kernel of glhip_softmin_xd.h instantiated for D <= 3
             // Big dense launches only (pre-packed columns, XCD-aware grid): that is where it was measured to win — 87.1 -> 79.2 ms at
@@ -778,68 +735,71 @@ int softmin_typed(const void* x, const void* y, const float* h, float* out, cons
             // (mid-size launches, 16384 <= M < 65536, through this kernel with pre-packed columns and a free split count: 0.164 -> 0.191 ms
             // at N = M = 4e4, 0.242 -> 0.250 at 5e4, round 6: they stay on the x32 kernel)
             // GLHIP_FLAG_F32_MFMA / GLHIP_FLAG_XDL16 keep these launches on the x32 kernel too.
-            if (fam == GLHIP_FAMILY_XD) {
 #define GL_D(DD) launch_xd_l<XD_SOFTMIN, DD, T, SoftminFwdOp<DD, 2, false, 1, T>, XL_F16X2>(prm, prm, rg, n_ranges, B, N, M, sc, st)
-                GLHIP_D3_DISPATCH(D, GL_D)
+            GLHIP_D3_DISPATCH(D, GL_D)
 #undef GL_D
-                return GLHIP_OK;
-            }
+        } else {                // 4 <= D <= 16
+#define GL_XD(DD) launch_xd<XD_SOFTMIN, DD, T, SoftminFwdOp<DD, 2, false, 1, T>>(prm, prm, rg, n_ranges, B, N, M, sc, st)
+            GLHIP_XD_DISPATCH(D, GL_XD)
+#undef GL_XD
         }
-#define GL_D(DD) launch_softmin_d<DD, BWD, T>(prm, rg, n_ranges, B, N, M, p, direct, mfma, sc, st)
+        break;
+    case GLHIP_FAMILY_XK:       // p = 2, 17 <= D <= 4095: K-chunked (glhip_softmin_xk.h)
+        launch_xk<XD_SOFTMIN, T, SoftminFwdOp<1, 2, false, 1, T>>(prm, prm, rg, n_ranges, B, N, M, D, sc, st);
+        break;
+    default: {                  // GLHIP_FAMILY_GENERIC: D > 3, a plain soft-min only
+        if (step.pot || step.prev || step.alpha != 1.f)
+            return fail(GLHIP_EUNSUPPORTED, "%s: no fused kernel for D=%d, p=%d, flags=%d (D > 3: the matrix-core kernels only — "
+                                            "p = 2 up to D = 4095, dense p = 1 up to D = 16, and up to D = 4095 under GLHIP_FLAG_XK_DIST): use glhip_softmin_fwd", fn, D, p, flags);
+        const GenericParams<T> gp{prm.x, prm.y, h, out, nullptr, nullptr, nullptr, (p == 1) ? prm.s2 : 0.5f * prm.s2, prm.out_scale, 1.f, 1e-8f};
+        if (p == 2) launch_generic<GM_SOFTMIN_P2, false, T>(gp, rg, n_ranges, B, N, M, D, st);
+        else launch_generic<GM_SOFTMIN_P1, false, T>(gp, rg, n_ranges, B, N, M, D, st);
+    }
+    }
+    return GLHIP_OK;
+}
+
+// The body of glhip_softmin_bwd_x (out NULL) and glhip_softmin_fwd_grad (g NULL; `shift2`: how far, in units of LSE2, the guess `fwd` may lie
+// below the value's upper bound): a switch on `fam` = softmin_bwd_family (glhip_family.h), which the entry point has evaluated — it keeps the
+// arms of 17 <= D <= 4095 (GLHIP_FAMILY_XK, and _DIST beyond D = 16: glhip_grad_xk.h) and the refusal of mode 2 to itself.
+template <typename T>
+int softmin_bwd_typed(int fam, const void* x, const void* y, const float* h, float* out, const float* fwd, const float* g, float* gx, int B,
+                      int N, int M, int D, float eps, int p, const Ranges& rg, int n_ranges, const Scratch& sc, int flags, hipStream_t st,
+                      float shift2 = 0.f) {
+    SoftminParams<T> prm = make_softmin_params<T>(x, y, h, out, eps, p, nullptr, nullptr, 1.f, 0.f);
+    prm.fwd = fwd; prm.g = g; prm.gx = gx; prm.shift2 = shift2;
+    switch (fam) {
+    case GLHIP_FAMILY_VALU:
+#define GL_D(DD) launch_softmin_valu<DD, true, T>(prm, rg, n_ranges, B, N, M, p, flags, sc, st)
         GLHIP_D3_DISPATCH(D, GL_D)
 #undef GL_D
-    } else {
-        if constexpr (!BWD) {
-            if (fam == GLHIP_FAMILY_DIST) {   // p = 1, dense: distances on the matrix cores
-                const SoftminParams<T> mprm = make_softmin_params<T>(x, y, h, out, eps, 1, step.pot, step.prev, step.alpha, step.beta);
-                const DistParams<T> dp = dist_params(mprm);
-                if (D > kXdMaxD) {            // 17 <= D <= 4095, GLHIP_FLAG_XK_DIST: K-chunked (glhip_dist_xk.h)
-                    launch_xk_dist<DM_SOFTMIN_P1, T, SoftminFwdOp<1, 1, true, 1, T>>(dp, mprm, B, N, M, D, sc, st);
-                    return GLHIP_OK;
-                }
-#define GL_XD(DD) launch_dist_xd<DM_SOFTMIN_P1, DD, T, SoftminFwdOp<DD, 1, true, 1, T>>(dp, mprm, B, N, M, sc, st)
-                GLHIP_XD_DISPATCH(D, GL_XD)
-#undef GL_XD
-                return GLHIP_OK;
-            }
-            if (fam == GLHIP_FAMILY_XD) {   // p = 2, 4 <= D <= 16: matrix cores
-                SoftminParams<T> prm = make_softmin_params<T>(x, y, h, out, eps, 2, step.pot, step.prev, step.alpha, step.beta);
-#define GL_XD(DD) launch_xd<XD_SOFTMIN, DD, T, SoftminFwdOp<DD, 2, false, 1, T>>(prm, prm, rg, n_ranges, B, N, M, sc, st)
-                GLHIP_XD_DISPATCH(D, GL_XD)
-#undef GL_XD
-                return GLHIP_OK;
-            }
-            if (fam == GLHIP_FAMILY_XK) {   // p = 2, 17 <= D <= 4095: matrix cores, K-chunked (glhip_softmin_xk.h)
-                SoftminParams<T> prm = make_softmin_params<T>(x, y, h, out, eps, 2, step.pot, step.prev, step.alpha, step.beta);
-                launch_xk<XD_SOFTMIN, T, SoftminFwdOp<1, 2, false, 1, T>>(prm, prm, rg, n_ranges, B, N, M, D, sc, st);
-                return GLHIP_OK;
-            }
-        } else {
-            if (p == 1 && D <= kXdMaxD && n_ranges == 0 && !out && !(flags & (GLHIP_FLAG_NO_MFMA | GLHIP_FLAG_DIRECT))) {   // p = 1 gradient, dense
-                SoftminParams<T> mprm = make_softmin_params<T>(x, y, h, nullptr, eps, 1, nullptr, nullptr, 1.f, 0.f);
-                mprm.fwd = fwd; mprm.g = g; mprm.gx = gx;
-                const DistXdGradParams<T> gp{dist_params(mprm), fwd, g, gx, 1.f};
-#define GL_XD(DD) launch_dist_xd_grad<DM_SOFTMIN_P1, DD, T, SoftminBwdOp<DD, 1, true, 1, T>>(gp, mprm, B, N, M, sc, st)
-                GLHIP_XD_DISPATCH(D, GL_XD)
-#undef GL_XD
-                return GLHIP_OK;
-            }
-            if (p == 2 && D <= kXdMaxD && !(flags & (GLHIP_FLAG_NO_MFMA | GLHIP_FLAG_DIRECT))) {   // gradient (+ value), 4 <= D <= 16
-                SoftminParams<T> prm = make_softmin_params<T>(x, y, h, out, eps, 2, nullptr, nullptr, 1.f, 0.f);
-                prm.fwd = fwd; prm.g = g; prm.gx = gx; prm.shift2 = step.shift2;
-                const WsumParams<T> w = softmin_wsum_params(prm);
+        break;
+    case GLHIP_FAMILY_X32: {    // p = 2, D <= 3: the 16x16x32 kernel only (x32 = false)
+        const WsumParams<T> w = softmin_wsum_params(prm);
+#define GL_D(DD) launch_wsum<WS_SOFTMIN_BWD, DD, T, SoftminBwdOp<DD, 2, false, 1, T>>(w, prm, rg, n_ranges, B, N, M, sc, false, st)
+        GLHIP_D3_DISPATCH(D, GL_D)
+#undef GL_D
+        break;
+    }
+    case GLHIP_FAMILY_XD: {     // p = 2, gradient (+ value), 4 <= D <= 16
+        const WsumParams<T> w = softmin_wsum_params(prm);
 #define GL_XD(DD) launch_wsum_t32<WS_SOFTMIN_BWD, DD, T, SoftminBwdOp<DD, 2, false, 1, T>>(w, prm, rg, n_ranges, B, N, M, sc, st)
-                GLHIP_XD_DISPATCH(D, GL_XD)
+        GLHIP_XD_DISPATCH(D, GL_XD)
 #undef GL_XD
-                return GLHIP_OK;
-            }
-        }
-        if (step.pot || step.prev || step.alpha != 1.f)
-            return fail(GLHIP_EUNSUPPORTED, "glhip_sinkhorn_step: no fused kernel for D=%d, p=%d, flags=%d (D > 3: the matrix-core kernels only — "
-                                            "p = 2 up to D = 4095, dense p = 1 up to D = 16, and up to D = 4095 under GLHIP_FLAG_XK_DIST): use glhip_softmin_fwd", D, p, flags);
-        const GenericParams<T> prm{static_cast<const T*>(x), static_cast<const T*>(y), h, out, fwd, g, gx, (p == 1) ? s2 : 0.5f * s2, out_scale, 1.f, 1e-8f};
-        if (p == 2) launch_generic<GM_SOFTMIN_P2, BWD, T>(prm, rg, n_ranges, B, N, M, D, st);
-        else launch_generic<GM_SOFTMIN_P1, BWD, T>(prm, rg, n_ranges, B, N, M, D, st);
+        break;
+    }
+    case GLHIP_FAMILY_DIST: {   // p = 1 gradient, dense, 4 <= D <= 16
+        const DistXdGradParams<T> gp{dist_params(prm), fwd, g, gx, 1.f};
+#define GL_XD(DD) launch_dist_xd_grad<DM_SOFTMIN_P1, DD, T, SoftminBwdOp<DD, 1, true, 1, T>>(gp, prm, B, N, M, sc, st)
+        GLHIP_XD_DISPATCH(D, GL_XD)
+#undef GL_XD
+        break;
+    }
+    default: {                  // GLHIP_FAMILY_GENERIC
+        const GenericParams<T> gp{prm.x, prm.y, h, out, fwd, g, gx, (p == 1) ? prm.s2 : 0.5f * prm.s2, prm.out_scale, 1.f, 1e-8f};
+        if (p == 2) launch_generic<GM_SOFTMIN_P2, true, T>(gp, rg, n_ranges, B, N, M, D, st);
+        else launch_generic<GM_SOFTMIN_P1, true, T>(gp, rg, n_ranges, B, N, M, D, st);
+    }
     }
     return GLHIP_OK;
 }
@@ -921,13 +881,13 @@ void launch_conv_dist_kind(int fam, const ConvParams<T>& prm, const Ranges& rg, 
 }
 
 // The body of the three kernel-product entry points: MODE 0 glhip_kernel_conv_fwd (g, gx NULL), 1 glhip_kernel_conv_bwd_x (out NULL),
-// 2 glhip_kernel_conv_fwd_grad (g NULL).  A switch on conv_family; `if constexpr (MODE ...)` where a translation unit must not
-// instantiate the other modes' kernels.
+// 2 glhip_kernel_conv_fwd_grad (g NULL).  A switch on `fam` = conv_family(kind, MODE, ...) (glhip_family.h), which the entry point has
+// evaluated: modes 1 and 2 keep the arms of 17 <= D <= 4095 (GLHIP_FAMILY_XK, and _DIST beyond D = 16: glhip_grad_xk.h) to themselves.
+// `if constexpr (MODE ...)` where a translation unit must not instantiate the other modes' kernels.
 template <int MODE, typename T>
-int conv_typed(int kind, const void* x, const void* y, const float* v, float* out, const float* g, float* gx,
+int conv_typed(int fam, int kind, const void* x, const void* y, const float* v, float* out, const float* g, float* gx,
                int B, int N, int M, int D, float blur, const Ranges& rg, int n_ranges, const Scratch& sc,
                int flags, hipStream_t st) {
-    const int fam = conv_family(kind, MODE, B, D, flags, n_ranges);
     const ConvParams<T> prm = make_conv_params<T>(kind, x, y, v, out, g, gx, blur);
     if (fam == GLHIP_FAMILY_GENERIC) {
         if constexpr (MODE != 2) {      // unscaled coordinates: the scales sit on the distance, the clamp is the reference's own 1e-8

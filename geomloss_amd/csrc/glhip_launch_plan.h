@@ -1,7 +1,7 @@
 // glhip_launch_plan.h — host side of the reductions whose partial per row and column split is (sums[nv], mass, m), and of argmin, which
 // shares their split policy: ONE pass launcher, ONE pass loop, ONE sizing rule and ONE argument prologue for glhip_api_plan.hip,
 // glhip_api_plan_xk.hip, glhip_api_grad_xk.hip, glhip_api_convgrad_xk.hip, glhip_api_distgrad_xk.hip and glhip_api_argmin.hip; for the three
-// gradient routes of 17 <= D <= 4095 also ONE predicate tail, ONE workspace rule and ONE launch prologue.
+// gradient routes of 17 <= D <= 4095 also ONE workspace rule and ONE launch prologue.
 // What the launcher takes and what the sizing calls promise must agree exactly: both read plan_splits, plan_pass_workspace_bytes and the
 // resident-slot constants, which live with every other split rule in glhip_split_policy.h.
 #pragma once
@@ -13,10 +13,7 @@ namespace {
 
 constexpr int kXkPlanWidth = 32 * kXkPlanMaxChunks;       // features / coordinates per pass of xk_plan_kernel
 
-// The EINVAL prologue the predicates of the family share
-inline bool plan_family_bad_args(int B, long N, long M, int D, int dtype, int n_ranges) {
-    return B < 0 || N < 0 || M < 0 || N > 0x7fffffffL || M > 0x7fffffffL || D < 1 || n_ranges < 0 || (dtype != GLHIP_F32 && dtype != GLHIP_BF16);
-}
+// (the EINVAL prologue the predicates of the family share: plan_family_bad_args, glhip_family.h)
 
 // One dense pass: `rows` per workgroup, `partial` floats per row and split, `slots` resident workgroups.  main(grid, sp) launches the
 // reduction, merge(sp) the kernel that combines its column splits.
@@ -76,13 +73,7 @@ void launch_xk_plan_passes(const PP<T>& prm, int width, int B, int N, int M, int
 
 // ---- The gradient routes of 17 <= D <= 4095 (glhip_api_grad_xk.hip, glhip_api_convgrad_xk.hip, glhip_api_distgrad_xk.hip) ----
 
-// The tail of their predicates, after the arguments are checked: the flag that opts in, none that opts out of the matrix cores, a
-// dimension of the K-chunked kernels, a dense launch within the grid's batch limit.  Host arithmetic only.
-inline int xk_grad_route(int opt_in, int flags, int B, int D, int n_ranges) {
-    if (!(flags & opt_in) || (flags & (GLHIP_FLAG_NO_MFMA | GLHIP_FLAG_DIRECT))) return 0;
-    return (D > kXdMaxD && D <= kXkMaxD && n_ranges == 0 && B <= 65535) ? 1 : 0;
-}
-
+// Which launch takes them is an arm of softmin_bwd_family / conv_family (glhip_family.h: xk_grad_route), which their exported predicates read.
 // Their sizing rule: the widest pass carries min(D, pass_width) coordinates; `uses`: what the route's predicate answers for float32 clouds
 inline size_t xk_grad_workspace_bytes(int uses, int B, int N, int M, int D, int flags, int pass_width) {
     if (B <= 0 || N <= 0 || M <= 0 || (flags & GLHIP_FLAG_NO_SPLIT) || uses != 1) return 0;

@@ -179,7 +179,10 @@ extern "C" {
 #define GLHIP_EUNSUPPORTED (-2) /* valid request this build has no kernel for */
 #define GLHIP_ELAUNCH (-3)      /* hipGetLastError() after the launch was not hipSuccess */
 
-/* kernel families of the soft-min forward / fused half-step (glhip_softmin_fwd_family) and of the kernel products (glhip_kernel_conv_fwd_family) */
+/* kernel families of the soft-min forward / fused half-step (glhip_softmin_fwd_family) and of the kernel products (glhip_kernel_conv_fwd_family).
+ * The same codes name the gradient routes inside the library (csrc/glhip_family.h: there _X32 / _XD / _XK are the weighted-sum and plan kernels
+ * of the same dimensions, _DIST the distance-gradient kernels); the gradient predicates below (glhip_softmin_bwd_x_uses_plan,
+ * glhip_kernel_conv_grad_uses_xk, glhip_dist_grad_uses_xk) report the routes of 17 <= D <= 4095 as 1 / 0. */
 #define GLHIP_FAMILY_VALU 0    /* D <= 3 on the VALU map-reduce skeleton (glhip_mapreduce.h): p = 1, GLHIP_FLAG_DIRECT / _NO_MFMA */
 #define GLHIP_FAMILY_X32 1     /* p = 2, D <= 3: matrix cores, glhip_softmin_x32.h */
 #define GLHIP_FAMILY_XD 2      /* p = 2, 4 <= D <= 16 (and big dense GLHIP_FLAG_F16X2 launches of D <= 3): matrix cores, glhip_softmin_xd.h */
