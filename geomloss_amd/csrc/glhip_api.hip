@@ -1,5 +1,5 @@
 // glhip_api.hip — C-ABI of libgeomloss_hip.so (include/glhip.h), part 1: version / errors / scratch size and the soft-min FORWARD family
-// (glhip_softmin_fwd, glhip_sinkhorn_step, glhip_sinkhorn_iter4, glhip_sinkhorn_anneal, glhip_sinkhorn_extrapolate4).  gfx950 only.
+// (glhip_softmin_fwd, glhip_sinkhorn_step, glhip_sinkhorn_step_perm, glhip_sinkhorn_iter4, glhip_sinkhorn_anneal, glhip_sinkhorn_extrapolate4).  gfx950 only.
 #include "glhip_autosort.h"
 #include "glhip_launch.h"
 
@@ -66,11 +66,20 @@ int glhip_softmin_fwd_family(int B, long N, long M, int D, int p, int dtype, int
     return softmin_fwd_family(B, N, M, D, p, flags, n_ranges);
 }
 
-// The body of glhip_sinkhorn_step and of glhip_softmin_fwd, which is the step with pot = prev = NULL and damping = 1.  `fn`: the entry point
-// the caller used, for messages.
+int glhip_softmin_perm_applies(int B, long N, long M, int D, int p, int dtype, int flags, int n_ranges) {
+    if (B < 0 || N < 0 || M < 0 || N > 0x7fffffffL || M > 0x7fffffffL || D < 1 || n_ranges < 0 || (p != 1 && p != 2) ||
+        (dtype != GLHIP_F32 && dtype != GLHIP_BF16))
+        return GLHIP_EINVAL;
+    return p == 2 && softmin_sorts(B, (int)N, (int)M, D, p, n_ranges, flags) ? 1 : 0;
+}
+
+// The body of glhip_sinkhorn_step_perm, of glhip_sinkhorn_step (no permutation buffers) and of glhip_softmin_fwd, which is the step with
+// pot = prev = NULL and damping = 1.  `fn`: the entry point the caller used, for messages.  perm_x / perm_y / perm_flags: the reused
+// permutations of the sorted p = 2 call (autosort_prepare), ignored by every other call.
 static int softmin_step(const char* fn, const void* x, const void* y, const float* logw, const float* pot, const float* prev, float* out, int B,
                         int N, int M, int D, float eps, float damping, int p, int in_dtype, const int32_t* ranges_i, const int32_t* slices_i,
-                        const int32_t* redranges_j, int n_ranges, void* workspace, size_t workspace_bytes, int flags, void* stream) {
+                        const int32_t* redranges_j, int n_ranges, void* workspace, size_t workspace_bytes, int flags, void* stream,
+                        int32_t* perm_x = nullptr, int32_t* perm_y = nullptr, int perm_flags = 0) {
     int rc = check_common(fn, x, y, logw, B, N, M, D, in_dtype, ranges_i, slices_i, redranges_j, n_ranges);
     if (rc) return rc;
     if (B == 0 || N == 0) return GLHIP_OK;   // nothing to write
@@ -83,19 +92,20 @@ static int softmin_step(const char* fn, const void* x, const void* y, const floa
     if (softmin_sorts(B, N, M, D, p, n_ranges, flags)) {
         AutoSort a;
         const int C = (N + kSortSlab - 1) / kSortSlab;
-        rc = autosort_prepare(a, x, y, N, M, D, in_dtype, workspace, workspace_bytes, glhip_workspace_bytes(1, N, M, D, C), st, p == 1);
+        rc = autosort_prepare(a, x, y, N, M, D, in_dtype, workspace, workspace_bytes, glhip_workspace_bytes(1, N, M, D, C), st, p == 1, perm_x,
+                              perm_y, perm_flags);
         if (rc) return rc;
         if (a.on) {      // the potentials travel with their clouds
-            gather_f32(logw, a.perm_y, a.col0, M, st);
-            if (pot) { gather_f32(pot, a.perm_y, a.col1, M, st); step.pot = a.col1; }
-            if (prev) { gather_f32(prev, a.perm_x, a.row0, N, st); step.prev = a.row0; }
+            gather_f32(logw, a.perm_y, a.col0, M, st, a.hint_y);
+            if (pot) { gather_f32(pot, a.perm_y, a.col1, M, st, a.hint_y); step.pot = a.col1; }
+            if (prev) { gather_f32(prev, a.perm_x, a.row0, N, st, a.hint_x); step.prev = a.row0; }
             // (the bound takes the column vector the kernels form: logw + pot / eps)
             if (p == 2)
                 prune_ranges(a.xs, a.ys, a.col0, step.pot, 1.0f / eps, N, M, D, in_dtype, eps, a.ranges_i, a.slices_i, a.red, a.blocks, a.groups, a.home,
                              a.t2, a.mlb, a.t1, st);
             rc = sorted_inner(fn, a, x, a.col0, N, M, D, eps, p, in_dtype, flags, st, step);
             if (rc) return rc;
-            scatter_f32(a.out, a.perm_x, out, N, st);
+            scatter_f32(a.out, a.perm_x, out, N, st, 1, a.hint_x);
             return check_launch(fn);
         }
     }
@@ -120,6 +130,15 @@ int glhip_sinkhorn_step(const void* x, const void* y, const float* logw, const f
                         void* workspace, size_t workspace_bytes, int flags, void* stream) {
     return softmin_step("glhip_sinkhorn_step", x, y, logw, pot, prev, out, B, N, M, D, eps, damping, p, in_dtype, ranges_i, slices_i, redranges_j,
                         n_ranges, workspace, workspace_bytes, flags, stream);
+}
+
+int glhip_sinkhorn_step_perm(const void* x, const void* y, const float* logw, const float* pot, const float* prev,
+                             float* out, int B, int N, int M, int D, float eps, float damping, int p, int in_dtype,
+                             const int32_t* ranges_i, const int32_t* slices_i, const int32_t* redranges_j, int n_ranges,
+                             void* workspace, size_t workspace_bytes, int flags, void* stream, int32_t* perm_x, int32_t* perm_y,
+                             int perm_flags) {
+    return softmin_step("glhip_sinkhorn_step_perm", x, y, logw, pot, prev, out, B, N, M, D, eps, damping, p, in_dtype, ranges_i, slices_i,
+                        redranges_j, n_ranges, workspace, workspace_bytes, flags, stream, perm_x, perm_y, perm_flags);
 }
 
 int glhip_prune_inspect_slots(int M) { return M > 0 ? prune_plan(M).S : GLHIP_EINVAL; }

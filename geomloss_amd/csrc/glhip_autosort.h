@@ -128,11 +128,13 @@ inline size_t as_align256(size_t b) { return (b + 255) & ~(size_t)255; }
 // implemented in glhip_cluster.hip (rocPRIM lives there)
 size_t compact_sort_scratch_bytes(int n);
 // sub > 1: inside a voxel, points are ordered by sub-voxel of edge voxel / sub (the minor key of path_keys_kernel), then every whole
-// block of kBalanceBlock positions is split into balanced cells (balance_kernel)
+// block of kBalanceBlock positions is split into balanced cells (balance_kernel).  hinted: `perm` already holds the order, from an
+// earlier call on the same cloud (glhip_sinkhorn_step_perm) — nothing but the gather runs, with every index clamped into [0, n)
+// (glhip_perm_index.h); the same flag on gather_f32 / scatter_f32 clamps theirs.
 int compact_sort(const void* z, int n, int D, int in_dtype, int rows_per_voxel, int32_t* perm, void* z_sorted, void* scratch,
-                 size_t scratch_bytes, hipStream_t st, int sub = 1);
-void gather_f32(const float* src, const int32_t* perm, float* dst, int n, hipStream_t st);       // dst[k] = src[perm[k]]
-void scatter_f32(const float* src, const int32_t* perm, float* dst, int n, hipStream_t st, int width = 1);      // dst[perm[k], :] = src[k, :]
+                 size_t scratch_bytes, hipStream_t st, int sub = 1, bool hinted = false);
+void gather_f32(const float* src, const int32_t* perm, float* dst, int n, hipStream_t st, bool hinted = false);       // dst[k] = src[perm[k]]
+void scatter_f32(const float* src, const int32_t* perm, float* dst, int n, hipStream_t st, int width = 1, bool hinted = false);      // dst[perm[k], :] = src[k, :]
 void slab_ranges(int N, int M, int32_t* ranges_i, int32_t* slices_i, int32_t* red, hipStream_t st);
 size_t prune_blocks_bytes(int M);
 size_t prune_groups_bytes(int M);
@@ -156,6 +158,7 @@ struct AutoSort {
     bool on = false;
     int C = 0;                              // slabs
     int32_t *perm_x = nullptr, *perm_y = nullptr, *ranges_i = nullptr, *slices_i = nullptr, *red = nullptr;
+    bool hint_x = false, hint_y = false;    // perm_x / perm_y is the caller's hint: whatever indexes through it clamps (glhip_perm_index.h)
     void *xs = nullptr, *ys = nullptr;
     float *col0 = nullptr, *col1 = nullptr, *row0 = nullptr, *out = nullptr;      // gathered per-column / per-row vectors, sorted output
     float* out_rows = nullptr;              // (N, D) sorted output (row gradients)
@@ -183,8 +186,16 @@ inline size_t autosort_bytes(int N, int M, int D) {
 // Sorts both clouds into the workspace; `a.on` stays false when the workspace is too small for the sorted call plus `inner_min`
 // bytes of scratch for the launch itself (the caller then runs the generic kernel).  slabs = false: the caller fills the ranges
 // itself (prune_ranges) once its column vector is gathered.
+// Reused permutations (library 134; the pruned p = 2 call only, slabs = false).  Bounding box, voxel edge, path keys, the 64-bit sort
+// and the balanced cells of a cloud depend on its coordinates alone, and a Sinkhorn loop calls a few hundred times on the same two
+// clouds.  ext_x / ext_y: a caller's buffer of N / M ints that takes the place of the workspace's perm_x / perm_y, without a copy —
+// with its bit of `perm_flags` (1: x, 2: y; GLHIP_PERM_HINT_*) it HOLDS the order and only the gather runs for that cloud, without it
+// the sort and balance_kernel write the order straight into it.  A hint is safe because the pruning is exact for any order (above):
+// every box of both levels is recomputed from the gathered coordinates on every call, so a stale hint costs kept pairs, never accuracy.
+// Only permutations are reused for that reason, never sorted coordinates or box records.  The workspace layout stays what it was.
 inline int autosort_prepare(AutoSort& a, const void* x, const void* y, int N, int M, int D, int in_dtype, void* workspace,
-                            size_t workspace_bytes, size_t inner_min, hipStream_t st, bool slabs = true) {
+                            size_t workspace_bytes, size_t inner_min, hipStream_t st, bool slabs = true, int32_t* ext_x = nullptr,
+                            int32_t* ext_y = nullptr, int perm_flags = 0) {
     const size_t need = autosort_bytes(N, M, D);
     if (!workspace || workspace_bytes < need + inner_min) return 0;
     char* w = static_cast<char*>(workspace);
@@ -210,11 +221,13 @@ inline int autosort_prepare(AutoSort& a, const void* x, const void* y, int N, in
     const int L = N > M ? N : M;
     const size_t sb = compact_sort_scratch_bytes(L);
     void* scratch = take(sb);
+    if (!slabs && ext_x) { a.perm_x = ext_x; a.hint_x = (perm_flags & 1) != 0; }
+    if (!slabs && ext_y) { a.perm_y = ext_y; a.hint_y = (perm_flags & 2) != 0; }
     // (slabs = false is the pruned p = 2 call: both clouds in voxels of kSortRowsPerVoxel points, compact sub-voxels inside)
-    int rc = compact_sort(x, N, D, in_dtype, kSortRowsPerVoxel, a.perm_x, a.xs, scratch, sb, st, slabs ? 1 : prune_sort_sub(D));
+    int rc = compact_sort(x, N, D, in_dtype, kSortRowsPerVoxel, a.perm_x, a.xs, scratch, sb, st, slabs ? 1 : prune_sort_sub(D), a.hint_x);
     if (rc) return rc;
     rc = compact_sort(y, M, D, in_dtype, slabs ? 2 * kSortRowsPerVoxel : kSortRowsPerVoxel, a.perm_y, a.ys, scratch, sb, st,
-                      slabs ? 1 : prune_sort_sub(D));
+                      slabs ? 1 : prune_sort_sub(D), a.hint_y);
     if (rc) return rc;
     if (slabs) slab_ranges(N, M, a.ranges_i, a.slices_i, a.red, st);
     // (the scratch holds 20 bytes per point of the larger cloud and more: N / 8 + 16 C bytes fit many times over)

@@ -16,6 +16,7 @@
 #include <cstdint>
 
 #include "glhip_autosort.h"
+#include "glhip_perm_index.h"
 #include "glhip_balance.h"
 #include "glhip_common.h"
 #include "glhip_error.h"
@@ -452,22 +453,26 @@ __global__ void __launch_bounds__(kBalanceBlock) balance_kernel(const T* __restr
     perm[base + tid] = src[p];
 }
 
-template <typename T>
+// kHinted: `perm` came from outside the call (a hinted permutation, glhip_perm_index.h): every entry is clamped into [0, n).  Without
+// it the three kernels are what they were.
+template <typename T, bool kHinted>
 __global__ void __launch_bounds__(256) gather_points_kernel(const T* __restrict__ x, const int32_t* __restrict__ perm, int n, int D, T* __restrict__ xs) {
     const long p = (long)blockIdx.x * 256 + threadIdx.x;
     if (p >= n) return;
-    const long j = perm[p];
+    const long j = kHinted ? perm_index(perm[p], n) : perm[p];
     for (int d = 0; d < D; ++d) xs[p * D + d] = x[j * D + d];
 }
 
+template <bool kHinted>
 __global__ void __launch_bounds__(256) gather_f32_kernel(const float* __restrict__ src, const int32_t* __restrict__ perm, float* __restrict__ dst, int n) {
     const long k = (long)blockIdx.x * 256 + threadIdx.x;
-    if (k < n) dst[k] = src[perm[k]];
+    if (k < n) dst[k] = src[kHinted ? perm_index(perm[k], n) : perm[k]];
 }
+template <bool kHinted>
 __global__ void __launch_bounds__(256) scatter_f32_kernel(const float* __restrict__ src, const int32_t* __restrict__ perm, float* __restrict__ dst, int n, int width) {
     const long k = (long)blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
-    const long j = perm[k];
+    const long j = kHinted ? perm_index(perm[k], n) : perm[k];
     for (int d = 0; d < width; ++d) dst[j * width + d] = src[k * width + d];
 }
 
@@ -1021,8 +1026,13 @@ size_t sort64_temp_bytes(int n) {
 
 template <typename T>
 int compact_sort_typed(const void* z_, int n, int D, int rows_per_voxel, int sub, int32_t* perm, void* z_sorted, void* scratch,
-                       size_t scratch_bytes, hipStream_t st) {
+                       size_t scratch_bytes, hipStream_t st, bool hinted) {
     const T* z = static_cast<const T*>(z_);
+    const int blocks = (n + 255) / 256;
+    if (hinted) {      // `perm` holds the order already (glhip_perm_index.h): no box, no keys, no sort, no balancing — the gather alone
+        hipLaunchKernelGGL((gather_points_kernel<T, true>), dim3(blocks), dim3(256), 0, st, z, perm, n, D, static_cast<T*>(z_sorted));
+        return GLHIP_OK;
+    }
     char* ws = static_cast<char*>(scratch);
     SortHead* head = reinterpret_cast<SortHead*>(ws);
     size_t off = align256(sizeof(SortHead));
@@ -1031,7 +1041,6 @@ int compact_sort_typed(const void* z_, int n, int D, int rows_per_voxel, int sub
     int32_t* idx_in = reinterpret_cast<int32_t*>(ws + off); off += align256((size_t)n * 4);
     size_t temp = sort64_temp_bytes(n);
     if (off + temp > scratch_bytes) return fail(GLHIP_EINVAL, "compact_sort: scratch of %zu bytes, need %zu", scratch_bytes, off + temp);
-    const int blocks = (n + 255) / 256;
     hipLaunchKernelGGL(sort_head_init_kernel, dim3(1), dim3(64), 0, st, head);
     hipLaunchKernelGGL((bbox_kernel<T>), dim3(blocks < 512 ? blocks : 512), dim3(256), 0, st, z, n, D, head);
     hipLaunchKernelGGL(voxel_kernel, dim3(1), dim3(64), 0, st, head, n, D, rows_per_voxel);
@@ -1041,7 +1050,7 @@ int compact_sort_typed(const void* z_, int n, int D, int rows_per_voxel, int sub
     // the sorted p = 2 call: balanced cells inside every whole block of kBalanceBlock positions; the partial last block keeps the path order
     if (sub > 1 && n >= kBalanceBlock)
         hipLaunchKernelGGL((balance_kernel<T>), dim3(n / kBalanceBlock), dim3(kBalanceBlock), 0, st, z, D, perm);
-    hipLaunchKernelGGL((gather_points_kernel<T>), dim3(blocks), dim3(256), 0, st, z, perm, n, D, static_cast<T*>(z_sorted));
+    hipLaunchKernelGGL((gather_points_kernel<T, false>), dim3(blocks), dim3(256), 0, st, z, perm, n, D, static_cast<T*>(z_sorted));
     return GLHIP_OK;
 }
 
@@ -1054,17 +1063,19 @@ size_t compact_sort_scratch_bytes(int n) {
 }
 
 int compact_sort(const void* z, int n, int D, int in_dtype, int rows_per_voxel, int32_t* perm, void* z_sorted, void* scratch,
-                 size_t scratch_bytes, hipStream_t st, int sub) {
-    return in_dtype == GLHIP_F32 ? compact_sort_typed<float>(z, n, D, rows_per_voxel, sub, perm, z_sorted, scratch, scratch_bytes, st)
-                                 : compact_sort_typed<bf16_t>(z, n, D, rows_per_voxel, sub, perm, z_sorted, scratch, scratch_bytes, st);
+                 size_t scratch_bytes, hipStream_t st, int sub, bool hinted) {
+    return in_dtype == GLHIP_F32 ? compact_sort_typed<float>(z, n, D, rows_per_voxel, sub, perm, z_sorted, scratch, scratch_bytes, st, hinted)
+                                 : compact_sort_typed<bf16_t>(z, n, D, rows_per_voxel, sub, perm, z_sorted, scratch, scratch_bytes, st, hinted);
 }
 
-void gather_f32(const float* src, const int32_t* perm, float* dst, int n, hipStream_t st) {
-    hipLaunchKernelGGL(gather_f32_kernel, dim3((n + 255) / 256), dim3(256), 0, st, src, perm, dst, n);
+void gather_f32(const float* src, const int32_t* perm, float* dst, int n, hipStream_t st, bool hinted) {
+    if (hinted) hipLaunchKernelGGL(gather_f32_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, st, src, perm, dst, n);
+    else hipLaunchKernelGGL(gather_f32_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, st, src, perm, dst, n);
 }
 
-void scatter_f32(const float* src, const int32_t* perm, float* dst, int n, hipStream_t st, int width) {
-    hipLaunchKernelGGL(scatter_f32_kernel, dim3((n + 255) / 256), dim3(256), 0, st, src, perm, dst, n, width);
+void scatter_f32(const float* src, const int32_t* perm, float* dst, int n, hipStream_t st, int width, bool hinted) {
+    if (hinted) hipLaunchKernelGGL(scatter_f32_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, st, src, perm, dst, n, width);
+    else hipLaunchKernelGGL(scatter_f32_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, st, src, perm, dst, n, width);
 }
 
 void slab_ranges(int N, int M, int32_t* ranges_i, int32_t* slices_i, int32_t* red, hipStream_t st) {

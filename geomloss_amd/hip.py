@@ -59,6 +59,9 @@ SIGNATURES = {
                           + _RANGES + _TAIL),
     "glhip_sinkhorn_step": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_float,
                                      _c_int, _c_int] + _RANGES + _TAIL),
+    "glhip_sinkhorn_step_perm": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_float,
+                                          _c_int, _c_int] + _RANGES + _TAIL + [_vp, _vp, _c_int]),
+    "glhip_softmin_perm_applies": (_c_int, [_c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int, _c_int]),
     "glhip_sinkhorn_iter4": (_c_int, [_vp] * 12 + [_c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _c_int, _c_int, _c_int]
                              + _TAIL),
     "glhip_sinkhorn_anneal": (_c_int, [_vp] * 6 + [_c_int] * 4 + [_vp, _vp, _c_int, _c_int, _c_int, _vp, _c_size, _c_int, _c_float, _vp]),
@@ -114,6 +117,10 @@ SIGNATURES.update({
     "glhip_kernel_conv_bwd_x_f64": (_c_int, [_c_int] + [_vp] * 5 + [_c_int, _c_int, _c_int, _c_int, _c_double] + _RANGES + [_vp]),
 })
 KEEP_DUAL_SLACK, KEEP_WITHIN = 0, 1
+PERM_HINT_X, PERM_HINT_Y = 1, 2     # perm_flags of glhip_sinkhorn_step_perm (GLHIP_PERM_HINT_*)
+# symbols younger than the oldest C-ABI that GEOMLOSS_HIP_LIB may name for an A/B run: an older build is bound without them, and the
+# calls that would use them take the entry points that build has (no permutation is reused with it)
+_SINCE = {"glhip_sinkhorn_step_perm": 134, "glhip_softmin_perm_applies": 134}
 
 _lib = None
 
@@ -131,7 +138,11 @@ def load_library(path=None):
             "The 'online' and 'multiscale' backends have no CPU or PyTorch fallback."
         )
     lib = ctypes.CDLL(path)
+    lib.glhip_version.restype = _c_int
+    version = int(lib.glhip_version())
     for name, (restype, argtypes) in SIGNATURES.items():
+        if version < _SINCE.get(name, 0) and path != LIB_PATH:
+            continue
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -258,11 +269,176 @@ def _as_batched(x, y, s):
 
 
 # ----------------------------------------------------------------------------------------------
+#  reused permutations of the sorted p = 2 call
+# ----------------------------------------------------------------------------------------------
+
+PERM_CACHE_ENTRIES = 8
+
+
+def perm_cache_key(t, stream_id):
+    """The key under which the sorted order of the cloud ``t`` ((N,D) or (1,N,D)) is kept: the identity of its storage, its data pointer,
+    the shape and strides of its last two axes, dtype, device, the launch stream and the tensor's version counter.  Pure Python on
+    tensor metadata (CPU tensors have keys too).  ``.detach()`` and views share storage and counter, so ``x``, ``x.detach()`` and
+    ``x[None]`` have one key; an in-place torch write bumps the counter.  None: a tensor without a counter (inference mode)."""
+    try:
+        version = t._version
+    except RuntimeError:
+        return None
+    return (t.untyped_storage()._cdata, t.data_ptr(), tuple(t.shape[-2:]), tuple(t.stride()[-2:]), t.dtype, str(t.device),
+            int(stream_id), int(version))
+
+
+class _PermCache:
+    """Per-CLOUD cache of the int32 permutations that ``glhip_sinkhorn_step_perm`` exports and takes back as hints.
+
+    The sorted p = 2 call (``softmin_perm_applies``: one dense problem of D <= 3 and N M >= 1e11) orders each cloud by its coordinates
+    alone — bounding box, voxel path keys, a 64-bit radix sort, balanced cells — before anything that depends on the dual vector or the
+    temperature.  A Sinkhorn loss calls 4 x (n_eps + 2) times on the same two clouds, and a cloud has the same order as rows and as
+    columns, so ``(x, y)``, ``(y, x)``, ``(x, x)`` and ``(y, y)`` share two entries: two sorts per loss.  Everything that depends on
+    ``h`` or ``eps`` — the gathers of the vectors, the three pruning kernels, the reduction — runs on every call.
+
+    An entry is used only if every part of :func:`perm_cache_key` matches and the storage is alive (a weak reference to the storage,
+    not to the Python tensor: the drivers pass fresh ``.detach()`` / ``[None]`` views on every call).  Entries of dead storages are
+    dropped at every lookup, which frees their permutations; a fresh tensor on a freed address is another storage and misses; another
+    stream misses (the permutation was produced elsewhere); at most ``PERM_CACHE_ENTRIES`` entries, least recently used out.
+    While the current stream is capturing a graph the cache is neither read nor filled: a replay must not depend on a buffer that the
+    cache may free.
+
+    What the key does NOT see: writes that bypass the version counter — through ``.data``, a raw pointer, another library.  The entry
+    is then stale, and the result is STILL RIGHT: the pruning is exact for any order (csrc/glhip_autosort.h), every box it uses is
+    recomputed from the gathered coordinates on every call, and a stale order only keeps more pairs, that is, costs time.
+    :func:`forget_permutations` clears the cache; ``GEOMLOSS_HIP_PERM_CACHE=0`` turns it off."""
+
+    def __init__(self):
+        import collections
+        import threading
+        self.lock = threading.Lock()
+        self.entries = collections.OrderedDict()      # key -> (StorageWeakRef, permutation)
+        self.hits = self.misses = 0
+
+    def lookup(self, key):
+        """The permutation kept for ``key`` (counted as a hit), or None (a miss); drops the entries of dead storages."""
+        with self.lock:
+            for k in [k for k, (ref, _) in self.entries.items() if ref.expired()]:
+                del self.entries[k]
+            hit = self.entries.get(key)
+            if hit is None:
+                self.misses += 1
+                return None
+            self.entries.move_to_end(key)
+            self.hits += 1
+            return hit[1]
+
+    def store(self, key, t, perm):
+        from torch.multiprocessing.reductions import StorageWeakRef
+        with self.lock:
+            self.entries[key] = (StorageWeakRef(t.untyped_storage()), perm)
+            self.entries.move_to_end(key)
+            while len(self.entries) > PERM_CACHE_ENTRIES:
+                self.entries.popitem(last=False)
+
+    def clear(self):
+        with self.lock:
+            self.entries.clear()
+
+
+_perm_cache = _PermCache()
+
+
+def perm_cache_enabled():
+    return os.environ.get("GEOMLOSS_HIP_PERM_CACHE", "1") != "0"
+
+
+def forget_permutations():
+    """Drops every cached permutation (see :class:`_PermCache`); the hit / miss counters stay."""
+    _perm_cache.clear()
+
+
+def perm_cache_stats():
+    """(hits, misses, live entries) of the permutation cache."""
+    return _perm_cache.hits, _perm_cache.misses, len(_perm_cache.entries)
+
+
+def softmin_perm_applies(B, N, M, D, p=2, dtype=F32, flags=0, n_ranges=0):
+    """Whether ``glhip_softmin_fwd`` / ``glhip_sinkhorn_step`` of this shape is the sorted p = 2 call, the one whose permutations can be
+    reused: the library's own predicate (``glhip_softmin_perm_applies``), host arithmetic only.  1 / 0, or ``ValueError``."""
+    return _route_predicate("glhip_softmin_perm_applies", (B, N, M, D, p, dtype, flags, n_ranges),
+                            f"B {B}, N {N}, M {M}, D {D}, p {p}, dtype {dtype}, n_ranges {n_ranges}")
+
+
+def stable_clouds(x, y, p=2):
+    """For the drivers, before a loop of soft-min calls on the clouds x (N,D), y (M,D): where those calls are the sorted p = 2 call and
+    a cloud would be converted or copied by EVERY call (``_points``: a dtype the kernels do not read, a non-contiguous layout), the
+    conversion is made once here — differentiably, so gradients reach the caller's tensor — and the calls of the loop see one storage
+    and reuse its permutation.  Everything else comes back as it is (mixed dtypes too: each call converts the columns to its rows')."""
+    if not (p == 2 and x.is_cuda and x.dim() == 2 and y.dim() == 2 and perm_cache_enabled()):
+        return x, y
+    lib = load_library()
+    N, M, D = x.shape[0], y.shape[0], x.shape[1]
+    if not hasattr(lib, "glhip_softmin_perm_applies") or (lib.glhip_softmin_perm_applies(1, N, M, D, 2, F32, 0, 0) != 1
+                                                           and lib.glhip_softmin_perm_applies(1, M, N, D, 2, F32, 0, 0) != 1):
+        return x, y
+
+    def once(t):
+        if t.dtype not in (torch.float32, torch.bfloat16, torch.float64):
+            t = t.float()
+        return t if t.is_contiguous() else t.contiguous()
+
+    return once(x), once(y)
+
+
+def _perm_plan(lib, x, y, p, ranges, flags):
+    """The permutation arguments of one ``glhip_sinkhorn_step_perm`` call on the clouds x (1,N,D), y (1,M,D), or None where the call
+    takes none (not the sorted p = 2 call, cache off, a capturing stream, a library without the entry point).  Returns
+    ``([perm_x, perm_y, perm_flags], commit)``; ``commit()`` keeps the exported permutations once the call has been queued."""
+    if not perm_cache_enabled() or not hasattr(lib, "glhip_softmin_perm_applies"):
+        return None
+    B, N, D = x.shape
+    M = y.shape[1]
+    n_ranges = 0 if ranges is None else int(ranges.ranges_i.shape[0])
+    if lib.glhip_softmin_perm_applies(B, N, M, D, int(p), _dtype_code(x), _range_flags(flags, ranges), n_ranges) != 1:
+        return None
+    if torch.cuda.is_current_stream_capturing():
+        return None
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    kx, ky = perm_cache_key(x, stream), perm_cache_key(y, stream)
+    if kx is None or ky is None:
+        return None
+    px = _perm_cache.lookup(kx)
+    fresh = []
+    bits = 0
+    if px is None:
+        px = torch.empty(N, dtype=torch.int32, device=x.device)
+        fresh.append((kx, x, px))
+    else:
+        bits |= PERM_HINT_X
+    if ky == kx:      # one cloud on both sides: the x side is prepared first, the y side reads what it wrote
+        py = px
+        with _perm_cache.lock:
+            _perm_cache.hits += 1
+        bits |= PERM_HINT_Y
+    else:
+        py = _perm_cache.lookup(ky)
+        if py is None:
+            py = torch.empty(M, dtype=torch.int32, device=x.device)
+            fresh.append((ky, y, py))
+        else:
+            bits |= PERM_HINT_Y
+
+    def commit():
+        for k, t, perm in fresh:
+            _perm_cache.store(k, t, perm)
+
+    return [ctypes.c_void_p(px.data_ptr()), ctypes.c_void_p(py.data_ptr()), bits], commit
+
+
+# ----------------------------------------------------------------------------------------------
 #  raw launches
 # ----------------------------------------------------------------------------------------------
 
 def softmin_fwd_raw(x, y, h, eps, p=2, ranges=None, flags=0):
-    """x (B,N,D), y (B,M,D) fp32|bf16 contiguous CUDA; h (B,M) fp32 -> (B,N) fp32."""
+    """x (B,N,D), y (B,M,D) fp32|bf16 contiguous CUDA; h (B,M) fp32 -> (B,N) fp32.  The sorted p = 2 call reuses the permutations of
+    its clouds from call to call (:class:`_PermCache`)."""
     lib = load_library()
     B, N, D = x.shape
     M = y.shape[1]
@@ -276,10 +452,18 @@ def softmin_fwd_raw(x, y, h, eps, p=2, ranges=None, flags=0):
     out = torch.empty((B, N), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
         ws, ws_args = _workspace(lib, x, B, N, M, D, ranges)
-        rc = lib.glhip_softmin_fwd(x.data_ptr(), y.data_ptr(), h.data_ptr(), out.data_ptr(), B, N, M, D,
-                                   float(eps), int(p), _dtype_code(x), *_range_args(ranges, B), *ws_args,
-                                   _range_flags(flags, ranges), _stream(x))
+        perm = _perm_plan(lib, x, y, p, ranges, flags)
+        if perm is None:
+            rc = lib.glhip_softmin_fwd(x.data_ptr(), y.data_ptr(), h.data_ptr(), out.data_ptr(), B, N, M, D,
+                                       float(eps), int(p), _dtype_code(x), *_range_args(ranges, B), *ws_args,
+                                       _range_flags(flags, ranges), _stream(x))
+        else:      # (glhip_softmin_fwd is the step with pot = prev = NULL and damping = 1: one body in the library)
+            rc = lib.glhip_sinkhorn_step_perm(x.data_ptr(), y.data_ptr(), h.data_ptr(), None, None, out.data_ptr(), B, N, M, D,
+                                              float(eps), 1.0, int(p), _dtype_code(x), *_range_args(ranges, B), *ws_args,
+                                              _range_flags(flags, ranges), _stream(x), *perm[0])
     _check(rc, lib)
+    if perm is not None:
+        perm[1]()
     return out
 
 
@@ -299,11 +483,15 @@ def sinkhorn_step_raw(x, y, logw, pot, prev, eps, damping, p=2, ranges=None, fla
     out = torch.empty((B, N), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
         ws, ws_args = _workspace(lib, x, B, N, M, D, ranges)
-        rc = lib.glhip_sinkhorn_step(x.data_ptr(), y.data_ptr(), logw.data_ptr(),
-                                     None if pot is None else pot.data_ptr(), None if prev is None else prev.data_ptr(),
-                                     out.data_ptr(), B, N, M, D, float(eps), float(damping), int(p), _dtype_code(x),
-                                     *_range_args(ranges, B), *ws_args, _range_flags(flags, ranges), _stream(x))
+        perm = _perm_plan(lib, x, y, p, ranges, flags)
+        step = lib.glhip_sinkhorn_step if perm is None else lib.glhip_sinkhorn_step_perm
+        rc = step(x.data_ptr(), y.data_ptr(), logw.data_ptr(),
+                  None if pot is None else pot.data_ptr(), None if prev is None else prev.data_ptr(),
+                  out.data_ptr(), B, N, M, D, float(eps), float(damping), int(p), _dtype_code(x),
+                  *_range_args(ranges, B), *ws_args, _range_flags(flags, ranges), _stream(x), *([] if perm is None else perm[0]))
     _check(rc, lib)
+    if perm is not None:
+        perm[1]()
     return out
 
 

@@ -313,6 +313,7 @@ def sinkhorn_online(
         p = _exponent_of(cost)
     if B == 1:  # like the reference, the single-problem path works on (N,D) clouds
         x, y = x.squeeze(0), y.squeeze(0)
+        x, y = hip.stable_clouds(x, y, p)      # big p = 2 problems: one storage per cloud for the whole loop (hip._PermCache)
     softmin = _HipSoftmin(p, multiscale=False)
 
     C_xx, C_yy = ((x, x.detach()), (y, y.detach())) if debias else (None, None)

@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 133 /* 0.1.33 */
+#define GLHIP_VERSION 134 /* 0.1.34 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
@@ -290,6 +290,41 @@ int glhip_sinkhorn_step(const void* x, const void* y, const float* logw, const f
                         const int32_t* ranges_i, const int32_t* slices_i,
                         const int32_t* redranges_j, int n_ranges,
                         void* workspace, size_t workspace_bytes, int flags, void* stream);
+
+/*
+ * glhip_sinkhorn_step with the permutations of the sorted p = 2 call handed in and out (version 134).  The big dense p = 2 call (see
+ * GLHIP_FLAG_NO_SORT) orders both clouds before it prunes: bounding box, voxel edge, path keys, a 64-bit radix sort and the balanced
+ * cells, all of them functions of a cloud's coordinates alone — 0.65 of 16.7 ms at N = M = 1e6, a fifth of the call at eps = 0.01^2 —
+ * while a Sinkhorn loop calls a few hundred times on the same two clouds.  A cloud gets the same order as rows and as columns.
+ *   perm_x (N ints), perm_y (M ints): DEVICE buffers, either may be NULL (no hint and no export for that cloud).
+ *   perm_flags & GLHIP_PERM_HINT_X: perm_x HOLDS the order of x — box, keys, sort and balancing are not launched for x, the call
+ *     reads the buffer and does not write it; GLHIP_PERM_HINT_Y: the same for perm_y and y.
+ *   A non-NULL buffer without its bit RECEIVES the order the call computes (sorted position -> caller's index, what
+ *     glhip_prune_inspect reports), written straight by the sort: no copy, no extra launch.
+ *   The x side is prepared first: where x and y are one cloud, one buffer may be passed as perm_x (export) and as perm_y with
+ *     GLHIP_PERM_HINT_Y, and the cloud is sorted once.
+ * Contract of a hint: a permutation of 0 .. n-1 that this library wrote for a cloud of the same n points, alive and unchanged until
+ * the work queued on `stream` has run, produced on `stream` or synchronised with it by the caller.  With anything else the outputs
+ * are unspecified, but every access stays in bounds: each kernel that indexes through a hint clamps the index into [0, n).
+ * A STALE hint — the right size, the order of other coordinates — changes no result beyond the pruned call's guarantee (a row loses
+ * < 2^-26 of its sum): the pruning is exact for any order, every box it uses is recomputed from the gathered coordinates on every
+ * call, and the order only decides how much is kept, that is, the time.  Only permutations are reused for this reason.
+ * Where glhip_softmin_perm_applies says 0, or the workspace is below glhip_workspace_bytes, the three arguments are ignored: nothing
+ * is read or written through them, and the call is glhip_sinkhorn_step.  glhip_softmin_fwd is this call with pot = prev = NULL,
+ * damping = 1.  The workspace size and layout are those of glhip_sinkhorn_step.
+ */
+#define GLHIP_PERM_HINT_X 1
+#define GLHIP_PERM_HINT_Y 2
+int glhip_sinkhorn_step_perm(const void* x, const void* y, const float* logw, const float* pot, const float* prev,
+                             float* out, int B, int N, int M, int D, float eps, float damping, int p, int in_dtype,
+                             const int32_t* ranges_i, const int32_t* slices_i,
+                             const int32_t* redranges_j, int n_ranges,
+                             void* workspace, size_t workspace_bytes, int flags, void* stream,
+                             int32_t* perm_x, int32_t* perm_y, int perm_flags);
+/* Whether a call of this shape is the sorted p = 2 call, the one that takes and gives permutations: 1 / 0, host arithmetic only, like
+ * glhip_softmin_fwd_family (1 exactly where that predicate routes a p = 2 call through the sort; 0 for p = 1, B > 1, ranges,
+ * GLHIP_FLAG_NO_SORT and below 1e11 pairs).  The workspace condition is the caller's.  GLHIP_EINVAL for arguments the entry points reject. */
+int glhip_softmin_perm_applies(int B, long N, long M, int D, int p, int dtype, int flags, int n_ranges);
 
 /*
  * One whole iteration of the symmetric Sinkhorn loop in ONE launch (+ one merge launch): the four
