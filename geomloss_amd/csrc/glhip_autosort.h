@@ -20,6 +20,7 @@
 #include <cstdint>
 
 #include "glhip_error.h"
+#include "glhip_split_policy.h"      // align256
 
 namespace glhip {
 
@@ -53,7 +54,7 @@ constexpr int kSortRowsPerVoxel = 256;
 //   Balanced cells (library 128).  Voxels and sub-voxels hold 256 and 32 points on average, with Poisson counts: an ALIGNED run of exactly
 //   256 (32) sorted points — what both levels put a box around — usually straddles two of them, and its box is up to twice the size
 //   it could be.  So after the radix sort the sorted p = 2 call splits every whole aligned block of kBalanceBlock = 1024 positions
-//   of the path order like a k-d tree (balance_kernel, glhip_cluster.hip; the rules: glhip_balance.h): five levels with segments of
+//   of the path order like a k-d tree (balance_kernel, glhip_compact_sort.hip; the rules: glhip_balance.h): five levels with segments of
 //   1024, 512, 256, 128 and 64 points, each segment sorted by (coordinate on the axis of its largest finite extent — ties: the lowest
 //   axis — in an order where -inf < ... < +inf < NaN, position the point had in the block).  The result: cells of exactly 512, 256,
 //   128, 64 and 32 points, every one the half of a median cut, which slabs, column blocks, row tiles and column groups are aligned to.
@@ -79,7 +80,7 @@ constexpr int kSortRowsPerVoxel = 256;
 //       < t2 sum to at most the budget; the kernel's threshold is max(term rule's, t2(W)).
 //   Thresholds come from histograms, not sorts: kPruneBuckets buckets of kPruneBucketNats from the term rule's threshold (Mlb - L,
 //   ms - L) up, each holding the actual mass of its keys; keys below the range share an underflow bucket that is always counted (and
-//   can never exceed a budget by itself: glhip_cluster.hip, prune_first_kept), keys above it are never dropped; the threshold is the
+//   can never exceed a budget by itself: glhip_prune.hip, prune_first_kept), keys above it are never dropped; the threshold is the
 //   lower edge of the first bucket at which the running sum passes the budget.  Rounding: the first level and t2 are float64 from the
 //   exact float32 corners; lse is a float32 rounded UP (kPruneLseSlack); t2 is stored in log2 units as a float32 rounded toward minus
 //   infinity; the kernel's ub carries its slack on the keep side.  Special blocks and groups are never dropped and enter no sum; a
@@ -123,9 +124,7 @@ inline bool prune_applies(int N, int M) {
     return (double)N * M >= kPruneMinPairs && C * (long)prune_plan(M).S * 2 < (1L << 31) - 1;
 }
 
-inline size_t as_align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// implemented in glhip_cluster.hip (rocPRIM lives there)
+// implemented in glhip_compact_sort.hip (rocPRIM's radix sort lives there)
 size_t compact_sort_scratch_bytes(int n);
 // sub > 1: inside a voxel, points are ordered by sub-voxel of edge voxel / sub (the minor key of path_keys_kernel), then every whole
 // block of kBalanceBlock positions is split into balanced cells (balance_kernel).  hinted: `perm` already holds the order, from an
@@ -136,6 +135,7 @@ int compact_sort(const void* z, int n, int D, int in_dtype, int rows_per_voxel, 
 void gather_f32(const float* src, const int32_t* perm, float* dst, int n, hipStream_t st, bool hinted = false);       // dst[k] = src[perm[k]]
 void scatter_f32(const float* src, const int32_t* perm, float* dst, int n, hipStream_t st, int width = 1, bool hinted = false);      // dst[perm[k], :] = src[k, :]
 void slab_ranges(int N, int M, int32_t* ranges_i, int32_t* slices_i, int32_t* red, hipStream_t st);
+// implemented in glhip_prune.hip
 size_t prune_blocks_bytes(int M);
 size_t prune_groups_bytes(int M);
 // the kept column intervals of every slab of the sorted clouds xs (N, D), ys (M, D) for the column vector h (+ pot * pot_scale); for the
@@ -176,11 +176,11 @@ inline size_t autosort_bytes(int N, int M, int D) {
     const int C = (N + kSortSlab - 1) / kSortSlab;
     const int L = N > M ? N : M;
     const size_t slots = (size_t)(kSortColChunks > prune_plan(M).S ? kSortColChunks : prune_plan(M).S);   // interval slots per slab
-    return as_align256((size_t)N * 4) + as_align256((size_t)M * 4) + as_align256((size_t)N * D * 4) + as_align256((size_t)M * D * 4) +
-           2 * as_align256((size_t)M * 4) + 2 * as_align256((size_t)N * 4) + as_align256((size_t)N * D * 4) + as_align256((size_t)C * 8) +
-           as_align256((size_t)C * 4) +
-           as_align256((size_t)C * slots * 8) + as_align256(prune_blocks_bytes(M)) + as_align256(prune_groups_bytes(M)) +
-           as_align256((size_t)C * 4) + compact_sort_scratch_bytes(L);
+    return align256((size_t)N * 4) + align256((size_t)M * 4) + align256((size_t)N * D * 4) + align256((size_t)M * D * 4) +
+           2 * align256((size_t)M * 4) + 2 * align256((size_t)N * 4) + align256((size_t)N * D * 4) + align256((size_t)C * 8) +
+           align256((size_t)C * 4) +
+           align256((size_t)C * slots * 8) + align256(prune_blocks_bytes(M)) + align256(prune_groups_bytes(M)) +
+           align256((size_t)C * 4) + compact_sort_scratch_bytes(L);
 }
 
 // Sorts both clouds into the workspace; `a.on` stays false when the workspace is too small for the sorted call plus `inner_min`
@@ -200,7 +200,7 @@ inline int autosort_prepare(AutoSort& a, const void* x, const void* y, int N, in
     if (!workspace || workspace_bytes < need + inner_min) return 0;
     char* w = static_cast<char*>(workspace);
     size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = w + off; off += as_align256(bytes); return p; };
+    auto take = [&](size_t bytes) { char* p = w + off; off += align256(bytes); return p; };
     a.C = (N + kSortSlab - 1) / kSortSlab;
     a.perm_x = reinterpret_cast<int32_t*>(take((size_t)N * 4));
     a.perm_y = reinterpret_cast<int32_t*>(take((size_t)M * 4));

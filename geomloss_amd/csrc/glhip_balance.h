@@ -1,4 +1,4 @@
-// glhip_balance.h — the balancing pass of the sorted p = 2 call (balance_kernel, glhip_cluster.hip; why: glhip_autosort.h).  Every whole
+// glhip_balance.h — the balancing pass of the sorted p = 2 call (balance_kernel, glhip_compact_sort.hip; why: glhip_autosort.h).  Every whole
 // aligned block of kBalanceBlock positions of the path order is split like a k-d tree: five levels with segments of 1024, 512, 256,
 // 128 and 64 points; a segment is sorted by (coordinate on its own longest axis, position the point had in the block), so its halves
 // are the two sides of a median cut.  The pieces here are what the kernel and the CPU model (tools/prune_model.py: balanced_order)

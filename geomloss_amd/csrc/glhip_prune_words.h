@@ -1,5 +1,5 @@
 // glhip_prune_words.h — the kept column blocks of a slab as a bit set, and its pieces for a gap length g, one 64-bit word at a time
-// (prune_slabs_kernel, glhip_cluster.hip; the rule itself: glhip_autosort.h).  Word w holds the blocks 64 w ... 64 w + 63, bit b set =
+// (prune_slabs_kernel, glhip_prune.hip; the rule itself: glhip_autosort.h).  Word w holds the blocks 64 w ... 64 w + 63, bit b set =
 // block 64 w + b is kept; bits from nT on are 0.  A piece starts at a kept block that opens a run (the first kept block, or one with
 // at least g blocks that are not kept in front of it: g = 1, its predecessor is not kept) or that is a multiple of PB (a cut on the
 // piece grid, on the kept bits as they are, also inside a run that closed a gap); it ends where the next piece starts, or behind the

@@ -280,7 +280,7 @@ __device__ __forceinline__ void softmin_fwd_x32_body(const SoftminParams<T>& prm
     // Grouped source: the packed columns are group-major ([group of 32][K block][column], the LDS tile layout: PackedCols), every tile
     // starts on a group boundary and is staged by a linear copy.  True for the dense pre-packed launches and for the sorted p = 2
     // launch (P2) on the f16 x 2 layout.  Precondition of the latter: its column intervals start on multiples of 32 and end on
-    // multiples of 32 or at M — they are whole column blocks of kPruneColBlock sorted columns (glhip_cluster.hip: kPruneColBlock % 64
+    // multiples of 32 or at M — they are whole column blocks of kPruneColBlock sorted columns (glhip_prune.hip: kPruneColBlock % 64
     // == 0), one piece per tile (the host launches P2 without SplitInfo::gather only).  The pack kernel has written neutral columns
     // into the cloud's last group.  The bf16 x 3 P2 kernel keeps [M][NR] and the gathered tile: it is held to 80 VGPRs (6 wavefronts
     // per SIMD) and already spills; the grouped fetch — four records 8 KB apart per thread instead of one column's four adjacent

@@ -1,5 +1,5 @@
 """The balanced cells of the sorted p = 2 call (csrc/glhip_autosort.h: balanced cells; csrc/glhip_balance.h; balance_kernel in
-csrc/glhip_cluster.hip), on the host.
+csrc/glhip_compact_sort.hip), on the host.
 
 Two things are checked here.  The CPU model tools/prune_model.py: balanced_order — every whole aligned block of 1024 positions of the
 path order split into cells of 512, ..., 32 points by median cuts along the longest axis — keeps every block's set of points, leaves

@@ -1,5 +1,5 @@
 """The balanced cells of the sorted p = 2 call on the device (csrc/glhip_autosort.h: balanced cells; balance_kernel in
-csrc/glhip_cluster.hip; the rules: csrc/glhip_balance.h).
+csrc/glhip_compact_sort.hip; the rules: csrc/glhip_balance.h).
 
 After the radix sort, every whole aligned block of 1024 positions of both sorted clouds is split by median cuts along the longest axis
 into cells of exactly 512, 256, 128, 64 and 32 points.  The order shows through glhip_prune_inspect (perm_x, perm_y): it must be a

@@ -1,4 +1,4 @@
-"""Exact block pruning of big dense p = 2 soft-min reductions (csrc/glhip_autosort.h, glhip_cluster.hip: prune_slabs_kernel).
+"""Exact block pruning of big dense p = 2 soft-min reductions (csrc/glhip_autosort.h, glhip_prune.hip: prune_slabs_kernel).
 
 Big dense p = 2 launches (B = 1, D <= 3, N >= 65536, N M >= 1e11) sort both clouds inside the library and reduce only the column blocks
 that can change a float32 result.  Every case runs the same call with GLHIP_FLAG_NO_SORT (the dense launch) next to it: the two differ

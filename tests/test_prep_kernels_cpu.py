@@ -1,4 +1,4 @@
-"""The host side of the cheaper preparation kernels of the pruned p = 2 call (csrc/glhip_cluster.hip), on the plain-C++ headers.
+"""The host side of the cheaper preparation kernels of the pruned p = 2 call (csrc/glhip_prune.hip), on the plain-C++ headers.
 
 Gap closing from the bit set (csrc/glhip_prune_words.h).  A slab with more than kPruneRuns runs of kept blocks closes its smallest gaps:
 g is the smallest gap length that leaves at most kPruneRuns runs, a run starts at the first kept block or at one with at least g blocks

@@ -1,4 +1,4 @@
-"""The preparation kernels of the pruned p = 2 call after their rework (csrc/glhip_cluster.hip: prune_slabs_kernel closes gaps from the
+"""The preparation kernels of the pruned p = 2 call after their rework (csrc/glhip_prune.hip: prune_slabs_kernel closes gaps from the
 bit set, prune_tiles_kernel maps a thread to a (group, tile) pair, balance_kernel partitions its upper levels) at the smallest shapes
 that prune (N M >= 1e11, N >= 65536): 65536 x 1525900 (256 slabs, 5961 column blocks), 320000 x 320000 and 317000 x 320037 with D = 2.
 

@@ -1,5 +1,5 @@
 """The mass rule of the exact pruning of big dense p = 2 soft-min launches (csrc/glhip_autosort.h; prune_slabs_kernel and
-prune_tiles_kernel in csrc/glhip_cluster.hip): both levels drop by the SUM of what they drop, bounded from the block / group records.
+prune_tiles_kernel in csrc/glhip_prune.hip): both levels drop by the SUM of what they drop, bounded from the block / group records.
 
 What is dropped stays below one ulp of the output by design, so the outputs cannot tell a correct budget from a generous one.  These
 tests read the thresholds themselves through glhip_prune_inspect: against the NumPy model (tools/prune_model.py) fed with the device's

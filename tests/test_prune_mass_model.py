@@ -1,5 +1,5 @@
 """Host-only check of the mass rule of the exact pruning (tools/prune_model.py: plan_mass / level2_mass restate prune_slabs_kernel and
-prune_tiles_kernel of csrc/glhip_cluster.hip).  On the points themselves, in float64: what the first level drops for a slab plus what
+prune_tiles_kernel of csrc/glhip_prune.hip).  On the points themselves, in float64: what the first level drops for a slab plus what
 the second level skips for a row's tile holds less than 2^-26 of the row's true sum; and the rule evaluates no more pairs than the
 term rule of rounds 7 / 9 on the same order."""
 

@@ -1,4 +1,4 @@
-"""Host-only check of the exact block-pruning bound (tools/prune_model.py restates csrc/glhip_cluster.hip: prune_slabs_kernel):
+"""Host-only check of the exact block-pruning bound (tools/prune_model.py restates csrc/glhip_prune.hip: prune_slabs_kernel):
 no dropped column block holds a term above Mlb(R) - L for any row of its slab, so the dropped mass of a row is below 2^-26 of its sum."""
 
 import os

@@ -1,4 +1,4 @@
-"""What prune_slabs_kernel and prune_tiles_kernel (csrc/glhip_cluster.hip) hand to the sorted p = 2 launch — every slab's Mlb, t1, home
+"""What prune_slabs_kernel and prune_tiles_kernel (csrc/glhip_prune.hip) hand to the sorted p = 2 launch — every slab's Mlb, t1, home
 block and column intervals, every tile's t2 — against the NumPy model (tools/prune_model.py) on the device's own order, read through
 glhip_prune_inspect.  tests/test_prune_mass_gpu.py does this on the headline law at an even shape; here are the inputs on which the
 kept blocks are found from the 64-bit words of a bit set (csrc/glhip_prune_words.h) and on which a cheaper evaluation of the keys could

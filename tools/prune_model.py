@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""CPU model of the exact block pruning of big dense p = 2 soft-min launches (csrc/glhip_autosort.h, glhip_cluster.hip).
+"""CPU model of the exact block pruning of big dense p = 2 soft-min launches (csrc/glhip_autosort.h, glhip_compact_sort.hip, glhip_prune.hip).
 
 Restates in NumPy what the library does on the device: both clouds voxel-sorted along a boustrophedon path (compact_sort), rows cut
 into slabs of 256, columns into blocks of 256, the float64 bound
@@ -27,7 +27,7 @@ SLAB, BLOCK, RUNS, MARGIN = 256, 256, 160, 1.0
 
 
 def compact_order(z, rows_per_voxel):
-    """glhip_cluster.hip: voxel_kernel + path_keys_kernel + a stable radix sort of the keys"""
+    """glhip_compact_sort.hip: voxel_kernel + path_keys_kernel + a stable radix sort of the keys"""
     z = np.asarray(z, np.float32)
     n, D = z.shape
     lo, hi = z.min(0), z.max(0)
@@ -99,7 +99,7 @@ def balance_axes(p):
 
 
 def balanced_order(z, perm, block=1024, leaf=32):
-    """glhip_cluster.hip: balance_kernel, on the order `perm` of the cloud z (float32 values; a bf16 cloud: its values as float32).
+    """glhip_compact_sort.hip: balance_kernel, on the order `perm` of the cloud z (float32 values; a bf16 cloud: its values as float32).
     Every whole aligned block of `block` positions is split like a k-d tree: levels with segments of block, block / 2, ..., 2 leaf
     points, each segment sorted by (order_key of the coordinate on the segment's own axis, position the point had in the block).
     The last n mod block positions are left as they are.  Returns the new order."""
