@@ -6,6 +6,10 @@ This module is the only place where Python touches the HIP kernels.  It plays th
 ``_legacy/sinkhorn_samples.py:322-334,432-442``; ``LazyTensor @ v`` at
 ``_legacy/kernel_samples.py:128-137``).  There is no fallback: if the shared library is missing or
 a tensor is not on a GPU, the call raises.
+
+Three leaves live in private modules and are re-exported here, so that everybody else keeps writing ``hip.NAME``: the mirror of
+``include/glhip.h`` with the loader (``_glhip.py``), the permutation cache's key and container (``_perm_cache.py``), the hipGraph cache
+and ``settle_host`` (``_graphs.py``).  What reads or calls a name that tests replace on this module stays here.
 """
 
 import ctypes
@@ -15,152 +19,17 @@ import warnings
 import torch
 from torch.autograd.function import once_differentiable
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libgeomloss_hip.so")
-
-GAUSSIAN, LAPLACIAN, ENERGY = 0, 1, 2
-KERNEL_KINDS = {"gaussian": GAUSSIAN, "laplacian": LAPLACIAN, "energy": ENERGY}
-F32, BF16 = 0, 1
-FLAG_DIRECT, FLAG_NO_MFMA, FLAG_NO_SPLIT, FLAG_F32_MFMA, FLAG_XDL16, FLAG_PREPACK, FLAG_MFMA_DIST, FLAG_SMALL_ROW_BLOCKS = 1, 2, 4, 8, 16, 32, 64, 128
-FLAG_F16X2 = 256                # exponents from two f16 pieces per coordinate; the caller vouches for the range (glhip.h)
-FLAG_NO_SORT = 512              # big dense distance reductions: do not voxel-sort the clouds inside the library (glhip.h)
-FLAG_XK_GRAD = 1024             # glhip_softmin_bwd_x: the p = 2 gradient of 17 <= D <= 4095 on the matrix cores (glhip_softmin_grad_xk.h);
-                                # glhip_kernel_conv_bwd_x / _fwd_grad: the gaussian gradient of those dimensions (glhip_gauss_grad_xk.h)
-FLAG_XK_DIST = 2048             # p = 1 soft-min / half-step, laplacian and energy products of 17 <= D <= 4095, dense launches: squared distances
-                                # from the K-chunked matrix-core chain (glhip_dist_xk.h); opt-in, the gradients stay on the generic kernel
-FLAG_XK_DIST_GRAD = 4096        # the p = 1 soft-min, laplacian and energy row gradients of 17 <= D <= 4095, dense launches, on the matrix cores
-                                # (glhip_dist_grad_xk.h); glhip_kernel_conv_fwd_grad takes those kinds under it
-DIST_GRAD_OPS = {"softmin_p1": 0, "laplacian": 1, "energy": 2}      # ops of glhip_dist_grad_uses_xk (GLHIP_DIST_GRAD_*)
-FLAG_GRAD_FAMILY = FLAG_XDL16   # kernel products rounded like the product-and-gradient kernel of the same kind (glhip.h)
-XD_MAX_DIM = 16                 # the fused four-softmin iteration / annealing / extrapolation, the one-pass value + gradient and the matrix-core
-                                # gradients stop at this dimension (glhip_softmin_xd.h, glhip_wsum_t32.h)
-MFMA_FWD_MAX_DIM = 4095         # p = 2 soft-min forward / half-step and gaussian product run on the matrix cores up to this dimension
-                                # (17 ... 4095: the K-chunked kernel of glhip_softmin_xk.h; kept in step with the library by tests/test_anyd_kernels_gpu.py)
-DIST_XK_MAX_DIM = 4095          # ... and under FLAG_XK_DIST the p = 1 soft-min / half-step and the laplacian / energy products too (glhip_dist_xk.h)
-ARGMIN_MAX_DIM = 4095           # argmin takes p = 2 clouds of every dimension up to this one (glhip_argmin_xk.h)
-PLAN_MAX_DIM = 4095             # plan_apply_nd applies p = 2 transport plans to features up to this dimension (17 ... 4095: glhip_plan_apply_xk.h)
-# kernel families reported by softmin_fwd_family (GLHIP_FAMILY_* of glhip.h)
-FAMILY_VALU, FAMILY_X32, FAMILY_XD, FAMILY_XK, FAMILY_DIST, FAMILY_GENERIC = 0, 1, 2, 3, 4, 5
-
-# every symbol include/glhip.h declares, with its ctypes signature
-_c_int, _c_float, _vp, _c_size = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
-_c_long = ctypes.c_long
-_RANGES = [_vp, _vp, _vp, _c_int]
-_TAIL = [_vp, _c_size, _c_int, _vp]  # workspace, workspace_bytes, flags, stream
-SIGNATURES = {
-    "glhip_version": (_c_int, []),
-    "glhip_last_error": (ctypes.c_char_p, []),
-    "glhip_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
-    "glhip_softmin_fwd_family": (_c_int, [_c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int, _c_int]),
-    "glhip_kernel_conv_fwd_family": (_c_int, [_c_int, _c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int]),
-    "glhip_prune_inspect_slots": (_c_int, [_c_int]),
-    "glhip_prune_inspect": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_float, _c_int] + [_vp] * 7 + [_vp, _c_size, _vp]),
-    "glhip_softmin_fwd": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int, _c_int]
-                          + _RANGES + _TAIL),
-    "glhip_sinkhorn_step": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_float,
-                                     _c_int, _c_int] + _RANGES + _TAIL),
-    "glhip_sinkhorn_step_perm": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_float,
-                                          _c_int, _c_int] + _RANGES + _TAIL + [_vp, _vp, _c_int]),
-    "glhip_softmin_perm_applies": (_c_int, [_c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int, _c_int]),
-    "glhip_sinkhorn_iter4": (_c_int, [_vp] * 12 + [_c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _c_int, _c_int, _c_int]
-                             + _TAIL),
-    "glhip_sinkhorn_anneal": (_c_int, [_vp] * 6 + [_c_int] * 4 + [_vp, _vp, _c_int, _c_int, _c_int, _vp, _c_size, _c_int, _c_float, _vp]),
-    "glhip_sinkhorn_extrapolate4": (_c_int, [_vp] * 14 + [_c_int] * 6 + [_c_float, _c_float, _c_int, _c_int] + _TAIL),
-    "glhip_softmin_bwd_x": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int,
-                                     _c_int] + _RANGES + _TAIL),
-    "glhip_softmin_bwd_x_uses_plan": (_c_int, [_c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int, _c_int]),
-    "glhip_softmin_bwd_x_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
-    "glhip_kernel_conv_grad_uses_xk": (_c_int, [_c_int, _c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int]),
-    "glhip_kernel_conv_grad_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
-    "glhip_dist_grad_uses_xk": (_c_int, [_c_int, _c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int]),
-    "glhip_dist_grad_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
-    "glhip_dist_grad_pass_width": (_c_int, []),
-    "glhip_plan_apply_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
-    "glhip_plan_apply": (_c_int, [_vp] * 7 + [_c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int, _c_int] + _RANGES + _TAIL),
-    "glhip_plan_apply_nd_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
-    "glhip_plan_apply_nd_family": (_c_int, [_c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int]),
-    "glhip_plan_apply_nd_pass_width": (_c_int, [_c_int]),
-    "glhip_plan_apply_nd": (_c_int, [_vp] * 7 + [_c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int, _c_int] + _RANGES + _TAIL),
-    "glhip_kernel_conv_fwd": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int]
-                              + _RANGES + _TAIL),
-    "glhip_kernel_conv_bwd_x": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float,
-                                         _c_int] + _RANGES + _TAIL),
-    "glhip_softmin_fwd_grad": (_c_int, [_vp, _vp, _vp, _vp, _c_float, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int,
-                                        _c_int] + _RANGES + _TAIL),
-    "glhip_kernel_conv_fwd_grad": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float,
-                                            _c_int] + _RANGES + _TAIL),
-    "glhip_softmin_dense_fwd": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_int, _c_float, _vp]),
-    "glhip_bounding_box": (_c_int, [_vp, _c_long, _vp, _c_long, _c_int, _c_int, _vp, _vp]),
-    "glhip_log_weights": (_c_int, [_vp, _vp, _vp, _c_int, _vp]),
-    "glhip_sinkhorn_cost": (_c_int, [_vp] * 7 + [_c_int] * 5 + [_vp]),
-    "glhip_lse_lines_fwd": (_c_int, [_vp, _vp, ctypes.c_long, _c_int, _c_float, _c_int, _vp]),
-    "glhip_lse_lines_bwd": (_c_int, [_vp, _vp, _vp, _vp, ctypes.c_long, _c_int, _c_float, _c_int, _vp]),
-    "glhip_cmin_fwd": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int] + _RANGES + _TAIL),
-    "glhip_max_lines_fwd": (_c_int, [_vp, _vp, ctypes.c_long, _c_int, _c_float, _c_int, _vp]),
-    "glhip_argmin_supported": (_c_int, [_c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int]),
-    "glhip_argmin_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int]),
-    "glhip_argmin": (_c_int, [_vp] * 5 + [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int] + _RANGES + _TAIL),
-    "glhip_cluster_workspace_bytes": (_c_size, [_c_int, _c_int]),
-    "glhip_grid_cluster": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_float, _c_float] + [_vp] * 7 + [_vp, _c_size, _vp]),
-    "glhip_block_ranges": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float] + [_vp] * 6
-                           + [ctypes.c_longlong, _vp, _vp]),
-    "glhip_block_ranges_count": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float] + [_vp] * 5 + [_vp]),
-    "glhip_block_ranges_kept_pairs": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float] + [_vp] * 4),
-}
-_c_double = ctypes.c_double
-SIGNATURES.update({
-    # float64 reductions (glhip_api_f64.hip): every array is double; no workspace, no flags
-    "glhip_softmin_fwd_f64": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_double, _c_int] + _RANGES + [_vp]),
-    "glhip_sinkhorn_step_f64": (_c_int, [_vp] * 6 + [_c_int, _c_int, _c_int, _c_int, _c_double, _c_double, _c_int] + _RANGES + [_vp]),
-    "glhip_softmin_bwd_x_f64": (_c_int, [_vp] * 6 + [_c_int, _c_int, _c_int, _c_int, _c_double, _c_int] + _RANGES + [_vp]),
-    "glhip_kernel_conv_fwd_f64": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_double] + _RANGES + [_vp]),
-    "glhip_kernel_conv_bwd_x_f64": (_c_int, [_c_int] + [_vp] * 5 + [_c_int, _c_int, _c_int, _c_int, _c_double] + _RANGES + [_vp]),
-})
-KEEP_DUAL_SLACK, KEEP_WITHIN = 0, 1
-PERM_HINT_X, PERM_HINT_Y = 1, 2     # perm_flags of glhip_sinkhorn_step_perm (GLHIP_PERM_HINT_*)
-# symbols younger than the oldest C-ABI that GEOMLOSS_HIP_LIB may name for an A/B run: an older build is bound without them, and the
-# calls that would use them take the entry points that build has (no permutation is reused with it)
-_SINCE = {"glhip_sinkhorn_step_perm": 134, "glhip_softmin_perm_applies": 134}
-
-_lib = None
+from . import _glhip
+from ._glhip import *  # noqa: F401,F403  (FLAG_*, FAMILY_*, kinds, dtype codes, *_MAX_DIM, SIGNATURES, LIB_PATH, load_library, bind, ...)
+from ._glhip import _HERE, _RANGES, _SINCE, _TAIL, _c_double, _c_float, _c_int, _c_long, _c_size, _check, _vp  # noqa: F401
+from ._graphs import GraphCache, settle_host  # noqa: F401
+from ._perm_cache import PERM_CACHE_ENTRIES, _PermCache, perm_cache_key  # noqa: F401
 
 
-def load_library(path=None):
-    """Loads (once) and returns the shared library; raises ``RuntimeError`` if it is not built."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    path = path or os.environ.get("GEOMLOSS_HIP_LIB") or LIB_PATH      # GEOMLOSS_HIP_LIB: another build of the same C-ABI (A/B runs)
-    if not os.path.exists(path):
-        raise RuntimeError(
-            f"geomloss_amd: the HIP extension {path} is missing. Build it with "
-            "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C geomloss_amd/csrc`). "
-            "The 'online' and 'multiscale' backends have no CPU or PyTorch fallback."
-        )
-    lib = ctypes.CDLL(path)
-    lib.glhip_version.restype = _c_int
-    version = int(lib.glhip_version())
-    for name, (restype, argtypes) in SIGNATURES.items():
-        if version < _SINCE.get(name, 0) and path != LIB_PATH:
-            continue
-        fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
-        fn.restype, fn.argtypes = restype, argtypes
-    _lib = lib
-    return lib
-
-
-def library_available():
-    return os.path.exists(LIB_PATH)
-
-
-def _check(rc, lib):
-    if rc != 0:
-        msg = lib.glhip_last_error().decode()
-        if rc == -1:
-            raise ValueError(msg)
-        if rc == -2:
-            raise NotImplementedError(msg)
-        raise RuntimeError(msg)
+def __getattr__(name):
+    if name == "_lib":      # the loaded library, or None before the first load_library(): state of _glhip, read through
+        return _glhip._lib
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def _stream(t):
@@ -248,14 +117,33 @@ def _range_args(ranges, B):
     return ranges.c_args()
 
 
-def _workspace(lib, x, B, N, M, D, ranges):
-    """Scratch buffer for column splits (torch's caching allocator makes this a free-list lookup)."""
-    n_ranges = 0 if ranges is None else int(ranges.ranges_i.shape[0])
-    nbytes = int(lib.glhip_workspace_bytes(B, N, M, D, n_ranges))
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _scratch(nbytes, device):
+    """A scratch buffer of ``nbytes`` bytes (torch's caching allocator makes this a free-list lookup) as ``(tensor | None, [pointer | None,
+    nbytes])``: the tensor keeps the bytes alive until the launch is queued, the list is the workspace pair of the C-ABI."""
     if nbytes == 0:
         return None, [None, 0]
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
     return ws, [ctypes.c_void_p(ws.data_ptr()), nbytes]
+
+
+def _workspace(lib, x, B, N, M, D, ranges):
+    """Scratch buffer for column splits."""
+    n_ranges = 0 if ranges is None else int(ranges.ranges_i.shape[0])
+    return _scratch(int(lib.glhip_workspace_bytes(B, N, M, D, n_ranges)), x.device)
+
+
+def _iter4_scratch(lib, x, B, rows, cols, D):
+    """Scratch buffer of the launches that run four reductions side by side (iteration, annealing, extrapolation): four times that of one
+    dense reduction of ``rows`` x ``cols``."""
+    return _scratch(4 * int(lib.glhip_workspace_bytes(B, rows, cols, D, 0)), x.device)
+
+
+# the part of ENV_FLAGS that reaches those launches
+_ITER4_ENV_MASK = FLAG_NO_SPLIT | FLAG_F16X2
 
 
 def _as_batched(x, y, s):
@@ -268,79 +156,40 @@ def _as_batched(x, y, s):
     return x, y, s.reshape(x.shape[0], -1), True
 
 
+def _clouds(x, y, s, allow_f64=False, detach=False):
+    """The inputs of a launch over the clouds x (N,D)|(B,N,D) and y (M,D)|(B,M,D): ``(xb, yb, sb, batched)`` with a batch axis, both clouds
+    as the kernels read them (:func:`_points`) in ONE dtype, x's.  ``s``: the per-column vector as the caller has converted it."""
+    if detach:
+        x, y = x.detach(), y.detach()
+    xb, yb, sb, batched = _as_batched(_points(x, "x", allow_f64), _points(y, "y", allow_f64), s)
+    if yb.dtype != xb.dtype:
+        yb = yb.to(xb.dtype)
+    return xb, yb, sb, batched
+
+
+def _kind(kind):
+    return KERNEL_KINDS[kind] if isinstance(kind, str) else int(kind)
+
+
+def _blur(blur):
+    return 1.0 if blur is None else float(blur)
+
+
+def _dist_flags(flags, ranges, applies):
+    """``flags`` of a distance-type launch — ``applies``: the caller's own condition (p = 1 soft-min / half-step, laplacian / energy
+    product of D <= 3) — with the word on squared distances from the matrix cores: the row blocks of a block-sparse launch are voxel
+    clusters already (FLAG_MFMA_DIST); big dense launches sort themselves inside the library unless told not to (FLAG_NO_SORT)."""
+    if applies and not (flags & (FLAG_NO_MFMA | FLAG_DIRECT)):
+        if not _dist_on_mfma:
+            return flags | FLAG_NO_SORT
+        if ranges is not None:
+            return flags | FLAG_MFMA_DIST
+    return flags
+
+
 # ----------------------------------------------------------------------------------------------
 #  reused permutations of the sorted p = 2 call
 # ----------------------------------------------------------------------------------------------
-
-PERM_CACHE_ENTRIES = 8
-
-
-def perm_cache_key(t, stream_id):
-    """The key under which the sorted order of the cloud ``t`` ((N,D) or (1,N,D)) is kept: the identity of its storage, its data pointer,
-    the shape and strides of its last two axes, dtype, device, the launch stream and the tensor's version counter.  Pure Python on
-    tensor metadata (CPU tensors have keys too).  ``.detach()`` and views share storage and counter, so ``x``, ``x.detach()`` and
-    ``x[None]`` have one key; an in-place torch write bumps the counter.  None: a tensor without a counter (inference mode)."""
-    try:
-        version = t._version
-    except RuntimeError:
-        return None
-    return (t.untyped_storage()._cdata, t.data_ptr(), tuple(t.shape[-2:]), tuple(t.stride()[-2:]), t.dtype, str(t.device),
-            int(stream_id), int(version))
-
-
-class _PermCache:
-    """Per-CLOUD cache of the int32 permutations that ``glhip_sinkhorn_step_perm`` exports and takes back as hints.
-
-    The sorted p = 2 call (``softmin_perm_applies``: one dense problem of D <= 3 and N M >= 1e11) orders each cloud by its coordinates
-    alone — bounding box, voxel path keys, a 64-bit radix sort, balanced cells — before anything that depends on the dual vector or the
-    temperature.  A Sinkhorn loss calls 4 x (n_eps + 2) times on the same two clouds, and a cloud has the same order as rows and as
-    columns, so ``(x, y)``, ``(y, x)``, ``(x, x)`` and ``(y, y)`` share two entries: two sorts per loss.  Everything that depends on
-    ``h`` or ``eps`` — the gathers of the vectors, the three pruning kernels, the reduction — runs on every call.
-
-    An entry is used only if every part of :func:`perm_cache_key` matches and the storage is alive (a weak reference to the storage,
-    not to the Python tensor: the drivers pass fresh ``.detach()`` / ``[None]`` views on every call).  Entries of dead storages are
-    dropped at every lookup, which frees their permutations; a fresh tensor on a freed address is another storage and misses; another
-    stream misses (the permutation was produced elsewhere); at most ``PERM_CACHE_ENTRIES`` entries, least recently used out.
-    While the current stream is capturing a graph the cache is neither read nor filled: a replay must not depend on a buffer that the
-    cache may free.
-
-    What the key does NOT see: writes that bypass the version counter — through ``.data``, a raw pointer, another library.  The entry
-    is then stale, and the result is STILL RIGHT: the pruning is exact for any order (csrc/glhip_autosort.h), every box it uses is
-    recomputed from the gathered coordinates on every call, and a stale order only keeps more pairs, that is, costs time.
-    :func:`forget_permutations` clears the cache; ``GEOMLOSS_HIP_PERM_CACHE=0`` turns it off."""
-
-    def __init__(self):
-        import collections
-        import threading
-        self.lock = threading.Lock()
-        self.entries = collections.OrderedDict()      # key -> (StorageWeakRef, permutation)
-        self.hits = self.misses = 0
-
-    def lookup(self, key):
-        """The permutation kept for ``key`` (counted as a hit), or None (a miss); drops the entries of dead storages."""
-        with self.lock:
-            for k in [k for k, (ref, _) in self.entries.items() if ref.expired()]:
-                del self.entries[k]
-            hit = self.entries.get(key)
-            if hit is None:
-                self.misses += 1
-                return None
-            self.entries.move_to_end(key)
-            self.hits += 1
-            return hit[1]
-
-    def store(self, key, t, perm):
-        from torch.multiprocessing.reductions import StorageWeakRef
-        with self.lock:
-            self.entries[key] = (StorageWeakRef(t.untyped_storage()), perm)
-            self.entries.move_to_end(key)
-            while len(self.entries) > PERM_CACHE_ENTRIES:
-                self.entries.popitem(last=False)
-
-    def clear(self):
-        with self.lock:
-            self.entries.clear()
-
 
 _perm_cache = _PermCache()
 
@@ -436,62 +285,66 @@ def _perm_plan(lib, x, y, p, ranges, flags):
 #  raw launches
 # ----------------------------------------------------------------------------------------------
 
-def softmin_fwd_raw(x, y, h, eps, p=2, ranges=None, flags=0):
-    """x (B,N,D), y (B,M,D) fp32|bf16 contiguous CUDA; h (B,M) fp32 -> (B,N) fp32.  The sorted p = 2 call reuses the permutations of
-    its clouds from call to call (:class:`_PermCache`)."""
+def _softmin_step(step, x, y, h, pot, prev, eps, damping, p, ranges, flags):
+    """The launch of the soft-min (``step`` False; pot = prev = None, damping = 1) and of the half-step: one body here as in the library,
+    where ``glhip_softmin_fwd`` is the step with those arguments (``softmin_step`` of csrc/glhip_api.hip).  Each keeps the entry point
+    of its name — ``glhip_last_error`` texts carry it — except that the sorted p = 2 call of either goes through
+    ``glhip_sinkhorn_step_perm`` and reuses the permutations of its clouds from call to call (:class:`_PermCache`)."""
     lib = load_library()
     B, N, D = x.shape
     M = y.shape[1]
-    if is_f64(x):
-        out = torch.empty((B, N), dtype=torch.float64, device=x.device)
-        with torch.cuda.device(x.device):
-            rc = lib.glhip_softmin_fwd_f64(x.data_ptr(), y.data_ptr(), h.data_ptr(), out.data_ptr(), B, N, M, D, float(eps), int(p),
-                                           *_range_args(ranges, B), _stream(x))
-        _check(rc, lib)
-        return out
-    out = torch.empty((B, N), dtype=torch.float32, device=x.device)
+    f64 = is_f64(x)
+    out = torch.empty((B, N), dtype=torch.float64 if f64 else torch.float32, device=x.device)
+    perm = None
     with torch.cuda.device(x.device):
-        ws, ws_args = _workspace(lib, x, B, N, M, D, ranges)
-        perm = _perm_plan(lib, x, y, p, ranges, flags)
-        if perm is None:
-            rc = lib.glhip_softmin_fwd(x.data_ptr(), y.data_ptr(), h.data_ptr(), out.data_ptr(), B, N, M, D,
-                                       float(eps), int(p), _dtype_code(x), *_range_args(ranges, B), *ws_args,
-                                       _range_flags(flags, ranges), _stream(x))
-        else:      # (glhip_softmin_fwd is the step with pot = prev = NULL and damping = 1: one body in the library)
-            rc = lib.glhip_sinkhorn_step_perm(x.data_ptr(), y.data_ptr(), h.data_ptr(), None, None, out.data_ptr(), B, N, M, D,
-                                              float(eps), 1.0, int(p), _dtype_code(x), *_range_args(ranges, B), *ws_args,
-                                              _range_flags(flags, ranges), _stream(x), *perm[0])
+        if f64:      # every array double (glhip_*_f64): no dtype code, no workspace, no flags, no permutations
+            entry = lib.glhip_sinkhorn_step_f64 if step else lib.glhip_softmin_fwd_f64
+            tail = (*_range_args(ranges, B), _stream(x))
+        else:
+            ws, ws_args = _workspace(lib, x, B, N, M, D, ranges)
+            perm = _perm_plan(lib, x, y, p, ranges, flags)
+            entry = lib.glhip_sinkhorn_step_perm if perm is not None else lib.glhip_sinkhorn_step if step else lib.glhip_softmin_fwd
+            tail = (_dtype_code(x), *_range_args(ranges, B), *ws_args, _range_flags(flags, ranges), _stream(x),
+                    *(() if perm is None else perm[0]))
+        if step or perm is not None:
+            rc = entry(x.data_ptr(), y.data_ptr(), h.data_ptr(), _ptr(pot), _ptr(prev), out.data_ptr(), B, N, M, D,
+                       float(eps), float(damping), int(p), *tail)
+        else:
+            rc = entry(x.data_ptr(), y.data_ptr(), h.data_ptr(), out.data_ptr(), B, N, M, D, float(eps), int(p), *tail)
     _check(rc, lib)
     if perm is not None:
         perm[1]()
     return out
 
 
+def softmin_fwd_raw(x, y, h, eps, p=2, ranges=None, flags=0):
+    """x (B,N,D), y (B,M,D) fp32|bf16|fp64 contiguous CUDA; h (B,M) fp32 (fp64 next to fp64 clouds) -> (B,N) of h's dtype."""
+    return _softmin_step(False, x, y, h, None, None, eps, 1.0, p, ranges, flags)
+
+
 def sinkhorn_step_raw(x, y, logw, pot, prev, eps, damping, p=2, ranges=None, flags=0):
     """Fused half-step: (prev + damping * softmin(eps, C(x,y), logw + pot/eps)) / 2, or damping * softmin(...) if prev is None."""
+    return _softmin_step(True, x, y, logw, pot, prev, eps, damping, p, ranges, flags)
+
+
+def _launch(stem, x, ranges, out_shape, head, dims, scalars, flags, routes=None, workspace=True):
+    """One reduction with a float32 / bfloat16 entry point ``<stem>`` and a float64 one ``<stem>_f64`` (softmin_bwd_x, kernel_conv_fwd,
+    kernel_conv_bwd_x).  Both take ``head`` (what stands before the output), the output, ``dims`` = (B, N, M, D), ``scalars``, the ranges
+    and the stream; ``<stem>`` alone takes the dtype code before the ranges and the workspace and ``flags`` after them.  That workspace is
+    :func:`_workspace`'s, or with ``routes`` (a gradient launch) :func:`_grad_workspace`'s.  Returns the output, allocated here in the
+    clouds' accumulation dtype."""
     lib = load_library()
-    B, N, D = x.shape
-    M = y.shape[1]
-    if is_f64(x):      # every array double (glhip_sinkhorn_step_f64): no workspace, no flags
-        out = torch.empty((B, N), dtype=torch.float64, device=x.device)
-        with torch.cuda.device(x.device):
-            rc = lib.glhip_sinkhorn_step_f64(x.data_ptr(), y.data_ptr(), logw.data_ptr(), None if pot is None else pot.data_ptr(),
-                                             None if prev is None else prev.data_ptr(), out.data_ptr(), B, N, M, D, float(eps),
-                                             float(damping), int(p), *_range_args(ranges, B), _stream(x))
-        _check(rc, lib)
-        return out
-    out = torch.empty((B, N), dtype=torch.float32, device=x.device)
+    f64 = is_f64(x)
+    out = torch.empty(out_shape, dtype=torch.float64 if f64 else torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        ws, ws_args = _workspace(lib, x, B, N, M, D, ranges)
-        perm = _perm_plan(lib, x, y, p, ranges, flags)
-        step = lib.glhip_sinkhorn_step if perm is None else lib.glhip_sinkhorn_step_perm
-        rc = step(x.data_ptr(), y.data_ptr(), logw.data_ptr(),
-                  None if pot is None else pot.data_ptr(), None if prev is None else prev.data_ptr(),
-                  out.data_ptr(), B, N, M, D, float(eps), float(damping), int(p), _dtype_code(x),
-                  *_range_args(ranges, B), *ws_args, _range_flags(flags, ranges), _stream(x), *([] if perm is None else perm[0]))
+        if f64:
+            rc = getattr(lib, stem + "_f64")(*head, out.data_ptr(), *dims, *scalars, *_range_args(ranges, dims[0]), _stream(x))
+        else:
+            ws, ws_args = (_workspace(lib, x, *dims, ranges) if routes is None
+                           else _grad_workspace(lib, x, *dims, ranges, flags, workspace, routes))
+            rc = getattr(lib, stem)(*head, out.data_ptr(), *dims, *scalars, _dtype_code(x), *_range_args(ranges, dims[0]), *ws_args,
+                                    int(flags), _stream(x))
     _check(rc, lib)
-    if perm is not None:
-        perm[1]()
     return out
 
 
@@ -505,16 +358,13 @@ def sinkhorn_iter4_raw(x, y, a_log, b_log, pots, eps, damping, debias=True, flag
     M = y.shape[1]
     first = pots is None
     outs = [torch.empty((B, n), dtype=torch.float32, device=x.device) for n in ((N, M, N, M) if debias else (N, M))]
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     old = [None] * 4 if first else list(pots) + [None] * (4 - len(pots))
     new = outs + [None] * (4 - len(outs))
     with torch.cuda.device(x.device):
-        L = max(N, M)
-        nbytes = 4 * int(lib.glhip_workspace_bytes(B, L, L, D, 0))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+        ws, ws_args = _iter4_scratch(lib, x, B, max(N, M), max(N, M), D)
         rc = lib.glhip_sinkhorn_iter4(x.data_ptr(), y.data_ptr(), a_log.data_ptr(), b_log.data_ptr(),
-                                      *[ptr(t) for t in old], *[ptr(t) for t in new], B, N, M, D, float(eps), float(damping),
-                                      int(p), _dtype_code(x), int(first), ptr(ws), nbytes, int(flags), _stream(x))
+                                      *[_ptr(t) for t in old], *[_ptr(t) for t in new], B, N, M, D, float(eps), float(damping),
+                                      int(p), _dtype_code(x), int(first), *ws_args, int(flags), _stream(x))
     _check(rc, lib)
     return tuple(outs)
 
@@ -531,18 +381,20 @@ def sinkhorn_extrapolate4_raw(x, y, xc, yc, a_log_c, b_log_c, pots, eps, damping
     old = [t.data_ptr() for t in pots] + [None] * (4 - len(pots))
     new = [t.data_ptr() for t in outs] + [None] * (4 - len(outs))
     with torch.cuda.device(x.device):
-        nbytes = 4 * int(lib.glhip_workspace_bytes(B, max(N, M), max(Nc, Mc), D, 0))     # rows: fine clouds, columns: coarse ones
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+        ws, ws_args = _iter4_scratch(lib, x, B, max(N, M), max(Nc, Mc), D)     # rows: fine clouds, columns: coarse ones
         rc = lib.glhip_sinkhorn_extrapolate4(x.data_ptr(), y.data_ptr(), xc.data_ptr(), yc.data_ptr(), a_log_c.data_ptr(), b_log_c.data_ptr(),
                                              *old, *new, B, N, M, Nc, Mc, D, float(eps), float(damping), int(p), _dtype_code(x),
-                                             None if ws is None else ws.data_ptr(), nbytes, int(flags), _stream(x))
+                                             *ws_args, int(flags), _stream(x))
     _check(rc, lib)
     return tuple(outs)
 
 
-def _route_predicate(name, args, shown):
-    """One of the library's route predicates (host arithmetic, no GPU): 1 / 0, or ``ValueError`` for arguments the entry point rejects."""
+def _route_predicate(name, args, shown, no_kernel=None):
+    """One of the library's route and family predicates (host arithmetic, no GPU): its answer >= 0, or ``ValueError`` for arguments the
+    entry point rejects.  ``no_kernel``: the text of the ``NotImplementedError`` for -2 where the predicate tells that apart."""
     r = int(getattr(load_library(), name)(*(int(a) for a in args)))
+    if r == -2 and no_kernel is not None:
+        raise NotImplementedError(no_kernel)
     if r < 0:
         raise ValueError(f"{name}: bad argument ({shown})")
     return r
@@ -578,37 +430,21 @@ def _grad_workspace(lib, x, B, N, M, D, ranges, flags, workspace, routes):
     n_ranges = 0 if ranges is None else int(ranges.ranges_i.shape[0])
     for uses, args, sizing in routes:
         if getattr(lib, uses)(*args, _dtype_code(x), int(flags), n_ranges) == 1:
-            nbytes = int(getattr(lib, sizing)(B, N, M, D, int(flags))) if workspace else 0
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
-            return ws, (None if ws is None else ws.data_ptr(), nbytes)
+            return _scratch(int(getattr(lib, sizing)(B, N, M, D, int(flags))) if workspace else 0, x.device)
     if workspace:
         return _workspace(lib, x, B, N, M, D, ranges)
-    return None, (None, 0)
+    return _scratch(0, x.device)
 
 
 def softmin_bwd_x_raw(x, y, h, out, grad_out, eps, p=2, ranges=None, flags=0, workspace=True):
     """``workspace=False``: launch without one (no column splits) — tests only."""
-    lib = load_library()
     B, N, D = x.shape
     M = y.shape[1]
-    if is_f64(x):
-        gx = torch.empty((B, N, D), dtype=torch.float64, device=x.device)
-        with torch.cuda.device(x.device):
-            rc = lib.glhip_softmin_bwd_x_f64(x.data_ptr(), y.data_ptr(), h.data_ptr(), out.data_ptr(), grad_out.data_ptr(), gx.data_ptr(),
-                                             B, N, M, D, float(eps), int(p), *_range_args(ranges, B), _stream(x))
-        _check(rc, lib)
-        return gx
-    gx = torch.empty((B, N, D), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        routes = [("glhip_softmin_bwd_x_uses_plan", (B, N, M, D, int(p)), "glhip_softmin_bwd_x_workspace_bytes")]
-        if int(p) == 1:
-            routes.append(("glhip_dist_grad_uses_xk", (DIST_GRAD_OPS["softmin_p1"], B, N, M, D), "glhip_dist_grad_workspace_bytes"))
-        ws, ws_args = _grad_workspace(lib, x, B, N, M, D, ranges, flags, workspace, routes)
-        rc = lib.glhip_softmin_bwd_x(x.data_ptr(), y.data_ptr(), h.data_ptr(), out.data_ptr(), grad_out.data_ptr(),
-                                     gx.data_ptr(), B, N, M, D, float(eps), int(p), _dtype_code(x),
-                                     *_range_args(ranges, B), *ws_args, int(flags), _stream(x))
-    _check(rc, lib)
-    return gx
+    routes = [("glhip_softmin_bwd_x_uses_plan", (B, N, M, D, int(p)), "glhip_softmin_bwd_x_workspace_bytes")]
+    if int(p) == 1:
+        routes.append(("glhip_dist_grad_uses_xk", (DIST_GRAD_OPS["softmin_p1"], B, N, M, D), "glhip_dist_grad_workspace_bytes"))
+    return _launch("glhip_softmin_bwd_x", x, ranges, (B, N, D), (x.data_ptr(), y.data_ptr(), h.data_ptr(), out.data_ptr(), grad_out.data_ptr()),
+                   (B, N, M, D), (float(eps), int(p)), flags, routes, workspace)
 
 
 def _plan_apply_call(entry, x, y, h, fwd, feat, eps, flags, want_mass, p, ranges, workspace):
@@ -624,11 +460,10 @@ def _plan_apply_call(entry, x, y, h, fwd, feat, eps, flags, want_mass, p, ranges
     out = torch.empty((B, N, V), dtype=torch.float32, device=x.device)
     mass = torch.empty((B, N), dtype=torch.float32, device=x.device) if want_mass else None
     with torch.cuda.device(x.device):
-        nbytes = int(getattr(lib, entry + "_workspace_bytes")(B, N, M, D, V)) if workspace else 0
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+        ws, ws_args = _scratch(int(getattr(lib, entry + "_workspace_bytes")(B, N, M, D, V)) if workspace else 0, x.device)
         rc = getattr(lib, entry)(x.data_ptr(), y.data_ptr(), h.data_ptr(), fwd.data_ptr(), feat.data_ptr(), out.data_ptr(),
-                                 None if mass is None else mass.data_ptr(), B, N, M, D, V, float(eps), int(p), _dtype_code(x),
-                                 *_range_args(ranges, B), None if ws is None else ws.data_ptr(), nbytes, int(flags), _stream(x))
+                                 _ptr(mass), B, N, M, D, V, float(eps), int(p), _dtype_code(x),
+                                 *_range_args(ranges, B), *ws_args, int(flags), _stream(x))
     _check(rc, lib)
     return (out, mass) if want_mass else out
 
@@ -665,24 +500,10 @@ def softmin_fwd_grad_raw(x, y, h, guess, margin, eps, ranges=None, flags=0):
 
 
 def kernel_conv_fwd_raw(kind, x, y, v, blur, ranges=None, flags=0):
-    lib = load_library()
     B, N, D = x.shape
     M = y.shape[1]
-    if is_f64(x):
-        out = torch.empty((B, N), dtype=torch.float64, device=x.device)
-        with torch.cuda.device(x.device):
-            rc = lib.glhip_kernel_conv_fwd_f64(int(kind), x.data_ptr(), y.data_ptr(), v.data_ptr(), out.data_ptr(), B, N, M, D, float(blur),
-                                               *_range_args(ranges, B), _stream(x))
-        _check(rc, lib)
-        return out
-    out = torch.empty((B, N), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        ws, ws_args = _workspace(lib, x, B, N, M, D, ranges)
-        rc = lib.glhip_kernel_conv_fwd(int(kind), x.data_ptr(), y.data_ptr(), v.data_ptr(), out.data_ptr(), B, N, M, D,
-                                       float(blur), _dtype_code(x), *_range_args(ranges, B), *ws_args, int(flags),
-                                       _stream(x))
-    _check(rc, lib)
-    return out
+    return _launch("glhip_kernel_conv_fwd", x, ranges, (B, N), (int(kind), x.data_ptr(), y.data_ptr(), v.data_ptr()),
+                   (B, N, M, D), (float(blur),), flags)
 
 
 def _conv_grad_routes(kind, B, N, M, D):
@@ -696,24 +517,10 @@ def _conv_grad_routes(kind, B, N, M, D):
 
 def kernel_conv_bwd_x_raw(kind, x, y, v, g, blur, ranges=None, flags=0, workspace=True):
     """``workspace=False``: launch without one (no column splits) — tests only."""
-    lib = load_library()
     B, N, D = x.shape
     M = y.shape[1]
-    if is_f64(x):
-        gx = torch.empty((B, N, D), dtype=torch.float64, device=x.device)
-        with torch.cuda.device(x.device):
-            rc = lib.glhip_kernel_conv_bwd_x_f64(int(kind), x.data_ptr(), y.data_ptr(), v.data_ptr(), g.data_ptr(), gx.data_ptr(), B, N, M, D,
-                                                 float(blur), *_range_args(ranges, B), _stream(x))
-        _check(rc, lib)
-        return gx
-    gx = torch.empty((B, N, D), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        ws, ws_args = _grad_workspace(lib, x, B, N, M, D, ranges, flags, workspace, _conv_grad_routes(kind, B, N, M, D))
-        rc = lib.glhip_kernel_conv_bwd_x(int(kind), x.data_ptr(), y.data_ptr(), v.data_ptr(), g.data_ptr(),
-                                         gx.data_ptr(), B, N, M, D, float(blur), _dtype_code(x),
-                                         *_range_args(ranges, B), *ws_args, int(flags), _stream(x))
-    _check(rc, lib)
-    return gx
+    return _launch("glhip_kernel_conv_bwd_x", x, ranges, (B, N, D), (int(kind), x.data_ptr(), y.data_ptr(), v.data_ptr(), g.data_ptr()),
+                   (B, N, M, D), (float(blur),), flags, _conv_grad_routes(kind, B, N, M, D), workspace)
 
 
 def kernel_conv_fwd_grad_raw(kind, x, y, v, blur, ranges=None, flags=0, workspace=True):
@@ -777,11 +584,10 @@ def grid_cluster_raw(x, weights, voxel, pre_div=1.0, gather=True, defer=False):
         w_c = torch.empty(N, dtype=torch.float32, device=dev)
         count = torch.empty(8, dtype=torch.int32, device=dev)        # {C, overflow, qmin[3], qmax[3]}
         nbytes = int(lib.glhip_cluster_workspace_bytes(N, D))
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        rc = lib.glhip_grid_cluster(x.data_ptr(), ptr(weights), N, D, _dtype_code(x), float(pre_div), float(voxel), perm.data_ptr(),
-                                    ptr(x_sorted), ptr(w_sorted), ranges.data_ptr(), cents.data_ptr(), w_c.data_ptr(),
-                                    count.data_ptr(), ws.data_ptr(), nbytes, _stream(x))
+        ws, (ws_ptr, _) = _scratch(max(nbytes, 1), dev)
+        rc = lib.glhip_grid_cluster(x.data_ptr(), _ptr(weights), N, D, _dtype_code(x), float(pre_div), float(voxel), perm.data_ptr(),
+                                    _ptr(x_sorted), _ptr(w_sorted), ranges.data_ptr(), cents.data_ptr(), w_c.data_ptr(),
+                                    count.data_ptr(), ws_ptr, nbytes, _stream(x))
     _check(rc, lib)
 
     def finish(values):
@@ -829,13 +635,12 @@ def block_ranges_raw(kind, rows, cols, f, g, ranges_rows, ranges_cols, thr, p=2,
     Cr, D = rows.shape
     Cc = cols.shape[0]
     dev = rows.device
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     with torch.cuda.device(dev):
         # symmetric (rows is cols, f is g: the caller's word): the transposed pattern is the same arrays — one orientation is built
         symmetric = bool(symmetric) and Cr == Cc
         slices_r = torch.empty(Cr, dtype=torch.int32, device=dev)
         slices_c = None if symmetric else torch.empty(Cc, dtype=torch.int32, device=dev)
-        head = (int(kind), rows.data_ptr(), cols.data_ptr(), ptr(f), ptr(g), Cr, Cc, D, int(p), float(thr),
+        head = (int(kind), rows.data_ptr(), cols.data_ptr(), _ptr(f), _ptr(g), Cr, Cc, D, int(p), float(thr),
                 ranges_rows.data_ptr(), ranges_cols.data_ptr())
         cap = max(Cr * ((Cc + 1) // 2), Cc * ((Cr + 1) // 2), 1)
         if cap > _worst_case_intervals(dev):
@@ -852,7 +657,7 @@ def block_ranges_raw(kind, rows, cols, f, g, ranges_rows, ranges_cols, thr, p=2,
         red_c = torch.empty((cap, 2), dtype=torch.int32, device=dev)
         red_r = None if symmetric else torch.empty((cap, 2), dtype=torch.int32, device=dev)
         status = torch.zeros(1, dtype=torch.int32, device=dev)          # set by the kernel if an interval did not fit `cap`
-        rc = lib.glhip_block_ranges(*head, slices_r.data_ptr(), red_c.data_ptr(), ptr(slices_c), ptr(red_r), cap,
+        rc = lib.glhip_block_ranges(*head, slices_r.data_ptr(), red_c.data_ptr(), _ptr(slices_c), _ptr(red_r), cap,
                                     status.data_ptr(), _stream(rows))
     _check(rc, lib)
     # worst-case buffers cannot overflow; counted ones could only if the two passes disagreed: the host is already in step with
@@ -917,9 +722,8 @@ def _cost_raw(a, f_ba, f_aa, b, g_ab, g_bb, B, N, M):
     c = lambda t: None if t is None else t.detach().contiguous()  # noqa: E731
     a, f_ba, f_aa, b, g_ab, g_bb = (c(t) for t in (a, f_ba, f_aa, b, g_ab, g_bb))
     out = torch.empty(B, dtype=torch.float32, device=f_ba.device)
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     with torch.cuda.device(f_ba.device):
-        _check(lib.glhip_sinkhorn_cost(ptr(a), ptr(f_ba), ptr(f_aa), ptr(b), ptr(g_ab), ptr(g_bb), out.data_ptr(), B, N, M,
+        _check(lib.glhip_sinkhorn_cost(_ptr(a), _ptr(f_ba), _ptr(f_aa), _ptr(b), _ptr(g_ab), _ptr(g_bb), out.data_ptr(), B, N, M,
                                        int(a.numel() == B * N), int(b.numel() == B * M), _stream(f_ba)), lib)
     return out
 
@@ -962,10 +766,9 @@ def kept_pairs_raw(kind, rows, cols, f, g, ranges_rows, ranges_cols, thr, p=2, d
     built.  ``defer``: the (3,) int64 device tensor instead, for a shared :func:`read_back`."""
     lib = load_library()
     Cr, D = rows.shape
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     with torch.cuda.device(rows.device):
         kept = torch.empty(3, dtype=torch.int64, device=rows.device)
-        _check(lib.glhip_block_ranges_kept_pairs(int(kind), rows.data_ptr(), cols.data_ptr(), ptr(f), ptr(g), Cr, cols.shape[0], D, int(p),
+        _check(lib.glhip_block_ranges_kept_pairs(int(kind), rows.data_ptr(), cols.data_ptr(), _ptr(f), _ptr(g), Cr, cols.shape[0], D, int(p),
                                                  float(thr), ranges_rows.data_ptr(), ranges_cols.data_ptr(), kept.data_ptr(),
                                                  _stream(rows)), lib)
     return kept if defer else tuple(read_back(kept)[0])
@@ -1136,14 +939,8 @@ class _Softmin(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, h, eps, p, ranges, flags):
-        xb, yb, hb, batched = _as_batched(_points(x, "x", True), _points(y, "y", True), h.detach().contiguous())
-        if yb.dtype != xb.dtype:
-            yb = yb.to(xb.dtype)
-        if p == 1 and not is_f64(xb) and not (flags & (FLAG_NO_MFMA | FLAG_DIRECT)):
-            if ranges is not None and _dist_on_mfma:
-                flags |= FLAG_MFMA_DIST            # multiscale: the row blocks are voxel clusters already
-            elif not _dist_on_mfma:
-                flags |= FLAG_NO_SORT              # (big dense launches sort themselves inside the library unless told not to)
+        xb, yb, hb, batched = _clouds(x, y, h.detach().contiguous(), allow_f64=True)
+        flags = _dist_flags(flags, ranges, p == 1 and not is_f64(xb))
         out = softmin_fwd_raw(xb, yb, hb, eps, p, ranges, flags)
         ctx.save_for_backward(x, yb, hb, out)         # (x itself: under create_graph the backward pass is differentiated through it)
         ctx.cfg = (eps, p, ranges, flags, xb.shape)
@@ -1168,9 +965,7 @@ class _SoftminValueGrad(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, h, eps, guess, margin, ranges, flags):
-        xb, yb, hb, batched = _as_batched(_points(x, "x"), _points(y, "y"), _f32(h))
-        if yb.dtype != xb.dtype:
-            yb = yb.to(xb.dtype)
+        xb, yb, hb, batched = _clouds(x, y, _f32(h))
         out, unit = softmin_fwd_grad_raw(xb, yb, hb, _f32(guess).reshape(hb.shape[0], -1), margin, eps, ranges, flags)
         ctx.unit, ctx.cfg = unit, (x.shape, x.dtype, eps, ranges, flags)
         ctx.save_for_backward(x, yb, hb, out)         # for a backward pass that is differentiated again (create_graph=True)
@@ -1215,13 +1010,11 @@ def sinkhorn_iter4(eps, x, y, a_log, b_log, pots, damping, debias=True, flags=0,
 
     x: (N,D)|(B,N,D), y: (M,D)|(B,M,D); a_log: (N,)|(1,N)|(B,N), b_log likewise; ``pots`` None (initial potentials)
     or the old ``(f_ba, g_ab, f_aa, g_bb)`` / ``(f_ba, g_ab)``.  Returns the new potentials, shaped like a_log / b_log."""
-    xb, yb, bl, _ = _as_batched(_points(x.detach(), "x"), _points(y.detach(), "y"), _f32(b_log))
-    if yb.dtype != xb.dtype:
-        yb = yb.to(xb.dtype)
+    xb, yb, bl, _ = _clouds(x, y, _f32(b_log), detach=True)
     B = xb.shape[0]
     al = _f32(a_log).reshape(B, -1)
     old = None if pots is None else tuple(_f32(t).reshape(B, -1) for t in pots)
-    new = sinkhorn_iter4_raw(xb, yb, al, bl, old, eps, damping, debias, int(flags) | (ENV_FLAGS & (FLAG_NO_SPLIT | FLAG_F16X2)), p)
+    new = sinkhorn_iter4_raw(xb, yb, al, bl, old, eps, damping, debias, int(flags) | (ENV_FLAGS & _ITER4_ENV_MASK), p)
     shapes = (a_log.shape, b_log.shape, a_log.shape, b_log.shape)
     return tuple(t.view(sh) for t, sh in zip(new, shapes))
 
@@ -1238,7 +1031,7 @@ def sinkhorn_extrapolate4(eps, x, y, xc, yc, a_log_c, b_log_c, pots, damping, fl
     B = xb.shape[0]
     row = lambda t: _f32(t).reshape(B, -1)      # noqa: E731
     outs = sinkhorn_extrapolate4_raw(xb, yb, xcb, ycb, row(a_log_c), row(b_log_c), tuple(row(t) for t in pots), eps, damping,
-                                     int(flags) | (ENV_FLAGS & (FLAG_NO_SPLIT | FLAG_F16X2)), p)
+                                     int(flags) | (ENV_FLAGS & _ITER4_ENV_MASK), p)
     return outs if batched else tuple(t.view(-1) for t in outs)
 
 
@@ -1251,24 +1044,20 @@ class Iter4Plan:
     def __init__(self, x, y, a_log, b_log, debias=True, flags=0, p=2):
         self.lib = load_library()
         self.p = int(p)
-        xb, yb, bl, _ = _as_batched(_points(x.detach(), "x"), _points(y.detach(), "y"), _f32(b_log))
-        if yb.dtype != xb.dtype:
-            yb = yb.to(xb.dtype)
+        xb, yb, bl, _ = _clouds(x, y, _f32(b_log), detach=True)
         self.x, self.y, self.b_log = xb, yb, bl
         B, N, D = xb.shape
         M = yb.shape[1]
         self.a_log = _f32(a_log).reshape(B, -1)
         self.dims = (B, N, M, D)
         self.debias = debias
-        self.flags = int(flags) | (ENV_FLAGS & (FLAG_NO_SPLIT | FLAG_F16X2))
+        self.flags = int(flags) | (ENV_FLAGS & _ITER4_ENV_MASK)
         self.shapes = (a_log.shape, b_log.shape, a_log.shape, b_log.shape)[: 4 if debias else 2]
         sizes = (N, M, N, M)[: 4 if debias else 2]
         dev = xb.device
         self.device = dev
         with torch.cuda.device(dev):
-            L = max(N, M)
-            self.nbytes = 4 * int(self.lib.glhip_workspace_bytes(B, L, L, D, 0))
-            self.ws = torch.empty(self.nbytes, dtype=torch.uint8, device=dev) if self.nbytes else None
+            self.ws, self.ws_args = _iter4_scratch(self.lib, xb, B, max(N, M), max(N, M), D)
             self.sets = []
             for _ in range(2):
                 flat = torch.empty(B * sum(sizes), dtype=torch.float32, device=dev)
@@ -1303,8 +1092,7 @@ class Iter4Plan:
         new = tuple(t.data_ptr() for t in outs) + (None,) * (4 - len(outs))
         stream = torch.cuda.current_stream(self.device).cuda_stream
         rc = self.lib.glhip_sinkhorn_iter4(*self.fixed, *old, *new, B, N, M, D, float(eps), float(damping), self.p, self.dtype,
-                                           1 if pots is None else (2 if last else 0), None if self.ws is None else self.ws.data_ptr(), self.nbytes,
-                                           self.flags | self.extra_flags, stream)
+                                           1 if pots is None else (2 if last else 0), *self.ws_args, self.flags | self.extra_flags, stream)
         _check(rc, self.lib)
         return shaped
 
@@ -1326,7 +1114,7 @@ class Iter4Plan:
             flags |= FLAG_F16X2
         rc = self.lib.glhip_sinkhorn_anneal(*self.fixed, sets[0], sets[1], B, N, M, D, farr(*[float(e) for e in eps_list]),
                                             farr(*[float(d) for d in dampings]), n, self.p, self.dtype,
-                                            None if self.ws is None else self.ws.data_ptr(), self.nbytes, flags, min_eps, stream)
+                                            *self.ws_args, flags, min_eps, stream)
         _check(rc, self.lib)
         self.turn = (n + 1) % 2          # the set the final potentials are NOT in
         return self.shaped[n % 2], self.shaped[(n + 1) % 2]
@@ -1407,14 +1195,10 @@ def plan_apply_nd_family(B, N, M, D, V, p=2, dtype=torch.float32, flags=0, n_ran
     """The kernel family (FAMILY_XD for D <= 16, FAMILY_XK for 17 <= D <= PLAN_MAX_DIM) that ``glhip_plan_apply_nd`` selects: the
     predicate the launch itself evaluates, host arithmetic only.  Raises ``NotImplementedError`` for valid requests without a
     kernel and ``ValueError`` for what the entry point rejects."""
-    lib = load_library()
-    code = {torch.float32: 0, torch.bfloat16: 1}.get(dtype, -1)
-    fam = int(lib.glhip_plan_apply_nd_family(int(B), int(N), int(M), int(D), int(V), int(p), code, int(flags), int(n_ranges)))
-    if fam == -2:
-        raise NotImplementedError(f"glhip_plan_apply_nd: no kernel for p = {p}, D = {D}, n_ranges = {n_ranges}")
-    if fam < 0:
-        raise ValueError(f"glhip_plan_apply_nd_family: bad arguments {(B, N, M, D, V, p, dtype, flags, n_ranges)}")
-    return fam
+    code = {torch.float32: F32, torch.bfloat16: BF16}.get(dtype, -1)
+    return _route_predicate("glhip_plan_apply_nd_family", (B, N, M, D, V, p, code, flags, n_ranges),
+                            f"B {B}, N {N}, M {M}, D {D}, V {V}, p {p}, dtype {dtype}, flags {flags}, n_ranges {n_ranges}",
+                            no_kernel=f"glhip_plan_apply_nd: no kernel for p = {p}, D = {D}, n_ranges = {n_ranges}")
 
 
 def _plan_apply(name, raw, max_dim, eps, x, y, h, feat, fwd, flags, p, ranges):
@@ -1430,9 +1214,7 @@ def _plan_apply(name, raw, max_dim, eps, x, y, h, feat, fwd, flags, p, ranges):
     if tuple(feat.shape[:len(lead)]) != lead or feat.dim() not in (len(lead), len(lead) + 1):
         raise ValueError(f"geomloss_amd.hip.{name}: expected features of shape {lead} or {lead + ('V',)}, got {tuple(feat.shape)}")
     with torch.no_grad():
-        xb, yb, hb, _ = _as_batched(_points(x.detach(), "x"), _points(y.detach(), "y"), _f32(h))
-        if yb.dtype != xb.dtype:
-            yb = yb.to(xb.dtype)
+        xb, yb, hb, _ = _clouds(x, y, _f32(h), detach=True)
         B, M = yb.shape[0], yb.shape[1]
         fb = _f32(feat).to(xb.device).reshape(B, M, -1)
         flags = int(flags) | ENV_FLAGS
@@ -1502,19 +1284,14 @@ def half_step_applies(D, p=2, flags=0, sparse=False):
 def softmin_fwd_family(B, N, M, D, p=2, dtype=F32, flags=0, n_ranges=0):
     """The kernel family (FAMILY_*) ``glhip_softmin_fwd`` / ``glhip_sinkhorn_step`` select for a launch of this shape: the library's own
     predicate (``glhip_softmin_fwd_family``), host arithmetic only — no device is touched."""
-    fam = load_library().glhip_softmin_fwd_family(int(B), int(N), int(M), int(D), int(p), int(dtype), int(flags), int(n_ranges))
-    if fam < 0:
-        raise ValueError(f"glhip_softmin_fwd_family: bad arguments B={B} N={N} M={M} D={D} p={p} dtype={dtype} n_ranges={n_ranges}")
-    return fam
+    return _route_predicate("glhip_softmin_fwd_family", (B, N, M, D, p, dtype, flags, n_ranges),
+                            f"B {B}, N {N}, M {M}, D {D}, p {p}, dtype {dtype}, n_ranges {n_ranges}")
 
 
 def kernel_conv_fwd_family(kind, B, N, M, D, dtype=F32, flags=0, n_ranges=0):
     """The same for the kernel products of ``glhip_kernel_conv_fwd`` (``glhip_kernel_conv_fwd_family``); ``kind``: a name or a code."""
-    fam = load_library().glhip_kernel_conv_fwd_family(int(KERNEL_KINDS.get(kind, kind)), int(B), int(N), int(M), int(D), int(dtype), int(flags),
-                                                      int(n_ranges))
-    if fam < 0:
-        raise ValueError(f"glhip_kernel_conv_fwd_family: bad arguments kind={kind} B={B} N={N} M={M} D={D} dtype={dtype} n_ranges={n_ranges}")
-    return fam
+    return _route_predicate("glhip_kernel_conv_fwd_family", (KERNEL_KINDS.get(kind, kind), B, N, M, D, dtype, flags, n_ranges),
+                            f"kind {kind}, B {B}, N {N}, M {M}, D {D}, dtype {dtype}, n_ranges {n_ranges}")
 
 
 def sinkhorn_step(eps, x, y, logw, pot, prev, damping, p=2, ranges=None, flags=0):
@@ -1525,30 +1302,22 @@ def sinkhorn_step(eps, x, y, logw, pot, prev, damping, p=2, ranges=None, flags=0
     x: (N,D)|(B,N,D), y: (M,D)|(B,M,D); logw, pot: (M,)|(B,M) (pot may be None); prev: (N,)|(B,N) or None.
     Returns fp32 (N,)|(B,N).  Used by the drivers inside the no-grad part of ``sinkhorn_loop``."""
     if is_f64(x) and p in (1, 2):      # float64 clouds: the fused double-precision half-step (any D, dense / batched / block-sparse)
-        xb, yb, lw, batched = _as_batched(_points(x.detach(), "x", allow_f64=True), _points(y.detach(), "y", allow_f64=True),
-                                          logw.detach().double().contiguous())
+        xb, yb, lw, batched = _clouds(x, y, logw.detach().double().contiguous(), allow_f64=True, detach=True)
         B = xb.shape[0]
         pt = None if pot is None else pot.detach().double().contiguous().reshape(B, -1)
         pv = None if prev is None else prev.detach().double().contiguous().reshape(B, -1)
-        out = sinkhorn_step_raw(xb, yb.double(), lw, pt, pv, eps, damping, p, ranges, 0)
+        out = sinkhorn_step_raw(xb, yb, lw, pt, pv, eps, damping, p, ranges, 0)
         return out if batched else out.view(-1)
     if not half_step_applies(x.shape[-1], p, flags, ranges is not None) or is_f64(x):
         with torch.no_grad():
             h = _vec(logw, x) if pot is None else _vec(logw, x) + _vec(pot, x).reshape(logw.shape) / eps
             ft = damping * softmin(eps, x.detach(), y.detach(), h, p=p, ranges=ranges, flags=flags)
             return ft if prev is None else 0.5 * (_vec(prev, x).reshape(ft.shape) + ft)
-    xb, yb, lw, batched = _as_batched(_points(x.detach(), "x"), _points(y.detach(), "y"), _f32(logw))
-    if yb.dtype != xb.dtype:
-        yb = yb.to(xb.dtype)
+    xb, yb, lw, batched = _clouds(x, y, _f32(logw), detach=True)
     B = xb.shape[0]
     pt = None if pot is None else _f32(pot).reshape(B, -1)
     pv = None if prev is None else _f32(prev).reshape(B, -1)
-    flags = int(flags) | ENV_FLAGS
-    if p == 1 and not (flags & (FLAG_NO_MFMA | FLAG_DIRECT)):
-        if ranges is not None and _dist_on_mfma:
-            flags |= FLAG_MFMA_DIST
-        elif not _dist_on_mfma:
-            flags |= FLAG_NO_SORT
+    flags = _dist_flags(int(flags) | ENV_FLAGS, ranges, p == 1)
     out = sinkhorn_step_raw(xb, yb, lw, pt, pv, eps, damping, p, ranges, flags)
     return out if batched else out.view(-1)
 
@@ -1595,9 +1364,7 @@ class _KernelConv(torch.autograd.Function):
     def product(kind, x, y, v, blur, ranges, flags, want_unit):
         """The launch behind forward: (xb, yb, vb, batched, out (B,N), unit (B,N,D) | None); unit_i = d out_i / d x_i when
         ``want_unit`` and a product-and-gradient kernel exists for this kind and dimension."""
-        xb, yb, vb, batched = _as_batched(_points(x, "x", True), _points(y, "y", True), v.detach().contiguous())
-        if yb.dtype != xb.dtype:
-            yb = yb.to(xb.dtype)
+        xb, yb, vb, batched = _clouds(x, y, v.detach().contiguous(), allow_f64=True)
         if is_f64(xb):      # double precision: the plain product kernel, no plans, no fused gradient
             return xb, yb, vb, batched, kernel_conv_fwd_raw(kind, xb, yb, vb, blur, ranges, flags), None
         # When x requires gradients, the product and its row gradient come out of ONE reduction: the gradient kernel
@@ -1612,12 +1379,7 @@ class _KernelConv(torch.autograd.Function):
         # laplacian / energy: squared distances from the matrix cores wherever the row blocks are spatially compact — the voxel
         # clusters of the multiscale backend as they are, large dense launches after the voxel sort the library does itself
         # (csrc/glhip_autosort.h) — for the product, the product + gradient and (GRAD_FAMILY) the companion products of a norm alike
-        fl = flags
-        if kind != GAUSSIAN and xb.shape[-1] <= 3 and not (flags & (FLAG_NO_MFMA | FLAG_DIRECT)):
-            if ranges is not None and _dist_on_mfma:
-                fl |= FLAG_MFMA_DIST
-            elif not _dist_on_mfma:
-                fl |= FLAG_NO_SORT
+        fl = _dist_flags(flags, ranges, kind != GAUSSIAN and xb.shape[-1] <= 3)
         rows = None
         X, Y, V, R = xb, yb, vb, ranges
         if fused or (flags & FLAG_GRAD_FAMILY):      # gaussian: the kernels with one centre per workgroup
@@ -1715,18 +1477,14 @@ def kernel_grad_fusion():
 
 def kernel_conv(kind, x, y, v, blur=0.05, ranges=None, flags=0):
     """Kernel-matrix x vector product on the GPU; ``kind`` is a name or a GLHIP_* code."""
-    kind = KERNEL_KINDS[kind] if isinstance(kind, str) else int(kind)
-    return _KernelConv.apply(kind, x, y, v, 1.0 if blur is None else float(blur), ranges, int(flags) | ENV_FLAGS,
-                             torch.is_grad_enabled() and x.requires_grad)
+    return _KernelConv.apply(_kind(kind), x, y, v, _blur(blur), ranges, int(flags) | ENV_FLAGS, torch.is_grad_enabled() and x.requires_grad)
 
 
 def kernel_conv_with_unit(kind, x, y, v, blur, want_unit, flags=0):
     """No autograd: ``(K v, d (K v)_i / d x_i | None)`` from one reduction where a product-and-gradient kernel exists (the building
     block of kernel_samples._UnionNorm); shapes follow x: (N,), (N,D) or (B,N), (B,N,D)."""
-    kind = KERNEL_KINDS[kind] if isinstance(kind, str) else int(kind)
     with torch.no_grad():
-        _, _, _, batched, out, unit = _KernelConv.product(kind, x, y, v, 1.0 if blur is None else float(blur), None, int(flags) | ENV_FLAGS,
-                                                          want_unit)
+        _, _, _, batched, out, unit = _KernelConv.product(_kind(kind), x, y, v, _blur(blur), None, int(flags) | ENV_FLAGS, want_unit)
     if not batched:
         out, unit = out.view(-1), (None if unit is None else unit.view(-1, unit.shape[-1]))
     return out, unit
@@ -1734,13 +1492,10 @@ def kernel_conv_with_unit(kind, x, y, v, blur, want_unit, flags=0):
 
 def kernel_conv_row_gradient(kind, x, y, v, g, blur, flags=0):
     """No autograd: d/dx of sum_i g_i (K v)_i as one gradient reduction (``glhip_kernel_conv_bwd_x``), shaped like x."""
-    kind = KERNEL_KINDS[kind] if isinstance(kind, str) else int(kind)
     with torch.no_grad():
-        xb, yb, vb, _ = _as_batched(_points(x, "x", True), _points(y, "y", True), v.detach().contiguous())
-        if yb.dtype != xb.dtype:
-            yb = yb.to(xb.dtype)
+        xb, yb, vb, _ = _clouds(x, y, v.detach().contiguous(), allow_f64=True)
         gb = _vec(g, xb).reshape(xb.shape[0], -1)
-        return _KernelConv._row_gradient(kind, xb, yb, vb, gb, 1.0 if blur is None else float(blur), None, int(flags) | ENV_FLAGS).reshape(x.shape)
+        return _KernelConv._row_gradient(_kind(kind), xb, yb, vb, gb, _blur(blur), None, int(flags) | ENV_FLAGS).reshape(x.shape)
 
 
 class _SoftminDense(torch.autograd.Function):
@@ -1810,9 +1565,7 @@ def cmin(x, y, g, p=2, ranges=None, flags=0):
     """Hard C-transform on the GPU: min_j [C(x_i, y_j) - g_j], C = |x-y|^2/2 (p = 2) or |x-y| (p = 1); not differentiable.
     x: (N,D)|(B,N,D), y: (M,D)|(B,M,D), g: (M,)|(B,M) -> (N,)|(B,N) fp32."""
     lib = load_library()
-    xb, yb, gb, batched = _as_batched(_points(x.detach(), "x"), _points(y.detach(), "y"), _f32(g))
-    if yb.dtype != xb.dtype:
-        yb = yb.to(xb.dtype)
+    xb, yb, gb, batched = _clouds(x, y, _f32(g), detach=True)
     B, N, D = xb.shape
     M = yb.shape[1]
     out = torch.empty((B, N), dtype=torch.float32, device=xb.device)
@@ -1828,10 +1581,8 @@ def argmin_supported(B, N, M, D, p=2, dtype=F32, n_ranges=0):
     """Whether ``glhip_argmin`` serves a launch of this shape (p = 2, dense, 1 <= D <= ARGMIN_MAX_DIM, fp32 / bf16 clouds): the
     predicate the launch itself evaluates (``glhip_argmin_supported``), host arithmetic only — no device is touched.  Raises
     ``ValueError`` for what the entry point rejects (negative sizes, D < 1, a bad p or dtype)."""
-    ok = int(load_library().glhip_argmin_supported(int(B), int(N), int(M), int(D), int(p), int(dtype), int(n_ranges)))
-    if ok < 0:
-        raise ValueError(f"glhip_argmin_supported: bad arguments B={B} N={N} M={M} D={D} p={p} dtype={dtype} n_ranges={n_ranges}")
-    return bool(ok)
+    return bool(_route_predicate("glhip_argmin_supported", (B, N, M, D, p, dtype, n_ranges),
+                                 f"B {B}, N {N}, M {M}, D {D}, p {p}, dtype {dtype}, n_ranges {n_ranges}"))
 
 
 def argmin(x, y, g=None, return_value=False, flags=0, p=2):
@@ -1849,14 +1600,11 @@ def argmin(x, y, g=None, return_value=False, flags=0, p=2):
         raise NotImplementedError(f"geomloss_amd.hip.argmin: only p = 2, D <= {ARGMIN_MAX_DIM} (got p = {p}, D = {D})")
     lib = load_library()
     with torch.no_grad():
-        xp, yp = _points(x.detach(), "x"), _points(y.detach(), "y")
-        if g is not None and g.numel() != yp.numel() // max(D, 1):
+        # (g may be None or empty: a placeholder goes with the clouds, g is checked against them and reshaped below)
+        xb, yb, _, batched = _clouds(x, y, torch.empty(x.shape[0] if x.dim() == 3 else 1, dtype=torch.float32, device=x.device), detach=True)
+        if g is not None and g.numel() != yb.numel() // max(D, 1):
             raise ValueError(f"geomloss_amd.hip.argmin: expected one dual value per column, {tuple(y.shape[:-1])}, got {tuple(g.shape)}")
-        gv = _f32(g).to(xp.device) if g is not None else torch.empty(yp.shape[:-1], dtype=torch.float32, device=xp.device)
-        xb, yb, _, batched = _as_batched(xp, yp, gv.new_empty(xp.shape[0] if xp.dim() == 3 else 1))      # (g may be empty: reshaped below)
-        gb = gv.reshape(yb.shape[:2])
-        if yb.dtype != xb.dtype:
-            yb = yb.to(xb.dtype)
+        gb = None if g is None else _f32(g).to(xb.device).reshape(yb.shape[:2])
         if yb.shape[0] != xb.shape[0] or yb.shape[2] != D:
             raise ValueError(f"geomloss_amd.hip.argmin: clouds of shapes {tuple(x.shape)} and {tuple(y.shape)} do not go together")
         B, N, _ = xb.shape
@@ -1864,11 +1612,9 @@ def argmin(x, y, g=None, return_value=False, flags=0, p=2):
         index = torch.empty((B, N), dtype=torch.int32, device=xb.device)
         value = torch.empty((B, N), dtype=torch.float32, device=xb.device) if return_value else None
         with torch.cuda.device(xb.device):
-            nbytes = int(lib.glhip_argmin_workspace_bytes(B, N, M, D))
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=xb.device) if nbytes else None
-            rc = lib.glhip_argmin(xb.data_ptr(), yb.data_ptr(), gb.data_ptr() if g is not None else None, index.data_ptr(),
-                                  value.data_ptr() if return_value else None, B, N, M, D, int(p), _dtype_code(xb), *_NO_RANGES,
-                                  ctypes.c_void_p(ws.data_ptr()) if nbytes else None, nbytes, int(flags) | ENV_FLAGS, _stream(xb))
+            ws, ws_args = _scratch(int(lib.glhip_argmin_workspace_bytes(B, N, M, D)), xb.device)
+            rc = lib.glhip_argmin(xb.data_ptr(), yb.data_ptr(), _ptr(gb), index.data_ptr(), _ptr(value), B, N, M, D, int(p), _dtype_code(xb),
+                                  *_NO_RANGES, *ws_args, int(flags) | ENV_FLAGS, _stream(xb))
         _check(rc, lib)
     if not batched:
         index = index.view(-1)
@@ -1892,50 +1638,3 @@ def max_lines(g, step, p=2):
 
 def lse_lines(h, eps, p=2):
     return _LseLines.apply(h, float(eps), int(p))
-
-
-def settle_host():
-    """For latency-critical loops (serving, benchmarks): one full Python garbage collection now, and its survivors moved out of the
-    collector's reach (``gc.freeze()``).  The first generation-2 collection of a process that has imported torch walks ~1e6 objects
-    and takes 30-40 ms; it fires once, a few thousand container allocations in, wherever the program happens to be — and while the
-    host is stopped the launch queue of a 2 ms loss drains and the GPU idles (measured: profiles/r05_shard_stall.txt; this was the
-    intermittent 2x outlier of the B = 32 shard of BASELINE configs[3]).  Call it after the warm-up of such a loop; bench.py does."""
-    import gc
-    gc.collect()
-    gc.freeze()
-
-
-# ----------------------------------------------------------------------------------------------
-#  hipGraph capture of launch-bound loops
-# ----------------------------------------------------------------------------------------------
-
-class GraphCache:
-    """Captures ``fn(*tensors) -> tuple of tensors`` into a hipGraph (``torch.cuda.CUDAGraph``) the first time a key is
-    seen and replays it afterwards.  Everything ``fn`` launches — our C-ABI kernels included: they are issued on torch's
-    current stream, which is the capture stream — becomes one graph launch.  Inputs are copied into static buffers,
-    outputs are cloned out of them.  Small LRU: a graph pins its memory pool."""
-
-    def __init__(self, capacity=8):
-        self.capacity, self.entries = capacity, {}
-
-    def run(self, key, fn, inputs):
-        entry = self.entries.pop(key, None)
-        if entry is None:
-            static_in = [t.detach().clone() for t in inputs]
-            side = torch.cuda.Stream(device=static_in[0].device)
-            side.wait_stream(torch.cuda.current_stream(static_in[0].device))
-            with torch.cuda.stream(side):      # warm-up outside capture (loads code objects, sizes the allocator pools)
-                fn(*static_in)
-            torch.cuda.current_stream(static_in[0].device).wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                static_out = fn(*static_in)
-            entry = (graph, static_in, static_out)
-            if len(self.entries) >= self.capacity:
-                self.entries.pop(next(iter(self.entries)))
-        else:
-            for dst, src in zip(entry[1], inputs):
-                dst.copy_(src)
-        self.entries[key] = entry   # most recently used last
-        entry[0].replay()
-        return tuple(None if o is None else o.clone() for o in entry[2])

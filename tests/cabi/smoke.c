@@ -2,7 +2,7 @@
  * tests/cabi/smoke.c — a caller of libgeomloss_hip.so that is NOT geomloss_amd/hip.py: plain C, the prototypes of
  * include/glhip.h as the compiler sees them, device memory from hipMalloc, no Python, no torch.
  *
- * Every other test reaches the library through the ctypes signature table of hip.py; a wrong `argtypes` entry there and a wrong
+ * Every other test reaches the library through the ctypes signature table of geomloss_amd/_glhip.py; a wrong `argtypes` entry there and a wrong
  * prototype here cannot agree with each other by accident, so this program pins the header itself (round-4 review, weak #9).
  * It plays the reference's call sites for the path: `lse_genred(...)(x, y, h, 1/eps)` (_legacy/sinkhorn_samples.py:322-346),
  * `keops_lse(..., ranges=...)` (:432-450), KeOps `Grad` of the last soft-min, and `K @ v` (kernel_samples.py:117-137).

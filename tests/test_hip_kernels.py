@@ -968,3 +968,40 @@ def test_distance_kernel_losses_dense_large_launches(cuda):
             assert e[0] < 1e-4 and e[2] < 1e-4
         else:
             assert abs(L.item() - ref) < 2e-7 * max(term, abs(ref))
+
+
+# ---- the soft-min is the half-step with pot = prev = None and damping = 1 ------------------------------------------------------------------
+# hip.softmin_fwd_raw and hip.sinkhorn_step_raw share one launch body (hip._softmin_step), as their entry points share one in the library
+# (softmin_step of csrc/glhip_api.hip; the float64 kernel multiplies by alpha = 1).  N = 257: one row past a 256-row tile; M = 130: two
+# columns past the 128-column float64 tile.
+
+def _bits(t):
+    return t.view(torch.int64 if t.dtype == torch.float64 else torch.int32)
+
+
+def _softmin_and_unit_step(x, y, h, eps, p, ranges=None):
+    a = hip.softmin_fwd_raw(x, y, h, eps, p, ranges)
+    b = hip.sinkhorn_step_raw(x, y, h, None, None, eps, 1.0, p, ranges)      # (p = 1, D > 16: a plain soft-min needs no fused half-step kernel)
+    assert a.dtype == b.dtype == h.dtype and a.shape == b.shape == x.shape[:2]
+    return a, b
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float64])
+@pytest.mark.parametrize("p", [1, 2])
+def test_softmin_and_unit_half_step_return_identical_bits(cuda, dtype, p):
+    N, M = 257, 130
+    for D in (3, 5, 20):
+        for B in (1, 2):
+            x, y, h = _clouds(100 * D + B, N, M, D, B=B)
+            x, y = _t(x, cuda).to(dtype), _t(y, cuda).to(dtype)
+            h = _t(h, cuda).to(torch.float64 if dtype == torch.float64 else torch.float32)
+            a, b = _softmin_and_unit_step(x, y, h, 0.05, p)
+            assert torch.isfinite(a).all() and torch.equal(_bits(a), _bits(b)), (D, B)
+    # block-sparse, two row blocks: the first reduces over the first column block, the second over both
+    x, y, h = _clouds(7, N, M, 3, B=1)
+    x, y = _t(x, cuda).to(dtype), _t(y, cuda).to(dtype)
+    h = _t(h, cuda).to(torch.float64 if dtype == torch.float64 else torch.float32)
+    ri, rj = np.array([[0, 100], [100, N]], np.int32), np.array([[0, 60], [60, M]], np.int32)
+    rg = from_matrix(_t(ri, cuda), _t(rj, cuda), _t(np.array([[1, 0], [1, 1]], bool), cuda))
+    a, b = _softmin_and_unit_step(x, y, h, 0.05, p, rg)
+    assert torch.isfinite(a).all() and torch.equal(_bits(a), _bits(b))

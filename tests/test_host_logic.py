@@ -546,7 +546,7 @@ def test_fused_half_step_dispatch_follows_the_flags(monkeypatch):
 def test_shared_library_exports_every_declared_symbol():
     header = open(os.path.join(ROOT, "include", "glhip.h")).read()
     declared = set(re.findall(r"\b(glhip_\w+)\s*\(", header))
-    assert declared == set(hip.SIGNATURES), "include/glhip.h and geomloss_amd/hip.py disagree"
+    assert declared == set(hip.SIGNATURES), "include/glhip.h and geomloss_amd/_glhip.py disagree"
     assert hip.library_available(), "libgeomloss_hip.so is not built (python -c 'import __graft_entry__ as g; g.build()')"
     lib = ctypes.CDLL(hip.LIB_PATH)
     for name in declared:
@@ -556,7 +556,7 @@ def test_shared_library_exports_every_declared_symbol():
 
 
 def test_ctypes_signatures_follow_the_header_prototypes():
-    """Every prototype of include/glhip.h against the ctypes signature geomloss_amd/hip.py binds it with: the same number of
+    """Every prototype of include/glhip.h against the ctypes signature geomloss_amd/_glhip.py binds it with: the same number of
     parameters, and the same kind in every position (pointer / int / long / float / double / size_t) — an argument short or a
     float where the header says int would be read from the wrong register without any error."""
     header = open(os.path.join(ROOT, "include", "glhip.h")).read()

@@ -1,5 +1,5 @@
 """Host side of the reused permutations of the sorted p = 2 call (library 134: glhip_sinkhorn_step_perm, glhip_softmin_perm_applies;
-geomloss_amd/hip.py: _PermCache).
+geomloss_amd/_perm_cache.py: _PermCache; geomloss_amd/hip.py: _perm_plan).
 
 * The clamp every kernel applies to an index it takes from a hinted permutation (csrc/glhip_perm_index.h) against a plain loop, with
   indices below 0, at n and at INT_MAX, as a stand-alone host program under the address and undefined-behaviour sanitizers (built the

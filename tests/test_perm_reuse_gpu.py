@@ -1,4 +1,4 @@
-"""Reused permutations of the sorted p = 2 call (library 134: glhip_sinkhorn_step_perm; geomloss_amd/hip.py: _PermCache) at the smallest
+"""Reused permutations of the sorted p = 2 call (library 134: glhip_sinkhorn_step_perm; geomloss_amd/_perm_cache.py: _PermCache; geomloss_amd/hip.py: _perm_plan) at the smallest
 shapes the pruned call accepts, those of tests/test_prep_kernels_gpu.py: 65536 x 1525900 (N at its minimum, N M just over 1e11) and
 317000 x 320037 (a partial last block of 1024 in both clouds: the tail keeps the path order).  Unit-cube clouds, eps = 0.05^2, the
 dual vector of bench.make_problem, the headline's f16 x 2 layout.
