@@ -30,6 +30,7 @@ MFMA_FWD_MAX_DIM = 4095         # p = 2 soft-min forward / half-step and gaussia
 DIST_XK_MAX_DIM = 4095          # ... and under FLAG_XK_DIST the p = 1 soft-min / half-step and the laplacian / energy products too (glhip_dist_xk.h)
 ARGMIN_MAX_DIM = 4095           # argmin takes p = 2 clouds of every dimension up to this one (glhip_argmin_xk.h)
 PLAN_MAX_DIM = 4095             # plan_apply_nd applies p = 2 transport plans to features up to this dimension (17 ... 4095: glhip_plan_apply_xk.h)
+PLAN_P1_MAX_DIM = 4095          # plan_apply_p1 applies p = 1 transport plans to features in every dimension up to this one (glhip_dist_plan_xk.h)
 # kernel families reported by softmin_fwd_family (GLHIP_FAMILY_* of glhip.h)
 FAMILY_VALU, FAMILY_X32, FAMILY_XD, FAMILY_XK, FAMILY_DIST, FAMILY_GENERIC = 0, 1, 2, 3, 4, 5
 
@@ -72,6 +73,10 @@ SIGNATURES = {
     "glhip_plan_apply_nd_family": (_c_int, [_c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int]),
     "glhip_plan_apply_nd_pass_width": (_c_int, [_c_int]),
     "glhip_plan_apply_nd": (_c_int, [_vp] * 7 + [_c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int, _c_int] + _RANGES + _TAIL),
+    "glhip_plan_apply_p1_supported": (_c_int, [_c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int]),
+    "glhip_plan_apply_p1_pass_width": (_c_int, []),
+    "glhip_plan_apply_p1_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "glhip_plan_apply_p1": (_c_int, [_vp] * 6 + [_c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int] + _RANGES + _TAIL),
     "glhip_kernel_conv_fwd": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int]
                               + _RANGES + _TAIL),
     "glhip_kernel_conv_bwd_x": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float,
@@ -111,7 +116,9 @@ KEEP_DUAL_SLACK, KEEP_WITHIN = 0, 1
 PERM_HINT_X, PERM_HINT_Y = 1, 2     # perm_flags of glhip_sinkhorn_step_perm (GLHIP_PERM_HINT_*)
 # symbols younger than the oldest C-ABI that GEOMLOSS_HIP_LIB may name for an A/B run: an older build is bound without them, and the
 # calls that would use them take the entry points that build has (no permutation is reused with it)
-_SINCE = {"glhip_sinkhorn_step_perm": 134, "glhip_softmin_perm_applies": 134}
+_SINCE = {"glhip_sinkhorn_step_perm": 134, "glhip_softmin_perm_applies": 134,
+          "glhip_plan_apply_p1_supported": 135, "glhip_plan_apply_p1_pass_width": 135, "glhip_plan_apply_p1_workspace_bytes": 135,
+          "glhip_plan_apply_p1": 135}
 
 _lib = None
 

@@ -29,7 +29,7 @@
 
 namespace glhip {
 
-// ---- The near-pair repair, shared with xk_dist_grad_kernel (glhip_dist_grad_xk.h) ----
+// ---- The near-pair repair, shared with xk_dist_grad_kernel (glhip_dist_grad_xk.h) and xk_dist_plan_kernel (glhip_dist_plan_xk.h) ----
 
 // t^2 |x_i - y_j|^2 on explicit differences of the points themselves: a run-time loop over D from global memory
 template <typename T>

@@ -49,8 +49,8 @@
 // argument (plan_merge_kernel below, one thread per row and feature) — one merge for every chunk count and any V, instead of one
 // MergeOp instantiation per width.
 //
-// Shared pieces (profiles/xk_plan_pieces.txt).  The plan half exists in three __global__ bodies: plan_apply_kernel here, xk_plan_kernel
-// (glhip_plan_apply_xk.h) and xk_dist_grad_kernel (glhip_dist_grad_xk.h).  What they share as __device__ __forceinline__ pieces is defined
+// Shared pieces (profiles/xk_plan_pieces.txt).  The plan half exists in four __global__ bodies: plan_apply_kernel here, xk_plan_kernel
+// (glhip_plan_apply_xk.h), xk_dist_grad_kernel (glhip_dist_grad_xk.h) and xk_dist_plan_kernel (glhip_dist_plan_xk.h).  What they share as __device__ __forceinline__ pieces is defined
 // here — plan_store_pieces (scale, split and store of one staged feature item), plan_rescale (the lazy rescale; this kernel keeps its
 // inline text: the helper costs the four-chunk instantiations 2 VGPRs), plan_split_weights, plan_chunk_mfma (the six MFMAs of a chunk) —
 // next to the register maps reg_column / reg_feature of glhip_klayout.h.  The staging loops, the fold of a fresh accumulator into the running
@@ -109,9 +109,9 @@ __device__ __forceinline__ uint32_t plan_scale_exponent(uint32_t max_bits) {
     return (uint32_t)min(max(se, 1), 254 - kWqShift - 1);
 }
 
-// ---- The pieces of the plan half.  plan_apply_kernel below, xk_plan_kernel (glhip_plan_apply_xk.h) and xk_dist_grad_kernel
-// (glhip_dist_grad_xk.h) are three __global__ bodies that call them (plan_rescale: the latter two); each is __device__ __forceinline__
-// and holds no barrier. ----
+// ---- The pieces of the plan half.  plan_apply_kernel below, xk_plan_kernel (glhip_plan_apply_xk.h), xk_dist_grad_kernel
+// (glhip_dist_grad_xk.h) and xk_dist_plan_kernel (glhip_dist_plan_xk.h) are four __global__ bodies that call them (plan_rescale: the
+// latter three); each is __device__ __forceinline__ and holds no barrier. ----
 
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));

@@ -482,6 +482,28 @@ def plan_apply_nd_raw(x, y, h, fwd, feat, eps, flags=0, want_mass=False, p=2, ra
     return _plan_apply_call("glhip_plan_apply_nd", x, y, h, fwd, feat, eps, flags, want_mass, p, ranges, workspace)
 
 
+def plan_apply_p1_raw(xb, yb, hb, fb, eps, flags=0, want_softmin=False, workspace=True):
+    """The plan of a p = 1 soft-min applied to features (``glhip_plan_apply_p1``, any D <= PLAN_P1_MAX_DIM): xb (B,N,D), yb (B,M,D)
+    fp32|bf16, hb (B,M), fb (B,M,V) fp32 -> (B,N,V) fp32 row-normalised averages [, (B,N) the soft-min computed on the side].  The kernel
+    normalises itself: no saved forward value comes in.  ``workspace=False`` passes no workspace: the launch runs without column splits
+    (same results up to summation order)."""
+    lib = load_library()
+    B, N, D = xb.shape
+    M, V = yb.shape[1], fb.shape[2]
+    if is_f64(xb):
+        raise NotImplementedError("glhip_plan_apply_p1: float64 clouds are not supported (cast to float32)")
+    if tuple(fb.shape[:2]) != (B, M) or tuple(hb.shape) != (B, M):
+        raise ValueError(f"glhip_plan_apply_p1: expected h {(B, M)}, feat {(B, M, 'V')}; got {tuple(hb.shape)}, {tuple(fb.shape)}")
+    out = torch.empty((B, N, V), dtype=torch.float32, device=xb.device)
+    soft = torch.empty((B, N), dtype=torch.float32, device=xb.device) if want_softmin else None
+    with torch.cuda.device(xb.device):
+        ws, ws_args = _scratch(int(lib.glhip_plan_apply_p1_workspace_bytes(B, N, M, D, V)) if workspace else 0, xb.device)
+        rc = lib.glhip_plan_apply_p1(xb.data_ptr(), yb.data_ptr(), hb.data_ptr(), fb.data_ptr(), out.data_ptr(), _ptr(soft),
+                                     B, N, M, D, V, float(eps), _dtype_code(xb), *_NO_RANGES, *ws_args, int(flags), _stream(xb))
+    _check(rc, lib)
+    return (out, soft) if want_softmin else out
+
+
 def softmin_fwd_grad_raw(x, y, h, guess, margin, eps, ranges=None, flags=0):
     """Soft-min and d out_i / d x_i in one reduction, given a guess within ``margin`` of the answer (``glhip_softmin_fwd_grad``;
     p = 2, D <= 16) -> (B,N), (B,N,D)."""
@@ -1250,6 +1272,49 @@ def plan_apply_nd(eps, x, y, h, feat, fwd=None, flags=0, p=2, ranges=None):
     (row-normalised, one-hot rows bit for bit, rows without mass give 0), not an autograd function.  float64 clouds, p = 1,
     D > 4095 and block-sparse ranges raise ``NotImplementedError``."""
     return _plan_apply("plan_apply_nd", plan_apply_nd_raw, PLAN_MAX_DIM, eps, x, y, h, feat, fwd, flags, p, ranges)
+
+
+def plan_apply_p1_applies(x, ranges=None):
+    """Whether :func:`plan_apply_p1` serves clouds like ``x``: dense, D <= PLAN_P1_MAX_DIM, float32 / bfloat16 compute."""
+    return ranges is None and 1 <= x.shape[-1] <= PLAN_P1_MAX_DIM and x.dtype != torch.float64
+
+
+def plan_apply_p1(eps, x, y, h, feat, flags=0, want_softmin=False, ranges=None):
+    """Row-normalised application of the plan of a p = 1 soft-min to a feature matrix on the matrix cores (``glhip_plan_apply_p1``,
+    glhip_dist_plan_xk.h), for clouds of any dimension D <= PLAN_P1_MAX_DIM = 4095:
+
+        out[i, v] = sum_j w_ij feat[j, v] / sum_j w_ij,     w_ij = exp(h_j - |x_i - y_j| / eps)
+
+    with the distance clamped from below as in ``utils.distances``.  Shapes as :func:`plan_apply_nd`: x: (N,D)|(B,N,D), y: (M,D)|(B,M,D),
+    h: (M,)|(B,M), feat: (M,V)|(B,M,V)|(M,) -> (N,V)|(B,N,V)|(N,) fp32.  The kernel normalises itself, so there is no ``fwd`` argument;
+    ``want_softmin=True`` also returns ``softmin(eps, x, y, h, p=1)`` as the kernel has computed it on the side, (N,)|(B,N): the
+    unnormalised product is ``exp(-softmin / eps)[..., None] * out``.  One sweep over the N x M pairs per pass of
+    ``glhip_plan_apply_p1_pass_width()`` feature columns; a remainder is a pass of its own.  One-hot plan rows return their features bit
+    for bit, rows without mass give 0 (soft-min +inf), results are bit-identical run to run.  NOT an autograd function: it runs under
+    ``torch.no_grad()`` and returns tensors without ``grad_fn``.  float64 clouds, D > 4095 and block-sparse ranges raise
+    ``NotImplementedError``."""
+    D = x.shape[-1]
+    if x.dtype == torch.float64 or y.dtype == torch.float64:
+        raise NotImplementedError("geomloss_amd.hip.plan_apply_p1: float64 clouds are not supported (cast to float32)")
+    if D > PLAN_P1_MAX_DIM or ranges is not None:
+        raise NotImplementedError(f"geomloss_amd.hip.plan_apply_p1: only D <= {PLAN_P1_MAX_DIM}, dense plans (got D = {D}, "
+                                  f"ranges {'given' if ranges is not None else 'None'})")
+    batched = x.dim() == 3
+    lead = tuple(y.shape[:-1])
+    vector = feat.dim() == len(lead)
+    if tuple(feat.shape[:len(lead)]) != lead or feat.dim() not in (len(lead), len(lead) + 1):
+        raise ValueError(f"geomloss_amd.hip.plan_apply_p1: expected features of shape {lead} or {lead + ('V',)}, got {tuple(feat.shape)}")
+    with torch.no_grad():
+        xb, yb, hb, _ = _clouds(x, y, _f32(h), detach=True)
+        B, M = yb.shape[0], yb.shape[1]
+        fb = _f32(feat).to(xb.device).reshape(B, M, -1)
+        res = plan_apply_p1_raw(xb, yb, hb, fb, float(eps), int(flags) | ENV_FLAGS, want_softmin)
+    out, soft = res if want_softmin else (res, None)
+    if not batched:
+        out = out[0]
+        soft = None if soft is None else soft[0]
+    out = out[..., 0] if vector else out
+    return (out, soft) if want_softmin else out
 
 
 def fused_step_applies(D, p=2, flags=0, sparse=False):

@@ -10,6 +10,16 @@ itself handles.  GPU tensors only, like the ``online`` backend; p = 2, float32 /
 the kernel with resident operands (up to 128 feature columns per pass), 17 <= D <= 4095 — principal components, embeddings — on the
 K-chunked kernel (64 per pass); beyond, ``NotImplementedError``.  Nothing here is recorded by autograd.
 
+``p=1`` (:func:`apply_plan`, :func:`barycentric_map`): the plan of ``SamplesLoss("sinkhorn", p=1, ...)``,
+
+    P_ij = a_i b_j exp((F_i + G_j - |x_i - y_j|) / blur),
+
+through ONE launch of :func:`geomloss_amd.hip.plan_apply_p1` per product, which normalises itself and returns the row sums' soft-min on
+the side: one kernel for every dimension 1 <= D <= 4095, 64 feature columns per pass.  Measured at N = M = 2e5 on an MI355X
+(profiles/dist_plan_xk.txt): a product of V = 3 / 32 / 128 columns costs 5.4 / 5.5 / 13.2 p = 1 soft-min reductions at D = 3,
+1.7 / 1.7 / 3.8 at D = 32 and 1.4 / 1.4 / 2.9 at D = 128 — less than the 2 V reductions of the log-domain loop at every measured
+(D, V), narrowly so at D = 3, V = 3 (the loop: 1.1x the product).
+
 :func:`plan_argmax` gives the hard correspondence instead of an average: the column that receives most of a row's mass, one
 arg-reduction (:func:`geomloss_amd.hip.argmin`), same clouds and dimensions.
 """
@@ -30,32 +40,47 @@ def _log_weights(w, like, count):
     return w.detach().to(like.dtype).reshape(like.shape).log()
 
 
-def apply_plan(x, y, F, G, feat, blur, a=None, b=None, transpose=False):
+def _eps(blur, p):
+    """The temperature ``blur ** p`` of the plan; only the costs |x - y| (p = 1) and |x - y|^2 / 2 (p = 2) have kernels here."""
+    if p not in (1, 2):
+        raise ValueError(f"geomloss_amd.transport: p must be 1 or 2, got {p!r}")
+    return float(blur) ** p
+
+
+def apply_plan(x, y, F, G, feat, blur, a=None, b=None, transpose=False, p=2):
     """``sum_j P_ij feat_j`` for the plan of the potentials ``F`` (N,)|(B,N), ``G`` (M,)|(B,M) on the clouds ``x`` (N,D)|(B,N,D),
     ``y`` (M,D)|(B,M,D) with weights ``a``, ``b`` (uniform by default): feat (M,V)|(B,M,V)|(M,) -> (N,V)|(B,N,V)|(N,) fp32.
-    ``transpose=True`` applies the transposed plan instead: ``sum_i P_ij feat_i`` for feat on the rows, (N,V) -> (M,V)."""
+    ``transpose=True`` applies the transposed plan instead: ``sum_i P_ij feat_i`` for feat on the rows, (N,V) -> (M,V).
+    ``p=1``: the plan of the cost |x_i - y_j| at temperature ``blur`` — ONE launch (:func:`geomloss_amd.hip.plan_apply_p1`), which
+    returns the row sums' soft-min next to the average.  Any other ``p`` than 1 or 2 raises ``ValueError``."""
     if transpose:
-        return apply_plan(y, x, G, F, feat, blur, a=b, b=a)
-    eps = float(blur) ** 2
+        return apply_plan(y, x, G, F, feat, blur, a=b, b=a, p=p)
+    eps = _eps(blur, p)
     with torch.no_grad():
         N, M = x.shape[-2], y.shape[-2]
         Ff = F.detach().float().reshape(x.shape[:-1])
         Gf = G.detach().float().reshape(y.shape[:-1])
         h = _log_weights(b, Gf, M) + Gf / eps
+        if p == 1:
+            avg, fwd = hip.plan_apply_p1(eps, x, y, h, feat, want_softmin=True)      # sum_j b_j exp((G_j - C_ij) / eps) = exp(-fwd_i / eps)
+            rows = (_log_weights(a, Ff, N) + (Ff - fwd) / eps).exp()                  # sum_j P_ij
+            return rows * avg if avg.dim() == rows.dim() else rows.unsqueeze(-1) * avg
         fwd = hip.softmin(eps, x.detach(), y.detach(), h)              # sum_j b_j exp((G_j - C_ij) / eps) = exp(-fwd_i / eps)
         avg = hip.plan_apply_nd(eps, x, y, h, feat, fwd=fwd)
         rows = (_log_weights(a, Ff, N) + (Ff - fwd) / eps).exp()       # sum_j P_ij
         return rows * avg if avg.dim() == rows.dim() else rows.unsqueeze(-1) * avg
 
 
-def barycentric_map(x, y, F, G, blur, b=None):
+def barycentric_map(x, y, F, G, blur, b=None, p=2):
     """``T(x_i) = sum_j P_ij y_j / sum_j P_ij`` (N,D)|(B,N,D) fp32: where the plan sends each x_i on average.  The row-normalised
     average does not depend on ``a`` or ``F`` (they scale a whole row); ``F`` is accepted so that the call reads like
-    :func:`apply_plan`."""
-    eps = float(blur) ** 2
+    :func:`apply_plan`.  ``p`` as there."""
+    eps = _eps(blur, p)
     with torch.no_grad():
         Gf = G.detach().float().reshape(y.shape[:-1])
         h = _log_weights(b, Gf, y.shape[-2]) + Gf / eps
+        if p == 1:
+            return hip.plan_apply_p1(eps, x, y, h, y.detach().float())
         return hip.plan_apply_nd(eps, x, y, h, y.detach().float())
 
 

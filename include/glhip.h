@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 134 /* 0.1.34 */
+#define GLHIP_VERSION 135 /* 0.1.35 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
@@ -512,6 +512,33 @@ int glhip_plan_apply_nd_pass_width(int D);
 int glhip_plan_apply_nd(const void* x, const void* y, const float* h, const float* fwd, const float* feat,
                         float* out, float* mass,
                         int B, int N, int M, int D, int V, float eps, int p, int in_dtype,
+                        const int32_t* ranges_i, const int32_t* slices_i, const int32_t* redranges_j, int n_ranges,
+                        void* workspace, size_t workspace_bytes, int flags, void* stream);
+
+/*
+ * The plan of a p = 1 soft-min applied to features (version 135), 1 <= D <= 4095, float32 / bfloat16 clouds, dense and batched launches:
+ *     w_ij = exp(h_j - c_ij / eps),  c_ij = sqrt(max(|x_i - y_j|^2, 1e-8))      (the clamp of utils.py:56-61)
+ *     out[b,i,v] = sum_j w_ij feat[b,j,v] / sum_j w_ij          softmin[b,i] = -eps log sum_j w_ij      (softmin may be NULL)
+ * xk_dist_plan_kernel (glhip_dist_plan_xk.h): the exact squared distances of the p = 1 forward kernel of 17 <= D <= 4095 (near pairs
+ * re-evaluated on explicit differences), handed to the second MFMA product of glhip_plan_apply.h.  ONE kernel for the whole range of D.  It
+ * normalises itself — no saved forward value comes in — and returns the soft-min it has computed on the side.  One pass over the columns
+ * per glhip_plan_apply_p1_pass_width() features (a remainder is a pass of its own).  Results are bit-identical run to run; a one-hot plan row
+ * returns its features bit for bit; a row whose columns all carry h = -inf gets out = 0 and softmin = +inf, never NaN.
+ *   M == 0 with N > 0 zeroes out (softmin: +inf); V == 0 writes nothing to out (softmin, where wanted, is still computed); N == 0 or
+ *   B == 0 writes nothing at all.  Validation in the order of glhip_plan_apply_nd.
+ *   Block-sparse ranges (n_ranges > 0: the arguments are in the ABI for later), D > 4095 and B > 65535 return GLHIP_EUNSUPPORTED.
+ *   GLHIP_FLAG_NO_SPLIT is honoured; GLHIP_FLAG_F16X2 is ignored (a squared distance needs all 24 bits); no other flag changes the result.
+ * glhip_plan_apply_p1_workspace_bytes holds the split partials only and never asks for more than 1 GiB; NULL or a short buffer means
+ * fewer or no splits, with the same results up to summation order.
+ * glhip_plan_apply_p1_supported: host arithmetic only, the predicate the launch itself evaluates — 1, 0 for valid requests without a
+ * kernel, GLHIP_EINVAL for what the entry point rejects (negative sizes, D < 1, bad dtype).
+ * glhip_plan_apply and glhip_plan_apply_nd keep refusing p = 1.
+ */
+int glhip_plan_apply_p1_supported(int B, long N, long M, int D, int V, int dtype, int n_ranges);
+int glhip_plan_apply_p1_pass_width(void);
+size_t glhip_plan_apply_p1_workspace_bytes(int B, int N, int M, int D, int V);
+int glhip_plan_apply_p1(const void* x, const void* y, const float* h, const float* feat, float* out, float* softmin,
+                        int B, int N, int M, int D, int V, float eps, int in_dtype,
                         const int32_t* ranges_i, const int32_t* slices_i, const int32_t* redranges_j, int n_ranges,
                         void* workspace, size_t workspace_bytes, int flags, void* stream);
 

@@ -10,6 +10,9 @@ V = 32 product at --big (1e6: 3 calls after 1).  Medians over --launches calls a
                                                      # feature spaces (glhip_plan_apply_nd, eps = 0.1 D / 3); with --legacy and
                                                      # GEOMLOSS_HIP_LIB=<library of the parent commit> this times that library's route:
                                                      # symbols it does not export yet are not bound
+    python tools/plan_apply_bench.py --p 1 --dims 3 32 128 --widths 3 32 128 --legacy --budget-ms 4000
+                                                     # the p = 1 product (glhip_plan_apply_p1), one p = 1 forward reduction and, with
+                                                     # --legacy, the loop of 2 V reductions it replaces, alternated in one process
 
 The solve itself is not timed: the potentials are a few Sinkhorn iterations at a moderate temperature, enough for a well-formed plan."""
 import argparse
@@ -80,8 +83,48 @@ def run_dims(args, lib, dev):
     torch.cuda.synchronize()
 
 
+def run_p1(args, lib, dev):
+    """--p 1: the raw ``glhip_plan_apply_p1`` product (glhip_dist_plan_xk.h) for clouds of each dimension and width, one plain
+    ``hip.softmin(p=1)`` forward reduction of the same shape and, with --legacy, the log-domain loop the product replaces — 2 V forward
+    reductions, the positive and the negative part of every column — alternated with it in the same process.  FLAG_XK_DIST where D > 16;
+    eps = 0.05 sqrt(D).  The loop is timed with one warm-up call."""
+    print(f"# libgeomloss_hip {lib.glhip_version()}; p = 1; float32; pass width {lib.glhip_plan_apply_p1_pass_width()}; median (min, spread) "
+          f"of up to {args.launches} calls after {args.warmup}; {torch.cuda.get_device_name(0)}")
+    n = args.n
+    for D in args.dims if args.dims is not None else [3]:
+        eps = 0.05 * D**0.5
+        flags = hip.FLAG_XK_DIST if D > 16 else 0
+        g = torch.Generator().manual_seed(n + D)
+        x, y = torch.rand(n, D, generator=g).to(dev), torch.rand(n, D, generator=g).to(dev)
+        h = (torch.randn(n, generator=g) * 2).to(dev)
+        xb, yb, hb = x[None].contiguous(), y[None].contiguous(), h[None].contiguous()
+        fwd_ms, lo, spread = timed(lambda: hip.softmin(eps, x, y, h, p=1, flags=flags), args.launches, args.warmup, args.budget_ms)
+        print(f"hip.softmin p=1     D={D:4d} N=M={n:8d}         {fwd_ms:10.3f} ms (min {lo:10.3f}, spread {spread:5.1%})", flush=True)
+        for V in args.widths:
+            S = features(n, V, g, dev)
+            Sb = S[None].contiguous()
+            med, lo, spread = timed(lambda: hip.plan_apply_p1_raw(xb, yb, hb, Sb, eps, 0, want_softmin=True), args.launches, args.warmup,
+                                    args.budget_ms)
+            line = (f"glhip_plan_apply_p1 D={D:4d} N=M={n:8d} V={V:4d}  {med:10.3f} ms (min {lo:10.3f}, spread {spread:5.1%})"
+                    f"  = {med / fwd_ms:6.2f} forwards")
+            if args.legacy:
+                logs = [(S[:, v].clamp_min(0).log(), (-S[:, v]).clamp_min(0).log()) for v in range(V)]
+
+                def loop():
+                    out = torch.empty(n, V, device=dev)
+                    for v, (lp, ln) in enumerate(logs):
+                        out[:, v] = ((-hip.softmin(eps, x, y, h + lp, p=1, flags=flags) / eps).exp()
+                                     - (-hip.softmin(eps, x, y, h + ln, p=1, flags=flags) / eps).exp())
+                    return out
+                lmed, llo, lspread = timed(loop, args.launches, 1, args.budget_ms)
+                line += f";  loop of {2 * V} reductions {lmed:10.3f} ms (min {llo:10.3f}, spread {lspread:5.1%}) = {lmed / med:6.2f} products"
+            print(line, flush=True)
+    torch.cuda.synchronize()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--p", type=int, choices=[1, 2], default=2, help="the cost: 2 (|x - y|^2 / 2, as ever) or 1 (|x - y|: glhip_plan_apply_p1)")
     ap.add_argument("--n", type=int, default=200_000)
     ap.add_argument("--big", type=int, default=0, help="one more V = 32 product at this N = M (1e6), 3 calls")
     ap.add_argument("--launches", type=int, default=20)
@@ -101,6 +144,9 @@ def main():
     if args.legacy:
         hip.plan_apply_applies = lambda *a, **k: False
         hip.plan_apply_nd_applies = lambda *a, **k: False
+    if args.p == 1:
+        run_p1(args, lib, dev)
+        return
     if args.dims is not None:
         run_dims(args, lib, dev)
         return
