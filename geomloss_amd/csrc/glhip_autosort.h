@@ -69,12 +69,12 @@ constexpr int kSortRowsPerVoxel = 256;
 //   guarantee needs is that the SUM of everything dropped stays under 2^-26 of the row sum, and that sum is bounded from the records:
 //   with lse(S) = log sum_{j in S} e^(h_j) and pen(A, S) = dmin(A, S)^2 / (2 eps), the terms of a set S of columns sum to at most
 //   e^(lse(S) - pen(A, S)) for every row in the box A.  The 2^-26 is split three ways, each piece with its own proof:
-//     first level, 2^-26 / e of e^Mlb(R): a block T has the key k(T) = lse(T) - pen(R, T); prune_slabs_kernel finds the largest threshold
+//     first level, kPruneBudget1 = 2^-26 (1 - 1 / e - 1 / 2) = 0.132 x 2^-26 of e^Mlb(R): a block T has the key k(T) = lse(T) - pen(R, T); prune_slabs_kernel finds the largest threshold
 //       t1(R) such that the masses e^(k(T) - Mlb(R)) of the blocks with k(T) < t1 sum to at most the budget, and keeps T iff k(T) >= t1(R)
 //       (or T is special, or the slab keeps everything).  Mlb and the home block are what they were: Mlb is a term the row really has.
 //     second level, term rule, 2^-26 / e: the kernel's test against the rows' running maxima, unchanged (at most M terms, each under
 //       e^-L of the row's largest).  The group records hold lse(G) in the place of hmax(G): lse >= hmax, the test stays valid.
-//     second level, mass rule, 2^-26 (1 - 2 / e) of e^ms(W), ms(W) the smallest of the exact largest exponents of the tile's 32 rows
+//     second level, mass rule, kPruneBudget2 = 2^-26 / 2 of e^ms(W), ms(W) the smallest of the exact largest exponents of the tile's 32 rows
 //       over the home block (each of them a term its row really has): prune_tiles_kernel finds, over the groups inside the slab's
 //       emitted intervals, the largest t2(W) such that the masses e^(k(W, G) - ms(W)) of the groups with k(W, G) = lse(G) - pen(W, G)
 //       < t2 sum to at most the budget; the kernel's threshold is max(term rule's, t2(W)).
@@ -97,11 +97,16 @@ constexpr int kPruneGrid = 64;        // pieces a whole row of column blocks is 
 constexpr double kPruneMarginNats = 1.0;
 // The mass rule (round 10): thresholds are found on histograms of the keys, kPruneBuckets buckets of kPruneBucketNats starting at the
 // classic threshold.  28 nats cover ln M + 4 for every M an int holds (ln 2^31 = 21.5).  The budgets: the row sum may lose 2^-26 in
-// all — 2^-26 / e by the first level, 2^-26 / e by the term rule of the second, the rest by the mass rule of the second.
+// all — 2^-26 / e by the term rule of the second level (fixed: it is the kernel's L), half of the 2^-26 by the mass rule of the second
+// level, the remaining 2^-26 (1 - 1 / e - 1 / 2) by the first.  Earlier builds gave the first level 1 / e and the mass rule 1 - 2 / e =
+// 0.264; only the mass rule decides how many exponentials run, and the first level's threshold moves by ln(0.368 / 0.132) ~ one nat.
+// Bench problem at 1e6 (tools/prune_model.py, profiles/chunk_skip.txt): first level keeps 0.2295 -> 0.2378 of the blocks, evaluated
+// 0.1434 -> 0.1389; measured: transcendental instructions of the sweep -3.2 %, the call 15.96 -> 15.72 ms.
 constexpr int kPruneBuckets = 112;
 constexpr double kPruneBucketNats = 0.25;
-constexpr double kPruneBudget1 = 1.4901161193847656e-08 / 2.718281828459045;                  // 2^-26 / e
-constexpr double kPruneBudget2 = 1.4901161193847656e-08 * (1.0 - 2.0 / 2.718281828459045);    // 2^-26 (1 - 2 / e)
+constexpr double kPruneMassShare = 0.5;                                                                           // the mass rule's part of the 2^-26
+constexpr double kPruneBudget1 = 1.4901161193847656e-08 * (1.0 - 1.0 / 2.718281828459045 - kPruneMassShare);      // 2^-26 (1 - 1 / e - 1 / 2)
+constexpr double kPruneBudget2 = 1.4901161193847656e-08 * kPruneMassShare;                                        // 2^-26 / 2
 
 struct PrunePlan {
     int nT;    // column blocks

@@ -160,7 +160,7 @@ __device__ __forceinline__ int prune_bucket(double key, double lo) {
 }
 // The first bucket that is kept: buckets are dropped from the bottom while the dropped mass (the underflow bucket first) stays within the
 // budget.  The underflow bucket alone cannot exceed it: every key in it has a mass below e^-L = 2^-26 e^-1 / M, and it holds at most
-// ceil(M / 256) blocks (first level, budget 2^-26 e^-1) or ceil(M / 32) groups (second level, budget 2^-26 (1 - 2 / e) > 2^-26 e^-1 / 16)
+// ceil(M / 256) blocks (first level, budget 0.132 x 2^-26 > 2^-26 e^-1 / 256) or ceil(M / 32) groups (second level, budget 2^-26 / 2 > 2^-26 e^-1 / 32)
 // — so bucket 0 is always a valid answer.
 __device__ __forceinline__ int prune_first_kept(const double* hist, double under, double budget) {
     double s = under;

@@ -252,7 +252,7 @@ constexpr int fwd_tile(int NW) { return NW == 2 ? 256 : kTileX; }
 //     and non-finite coordinates, whose NaN / infinity pattern depends on the side of the centre a row lies on, give the same pattern.
 //   * mass rule (round 10; the argument: glhip_autosort.h): the records hold lse(G) >= hmax(G) in the place of hmax(G) — the test above
 //     stays valid, a little more conservative — and thr is the larger of the term rule's threshold above and Level2::t2 of the
-//     wavefront's tile of 32 rows (prune_tiles_kernel: groups whose keys lie under it hold, together, under 2^-26 (1 - 2 / e) of a term
+//     wavefront's tile of 32 rows (prune_tiles_kernel: groups whose keys lie under it hold, together, under 2^-26 / 2 (kPruneBudget2) of a term
 //     every row of the tile has).  Taken where thr is set (seed, redo): the group loops are what they were.
 //   Launches without Level2 (P2 = false: everything but the sorted p = 2 path) compile to what they were.
 constexpr float kP2Slack = 9.5367431640625e-7f;      // 2^-20

@@ -153,7 +153,7 @@ extern "C" {
                                   Version 123: both levels drop by the SUM of what they drop instead of by single terms.  The terms of a
                                   set S of columns sum to at most e^(lse(S) - dmin(box, S)^2 / (2 eps)) for every row of the box; per slab
                                   (blocks of 256 columns) and per tile of 32 rows (groups of 32 columns) the largest threshold on that key
-                                  is taken whose dropped masses stay within a budget — 2^-26 / e, and 2^-26 (1 - 2 / e) beside the 2^-26 / e
+                                  is taken whose dropped masses stay within a budget — 0.132 x 2^-26, and 2^-26 / 2 beside the 2^-26 / e
                                   of the term rule — found on 0.25-nat histograms in float64 (csrc/glhip_autosort.h).  Same guarantee:
                                   a row loses < 2^-26 of its sum.  glhip_prune_inspect shows the thresholds (profiles/r10_*).
                                   Version 128: balanced cells.  After the radix sort, every whole aligned block of 1024 positions of both

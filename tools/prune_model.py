@@ -250,8 +250,10 @@ def level2(xs, ys, h, eps, keep, L, slabs, check=False):
 # ---- the mass rule (glhip_autosort.h, round 10): thresholds by dropped mass, found on histograms of the keys ----------------------------
 
 BUCKETS, BUCKET_NATS = 112, 0.25                 # kPruneBuckets, kPruneBucketNats
-BUDGET1 = 2.0**-26 / math.e                      # first level, relative to e^Mlb(R)
-BUDGET2 = 2.0**-26 * (1.0 - 2.0 / math.e)        # second level's mass rule, relative to e^ms(W)
+MASS_SHARE = 0.5                                 # kPruneMassShare: the mass rule's part of the 2^-26 (the term rule keeps 1 / e)
+BUDGET1 = 2.0**-26 * (1.0 - 1.0 / math.e - MASS_SHARE)      # first level, relative to e^Mlb(R)
+BUDGET2 = 2.0**-26 * MASS_SHARE                  # second level's mass rule, relative to e^ms(W)
+CHUNK = 128                                      # the rows of one f16 x 2 workgroup, half a slab: the chunk-live rule below (model only)
 LSE_SLACK = np.float32(2.0**-20)                 # kPruneLseSlack
 LOG2E = 1.4426950408889634
 
@@ -349,7 +351,10 @@ def level2_mass(xs, ys, h, eps, keep, L, slabs, intervals=None):
     intervals instead of the runs of kept blocks.  Returns (pairs evaluated, pairs kept by the first level, per slab a dict with
     home, groups (the groups walked), ms, t2 (nats) per tile and skip (tiles, groups) bool).  A group is evaluated iff its key
     lse(G) - pen(W, G) lies in a bucket from the tile's first kept one on; the kernel's term rule, thr = ms - L against the same key,
-    is bucket >= 0."""
+    is bucket >= 0.  A chunk level between the two (modelled only — measured on the device and not kept, profiles/chunk_skip.txt):
+    blocks (the column blocks walked) and live (2, blocks) bool per half slab of CHUNK rows — some group of the block lies in a bucket
+    >= the first kept one of some row tile of the half slab, or the block is the home block; fk and top (tiles, blocks) are the first
+    kept bucket and the block's largest bucket per tile."""
     N, M = xs.shape[0], ys.shape[0]
     x64, y64, h64 = xs.astype(np.float64), ys.astype(np.float64), h.astype(np.float64)
     rlo, rhi = boxes(xs, SLAB)
@@ -369,7 +374,8 @@ def level2_mass(xs, ys, h, eps, keep, L, slabs, intervals=None):
         iv = intervals[c] if intervals is not None else intervals_of(keep[c])
         groups = np.concatenate([np.arange(j0 // GROUP, (min(je, M) + GROUP - 1) // GROUP) for j0, je in iv if je > j0])
         r1 = min(N, (c + 1) * SLAB)
-        ms, t2, skip = [], [], []
+        ms, t2, skip, fks, top = [], [], [], [], []
+        blocks, inv = np.unique(groups // (BLOCK // GROUP), return_inverse=True)
         for w0 in range(c * SLAB, r1, TILE):
             xr = x64[w0:min(w0 + TILE, r1)]
             seed = (h64[hc][None] - ((xr[:, None, :] - y64[hc][None]) ** 2).sum(-1) * i2e).max(1)
@@ -384,9 +390,21 @@ def level2_mass(xs, ys, h, eps, keep, L, slabs, intervals=None):
             ms.append(m)
             t2.append(m - L + fk * BUCKET_NATS)
             skip.append(bk < fk)
+            fks.append(fk)
+            tb = np.full(blocks.size, -1, np.int64)
+            np.maximum.at(tb, inv, bk)
+            top.append(tb)
             evaluated += float(gcols[groups][bk >= fk].sum()) * xr.shape[0]
             kept1 += float(gcols[groups].sum()) * xr.shape[0]
-        out[c] = dict(home=home, groups=groups, ms=np.array(ms), t2=np.array(t2), skip=np.array(skip))
+        fks, top = np.array(fks), np.array(top)
+        per = CHUNK // TILE
+        live = np.zeros((SLAB // CHUNK, blocks.size), bool)
+        for hs in range(live.shape[0]):
+            rows = slice(hs * per, (hs + 1) * per)
+            live[hs] = blocks == home
+            if top[rows].shape[0]:
+                live[hs] |= (top[rows] >= fks[rows, None]).any(0)
+        out[c] = dict(home=home, groups=groups, ms=np.array(ms), t2=np.array(t2), skip=np.array(skip), blocks=blocks, live=live, fk=fks, top=top)
     return evaluated, kept1, out
 
 
@@ -431,6 +449,36 @@ def tiles_of(keep_row, width=512):
     return int(sum(-(-(int(b) - int(a)) * BLOCK // width) for a, b in zip(np.flatnonzero(d == 1), np.flatnonzero(d == -1))))
 
 
+def walk_live(iv, live_of, M, width=2 * BLOCK):
+    """The walk a reducing kernel would make under the chunk level: inside the intervals iv = [(j0, je), ...] only the blocks t with
+    live_of(t) are staged; a tile is one live block or two adjacent live blocks of one interval.  Returns the tiles as (first
+    column, columns)."""
+    tiles = []
+    for j0, je in iv:
+        je = min(je, M)
+        t, te = j0 // BLOCK, -(-je // BLOCK)
+        while t < te:
+            if not live_of(t):
+                t += 1
+                continue
+            two = width >= 2 * BLOCK and t + 1 < te and live_of(t + 1)
+            tiles.append((t * BLOCK, min(je, (t + (2 if two else 1)) * BLOCK) - t * BLOCK))
+            t += 2 if two else 1
+    return tiles
+
+
+def chunk_counts(rec, iv, M):
+    """(512-column tiles staged today, tiles staged under the chunk level, blocks walked, blocks dead) summed over the half slabs of one
+    slab's level2_mass record"""
+    today = sum(-(-(min(je, M) - j0) // (2 * BLOCK)) for j0, je in iv if je > j0)
+    tiles = dead = 0
+    for hs in range(rec["live"].shape[0]):
+        lv = dict(zip(rec["blocks"].tolist(), rec["live"][hs].tolist()))
+        tiles += len(walk_live(iv, lambda t: lv.get(t, False), M))
+        dead += int((~rec["live"][hs]).sum())
+    return today * rec["live"].shape[0], tiles, rec["blocks"].size * rec["live"].shape[0], dead
+
+
 def balanced_lines(x, y, h, n, eps_list, n_slabs):
     """The mass rule on today's order of the sorted p = 2 call and on the balanced one (balanced_order): first level, runs, gap closing,
     tiles, and the second level on a sample of slabs scaled to all of them by the first-level fraction."""
@@ -452,9 +500,13 @@ def balanced_lines(x, y, h, n, eps_list, n_slabs):
                     f"{r.mean():.1f} max {r.max()}, slabs over {RUNS} runs {(r > RUNS).sum()}, kept blocks {int(keep.sum())} + {int(closed.sum() - keep.sum())} "
                     f"by gap closing, 512-column tiles {sum(tiles_of(closed[c]) for c in range(C))}")
             if len(slabs):
-                ev, k1, _ = level2_mass(xs, ys, hs, eps, closed, L, slabs)
+                ev, k1, rec = level2_mass(xs, ys, hs, eps, closed, L, slabs)
                 line += (f"; on {len(slabs)} slabs: first level {k1 / (rows * n):.4f}, evaluated after the second {ev / (rows * n):.4f}, "
                          f"scaled to all slabs {ev / k1 * first:.4f}")
+                cc = np.array([chunk_counts(rec[c], intervals_of(closed[c]), n) for c in slabs if not closed[c].all()]).sum(0)
+                if cc.ndim and cc[0]:
+                    line += (f"; chunk level (half slabs of {CHUNK} rows): {cc[3] / cc[2]:.4f} of the walked blocks dead, tiles staged "
+                             f"{cc[1]} against {cc[0]} ({cc[1] / cc[0]:.4f})")
             print(line, flush=True)
 
 
