@@ -102,7 +102,7 @@ static int softmin_step(const char* fn, const void* x, const void* y, const floa
             // (the bound takes the column vector the kernels form: logw + pot / eps)
             if (p == 2)
                 prune_ranges(a.xs, a.ys, a.col0, step.pot, 1.0f / eps, N, M, D, in_dtype, eps, a.ranges_i, a.slices_i, a.red, a.blocks, a.groups, a.home,
-                             a.t2, a.mlb, a.t1, st);
+                             a.t2, a.mlb, a.t1, a.refs, st);
             rc = sorted_inner(fn, a, x, a.col0, N, M, D, eps, p, in_dtype, flags, st, step);
             if (rc) return rc;
             scatter_f32(a.out, a.perm_x, out, N, st, 1, a.hint_x);
@@ -164,7 +164,7 @@ int glhip_prune_inspect(const void* x, const void* y, const float* logw, const f
     if (hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a.t2), (int)0xFF800000u, (size_t)((N + 31) / 32), st) != hipSuccess)
         return fail(GLHIP_ELAUNCH, "%s: memset failed: %s", fn, hipGetErrorString(hipGetLastError()));
     prune_ranges(a.xs, a.ys, a.col0, pot ? a.col1 : nullptr, 1.0f / eps, N, M, D, in_dtype, eps, a.ranges_i, a.slices_i, a.red, a.blocks, a.groups,
-                 a.home, a.t2, a.mlb, a.t1, st);
+                 a.home, a.t2, a.mlb, a.t1, a.refs, st);
     auto copy = [&](void* dst, const void* src, size_t bytes) {
         return !dst || hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st) == hipSuccess;
     };

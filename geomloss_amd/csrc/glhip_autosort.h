@@ -86,6 +86,45 @@ constexpr int kSortRowsPerVoxel = 256;
 //   infinity; the kernel's ub carries its slack on the keep side.  Special blocks and groups are never dropped and enter no sum; a
 //   slab with home = -1 gets no threshold work; a tile without a finite seed gets t2 = -inf.  The thresholds live in the sort scratch.
 //   Headline law at 1e6: tools/prune_model.py, profiles/r10_*.
+//   Sum reference (library 136).  The two mass budgets above are stated relative to ONE term the row has (e^Mlb, e^ms); the guarantee
+//   is relative to the row SUM S_i = sum_j e^(h_j - |x_i - y_j|^2 / (2 eps)), which exceeds its largest term by ln(S_i / max) nats
+//   (bench law 1.35, a uniform dual vector 7.5 at the headline density).  Both budgets now refer to a lower bound of log S_i that the
+//   records give; everything else — Mlb, the home block, the bucket grids anchored at Mlb - L and ms - L, t1 and t2 as stored, the
+//   term rule, the three shares — is what it was.
+//     Notation.  lse_dn(S): the record's rounded-up lse lowered again, in float64, by twice its own slack for a group and four times
+//       for a block (a block's record is rounded up twice: it is formed from its groups' rounded-up values), lse_dn(v, n) =
+//       v - n 2^-20 (|v| + 8).  The float32 value before rounding up is within 0.3 slacks of the true lse (glhip_prune.hip, lse_up),
+//       so a group's record is at most 1.3 slacks and a block's at most 2.3 slacks + 2.7 x 2^-20 < 3 slacks above the truth (the
+//       groups' slacks s (|g| + 8) enter a block with their weights e^(g - b): sum_g w_g |g| <= |b| + sum_g w_g ln(1 / w_g) <= |b| +
+//       ln 8): lse_dn(S) <= log sum_{j in S} e^(h_j).  dmaxpen(A, S) = dmax(A, S)^2 / (2 eps), dmax the largest distance between the
+//       box (or point) A and the box of S, float64 from the exact float32 corners.
+//     First level.  Slb(R) = log sum_T e^(lse_dn(T) - dmaxpen(R, T)) over the non-special blocks T, lowered by kPruneSumSlack (float64
+//       sums of at most 2^23 terms; terms below e^-40 of e^Mlb are left out, which only lowers it), and max(Slb, Mlb).  For every
+//       row i of R and column j of T, |x_i - y_j| <= dmax(R, T), so S_i >= sum_T e^(-dmaxpen(R, T)) sum_{j in T} e^(h_j) >= e^Slb(R).
+//       The masses of the first-level histogram are e^(k(T) - Slb(R)): the kernel keeps them relative to Mlb and multiplies the
+//       budget by e^(Slb - Mlb) instead, which is the same comparison.  Dropped: at most kPruneBudget1 e^Slb <= kPruneBudget1 S_i.
+//     Reference set.  Per slab a list of at most kPruneRefBlocks blocks with the largest scores s(T) = lse_dn(T) - dmaxpen(R, T),
+//       ranked on a grid: cell(T) = floor((Mlb + kPruneRefTop - s(T)) kPruneRefCellsPerNat) (>= 0: lse(T) <= hmax(T) + ln 256 and
+//       hmax(T) - dmaxpen(R, T) <= Mlb), whole cells taken from cell 0 up while at most kPruneRefBlocks - 1 blocks are in, then the
+//       home block if it is not among them.  Blocks of one cell go in together or not at all, so no tie needs breaking and the list
+//       is a function of the records alone; it is written in ascending block order, unused entries -1.  (A list that takes the
+//       largest scores one by one would win 1.5 points more of the evaluated pairs on the bench law; it needs a sort per slab.)
+//     Second level.  For every row, ls_i = log sum_G e^(lse_dn(G) - dmaxpen(x_i, G)) over the non-special groups G of the reference
+//       blocks (point to box, float64), the exponentials in float32 on arguments relative to the row's seed — or to the last term
+//       that lay more than 60 nats above the reference: it becomes the reference, and what was summed before it, now under
+//       128 e^-60 of the sum, is scaled down with it — lowered by kPruneLsSlack = 1e-4: the float32 argument (at most 60 nats:
+//       3.6e-6), the hardware exponential __expf (the argument times log2 e, 87 log2 units at most, rounds by 5.2e-6; v_exp_f32
+//       itself 1 ulp), the sum of 128 terms (7.6e-6) and logf (2 ulp of at most 65: 1.6e-5) stay under 3.3e-5.
+//       S_i >= e^ls_i as above, and S_i >= e^seed_i, the row's exact largest exponent over the home block (one term of the same sum; rows
+//       of one tile can lie a hundred nats apart when the dual values do).  ls(W) = min_i max(seed_i, ls_i) >= ms(W); the masses of the
+//       tile's histogram are e^(k(W, G) - ls(W)), again as a budget multiplied by e^(ls - ms).  Dropped: at most kPruneBudget2
+//       e^ls(W) <= kPruneBudget2 S_i for every row of the tile.  With the term rule's 2^-26 / e of the largest term <= 2^-26 / e S_i
+//       the three pieces stay under 2^-26 S_i.  The underflow argument of prune_first_kept holds: the budgets only grew.
+//     Special values: special blocks and groups enter no sum and no list; a slab with a non-finite coordinate or Mlb keeps everything;
+//       a tile without a finite seed gets t2 = -inf; a Slb or ls that is not finite, or below Mlb or ms, falls back to Mlb or ms.
+//     Bench problem at 1e6 (tools/prune_model.py --balanced, profiles/sum_reference.txt): first level keeps 0.2378 -> 0.2287, 512-column
+//     tiles 1 946 177 -> 1 873 861, evaluated 0.1333 -> 0.1232 (-7.6 %); a uniform dual vector: 0.1820 -> 0.1378 (-24 %).  With 32
+//     reference blocks: 0.1220 and 0.1358 in the model; what prune_tiles_kernel then costs on the device: profiles/sum_reference.txt.
 constexpr int kPruneColBlock = 256;   // columns per column block T (a multiple of 64)
 constexpr int kPruneRuns = 160;       // runs of kept blocks per slab (the bench problem under the mass rule: mean 71, max 175 — 8 of 3907 slabs
                                       // close their one-block gaps, 0.01 % more kept pairs: profiles/r10_prune_model.txt; with balanced
@@ -107,6 +146,14 @@ constexpr double kPruneBucketNats = 0.25;
 constexpr double kPruneMassShare = 0.5;                                                                           // the mass rule's part of the 2^-26
 constexpr double kPruneBudget1 = 1.4901161193847656e-08 * (1.0 - 1.0 / 2.718281828459045 - kPruneMassShare);      // 2^-26 (1 - 1 / e - 1 / 2)
 constexpr double kPruneBudget2 = 1.4901161193847656e-08 * kPruneMassShare;                                        // 2^-26 / 2
+// The sum reference (above): the reference list of a slab and the grid its scores are ranked on (32 nats below Mlb + kPruneRefTop,
+// kPruneRefTop >= ln 256 + the records' slack), and what the two lower bounds of the row sum are lowered by.
+constexpr int kPruneRefBlocks = 16;      // 8 and 32 modelled and 32 measured: profiles/sum_reference.txt
+constexpr double kPruneRefTop = 5.625;
+constexpr int kPruneRefCellsPerNat = 16;
+constexpr int kPruneRefCells = 512;
+constexpr double kPruneSumSlack = 1e-9;
+constexpr double kPruneLsSlack = 1e-4;
 
 struct PrunePlan {
     int nT;    // column blocks
@@ -145,10 +192,11 @@ size_t prune_blocks_bytes(int M);
 size_t prune_groups_bytes(int M);
 // the kept column intervals of every slab of the sorted clouds xs (N, D), ys (M, D) for the column vector h (+ pot * pot_scale); for the
 // second level: the records of the groups of 32 columns (`groups`, prune_groups_bytes), every slab's home block (`home`, C ints) and the
-// mass-rule threshold of every tile of 32 rows (`t2`, ceil(N / 32) floats); for glhip_prune_inspect: every slab's Mlb and t1 (C doubles each)
+// mass-rule threshold of every tile of 32 rows (`t2`, ceil(N / 32) floats); for glhip_prune_inspect: every slab's Mlb and t1 (C doubles each);
+// between the two kernels: every slab's reference blocks (`refs`, C x kPruneRefBlocks ints)
 void prune_ranges(const void* xs, const void* ys, const float* h, const float* pot, float pot_scale, int N, int M, int D, int in_dtype,
                   float eps, int32_t* ranges_i, int32_t* slices_i, int32_t* red, void* blocks, void* groups, int32_t* home, float* t2,
-                  double* mlb, double* t1, hipStream_t st);
+                  double* mlb, double* t1, int32_t* refs, hipStream_t st);
 // L of the bound in nats
 inline double prune_L(int M) { return std::log((double)M) + 26.0 * 0.6931471805599453 + kPruneMarginNats; }
 // sub-voxels per axis of the sorted p = 2 call: sub^D ~ 8 sub-voxels of ~32 points in a voxel of kSortRowsPerVoxel
@@ -171,7 +219,8 @@ struct AutoSort {
     void* groups = nullptr;                 // the same per group of 32 columns, and every slab's home block: the second level
     int32_t* home = nullptr;
     float* t2 = nullptr;                    // per tile of 32 rows: the second level's mass-rule threshold; per slab: Mlb and the first
-    double *mlb = nullptr, *t1 = nullptr;   // level's threshold.  All three live in the sort scratch, dead once both sorts have run
+    double *mlb = nullptr, *t1 = nullptr;   // level's threshold.  All three live in the sort scratch, dead once both sorts have run,
+    int32_t* refs = nullptr;                // and so do the reference blocks of every slab (the sum reference)
     void* inner_ws = nullptr;
     size_t inner_bytes = 0;
 };
@@ -235,10 +284,13 @@ inline int autosort_prepare(AutoSort& a, const void* x, const void* y, int N, in
                       slabs ? 1 : prune_sort_sub(D), a.hint_y);
     if (rc) return rc;
     if (slabs) slab_ranges(N, M, a.ranges_i, a.slices_i, a.red, st);
-    // (the scratch holds 20 bytes per point of the larger cloud and more: N / 8 + 16 C bytes fit many times over)
+    // (the scratch holds 20 bytes per point of the larger cloud and more: N / 8 + (16 + 4 kPruneRefBlocks) C bytes, 0.7 bytes per
+    // row, fit many times over)
+    static_assert(kPruneRefBlocks <= 256, "the reference lists stay under 4 bytes per row");
     a.mlb = reinterpret_cast<double*>(scratch);
     a.t1 = a.mlb + a.C;
     a.t2 = reinterpret_cast<float*>(a.t1 + a.C);
+    a.refs = reinterpret_cast<int32_t*>(a.t2 + (N + 31) / 32);
     a.inner_ws = w + off;
     a.inner_bytes = workspace_bytes - off;
     a.on = true;

@@ -1,5 +1,6 @@
 // glhip_prune.hip — the exact pruning of the sorted p = 2 call: what is kept of every slab of sorted rows, on the device:
-//   prune_ranges   column-block and group records -> per slab: Mlb, t1, home block, kept blocks as column intervals -> per tile: t2
+//   prune_ranges   column-block and group records -> per slab: Mlb, t1, home block, reference blocks, kept blocks as column intervals
+//                  -> per tile: t2
 // Declared in glhip_autosort.h, which also holds the reasoning (the bound and why it is exact, the second level, the mass rule and its
 // budgets); the kept blocks of a slab as 64-bit words: glhip_prune_words.h; the second level's test itself: glhip_softmin_x32.h.
 #include <climits>
@@ -27,6 +28,18 @@ struct ColBlock {           // one block of kPruneColBlock sorted columns
 // 2^-20 (|lse| + 8): 16 ulp of the value plus 7.6e-6, several times the sum of those.
 constexpr float kPruneLseSlack = 9.5367431640625e-7f;      // 2^-20
 __device__ __forceinline__ float lse_up(float v) { return v + kPruneLseSlack * (__builtin_fabsf(v) + 8.f); }
+// a record lowered by `times` its own slack, in float64: never above the true log sum exp for times = 2 (a group's record) and
+// times = 4 (a block's: rounded up twice) — the sum reference of glhip_autosort.h.  -inf stays -inf.
+__device__ __forceinline__ double lse_dn(float v, double times) {
+    return (double)v - times * (double)kPruneLseSlack * ((double)__builtin_fabsf(v) + 8.0);
+}
+// the cell of a block's score on the grid its slab's reference list is ranked on (kPruneRefCells: not on it); the score of a block
+// whose dual values are all -inf is -inf
+__device__ __forceinline__ int prune_ref_cell(double score, double mlb) {
+    const double q = (mlb + kPruneRefTop - score) * (double)kPruneRefCellsPerNat;
+    if (!(q < (double)kPruneRefCells)) return kPruneRefCells;
+    return q > 0.0 ? (int)q : 0;
+}
 
 static_assert(kHomeCols == kPruneColBlock && kPruneColBlock % 64 == 0 && sizeof(GroupBox) == 32, "block / group records");
 
@@ -187,10 +200,12 @@ template <typename T>
 __global__ void __launch_bounds__(256) prune_slabs_kernel(const T* __restrict__ xs, int N, int M, int D, const ColBlock* __restrict__ blocks,
                                                           int nT, int PB, int S, double inv2eps, double L, int32_t* __restrict__ ranges_i,
                                                           int32_t* __restrict__ slices_i, int32_t* __restrict__ red, int32_t* __restrict__ home,
-                                                          double* __restrict__ mlb_out, double* __restrict__ t1_out) {
+                                                          double* __restrict__ mlb_out, double* __restrict__ t1_out, int32_t* __restrict__ refs_out) {
     __shared__ int buf[256];
     __shared__ double hist[kPruneBuckets + 1];      // (the last entry: the underflow bucket)
     __shared__ int first_kept;
+    __shared__ int cells[kPruneRefCells];           // blocks per cell of the score grid: the reference list (the sum reference)
+    __shared__ int ref_cells, ref_n, ref_l[kPruneRefBlocks];
     __shared__ unsigned long long mask[kPruneMaskWords];
     __shared__ int32_t gaps[kPruneGaps];
     __shared__ float wlo[4][3], whi[4][3];
@@ -264,26 +279,54 @@ __global__ void __launch_bounds__(256) prune_slabs_kernel(const T* __restrict__ 
         return (double)b.lse - dmin2 * inv2eps;
     };
     for (int q = tid; q <= kPruneBuckets; q += 256) hist[q] = 0.0;
+    for (int q = tid; q < kPruneRefCells; q += 256) cells[q] = 0;
+    if (tid == 0) ref_n = 0;
     __syncthreads();
+    // The same pass sums e^(s(T) - Mlb) of the scores s(T) = lse_dn(T) - dmaxpen(R, T) for Slb(R), the lower bound of every row's SUM
+    // that the budget refers to (terms below e^-40: left out), and counts the blocks per cell of the score grid
+    double ssum = 0.0;
     if (!keep_all) {
         for (int t = tid; t < nT; t += 256) {
             const ColBlock b = blocks[t];
             if (__builtin_isnan(b.lse)) continue;
-            const double key = block_key(b);
+            double dmin2, dmax2;
+            box_d2(rlo, rhi, b, D, dmin2, dmax2);
+            const double score = lse_dn(b.lse, 4.0) - dmax2 * inv2eps;
+            if (score - mlb > -40.0) ssum += exp(score - mlb);
+            const int cell = prune_ref_cell(score, mlb);
+            if (cell < kPruneRefCells) atomicAdd(&cells[cell], 1);
+            const double key = (double)b.lse - dmin2 * inv2eps;
             const int q = prune_bucket(key, lo_key);
             if (q >= kPruneBuckets) continue;      // above the range: never added, so no exp for it
             const double mass = exp(key - mlb);
             if (mass > 0.0) atomicAdd(&hist[q < 0 ? kPruneBuckets : q], mass);
         }
     }
+    for (int off = 32; off > 0; off >>= 1) ssum += __shfl_xor(ssum, off, 64);
+    __syncthreads();      // (also: every read of wm above is done)
+    if (lane == 0) wm[wave] = ssum;
     __syncthreads();
     if (tid == 0) {
-        first_kept = keep_all ? 0 : prune_first_kept(hist, hist[kPruneBuckets], kPruneBudget1);
+        // the masses stay relative to Mlb and the budget is multiplied by e^(Slb - Mlb): the same comparison
+        const double sum = (wm[0] + wm[1]) + (wm[2] + wm[3]);
+        double slb = mlb;
+        if (!keep_all && sum > 0.0 && __builtin_isfinite(sum)) slb = fmax(mlb, mlb + log(sum) - kPruneSumSlack);
+        first_kept = keep_all ? 0 : prune_first_kept(hist, hist[kPruneBuckets], kPruneBudget1 * exp(slb - mlb));
         mlb_out[k] = mlb;
         t1_out[k] = keep_all ? -INFINITY : lo_key + first_kept * kPruneBucketNats;
+        // whole cells from the top while at most kPruneRefBlocks - 1 blocks are in: one place stays for the home block
+        int nc = 0;
+        for (int n = 0; nc < kPruneRefCells && n + cells[nc] <= kPruneRefBlocks - 1; ++nc) n += cells[nc];
+        ref_cells = nc;
     }
     __syncthreads();
-    const int fk = first_kept;
+    const int fk = first_kept, rc = ref_cells;
+    // a block of the reference list: on the kept cells of the score grid, or the home block
+    auto ref_take = [&](int t, const ColBlock& b, double dmax2) {
+        if (t != best && prune_ref_cell(lse_dn(b.lse, 4.0) - dmax2 * inv2eps, mlb) >= rc) return;
+        const int i = atomicAdd(&ref_n, 1);
+        if (i < kPruneRefBlocks) ref_l[i] = t;
+    };
     auto kept = [&](int t) {
         if (keep_all) return true;
         const ColBlock b = blocks[t];
@@ -299,15 +342,43 @@ __global__ void __launch_bounds__(256) prune_slabs_kernel(const T* __restrict__ 
         if (masked) {      // one word per wavefront and step
             for (int w = wave; w < nW; w += 4) {
                 const int t = 64 * w + lane;
-                const unsigned long long m = __ballot(t < nT && kept(t));
+                bool kp = t < nT;
+                if (kp && !keep_all) {      // (kept(t), and the reference list from the same distances)
+                    const ColBlock b = blocks[t];
+                    if (!__builtin_isnan(b.lse)) {
+                        double dmin2, dmax2;
+                        box_d2(rlo, rhi, b, D, dmin2, dmax2);
+                        kp = prune_bucket((double)b.lse - dmin2 * inv2eps, lo_key) >= fk;
+                        ref_take(t, b, dmax2);
+                    }
+                }
+                const unsigned long long m = __ballot(kp);
                 if (lane == 0) mask[w] = m;
                 all &= m == (nT - 64 * w >= 64 ? ~0ull : (1ull << (nT - 64 * w)) - 1ull);
             }
         } else if (!keep_all) {
             for (int t = tid; t < nT && all; t += 256) all = kept(t) ? 1 : 0;
+            for (int t = tid; t < nT; t += 256) {
+                const ColBlock b = blocks[t];
+                if (__builtin_isnan(b.lse)) continue;
+                double dmin2, dmax2;
+                box_d2(rlo, rhi, b, D, dmin2, dmax2);
+                ref_take(t, b, dmax2);
+            }
         }
-        all = __syncthreads_and(all);      // (also: the bit set is written)
+        all = __syncthreads_and(all);      // (also: the bit set and the reference list are written)
         if (tid == 0) home[k] = (keep_all || all) ? -1 : best;
+        // the list in ascending block order, whatever order the atomics gave it; unused entries: -1
+        if (tid < kPruneRefBlocks) {
+            const int n = min(ref_n, kPruneRefBlocks);
+            int rank = tid, v = -1;
+            if (tid < n) {
+                v = ref_l[tid];
+                rank = 0;
+                for (int j = 0; j < n; ++j) rank += ref_l[j] < v;
+            }
+            refs_out[(long)k * kPruneRefBlocks + rank] = v;
+        }
     }
     auto kept_at = [&](int t) { return masked ? ((mask[t >> 6] >> (t & 63)) & 1ull) != 0 : kept(t); };
     // one walk over the blocks: the number of runs for gap length g, and (EMIT) the pieces written out
@@ -403,13 +474,24 @@ __global__ void __launch_bounds__(256) prune_slabs_kernel(const T* __restrict__ 
 // block, float64 from the points themselves — then one histogram per tile of the keys k(W, G) = lse(G) - dmin(W,G)^2 / (2 eps) of the
 // groups G inside the slab's emitted intervals, starting at ms(W) - L, and from it the threshold t2(W): written in log2 units, the
 // reducing kernel's, as a float32 rounded toward minus infinity.  Thread = row for the seeds, thread = (group, tile) for the histograms.
+// The sum reference (glhip_autosort.h): the budget is a share of e^ls(W), ls(W) = min_i max(seed_i, ls_i), where ls_i — thread = row
+// again — is the log of the sum over the groups G of the slab's reference blocks (`refs`, staged in LDS with their lowered records) of
+// e^(lse_dn(G) - dmaxpen(x_i, G)): a lower bound of the row's SUM where the seed is one term of it.
+struct RefGroup {           // one group of a reference block: its box and lse_dn (-inf: no such group, or a special one)
+    float lo[3], hi[3];
+    double dn;
+};
+constexpr int kRefGroups = kPruneRefBlocks * (kPruneColBlock / 32);
 static_assert(kPruneRuns + kPruneGrid <= 256 && kSortSlab == 256, "one thread per interval slot / per row");
 template <typename T>
 __global__ void __launch_bounds__(256) prune_tiles_kernel(const T* __restrict__ xs, const T* __restrict__ ys, const float* __restrict__ h,
                                                           const float* __restrict__ pot, float pot_scale, int N, int M, int D,
                                                           const GroupBox* __restrict__ groups, const int32_t* __restrict__ red, int S,
-                                                          const int32_t* __restrict__ home, double inv2eps, double L, float* __restrict__ t2) {
+                                                          const int32_t* __restrict__ home, const int32_t* __restrict__ refs, double inv2eps,
+                                                          double L, float* __restrict__ t2) {
     constexpr int kTiles = kSortSlab / 32;
+    __shared__ RefGroup rg[kRefGroups];
+    __shared__ double lsw[kTiles];
     __shared__ int buf[256];
     __shared__ int first_group[256];
     __shared__ double hy[kPruneColBlock][3], hh[kPruneColBlock];
@@ -428,6 +510,26 @@ __global__ void __launch_bounds__(256) prune_tiles_kernel(const T* __restrict__ 
         hh[tid] = real ? (double)(pot ? __builtin_fmaf(pot[j], pot_scale, h[j]) : h[j]) : -INFINITY;
     }
     for (int q = tid; q < kTiles * (kPruneBuckets + 1); q += 256) (&hist[0][0])[q] = 0.0;
+    // the groups of the reference blocks (the list is ascending, its unused entries at the end)
+    const int n_ref = __syncthreads_count(tid < kPruneRefBlocks && refs[(long)k * kPruneRefBlocks + tid] >= 0);
+    for (int q = tid; q < n_ref * (kPruneColBlock / 32); q += 256) {
+        const int t = refs[(long)k * kPruneRefBlocks + q / (kPruneColBlock / 32)];
+        const long g = (long)t * (kPruneColBlock / 32) + q % (kPruneColBlock / 32);
+        RefGroup r;
+        for (int d = 0; d < 3; ++d) r.lo[d] = r.hi[d] = 0.f;
+        r.dn = -INFINITY;
+        if (t >= 0 && t < (M + kPruneColBlock - 1) / kPruneColBlock && g < (M + 31) / 32) {
+            const GroupBox b = groups[g];
+            if (!b.special && !__builtin_isnan(b.lse)) {
+                for (int d = 0; d < 3; ++d) {
+                    r.lo[d] = b.lohi[d][0];
+                    r.hi[d] = b.lohi[d][1];
+                }
+                r.dn = lse_dn(b.lse, 2.0);
+            }
+        }
+        rg[q] = r;
+    }
     // this thread's row, its tile's box and seed
     const bool row = r0 + tid < r1;
     float x[3] = {0.f, 0.f, 0.f};
@@ -456,11 +558,41 @@ __global__ void __launch_bounds__(256) prune_tiles_kernel(const T* __restrict__ 
         // the tile's smallest seed; a seed that is not finite (none should be: the home block attains a finite Mlb) turns the rule off
         int ok = !row || __builtin_isfinite(seed);
         double v = row ? seed : INFINITY;
+        // ls_i: float32 exponentials on arguments relative to the row's own seed, the result lowered by kPruneLsSlack.  A term more
+        // than 60 nats above the reference (dual values hundreds of nats apart at a small eps: another block can hold far more than
+        // the home block does) becomes the reference, so no exponential overflows; what was summed so far is scaled down with it.
+        double ls = INFINITY;
+        if (row && __builtin_isfinite(seed)) {
+            double mref = seed;
+            float acc = 0.f;
+            for (int q = 0; q < n_ref * (kPruneColBlock / 32); ++q) {
+                const RefGroup& r = rg[q];
+                double d2 = 0.0;
+                for (int d = 0; d < 3; ++d) {
+                    const double far = fmax(fabs(xd[d] - (double)r.lo[d]), fabs((double)r.hi[d] - xd[d]));
+                    d2 = fma(far, far, d2);
+                }
+                double arg = r.dn - d2 * inv2eps - mref;      // (dn = -inf: e^-inf = 0)
+                if (arg > 60.0) {
+                    acc *= __expf((float)-arg);
+                    mref += arg;
+                    arg = 0.0;
+                }
+                acc += __expf((float)arg);      // (the hardware exponential: its error is part of kPruneLsSlack)
+            }
+            // the seed is one term of the same sum: the better of the two bounds (acc = 0, every reference term under e^-87 of
+            // the seed in float32: the seed)
+            ls = fmax(seed, mref + (double)logf(acc) - kPruneLsSlack);
+        }
         for (int off = 16; off > 0; off >>= 1) {
             v = fmin(v, __shfl_xor(v, off, 64));
+            ls = fmin(ls, __shfl_xor(ls, off, 64));      // (a NaN — none should be — is dropped here or fails the test below)
             ok &= __shfl_xor(ok, off, 64);
         }
-        if ((tid & 31) == 0) ms[w] = (ok && r0 + 32 * w < r1) ? v : NAN;      // NaN: no rows, or no finite seed
+        if ((tid & 31) == 0) {
+            ms[w] = (ok && r0 + 32 * w < r1) ? v : NAN;      // NaN: no rows, or no finite seed
+            lsw[w] = (__builtin_isfinite(ls) && ls > v) ? ls : v;
+        }
     }
     // the groups of the emitted intervals, numbered through: first_group[q] = groups before interval q
     const int32_t* slots = red + 2 * (long)k * S;
@@ -526,7 +658,8 @@ __global__ void __launch_bounds__(256) prune_tiles_kernel(const T* __restrict__ 
         const double m = ms[tid];
         float out = -INFINITY;
         if (m == m) {
-            const int fk = prune_first_kept(hist[tid], hist[tid][kPruneBuckets], kPruneBudget2);
+            // the masses stay relative to ms and the budget is multiplied by e^(ls - ms): the same comparison
+            const int fk = prune_first_kept(hist[tid], hist[tid][kPruneBuckets], kPruneBudget2 * exp(lsw[tid] - m));
             const double v = (m - L + fk * kPruneBucketNats) * 1.4426950408889634;
             out = (float)v;
             if ((double)out > v) out = nextafterf(out, -INFINITY);
@@ -538,7 +671,7 @@ __global__ void __launch_bounds__(256) prune_tiles_kernel(const T* __restrict__ 
 template <typename T>
 void prune_ranges_typed(const void* xs_, const void* ys_, const float* h, const float* pot, float pot_scale, int N, int M, int D, float eps,
                         int32_t* ranges_i, int32_t* slices_i, int32_t* red, void* blocks_, void* groups_, int32_t* home, float* t2,
-                        double* mlb, double* t1, hipStream_t st) {
+                        double* mlb, double* t1, int32_t* refs, hipStream_t st) {
     const T *xs = static_cast<const T*>(xs_), *ys = static_cast<const T*>(ys_);
     const PrunePlan pp = prune_plan(M);
     const int C = (N + kSortSlab - 1) / kSortSlab;
@@ -548,8 +681,8 @@ void prune_ranges_typed(const void* xs_, const void* ys_, const float* h, const 
     const double L = prune_L(M);
     hipLaunchKernelGGL(prune_blocks_kernel<T>, dim3((pp.nT + 3) / 4), dim3(256), 0, st, ys, h, pot, pot_scale, M, D, pp.nT, blocks, groups);
     hipLaunchKernelGGL(prune_slabs_kernel<T>, dim3(C), dim3(256), 0, st, xs, N, M, D, blocks, pp.nT, pp.PB, pp.S, inv2eps, L, ranges_i, slices_i,
-                       red, home, mlb, t1);
-    hipLaunchKernelGGL(prune_tiles_kernel<T>, dim3(C), dim3(256), 0, st, xs, ys, h, pot, pot_scale, N, M, D, groups, red, pp.S, home, inv2eps, L,
+                       red, home, mlb, t1, refs);
+    hipLaunchKernelGGL(prune_tiles_kernel<T>, dim3(C), dim3(256), 0, st, xs, ys, h, pot, pot_scale, N, M, D, groups, red, pp.S, home, refs, inv2eps, L,
                        t2);
 }
 
@@ -562,9 +695,9 @@ size_t prune_groups_bytes(int M) { return (size_t)((M + 31) / 32) * sizeof(Group
 
 void prune_ranges(const void* xs, const void* ys, const float* h, const float* pot, float pot_scale, int N, int M, int D, int in_dtype,
                   float eps, int32_t* ranges_i, int32_t* slices_i, int32_t* red, void* blocks, void* groups, int32_t* home, float* t2,
-                  double* mlb, double* t1, hipStream_t st) {
-    if (in_dtype == GLHIP_F32) prune_ranges_typed<float>(xs, ys, h, pot, pot_scale, N, M, D, eps, ranges_i, slices_i, red, blocks, groups, home, t2, mlb, t1, st);
-    else prune_ranges_typed<bf16_t>(xs, ys, h, pot, pot_scale, N, M, D, eps, ranges_i, slices_i, red, blocks, groups, home, t2, mlb, t1, st);
+                  double* mlb, double* t1, int32_t* refs, hipStream_t st) {
+    if (in_dtype == GLHIP_F32) prune_ranges_typed<float>(xs, ys, h, pot, pot_scale, N, M, D, eps, ranges_i, slices_i, red, blocks, groups, home, t2, mlb, t1, refs, st);
+    else prune_ranges_typed<bf16_t>(xs, ys, h, pot, pot_scale, N, M, D, eps, ranges_i, slices_i, red, blocks, groups, home, t2, mlb, t1, refs, st);
 }
 
 }  // namespace glhip

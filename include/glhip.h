@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 135 /* 0.1.35 */
+#define GLHIP_VERSION 136 /* 0.1.36 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
@@ -161,6 +161,13 @@ extern "C" {
                                   32 points (csrc/glhip_balance.h), which the slabs, blocks, tiles and groups of both levels are aligned
                                   to: their boxes no longer straddle two voxels.  The guarantee does not depend on the order; perm_x / perm_y
                                   of glhip_prune_inspect show it.  The last N mod 1024 (M mod 1024) points keep the path order.
+                                  Version 136: the two mass budgets are shares of a lower bound of the row SUM, not of one term of it.
+                                  Per slab, Slb = log sum_T e^(lse_dn(T) - dmax(R, T)^2 / (2 eps)) over the column blocks (lse_dn: the
+                                  rounded-up record lowered by twice its slack, four times for a block); per row of a tile the same sum
+                                  over the groups of at most 16 reference blocks of its slab, point to box, or the row's exact largest
+                                  exponent over the home block where that is more.  A smooth dual vector gains ~6 nats of threshold, the
+                                  bench law 1-1.7; Mlb, home, the bucket grids and the stored t1 / t2 mean what they did, and
+                                  glhip_prune_inspect shows them (csrc/glhip_autosort.h, "Sum reference"; profiles/sum_reference.txt).
                                   Here this flag means the dense xd / x32 launch. */
 
 /* Environment variables read ONCE per process by the library itself (test / tuning knobs; everything else is an argument):

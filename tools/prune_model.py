@@ -15,6 +15,10 @@ the groups that pass; ``compact_order2`` is the order of the sorted p = 2 call (
 sub-voxels inside).  ``level2`` also verifies on the points themselves that no skipped pair holds a term above its row's true
 maximum - L.  The model's test is exact arithmetic; the kernel's float32 test keeps a little more (its slack is on the keep side).
 
+The mass rule (``plan_mass`` / ``level2_mass``) takes its two budgets relative to a lower bound of the row SUM (glhip_autosort.h, "Sum
+reference": Slb per slab from the block records, ls per tile from the group records of the slab's reference blocks);
+``reference="term"`` is the rule before library 136, relative to one term of the sum, and ``reference_lines`` prints one beside the other.
+
     python tools/prune_model.py [--n 1000000] [--eps 0.0025] [--slabs 40]     (the bench problem: bench.make_problem(n, seed=1000))
 """
 
@@ -256,6 +260,10 @@ BUDGET2 = 2.0**-26 * MASS_SHARE                  # second level's mass rule, rel
 CHUNK = 128                                      # the rows of one f16 x 2 workgroup, half a slab: the chunk-live rule below (model only)
 LSE_SLACK = np.float32(2.0**-20)                 # kPruneLseSlack
 LOG2E = 1.4426950408889634
+REF_BLOCKS = 16                                  # kPruneRefBlocks: reference blocks per slab (the sum reference, glhip_autosort.h)
+REF_TOP, REF_CELLS_PER_NAT, REF_CELLS = 5.625, 16, 512      # kPruneRefTop, kPruneRefCellsPerNat, kPruneRefCells: the grid the scores are ranked on
+SUM_SLACK = 1e-9                                 # kPruneSumSlack: Slb is lowered by this (float64 sums)
+LS_SLACK = 1e-4                                  # kPruneLsSlack: ls_i is lowered by this (the device sums float32 exponentials)
 
 
 def inv2eps_of(eps):
@@ -273,6 +281,39 @@ def lse_up(hp):
         v = np.where(fin, m + np.log(np.where(fin, s, 1.0)), m).astype(np.float32)
         up = (v + LSE_SLACK * (np.abs(v) + np.float32(8.0))).astype(np.float32)
     return np.where(fin, up, v).astype(np.float64)
+
+
+def lse_dn(v, times=2):
+    """The record v = lse_up(...) lowered by `times` of its own slack, in float64: never above the true log sum exp.  A group's record
+    is rounded up once (times = 2), a block's twice — it is formed from its groups' rounded-up values (times = 4)."""
+    v = np.asarray(v, np.float64)
+    with np.errstate(invalid="ignore"):
+        return np.where(np.isfinite(v), v - times * float(LSE_SLACK) * (np.abs(v) + 8.0), v)
+
+
+def logsumexp_rows(a):
+    """log sum exp over the last axis, float64; a row without a finite entry gives -inf"""
+    m = a.max(-1)
+    fin = np.isfinite(m)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        s = np.exp(a - np.where(fin, m, 0.0)[..., None]).sum(-1)
+        return np.where(fin, m + np.log(np.where(fin, s, 1.0)), -np.inf)
+
+
+def reference_blocks(score, mlb, home, K=None):
+    """prune_slabs_kernel's reference list of one slab: the blocks are ranked by their score on a grid of 1 / REF_CELLS_PER_NAT nats
+    below Mlb + REF_TOP (no score lies above it), and whole cells are taken from the top while at most K - 1 blocks are in; the home
+    block is always in.  Ascending block numbers."""
+    K = REF_BLOCKS if K is None else K
+    with np.errstate(invalid="ignore"):
+        q = np.floor((mlb + REF_TOP - score) * REF_CELLS_PER_NAT)
+    ok = np.isfinite(q) & (q < REF_CELLS)
+    cell = np.clip(np.where(ok, q, 0), 0, REF_CELLS - 1).astype(np.int64)
+    cum = np.cumsum(np.bincount(cell[ok], minlength=REF_CELLS))
+    n_cells = int(np.searchsorted(cum, K - 1, side="right"))       # cells 0 .. n_cells - 1 hold at most K - 1 blocks
+    take = ok & (cell < n_cells)
+    take[home] = True
+    return np.flatnonzero(take)
 
 
 def group_block_lse(h, M):
@@ -293,24 +334,26 @@ def bucket_of(key, lo):
 
 def first_kept(hist, under, budget):
     """prune_first_kept over the last axis: the first bucket whose mass would take the dropped sum past the budget"""
-    over = under[..., None] + np.cumsum(hist, -1) > budget
+    over = under[..., None] + np.cumsum(hist, -1) > np.asarray(budget, np.float64)[..., None]
     return np.where(over.any(-1), over.argmax(-1), BUCKETS)
 
 
-def plan_mass(xs, ys, h, eps):
+def plan_mass(xs, ys, h, eps, reference="sum", slb_out=None):
     """The first level under the mass rule: keep (C, nT) bool, Mlb (C,), t1 (C,), L — for finite inputs.  A slab that keeps every
-    block is what the device calls home = -1."""
+    block is what the device calls home = -1.  The budget is a share of e^Slb(R), Slb = log sum_T e^(lse_dn(T) - dmaxpen(R, T)) >= Mlb,
+    a lower bound of every row's SUM (reference = "term": of e^Mlb(R), as before library 136).  slb_out: a list that receives Slb (C,)."""
     M = ys.shape[0]
     rlo, rhi = boxes(xs, SLAB)
     blo, bhi = boxes(ys, BLOCK)
     nT = blo.shape[0]
     hmax = np.concatenate([h.astype(np.float64), np.full(nT * BLOCK - M, -np.inf)]).reshape(nT, BLOCK).max(1)
     _, blse = group_block_lse(h, M)
+    bdn = lse_dn(blse, 4)
     L = math.log(M) + 26 * math.log(2) + MARGIN
     i2e = inv2eps_of(eps)
     C = rlo.shape[0]
     keep = np.zeros((C, nT), bool)
-    mlb, t1 = np.zeros(C), np.zeros(C)
+    mlb, t1, slb = np.zeros(C), np.zeros(C), np.zeros(C)
     for c0 in range(0, C, 256):
         a, b = rlo[c0:c0 + 256, None], rhi[c0:c0 + 256, None]
         gap = np.maximum(np.maximum(blo[None] - b, a - bhi[None]), 0.0)
@@ -325,10 +368,17 @@ def plan_mass(xs, ys, h, eps):
         n = m.shape[0]
         flat = (np.arange(n)[:, None] * (BUCKETS + 2) + bk + 1).ravel()
         hist = np.bincount(flat, weights=mass.ravel(), minlength=n * (BUCKETS + 2)).reshape(n, BUCKETS + 2)
-        fk = first_kept(hist[:, 1:BUCKETS + 1], hist[:, 0], BUDGET1)
+        sl = m.copy()
+        if reference == "sum":
+            sl = logsumexp_rows(bdn[None] - dmax2 * i2e) - SUM_SLACK
+            sl = np.where(np.isfinite(sl) & (sl > m), sl, m)
+        fk = first_kept(hist[:, 1:BUCKETS + 1], hist[:, 0], BUDGET1 * np.exp(sl - m))
         mlb[c0:c0 + 256] = m
+        slb[c0:c0 + 256] = sl
         t1[c0:c0 + 256] = m - L + fk * BUCKET_NATS
         keep[c0:c0 + 256] = bk >= fk[:, None]
+    if slb_out is not None:
+        slb_out.append(slb)
     return keep, mlb, t1, L
 
 
@@ -346,7 +396,7 @@ def intervals_of(keep_row):
     return [(int(a) * BLOCK, int(b) * BLOCK) for a, b in zip(np.flatnonzero(d == 1), np.flatnonzero(d == -1))]
 
 
-def level2_mass(xs, ys, h, eps, keep, L, slabs, intervals=None):
+def level2_mass(xs, ys, h, eps, keep, L, slabs, intervals=None, reference="sum", ref_blocks=None):
     """The second level under the mass rule on the given slabs.  intervals: {slab: [(j0, je), ...]} to walk the device's emitted
     intervals instead of the runs of kept blocks.  Returns (pairs evaluated, pairs kept by the first level, per slab a dict with
     home, groups (the groups walked), ms, t2 (nats) per tile and skip (tiles, groups) bool).  A group is evaluated iff its key
@@ -354,7 +404,10 @@ def level2_mass(xs, ys, h, eps, keep, L, slabs, intervals=None):
     is bucket >= 0.  A chunk level between the two (modelled only — measured on the device and not kept, profiles/chunk_skip.txt):
     blocks (the column blocks walked) and live (2, blocks) bool per half slab of CHUNK rows — some group of the block lies in a bucket
     >= the first kept one of some row tile of the half slab, or the block is the home block; fk and top (tiles, blocks) are the first
-    kept bucket and the block's largest bucket per tile."""
+    kept bucket and the block's largest bucket per tile.
+    The budget is a share of e^ls(W): ls(W) = min_i max(seed_i, ls_i), ls_i = log sum_G e^(lse_dn(G) - dmaxpen(x_i, G)) - LS_SLACK over the
+    groups G of the slab's reference blocks (refs in the record; ref_blocks: K) — a lower bound of the row's SUM (reference = "term": of
+    e^ms(W), as before library 136).  ls (tiles,) joins the record."""
     N, M = xs.shape[0], ys.shape[0]
     x64, y64, h64 = xs.astype(np.float64), ys.astype(np.float64), h.astype(np.float64)
     rlo, rhi = boxes(xs, SLAB)
@@ -362,32 +415,45 @@ def level2_mass(xs, ys, h, eps, keep, L, slabs, intervals=None):
     glo, ghi = boxes(ys, GROUP)
     nT, nG = blo.shape[0], glo.shape[0]
     hmax = np.concatenate([h64, np.full(nT * BLOCK - M, -np.inf)]).reshape(nT, BLOCK).max(1)
-    glse, _ = group_block_lse(h, M)
+    glse, blse = group_block_lse(h, M)
+    gdn, bdn = lse_dn(glse, 2), lse_dn(blse, 4)
     gcols = np.minimum(GROUP, M - GROUP * np.arange(nG))
     i2e = inv2eps_of(eps)
     evaluated = kept1 = 0.0
     out = {}
+    per_block = BLOCK // GROUP
     for c in slabs:
         far = np.maximum(bhi - rlo[c], rhi[c] - blo)
-        home = int(np.argmax(hmax - (far**2).sum(-1) * i2e))
+        dmax2 = (far**2).sum(-1)
+        home = int(np.argmax(hmax - dmax2 * i2e))
+        refs = reference_blocks(bdn - dmax2 * i2e, float((hmax - dmax2 * i2e)[home]), home, ref_blocks)
+        rg = (refs[:, None] * per_block + np.arange(per_block)[None]).ravel()
+        rg = rg[rg < nG]
         hc = np.arange(home * BLOCK, min(M, (home + 1) * BLOCK))
         iv = intervals[c] if intervals is not None else intervals_of(keep[c])
         groups = np.concatenate([np.arange(j0 // GROUP, (min(je, M) + GROUP - 1) // GROUP) for j0, je in iv if je > j0])
         r1 = min(N, (c + 1) * SLAB)
-        ms, t2, skip, fks, top = [], [], [], [], []
+        ms, t2, skip, fks, top, lss = [], [], [], [], [], []
         blocks, inv = np.unique(groups // (BLOCK // GROUP), return_inverse=True)
         for w0 in range(c * SLAB, r1, TILE):
             xr = x64[w0:min(w0 + TILE, r1)]
             seed = (h64[hc][None] - ((xr[:, None, :] - y64[hc][None]) ** 2).sum(-1) * i2e).max(1)
             m = seed.min()
+            ls = m
+            if reference == "sum":
+                pfar = np.maximum(np.abs(xr[:, None, :] - glo[rg][None]), np.abs(ghi[rg][None] - xr[:, None, :]))
+                ls = float(np.maximum(logsumexp_rows(gdn[rg][None] - (pfar**2).sum(-1) * i2e) - LS_SLACK, seed).min())
+                ls = ls if np.isfinite(ls) and ls > m else m
             wlo, whi = xr.min(0), xr.max(0)
             gap = np.maximum(np.maximum(glo[groups] - whi, wlo - ghi[groups]), 0.0)
             key = glse[groups] - (gap**2).sum(-1) * i2e
             bk = bucket_of(key, m - L)
             with np.errstate(over="ignore"):
                 hist = np.bincount(bk + 1, weights=np.exp(key - m), minlength=BUCKETS + 2)
-            fk = int(first_kept(hist[1:BUCKETS + 1], hist[0], BUDGET2))
+            with np.errstate(over="ignore"):      # (rows hundreds of nats apart: an infinite budget drops every bucket, as on the device)
+                fk = int(first_kept(hist[1:BUCKETS + 1], hist[0], BUDGET2 * np.exp(np.float64(ls - m))))
             ms.append(m)
+            lss.append(ls)
             t2.append(m - L + fk * BUCKET_NATS)
             skip.append(bk < fk)
             fks.append(fk)
@@ -404,7 +470,8 @@ def level2_mass(xs, ys, h, eps, keep, L, slabs, intervals=None):
             live[hs] = blocks == home
             if top[rows].shape[0]:
                 live[hs] |= (top[rows] >= fks[rows, None]).any(0)
-        out[c] = dict(home=home, groups=groups, ms=np.array(ms), t2=np.array(t2), skip=np.array(skip), blocks=blocks, live=live, fk=fks, top=top)
+        out[c] = dict(home=home, groups=groups, ms=np.array(ms), t2=np.array(t2), skip=np.array(skip), blocks=blocks, live=live, fk=fks, top=top,
+                      ls=np.array(lss), refs=refs)
     return evaluated, kept1, out
 
 
@@ -510,16 +577,55 @@ def balanced_lines(x, y, h, n, eps_list, n_slabs):
             print(line, flush=True)
 
 
+def uniform_problem(n, seed=1000):
+    """the bench clouds with a uniform dual vector h = -ln n: smooth potentials, where the row sum exceeds its largest term most"""
+    x, y, h, eps = bench_problem(n, seed)
+    return x, y, np.full(n, -math.log(n), np.float32), eps
+
+
+def reference_lines(n, eps_list, n_slabs, ref_blocks=(REF_BLOCKS,)):
+    """The old reference of the two mass budgets (one term the row has: e^Mlb, e^ms) beside the new one (a lower bound of the row sum:
+    e^Slb, e^ls), balanced order: first level, tiles, evaluated pairs and the gained nats, bench law and a uniform dual vector."""
+    for law, (x, y, h, _) in (("bench law", bench_problem(n)), ("uniform h", uniform_problem(n))):
+        sub = sort_sub(x.shape[1])
+        qx, qy = balanced_order(x, compact_order2(x, 256, sub)), balanced_order(y, compact_order2(y, 256, sub))
+        xs, ys, hs = x[qx], y[qy], h[qy]
+        C = (n + SLAB - 1) // SLAB
+        slabs = np.arange(5, C, max(1, (C - 5) // n_slabs)) if n_slabs > 0 and C > 5 else np.zeros(0, int)
+        for eps in eps_list:
+            base = None
+            for ref, K in [("term", 0)] + [("sum", k) for k in ref_blocks]:
+                got = []
+                keep, mlb, t1, L = plan_mass(xs, ys, hs, eps, reference=ref, slb_out=got)
+                closed = keep.copy()
+                for c in np.flatnonzero(runs_per_slab(keep) > RUNS):
+                    closed[c] = closed_gaps(keep[c])
+                first = kept_pairs(closed, n, n) / (float(n) * n)
+                tiles = sum(tiles_of(closed[c]) for c in range(C))
+                line = (f"{law}: n = {n}  eps = {eps:.4g}  reference {ref}" + (f" K = {K}" if K else "") + f": first level keeps {first:.4f}, "
+                        f"512-column tiles {tiles}, Slb - Mlb mean {(got[0] - mlb).mean():.3f} nats")
+                if len(slabs):
+                    ev, k1, rec = level2_mass(xs, ys, hs, eps, closed, L, slabs, reference=ref, ref_blocks=K or None)
+                    gain = np.concatenate([rec[c]["ls"] - rec[c]["ms"] for c in slabs])
+                    frac = ev / k1 * first
+                    base = frac if base is None else base
+                    line += (f"; on {len(slabs)} slabs: evaluated, scaled to all slabs {frac:.4f} ({frac / base - 1:+.1%}), ls - ms mean {gain.mean():.3f} "
+                             f"min {gain.min():.3f} nats, reference blocks mean {np.mean([rec[c]['refs'].size for c in slabs]):.1f}")
+                print(line, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--balanced", action="store_true", help="only the lines that compare the path order with the balanced one")
     ap.add_argument("--n", type=int, default=1000000)
     ap.add_argument("--eps", type=float, nargs="*", default=[0.01**2, 0.05**2, 0.2**2, 1.0])
     ap.add_argument("--slabs", type=int, default=40, help="slabs sampled for the second level (0: first level only)")
+    ap.add_argument("--ref-blocks", type=int, nargs="*", default=[REF_BLOCKS], help="reference blocks per slab (K) for the old-against-new lines")
     a = ap.parse_args()
     x, y, h, _ = bench_problem(a.n)
     if a.balanced:
-        return balanced_lines(x, y, h, a.n, a.eps, a.slabs)
+        balanced_lines(x, y, h, a.n, a.eps, a.slabs)
+        return reference_lines(a.n, a.eps, a.slabs, a.ref_blocks)
     px, py = compact_order(x, 256), compact_order(y, 512)
     xs, ys, hs = x[px], y[py], h[py]
     for eps in a.eps:
@@ -553,6 +659,7 @@ def main():
                   f"(runs per slab mean {r.mean():.1f} max {r.max()}, slabs over {RUNS} runs {(r > RUNS).sum()}); on {len(slabs)} slabs: "
                   f"first level {k1 / (rows * a.n):.4f}, evaluated after the second {ev / (rows * a.n):.4f}", flush=True)
     balanced_lines(x, y, h, a.n, a.eps, a.slabs)
+    reference_lines(a.n, a.eps, a.slabs, a.ref_blocks)
 
 
 if __name__ == "__main__":
