@@ -69,6 +69,9 @@ __device__ __forceinline__ double exp_f64(double t) {
     return ldexp(p, (int)n);
 }
 
+// fwd_i / eps, the constant that centres the plan weights of a row in the gradient mode; -inf for a row without mass (fwd_i = +inf)
+__device__ __forceinline__ double f64_centre(double fwd, double inv_eps) { return (fwd == INFINITY) ? -INFINITY : fwd * inv_eps; }
+
 // TPR threads per row (a power of two <= 64: the threads of a row are lanes of one wavefront).  DMAX = 4 | 16: register arrays of DMAX
 // doubles, loops fully unrolled and predicated on d < D.  Thread `sub` of a row takes the columns sub, sub + TPR, ... of every tile
 // and the partial results meet in a butterfly at the end: 2 000 rows — the coarse level of a two-scale loss, the few hundred points
@@ -110,7 +113,9 @@ f64_kernel(F64Params prm, Ranges rg, int n_ranges, int N, int M, int D) {
         double m = -INFINITY, ssum = 0.0, acc[DMAX];
 #pragma unroll
         for (int d = 0; d < DMAX; ++d) acc[d] = 0.0;
-        const double fwd_i = (MODE == F64_SOFTMIN_GRAD && live) ? prm.fwd[(long)b * N + i] * inv_eps : 0.0;
+        // (a row without mass — every h_j = -inf, saved forward value +inf — is centred on -inf: its weights are e^-inf = 0 and its gradient is 0,
+        // not the NaN of e^(-inf + inf))
+        const double fwd_i = (MODE == F64_SOFTMIN_GRAD && live) ? f64_centre(prm.fwd[(long)b * N + i], inv_eps) : 0.0;
 
         for (int q = q_begin; q < q_end; ++q) {
             const int js = sparse ? rg.redranges_j[2 * q] : 0, je = sparse ? rg.redranges_j[2 * q + 1] : M;
@@ -244,7 +249,7 @@ f64_generic_kernel(F64Params prm, Ranges rg, int n_ranges, int N, int M, int D, 
         const bool live = i < row_end;
         const double* xi = xb + (long)(live ? i : row_begin) * D;
         const long idx = (long)b * N + i;
-        const double fwd_i = (MODE == F64_SOFTMIN_GRAD && live) ? prm.fwd[idx] * inv_eps : 0.0;
+        const double fwd_i = (MODE == F64_SOFTMIN_GRAD && live) ? f64_centre(prm.fwd[idx], inv_eps) : 0.0;      // (a row without mass: as in f64_kernel)
         const int sweeps = GRAD ? (D + kF64Chunk - 1) / kF64Chunk : 1;
         for (int sweep = 0; sweep < sweeps; ++sweep) {
             const int d0 = sweep * kF64Chunk;

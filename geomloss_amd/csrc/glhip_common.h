@@ -17,6 +17,17 @@ constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLn2 = 0.6931471805599453f;
 constexpr float kNegBig = -1.0e30f;   // "minus infinity" that survives (a - a)
 
+// The base-2 log-sum-exp on which a gradient kernel centres the exponents of a row, from the saved forward value.  A row without mass
+// (every h_j = -inf) comes back from the forward as +inf or as about kNegBig * out_scale (its neutral padding was all it saw): centred on
+// that, the padding of the gradient sweep would weigh 2^(kNegBig - kNegBig).  Such a row is centred on -kNegBig instead, so that each
+// of its weights is 2^(-huge) = 0, and its gradient is 0 (`row_gradient_scale`).  NaN passes through.
+__device__ __forceinline__ float centring_lse2(float fwd, float out_scale) {
+    const float lse2 = fwd / out_scale;
+    return (lse2 <= 0.5f * kNegBig) ? -kNegBig : lse2;
+}
+// grad_out_i for a row with mass, 0 for a row without: g_i (x_i - sum_j P_ij y_j / mass_i) has no second term there, and the result is 0
+__device__ __forceinline__ float row_gradient_scale(float gi, float mass) { return (mass > 0.f) ? gi : 0.f; }
+
 // bf16 is carried as raw uint16_t: widening to fp32 is a 16-bit shift.
 struct bf16_t { uint16_t bits; };
 

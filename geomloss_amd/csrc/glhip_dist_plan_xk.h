@@ -135,10 +135,19 @@ xk_dist_plan_kernel(XkDistPlanParams<T> prm, int N, int M, int D, SplitInfo sp) 
         const int n = min(kXkCols, je - j0);
         const int ncg = (n + 31) >> 5;                        // column groups that are packed and multiplied
         const int col = (tid < n) ? j0 + tid : -1;            // this thread's column (tid < kXkCols), -1 = padding
+        {   // which of the tile's columns carry mass (h_j > -inf): read by the feature staging between the next two barriers
+            const float hcol = (col >= 0) ? prm.h[(long)b * M + col] : -__builtin_inff();
+            const unsigned long long live = __ballot(hcol != -__builtin_inff());
+            if (lane == 0 && wave < 2) {
+                lds.live[2 * wave] = (uint32_t)live;
+                lds.live[2 * wave + 1] = (uint32_t)(live >> 32);
+            }
+        }
         __syncthreads();                                      // the previous tile (and the row scalars) are settled
         if (tid < kXkCols) lds.xk.idx[kXkRows + tid] = col;
         // features (xk_plan_kernel): item (column quad cq, feature c of the pass) — c runs fastest: contiguous runs of feat rows
         float fv[kFItems][4];
+        const bool voids = __popc(lds.live[0]) + __popc(lds.live[1]) + __popc(lds.live[2]) + __popc(lds.live[3]) != n;      // (rare)
 #pragma unroll
         for (int k = 0; k < kFItems; ++k) {
             const int it = tid + k * kXkThreads;
@@ -150,8 +159,10 @@ xk_dist_plan_kernel(XkDistPlanParams<T> prm, int N, int M, int D, SplitInfo sp) 
                 float f = 0.f;
                 if (t + q < n && c < prm.nv) f = prm.feat[((long)b * M + j0 + t + q) * prm.V + prm.v0 + c];
                 fv[k][q] = f;
-                mx = max(mx, __float_as_uint(f) & 0x7FFFFFFFu);
             }
+            if (voids) plan_live_features(fv[k], lds.live, t);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) mx = max(mx, __float_as_uint(fv[k][q]) & 0x7FFFFFFFu);
             if (mx) atomicMax(&lds.fmax[parity][c], mx);
         }
         __syncthreads();                                      // the tile's indices and feature maxima are complete

@@ -298,7 +298,7 @@ dist_xd_grad_kernel(DistXdGradParams<T> gp, int N, int M, SplitInfo sp) {
 #pragma unroll
         for (int mm = 0; mm < NM; ++mm)
             X[mm] = select_u4(half != 0, xd_record_of<D, true>(2 * mm + 1, nx, a), xd_record_of<D, true>(2 * mm, nx, a));
-        if (SM) lse2 = gp.fwd[(long)b * N + i_lane] / prm.out_scale;      // base-2 log-sum-exp of the row
+        if (SM) lse2 = centring_lse2(gp.fwd[(long)b * N + i_lane], prm.out_scale);      // base-2 log-sum-exp of the row
     }
     const float thr = fmaxf(prm.guard * nx, 4.f * prm.clamp2);
     float S0 = 0.f, mass = 0.f, S1[D];

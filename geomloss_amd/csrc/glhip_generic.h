@@ -76,7 +76,7 @@ generic_kernel(GenericParams<T> p, Ranges rg, int N, int M, int D) {
         float m = kNegBig, ssum = 0.f, accv = 0.f;
         float lse2 = 0.f;
         float gacc[BWD ? kGenericGradPass : 1];
-        if (BWD && SOFTMIN) lse2 = p.fwd[(long)b * N + i] / p.out_scale;
+        if (BWD && SOFTMIN) lse2 = centring_lse2(p.fwd[(long)b * N + i], p.out_scale);
         const int npass = BWD ? (D + kGenericGradPass - 1) / kGenericGradPass : 1;
 
         for (int pass = 0; pass < npass; ++pass) {

@@ -24,7 +24,8 @@
 //     ds_max_u32 per thread and item on the |f| bit patterns, no pre-pass over feat, no host round trip, no workspace): the largest
 //     |f| of the tile's 128 (64) columns lands in [2^14, 2^15).  Columns of any magnitude sit next to each other, and a column
 //     whose entries span many orders of magnitude along j is rescaled tile by tile.  The inverse scale (times 2^-13) multiplies
-//     the block result on its way into the running sums.
+//     the block result on its way into the running sums.  The features of a column without mass (h_j = -inf) are staged as 0: they weigh
+//     nothing, and a huge one would otherwise set the scale of its tile (plan_live_features, in the tiles that have such a column).
 //
 // Accumulation: the discipline of wsum_t32q_kernel — a fresh accumulator per 32-column block, folded into the running sums with one
 // VALU instruction per register (here v_fma_f32 with the tile's inverse scale, round to nearest); chained through 31 250 blocks the
@@ -40,9 +41,11 @@
 //   registers / LDS over all D, both layouts, fp32 and bf16 clouds (gfx950, tools/kernel_resources.py, profiles/plan_apply.txt);
 //   LDS = 16 NBP bytes of exponent records + 128 NCH bytes of feature pieces per column, tiles of 128 columns (64 for NCH = 4):
 //     NCH = 1: 124-177 VGPRs (<= 128 for D <= 3 with fp32 clouds: 4 wavefronts per SIMD; 2-3 otherwise), 20.4-44.4 KiB of LDS
-//     NCH = 2: 211-250 VGPRs (2 wavefronts per SIMD), 36.8-52.8 KiB      (D <= 11)
-//     NCH = 4: 250-256 VGPRs (2 wavefronts per SIMD), 35.5-37.5 KiB      (D <= 4)
-//     scratch: 0 bytes in every instantiation
+//     NCH = 2: 219-250 VGPRs (2 wavefronts per SIMD), 36.8-52.8 KiB      (D <= 11)
+//     NCH = 4: 252-256 VGPRs (2 wavefronts per SIMD), 35.5-37.5 KiB      (D <= 4)
+//     scratch: 0 bytes, except the two one-chunk bf16 x 3 instantiations that sit on the 128-VGPR budget with fp32 clouds: D = 2 spills 20
+//     bytes per lane, D = 3 8 bytes (the dual value of the next tile's column, held across the MFMA loop); measured cost of the mask of
+//     columns without mass: 1.3 % of a pass at NCH = 1, 3.6 % at NCH = 2, 4.3 % at NCH = 4 (profiles/hostile_duals.txt)
 //
 // Column splits: the SplitLaunch plumbing (glhip_mapreduce.h); the partial of a row is (sums[nv], mass, m), nv = the features of the pass,
 // sums and mass relative to 2^m.  The merge brings the splits to the largest m, adds and divides.  Its width is a RUN-TIME
@@ -127,6 +130,16 @@ __device__ __forceinline__ void plan_store_pieces(const float (&f)[4], float sc,
     qb[256] = uint2{__builtin_bit_cast(uint32_t, l01), __builtin_bit_cast(uint32_t, l23)};
 }
 
+// The features of a column without mass (h_j = -inf) are staged as 0, whatever finite value they hold: their weight is 0, and left in, a
+// large one would set the power-of-two scale of its tile and push the features of the columns that do carry mass below the f16 pieces.
+// A staged item of four consecutive columns t .. t + 3 (t a multiple of 4), from the tile's mask of columns with mass: bit c of
+// live[c / 32], as the wavefronts that hold the dual values of the tile's columns published it (the halves of their `__ballot`).
+__device__ __forceinline__ void plan_live_features(float (&f)[4], const uint32_t* live, int t) {
+    const uint32_t bits = live[t >> 5] >> (t & 31);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) f[q] = ((bits >> q) & 1u) ? f[q] : 0.f;
+}
+
 // A block whose row maximum bm (the same in both lane halves of a row) passes the running maximum m of some row of the wavefront
 // brings the running sums and every four-register scalar to the new maximum: factor exactly 1 for the rows that keep theirs.
 template <int NCH, class... Scal4>
@@ -186,6 +199,7 @@ plan_apply_kernel(PlanParams<T> prm, int N, int M, SplitInfo sp) {
     __shared__ uint4 tileQ[kGroups * S::kQRecs];         // feature A operands: [group][chunk][piece][instruction][lane = 32 h + c] x 8 f16
     __shared__ uint32_t tileMax[2][VC];                  // largest |f| bit pattern per feature, tiles of even / odd index
     __shared__ __attribute__((aligned(16))) float tileInv[VC];      // 2^-13 / scale of the current tile, per feature
+    __shared__ uint32_t tileLive[4];                     // the current tile's columns with mass (h_j > -inf), one bit each
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -249,11 +263,7 @@ plan_apply_kernel(PlanParams<T> prm, int N, int M, SplitInfo sp) {
         const int n = min(kTileD, je - j0);
 #pragma unroll
         for (int d = 0; d < D; ++d) yreg[d] = 0.f;
-        if (tid < n) {
-            const long col = (long)b * M + j0 + tid;
-            load_point<D, T>(prm.y, col, yreg);
-            hreg = prm.h[col];
-        }
+        if (tid < n) load_point<D, T>(prm.y, (long)b * M + j0 + tid, yreg);
         // features: item (column quad cq, feature c of the pass) — c runs fastest, so the four loads of a wavefront are contiguous runs
         // of feat rows
 #pragma unroll
@@ -269,11 +279,25 @@ plan_apply_kernel(PlanParams<T> prm, int N, int M, SplitInfo sp) {
             }
         }
     };
+    // The dual value of this thread's column is always loaded one tile ahead: the wavefronts that hold them publish, before the first barrier
+    // of a tile, which of its columns carry mass (h_j > -inf).
+    auto load_h = [&](int j0) {
+        if (tid < min(kTileD, je - j0)) hreg = prm.h[(long)b * M + j0 + tid];
+    };
+    if (js < je) load_h(js);
     if (S::kPrefetch && js < je) load_tile(js);
     int parity = 0;
     for (int j0 = js; j0 < je; j0 += kTileD, parity ^= 1) {
         const int n = min(kTileD, je - j0);
         const int npad = (n + 31) & ~31;
+        {   // the tile's columns with mass, for the staging of its features (read between the next two barriers; the previous tile's mask
+            // was last read before the second barrier of its iteration)
+            const unsigned long long live = __ballot(tid < n && hreg != -__builtin_inff());
+            if (lane == 0 && wave < 2) {
+                tileLive[2 * wave] = (uint32_t)live;
+                tileLive[2 * wave + 1] = (uint32_t)(live >> 32);
+            }
+        }
         __syncthreads();      // the previous tile is consumed (and, the first time, tileMax is zero)
         if (!S::kPrefetch) load_tile(j0);
         if (tid < npad) {     // (kTileD <= 128 columns: one per thread)
@@ -303,11 +327,14 @@ plan_apply_kernel(PlanParams<T> prm, int N, int M, SplitInfo sp) {
 #pragma unroll
             for (int r = 0; r < NBP; ++r) base[r * 32] = xd_record_of<D, false, L>(r, H, yt);
         }
+        // (nearly every tile: all n columns carry mass, and the features stay as they were loaded)
+        const bool voids = __popc(tileLive[0]) + __popc(tileLive[1]) + __popc(tileLive[2]) + __popc(tileLive[3]) != n;
 #pragma unroll
         for (int k = 0; k < kItems; ++k) {
             const int it = tid + k * kThreads;
             const int cq = it / VC, c = it - cq * VC;
             uint32_t mx = 0u;
+            if (voids) plan_live_features(fv[k], tileLive, cq << 2);
 #pragma unroll
             for (int q = 0; q < 4; ++q) mx = max(mx, __float_as_uint(fv[k][q]) & 0x7FFFFFFFu);
             if ((cq << 2) < npad && mx) atomicMax(&tileMax[parity][c], mx);
@@ -333,6 +360,7 @@ plan_apply_kernel(PlanParams<T> prm, int N, int M, SplitInfo sp) {
             }
         }
         __syncthreads();
+        if (j0 + kTileD < je) load_h(j0 + kTileD);
         if (S::kPrefetch && j0 + kTileD < je) load_tile(j0 + kTileD);
         if (!wave_active) continue;
 

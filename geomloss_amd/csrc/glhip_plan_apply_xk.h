@@ -81,6 +81,7 @@ struct XkPlanLds {
     uint4 q[(kXkCols / 32) * NCH * 4 * 64];              // feature A operands: [group][chunk][piece][instruction][lane = 32 h + c] x 8 f16
     uint32_t fmax[2][32 * NCH];                          // largest |f| bit pattern per feature, tiles of even / odd index
     __attribute__((aligned(16))) float inv[32 * NCH];    // 2^-13 / scale of the current tile, per feature
+    uint32_t live[4];                                    // the current tile's columns with mass (h_j > -inf), one bit each: plan_live_features
 };
 
 // P = PlanParams<T>: the plan applied to prm.feat.  P = XkGradParams<T> (glhip_softmin_grad_xk.h): the gradient with respect to the row
@@ -162,11 +163,21 @@ xk_plan_kernel(P prm, int N, int M, int D, SplitInfo sp) {
         const int n = min(kXkCols, je - j0);                  // real columns, in the slots kXkRows .. kXkRows + n - 1
         const int ncg = (n + 31) >> 5;                        // column groups that are packed and multiplied
         const int col = (tid < n) ? j0 + tid : -1;            // this thread's column (tid < kXkCols), -1 = padding
+        if constexpr (!GRAD && !GAUSS) {   // which of the tile's columns carry mass (h_j > -inf): read by the feature staging between the next two barriers
+            const float hcol = (col >= 0) ? prm.h[(long)b * M + col] : -__builtin_inff();
+            const unsigned long long live = __ballot(hcol != -__builtin_inff());
+            if (lane == 0 && wave < 2) {
+                lds.live[2 * wave] = (uint32_t)live;
+                lds.live[2 * wave + 1] = (uint32_t)(live >> 32);
+            }
+        }
         __syncthreads();                                      // the previous tile (and the row scalars) are settled
         if (tid < kXkCols) lds.xk.idx[kXkRows + tid] = col;
         // features: item (column quad cq, feature c of the pass) — c runs fastest, so the loads of a wavefront are contiguous runs of
         // feat rows (plan_apply_kernel).  GRAD: the centred coordinates v0 .. v0 + nv - 1 of the tile's columns, runs of y rows
         float fv[kFItems][4];
+        bool voids = false;                                   // (nearly every tile: all n columns carry mass)
+        if constexpr (!GRAD && !GAUSS) voids = __popc(lds.live[0]) + __popc(lds.live[1]) + __popc(lds.live[2]) + __popc(lds.live[3]) != n;
 #pragma unroll
         for (int k = 0; k < kFItems; ++k) {
             const int it = tid + k * kXkThreads;
@@ -184,8 +195,10 @@ xk_plan_kernel(P prm, int N, int M, int D, SplitInfo sp) {
                     if constexpr (GAUSS) f *= prm.v[(long)b * M + j0 + t + q];      // v_j (y_j - centre)
                 }
                 fv[k][q] = f;
-                mx = max(mx, __float_as_uint(f) & 0x7FFFFFFFu);
             }
+            if (voids) plan_live_features(fv[k], lds.live, t);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) mx = max(mx, __float_as_uint(fv[k][q]) & 0x7FFFFFFFu);
             if (mx) atomicMax(&lds.fmax[parity][c], mx);
         }
         __syncthreads();                                      // the tile's indices and feature maxima are complete

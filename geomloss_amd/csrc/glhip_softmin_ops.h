@@ -351,7 +351,7 @@ struct SoftminBwdOp {
                 st.a[r][d] = xt * (DIRECT ? p.t : p.s2);
                 st.acc[r][d] = 0.f;
             }
-            const float lse2 = p.fwd[(long)b * N + i] / p.out_scale;   // out = out_scale * LSE2
+            const float lse2 = centring_lse2(p.fwd[(long)b * N + i], p.out_scale);   // out = out_scale * LSE2
             st.l[r] = DIRECT ? lse2 : lse2 + 0.5f * p.s2 * n2;          // LSE2 - r_i
             st.sw[r] = 0.f;
         }
@@ -400,7 +400,7 @@ struct SoftminBwdOp {
         for (int r = 0; r < R; ++r) {
             const int i = row0 + r * kBlock + tid;
             if (i < row_end) {
-                const float gi = p.g[(long)b * N + i];
+                const float gi = row_gradient_scale(p.g[(long)b * N + i], st.sw[r]);
                 const float inv = (st.sw[r] > 0.f) ? 1.0f / st.sw[r] : 0.f;
 #pragma unroll
                 for (int d = 0; d < D_; ++d) {
@@ -438,7 +438,7 @@ struct SoftminBwdOp {
         }
         float xi[D_];
         load_point<D_, T>(p.x, (long)b * N + i, xi);
-        const float gi = p.g ? p.g[(long)b * N + i] : 1.f;
+        const float gi = row_gradient_scale(p.g ? p.g[(long)b * N + i] : 1.f, sw);
         const float inv = (sw > 0.f) ? 1.0f / sw : 0.f;
         if (p.out) p.out[(long)b * N + i] = p.fwd[(long)b * N + i] + p.out_scale * (p.shift2 + fast_log2(sw));   // value-and-gradient mode
 #pragma unroll

@@ -124,7 +124,7 @@ wsum_mfma_kernel(WsumParams<T> prm, Ranges rg, int N, int M, SplitInfo sp) {
                 }
                 const float ri = -0.5f * prm.s2 * n2;
                 // -(LSE2 - r_i); in value-and-gradient mode `fwd` is a guess and tscale the margin that makes it an upper bound
-                if (MODE == WS_SOFTMIN_BWD) Cop[rt][r] = ri - (prm.fwd[(long)b * N + ir] / prm.out_scale + prm.tscale);
+                if (MODE == WS_SOFTMIN_BWD) Cop[rt][r] = ri - (centring_lse2(prm.fwd[(long)b * N + ir], prm.out_scale) + prm.tscale);
                 else Cop[rt][r] = ri;
             }
 #pragma unroll
@@ -236,7 +236,7 @@ wsum_mfma_kernel(WsumParams<T> prm, Ranges rg, int N, int M, SplitInfo sp) {
                             float* part = sp.workspace + split * sp.split_stride + ((long)b * N + i) * WsumShape<MODE, D>::kPart;
                             if (MODE == WS_SOFTMIN_BWD) {
                                 if (ns == 1) {
-                                    const float gi = prm.g ? prm.g[(long)b * N + i] : 1.f;
+                                    const float gi = row_gradient_scale(prm.g ? prm.g[(long)b * N + i] : 1.f, a_[D]);
                                     const float inv = (a_[D] > 0.f) ? 1.0f / a_[D] : 0.f;
 #pragma unroll
                                     for (int d = 0; d < D; ++d) prm.gx[((long)b * N + i) * D + d] = gi * (xt[d] - a_[d] * inv);

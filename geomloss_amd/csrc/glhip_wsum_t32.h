@@ -92,7 +92,7 @@ wsum_t32_kernel(WsumParams<T> prm, Ranges rg, int N, int M, SplitInfo sp) {
             // per-row constant of the exponent: r_i = -s/2 |xt_i|^2, minus (LSE2_i - r_i)'s other half for the soft-min gradient:
             //   C_i = r_i - LSE2_i, LSE2_i = fwd_i / out_scale (+ tscale: value-and-gradient mode, `fwd` is a guess and tscale the margin)
             float cst = -0.5f * prm.s2 * n2;
-            if (MODE == WS_SOFTMIN_BWD) cst -= prm.fwd[(long)b * N + i] / prm.out_scale + prm.tscale;
+            if (MODE == WS_SOFTMIN_BWD) cst -= centring_lse2(prm.fwd[(long)b * N + i], prm.out_scale) + prm.tscale;
             if (L == XL_F16X2) cst = __builtin_fminf(__builtin_fmaxf(cst, kH2Floor), -kH2Floor);
 #pragma unroll
             for (int mm = 0; mm < NM; ++mm)     // scalar item [1,1,1,c1,c2,c3] with c = cst, then the slots of every coordinate (xd_record_of)
@@ -196,7 +196,7 @@ wsum_t32_kernel(WsumParams<T> prm, Ranges rg, int N, int M, SplitInfo sp) {
                     if (MODE == WS_SOFTMIN_BWD) {
                         // a_[d] = sum_j P_ij yt_jd, a_[D] = sum_j P_ij;  d f_i / d x_i = x_i - sum_j P_ij y_j / sum_j P_ij
                         if (ns == 1) {
-                            const float gi = prm.g ? prm.g[idx] : 1.f;
+                            const float gi = row_gradient_scale(prm.g ? prm.g[idx] : 1.f, a_[D]);
                             const float inv = (a_[D] > 0.f) ? 1.0f / a_[D] : 0.f;
 #pragma unroll
                             for (int d = 0; d < D; ++d) prm.gx[idx * D + d] = gi * (xt[d] - a_[d] * inv);
@@ -312,7 +312,7 @@ wsum_t32q_kernel(WsumParams<T> prm, Ranges rg, int N, int M, SplitInfo sp) {
                 a[d] = xt * qs;
             }
             // C_i = r_i - LSE2_i (+ the margin of the value-and-gradient mode) + the 2^13 of the weights
-            float cst = -0.5f * prm.s2 * n2 - (prm.fwd[(long)b * N + i] / prm.out_scale + prm.tscale) + (float)kWqShift;
+            float cst = -0.5f * prm.s2 * n2 - (centring_lse2(prm.fwd[(long)b * N + i], prm.out_scale) + prm.tscale) + (float)kWqShift;
             cst = __builtin_fminf(__builtin_fmaxf(cst, kH2Floor), -kH2Floor);
 #pragma unroll
             for (int mm = 0; mm < NM; ++mm)
@@ -408,7 +408,7 @@ wsum_t32q_kernel(WsumParams<T> prm, Ranges rg, int N, int M, SplitInfo sp) {
                 float xi[D];
                 load_point<D, T>(prm.x, idx, xi);
                 float* part = sp.workspace + split * sp.split_stride + idx * (D + 1);
-                const float gi = (ns == 1 && prm.g) ? prm.g[idx] : 1.f;
+                const float gi = row_gradient_scale((ns == 1 && prm.g) ? prm.g[idx] : 1.f, mass);
                 const float inv = (mass > 0.f) ? 1.0f / mass : 0.f;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {

@@ -136,7 +136,7 @@ wsum_x32_kernel(WsumParams<T> prm, Ranges rg, int N, int M, SplitInfo sp, Packed
                 n2 = __builtin_fmaf(xt, xt, n2);
             }
             float cst = -0.5f * prm.s2 * n2;                                                     // r_i
-            if (MODE == WS_SOFTMIN_BWD) cst -= prm.fwd[(long)b * N + i] / prm.out_scale;         // -(LSE2_i - r_i)
+            if (MODE == WS_SOFTMIN_BWD) cst -= centring_lse2(prm.fwd[(long)b * N + i], prm.out_scale);         // -(LSE2_i - r_i)
             const uint4 z = uint4{0u, 0u, 0u, 0u};
             const uint4 p0 = pack_a(a[0]), p1 = (D > 1) ? pack_a(a[1]) : z, p2 = (D > 2) ? pack_a(a[2]) : z;
             Xlo = half ? p1 : p0;
@@ -260,7 +260,7 @@ wsum_x32_kernel(WsumParams<T> prm, Ranges rg, int N, int M, SplitInfo sp, Packed
                         float* part = sp.workspace + split * sp.split_stride + ((long)b * N + i) * WsumShape<MODE, D>::kPart;
                         if (MODE == WS_SOFTMIN_BWD) {
                             if (ns == 1) {
-                                const float gi = prm.g[(long)b * N + i];
+                                const float gi = row_gradient_scale(prm.g[(long)b * N + i], a_[D]);
                                 const float inv = (a_[D] > 0.f) ? 1.0f / a_[D] : 0.f;
 #pragma unroll
                                 for (int d = 0; d < D; ++d) prm.gx[((long)b * N + i) * D + d] = gi * (xt[d] - a_[d] * inv);

@@ -1259,7 +1259,8 @@ def plan_apply(eps, x, y, h, feat, fwd=None, flags=0, p=2, ranges=None):
     a single column is a whole pass: V = 129 at D = 3 costs two.  Inside the kernel the weights are taken relative to the largest one
     of their row, and ``out`` is divided by the recomputed row sum: ``fwd`` only centres the exponents (an error of a few units of
     ``eps`` in it costs no accuracy in ``out``; it must be close enough for the exponents to stay in range), and one-hot plan rows
-    return their features bit for bit.  NOT an autograd function: it runs under ``torch.no_grad()`` and returns a tensor without
+    return their features bit for bit where two f16 pieces hold them (within 1.5 x 2^-23 of the column's largest entry otherwise:
+    include/glhip.h); the features of a column with ``h = -inf`` are staged as 0.  NOT an autograd function: it runs under ``torch.no_grad()`` and returns a tensor without
     ``grad_fn``.  float64 clouds, p = 1, D > 16 and block-sparse ranges raise ``NotImplementedError``; :func:`plan_apply_nd` is the
     same function for any D <= PLAN_MAX_DIM = 4095."""
     return _plan_apply("plan_apply", plan_apply_raw, XD_MAX_DIM, eps, x, y, h, feat, fwd, flags, p, ranges)

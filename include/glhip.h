@@ -449,6 +449,11 @@ int glhip_lse_lines_bwd(const float* h, const float* lse, const float* grad_out,
  *   with glhip_workspace_bytes, which does not change) or under GLHIP_FLAG_NO_SPLIT.  NULL or a short workspace: fewer or no splits,
  *   the same results up to summation order.  N == 0 or B == 0 launches nothing; M == 0 zeroes grad_x.
  *   out = the saved forward result (B,N);  grad_out (B,N) fp32;  grad_x (B,N,D) fp32.
+ *   A row without mass — every h_j = -inf (or no column at all in its ranges), whose saved forward value is +inf or the huge
+ *   finite value the forward kernels return where their neutral padding was all they saw — gets grad_x = 0, never NaN: in every
+ *   dimension, on every route and in both exponent layouts; glhip_softmin_fwd_grad likewise (its value there: +inf or that huge value).
+ *   glhip_softmin_bwd_x_f64 below does the same.  Columns with h_j = -inf weigh exactly 0 whatever finite coordinates they hold
+ *   (under GLHIP_FLAG_F16X2: inside that flag's range contract).
  */
 int glhip_softmin_bwd_x(const void* x, const void* y, const float* h,
                         const float* out, const float* grad_out, float* grad_x,
@@ -474,7 +479,11 @@ size_t glhip_softmin_bwd_x_workspace_bytes(int B, int N, int M, int D, int flags
  *   chunk, fresh accumulator per 32 columns); features are split into two f16 pieces under a power-of-two scale per column and tile,
  *   found on the device.  Inside the kernel the weights are taken relative to the running maximum of their row (fwd centres the
  *   exponents and scales `mass`; an inaccurate fwd costs no accuracy in `out`), so the largest weight of a row is exact and a one-hot
- *   plan row returns its features bit for bit.  Rounding of the product: <= 2e-7 of sum_j w_ij |feat_jv| (tools/plan_apply_model.py), next to the ~1e-6 the
+ *   plan row returns its features as the two f16 pieces carry them: bit for bit where they hold them (22 significant bits below the
+ *   power of two above the column's largest |f| within the tile: integers, fixed-point grids), within 1.5 x 2^-23 of that largest
+ *   |f| for arbitrary float32 features.  A column with h_j = -inf (exactly; not a large negative stand-in for log 0) has its
+ *   features staged as 0, whatever finite value they hold: they do not enter the scale of their tile.
+ *   Rounding of the product: <= 2e-7 of sum_j w_ij |feat_jv| (tools/plan_apply_model.py), next to the ~1e-6 the
  *   exponents leave.
  *   Supported: p == 2, 1 <= D <= 16 (this contract stays: D >= 17 goes through glhip_plan_apply_nd below), dense launches
  *   (n_ranges == 0), any B; anything else returns GLHIP_EUNSUPPORTED (the range
@@ -774,6 +783,7 @@ int glhip_softmin_fwd_f64(const double* x, const double* y, const double* h, dou
 int glhip_sinkhorn_step_f64(const double* x, const double* y, const double* logw, const double* pot, const double* prev, double* out,
                             int B, int N, int M, int D, double eps, double damping, int p, const int32_t* ranges_i,
                             const int32_t* slices_i, const int32_t* redranges_j, int n_ranges, void* stream);
+/* (a row without mass — every h_j = -inf, saved forward value +inf — gets grad_x = 0, never NaN) */
 int glhip_softmin_bwd_x_f64(const double* x, const double* y, const double* h, const double* out, const double* grad_out, double* grad_x,
                             int B, int N, int M, int D, double eps, int p, const int32_t* ranges_i, const int32_t* slices_i,
                             const int32_t* redranges_j, int n_ranges, void* stream);

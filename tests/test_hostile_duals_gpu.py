@@ -1,0 +1,590 @@
+"""Every kernel that carries weighted sums, driven with dual vectors built to break a running maximum (tests/dual_patterns.py; what each
+pattern does on these clouds is checked on the host in tests/test_dual_patterns_cpu.py), against float64.
+
+References are float64 only: ``oracle_c`` / ``oracle_torch64`` for the soft-min and its gradient, the ``_ref`` restatements of the plan
+tests on the rounded float32 inputs for the plan applications.  No HIP kernel is compared with another, except "split equals unsplit".
+
+Bounds.  One-hot patterns (``late``, ``stairs``): the plan routes return the features of the one column bit for bit, the gradients are
+g_i (x_i - y_j*) (p = 1: g_i times the unit direction) to the flat bound of the route's parity test.  Spread patterns: the error is measured
+as that parity test measures it and held to max(its flat bound, 4 e_ref), e_ref the error of the same quantity in plain float32 torch on
+the same inputs (tests/test_softmin_grad_xk_gpu.py::_bound).  The flat bounds are those of tests/dual_patterns.py, each named there with
+its source.  Voids: the reference is computed without the void columns, whose features are 1e30 in the launch (gradients: coordinates
+1e4; 2 under FLAG_F16X2, whose range contract covers them too).  Rows without mass: exact zeros.  Eight (route, pattern) pairs are expected
+failures: ``LONG_CHAIN``.  Every function collects its violations and asserts once, figures first (``pytest -s``;
+profiles/hostile_duals.txt)."""
+import functools
+import math
+import time
+
+import numpy as np
+import pytest
+import torch
+
+import dual_patterns as dp
+import test_plan_apply_gpu as t_xd
+import test_plan_apply_nd_gpu as t_nd
+import test_plan_apply_p1_gpu as t_p1
+from conftest import relerr
+from geomloss_amd import hip
+from geomloss_amd.cluster import from_matrix
+from oracle import oracle_c
+from oracle import oracle_torch64 as o64
+from test_dist_grad_xk_gpu import f32_error as _p1_grad_f32_error
+from test_f64_gpu import _clouds as _clouds_f64
+from test_softmin_grad_xk_gpu import _f32_error as _p2_grad_f32_error
+
+pytestmark = pytest.mark.gpu
+
+NS, H2, XK, XKD, XDG, MD = hip.FLAG_NO_SPLIT, hip.FLAG_F16X2, hip.FLAG_XK_GRAD, hip.FLAG_XK_DIST, hip.FLAG_XK_DIST_GRAD, hip.FLAG_MFMA_DIST
+PATTERNS = dp.ONE_HOT + dp.SPREAD
+MARGIN = 4.0      # the project's margin over plain float32 for chains whose exponent error exceeds it (tests/test_softmin_grad_xk_gpu.py::_bound)
+ONE_HOT_F32 = 1.5 * 2.0 ** -23      # one-hot rows on arbitrary float32 features, of the column's largest |f|: see _plan_route
+
+# (route, D, flags, pattern) on which a kernel that is right misses max(flat bound, 4 e_ref): the K-chunked exponent chains of D > 16 on
+# duals of magnitude 80 ... 255 whose mass sits on a few columns.  Each MFMA of the chain rounds (truncates) a partial sum that already holds
+# log2(e) h_j ~ 370, an ulp of 3e-5, where plain float32 rounds h_j - C_ij / eps once; a row that averages over few columns keeps that
+# error.  That reading of the cause is an argument from the code, not a measurement (profiles/hostile_duals.txt, section 4).  Worst error /
+# bound measured on an MI355X.  They run as test_long_chains_on_steep_duals, expected to miss the bound and nothing else, and are left out
+# of the functions below.
+LONG_CHAIN = {
+    ("nd", 24, 0, "ramp"): "1.28", ("nd", 24, H2, "ramp"): "1.01", ("nd", 70, 0, "ramp"): "2.56", ("nd", 70, H2, "ramp"): "1.75",
+    ("nd", 70, 0, "twin"): "1.27", ("grad", 24, XK, "ramp"): "1.91", ("grad", 70, XK, "ramp"): "2.99", ("grad", 70, XK, "twin"): "1.77",
+}
+
+
+def _t(a, dev):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+class _Report:
+    """(route, pattern, variant, error, bound, e_ref) of every check of a function; the worst ratio per route is printed, the violations
+    are asserted once at the end (as ``_Report`` of tests/test_dimension_sweep_gpu.py)."""
+
+    def __init__(self, name):
+        self.name, self.bad, self.worst, self.n, self.t0 = name, [], {}, 0, time.perf_counter()
+
+    def add(self, route, pattern, variant, err, bound, e_ref=None):
+        ratio = float(err) / float(bound) if np.isfinite(err) else math.inf
+        self.n += 1
+        if ratio > self.worst.get(route, (-1.0,))[0]:
+            self.worst[route] = (ratio, pattern, variant, float(err), float(bound), e_ref)
+        if not err <= bound:
+            self.bad.append((route, pattern, variant, float(f"{ratio:.3g}")))
+
+    def exact(self, route, pattern, variant, ok, detail=""):
+        self.n += 1
+        if not ok:
+            self.bad.append((route, pattern, variant, detail))
+
+    def finish(self):
+        self.figures()
+        assert not self.bad, f"{self.name}: {len(self.bad)} of {self.n} checks failed (route, pattern, variant, error / bound or what): {self.bad}"
+
+    def figures(self):
+        for route, (ratio, pattern, variant, err, bound, e_ref) in sorted(self.worst.items()):
+            e = "-" if e_ref is None else f"{e_ref:.2e}"
+            print(f"hostile {self.name} [{route}]: worst error / bound {ratio:.3f} on {pattern} ({variant}): error {err:.2e}, bound {bound:.2e}, e_ref {e}")
+        print(f"hostile {self.name}: {self.n} checks, {time.perf_counter() - self.t0:.1f} s")
+
+
+@functools.lru_cache(maxsize=None)
+def _host(D, p, N, M):
+    """clouds, temperature and patterns: the very inputs tests/test_dual_patterns_cpu.py examines"""
+    x, y, eps = dp.clouds(D, p, N, M)
+    return x, y, eps, dp.patterns(M, np.random.default_rng(M + D))
+
+
+@functools.lru_cache(maxsize=None)
+def _peak(D, p, N, M, name):
+    """the column that holds a one-hot row's mass, per row, in float64"""
+    x, y, eps, pats = _host(D, p, N, M)
+    return dp.log_weights(x, y, pats[name], eps, p).argmax(1)
+
+
+def _variants(M, flags):
+    """the unsplit shape as it is; the split shape also under FLAG_NO_SPLIT and without a workspace"""
+    return [(flags, True, "")] if M < 1000 else [(flags, True, "split"), (flags | NS, True, "no-split flag"), (flags, False, "no workspace")]
+
+
+def _split_agreement(rep, route, name, outs, measure, key):
+    """split against unsplit and against the launch without a workspace, where the entry point's own split test states a bound (dp.SPLIT_BOUND)"""
+    bound = dp.SPLIT_BOUND.get(key)
+    if len(outs) == 3 and bound is not None:
+        rep.add(route + " split = unsplit", name, "", max(measure(outs[0], outs[1]), measure(outs[0], outs[2])), bound)
+
+
+# ---- plan application -------------------------------------------------------------------------------------------------------------
+def _plan_family(D, N, M, V, flags):
+    return hip.plan_apply_nd_family(1, N, M, D, V, flags=flags) == (hip.FAMILY_XD if D <= 16 else hip.FAMILY_XK)
+
+
+def _plan_launch(dev, kind, x, y, h, feat, eps, flags, ws, fwd=None):
+    """-> out, mass (p = 2) / soft-min (p = 1), NumPy, of one unbatched or batched problem"""
+    xb, yb, hb, fb = (_t(a, dev) for a in (x, y, h, feat))
+    one = xb.dim() == 2
+    if one:
+        xb, yb, hb, fb = xb[None], yb[None], hb[None], fb[None]
+    if kind == "p1":
+        out, side = hip.plan_apply_p1_raw(xb, yb, hb, fb, eps, flags, want_softmin=True, workspace=ws)
+    else:
+        fw = hip.softmin_fwd_raw(xb, yb, hb, eps, 2, None, flags) if fwd is None else _t(fwd, dev).reshape(hb.shape[0], -1)
+        raw = hip.plan_apply_raw if kind == "xd" else hip.plan_apply_nd_raw
+        out, side = raw(xb, yb, hb, fw, fb, eps, flags, want_mass=True, workspace=ws)
+    out, side = out.cpu().numpy(), side.cpu().numpy()
+    return (out[0], side[0]) if one else (out, side)
+
+
+def _plan_ref(kind, x, y, h, eps, feat):
+    """float64 (out, soft-min or None) on the columns that carry mass"""
+    keep = np.isfinite(h)
+    if kind == "p1":
+        return t_p1._ref(x, y[keep], h[keep], eps, feat[keep])
+    return (t_xd._ref if kind == "xd" else t_nd._ref)(x, y[keep], h[keep], eps, feat[keep]), None
+
+
+def _plan_e_ref(dev, kind, x, y, h, eps, feat, ref):
+    keep = np.isfinite(h)
+    f = t_p1._torch_f32_error if kind == "p1" else t_nd._torch_f32_error
+    return f(dev, x, y[keep], h[keep], eps, feat[keep], ref)
+
+
+def _plan_worst(out, ref, feat):
+    return t_nd._worst(out, ref, feat)
+
+
+def _plan_route(rep, dev, kind, D, V, flag_list, only=None):
+    """Every pattern (or ``only``) at both shapes.  One-hot rows: the kernel's largest weight of a row is exact and every other one is 0, so
+    ``out`` is the one column's features as the plan half carries them — two f16 pieces under a power-of-two scale that puts the largest
+    |f| of a column and tile into [2^14, 2^15): features on a grid of 2^-10 (13 bits) come back bit for bit; arbitrary float32 features
+    lose at most 2^-9 of those units to the low piece (11 bits below a remainder of <= 2^3), 2^-23 of the column's largest |f|, and 2^-24
+    more to the float32 rounding of the sum."""
+    p = 1 if kind == "p1" else 2
+    for N, M in dp.SHAPES:
+        x, y, eps, pats = _host(D, p, N, M)
+        feat = np.random.default_rng(V).standard_normal((M, V)).astype(np.float32)
+        grid = (np.round(feat * 1024.0) / 1024.0).astype(np.float32)
+        for name in (PATTERNS if only is None else (only,)):
+            h = pats[name]
+            keep = np.isfinite(h)
+            launch_feat = np.where(keep[:, None], feat, np.float32(1e30))
+            if name in dp.ONE_HOT:
+                peak = _peak(D, p, N, M, name)
+            else:
+                ref, sref = _plan_ref(kind, x, y, h, eps, feat)
+                e_ref = _plan_e_ref(dev, kind, x, y, h, eps, feat, ref)
+                bound = max(dp.PLAN_BOUND, MARGIN * e_ref)
+            for flags in flag_list:
+                if only is None and (kind, D, flags, name) in LONG_CHAIN:
+                    continue
+                route = f"plan {kind} D={D} V={V} flags={flags}"
+                outs = []
+                for fl, ws, tag in _variants(M, flags):
+                    if kind != "p1":
+                        assert _plan_family(D, N, M, V, fl), (D, V, fl)
+                    else:
+                        assert hip.plan_apply_p1_applies(_t(x, "cpu")), D
+                    out, side = _plan_launch(dev, kind, x, y, h, launch_feat, eps, fl, ws)
+                    outs.append(out)
+                    variant = f"M={M} {tag}"
+                    rep.exact(route, name, variant, bool(np.isfinite(out).all() and np.isfinite(side).all()), "not finite")
+                    if name in dp.ONE_HOT:
+                        rep.add(route + " one-hot, float32 features", name, variant, (np.abs(out - feat[peak]).max(0) / np.abs(feat).max(0)).max(), ONE_HOT_F32)
+                        out, _ = _plan_launch(dev, kind, x, y, h, grid, eps, fl, ws)
+                        want = grid[peak]
+                        rep.exact(route, name, variant, np.array_equal(out, want), f"{int((out != want).sum())} entries are not the one column's, "
+                                  f"max |out - want| {np.abs(out - want).max():.2e}")
+                    else:
+                        rep.add(route, name, variant, _plan_worst(out, ref, feat[keep]), bound, e_ref)
+                        if kind == "p1":
+                            rep.add(route + " soft-min", name, variant, np.abs(side - sref).max(), dp.p1_value_bound(sref, 17))      # (_sbound of the p = 1 plan tests)
+                _split_agreement(rep, route, name, outs, lambda a, b: _plan_worst(a, b, feat[keep]), f"plan {kind}")
+
+
+def test_plan_apply(cuda):
+    """``glhip_plan_apply``: D = 3 with 1, 2 and 4 chunks per pass plus a remainder pass, D = 8, D = 16; both exponent layouts."""
+    rep = _Report("plan_apply")
+    for D, V in ((3, 5), (3, 40), (3, 129), (8, 40), (16, 31)):
+        _plan_route(rep, cuda, "xd", D, V, (0, H2))
+    rep.finish()
+
+
+def test_plan_apply_nd(cuda):
+    rep = _Report("plan_apply_nd")
+    for D in (24, 70):
+        _plan_route(rep, cuda, "nd", D, 70, (0, H2))
+    rep.finish()
+
+
+def test_plan_apply_p1(cuda):
+    """with the soft-min on the side"""
+    rep = _Report("plan_apply_p1")
+    for D in (3, 33):
+        _plan_route(rep, cuda, "p1", D, 70, (0,))
+    rep.finish()
+
+
+# ---- soft-min gradients -----------------------------------------------------------------------------------------------------------
+def _oracle_grad(dev, D, eps, x, y, h, g, p):
+    if D <= 64:
+        return oracle_c.softmin_grad_x(eps, x, y, h, g, p)
+    return o64.softmin_grad_x(eps, x, y, h, g, p, device=dev)
+
+
+def _one_hot_grad(x, y, g, peak, p):
+    diff = x.astype(np.float64) - y.astype(np.float64)[peak]
+    if p == 1:
+        diff = diff / np.sqrt((diff * diff).sum(1, keepdims=True))
+    return g.astype(np.float64)[:, None] * diff
+
+
+def _grad_launch(dev, x, y, h, g, eps, p, fwd_flags, flags, ws, ranges=None):
+    """forward, then ``glhip_softmin_bwd_x`` -> (soft-min, gradient), NumPy"""
+    xb, yb, hb, gb = (_t(a, dev) for a in (x, y, h, g))
+    one = xb.dim() == 2
+    if one:
+        xb, yb, hb, gb = xb[None], yb[None], hb[None], gb[None]
+    fwd = hip.softmin_fwd_raw(xb, yb, hb, eps, p, ranges, fwd_flags)
+    gx = hip.softmin_bwd_x_raw(xb, yb, hb, fwd, gb, eps, p, ranges, flags, workspace=ws)
+    fwd, gx = fwd.cpu().numpy(), gx.cpu().numpy()
+    return (fwd[0], gx[0]) if one else (fwd, gx)
+
+
+def _grad_predicates(D, p, N, M, fwd_flags, flags, n_ranges=0):
+    """the library's own predicates name the expected kernels"""
+    if p == 2:
+        assert hip.softmin_bwd_x_uses_plan(1, N, M, D, flags=flags) == int(bool(flags & XK) and D > 16), (D, flags)
+        want = (hip.FAMILY_X32, hip.FAMILY_VALU, hip.FAMILY_XD) if D <= 3 else (hip.FAMILY_XD,) if D <= 16 else (hip.FAMILY_XK,)
+        assert hip.softmin_fwd_family(1, N, M, D, 2, hip.F32, fwd_flags) in want, (D, fwd_flags)
+    else:
+        if D > 3 or n_ranges > 0:      # glhip_dist_xd.h (4 <= D <= 16, dense), glhip_dist_xk.h under its flag, glhip_dist_x32.h (block-sparse, under its flag)
+            dist = (4 <= D <= 16 and n_ranges == 0) or (D > 16 and bool(fwd_flags & XKD)) or (D <= 3 and bool(fwd_flags & MD))
+            assert (hip.softmin_fwd_family(1, N, M, D, 1, hip.F32, fwd_flags, n_ranges) == hip.FAMILY_DIST) == dist, (D, fwd_flags, n_ranges)
+        assert hip.dist_grad_uses_xk("softmin_p1", 1, N, M, D, flags=flags, n_ranges=n_ranges) == int(D > 16 and bool(flags & XDG)), (D, flags)
+
+
+def _with_void_points(y, keep, flags):
+    """whatever (huge, finite) coordinates a column without mass holds; under FLAG_F16X2 the caller vouches for every exponent term, those of
+    such columns included: they stay inside that range"""
+    out = np.array(y)
+    out[~keep] = 2.0 if flags & H2 else 1e4
+    return out
+
+
+def _grad_route(rep, dev, D, p, fwd_flags, flags, value=False, sparse=False, only=None):
+    """every pattern at both shapes through forward + gradient; ``value``: the forward values are checked too (p = 1)"""
+    for N, M in dp.SHAPES:
+        x, y, eps, pats = _host(D, p, N, M)
+        g = np.random.default_rng(D + N).standard_normal(N).astype(np.float32)
+        ranges = None
+        if sparse:      # one range that covers everything reaches the block-sparse kernels
+            ranges = from_matrix(torch.tensor([[0, N]], dtype=torch.int32, device=dev), torch.tensor([[0, M]], dtype=torch.int32, device=dev),
+                                 torch.ones((1, 1), dtype=torch.bool, device=dev))
+        route = f"grad p={p} D={D} flags={flags}" + (" block-sparse" if sparse else "")
+        for name in (PATTERNS if only is None else (only,)):
+            if only is None and p == 2 and ("grad", D, flags, name) in LONG_CHAIN:
+                continue
+            h = pats[name]
+            keep = np.isfinite(h)
+            yk, hk = y[keep], h[keep]
+            bound = dp.grad_bound(D, p)
+            e_ref = None
+            if name in dp.ONE_HOT:
+                ref = _one_hot_grad(x, y, g, _peak(D, p, N, M, name), p)
+            else:
+                ref = _oracle_grad(dev, D, eps, x, yk, hk, g, p)
+                e_ref = (_p2_grad_f32_error(dev, x, yk, hk, g, eps, ref) if p == 2 else _p1_grad_f32_error(dev, "softmin_p1", x, yk, hk, g, eps, ref))
+                bound = max(bound, MARGIN * e_ref)
+            if value:
+                vref = oracle_c.softmin(eps, x, yk, hk, p)
+                vbound = dp.p1_value_bound(vref, D)
+                v_e_ref = None
+                if name not in dp.ONE_HOT:
+                    v32 = -eps * torch.logsumexp(_t(hk, dev)[None, :] - torch.cdist(_t(x, dev), _t(yk, dev)).clamp_min(1e-4) / eps, dim=1)
+                    v_e_ref = float(np.abs(v32.cpu().numpy() - vref).max())
+                    vbound = max(vbound, MARGIN * v_e_ref)
+            outs = []
+            for fl, ws, tag in ([(flags, True, "")] if sparse else _variants(M, flags)):
+                ffl = fwd_flags | (fl & NS)
+                _grad_predicates(D, p, N, M, ffl, fl, 1 if sparse else 0)
+                fwd, gx = _grad_launch(dev, x, _with_void_points(y, keep, fl), h, g, eps, p, ffl, fl, ws, ranges)
+                outs.append(gx)
+                variant = f"M={M} {tag}"
+                rep.exact(route, name, variant, bool(np.isfinite(gx).all() and np.isfinite(fwd).all()), "not finite")
+                rep.add(route, name, variant, relerr(gx, ref), bound, e_ref)
+                if value:
+                    rep.add(route + " value", name, variant, np.abs(fwd - vref).max(), vbound, v_e_ref)
+            scale = np.abs(ref).max()
+            _split_agreement(rep, route, name, outs, lambda a, b: float(np.abs(a - b).max() / scale),
+                             "grad p2 xk" if p == 2 and flags & XK else "grad p1 xk" if p == 1 and flags & XDG else None)
+
+
+def test_softmin_gradient_p2(cuda):
+    """``glhip_softmin_fwd`` then ``glhip_softmin_bwd_x``: the kernels of D <= 3, of 4 <= D <= 16 in both layouts, and of D > 16 on both routes."""
+    rep = _Report("softmin gradient p=2")
+    for D in (3, 5, 8, 16):
+        for flags in (0, H2):
+            _grad_route(rep, cuda, D, 2, flags, flags)
+    for D in (24, 70):
+        for flags in (0, XK):
+            _grad_route(rep, cuda, D, 2, 0, flags)
+    rep.finish()
+
+
+def test_softmin_p1_forward_and_gradient(cuda):
+    """p = 1: the lazy maximum of the three forward kernels (glhip_dist_x32.h block-sparse, glhip_dist_xd.h, glhip_dist_xk.h) and the gradients."""
+    rep = _Report("softmin p=1")
+    for D in (3, 8, 33):
+        _grad_route(rep, cuda, D, 1, 0, 0, value=True)
+    _grad_route(rep, cuda, 33, 1, XKD, XDG, value=True)
+    _grad_route(rep, cuda, 3, 1, MD, MD, value=True, sparse=True)
+    rep.finish()
+
+
+@pytest.mark.parametrize("route,D,flags,name", list(LONG_CHAIN))
+def test_long_chains_on_steep_duals(cuda, route, D, flags, name):
+    """The (route, pattern) pairs of ``LONG_CHAIN``, held to the same bound as every other pair — the plan routes also with the saved forward
+    value off by -20 and +20 eps — and expected to miss it: an expected failure (``pytest.xfail``) with the measured figure, strict by hand.
+    Everything else about the pair is asserted as usual: finite results, split against unsplit, the mass under an inaccurate forward value,
+    and an error of at most twice the recorded one; a pair that meets its bound fails here until it is taken out of ``LONG_CHAIN``."""
+    rep = _Report(f"long chain {route} D={D} flags={flags} {name}")
+    if route == "grad":
+        _grad_route(rep, cuda, D, 2, 0, flags, only=name)
+    else:
+        _plan_route(rep, cuda, route, D, 70, (flags,), only=name)
+        _inaccurate_forward_route(rep, cuda, route, D, 70, (flags,), (name,), known=False)
+    rep.figures()
+    misses = [b for b in rep.bad if isinstance(b[3], float) and not b[0].endswith((" mass", " split = unsplit"))]
+    others = [b for b in rep.bad if b not in misses]
+    assert not others, f"{rep.name}: beyond the expected miss of the bound: {others}"
+    worst, recorded = max((b[3] for b in misses), default=0.0), float(LONG_CHAIN[(route, D, flags, name)])
+    assert worst <= 2.0 * recorded, f"{rep.name}: error / bound {worst:.3g}, recorded {recorded}: {misses}"
+    if not misses:
+        pytest.fail(f"{rep.name}: within its bound now (recorded error / bound {recorded}): take the pair out of LONG_CHAIN")
+    pytest.xfail(f"error / bound {worst:.3g} (recorded: {recorded}): LONG_CHAIN")
+
+
+# ---- value and gradient from a guess ----------------------------------------------------------------------------------------------
+def test_softmin_value_and_gradient_from_a_guess(cuda):
+    """``glhip_softmin_fwd_grad``, p = 2: guess = exact +- margin with margin / eps in {0, 1, 20} (the header allows about 25).  Bounds: the value
+    as tests/test_xd_kernels_gpu.py::test_softmin_value_and_gradient_transposed_kernel (_tol + 4e-7 margin; D <= 3: 4e-7 D + 3e-6 |ref|max of
+    tests/test_hip_kernels.py::test_softmin_value_and_gradient_in_one_pass), the gradient 2e-5 / 3e-5 of the same two tests."""
+    rep = _Report("softmin_fwd_grad")
+    for D in (3, 8):
+        for N, M in dp.SHAPES:
+            x, y, eps, pats = _host(D, 2, N, M)
+            ones = np.ones(N, np.float32)
+            sign = np.where(np.random.default_rng(N).random(N) < 0.5, -1.0, 1.0)
+            for name in ("ramp", "twin", "floors"):
+                h = pats[name]
+                ref = oracle_c.softmin(eps, x, y, h, 2)
+                refg = oracle_c.softmin_grad_x(eps, x, y, h, ones, 2)
+                e_ref = _p2_grad_f32_error(cuda, x, y, h, ones, eps, refg)
+                gbound = max(2e-5 if D >= 4 else 3e-5, MARGIN * e_ref)
+                C = ((x.astype(np.float64)[:, None, :] - y.astype(np.float64)[None, :, :]) ** 2).sum(-1) / 2
+                v32 = -eps * torch.logsumexp(_t(h, cuda)[None, :] - _t(C.astype(np.float32), cuda) / eps, dim=1)
+                v_e_ref = float(np.abs(v32.cpu().numpy() - ref).max())
+                for k in (0, 1, 20):
+                    margin = k * eps
+                    guess = (ref + sign * margin).astype(np.float32)
+                    margin_given = 1.0001 * float(np.abs(guess - ref).max()) + 1e-7      # (the rounding of the guess to float32 included)
+                    vbound = (4e-7 * D + (2e-6 if D >= 4 else 3e-6) * np.abs(ref).max()) + (4e-7 * margin if D >= 4 else 0.0)
+                    vbound = max(vbound, MARGIN * v_e_ref)
+                    out, unit = hip.softmin_fwd_grad_raw(_t(x, cuda)[None], _t(y, cuda)[None], _t(h, cuda)[None], _t(guess, cuda)[None], margin_given, eps)
+                    out, unit = out[0].cpu().numpy(), unit[0].cpu().numpy()
+                    route, variant = f"fwd_grad D={D}", f"M={M} margin={k} eps"
+                    rep.exact(route, name, variant, bool(np.isfinite(out).all() and np.isfinite(unit).all()), "not finite")
+                    rep.add(route + " value", name, variant, np.abs(out - ref).max(), vbound, v_e_ref)
+                    rep.add(route + " gradient", name, variant, relerr(unit, refg), gbound, e_ref)
+    rep.finish()
+
+
+# ---- float64 ----------------------------------------------------------------------------------------------------------------------
+def test_float64(cuda):
+    """``hip.softmin`` and its autograd gradient on float64 clouds: steps past the e^500 threshold of the lazy maximum (``stairs600``), terms
+    between e^0 and e^500 above it (``stairs400``), a late maximum, voids.  Clouds, temperatures and bounds of tests/test_f64_gpu.py."""
+    rep = _Report("float64")
+    N, M = 300, 1000
+    pats = dp.patterns(M, np.random.default_rng(M))
+    for D in (3, 20):
+        for p in (2, 1):
+            x, y, _ = _clouds_f64(D + p, N, M, D)
+            eps = 0.05 if p == 2 else 0.1
+            g = np.random.default_rng(1).standard_normal(N)
+            for name in ("stairs600", "stairs400", "late") + dp.VOIDS:
+                h = pats[name].astype(np.float64)
+                keep = np.isfinite(h)
+                ref = oracle_c.softmin(eps, x, y[keep], h[keep], p)
+                refg = oracle_c.softmin_grad_x(eps, x, y[keep], h[keep], g, p)
+                yl = np.array(y)
+                yl[~keep] = 1e30
+                xt = _t(x, cuda).requires_grad_(True)
+                out = hip.softmin(eps, xt, _t(yl, cuda), _t(h, cuda), p=p)
+                (gx,) = torch.autograd.grad(out, [xt], grad_outputs=_t(g, cuda))
+                route = f"f64 p={p} D={D}"
+                rep.exact(route, name, "", out.dtype == torch.float64 and gx.dtype == torch.float64 and bool(torch.isfinite(out).all() and torch.isfinite(gx).all()),
+                          "dtype or not finite")
+                rep.add(route + " value", name, "", relerr(out.detach().cpu().numpy(), ref), dp.F64_VALUE_BOUND)
+                rep.add(route + " gradient", name, "", relerr(gx.cpu().numpy(), refg), dp.F64_GRAD_BOUND)
+    rep.finish()
+
+
+# ---- rows without mass ------------------------------------------------------------------------------------------------------------
+def test_rows_without_mass(cuda):
+    """A batch of two whose second item has h = -inf throughout, at M = 300 (a padded last tile), M = 256 (none) and the split shape
+    (130, 5000: the partials of whole rows of mass 0 meet in the merges): that item's out, mass and gradient are exactly 0 and the soft-min
+    of ``plan_apply_p1`` is +inf; the first item (``floors``) is within its bound.  ``glhip_softmin_fwd_grad`` runs the same gradient
+    kernels from a guess: a finite one, and the forward's own value for such a row."""
+    rep = _Report("rows without mass")
+    for N, M in ((300, 300), (300, 256), (130, 5000)):
+        def batch(D, p):
+            x, y, eps = dp.clouds(D, p, N, M)
+            h0 = dp.patterns(M, np.random.default_rng(M + D))["floors"]
+            return np.stack([x, x]), np.stack([y, y]), np.stack([h0, np.full(M, -np.inf, np.float32)]), eps
+
+        # plan routes
+        for kind, D, V, flag_list in (("xd", 3, 40, (0, H2)), ("xd", 8, 40, (0, H2)), ("xd", 16, 31, (0, H2)), ("nd", 24, 70, (0, H2)), ("nd", 70, 70, (0, H2)),
+                                      ("p1", 3, 70, (0,)), ("p1", 33, 70, (0,))):
+            p = 1 if kind == "p1" else 2
+            x, y, h, eps = batch(D, p)
+            feat = np.random.default_rng(V).standard_normal((M, V)).astype(np.float32)
+            ref, _ = _plan_ref(kind, x[0], y[0], h[0], eps, feat)
+            e_ref = _plan_e_ref(cuda, kind, x[0], y[0], h[0], eps, feat, ref)
+            for flags in flag_list:
+                for fl in (flags, flags | NS):
+                    out, side = _plan_launch(cuda, kind, x, y, h, np.stack([feat, feat]), eps, fl, True)
+                    route, variant = f"plan {kind} D={D} flags={flags}", f"M={M} flags={fl}"
+                    rep.add(route, "floors", variant, _plan_worst(out[0], ref, feat), max(dp.PLAN_BOUND, MARGIN * e_ref), e_ref)
+                    rep.exact(route, "massless", variant, bool((out[1] == 0).all()), f"out: {int((out[1] != 0).sum())} entries are not 0 "
+                              f"({int(np.isnan(out[1]).sum())} NaN)")
+                    if kind == "p1":
+                        rep.exact(route, "massless", variant, bool(np.isposinf(side[1]).all()), f"soft-min {side[1][:3]} is not +inf")
+                    else:
+                        rep.exact(route, "massless", variant, bool((side[1] == 0).all()), f"mass {side[1][:3]} is not 0")
+        # gradient routes
+        for D, p, fwd_flags, flags in ([(D, 2, f, f) for D in (3, 5, 8, 16) for f in (0, H2)] + [(D, 2, 0, f) for D in (24, 70) for f in (0, XK)]
+                                       + [(3, 1, 0, 0), (8, 1, 0, 0), (33, 1, 0, 0), (33, 1, XKD, XDG)]):
+            x, y, h, eps = batch(D, p)
+            g = np.random.default_rng(D).standard_normal((2, N)).astype(np.float32)
+            ref = _oracle_grad(cuda, D, eps, x[0], y[0], h[0], g[0], p)
+            e_ref = (_p2_grad_f32_error(cuda, x[0], y[0], h[0], g[0], eps, ref) if p == 2
+                     else _p1_grad_f32_error(cuda, "softmin_p1", x[0], y[0], h[0], g[0], eps, ref))
+            for fl in (flags, flags | NS):
+                _, gx = _grad_launch(cuda, x, y, h, g, eps, p, fwd_flags | (fl & NS), fl, True)
+                route, variant = f"grad p={p} D={D} flags={flags}", f"M={M} flags={fl}"
+                rep.add(route, "floors", variant, relerr(gx[0], ref), max(dp.grad_bound(D, p), MARGIN * e_ref), e_ref)
+                rep.exact(route, "massless", variant, bool((gx[1] == 0).all()), f"gradient: {int((gx[1] != 0).sum())} entries are not 0 "
+                          f"({int(np.isnan(gx[1]).sum())} NaN), largest {np.nanmax(np.abs(gx[1])):.2e}")
+        # value and gradient from a guess (p = 2, D <= 16): gradient 0; the value +inf, or huge where the forward kernels return that
+        for D in (3, 8):
+            x, y, h, eps = batch(D, 2)
+            xb, yb, hb = _t(x, cuda), _t(y, cuda), _t(h, cuda)
+            ref = oracle_c.softmin(eps, x[0], y[0], h[0], 2)
+            refg = oracle_c.softmin_grad_x(eps, x[0], y[0], h[0], np.ones(N, np.float32), 2)
+            e_ref = _p2_grad_f32_error(cuda, x[0], y[0], h[0], np.ones(N, np.float32), eps, refg)
+            fwd = hip.softmin_fwd_raw(xb, yb, hb, eps, 2, None, 0).cpu().numpy()
+            for what, guess1 in (("finite guess", np.zeros(N, np.float32)), ("the forward's value", fwd[1])):
+                guess = np.stack([(ref + eps).astype(np.float32), guess1])
+                margin = 1.0001 * float(np.abs(guess[0] - ref).max()) + 1e-7
+                out, unit = hip.softmin_fwd_grad_raw(xb, yb, hb, _t(guess, cuda), margin, eps)
+                out, unit = out.cpu().numpy(), unit.cpu().numpy()
+                route, variant = f"fwd_grad D={D}", f"M={M} {what}"
+                rep.add(route + " gradient", "floors", variant, relerr(unit[0], refg), max(2e-5 if D >= 4 else 3e-5, MARGIN * e_ref), e_ref)
+                rep.exact(route, "massless", variant, bool((unit[1] == 0).all()), f"gradient: {int((unit[1] != 0).sum())} entries are not 0 "
+                          f"({int(np.isnan(unit[1]).sum())} NaN)")
+                rep.exact(route, "massless", variant, bool((out[1] > 1e20).all()), f"value {out[1][:3]} is neither +inf nor huge")
+        # the block-sparse p = 1 kernels of D <= 3 take one problem per launch
+        x, y, eps = dp.clouds(3, 1, N, M)
+        ranges = from_matrix(torch.tensor([[0, N]], dtype=torch.int32, device=cuda), torch.tensor([[0, M]], dtype=torch.int32, device=cuda),
+                             torch.ones((1, 1), dtype=torch.bool, device=cuda))
+        _, gx = _grad_launch(cuda, x, y, np.full(M, -np.inf, np.float32), np.ones(N, np.float32), eps, 1, MD, MD, True, ranges)
+        rep.exact("grad p=1 D=3 block-sparse", "massless", f"M={M}", bool((gx == 0).all()), f"gradient: {int((gx != 0).sum())} entries are not 0")
+        # float64
+        for D in (3, 20):
+            for p in (2, 1):
+                x, y, _ = _clouds_f64(D + p, N, M, D, B=2)
+                h = np.stack([dp.patterns(M, np.random.default_rng(M))["floors"].astype(np.float64), np.full(M, -np.inf)])
+                eps = 0.05 if p == 2 else 0.1
+                g = np.random.default_rng(1).standard_normal((2, N))
+                xt = _t(x, cuda).requires_grad_(True)
+                out = hip.softmin(eps, xt, _t(y, cuda), _t(h, cuda), p=p)
+                (gx,) = torch.autograd.grad(out, [xt], grad_outputs=_t(g, cuda))
+                out, gx = out.detach().cpu().numpy(), gx.cpu().numpy()
+                route, variant = f"f64 p={p} D={D}", f"M={M}"
+                rep.add(route + " gradient", "floors", variant, relerr(gx[0], oracle_c.softmin_grad_x(eps, x[0], y[0], h[0], g[0], p)), dp.F64_GRAD_BOUND)
+                rep.exact(route, "massless", variant, bool(np.isposinf(out[1]).all()), "soft-min is not +inf")
+                rep.exact(route, "massless", variant, bool((gx[1] == 0).all()), f"gradient: {int((gx[1] != 0).sum())} entries are not 0 "
+                          f"({int(np.isnan(gx[1]).sum())} NaN)")
+    rep.finish()
+
+
+# ---- an inaccurate saved forward value --------------------------------------------------------------------------------------------
+def _inaccurate_forward_route(rep, dev, kind, D, V, flag_list, names, known=True):
+    """``known``: leave the ``out`` check of the ``LONG_CHAIN`` pairs to test_long_chains_on_steep_duals, which runs it"""
+    for N, M in dp.SHAPES:
+        x, y, eps, pats = _host(D, 2, N, M)
+        feat = np.random.default_rng(V).standard_normal((M, V)).astype(np.float32)
+        for name in names:
+            h = pats[name]
+            ref, _ = _plan_ref(kind, x, y, h, eps, feat)
+            e_ref = _plan_e_ref(dev, kind, x, y, h, eps, feat, ref)
+            exact = o64.softmin(eps, x, y, h, 2, device=dev) if D > 64 else oracle_c.softmin(eps, x, y, h, 2)
+            for k in (-20, 20):
+                fwd = (exact + k * eps).astype(np.float32)
+                want_mass = np.exp((fwd.astype(np.float64) - exact) / eps)
+                for flags in flag_list:
+                    for fl, ws, tag in _variants(M, flags):
+                        out, mass = _plan_launch(dev, kind, x, y, h, feat, eps, fl, ws, fwd=fwd)
+                        route, variant = f"plan {kind} D={D} flags={flags} inaccurate fwd", f"M={M} {tag} delta={k} eps"
+                        rep.exact(route, name, variant, bool(np.isfinite(out).all() and np.isfinite(mass).all()), "not finite")
+                        if not (known and (kind, D, flags, name) in LONG_CHAIN):
+                            rep.add(route, name, variant, _plan_worst(out, ref, feat), max(dp.PLAN_BOUND, MARGIN * e_ref), e_ref)
+                        rep.add(route + " mass", name, variant, np.abs(mass / want_mass - 1.0).max(), dp.PLAN_MASS_BOUND)
+
+
+def test_inaccurate_forward_value(cuda):
+    """fwd + delta with delta / eps = -20, +20 on the p = 2 plan routes: ``out`` stays within the same bound, ``mass`` is exp(delta / eps) to
+    1e-4 relative (the |mass - 1| bound of test_parity).  The exact soft-min is float64's; the delta the kernel sees is that of the float32
+    value it is given."""
+    rep = _Report("inaccurate fwd")
+    for kind, D, V in (("xd", 3, 40), ("xd", 8, 40), ("xd", 16, 31), ("nd", 24, 70), ("nd", 70, 70)):
+        _inaccurate_forward_route(rep, cuda, kind, D, V, (0, H2), ("ramp", "twin"))
+    rep.finish()
+
+
+# ---- feature range ----------------------------------------------------------------------------------------------------------------
+def test_feature_range(cuda):
+    """``feature_patterns`` on N(0, 1) duals and on ``ramp``, all three plan routes.  Per-column error as
+    tests/test_plan_apply_gpu.py::test_feature_range (relative to max_j |f_j|, bound 2e-5; zero column exactly 0; constant column 2e-6), except
+    the 24-decade column, whose error is relative to float64's own weighting of it: max_i |out - ref| / max_i sum_j P_ij |f_j|."""
+    rep = _Report("feature range")
+    V = 7
+    for kind, D in (("xd", 3), ("xd", 8), ("nd", 24), ("p1", 33)):
+        p = 1 if kind == "p1" else 2
+        for N, M in dp.SHAPES:
+            x, y, eps, pats = _host(D, p, N, M)
+            feat = dp.feature_patterns(M, V, np.random.default_rng(V))
+            normal = np.random.default_rng(D + M).standard_normal(M).astype(np.float32)
+            for name, h in (("normal", normal), ("ramp", pats["ramp"])):
+                ref, _ = _plan_ref(kind, x, y, h, eps, feat)
+                weighted, _ = _plan_ref(kind, x, y, h, eps, np.abs(feat))
+                scale = np.abs(feat).max(0).astype(np.float64)
+                scale[0] = weighted[:, 0].max()
+                scale[3] = 1.0
+                xt, yt, ht, ft = (_t(a, cuda) for a in (x, y, h, feat))
+                if kind == "p1":
+                    P = torch.softmax(ht[None, :] - torch.cdist(xt, yt).clamp_min(1e-4) / eps, dim=1)
+                else:
+                    C = (xt * xt).sum(1)[:, None] - 2.0 * xt @ yt.t() + (yt * yt).sum(1)[None, :]
+                    P = torch.softmax(ht[None, :] - C / (2.0 * eps), dim=1)
+                e_ref = np.abs((P @ ft).cpu().numpy() - ref).max(0) / scale
+                for flags in ((0,) if kind == "p1" else (0, H2)):
+                    for fl, ws, tag in _variants(M, flags):
+                        out, _ = _plan_launch(cuda, kind, x, y, h, feat, eps, fl, ws)
+                        per_col = np.abs(out - ref).max(0) / scale
+                        route, variant = f"plan {kind} D={D} flags={flags}", f"M={M} {tag}"
+                        rep.exact(route, name, variant, bool(np.isfinite(out).all()), "not finite")
+                        for v, what in ((0, "24 decades"), (1, "x 1e12"), (2, "x 1e-12"), (5, "normal"), (6, "normal")):
+                            rep.add(f"{route} column {what}", name, variant, per_col[v], max(dp.PLAN_BOUND, MARGIN * e_ref[v]), float(e_ref[v]))
+                        rep.exact(route, name, variant, bool((out[:, 3] == 0).all()), "the zero column is not exactly 0")
+                        rep.add(route + " constant column", name, variant, np.abs(out[:, 4] / 2.5 - 1.0).max(), 2e-6)
+    rep.finish()
