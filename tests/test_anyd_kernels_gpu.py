@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from cloud_support import clouds as _clouds, random_ranges as _random_ranges, to_dev as _t, tol as _tol
 from conftest import load_golden, relerr
 from geomloss_amd import SamplesLoss, hip
 from geomloss_amd.cluster import from_matrix
@@ -20,23 +21,6 @@ from oracle import oracle_torch64 as o64
 pytestmark = pytest.mark.gpu
 
 H2 = hip.FLAG_F16X2
-
-
-def _clouds(seed, N, M, D, B=None):      # as tests/test_xd_kernels_gpu.py
-    rng = np.random.default_rng(seed)
-    shp = (lambda n: (n, D)) if B is None else (lambda n: (B, n, D))
-    x = rng.random(shp(N)).astype(np.float32)
-    y = (rng.random(shp(M)) * 0.8 + 0.1).astype(np.float32)
-    h = rng.standard_normal(shp(M)[:-1]).astype(np.float32)
-    return x, y, h
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def _tol(ref, D):
-    return 4e-7 * D + 2e-6 * np.abs(ref).max()       # the bound of tests/test_xd_kernels_gpu.py: ~2^-22 diam^2 on a potential; diam^2 <= D
 
 
 # ---- 1. soft-min forward ---------------------------------------------------------------------------------------------------
@@ -138,19 +122,6 @@ def test_softmin_batched_bf16_and_fused_step(cuda):
 
 # ---- 4. block-sparse launches ----------------------------------------------------------------------------------------------
 
-def _random_ranges(rng, N, M, ci, cj, density, dev):
-    cut_i = np.sort(rng.choice(np.arange(1, N), ci - 1, replace=False))
-    cut_j = np.sort(rng.choice(np.arange(1, M), cj - 1, replace=False))
-    ri = np.stack([np.r_[0, cut_i], np.r_[cut_i, N]], 1).astype(np.int32)
-    rj = np.stack([np.r_[0, cut_j], np.r_[cut_j, M]], 1).astype(np.int32)
-    keep = rng.random((ci, cj)) < density
-    keep[0, :] = False      # one row block with nothing to reduce over
-    keep[1, :] = True
-    rg = from_matrix(torch.from_numpy(ri).to(dev), torch.from_numpy(rj).to(dev), torch.from_numpy(keep).to(dev))
-    tup = tuple(t.cpu().numpy() for t in (rg.ranges_i, rg.slices_i, rg.redranges_j))
-    return rg, tup, ri
-
-
 @pytest.mark.parametrize("ci,cj", [(9, 11), (60, 70)])
 def test_block_sparse_softmin_and_gaussian(cuda, ci, cj):
     """Ragged ranges at D = 32; 60 x 70 clusters: row clusters of ~40 points whose tiles gather several column intervals."""
@@ -158,7 +129,7 @@ def test_block_sparse_softmin_and_gaussian(cuda, ci, cj):
     rng = np.random.default_rng(17)
     N, M = 2300, 2600
     x, y, h = _clouds(23, N, M, D)
-    rg, tup, ri = _random_ranges(rng, N, M, ci, cj, 0.4, cuda)
+    rg, tup, _, _, ri = _random_ranges(rng, N, M, ci, cj, 0.4, cuda)
     eps = 0.02 * D / 3
     ref = oracle_c.softmin(eps, x, y, h, 2, ranges=tup)
     empty = slice(ri[0, 0], ri[0, 1])
@@ -345,7 +316,7 @@ def test_block_sparse_gradients_any_dimension(cuda):
     rng = np.random.default_rng(19)
     N, M = 900, 1000
     x, y, h = _clouds(29, N, M, D)
-    rg, tup, ri = _random_ranges(rng, N, M, 9, 11, 0.5, cuda)
+    rg, tup, _, _, ri = _random_ranges(rng, N, M, 9, 11, 0.5, cuda)
     live = np.ones(N, bool)
     live[ri[0, 0]:ri[0, 1]] = False
     g = rng.standard_normal(N).astype(np.float32)

@@ -5,14 +5,11 @@ After the radix sort, every whole aligned block of 1024 positions of both sorted
 into cells of exactly 512, 256, 128, 64 and 32 points.  The order shows through glhip_prune_inspect (perm_x, perm_y): it must be a
 permutation, the same on every call, with the split property at all five levels of every whole block, the axis recomputed from the
 points; and it must buy what it is for: the device's intervals cover at most 0.9 of the blocks the CPU model keeps on the path order
-of the same input.  The pruning is exact for any order, so launches are held to the rule of tests/test_exact_prune_gpu.py against the
+of the same input.  The pruning is exact for any order, so launches are held to prune_support.close against the
 same call under GLHIP_FLAG_NO_SORT, on inputs that put NaN, infinities and runs of identical points inside whole blocks.
 """
 
-import ctypes
 import math
-import os
-import sys
 
 import numpy as np
 import pytest
@@ -20,82 +17,15 @@ import torch
 
 from geomloss_amd import hip
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-import prune_model as pm  # noqa: E402
+import prune_support as ps
+from prune_support import pm
 
 pytestmark = pytest.mark.gpu
 
-F16X2, NO_SORT = hip.FLAG_F16X2, hip.FLAG_NO_SORT
-DEV = torch.device("cuda:0") if torch.cuda.is_available() else None
-LAYOUTS = pytest.mark.parametrize("flags", [F16X2, 0], ids=["f16x2", "bf16x3"])
+DEV, NO_SORT, LAYOUTS = ps.DEV, ps.NO_SORT, ps.LAYOUTS
 BLOCK, LEAF = 1024, 32
 EPS = 0.05**2
-
-
-def _law(n, m, D, seed, dtype=torch.float32):
-    """the headline law (bench.make_problem) in D dimensions: uniform unit cube, h = -log M + N(0, 0.01^2) / 0.05^2"""
-    g = torch.Generator().manual_seed(seed)
-    x = torch.rand(1, n, D, generator=g)
-    y = torch.rand(1, m, D, generator=g)
-    h = torch.full((1, m), -math.log(m)) + 0.01 * torch.randn(1, m, generator=g) / (0.05**2)
-    return x.to(DEV, dtype).contiguous(), y.to(DEV, dtype).contiguous(), h.to(DEV).contiguous()
-
-
-def _workspace(lib, n, m, D):
-    nbytes = int(lib.glhip_workspace_bytes(1, n, m, D, 0))
-    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=DEV), nbytes
-
-
-def _fwd(x, y, h, eps, flags):
-    lib = hip.load_library()
-    B, n, D = x.shape
-    m = y.shape[1]
-    ws, nbytes = _workspace(lib, n, m, D)
-    out = torch.empty((B, n), dtype=torch.float32, device=DEV)
-    rc = lib.glhip_softmin_fwd(x.data_ptr(), y.data_ptr(), h.data_ptr(), out.data_ptr(), B, n, m, D, float(eps), 2, hip._dtype_code(x),
-                               None, None, None, 0, ctypes.c_void_p(ws.data_ptr()), nbytes, int(flags), hip._stream(x))
-    assert rc == 0, lib.glhip_last_error()
-    return out
-
-
-def _inspect(x, y, h, eps):
-    """glhip_prune_inspect -> NumPy records (the orders and the intervals)"""
-    lib = hip.load_library()
-    _, n, D = x.shape
-    m = y.shape[1]
-    C, S = (n + 255) // 256, int(lib.glhip_prune_inspect_slots(m))
-    i32 = dict(dtype=torch.int32, device=DEV)
-    r = dict(perm_x=torch.empty(n, **i32), perm_y=torch.empty(m, **i32), intervals=torch.empty((C, S, 2), **i32))
-    ws, nbytes = _workspace(lib, n, m, D)
-    rc = lib.glhip_prune_inspect(x.data_ptr(), y.data_ptr(), h.data_ptr(), None, n, m, D, float(eps), hip._dtype_code(x),
-                                 r["perm_x"].data_ptr(), r["perm_y"].data_ptr(), None, None, None, r["intervals"].data_ptr(), None,
-                                 ctypes.c_void_p(ws.data_ptr()), nbytes, hip._stream(x))
-    assert rc == 0, lib.glhip_last_error()
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in r.items()}
-
-
-def _diam2(x, y):
-    z = torch.cat([x[0].float(), y[0].float()])
-    z = z[torch.isfinite(z).all(1)]
-    return float(((z.max(0).values - z.min(0).values) ** 2).sum())
-
-
-def _close(a, b, diam2):
-    """tests/test_exact_prune_gpu.py: the dense launch's own rounding, same NaN / infinity pattern"""
-    assert torch.equal(a.isnan(), b.isnan())
-    fin = ~b.isnan()
-    if not bool(fin.any()):
-        return
-    assert torch.equal(a[fin].isinf(), b[fin].isinf()) and torch.equal(a[fin & a.isinf()], b[fin & b.isinf()])
-    ok = fin & ~b.isinf()
-    if bool(ok.any()):
-        av, bv = a[ok].double(), b[ok].double()
-        err = float((av - bv).abs().max())
-        print(f"max|pruned - dense| {err:.3e} (bound {4e-7 * diam2 + 2e-6 * float(bv.abs().max()):.3e})")
-        assert err <= 4e-7 * diam2 + 2e-6 * float(bv.abs().max()), (err, diam2)
+ORDER = ("perm_x", "perm_y", "intervals")      # the records these tests read
 
 
 def _check_order(z, perm):
@@ -121,9 +51,9 @@ def _check_order(z, perm):
 @pytest.mark.parametrize("n,m,D,dtype", [(320000, 320000, 3, torch.float32), (320000, 320000, 3, torch.bfloat16), (317000, 320037, 2, torch.float32),
                                          (330001, 310000, 1, torch.float32)], ids=["d3", "d3-bf16", "d2-uneven", "d1"])
 def test_order_is_balanced_and_repeatable(n, m, D, dtype):
-    x, y, h = _law(n, m, D, 40 + D, dtype)
-    a = _inspect(x, y, h, EPS)
-    b = _inspect(x, y, h, EPS)
+    x, y, h = ps.law(n, m, 40 + D, D=D, dtype=dtype)
+    a = ps.inspect(x, y, h, EPS, records=ORDER)
+    b = ps.inspect(x, y, h, EPS, records=ORDER)
     for k in a:
         assert np.array_equal(a[k], b[k]), k
     _check_order(x[0].float().cpu().numpy(), a["perm_x"])
@@ -134,14 +64,11 @@ def test_order_is_in_effect_on_the_mass_law():
     """the law of tests/test_prune_mass_gpu.py (seed 21): the blocks the device's intervals cover against the first-level fraction of
     the model on the path order of the same input (modelled: 0.3183 against 0.3802)"""
     n = 320000
-    g = torch.Generator().manual_seed(21)
-    x = torch.rand(1, n, 3, generator=g)
-    y = torch.rand(1, n, 3, generator=g)
-    h = torch.full((1, n), -math.log(n)) + 0.01 * torch.randn(1, n, generator=g) / (0.05**2)
-    xn, yn, hn = x[0].numpy(), y[0].numpy(), h[0].numpy()
+    x, y, h = ps.law(n, n, 21)
+    xn, yn, hn = x[0].cpu().numpy(), y[0].cpu().numpy(), h[0].cpu().numpy()
     px, py = pm.compact_order2(xn, 256, 2), pm.compact_order2(yn, 256, 2)
     path = float(pm.plan_mass(xn[px], yn[py], hn[py], EPS)[0].mean())
-    rec = _inspect(x.to(DEV).contiguous(), y.to(DEV).contiguous(), h.to(DEV).contiguous(), EPS)
+    rec = ps.inspect(x, y, h, EPS, records=ORDER)
     iv = rec["intervals"].astype(np.int64)
     length = np.maximum(iv[:, :, 1] - iv[:, :, 0], 0)
     covered = float(((length + pm.BLOCK - 1) // pm.BLOCK).sum()) / (iv.shape[0] * ((n + pm.BLOCK - 1) // pm.BLOCK))
@@ -167,7 +94,7 @@ def test_nan_and_infinities_inside_whole_blocks(flags):
     makes every row NaN: the pattern is compared); then 50 infinite coordinates on top: an infinite bounding box leaves the path order
     the caller's order, and the marked points sit in the middle of it."""
     n = 320000
-    x, y, h = _law(n, n, 3, 51)
+    x, y, h = ps.law(n, n, 51)
     g = torch.Generator().manual_seed(52)
     ix, iy = _middle(x), _middle(y)
     ix = ix[torch.randperm(ix.numel(), generator=g)[:3000].to(DEV)]
@@ -175,15 +102,15 @@ def test_nan_and_infinities_inside_whole_blocks(flags):
     whole = (n // BLOCK) * BLOCK
 
     def check(marked_x, marked_y):
-        rec = _inspect(x, y, h, EPS)
+        rec = ps.inspect(x, y, h, EPS, records=ORDER)
         for perm, idx in ((rec["perm_x"], marked_x), (rec["perm_y"], marked_y)):
             if idx is not None:
                 pos = _positions(perm, idx)
                 assert pos.min() >= BLOCK and pos.max() < whole      # inside whole blocks, away from the ends
         _check_order(x[0].cpu().numpy(), rec["perm_x"])
         _check_order(y[0].cpu().numpy(), rec["perm_y"])
-        a, b = _fwd(x, y, h, EPS, flags), _fwd(x, y, h, EPS, flags | NO_SORT)
-        _close(a, b, _diam2(x, y))
+        a, b = ps.fwd(x, y, h, EPS, flags), ps.fwd(x, y, h, EPS, flags | NO_SORT)
+        ps.close(a, b, ps.diam2(x, y))
         return a
 
     x, y = x.clone(), y.clone()
@@ -204,11 +131,11 @@ def test_nan_and_infinities_inside_whole_blocks(flags):
 def test_identical_points(flags):
     """5000 identical points in each cloud: they share a voxel, so whole blocks of the path order hold nothing else"""
     n = 320000
-    x, y, h = _law(n, n, 3, 53)
+    x, y, h = ps.law(n, n, 53)
     x, y = x.clone(), y.clone()
     x[0, 150000:155000] = torch.tensor([0.5, 0.5, 0.5], device=DEV)
     y[0, 70000:75000] = torch.tensor([0.5, 0.25, 0.75], device=DEV)
-    rec = _inspect(x, y, h, EPS)
+    rec = ps.inspect(x, y, h, EPS, records=ORDER)
     for perm, lo in ((rec["perm_x"], 150000), (rec["perm_y"], 70000)):
         pos = _positions(perm, torch.arange(lo, lo + 5000))
         full = np.flatnonzero(np.bincount(pos // BLOCK, minlength=n // BLOCK + 1) == BLOCK)
@@ -217,17 +144,17 @@ def test_identical_points(flags):
             assert (np.diff(perm[b * BLOCK:(b + 1) * BLOCK]) > 0).all(), b
     _check_order(x[0].cpu().numpy(), rec["perm_x"])
     _check_order(y[0].cpu().numpy(), rec["perm_y"])
-    _close(_fwd(x, y, h, EPS, flags), _fwd(x, y, h, EPS, flags | NO_SORT), _diam2(x, y))
+    ps.close(ps.fwd(x, y, h, EPS, flags), ps.fwd(x, y, h, EPS, flags | NO_SORT), ps.diam2(x, y))
 
 
 @LAYOUTS
 def test_half_step_at_the_uneven_d2_shape(flags):
     n, m = 317000, 320037
-    x, y, h = _law(n, m, 2, 54)
+    x, y, h = ps.law(n, m, 54, D=2)
     g = torch.Generator().manual_seed(55)
     logw = torch.full((1, m), -math.log(m)).to(DEV)
     pot = (h - logw) * EPS      # logw + pot / eps = h
     prev = (0.01 * torch.randn(1, n, generator=g)).to(DEV)
     a = hip.sinkhorn_step_raw(x, y, logw, pot, prev, EPS, 0.9, 2, None, flags)
     b = hip.sinkhorn_step_raw(x, y, logw, pot, prev, EPS, 0.9, 2, None, flags | NO_SORT)
-    _close(a, b, _diam2(x, y))
+    ps.close(a, b, ps.diam2(x, y))

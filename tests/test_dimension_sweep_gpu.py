@@ -28,6 +28,7 @@ import numpy as np
 import pytest
 import torch
 
+from cloud_support import tol as _tol
 from conftest import relerr
 from geomloss_amd import hip
 from oracle import oracle_c
@@ -86,10 +87,6 @@ def _rows(t, tags):
 
 def _drop(*clouds):
     return tuple(np.ascontiguousarray(c[..., :-1]) for c in clouds)
-
-
-def _tol(ref, D):
-    return 4e-7 * D + 2e-6 * np.abs(ref).max()      # tests/test_xd_kernels_gpu.py / test_anyd_kernels_gpu.py::_tol; diam^2 <= D
 
 
 def _eps2(D):

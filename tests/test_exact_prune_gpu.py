@@ -13,98 +13,49 @@ import torch
 
 from geomloss_amd import hip
 
+import prune_support as ps
+
 pytestmark = pytest.mark.gpu
 
-F16X2, NO_SORT = hip.FLAG_F16X2, hip.FLAG_NO_SORT
-DEV = torch.device("cuda:0") if torch.cuda.is_available() else None
-
-
-def _law(n, m, seed, eps=0.05**2, dtype=torch.float32):
-    """the headline law (bench.make_problem): uniform unit cube, h = -log M + N(0, 0.01^2) / eps"""
-    g = torch.Generator().manual_seed(seed)
-    x = torch.rand(1, n, 3, generator=g)
-    y = torch.rand(1, m, 3, generator=g)
-    h = torch.full((1, m), -math.log(m)) + 0.01 * torch.randn(1, m, generator=g) / (0.05**2)
-    return x.to(DEV, dtype).contiguous(), y.to(DEV, dtype).contiguous(), h.to(DEV).contiguous(), eps
-
-
-def _fwd(x, y, h, eps, flags, ws_bytes=None):
-    """one glhip_softmin_fwd call through the C-ABI; ws_bytes: a workspace of that many bytes instead of glhip_workspace_bytes"""
-    lib = hip.load_library()
-    B, N, D = x.shape
-    M = y.shape[1]
-    nbytes = int(lib.glhip_workspace_bytes(B, N, M, D, 0)) if ws_bytes is None else int(ws_bytes)
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=DEV)
-    out = torch.empty((B, N), dtype=torch.float32, device=DEV)
-    rc = lib.glhip_softmin_fwd(x.data_ptr(), y.data_ptr(), h.data_ptr(), out.data_ptr(), B, N, M, D, float(eps), 2, hip._dtype_code(x),
-                               None, None, None, 0, ctypes.c_void_p(ws.data_ptr()), nbytes, int(flags), hip._stream(x))
-    assert rc == 0, lib.glhip_last_error()
-    return out
-
-
-def _oracle_rows(x, y, h, eps, rows):
-    """float64 soft-min of a sample of rows"""
-    xi = x[0, rows].double()
-    e = h[0].double()[None] - torch.cdist(xi, y[0].double()).pow(2) / (2 * eps)
-    return -eps * torch.logsumexp(e, 1)
-
-
-def _diam2(x, y):
-    z = torch.cat([x[0].float(), y[0].float()])
-    z = z[torch.isfinite(z).all(1)]
-    return float(((z.max(0).values - z.min(0).values) ** 2).sum())
-
-
-def _close(a, b, diam2):
-    """the dense launch's own rounding, the bound tests/test_hip_kernels.py uses for the expanded p = 2 form: 4e-7 diam^2 + 2e-6 of
-    the output's magnitude; same NaN / infinity pattern"""
-    assert torch.equal(a.isnan(), b.isnan())
-    fin = ~b.isnan()
-    if not bool(fin.any()):
-        return
-    assert torch.equal(a[fin].isinf(), b[fin].isinf()) and torch.equal(a[fin & a.isinf()], b[fin & b.isinf()])
-    ok = fin & ~b.isinf()
-    if bool(ok.any()):
-        av, bv = a[ok].double(), b[ok].double()
-        err = float((av - bv).abs().max())
-        assert err <= 4e-7 * diam2 + 2e-6 * float(bv.abs().max()), (err, diam2)
+DEV, F16X2, NO_SORT, LAYOUTS = ps.DEV, ps.F16X2, ps.NO_SORT, ps.LAYOUTS
+EPS = 0.05**2
 
 
 def _check_oracle(x, y, h, eps, flags, pruned):
     """the pruned result is as close to float64 as the dense launch is (plus one float32 ulp of the output)"""
     n = x.shape[1]
     rows = torch.linspace(0, n - 1, 256, device=DEV).long()
-    ref = _oracle_rows(x.float(), y.float(), h, eps, rows)
-    dense = _fwd(x, y, h, eps, flags | NO_SORT)
+    ref = ps.oracle_rows(x.float(), y.float(), h, eps, rows)
+    dense = ps.fwd(x, y, h, eps, flags | NO_SORT)
     ep = float((pruned[0, rows].double() - ref).abs().max())
     ed = float((dense[0, rows].double() - ref).abs().max())
     assert ep <= 1.5 * ed + 2 * float(ref.abs().max()) * 2**-24, (ep, ed)
 
 
-@pytest.mark.parametrize("flags", [F16X2, 0], ids=["f16x2", "bf16x3"])
+@LAYOUTS
 def test_headline_law_matches_dense(flags):
-    x, y, h, eps = _law(320000, 320000, 1)
-    a = _fwd(x, y, h, eps, flags)
-    _close(a, _fwd(x, y, h, eps, flags | NO_SORT), _diam2(x, y))
-    _check_oracle(x, y, h, eps, flags, a)
+    x, y, h = ps.law(320000, 320000, 1)
+    a = ps.fwd(x, y, h, EPS, flags)
+    ps.close(a, ps.fwd(x, y, h, EPS, flags | NO_SORT), ps.diam2(x, y))
+    _check_oracle(x, y, h, EPS, flags, a)
 
 
-@pytest.mark.parametrize("flags", [F16X2, 0], ids=["f16x2", "bf16x3"])
+@LAYOUTS
 def test_uneven_shapes(flags):
     # N != M, N not a multiple of the 256-row slab, M not a multiple of the 256-column block
-    x, y, h, eps = _law(250001, 400007, 2)
-    a = _fwd(x, y, h, eps, flags)
-    _close(a, _fwd(x, y, h, eps, flags | NO_SORT), _diam2(x, y))
-    _check_oracle(x, y, h, eps, flags, a)
+    x, y, h = ps.law(250001, 400007, 2)
+    a = ps.fwd(x, y, h, EPS, flags)
+    ps.close(a, ps.fwd(x, y, h, EPS, flags | NO_SORT), ps.diam2(x, y))
+    _check_oracle(x, y, h, EPS, flags, a)
 
 
-@pytest.mark.parametrize("flags", [F16X2, 0], ids=["f16x2", "bf16x3"])
+@LAYOUTS
 def test_bf16_input(flags):
-    x, y, h, eps = _law(300000, 340000, 3, dtype=torch.bfloat16)
-    _close(_fwd(x, y, h, eps, flags), _fwd(x, y, h, eps, flags | NO_SORT), _diam2(x, y))
+    x, y, h = ps.law(300000, 340000, 3, dtype=torch.bfloat16)
+    ps.close(ps.fwd(x, y, h, EPS, flags), ps.fwd(x, y, h, EPS, flags | NO_SORT), ps.diam2(x, y))
 
 
-@pytest.mark.parametrize("flags", [F16X2, 0], ids=["f16x2", "bf16x3"])
+@LAYOUTS
 def test_clusters_with_far_outlier(flags):
     g = torch.Generator().manual_seed(4)
     n = 327680
@@ -116,84 +67,83 @@ def test_clusters_with_far_outlier(flags):
     h = 0.3 * torch.randn(n, generator=g)
     x, y, h = x[None].to(DEV).contiguous(), y[None].to(DEV).contiguous(), h[None].to(DEV).contiguous()
     eps = 0.1**2      # diameter^2 / eps ~ 4e3: inside the f16 x 2 range contract
-    a = _fwd(x, y, h, eps, flags)
-    _close(a, _fwd(x, y, h, eps, flags | NO_SORT), _diam2(x, y))
+    a = ps.fwd(x, y, h, eps, flags)
+    ps.close(a, ps.fwd(x, y, h, eps, flags | NO_SORT), ps.diam2(x, y))
     _check_oracle(x, y, h, eps, flags, a)
 
 
-@pytest.mark.parametrize("flags", [F16X2, 0], ids=["f16x2", "bf16x3"])
+@LAYOUTS
 def test_nothing_pruned_at_large_eps(flags):
-    x, y, h, _ = _law(320000, 320000, 5)
-    _close(_fwd(x, y, h, 1.0, flags), _fwd(x, y, h, 1.0, flags | NO_SORT), _diam2(x, y))
+    x, y, h = ps.law(320000, 320000, 5)
+    ps.close(ps.fwd(x, y, h, 1.0, flags), ps.fwd(x, y, h, 1.0, flags | NO_SORT), ps.diam2(x, y))
 
 
 def test_most_pruned_at_small_eps():
     # eps = 0.015^2: diameter^2 / eps = 1.3e4, inside the f16 x 2 contract; the CPU model (tools/prune_model.py) keeps < 10 % here
-    x, y, h, _ = _law(320000, 320000, 6)
+    x, y, h = ps.law(320000, 320000, 6)
     h = torch.zeros_like(h)
     eps = 0.015**2
     for flags in (F16X2, 0):
-        a = _fwd(x, y, h, eps, flags)
-        _close(a, _fwd(x, y, h, eps, flags | NO_SORT), _diam2(x, y))
+        a = ps.fwd(x, y, h, eps, flags)
+        ps.close(a, ps.fwd(x, y, h, eps, flags | NO_SORT), ps.diam2(x, y))
         _check_oracle(x, y, h, eps, flags, a)
 
 
-@pytest.mark.parametrize("flags", [F16X2, 0], ids=["f16x2", "bf16x3"])
+@LAYOUTS
 def test_half_step_matches_dense(flags):
-    x, y, h, eps = _law(300000, 340000, 7)
+    x, y, h = ps.law(300000, 340000, 7)
     g = torch.Generator().manual_seed(8)
     m, n = y.shape[1], x.shape[1]
     logw = torch.full((1, m), -math.log(m)).to(DEV)
-    pot = (h - logw) * eps      # logw + pot / eps = h
+    pot = (h - logw) * EPS      # logw + pot / EPS = h
     prev = (0.01 * torch.randn(1, n, generator=g)).to(DEV)
     for p_, v_ in ((pot, prev), (pot, None), (None, None)):
-        a = hip.sinkhorn_step_raw(x, y, logw if p_ is not None else h, p_, v_, eps, 0.9, 2, None, flags)
-        b = hip.sinkhorn_step_raw(x, y, logw if p_ is not None else h, p_, v_, eps, 0.9, 2, None, flags | NO_SORT)
-        _close(a, b, _diam2(x, y))
+        a = hip.sinkhorn_step_raw(x, y, logw if p_ is not None else h, p_, v_, EPS, 0.9, 2, None, flags)
+        b = hip.sinkhorn_step_raw(x, y, logw if p_ is not None else h, p_, v_, EPS, 0.9, 2, None, flags | NO_SORT)
+        ps.close(a, b, ps.diam2(x, y))
 
 
-@pytest.mark.parametrize("flags", [F16X2, 0], ids=["f16x2", "bf16x3"])
+@LAYOUTS
 def test_special_values(flags):
-    x, y, h, eps = _law(300000, 340000, 9)
+    x, y, h = ps.law(300000, 340000, 9)
     # -inf entries: whole blocks of them may go
     hm = h.clone()
     hm[0, ::3] = -math.inf
     hm[0, 1000:90000] = -math.inf
-    _close(_fwd(x, y, hm, eps, flags), _fwd(x, y, hm, eps, flags | NO_SORT), _diam2(x, y))
+    ps.close(ps.fwd(x, y, hm, EPS, flags), ps.fwd(x, y, hm, EPS, flags | NO_SORT), ps.diam2(x, y))
     # all -inf: every slab keeps everything
     hi = torch.full_like(h, -math.inf)
-    _close(_fwd(x, y, hi, eps, flags), _fwd(x, y, hi, eps, flags | NO_SORT), _diam2(x, y))
+    ps.close(ps.fwd(x, y, hi, EPS, flags), ps.fwd(x, y, hi, EPS, flags | NO_SORT), ps.diam2(x, y))
     # one NaN in h: the dense launch's NaN pattern
     hn = h.clone()
     hn[0, 4321] = math.nan
-    _close(_fwd(x, y, hn, eps, flags), _fwd(x, y, hn, eps, flags | NO_SORT), _diam2(x, y))
+    ps.close(ps.fwd(x, y, hn, EPS, flags), ps.fwd(x, y, hn, EPS, flags | NO_SORT), ps.diam2(x, y))
     # one NaN coordinate in x, then in y
     xn = x.clone()
     xn[0, 555, 1] = math.nan
-    _close(_fwd(xn, y, h, eps, flags), _fwd(xn, y, h, eps, flags | NO_SORT), _diam2(xn, y))
+    ps.close(ps.fwd(xn, y, h, EPS, flags), ps.fwd(xn, y, h, EPS, flags | NO_SORT), ps.diam2(xn, y))
     yn = y.clone()
     yn[0, 666, 2] = math.nan
-    _close(_fwd(x, yn, h, eps, flags), _fwd(x, yn, h, eps, flags | NO_SORT), _diam2(x, yn))
+    ps.close(ps.fwd(x, yn, h, EPS, flags), ps.fwd(x, yn, h, EPS, flags | NO_SORT), ps.diam2(x, yn))
 
 
 def test_small_workspace_falls_back_to_dense():
-    x, y, h, eps = _law(320000, 320000, 10)
+    x, y, h = ps.law(320000, 320000, 10)
     lib = hip.load_library()
     full = int(lib.glhip_workspace_bytes(1, 320000, 320000, 3, 0))
     small = full // 8
     # too small for the sorted call: the dense launch on the same (smaller) workspace, bit for bit
-    assert torch.equal(_fwd(x, y, h, eps, F16X2, small), _fwd(x, y, h, eps, F16X2 | NO_SORT, small))
+    assert torch.equal(ps.fwd(x, y, h, EPS, F16X2, small), ps.fwd(x, y, h, EPS, F16X2 | NO_SORT, small))
 
 
 def test_stream_capture():
-    x, y, h, eps = _law(320000, 320000, 11)
+    x, y, h = ps.law(320000, 320000, 11)
     lib = hip.load_library()
-    nbytes = int(lib.glhip_workspace_bytes(1, 320000, 320000, 3, 0))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+    ws, nbytes = ps.workspace(lib, 320000, 320000, 3)
     out = torch.empty((1, 320000), dtype=torch.float32, device=DEV)
 
     def run():
-        rc = lib.glhip_softmin_fwd(x.data_ptr(), y.data_ptr(), h.data_ptr(), out.data_ptr(), 1, 320000, 320000, 3, float(eps), 2,
+        rc = lib.glhip_softmin_fwd(x.data_ptr(), y.data_ptr(), h.data_ptr(), out.data_ptr(), 1, 320000, 320000, 3, float(EPS), 2,
                                    hip._dtype_code(x), None, None, None, 0, ctypes.c_void_p(ws.data_ptr()), nbytes, F16X2,
                                    hip._stream(x))
         assert rc == 0, lib.glhip_last_error()

@@ -8,16 +8,13 @@ import numpy as np
 import pytest
 import torch
 
+from cloud_support import to_dev as _t
 from conftest import golden_cases, load_golden, relerr
 from geomloss_amd import SamplesLoss, hip
 from geomloss_amd.cluster import from_matrix
 from oracle import oracle_c, oracle_np
 
 pytestmark = pytest.mark.gpu
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
 def _clouds(seed, N, M, D, B=None):

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+from cloud_support import to_dev as _t
 from conftest import relerr
 from geomloss_amd import SamplesLoss, hip
 from geomloss_amd import kernel_samples
@@ -41,10 +42,6 @@ def _clouds(seed, N, M, D, B=None, offset=0.0):
 
 def _blur(D):
     return 0.3 * math.sqrt(D / 3)
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
 def _batched(f):

@@ -15,25 +15,13 @@ import numpy as np
 import pytest
 import torch
 
+from cloud_support import clouds as _clouds, random_ranges as _random_ranges, to_dev as _t
 from conftest import relerr
 from geomloss_amd import hip
 from geomloss_amd.cluster import from_matrix
 from oracle import oracle_c, oracle_np
 
 pytestmark = pytest.mark.gpu
-
-
-def _clouds(seed, N, M, D, B=None, offset=0.0):
-    rng = np.random.default_rng(seed)
-    shp = (lambda n: (n, D)) if B is None else (lambda n: (B, n, D))
-    x = rng.random(shp(N)).astype(np.float32) + offset
-    y = (rng.random(shp(M)) * 0.8 + 0.1).astype(np.float32) + offset
-    h = rng.standard_normal(shp(M)[:-1]).astype(np.float32)
-    return x, y, h
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
 SOFTMIN_SHAPES = [(300, 257, 3), (1030, 2100, 3), (513, 1025, 2), (700, 900, 1), (64, 8, 3), (1, 1, 3), (5, 3000, 2)]
@@ -141,20 +129,6 @@ def test_softmin_rescale_branch_and_infinities(cuda):
     for flags in (0, 8, hip.FLAG_NO_MFMA, hip.FLAG_F16X2, hip.FLAG_F16X2 | hip.FLAG_NO_SPLIT):
         out2 = hip.softmin(eps, _t(x, cuda), _t(y, cuda), _t(h2, cuda), flags=flags).cpu().numpy()
         assert np.isfinite(out2).all() and relerr(out2, ref2) < 2e-6, flags
-
-
-def _random_ranges(rng, N, M, ci, cj, density, dev):
-    cut_i = np.sort(rng.choice(np.arange(1, N), ci - 1, replace=False))
-    cut_j = np.sort(rng.choice(np.arange(1, M), cj - 1, replace=False))
-    ri = np.stack([np.r_[0, cut_i], np.r_[cut_i, N]], 1).astype(np.int32)
-    rj = np.stack([np.r_[0, cut_j], np.r_[cut_j, M]], 1).astype(np.int32)
-    keep = rng.random((ci, cj)) < density
-    keep[0, :] = False      # one row block with nothing to reduce over
-    keep[1, :] = True
-    rg = from_matrix(torch.from_numpy(ri).to(dev), torch.from_numpy(rj).to(dev), torch.from_numpy(keep).to(dev))
-    tup = tuple(t.cpu().numpy() for t in (rg.ranges_i, rg.slices_i, rg.redranges_j))
-    tup_t = tuple(t.cpu().numpy() for t in (rg.ranges_j, rg.slices_j, rg.redranges_i))
-    return rg, tup, tup_t, keep, ri
 
 
 @pytest.mark.parametrize("p", [2, 1])

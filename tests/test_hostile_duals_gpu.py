@@ -24,6 +24,7 @@ import dual_patterns as dp
 import test_plan_apply_gpu as t_xd
 import test_plan_apply_nd_gpu as t_nd
 import test_plan_apply_p1_gpu as t_p1
+from cloud_support import to_dev as _t
 from conftest import relerr
 from geomloss_amd import hip
 from geomloss_amd.cluster import from_matrix
@@ -50,10 +51,6 @@ LONG_CHAIN = {
     ("nd", 24, 0, "ramp"): "1.28", ("nd", 24, H2, "ramp"): "1.01", ("nd", 70, 0, "ramp"): "2.56", ("nd", 70, H2, "ramp"): "1.75",
     ("nd", 70, 0, "twin"): "1.27", ("grad", 24, XK, "ramp"): "1.91", ("grad", 70, XK, "ramp"): "2.99", ("grad", 70, XK, "twin"): "1.77",
 }
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
 class _Report:

@@ -8,7 +8,7 @@ dual vector of bench.make_problem, the headline's f16 x 2 layout.
   return identical outputs, for glhip_softmin_fwd and for glhip_sinkhorn_step with pot and prev, and the glhip_prune_inspect records
   taken before and after them are identical;
 * a stale hint — the identity, and the order of ANOTHER cloud of the same size — stays within the bound that
-  tests/test_prep_kernels_gpu.py applies to pruned against dense (4e-7 diam^2 + 2e-6 of the output's magnitude);
+  prune_support.close applies to pruned against dense (4e-7 diam^2 + 2e-6 of the output's magnitude);
 * hip.softmin_fwd_raw: two hits on the second call, a miss after ``x.mul_(1.0)`` with the output of a cache-disabled call, hits for both
   clouds on (y, x) after (x, y).
 No test hands an out-of-range hint to the GPU: the clamp is tested on the host (tests/test_perm_reuse_cpu.py).
@@ -23,13 +23,15 @@ import torch
 
 from geomloss_amd import hip
 
+import prune_support as ps
+from prune_support import RECORDS
+
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda:0") if torch.cuda.is_available() else None
+DEV = ps.DEV
 EPS = 0.05**2
 FLAGS = hip.FLAG_F16X2
 SHAPES = {"wide": (65536, 1525900), "uneven": (317000, 320037)}
-RECORDS = ("perm_x", "perm_y", "mlb", "t1", "home", "intervals", "t2")
 
 
 def _problem(shape, D=3, dtype=torch.float32, seed=0):
@@ -42,28 +44,6 @@ def _problem(shape, D=3, dtype=torch.float32, seed=0):
     return x[None].contiguous(), y[None].contiguous(), h[None].contiguous()
 
 
-def _workspace(lib, x, y):
-    nbytes = int(lib.glhip_workspace_bytes(1, x.shape[1], y.shape[1], x.shape[2], 0))
-    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=DEV), nbytes
-
-
-def _inspect(x, y, h, pot=None):
-    lib = hip.load_library()
-    _, n, D = x.shape
-    m = y.shape[1]
-    C, S, nt = (n + 255) // 256, int(lib.glhip_prune_inspect_slots(m)), (n + 31) // 32
-    i32, f64 = dict(dtype=torch.int32, device=DEV), dict(dtype=torch.float64, device=DEV)
-    r = dict(perm_x=torch.empty(n, **i32), perm_y=torch.empty(m, **i32), mlb=torch.empty(C, **f64), t1=torch.empty(C, **f64),
-             home=torch.empty(C, **i32), intervals=torch.empty((C, S, 2), **i32), t2=torch.empty(nt, dtype=torch.float32, device=DEV))
-    ws, nbytes = _workspace(lib, x, y)
-    rc = lib.glhip_prune_inspect(x.data_ptr(), y.data_ptr(), h.data_ptr(), None if pot is None else pot.data_ptr(), n, m, D, float(EPS),
-                                 hip._dtype_code(x), *[r[k].data_ptr() for k in RECORDS], ctypes.c_void_p(ws.data_ptr()), nbytes,
-                                 hip._stream(x))
-    assert rc == 0, lib.glhip_last_error()
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in r.items()}
-
-
 def _same_records(a, b):
     for k in RECORDS:
         assert np.array_equal(a[k], b[k], equal_nan=k in ("mlb", "t1", "t2")), k
@@ -74,7 +54,7 @@ def _step(x, y, logw, pot=None, prev=None, damping=1.0, perm_x=None, perm_y=None
     lib = hip.load_library()
     _, n, D = x.shape
     m = y.shape[1]
-    ws, nbytes = _workspace(lib, x, y)
+    ws, nbytes = ps.workspace(lib, n, m, D)
     out = torch.empty((1, n), dtype=torch.float32, device=DEV)
     ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     tail = [None, None, None, 0, ctypes.c_void_p(ws.data_ptr()), nbytes, int(flags), hip._stream(x)]
@@ -103,7 +83,7 @@ def _shared(shape):
     """the D = 3 float32 problem of a shape, its inspect records and its exported permutations: made once, left unchanged"""
     if shape not in _PROBLEMS:
         x, y, h = _problem(shape)
-        rec = _inspect(x, y, h)
+        rec = ps.inspect(x, y, h, EPS)
         px, py = _buffers(x, y)
         out = _step(x, y, h, perm_x=px, perm_y=py)
         _PROBLEMS[shape] = (x, y, h, rec, px, py, out)
@@ -119,7 +99,7 @@ def test_exported_permutations_are_the_inspected_ones(shape, D, dtype):
         x, y, h, rec, px, py, _ = _shared(shape)
     else:
         x, y, h = _problem(shape, D, dtype)
-        rec = _inspect(x, y, h)
+        rec = ps.inspect(x, y, h, EPS)
         px, py = _buffers(x, y)
         _step(x, y, h, perm_x=px, perm_y=py)
     n, m = x.shape[1], y.shape[1]
@@ -164,7 +144,7 @@ def test_reuse_is_bit_identical(shape):
         assert torch.equal(out, plain)
     assert torch.equal(qy, py)
     assert torch.equal(px, keep_x) and torch.equal(py, keep_y)      # a hint is read, never written
-    _same_records(_inspect(x, y, h), rec)
+    _same_records(ps.inspect(x, y, h, EPS), rec)
     assert bool(torch.isfinite(plain).all())
 
 
@@ -176,7 +156,7 @@ def test_reuse_is_bit_identical_for_the_half_step(shape):
     logw = torch.full((1, m), -math.log(m), device=DEV)
     pot = (0.01 * torch.randn(1, m, generator=g)).to(DEV)
     prev = (0.01 * torch.randn(1, n, generator=g)).to(DEV)
-    before = _inspect(x, y, logw, pot)
+    before = ps.inspect(x, y, logw, EPS, pot)
     plain = _step(x, y, logw, pot, prev, 0.9, entry="step")
     qx, qy = _buffers(x, y)
     export = _step(x, y, logw, pot, prev, 0.9, perm_x=qx, perm_y=qy)
@@ -186,7 +166,7 @@ def test_reuse_is_bit_identical_for_the_half_step(shape):
     only_y = _step(x, y, logw, pot, prev, 0.9, perm_y=py, bits=hip.PERM_HINT_Y)
     for out in (export, both, only_x, only_y):
         assert torch.equal(out, plain)
-    _same_records(_inspect(x, y, logw, pot), before)
+    _same_records(ps.inspect(x, y, logw, EPS, pot), before)
     assert np.array_equal(before["perm_x"], rec["perm_x"]) and np.array_equal(before["perm_y"], rec["perm_y"])
     assert bool(torch.isfinite(plain).all())
 
@@ -201,38 +181,26 @@ def test_one_cloud_on_both_sides_sorts_once():
     plain = _step(x, x, h, entry="fwd")
     buf = torch.full((n,), -1, dtype=torch.int32, device=DEV)
     assert torch.equal(_step(x, x, h, perm_x=buf, perm_y=buf, bits=hip.PERM_HINT_Y), plain)
-    assert np.array_equal(buf.cpu().numpy(), _inspect(x, x, h)["perm_x"])
+    assert np.array_equal(buf.cpu().numpy(), ps.inspect(x, x, h, EPS)["perm_x"])
 
 
 # ---- 3. a stale hint is exact ------------------------------------------------------------------------------------------------------------
-
-def _close(a, b, diam2):
-    """tests/test_prep_kernels_gpu.py::_close: the dense launch's own rounding, 4e-7 diam^2 + 2e-6 of the output's magnitude"""
-    assert torch.equal(a.isnan(), b.isnan()) and torch.equal(a.isinf(), b.isinf())
-    ok = ~b.isnan() & ~b.isinf()
-    assert bool(ok.any())
-    err = float((a[ok].double() - b[ok].double()).abs().max())
-    bound = 4e-7 * diam2 + 2e-6 * float(b[ok].double().abs().max())
-    print(f"largest difference {err:.3e} (bound {bound:.3e})")
-    assert err <= bound, (err, bound)
-
 
 def test_a_stale_hint_is_exact():
     x, y, h, rec, px, py, pruned = _shared("wide")
     n, m = x.shape[1], y.shape[1]
     dense = _step(x, y, h, flags=FLAGS | hip.FLAG_NO_SORT, entry="fwd")
-    z = torch.cat([x[0], y[0]])
-    diam2 = float(((z.max(0).values - z.min(0).values) ** 2).sum())
-    _close(pruned, dense, diam2)
+    diam2 = ps.diam2(x, y)
+    ps.close(pruned, dense, diam2, require_finite=True)
     ident_x, ident_y = torch.arange(n, dtype=torch.int32, device=DEV), torch.arange(m, dtype=torch.int32, device=DEV)
-    _close(_step(x, y, h, perm_x=ident_x, perm_y=ident_y, bits=3), dense, diam2)
+    ps.close(_step(x, y, h, perm_x=ident_x, perm_y=ident_y, bits=3), dense, diam2, require_finite=True)
     # the order of ANOTHER cloud of the same size
     x2, y2, h2 = _problem("wide", seed=1)
     ox, oy = _buffers(x2, y2)
     _step(x2, y2, h2, perm_x=ox, perm_y=oy)
     assert not torch.equal(ox, px) and not torch.equal(oy, py)
-    _close(_step(x, y, h, perm_x=ox, perm_y=oy, bits=3), dense, diam2)
-    _close(_step(x, y, h, perm_x=ox, perm_y=py, bits=3), dense, diam2)      # one stale, one right
+    ps.close(_step(x, y, h, perm_x=ox, perm_y=oy, bits=3), dense, diam2, require_finite=True)
+    ps.close(_step(x, y, h, perm_x=ox, perm_y=py, bits=3), dense, diam2, require_finite=True)      # one stale, one right
 
 
 # ---- 4. through hip.softmin_fwd_raw -------------------------------------------------------------------------------------------------------

@@ -8,59 +8,14 @@ import numpy as np
 import pytest
 import torch
 
+from cloud_support import clouds as _clouds, plan_apply as _apply, plan_ref as _ref, plan_worst as _worst, to_dev as _t
 from geomloss_amd import hip
 
 pytestmark = pytest.mark.gpu
 
 
-def _clouds(seed, N, M, D, B=None, offset=0.0):      # tests/test_hip_kernels.py::_clouds
-    rng = np.random.default_rng(seed)
-    shp = (lambda n: (n, D)) if B is None else (lambda n: (B, n, D))
-    x = rng.random(shp(N)).astype(np.float32) + offset
-    y = (rng.random(shp(M)) * 0.8 + 0.1).astype(np.float32) + offset
-    h = rng.standard_normal(shp(M)[:-1]).astype(np.float32)
-    return x, y, h
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
 def _eps(D):
     return 0.01 if D <= 3 else 0.1 * D / 3
-
-
-def _ref(x, y, h, eps, feat, rows=64):
-    """float64: (W @ feat, rows that carry mass), row-chunked so that M = 70 001 stays small."""
-    x, y, h, feat = (np.asarray(t, dtype=np.float64) for t in (x, y, h, feat))
-    out = np.zeros((x.shape[0], feat.shape[1]))
-    for i0 in range(0, x.shape[0], rows):
-        xi = x[i0:i0 + rows]
-        E = h[None, :] - ((xi * xi).sum(1)[:, None] - 2.0 * xi @ y.T + (y * y).sum(1)[None, :]) / (2.0 * eps)
-        m = E.max(1, keepdims=True)
-        m = np.where(np.isfinite(m), m, 0.0)
-        W = np.exp(E - m)
-        s = W.sum(1, keepdims=True)
-        out[i0:i0 + rows] = (W / np.where(s > 0, s, 1.0)) @ np.where(np.isfinite(feat), feat, 0.0)
-    return out
-
-
-def _apply(dev, x, y, h, feat, eps, flags=0, **kw):
-    """Raw launch on (N,D) / (B,N,D) NumPy inputs -> out, mass as NumPy."""
-    xb, yb, hb, fb = (_t(a, dev) for a in (x, y, h, feat))
-    if xb.dim() == 2:
-        xb, yb, hb, fb = xb[None], yb[None], hb[None], fb[None]
-    fwd = hip.softmin_fwd_raw(xb, yb, hb, eps, 2, None, flags)
-    out, mass = hip.plan_apply_raw(xb, yb, hb, fwd, fb, eps, flags, want_mass=True, **kw)
-    out, mass = out.cpu().numpy(), mass.cpu().numpy()
-    return (out[0], mass[0]) if np.ndim(x) == 2 else (out, mass)
-
-
-def _worst(out, ref, feat):
-    """max over columns of max_i |out - ref| / max_j |feat_j|."""
-    scale = np.abs(feat).reshape(-1, feat.shape[-1]).max(0) if feat.ndim == 2 else np.abs(feat).max(-2, keepdims=True)
-    scale = np.where(scale > 0, scale, 1.0)
-    return float((np.abs(out - ref) / scale).max())
 
 
 SHAPES = [(300, 257, 3, 1), (1030, 1100, 2, 33), (200, 300, 1, 32), (64, 8, 3, 5), (1, 1, 3, 3), (5, 3000, 2, 70), (130, 600, 8, 40),
@@ -82,7 +37,7 @@ def _parity_case(N, M, D, V):      # inputs and the float64 reference, computed 
 def test_parity(cuda, N, M, D, V, flags):
     """Measured worst case over all shapes and flags on an MI355X: see DESIGN §4."""
     x, y, h, feat, ref = _parity_case(N, M, D, V)
-    out, mass = _apply(cuda, x, y, h, feat, _eps(D), flags)
+    out, mass = _apply(cuda, x, y, h, feat, _eps(D), flags, raw=hip.plan_apply_raw)
     err = _worst(out, ref, feat)
     print(f"parity N={N} M={M} D={D} V={V} flags={flags}: {err:.2e}, |mass - 1| {np.abs(mass - 1).max():.2e}")
     assert out.shape == (N, V) and np.isfinite(out).all()
@@ -116,9 +71,9 @@ def test_column_splits_and_long_reductions(cuda, N, M, D, V):
     feat = np.random.default_rng(V).standard_normal((M, V)).astype(np.float32)
     eps = 0.05**2 * D
     ref = _ref(x, y, h, eps, feat)
-    split, m0 = _apply(cuda, x, y, h, feat, eps, 0)
-    unsplit, m1 = _apply(cuda, x, y, h, feat, eps, hip.FLAG_NO_SPLIT)
-    nows, m2 = _apply(cuda, x, y, h, feat, eps, 0, workspace=False)
+    split, m0 = _apply(cuda, x, y, h, feat, eps, 0, raw=hip.plan_apply_raw)
+    unsplit, m1 = _apply(cuda, x, y, h, feat, eps, hip.FLAG_NO_SPLIT, raw=hip.plan_apply_raw)
+    nows, m2 = _apply(cuda, x, y, h, feat, eps, 0, workspace=False, raw=hip.plan_apply_raw)
     errs = [_worst(o, ref, feat) for o in (split, unsplit, nows)]
     agree = max(_worst(split, unsplit, feat), _worst(split, nows, feat))
     print(f"splits N={N} M={M} D={D} V={V}: vs reference {errs}, split vs unsplit {agree:.2e}")
@@ -137,7 +92,7 @@ def test_feature_range(cuda):
     feat[:, 4] = 2.5
     feat[:, 5] = np.abs(feat[:, 5])
     ref = _ref(x, y, h, 0.01, feat)
-    out, _ = _apply(cuda, x, y, h, feat, 0.01)
+    out, _ = _apply(cuda, x, y, h, feat, 0.01, raw=hip.plan_apply_raw)
     per_col = np.abs(out - ref).max(0) / np.where(np.abs(feat).max(0) > 0, np.abs(feat).max(0), 1.0)
     print(f"feature range: per column {per_col}, constant column {np.abs(out[:, 4] / 2.5 - 1).max():.2e}")
     assert (per_col <= 2e-5).all()
@@ -186,7 +141,7 @@ def test_special_values(cuda, flags):
     h[0, ::3] = -np.inf                      # a third of the columns carry no mass ...
     feat[0, ::3] = 1e4                       # ... whatever (finite) features they hold
     h[1, :] = -np.inf                        # a batch item without any mass
-    out, mass = _apply(cuda, x, y, h, feat, 0.01, flags)
+    out, mass = _apply(cuda, x, y, h, feat, 0.01, flags, raw=hip.plan_apply_raw)
     assert np.isfinite(out).all() and np.isfinite(mass).all()
     err = _worst(out[0], _ref(x[0], y[0], h[0], 0.01, np.where(np.isfinite(h[0])[:, None], feat[0], 0.0)), feat[0, 1::3])
     print(f"special values: masked columns {err:.2e}")
@@ -199,7 +154,7 @@ def test_offset_clouds(cuda):
     x, y, h = _clouds(8, N, M, D, offset=1000.0)
     feat = np.random.default_rng(7).standard_normal((M, V)).astype(np.float32)
     eps = 0.05**2
-    out, mass = _apply(cuda, x, y, h, feat, eps)
+    out, mass = _apply(cuda, x, y, h, feat, eps, raw=hip.plan_apply_raw)
     err = _worst(out, _ref(x, y, h, eps, feat), feat)
     print(f"offset clouds: {err:.2e}")
     assert err <= 1e-4

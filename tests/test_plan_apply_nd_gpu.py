@@ -1,66 +1,22 @@
 """``hip.plan_apply_nd`` / ``glhip_plan_apply_nd`` for clouds of 17 <= D <= 4095 (geomloss_amd/csrc/glhip_plan_apply_xk.h): the plan of a
 p = 2 soft-min applied to a feature matrix on the matrix cores, against a float64 NumPy reference W = exp(E - lse(E)), ref = W @ feat.
 
-The float64 reference, ``_clouds``, ``_eps`` and the ``_worst`` measure restate tests/test_plan_apply_gpu.py.  Acceptance bound, per
-feature column: |out - ref|[:, v] <= 2e-5 max_j |feat[j, v]| and |mass - 1| <= 1e-4, the project's bars for these plan weights at
+The float64 reference ``_ref``, ``_clouds`` and the ``_worst`` measure are those of tests/test_plan_apply_gpu.py (tests/cloud_support.py);
+``_eps`` restates it for D >= 17.  Acceptance bound, per feature column: |out - ref|[:, v] <= 2e-5 max_j |feat[j, v]| and
+|mass - 1| <= 1e-4, the project's bars for these plan weights at
 eps = 0.1 D / 3 (diam^2 / eps <= 30: the f16 range contract holds); 1e-4 for the many-column launch at eps = 0.05^2 D."""
 import numpy as np
 import pytest
 import torch
 
+from cloud_support import clouds as _clouds, plan_apply as _apply, plan_ref as _ref, plan_worst as _worst, to_dev as _t
 from geomloss_amd import hip
 
 pytestmark = pytest.mark.gpu
 
 
-def _clouds(seed, N, M, D, B=None, offset=0.0):
-    rng = np.random.default_rng(seed)
-    shp = (lambda n: (n, D)) if B is None else (lambda n: (B, n, D))
-    x = rng.random(shp(N)).astype(np.float32) + offset
-    y = (rng.random(shp(M)) * 0.8 + 0.1).astype(np.float32) + offset
-    h = rng.standard_normal(shp(M)[:-1]).astype(np.float32)
-    return x, y, h
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
 def _eps(D):
     return 0.1 * D / 3
-
-
-def _ref(x, y, h, eps, feat, rows=64):
-    """float64: W @ feat with rows of W summing to 1 (0 for a row without mass), row-chunked so that M = 70 001 stays small."""
-    x, y, h, feat = (np.asarray(t, dtype=np.float64) for t in (x, y, h, feat))
-    out = np.zeros((x.shape[0], feat.shape[1]))
-    for i0 in range(0, x.shape[0], rows):
-        xi = x[i0:i0 + rows]
-        E = h[None, :] - ((xi * xi).sum(1)[:, None] - 2.0 * xi @ y.T + (y * y).sum(1)[None, :]) / (2.0 * eps)
-        m = E.max(1, keepdims=True)
-        m = np.where(np.isfinite(m), m, 0.0)
-        W = np.exp(E - m)
-        s = W.sum(1, keepdims=True)
-        out[i0:i0 + rows] = (W / np.where(s > 0, s, 1.0)) @ np.where(np.isfinite(feat), feat, 0.0)
-    return out
-
-
-def _apply(dev, x, y, h, feat, eps, flags=0, raw=None, **kw):
-    """Raw launch on (N,D) / (B,N,D) NumPy inputs -> out, mass as NumPy."""
-    xb, yb, hb, fb = (_t(a, dev) for a in (x, y, h, feat))
-    if xb.dim() == 2:
-        xb, yb, hb, fb = xb[None], yb[None], hb[None], fb[None]
-    fwd = hip.softmin_fwd_raw(xb, yb, hb, eps, 2, None, flags)
-    out, mass = (raw or hip.plan_apply_nd_raw)(xb, yb, hb, fwd, fb, eps, flags, want_mass=True, **kw)
-    out, mass = out.cpu().numpy(), mass.cpu().numpy()
-    return (out[0], mass[0]) if np.ndim(x) == 2 else (out, mass)
-
-
-def _worst(out, ref, feat):
-    """max over columns of max_i |out - ref| / max_j |feat_j|."""
-    scale = np.abs(feat).reshape(-1, feat.shape[-1]).max(0) if feat.ndim == 2 else np.abs(feat).max(-2, keepdims=True)
-    scale = np.where(scale > 0, scale, 1.0)
-    return float((np.abs(out - ref) / scale).max())
 
 
 def _torch_f32_error(dev, x, y, h, eps, feat, ref):
@@ -94,7 +50,7 @@ def _parity_case(N, M, D, V):      # inputs and the float64 reference, computed 
 def test_parity(cuda, N, M, D, V, flags):
     """Measured worst case per dimension on an MI355X: see DESIGN §4."""
     x, y, h, feat, ref = _parity_case(N, M, D, V)
-    out, mass = _apply(cuda, x, y, h, feat, _eps(D), flags)
+    out, mass = _apply(cuda, x, y, h, feat, _eps(D), flags, raw=hip.plan_apply_nd_raw)
     err = _worst(out, ref, feat)
     print(f"parity N={N} M={M} D={D} V={V} flags={flags}: {err:.2e}, |mass - 1| {np.abs(mass - 1).max():.2e}")
     assert out.shape == (N, V) and np.isfinite(out).all()
@@ -145,7 +101,7 @@ def test_massless_rows_and_columns(cuda, flags):
     h[0, ::3] = -np.inf                      # a third of the columns carry no mass ...
     feat[0, ::3] = 1e4                       # ... whatever (finite) features they hold
     h[1, :] = -np.inf                        # a batch item without any mass
-    out, mass = _apply(cuda, x, y, h, feat, _eps(D), flags)
+    out, mass = _apply(cuda, x, y, h, feat, _eps(D), flags, raw=hip.plan_apply_nd_raw)
     assert np.isfinite(out).all() and np.isfinite(mass).all()
     err = _worst(out[0], _ref(x[0], y[0], h[0], _eps(D), np.where(np.isfinite(h[0])[:, None], feat[0], 0.0)), feat[0, 1::3])
     print(f"massless columns, flags={flags}: {err:.2e}")
@@ -159,9 +115,9 @@ def test_column_splits(cuda):
     feat = np.random.default_rng(V).standard_normal((M, V)).astype(np.float32)
     eps = 0.05**2 * D
     ref = _ref(x, y, h, eps, feat)
-    split, m0 = _apply(cuda, x, y, h, feat, eps, 0)
-    unsplit, m1 = _apply(cuda, x, y, h, feat, eps, hip.FLAG_NO_SPLIT)
-    nows, m2 = _apply(cuda, x, y, h, feat, eps, 0, workspace=False)
+    split, m0 = _apply(cuda, x, y, h, feat, eps, 0, raw=hip.plan_apply_nd_raw)
+    unsplit, m1 = _apply(cuda, x, y, h, feat, eps, hip.FLAG_NO_SPLIT, raw=hip.plan_apply_nd_raw)
+    nows, m2 = _apply(cuda, x, y, h, feat, eps, 0, workspace=False, raw=hip.plan_apply_nd_raw)
     errs = [_worst(o, ref, feat) for o in (split, unsplit, nows)]
     print(f"splits N={N} M={M} D={D} V={V}: vs reference {errs}, split vs unsplit {_worst(split, unsplit, feat):.2e}")
     assert max(errs) <= 1e-4
@@ -173,11 +129,11 @@ def test_continuity_with_the_resident_operand_kernel(cuda):
     x, y, h = _clouds(N + M + D, N, M, D)
     feat = np.random.default_rng(V).standard_normal((M, V)).astype(np.float32)
     eps = _eps(D)
-    nd, mnd = _apply(cuda, x, y, h, feat, eps)
+    nd, mnd = _apply(cuda, x, y, h, feat, eps, raw=hip.plan_apply_nd_raw)
     xd, mxd = _apply(cuda, x, y, h, feat, eps, raw=hip.plan_apply_raw)
     assert np.array_equal(nd, xd) and np.array_equal(mnd, mxd)      # the very same launch
     pad = lambda a: np.concatenate([a, np.zeros((a.shape[0], 1), np.float32)], 1)  # noqa: E731
-    xk, _ = _apply(cuda, pad(x), pad(y), h, feat, eps)
+    xk, _ = _apply(cuda, pad(x), pad(y), h, feat, eps, raw=hip.plan_apply_nd_raw)
     err = _worst(xk, xd, feat)
     print(f"continuity D=16 -> 17: {err:.2e}")
     assert err <= 4e-5

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from cloud_support import to_dev as _t
 from geomloss_amd import hip
 
 pytestmark = pytest.mark.gpu
@@ -30,10 +31,6 @@ def _law(rng, N, M, D):
 
 def _eps(D):
     return 0.05 * float(np.sqrt(D))
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
 def _ref(x, y, h, eps, feat):

@@ -8,29 +8,21 @@ that prune (N M >= 1e11, N >= 65536): 65536 x 1525900 (256 slabs, 5961 column bl
   smallest gaps closed, and t2 follows tools/prune_model.py: level2_mass on 24 slabs under that file's conditions (exact, or one bucket
   away in at most 1 % of the finite tiles); the same interval check on the wide shape, whose bit set has 94 words;
 * bf16 input and D = 1 once each through the pruned forward against the dense launch, within the bound of
-  tests/test_exact_prune_gpu.py (_close: 4e-7 diam^2 + 2e-6 of the output's magnitude).
+  prune_support.close (4e-7 diam^2 + 2e-6 of the output's magnitude).
 """
 
-import ctypes
 import math
-import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-from geomloss_amd import hip
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-import prune_model as pm  # noqa: E402
+import prune_support as ps
+from prune_support import RECORDS, pm
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda:0") if torch.cuda.is_available() else None
-RECORDS = ("perm_x", "perm_y", "mlb", "t1", "home", "intervals", "t2")
+DEV = ps.DEV
 
 
 def _input(name):
@@ -46,24 +38,6 @@ def _input(name):
     return x, y, h, eps
 
 
-def _inspect(x, y, h, eps):
-    """glhip_prune_inspect -> NumPy records"""
-    lib = hip.load_library()
-    _, n, D = x.shape
-    m = y.shape[1]
-    C, S, nt = (n + 255) // 256, int(lib.glhip_prune_inspect_slots(m)), (n + 31) // 32
-    i32, f64 = dict(dtype=torch.int32, device=DEV), dict(dtype=torch.float64, device=DEV)
-    r = dict(perm_x=torch.empty(n, **i32), perm_y=torch.empty(m, **i32), mlb=torch.empty(C, **f64), t1=torch.empty(C, **f64),
-             home=torch.empty(C, **i32), intervals=torch.empty((C, S, 2), **i32), t2=torch.empty(nt, dtype=torch.float32, device=DEV))
-    nbytes = int(lib.glhip_workspace_bytes(1, n, m, D, 0))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=DEV)
-    rc = lib.glhip_prune_inspect(x.data_ptr(), y.data_ptr(), h.data_ptr(), None, n, m, D, float(eps), hip._dtype_code(x),
-                                 *[r[k].data_ptr() for k in RECORDS], ctypes.c_void_p(ws.data_ptr()), nbytes, hip._stream(x))
-    assert rc == 0, lib.glhip_last_error()
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in r.items()}
-
-
 _CACHE = {}
 
 
@@ -72,7 +46,7 @@ def _case(name):
     if name not in _CACHE:
         x, y, h, eps = _input(name)
         dx, dy, dh = x[None].to(DEV).contiguous(), y[None].to(DEV).contiguous(), h[None].to(DEV).contiguous()
-        rec, again = _inspect(dx, dy, dh, eps), _inspect(dx, dy, dh, eps)
+        rec, again = ps.inspect(dx, dy, dh, eps), ps.inspect(dx, dy, dh, eps)
         n, m = x.shape[0], y.shape[0]
         assert np.array_equal(np.sort(rec["perm_x"]), np.arange(n)) and np.array_equal(np.sort(rec["perm_y"]), np.arange(m))
         xs, ys, hs = x.numpy()[rec["perm_x"]], y.numpy()[rec["perm_y"]], h.numpy()[rec["perm_y"]]
@@ -86,14 +60,6 @@ def test_records_repeat(name):
     for k in RECORDS:
         assert np.array_equal(rec[k], again[k], equal_nan=k in ("mlb", "t1", "t2")), k
     assert (rec["home"] >= 0).any() and np.isfinite(rec["t2"]).any()      # the input prunes: both levels ran
-
-
-def _covered(rec, c, nT):
-    k = np.zeros(nT, bool)
-    for a, b in rec["intervals"][c]:
-        if b > a:
-            k[a // pm.BLOCK:(b + pm.BLOCK - 1) // pm.BLOCK] = True
-    return k
 
 
 def _closed(keep_row):
@@ -138,7 +104,7 @@ def test_closed_gaps_on_every_slab_over_the_limit(name):
         assert ((iv[:n, 1] % pm.BLOCK == 0) | (iv[:n, 1] == M)).all(), c
         assert n <= S and (np.diff(iv[:n, 0]) > 0).all(), c
         want = _closed(keep[c])
-        assert np.array_equal(_covered(rec, c, nT), want), c
+        assert np.array_equal(ps.covered(rec, c, nT), want), c
         assert pm.runs_per_slab(want[None])[0] <= pm.RUNS, c
         pieces.append(n)
     print(f"{name}: pieces per checked slab {min(pieces)} to {max(pieces)} of {S} slots")
@@ -172,38 +138,9 @@ def test_second_level_with_closed_gaps():
 
 # ---- the pruned forward against the dense launch ----------------------------------------------------------------------------------------
 
-def _fwd(x, y, h, eps, flags):
-    lib = hip.load_library()
-    B, N, D = x.shape
-    M = y.shape[1]
-    nbytes = int(lib.glhip_workspace_bytes(B, N, M, D, 0))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=DEV)
-    out = torch.empty((B, N), dtype=torch.float32, device=DEV)
-    rc = lib.glhip_softmin_fwd(x.data_ptr(), y.data_ptr(), h.data_ptr(), out.data_ptr(), B, N, M, D, float(eps), 2, hip._dtype_code(x),
-                               None, None, None, 0, ctypes.c_void_p(ws.data_ptr()), nbytes, int(flags), hip._stream(x))
-    assert rc == 0, lib.glhip_last_error()
-    return out
-
-
-def _close(a, b, diam2):
-    """tests/test_exact_prune_gpu.py: the dense launch's own rounding, 4e-7 diam^2 + 2e-6 of the output's magnitude; same NaN / infinity pattern"""
-    assert torch.equal(a.isnan(), b.isnan()) and torch.equal(a.isinf(), b.isinf())
-    ok = ~b.isnan() & ~b.isinf()
-    assert bool(ok.any())
-    err = float((a[ok].double() - b[ok].double()).abs().max())
-    bound = 4e-7 * diam2 + 2e-6 * float(b[ok].double().abs().max())
-    assert err <= bound, (err, bound)
-    return err, bound
-
-
 @pytest.mark.parametrize("D,dtype", [(3, torch.bfloat16), (1, torch.float32)], ids=["bf16", "d1"])
 def test_pruned_forward_matches_dense(D, dtype):
     n, m, eps = 320000, 320037, 0.05**2
-    g = torch.Generator().manual_seed(80 + D)
-    x = torch.rand(1, n, D, generator=g).to(DEV, dtype).contiguous()
-    y = torch.rand(1, m, D, generator=g).to(DEV, dtype).contiguous()
-    h = (torch.full((1, m), -math.log(m)) + 0.01 * torch.randn(1, m, generator=g) / 0.05**2).to(DEV).contiguous()
-    z = torch.cat([x[0].float(), y[0].float()])
-    diam2 = float(((z.max(0).values - z.min(0).values) ** 2).sum())
-    err, bound = _close(_fwd(x, y, h, eps, hip.FLAG_F16X2), _fwd(x, y, h, eps, hip.FLAG_F16X2 | hip.FLAG_NO_SORT), diam2)
+    x, y, h = ps.law(n, m, 80 + D, D=D, dtype=dtype)
+    err, bound = ps.close(ps.fwd(x, y, h, eps, ps.F16X2), ps.fwd(x, y, h, eps, ps.F16X2 | ps.NO_SORT), ps.diam2(x, y), require_finite=True)
     print(f"D = {D} {dtype}: pruned against dense, largest difference {err:.3e} (bound {bound:.3e})")

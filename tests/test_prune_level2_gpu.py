@@ -4,8 +4,8 @@ Inside the column intervals the first level keeps, every wavefront skips the gro
 What tests/test_exact_prune_gpu.py cannot see: laws where the second level removes far more than the first, dual values with rare
 columns far above the rest, special values inside groups that would otherwise be skipped and inside home blocks, the half-step, shapes
 that are no multiples of 32, D < 3, stream capture.  Every case runs the same call with GLHIP_FLAG_NO_SORT (the dense launch) next to
-it and is held to that file's rule: |pruned - dense| <= 4e-7 diam^2 + 2e-6 max|out| with the same NaN / infinity pattern, and on 256
-sampled rows an error against float64 of at most 1.5 x the dense launch's + 2 ulp.
+it and is held to prune_support.close: |pruned - dense| <= 4e-7 diam^2 + 2e-6 max|out| with the same NaN / infinity pattern, and on 256
+sampled rows (prune_support.check_rows) an error against float64 of at most 1.5 x the dense launch's + 2 ulp.
 """
 
 import ctypes
@@ -16,118 +16,47 @@ import torch
 
 from geomloss_amd import hip
 
+import prune_support as ps
+
 pytestmark = pytest.mark.gpu
 
-F16X2, NO_SORT = hip.FLAG_F16X2, hip.FLAG_NO_SORT
-DEV = torch.device("cuda:0") if torch.cuda.is_available() else None
-LAYOUTS = pytest.mark.parametrize("flags", [F16X2, 0], ids=["f16x2", "bf16x3"])
-
-
-def _law(n, m, seed, D=3, dtype=torch.float32, noise=0.01):
-    """the headline law (bench.make_problem) in D dimensions: uniform unit cube, h = -log M + N(0, noise^2) / 0.05^2"""
-    g = torch.Generator().manual_seed(seed)
-    x = torch.rand(1, n, D, generator=g)
-    y = torch.rand(1, m, D, generator=g)
-    h = torch.full((1, m), -math.log(m)) + noise * torch.randn(1, m, generator=g) / (0.05**2)
-    return x.to(DEV, dtype).contiguous(), y.to(DEV, dtype).contiguous(), h.to(DEV).contiguous()
-
-
-def _fwd(x, y, h, eps, flags):
-    lib = hip.load_library()
-    B, N, D = x.shape
-    M = y.shape[1]
-    nbytes = int(lib.glhip_workspace_bytes(B, N, M, D, 0))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=DEV)
-    out = torch.empty((B, N), dtype=torch.float32, device=DEV)
-    rc = lib.glhip_softmin_fwd(x.data_ptr(), y.data_ptr(), h.data_ptr(), out.data_ptr(), B, N, M, D, float(eps), 2, hip._dtype_code(x),
-                               None, None, None, 0, ctypes.c_void_p(ws.data_ptr()), nbytes, int(flags), hip._stream(x))
-    assert rc == 0, lib.glhip_last_error()
-    return out
-
-
-def _diam2(x, y):
-    z = torch.cat([x[0].float(), y[0].float()])
-    z = z[torch.isfinite(z).all(1)]
-    return float(((z.max(0).values - z.min(0).values) ** 2).sum())
-
-
-def _close(a, b, diam2):
-    """tests/test_exact_prune_gpu.py: the dense launch's own rounding, same NaN / infinity pattern"""
-    assert torch.equal(a.isnan(), b.isnan())
-    fin = ~b.isnan()
-    if not bool(fin.any()):
-        return
-    assert torch.equal(a[fin].isinf(), b[fin].isinf()) and torch.equal(a[fin & a.isinf()], b[fin & b.isinf()])
-    ok = fin & ~b.isinf()
-    if bool(ok.any()):
-        av, bv = a[ok].double(), b[ok].double()
-        err = float((av - bv).abs().max())
-        print(f"max|pruned - dense| {err:.3e} (bound {4e-7 * diam2 + 2e-6 * float(bv.abs().max()):.3e})")
-        assert err <= 4e-7 * diam2 + 2e-6 * float(bv.abs().max()), (err, diam2)
-
-
-def _oracle_rows(x, y, hcol, eps, rows):
-    """float64 soft-min of a sample of rows; hcol: the column vector as the kernels form it"""
-    xi = x[0, rows].double()
-    e = hcol[0].double()[None] - torch.cdist(xi, y[0].double()).pow(2) / (2 * eps)
-    return -eps * torch.logsumexp(e, 1)
-
-
-def _check_rows(pruned, dense, ref, rows):
-    """on the sampled rows where float64 and the dense launch are finite: the pruned result is as close to float64 as the dense one
-    (+ 2 float32 ulp of the output); elsewhere _close has already compared the two launches' patterns"""
-    ok = torch.isfinite(ref) & torch.isfinite(dense[0, rows])
-    if not bool(ok.any()):
-        return
-    ep = float((pruned[0, rows].double() - ref)[ok].abs().max())
-    ed = float((dense[0, rows].double() - ref)[ok].abs().max())
-    print(f"error against float64: pruned {ep:.3e} dense {ed:.3e}")
-    assert ep <= 1.5 * ed + 2 * float(ref[ok].abs().max()) * 2**-24, (ep, ed)
-
-
-def _compare(x, y, h, eps, flags):
-    a = _fwd(x, y, h, eps, flags)
-    b = _fwd(x, y, h, eps, flags | NO_SORT)
-    _close(a, b, _diam2(x, y))
-    rows = torch.linspace(0, x.shape[1] - 1, 256, device=DEV).long()
-    _check_rows(a, b, _oracle_rows(x.float(), y.float(), h, eps, rows), rows)
-    return a
+DEV, NO_SORT, LAYOUTS = ps.DEV, ps.NO_SORT, ps.LAYOUTS
 
 
 # (a) laws where the second level removes much more than the first
 @LAYOUTS
 def test_small_eps_flat_duals(flags):
     # the law of test_most_pruned_at_small_eps: eps = 0.015^2, diameter^2 / eps = 1.3e4 (inside the f16 x 2 contract)
-    x, y, h = _law(320000, 320000, 6)
-    _compare(x, y, torch.zeros_like(h), 0.015**2, flags)
+    x, y, h = ps.law(320000, 320000, 6)
+    ps.compare(x, y, torch.zeros_like(h), 0.015**2, flags)
 
 
 def test_headline_law_at_tiny_eps_bf16x3():
     # eps = 0.01^2: diameter^2 / eps = 3e4 with dual values of +-400 nats — outside the f16 x 2 contract (profiles/r07_prune_curve.txt)
-    x, y, h = _law(320000, 320000, 12)
-    _compare(x, y, h, 0.01**2, 0)
+    x, y, h = ps.law(320000, 320000, 12)
+    ps.compare(x, y, h, 0.01**2, 0)
 
 
 @LAYOUTS
 def test_bf16_input(flags):
-    x, y, h = _law(300000, 340000, 13, dtype=torch.bfloat16)
-    _compare(x, y, torch.zeros_like(h), 0.02**2, flags)
+    x, y, h = ps.law(300000, 340000, 13, dtype=torch.bfloat16)
+    ps.compare(x, y, torch.zeros_like(h), 0.02**2, flags)
 
 
 # (b) a few columns far above the rest: whole groups stay for one member, and the home-block seed is not the row's maximum
 @LAYOUTS
 def test_rare_high_duals(flags):
-    x, y, h = _law(320000, 320000, 14, noise=0.001)
+    x, y, h = ps.law(320000, 320000, 14, noise=0.001)
     h = h.clone()
     h[0, ::10000] += 40.0
-    _compare(x, y, h, 0.02**2, flags)
+    ps.compare(x, y, h, 0.02**2, flags)
 
 
 # (c) special values inside groups that would otherwise be skipped, and (every ~5000th column: dozens of blocks) inside home blocks
 @LAYOUTS
 @pytest.mark.parametrize("what", ["y_nan", "y_pinf", "y_minf", "h_nan", "h_pinf", "h_minf", "x_nan", "x_inf"])
 def test_special_values(flags, what):
-    x, y, h = _law(300000, 340000, 15)
+    x, y, h = ps.law(300000, 340000, 15)
     h = torch.zeros_like(h)
     x, y, h = x.clone(), y.clone(), h.clone()
     if what == "y_nan":
@@ -147,13 +76,13 @@ def test_special_values(flags, what):
         x[0, 555::7001, 1] = math.nan
     else:
         x[0, 555::7001, 0] = math.inf
-    _compare(x, y, h, 0.02**2, flags)
+    ps.compare(x, y, h, 0.02**2, flags)
 
 
 # (d) the half-step, with pot and prev
 @LAYOUTS
 def test_half_step(flags):
-    x, y, h = _law(300000, 340000, 16, noise=0.002)
+    x, y, h = ps.law(300000, 340000, 16, noise=0.002)
     eps, damping = 0.02**2, 0.9
     g = torch.Generator().manual_seed(17)
     m, n = y.shape[1], x.shape[1]
@@ -164,36 +93,35 @@ def test_half_step(flags):
     for p_, v_ in ((pot, prev), (pot, None)):
         a = hip.sinkhorn_step_raw(x, y, logw, p_, v_, eps, damping, 2, None, flags)
         b = hip.sinkhorn_step_raw(x, y, logw, p_, v_, eps, damping, 2, None, flags | NO_SORT)
-        _close(a, b, _diam2(x, y))
-        f = _oracle_rows(x, y, logw.double() + p_.double() / eps, eps, rows)
+        ps.close(a, b, ps.diam2(x, y))
+        f = ps.oracle_rows(x, y, logw.double() + p_.double() / eps, eps, rows)
         ref = (0.5 * damping * f + 0.5 * v_[0, rows].double()) if v_ is not None else damping * f
-        _check_rows(a, b, ref, rows)
+        ps.check_rows(a, b, ref, rows)
 
 
 # (e) N and M no multiples of 32 (nor of the 256-row slab, the 256-column block)
 @LAYOUTS
 def test_uneven_shapes(flags):
-    x, y, h = _law(300017, 340003, 18)
-    _compare(x, y, torch.zeros_like(h), 0.02**2, flags)
+    x, y, h = ps.law(300017, 340003, 18)
+    ps.compare(x, y, torch.zeros_like(h), 0.02**2, flags)
 
 
 # D < 3: the group records carry empty boxes beyond D, the sort's minor key has 3^2 / 8 sub-voxels
 @LAYOUTS
 @pytest.mark.parametrize("D", [1, 2])
 def test_lower_dimensions(flags, D):
-    x, y, h = _law(320000, 320000, 19 + D, D=D, noise=0.001)
-    _compare(x, y, h, 0.03**2, flags)
+    x, y, h = ps.law(320000, 320000, 19 + D, D=D, noise=0.001)
+    ps.compare(x, y, h, 0.03**2, flags)
 
 
 # (f) stream capture and replay equal the eager call, bit for bit
 @LAYOUTS
 def test_stream_capture(flags):
-    x, y, h = _law(320000, 320000, 22)
+    x, y, h = ps.law(320000, 320000, 22)
     h = torch.zeros_like(h)
     eps = 0.02**2
     lib = hip.load_library()
-    nbytes = int(lib.glhip_workspace_bytes(1, 320000, 320000, 3, 0))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+    ws, nbytes = ps.workspace(lib, 320000, 320000, 3)
     out = torch.empty((1, 320000), dtype=torch.float32, device=DEV)
 
     def run():
@@ -216,4 +144,4 @@ def test_stream_capture(flags):
     graph.replay()
     torch.cuda.synchronize()
     assert torch.equal(out, eager)
-    _close(out, _fwd(x, y, h, eps, flags | NO_SORT), _diam2(x, y))
+    ps.close(out, ps.fwd(x, y, h, eps, flags | NO_SORT), ps.diam2(x, y))

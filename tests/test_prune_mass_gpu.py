@@ -4,8 +4,8 @@ prune_tiles_kernel in csrc/glhip_prune.hip): both levels drop by the SUM of what
 What is dropped stays below one ulp of the output by design, so the outputs cannot tell a correct budget from a generous one.  These
 tests read the thresholds themselves through glhip_prune_inspect: against the NumPy model (tools/prune_model.py) fed with the device's
 own permutations; on an input built against a mass rule (many equal small terms), where the float64 sum of everything the device may
-drop is held to 2^-26 of each row's true sum; through the half-step; and on slabs without a second level.  Launches are held to the
-rule of tests/test_exact_prune_gpu.py against the same call under GLHIP_FLAG_NO_SORT.
+drop is held to 2^-26 of each row's true sum; through the half-step; and on slabs without a second level.  Launches are held to
+prune_support.close against the same call under GLHIP_FLAG_NO_SORT.
 
 A tile with a home block but no finite seed cannot be built from outside: a home block attains a finite Mlb, so it holds a finite dual
 value and finite points, and a slab with a non-finite row has no home block; the kernel's guard for it (t2 = -inf) is not reachable
@@ -15,8 +15,6 @@ tiles): see test_thresholds_match_the_model's docstring.
 
 import ctypes
 import math
-import os
-import sys
 
 import numpy as np
 import pytest
@@ -24,94 +22,18 @@ import torch
 
 from geomloss_amd import hip
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-import prune_model as pm  # noqa: E402
+import prune_support as ps
+from prune_support import pm
 
 pytestmark = pytest.mark.gpu
 
-F16X2, NO_SORT = hip.FLAG_F16X2, hip.FLAG_NO_SORT
-DEV = torch.device("cuda:0") if torch.cuda.is_available() else None
-LAYOUTS = pytest.mark.parametrize("flags", [F16X2, 0], ids=["f16x2", "bf16x3"])
+DEV, F16X2, NO_SORT, LAYOUTS = ps.DEV, ps.F16X2, ps.NO_SORT, ps.LAYOUTS
 N = 320000          # the smallest square shape the p = 2 call prunes (N M >= 1e11)
 BUDGET = 2.0**-26
 
 
-def _law(n, m, seed, noise=0.01):
-    """the headline law (bench.make_problem): uniform unit cube, h = -log M + N(0, noise^2) / 0.05^2"""
-    g = torch.Generator().manual_seed(seed)
-    x = torch.rand(1, n, 3, generator=g)
-    y = torch.rand(1, m, 3, generator=g)
-    h = torch.full((1, m), -math.log(m)) + noise * torch.randn(1, m, generator=g) / (0.05**2)
-    return x.to(DEV).contiguous(), y.to(DEV).contiguous(), h.to(DEV).contiguous()
-
-
-def _workspace(lib, n, m, D):
-    nbytes = int(lib.glhip_workspace_bytes(1, n, m, D, 0))
-    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=DEV), nbytes
-
-
-def _fwd(x, y, h, eps, flags):
-    lib = hip.load_library()
-    B, n, D = x.shape
-    m = y.shape[1]
-    ws, nbytes = _workspace(lib, n, m, D)
-    out = torch.empty((B, n), dtype=torch.float32, device=DEV)
-    rc = lib.glhip_softmin_fwd(x.data_ptr(), y.data_ptr(), h.data_ptr(), out.data_ptr(), B, n, m, D, float(eps), 2, hip._dtype_code(x),
-                               None, None, None, 0, ctypes.c_void_p(ws.data_ptr()), nbytes, int(flags), hip._stream(x))
-    assert rc == 0, lib.glhip_last_error()
-    return out
-
-
-def _inspect(x, y, logw, pot, eps):
-    """glhip_prune_inspect -> NumPy records"""
-    lib = hip.load_library()
-    _, n, D = x.shape
-    m = y.shape[1]
-    C, S, nt = (n + 255) // 256, int(lib.glhip_prune_inspect_slots(m)), (n + 31) // 32
-    i32, f64 = dict(dtype=torch.int32, device=DEV), dict(dtype=torch.float64, device=DEV)
-    r = dict(perm_x=torch.empty(n, **i32), perm_y=torch.empty(m, **i32), mlb=torch.empty(C, **f64), t1=torch.empty(C, **f64),
-             home=torch.empty(C, **i32), intervals=torch.empty((C, S, 2), **i32), t2=torch.empty(nt, dtype=torch.float32, device=DEV))
-    ws, nbytes = _workspace(lib, n, m, D)
-    rc = lib.glhip_prune_inspect(x.data_ptr(), y.data_ptr(), logw.data_ptr(), None if pot is None else pot.data_ptr(), n, m, D, float(eps),
-                                 hip._dtype_code(x), *[r[k].data_ptr() for k in ("perm_x", "perm_y", "mlb", "t1", "home", "intervals", "t2")],
-                                 ctypes.c_void_p(ws.data_ptr()), nbytes, hip._stream(x))
-    assert rc == 0, lib.glhip_last_error()
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in r.items()}
-
-
-def _diam2(x, y):
-    z = torch.cat([x[0].float(), y[0].float()])
-    z = z[torch.isfinite(z).all(1)]
-    return float(((z.max(0).values - z.min(0).values) ** 2).sum())
-
-
-def _close(a, b, diam2):
-    """tests/test_exact_prune_gpu.py: the dense launch's own rounding, same NaN / infinity pattern"""
-    assert torch.equal(a.isnan(), b.isnan())
-    fin = ~b.isnan()
-    if not bool(fin.any()):
-        return
-    assert torch.equal(a[fin].isinf(), b[fin].isinf()) and torch.equal(a[fin & a.isinf()], b[fin & b.isinf()])
-    ok = fin & ~b.isinf()
-    if bool(ok.any()):
-        av, bv = a[ok].double(), b[ok].double()
-        err = float((av - bv).abs().max())
-        print(f"max|pruned - dense| {err:.3e} (bound {4e-7 * diam2 + 2e-6 * float(bv.abs().max()):.3e})")
-        assert err <= 4e-7 * diam2 + 2e-6 * float(bv.abs().max()), (err, diam2)
-
-
 def _device_intervals(rec, c):
     return [(int(a), int(b)) for a, b in rec["intervals"][c] if b > a]
-
-
-def _covered_blocks(iv, nT):
-    k = np.zeros(nT, bool)
-    for a, b in iv:
-        k[a // pm.BLOCK:(b + pm.BLOCK - 1) // pm.BLOCK] = True
-    return k
 
 
 def test_thresholds_match_the_model():
@@ -120,8 +42,8 @@ def test_thresholds_match_the_model():
     and capped at 1 % of the slabs / tiles.  (The model against itself with every group's lse moved up by one float32 ulp, this input,
     on the host and in the model's own order: 0 of 1250 slabs and 0 of 10000 tiles move.)"""
     eps = 0.05**2
-    x, y, h = _law(N, N, 21)
-    rec = _inspect(x, y, h, None, eps)
+    x, y, h = ps.law(N, N, 21)
+    rec = ps.inspect(x, y, h, eps)
     assert np.array_equal(np.sort(rec["perm_x"]), np.arange(N)) and np.array_equal(np.sort(rec["perm_y"]), np.arange(N))
     xs, ys, hs = x[0].cpu().numpy()[rec["perm_x"]], y[0].cpu().numpy()[rec["perm_y"]], h[0].cpu().numpy()[rec["perm_y"]]
     keep, mlb, t1, L = pm.plan_mass(xs, ys, hs, eps)
@@ -139,7 +61,7 @@ def test_thresholds_match_the_model():
     same = np.flatnonzero(q_dev == q_mod)
     assert (pm.runs_per_slab(keep) <= pm.RUNS).all()                 # no gap closing on this input: intervals = kept blocks
     for c in same[:: max(1, len(same) // 200)]:
-        assert np.array_equal(_covered_blocks(iv[c], nT), keep[c]), c
+        assert np.array_equal(ps.covered(rec, c, nT), keep[c]), c
     # second level: every tile of every slab, on the device's intervals
     has = rec["home"] >= 0
     assert np.array_equal(has[same], ~keep[same].all(1))             # a slab whose blocks all pass has no home block
@@ -186,7 +108,7 @@ def test_dropped_mass_on_many_equal_small_terms():
     tile's threshold max(t2, smallest true row maximum - L) — sums in float64 to less than 2^-26 of each row's true sum, while the band
     as a whole holds more than that."""
     x, y, h, eps, L = _shells(31)
-    rec = _inspect(x, y, h, None, eps)
+    rec = ps.inspect(x, y, h, eps)
     ys = y[0][torch.from_numpy(rec["perm_y"]).to(DEV).long()].double()
     xs = x[0][torch.from_numpy(rec["perm_x"]).to(DEV).long()].double()
     hs = h[0][torch.from_numpy(rec["perm_y"]).to(DEV).long()].double()
@@ -232,23 +154,23 @@ def test_dropped_mass_on_many_equal_small_terms():
 @LAYOUTS
 def test_many_equal_small_terms_launch(flags):
     x, y, h, eps, _ = _shells(31)
-    _close(_fwd(x, y, h, eps, flags), _fwd(x, y, h, eps, flags | NO_SORT), _diam2(x, y))
+    ps.close(ps.fwd(x, y, h, eps, flags), ps.fwd(x, y, h, eps, flags | NO_SORT), ps.diam2(x, y))
 
 
 def test_half_step_thresholds_equal_the_forward_call_on_the_formed_duals():
     eps = 0.03**2
-    x, y, logw = _law(N, N, 22, noise=0.001)
+    x, y, logw = ps.law(N, N, 22, noise=0.001)
     g = torch.Generator().manual_seed(5)
     pot = (0.002 * torch.randn(1, N, generator=g)).to(DEV)
     scale = np.float32(1.0) / np.float32(eps)
     hcol = (pot.double() * float(scale) + logw.double()).float()      # fma(pot, 1 / eps, logw): one rounding
-    a = _inspect(x, y, logw, pot, eps)
-    b = _inspect(x, y, hcol, None, eps)
+    a = ps.inspect(x, y, logw, eps, pot)
+    b = ps.inspect(x, y, hcol, eps)
     assert (a["home"] >= 0).any() and np.isfinite(a["t2"]).any()
     for k in a:
         assert np.array_equal(a[k], b[k]), k
     lib = hip.load_library()
-    ws, nbytes = _workspace(lib, N, N, 3)
+    ws, nbytes = ps.workspace(lib, N, N, 3)
     outs = []
     for fl in (F16X2, F16X2 | NO_SORT):
         out = torch.empty((1, N), dtype=torch.float32, device=DEV)
@@ -256,7 +178,7 @@ def test_half_step_thresholds_equal_the_forward_call_on_the_formed_duals():
                                      1.0, 2, hip._dtype_code(x), None, None, None, 0, ctypes.c_void_p(ws.data_ptr()), nbytes, fl, hip._stream(x))
         assert rc == 0, lib.glhip_last_error()
         outs.append(out)
-    _close(outs[0], outs[1], _diam2(x, y))
+    ps.close(outs[0], outs[1], ps.diam2(x, y))
 
 
 @LAYOUTS
@@ -265,35 +187,32 @@ def test_slabs_without_a_second_level(flags):
     degenerate: no slab is compact, every block passes); a law whose first level keeps every block — leaves the tile thresholds
     untouched (the inspect entry presets them to -inf), and the launch gives the dense launch's pattern."""
     eps = 0.05**2
-    x, y, h = _law(N, N, 23)
+    x, y, h = ps.law(N, N, 23)
     x = x.clone()
     x[0, 1000, 1] = math.nan
     x[0, 200000, 0] = math.nan
-    rec = _inspect(x, y, h, None, eps)
+    rec = ps.inspect(x, y, h, eps)
     pos = np.empty(N, np.int64)
     pos[rec["perm_x"]] = np.arange(N)
     bad = np.unique(pos[[1000, 200000]] // 256)
     assert (rec["home"][bad] == -1).all() and np.isinf(rec["t1"][bad]).all() and (rec["home"] >= 0).sum() > 1000
     t2 = rec["t2"].reshape(-1, 8)
     assert np.array_equal(np.isneginf(t2).all(1), rec["home"] < 0) and np.isfinite(t2[rec["home"] >= 0]).all()
-    _close(_fwd(x, y, h, eps, flags), _fwd(x, y, h, eps, flags | NO_SORT), _diam2(x, y))
+    ps.close(ps.fwd(x, y, h, eps, flags), ps.fwd(x, y, h, eps, flags | NO_SORT), ps.diam2(x, y))
     # an infinite row: no slab has a home block, the slab that holds it has no bound at all
     x[0, 1000, 1] = math.inf
-    rec = _inspect(x, y, h, None, eps)
+    rec = ps.inspect(x, y, h, eps)
     pos[rec["perm_x"]] = np.arange(N)
     assert (rec["home"] == -1).all() and np.isneginf(rec["t2"]).all() and np.isneginf(rec["t1"][pos[1000] // 256])
-    _close(_fwd(x, y, h, eps, flags), _fwd(x, y, h, eps, flags | NO_SORT), _diam2(x, y))
+    ps.close(ps.fwd(x, y, h, eps, flags), ps.fwd(x, y, h, eps, flags | NO_SORT), ps.diam2(x, y))
     # eps = 1: every block passes, no slab has a home block
-    x, y, h = _law(N, N, 24)
-    rec = _inspect(x, y, h, None, 1.0)
+    x, y, h = ps.law(N, N, 24)
+    rec = ps.inspect(x, y, h, 1.0)
     assert (rec["home"] == -1).all() and np.isneginf(rec["t2"]).all()
-    _close(_fwd(x, y, h, 1.0, flags), _fwd(x, y, h, 1.0, flags | NO_SORT), _diam2(x, y))
+    ps.close(ps.fwd(x, y, h, 1.0, flags), ps.fwd(x, y, h, 1.0, flags | NO_SORT), ps.diam2(x, y))
 
 
 def test_inspect_rejects_shapes_that_are_not_pruned():
-    lib = hip.load_library()
-    x, y, h = _law(70000, 70000, 25)
-    ws, nbytes = _workspace(lib, 70000, 70000, 3)
-    rc = lib.glhip_prune_inspect(x.data_ptr(), y.data_ptr(), h.data_ptr(), None, 70000, 70000, 3, 0.0025, hip._dtype_code(x),
-                                 None, None, None, None, None, None, None, ctypes.c_void_p(ws.data_ptr()), nbytes, hip._stream(x))
+    x, y, h = ps.law(70000, 70000, 25)
+    rc, _ = ps.inspect_call(x, y, h, 0.0025, records=())
     assert rc == -2

@@ -14,25 +14,18 @@ slabs over the run limit (the first three: none).  On the large-exponent input t
 is held to 2^-26 of each row's sum on 64 tiles, as tests/test_prune_mass_gpu.py does on its shells.
 """
 
-import ctypes
 import math
-import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-from geomloss_amd import hip
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-import prune_model as pm  # noqa: E402
+import prune_support as ps
+from prune_support import pm
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda:0") if torch.cuda.is_available() else None
+DEV = ps.DEV
 BUDGET = 2.0**-26
 
 
@@ -57,25 +50,6 @@ def _input(name):
     return x, y, h, eps
 
 
-def _inspect(x, y, h, eps):
-    """glhip_prune_inspect -> NumPy records"""
-    lib = hip.load_library()
-    _, n, D = x.shape
-    m = y.shape[1]
-    C, S, nt = (n + 255) // 256, int(lib.glhip_prune_inspect_slots(m)), (n + 31) // 32
-    i32, f64 = dict(dtype=torch.int32, device=DEV), dict(dtype=torch.float64, device=DEV)
-    r = dict(perm_x=torch.empty(n, **i32), perm_y=torch.empty(m, **i32), mlb=torch.empty(C, **f64), t1=torch.empty(C, **f64),
-             home=torch.empty(C, **i32), intervals=torch.empty((C, S, 2), **i32), t2=torch.empty(nt, dtype=torch.float32, device=DEV))
-    nbytes = int(lib.glhip_workspace_bytes(1, n, m, D, 0))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=DEV)
-    rc = lib.glhip_prune_inspect(x.data_ptr(), y.data_ptr(), h.data_ptr(), None, n, m, D, float(eps), hip._dtype_code(x),
-                                 *[r[k].data_ptr() for k in ("perm_x", "perm_y", "mlb", "t1", "home", "intervals", "t2")],
-                                 ctypes.c_void_p(ws.data_ptr()), nbytes, hip._stream(x))
-    assert rc == 0, lib.glhip_last_error()
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in r.items()}
-
-
 _CACHE = {}
 
 
@@ -83,20 +57,12 @@ def _case(name):
     """device records and the model's first level on the device's order, once per input"""
     if name not in _CACHE:
         x, y, h, eps = _input(name)
-        rec = _inspect(x[None].to(DEV).contiguous(), y[None].to(DEV).contiguous(), h[None].to(DEV).contiguous(), eps)
+        rec = ps.inspect(x[None].to(DEV).contiguous(), y[None].to(DEV).contiguous(), h[None].to(DEV).contiguous(), eps)
         n, m = x.shape[0], y.shape[0]
         assert np.array_equal(np.sort(rec["perm_x"]), np.arange(n)) and np.array_equal(np.sort(rec["perm_y"]), np.arange(m))
         xs, ys, hs = x.numpy()[rec["perm_x"]], y.numpy()[rec["perm_y"]], h.numpy()[rec["perm_y"]]
         _CACHE[name] = (rec, xs, ys, hs, eps, pm.plan_mass(xs, ys, hs, eps))
     return _CACHE[name]
-
-
-def _covered(rec, c, nT):
-    k = np.zeros(nT, bool)
-    for a, b in rec["intervals"][c]:
-        if b > a:
-            k[a // pm.BLOCK:(b + pm.BLOCK - 1) // pm.BLOCK] = True
-    return k
 
 
 def _closed(keep_row):
@@ -148,7 +114,7 @@ def test_first_level_matches_the_model(name):
         assert (iv[:n, 0] % pm.BLOCK == 0).all() and (np.diff(iv[:n].ravel()) >= 0).all(), c
         assert ((iv[:n, 1] % pm.BLOCK == 0) | (iv[:n, 1] == M)).all(), c
         assert n <= S and (np.diff(iv[:n, 0]) > 0).all(), c
-        assert np.array_equal(_covered(rec, c, nT), _closed(keep[c])), c
+        assert np.array_equal(ps.covered(rec, c, nT), _closed(keep[c])), c
 
 
 @pytest.mark.parametrize("name", ["d2_uneven", "large_exponents", "equal_duals"])

@@ -4,14 +4,15 @@ inputs.  Errors are ``relerr``: relative to the largest entry of the reference.
 
 Bound: the project's rule for this gradient (tests/test_anyd_kernels_gpu.py) — 5e-6, and for D > 64 max(5e-6, 4 e_ref) with e_ref the
 error of the same gradient in plain float32 torch on the expanded cost |x|^2 - 2 x.y + |y|^2 with a softmax (the arithmetic of
-``_torch_f32_error`` in tests/test_plan_apply_nd_gpu.py), computed here.  ``_clouds`` and ``_eps`` restate tests/test_plan_apply_nd_gpu.py,
-``_clouds_anyd`` restates tests/test_anyd_kernels_gpu.py.  Every figure is printed before it is asserted."""
+``_torch_f32_error`` in tests/test_plan_apply_nd_gpu.py), computed here.  ``_clouds`` is cloud_support.clouds, ``_eps`` restates
+tests/test_plan_apply_nd_gpu.py.  Every figure is printed before it is asserted."""
 import math
 
 import numpy as np
 import pytest
 import torch
 
+from cloud_support import clouds as _clouds, to_dev as _t
 from conftest import relerr
 from geomloss_amd import SamplesLoss, hip
 from geomloss_amd import sinkhorn_samples
@@ -22,28 +23,6 @@ pytestmark = pytest.mark.gpu
 
 XK = hip.FLAG_XK_GRAD
 FLAGS = [XK, XK | hip.FLAG_NO_SPLIT, XK | hip.FLAG_F16X2, XK | hip.FLAG_F16X2 | hip.FLAG_NO_SPLIT]
-
-
-def _clouds(seed, N, M, D, B=None, offset=0.0):
-    rng = np.random.default_rng(seed)
-    shp = (lambda n: (n, D)) if B is None else (lambda n: (B, n, D))
-    x = rng.random(shp(N)).astype(np.float32) + offset
-    y = (rng.random(shp(M)) * 0.8 + 0.1).astype(np.float32) + offset
-    h = rng.standard_normal(shp(M)[:-1]).astype(np.float32)
-    return x, y, h
-
-
-def _clouds_anyd(seed, N, M, D, B=None):
-    rng = np.random.default_rng(seed)
-    shp = (lambda n: (n, D)) if B is None else (lambda n: (B, n, D))
-    x = rng.random(shp(N)).astype(np.float32)
-    y = (rng.random(shp(M)) * 0.8 + 0.1).astype(np.float32)
-    h = rng.standard_normal(shp(M)[:-1]).astype(np.float32)
-    return x, y, h
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
 def _eps(D):
@@ -119,7 +98,7 @@ def test_open_measurement(cuda, D, B):
     2.8e-6, 7.9e-7 / 2.1e-6 / 5.5e-6, 2.2e-6 / 2.0e-6 / 1.1e-5, 6.4e-6 / 5.9e-6 / 3.6e-5.  At D = 300 the new route is above the flat 5e-6:
     the flag stays opt-in for raw calls."""
     N, M, eps = 270, 310, 0.3
-    x, y, h = _clouds_anyd(51 + D, N, M, D, B=B)
+    x, y, h = _clouds(51 + D, N, M, D, B=B)
     g = np.random.default_rng(6).standard_normal(x.shape[:-1]).astype(np.float32)
     ref = _ref(cuda, x, y, h, g, eps)
     e_new = relerr(_grad(cuda, x, y, h, g, eps, XK), ref)

@@ -17,27 +17,18 @@ Values: the pruned call against the dense launch (GLHIP_FLAG_NO_SORT) on all row
 pattern equals the dense launch's and the finite rows stay within the bound.
 """
 
-import ctypes
 import math
-import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-from geomloss_amd import hip
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-import prune_model as pm  # noqa: E402
+import prune_support as ps
+from prune_support import pm
 
 pytestmark = pytest.mark.gpu
 
-F16X2, NO_SORT = hip.FLAG_F16X2, hip.FLAG_NO_SORT
-DEV = torch.device("cuda:0") if torch.cuda.is_available() else None
-LAYOUTS = pytest.mark.parametrize("flags", [F16X2, 0], ids=["f16x2", "bf16x3"])
+DEV, NO_SORT, LAYOUTS = ps.DEV, ps.NO_SORT, ps.LAYOUTS
 EVEN, UNEVEN = (320000, 320000), (320037, 313000)
 
 # name: (shape, D, cloud dtype, law, eps, half-step)
@@ -71,53 +62,10 @@ def _input(name):
     return dev(x), dev(y), dev(logw), dev(pot), h[0].numpy(), eps
 
 
-def _workspace(lib, n, m, D):
-    nbytes = int(lib.glhip_workspace_bytes(1, n, m, D, 0))
-    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=DEV), nbytes
-
-
-def _fwd(x, y, h, eps, flags):
-    lib = hip.load_library()
-    B, n, D = x.shape
-    m = y.shape[1]
-    ws, nbytes = _workspace(lib, n, m, D)
-    out = torch.empty((B, n), dtype=torch.float32, device=DEV)
-    rc = lib.glhip_softmin_fwd(x.data_ptr(), y.data_ptr(), h.data_ptr(), out.data_ptr(), B, n, m, D, float(eps), 2, hip._dtype_code(x),
-                               None, None, None, 0, ctypes.c_void_p(ws.data_ptr()), nbytes, int(flags), hip._stream(x))
-    assert rc == 0, lib.glhip_last_error()
-    return out
-
-
-def _inspect(x, y, logw, pot, eps):
-    """glhip_prune_inspect -> NumPy records"""
-    lib = hip.load_library()
-    _, n, D = x.shape
-    m = y.shape[1]
-    C, S, nt = (n + 255) // 256, int(lib.glhip_prune_inspect_slots(m)), (n + 31) // 32
-    i32, f64 = dict(dtype=torch.int32, device=DEV), dict(dtype=torch.float64, device=DEV)
-    r = dict(perm_x=torch.empty(n, **i32), perm_y=torch.empty(m, **i32), mlb=torch.empty(C, **f64), t1=torch.empty(C, **f64),
-             home=torch.empty(C, **i32), intervals=torch.empty((C, S, 2), **i32), t2=torch.empty(nt, dtype=torch.float32, device=DEV))
-    ws, nbytes = _workspace(lib, n, m, D)
-    rc = lib.glhip_prune_inspect(x.data_ptr(), y.data_ptr(), logw.data_ptr(), None if pot is None else pot.data_ptr(), n, m, D, float(eps),
-                                 hip._dtype_code(x), *[r[k].data_ptr() for k in ("perm_x", "perm_y", "mlb", "t1", "home", "intervals", "t2")],
-                                 ctypes.c_void_p(ws.data_ptr()), nbytes, hip._stream(x))
-    assert rc == 0, lib.glhip_last_error()
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in r.items()}
-
-
-def _covered(rec, c, nT):
-    k = np.zeros(nT, bool)
-    for a, b in rec["intervals"][c]:
-        if b > a:
-            k[a // pm.BLOCK:(b + pm.BLOCK - 1) // pm.BLOCK] = True
-    return k
-
-
 @pytest.mark.parametrize("name", list(CASES))
 def test_thresholds_match_the_model(name):
     x, y, logw, pot, h, eps = _input(name)
-    rec = _inspect(x, y, logw, pot, eps)
+    rec = ps.inspect(x, y, logw, eps, pot)
     n, m = x.shape[1], y.shape[1]
     assert np.array_equal(np.sort(rec["perm_x"]), np.arange(n)) and np.array_equal(np.sort(rec["perm_y"]), np.arange(m))
     xs, ys, hs = x[0].float().cpu().numpy()[rec["perm_x"]], y[0].float().cpu().numpy()[rec["perm_y"]], h[rec["perm_y"]]
@@ -139,7 +87,7 @@ def test_thresholds_match_the_model(name):
     runs = pm.runs_per_slab(keep)
     for c in np.flatnonzero(same)[:: max(1, C // 150)]:
         want = pm.closed_gaps(keep[c]) if runs[c] > pm.RUNS else keep[c]
-        assert np.array_equal(_covered(rec, c, nT), want), c
+        assert np.array_equal(ps.covered(rec, c, nT), want), c
     # second level: 100 slabs, on the device's intervals
     has = np.flatnonzero((rec["home"] >= 0) & same)
     slabs = has[:: max(1, len(has) // 100)]
@@ -163,28 +111,6 @@ def test_thresholds_match_the_model(name):
     assert gain.mean() > 0.5
 
 
-def _diam2(x, y):
-    z = torch.cat([x[0].float(), y[0].float()])
-    z = z[torch.isfinite(z).all(1)]
-    return float(((z.max(0).values - z.min(0).values) ** 2).sum())
-
-
-def _close(a, b, diam2, what):
-    """tests/test_exact_prune_gpu.py: the dense launch's own rounding, same NaN / infinity pattern"""
-    assert torch.equal(a.isnan(), b.isnan())
-    fin = ~b.isnan()
-    if not bool(fin.any()):
-        return
-    assert torch.equal(a[fin].isinf(), b[fin].isinf()) and torch.equal(a[fin & a.isinf()], b[fin & b.isinf()])
-    ok = fin & ~b.isinf()
-    if bool(ok.any()):
-        av, bv = a[ok].double(), b[ok].double()
-        err = float((av - bv).abs().max())
-        bound = 4e-7 * diam2 + 2e-6 * float(bv.abs().max())
-        print(f"max|pruned - {what}| {err:.3e} (bound {bound:.3e})")
-        assert err <= bound, (err, bound)
-
-
 def _float64_rows(x, y, h, eps, rows):
     """-eps log sum_j exp(h_j - |x_i - y_j|^2 / (2 eps)) for the given rows, float64 on the device"""
     xr, yy, hh = x[0, rows].double(), y[0].double(), h[0].double()
@@ -199,11 +125,11 @@ def _float64_rows(x, y, h, eps, rows):
 @pytest.mark.parametrize("name", ["even_d3_f32_bench", "uneven_d2_f32_uniform", "uneven_d3_bf16_bench"])
 def test_values_against_dense_and_float64(name, flags):
     x, y, h, _, _, eps = _input(name)
-    diam2 = _diam2(x, y)
-    pruned = _fwd(x, y, h, eps, flags)
-    _close(pruned, _fwd(x, y, h, eps, flags | NO_SORT), diam2, "dense")
+    diam2 = ps.diam2(x, y)
+    pruned = ps.fwd(x, y, h, eps, flags)
+    ps.close(pruned, ps.fwd(x, y, h, eps, flags | NO_SORT), diam2, "dense")
     rows = torch.arange(0, x.shape[1], max(1, x.shape[1] // 2048), device=DEV)[:2048]
-    _close(pruned[0, rows], _float64_rows(x, y, h, eps, rows).float(), diam2, "float64")
+    ps.close(pruned[0, rows], _float64_rows(x, y, h, eps, rows).float(), diam2, "float64")
 
 
 @LAYOUTS
@@ -217,6 +143,6 @@ def test_special_values_as_the_dense_launch(special, flags):
         h[0, 70000:70032] = float("inf")
     else:
         h[:] = float("-inf")
-    pruned, dense = _fwd(x, y, h, eps, flags), _fwd(x, y, h, eps, flags | NO_SORT)
+    pruned, dense = ps.fwd(x, y, h, eps, flags), ps.fwd(x, y, h, eps, flags | NO_SORT)
     assert bool((~torch.isfinite(dense)).any())                       # the input does what it is meant to
-    _close(pruned, dense, _diam2(x, y), "dense")
+    ps.close(pruned, dense, ps.diam2(x, y), "dense")
