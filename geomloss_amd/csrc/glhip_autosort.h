@@ -48,7 +48,15 @@ constexpr int kSortRowsPerVoxel = 256;
 //   with their exact maxima over the slab's HOME BLOCK — the block that attains Mlb(R), always kept (its dmin <= its dmax).  For it
 //   prune_blocks_kernel also writes one record per aligned group of 32 sorted columns (intervals start on multiples of kPruneColBlock,
 //   so a tile's group g is a global group) and prune_slabs_kernel the home block of every slab (-1: a slab that keeps everything, for
-//   lack of a finite bound or because every block passes it — no second level, no cost of it, for such a slab).  The sorted p = 2 call orders both clouds in voxels of kSortRowsPerVoxel
+//   lack of a finite bound or because every block passes it — no second level, no cost of it, for such a slab).
+//   The sweep (library 137).  bf16 x 3: softmin_fwd_x32_p2_kernel, 8 wavefronts on one staged 512-column LDS tile, the test per tile
+//   on its 16 groups.  f16 x 2: one of two kernels, chosen per launch on the device from the records of eight reference slabs
+//   (glhip_list_cursor.h, list_takes_launch) — where the first level keeps at most 30 % of the columns, or no slab has a home block,
+//   softmin_fwd_list_p2_kernel (glhip_softmin_list.h): one wavefront per tile of 32 rows, no LDS tile and no barrier, one test and
+//   one ballot per batch of up to 64 groups of a piece, the kept groups read straight from the group-major packed columns through
+//   a ring of four operands in registers, the lazy maximum with a batch = one ballot; otherwise the staged kernel on 4 wavefronts
+//   (same test per tile of 16 groups).  Same seed, same test expression, same thresholds, same guarantee in both.
+//   The sorted p = 2 call orders both clouds in voxels of kSortRowsPerVoxel
 //   points with a minor key of sub-voxels of ~32 points (prune_sort_sub), so that 32 consecutive points are compact; the distance
 //   launches (p = 1, laplacian, energy) keep the order they had.
 //   Balanced cells (library 128).  Voxels and sub-voxels hold 256 and 32 points on average, with Poisson counts: an ALIGNED run of exactly

@@ -26,6 +26,7 @@
 #include "glhip_softmin_ops.h"
 #include "glhip_wsum_mfma.h"
 #include "glhip_softmin_x32.h"
+#include "glhip_softmin_list.h"
 #include "glhip_wsum_x32.h"
 #include "glhip_dist_x32.h"
 #include "glhip_dist_grad_x32.h"
@@ -166,7 +167,15 @@ void launch_softmin_mfma_nw(const SoftminParams<T>& prm, const Ranges& rg, int n
         constexpr bool SP = decltype(sparse)::value;
         if constexpr (SP && kP2Shape) {
             if (use_p2) {
-                hipLaunchKernelGGL((softmin_fwd_x32_p2_kernel<D, T, NW, L>), grid, dim3(NW * 64), 0, st, prm, r, N, M, sl.sp, pk, sc.l2);
+                // f16 x 2: two sweeps back to back on the same grid, and ONE of them does the launch's work (list_takes_launch,
+                // glhip_list_cursor.h: decided on the device from the records, the same in every workgroup) — the list-driven kernel
+                // (glhip_softmin_list.h) where the first level keeps little or no slab has a home block, the staged one otherwise;
+                // the workgroups of the other return at once.  bf16 x 3: the staged kernel alone (the two arguments are not read).
+                // GLHIP_LIST_KEEP: the rule's threshold in percent (tuning knob, read per launch: 100 = always list-driven, 0 = only without home blocks)
+                const char* knob = getenv("GLHIP_LIST_KEEP");
+                const int keep_pct = knob ? atoi(knob) : kListKeepPct;
+                if constexpr (L == XL_F16X2) hipLaunchKernelGGL((softmin_fwd_list_p2_kernel<D, T>), grid, dim3(NW * 64), 0, st, prm, r, N, M, sl.sp, pk, sc.l2, n_ranges, keep_pct);
+                hipLaunchKernelGGL((softmin_fwd_x32_p2_kernel<D, T, NW, L>), grid, dim3(NW * 64), 0, st, prm, r, N, M, sl.sp, pk, sc.l2, n_ranges, keep_pct);
                 return;
             }
         }

@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 136 /* 0.1.36 */
+#define GLHIP_VERSION 137 /* 0.1.37 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
@@ -168,6 +168,9 @@ extern "C" {
                                   exponent over the home block where that is more.  A smooth dual vector gains ~6 nats of threshold, the
                                   bench law 1-1.7; Mlb, home, the bucket grids and the stored t1 / t2 mean what they did, and
                                   glhip_prune_inspect shows them (csrc/glhip_autosort.h, "Sum reference"; profiles/sum_reference.txt).
+                                  Version 137: on the f16 x 2 layout the sorted launch is swept by a list-driven kernel (one wavefront per
+                                  tile of 32 rows, one keep test per 64 groups, operands straight from the packed columns: csrc/
+                                  glhip_softmin_list.h).  Same test, same guarantee; the order of summation differs (profiles/list_sweep.txt).
                                   Here this flag means the dense xd / x32 launch. */
 
 /* Environment variables read ONCE per process by the library itself (test / tuning knobs; everything else is an argument):
