@@ -22,7 +22,7 @@ from .wasserstein_barycenter_images import ImagesBarycenter  # noqa: E402
 from . import sinkhorn_divergence  # noqa: E402
 from . import ot  # noqa: E402  (`from geomloss import ot`: ot.solve_sample on the same kernels)
 from . import transport  # noqa: E402  (apply_plan / barycentric_map for the potentials of the legacy API)
-from .transport import apply_plan, barycentric_map, plan_argmax  # noqa: E402
-from .cluster import kmeans  # noqa: E402  (cluster labels in any dimension for the "multiscale" backend)
+from .transport import apply_plan, barycentric_map, plan_argmax, plan_topk  # noqa: E402
+from .cluster import kmeans, knn  # noqa: E402  (cluster labels in any dimension for the "multiscale" backend; k nearest neighbours)
 
-__all__ = ["SamplesLoss", "ImagesBarycenter", "sinkhorn_divergence", "hip", "ot", "transport", "apply_plan", "barycentric_map", "plan_argmax", "kmeans"]
+__all__ = ["SamplesLoss", "ImagesBarycenter", "sinkhorn_divergence", "hip", "ot", "transport", "apply_plan", "barycentric_map", "plan_argmax", "plan_topk", "kmeans", "knn"]

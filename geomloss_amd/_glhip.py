@@ -96,6 +96,10 @@ SIGNATURES = {
     "glhip_argmin_supported": (_c_int, [_c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int]),
     "glhip_argmin_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int]),
     "glhip_argmin": (_c_int, [_vp] * 5 + [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int] + _RANGES + _TAIL),
+    "glhip_argkmin_max_k": (_c_int, []),
+    "glhip_argkmin_supported": (_c_int, [_c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int, _c_int]),
+    "glhip_argkmin_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "glhip_argkmin": (_c_int, [_vp] * 5 + [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int] + _RANGES + _TAIL),
     "glhip_cluster_workspace_bytes": (_c_size, [_c_int, _c_int]),
     "glhip_grid_cluster": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_float, _c_float] + [_vp] * 7 + [_vp, _c_size, _vp]),
     "glhip_block_ranges": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float] + [_vp] * 6
@@ -118,7 +122,8 @@ PERM_HINT_X, PERM_HINT_Y = 1, 2     # perm_flags of glhip_sinkhorn_step_perm (GL
 # calls that would use them take the entry points that build has (no permutation is reused with it)
 _SINCE = {"glhip_sinkhorn_step_perm": 134, "glhip_softmin_perm_applies": 134,
           "glhip_plan_apply_p1_supported": 135, "glhip_plan_apply_p1_pass_width": 135, "glhip_plan_apply_p1_workspace_bytes": 135,
-          "glhip_plan_apply_p1": 135}
+          "glhip_plan_apply_p1": 135,
+          "glhip_argkmin_max_k": 138, "glhip_argkmin_supported": 138, "glhip_argkmin_workspace_bytes": 138, "glhip_argkmin": 138}
 
 _lib = None
 

@@ -12,7 +12,7 @@ One deliberate difference: ``from_matrix`` merges column intervals that are adja
 (i, j) pairs is unchanged.
 
 :func:`kmeans` produces cluster labels in any dimension (the reference's tutorial recipe for D > 3, where there is no cubic grid),
-for the 6-argument call form of ``SamplesLoss``.
+for the 6-argument call form of ``SamplesLoss``; :func:`knn` is the k-nearest-neighbour search that goes with it.
 """
 
 import torch
@@ -131,6 +131,17 @@ def kmeans(x, K, n_iter=10, init=None, weights=None, generator=None):
         if labels is None:
             labels = hip.argmin(x, c)
         return labels.int(), c
+
+
+def knn(x, y, k):
+    """The ``k`` nearest points of ``y`` for every point of ``x``: ``(index, sqdist)``, int32 and fp32 (N,k)|(B,N,k), nearest first —
+    KeOps' ``Kmin_argKmin(k, dim=1)`` of ``SqDist(x, y)``, on the matrix cores (:func:`geomloss_amd.hip.argkmin`): nothing of size
+    N x M is stored.  x (N,D)|(B,N,D), y (M,D)|(B,M,D) fp32 | bf16 on a GPU, 1 <= D <= 4095, 1 <= k <= ``hip.ARGKMIN_MAX_K``.
+    ``sqdist`` is the kernel's float32 ``|x_i - y_j|^2`` (twice its half-squared cost, an exact doubling); equal distances come in
+    ascending index order; with fewer than k points in ``y`` the last ranks are (-1, +inf).  Not recorded by autograd."""
+    from . import hip
+    index, value = hip.argkmin(x, y, k, return_value=True)
+    return index, 2.0 * value
 
 
 def sort_clusters(x, lab):

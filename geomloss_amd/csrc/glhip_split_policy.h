@@ -23,6 +23,7 @@ constexpr long kFwdSlots = 256 * 3;   // ... the forward / gaussian x32 kernels 
 constexpr long kXdSlots = 256 * 2;    // ... the kernels of 4 <= D <= 16 (<= 48 KiB of LDS, <= 128 VGPRs)
 constexpr long kXkSlots = 256 * 2;    // ... the kernels of 17 <= D <= 4095 (78.75 KiB of LDS, <= 128 VGPRs)
 constexpr long kXkPlanSlots = 256;    // ... xk_plan_kernel: one per CU (glhip_plan_apply_xk.h)
+constexpr long kXkTopkSlots = 256;    // ... argkmin_xk_kernel with lists of 8 / 16 candidates: one per CU (> 128 VGPRs; glhip_argkmin_xk.h)
 
 constexpr int kXdMaxD = 16;           // 4 <= D <= 16: the xd kernels (glhip_softmin_xd.h); beyond, up to kSizedMaxD, the K-chunked ones
 // Rows per workgroup of the kernel shapes the sizing rule counts with, and the last dimension it sizes; glhip_launch.h asserts each

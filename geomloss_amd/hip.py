@@ -29,6 +29,8 @@ from ._perm_cache import PERM_CACHE_ENTRIES, _PermCache, perm_cache_key  # noqa:
 def __getattr__(name):
     if name == "_lib":      # the loaded library, or None before the first load_library(): state of _glhip, read through
         return _glhip._lib
+    if name == "ARGKMIN_MAX_K":      # the largest k of argkmin: the library's own limit (glhip_argkmin_max_k), read when asked for
+        return int(load_library().glhip_argkmin_max_k())
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
@@ -1658,7 +1660,7 @@ def argmin(x, y, g=None, return_value=False, flags=0, p=2):
     x: (N,D)|(B,N,D), y: (M,D)|(B,M,D), g: (M,)|(B,M)|None -> int32 (N,)|(B,N); with ``return_value`` also the fp32 minima.
     Ties go to the smallest index; ``g_j = -inf`` excludes column j; a row without an admissible column (M = 0, every g = -inf) gets
     index -1 and value +inf.  Not recorded by autograd.  float64 clouds, p != 2 and D > ARGMIN_MAX_DIM = 4095 raise
-    ``NotImplementedError``; block-sparse ranges, k > 1 neighbours and p = 1 are out of scope."""
+    ``NotImplementedError``; block-sparse ranges and p = 1 are out of scope; k > 1 neighbours: :func:`argkmin`."""
     if x.dtype == torch.float64 or y.dtype == torch.float64:
         raise NotImplementedError("geomloss_amd.hip.argmin: float64 clouds are not supported (cast to float32)")
     D = x.shape[-1]
@@ -1685,6 +1687,58 @@ def argmin(x, y, g=None, return_value=False, flags=0, p=2):
     if not batched:
         index = index.view(-1)
         value = value.view(-1) if return_value else None
+    return (index, value) if return_value else index
+
+
+def argkmin_supported(B, N, M, D, k, p=2, dtype=F32, n_ranges=0):
+    """Whether ``glhip_argkmin`` serves a launch of this shape (p = 2, dense, 1 <= D <= ARGMIN_MAX_DIM, 1 <= k <= ARGKMIN_MAX_K, fp32 /
+    bf16 clouds): the predicate the launch itself evaluates (``glhip_argkmin_supported``), host arithmetic only — no device is touched.
+    Raises ``ValueError`` for what the entry point rejects (negative sizes, D < 1, k < 1, a bad p or dtype)."""
+    return bool(_route_predicate("glhip_argkmin_supported", (B, N, M, D, k, p, dtype, n_ranges),
+                                 f"B {B}, N {N}, M {M}, D {D}, k {k}, p {p}, dtype {dtype}, n_ranges {n_ranges}"))
+
+
+def argkmin(x, y, k, g=None, return_value=False, flags=0, p=2):
+    """Top-k arg-reduction on the matrix cores (``glhip_argkmin``): for every row the ``k`` columns of the smallest
+    ``|x_i - y_j|^2 / 2 - g_j``, best first — the k nearest columns for ``g = None``, what KeOps' ``LazyTensor.argKmin(k, dim=1)`` of
+    ``SqDist`` returns (``Kmin_argKmin`` with ``return_value``: the squared distance is twice the value); the k columns a plan row sends
+    most of its mass to for g = dual potential + eps log weight.
+    x: (N,D)|(B,N,D), y: (M,D)|(B,M,D), g: (M,)|(B,M)|None -> int32 (N,k)|(B,N,k); with ``return_value`` also the fp32 costs.
+    Entries are sorted by (cost ascending, index ascending) on the kernel's float32 exponents: the first k' < k columns are what a call
+    with k' returns, ``k = 1`` is :func:`argmin`, bit for bit both, whatever the launch.  ``g_j = -inf`` excludes column j; ranks a row
+    has no admissible column for (M < k, masks, M = 0) get index -1 and value +inf.  Not recorded by autograd.  float64 clouds, p != 2,
+    D > ARGMIN_MAX_DIM = 4095 and k > ARGKMIN_MAX_K raise ``NotImplementedError``, k < 1 ``ValueError``; block-sparse ranges and p = 1
+    are out of scope."""
+    if x.dtype == torch.float64 or y.dtype == torch.float64:
+        raise NotImplementedError("geomloss_amd.hip.argkmin: float64 clouds are not supported (cast to float32)")
+    D = x.shape[-1]
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"geomloss_amd.hip.argkmin: k must be at least 1, got {k}")
+    lib = load_library()
+    max_k = int(lib.glhip_argkmin_max_k())
+    if p != 2 or D > ARGMIN_MAX_DIM or k > max_k:
+        raise NotImplementedError(f"geomloss_amd.hip.argkmin: only p = 2, D <= {ARGMIN_MAX_DIM}, k <= {max_k} (got p = {p}, D = {D}, k = {k})")
+    with torch.no_grad():
+        # (g may be None or empty: a placeholder goes with the clouds, g is checked against them and reshaped below)
+        xb, yb, _, batched = _clouds(x, y, torch.empty(x.shape[0] if x.dim() == 3 else 1, dtype=torch.float32, device=x.device), detach=True)
+        if g is not None and g.numel() != yb.numel() // max(D, 1):
+            raise ValueError(f"geomloss_amd.hip.argkmin: expected one dual value per column, {tuple(y.shape[:-1])}, got {tuple(g.shape)}")
+        gb = None if g is None else _f32(g).to(xb.device).reshape(yb.shape[:2])
+        if yb.shape[0] != xb.shape[0] or yb.shape[2] != D:
+            raise ValueError(f"geomloss_amd.hip.argkmin: clouds of shapes {tuple(x.shape)} and {tuple(y.shape)} do not go together")
+        B, N, _ = xb.shape
+        M = yb.shape[1]
+        index = torch.empty((B, N, k), dtype=torch.int32, device=xb.device)
+        value = torch.empty((B, N, k), dtype=torch.float32, device=xb.device) if return_value else None
+        with torch.cuda.device(xb.device):
+            ws, ws_args = _scratch(int(lib.glhip_argkmin_workspace_bytes(B, N, M, D, k)), xb.device)
+            rc = lib.glhip_argkmin(xb.data_ptr(), yb.data_ptr(), _ptr(gb), index.data_ptr(), _ptr(value), B, N, M, D, k, int(p), _dtype_code(xb),
+                                   *_NO_RANGES, *ws_args, int(flags) | ENV_FLAGS, _stream(xb))
+        _check(rc, lib)
+    if not batched:
+        index = index.view(N, k)
+        value = value.view(N, k) if return_value else None
     return (index, value) if return_value else index
 
 

@@ -264,7 +264,7 @@ class LinearOperator:
 
 class OTResultSample:
     """Result of :func:`solve_sample` (``sample.py:447-639`` + ``_ot_result.py:164-454``): lazily computed, cached attributes
-    ``value``, ``potential_a/b/aa/bb``, ``plan``, ``density``, ``lazy_plan``, ``lazy_density``, ``density_operator``,
+    ``value``, ``potential_a/b/aa/bb``, ``plan``, ``sparse_plan(k)``, ``density``, ``lazy_plan``, ``lazy_density``, ``density_operator``,
     ``plan_operator``, ``marginal_a/b``, ``a_to_b``, ``b_to_a``, ``citation``.  Arrays come back in the library, dtype and
     device of the solver's inputs; operators act on fp32 GPU tensors."""
 
@@ -380,6 +380,29 @@ class OTResultSample:
     @cached_property
     def lazy_plan(self):
         return self.plan_operator
+
+    def sparse_plan(self, k):
+        """The ``k`` heaviest entries of every row of :attr:`plan`: ``(index, weight)``, (N, k) arrays in the caller's library, heaviest
+        first, ``weight[i, r] = plan[i, index[i, r]]`` — what a user of the reference extracts with ``lazy_plan.argKmin(k, dim=1)`` /
+        ``Kmin_argKmin``.  One top-k arg-reduction (:func:`geomloss_amd.hip.argkmin`), nothing of size N x M: the library's
+        half-squared cost at eps = reg / 2 serves the solver's |x - y|^2 as in ``_apply_density``.  Columns of zero weight are never
+        returned; ranks without a column have index -1 and weight 0.  Where the reduction does not apply (float64 clouds, D > 4095)
+        it raises ``NotImplementedError``: use :attr:`plan` there."""
+        self._check_kl()
+        x, y = self._X_a.detach(), self._X_b.detach()
+        if x.dtype == torch.float64 or x.shape[-1] > hip.ARGMIN_MAX_DIM:
+            raise NotImplementedError("OTResultSample.sparse_plan: the top-k arg-reduction takes float32 / bfloat16 clouds of dimension "
+                                      f"D <= {hip.ARGMIN_MAX_DIM}; use the dense `plan` for these clouds.")
+        eps = self._reg / 2.0
+        f, g = self._potentials.f_ba.detach().float(), self._potentials.g_ab.detach().float()
+        # P_ij = a_i b_j exp((f_i + g_j - 2 C_ij) / reg) = a_i exp((f_i / 2 - [C_ij - g_j / 2 - eps log b_j]) / eps),  C = |x - y|^2 / 2
+        index, value = hip.argkmin(x, y, k, g / 2.0 + eps * self._b.detach().float().log(), return_value=True)      # (log 0 = -inf: no mass, never returned)
+        weight = (self._a.detach().float().log()[:, None] + (f[:, None] / 2.0 - value) / eps).exp()
+        weight = torch.where(index >= 0, weight, torch.zeros_like(weight))
+        ap = self._array_properties
+        if ap.library == "numpy":
+            return index.cpu().numpy(), weight.cpu().numpy().astype(ap.dtype)
+        return index.to(device=ap.device), weight.to(dtype=ap.dtype, device=ap.device)
 
     # values ---------------------------------------------------------------------------------------------------------
     @cached_property

@@ -21,7 +21,8 @@ the side: one kernel for every dimension 1 <= D <= 4095, 64 feature columns per 
 (D, V), narrowly so at D = 3, V = 3 (the loop: 1.1x the product).
 
 :func:`plan_argmax` gives the hard correspondence instead of an average: the column that receives most of a row's mass, one
-arg-reduction (:func:`geomloss_amd.hip.argmin`), same clouds and dimensions.
+arg-reduction (:func:`geomloss_amd.hip.argmin`), same clouds and dimensions.  :func:`plan_topk` gives the k heaviest entries of
+every row with their weights — a sparse plan — from one top-k arg-reduction (:func:`geomloss_amd.hip.argkmin`).
 """
 
 import math
@@ -30,7 +31,7 @@ import torch
 
 from . import hip
 
-__all__ = ["apply_plan", "barycentric_map", "plan_argmax"]
+__all__ = ["apply_plan", "barycentric_map", "plan_argmax", "plan_topk"]
 
 
 def _log_weights(w, like, count):
@@ -93,3 +94,33 @@ def plan_argmax(x, y, F, G, blur, b=None):
     with torch.no_grad():
         Gf = G.detach().float().reshape(y.shape[:-1])
         return hip.argmin(x, y, Gf + eps * _log_weights(b, Gf, y.shape[-2]))
+
+
+def plan_topk(x, y, F, G, blur, k, a=None, b=None, p=2):
+    """The ``k`` heaviest entries of every row of the plan: ``(index, weight)``, int32 and fp32 (N,k)|(B,N,k), heaviest first, with
+    ``weight[i, r] = P[i, index[i, r]]``.  One top-k arg-reduction (:func:`geomloss_amd.hip.argkmin`) of
+    ``|x_i - y_j|^2 / 2 - G_j - blur^2 log b_j``, whose values give the weights as ``a_i exp((F_i - value_ir) / blur^2)``: nothing of
+    size N x M is stored.  Columns of zero weight are never returned; a row with fewer than k columns of positive weight has index -1 and
+    weight 0 in its last ranks; equal entries come in ascending column order.  1 <= k <= ``hip.ARGKMIN_MAX_K``; ``p=1`` raises
+    ``NotImplementedError`` (the arg-reduction has the squared cost only).
+
+    As a sparse matrix (unbatched, every rank filled)::
+
+        rows = torch.arange(N, device=index.device).repeat_interleave(k)
+        P_k = torch.sparse_coo_tensor(torch.stack((rows, index.reshape(-1).long())), weight.reshape(-1), (N, M))
+
+    and the share of every row's mass that its k entries keep (``fwd`` is the soft-min :func:`apply_plan` starts from)::
+
+        fwd = hip.softmin(blur**2, x, y, G / blur**2 + b.log())
+        share = weight.sum(-1) / (a * ((F - fwd) / blur**2).exp())
+    """
+    if p != 2:
+        raise NotImplementedError(f"geomloss_amd.transport.plan_topk: only the plans of p = 2 (got p = {p!r})")
+    eps = float(blur) ** 2
+    with torch.no_grad():
+        Ff = F.detach().float().reshape(x.shape[:-1])
+        Gf = G.detach().float().reshape(y.shape[:-1])
+        index, value = hip.argkmin(x, y, k, Gf + eps * _log_weights(b, Gf, y.shape[-2]), return_value=True)
+        la = _log_weights(a, Ff, x.shape[-2]).to(value.device)
+        weight = (la.unsqueeze(-1) + (Ff.to(value.device).unsqueeze(-1) - value) / eps).exp()
+        return index, torch.where(index >= 0, weight, torch.zeros_like(weight))

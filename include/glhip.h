@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 137 /* 0.1.37 */
+#define GLHIP_VERSION 138 /* 0.1.38 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
@@ -705,6 +705,40 @@ int glhip_argmin(const void* x, const void* y, const float* g, int32_t* index, f
                  int B, int N, int M, int D, int p, int in_dtype,
                  const int32_t* ranges_i, const int32_t* slices_i, const int32_t* redranges_j, int n_ranges,
                  void* workspace, size_t workspace_bytes, int flags, void* stream);
+/*
+ * Top-k arg-reduction (version 138; glhip_argkmin_xk.h): for every row the k columns of the smallest dual-shifted cost, best first,
+ *   index[b,i,r] = column of the (r+1)-th smallest c_ij = |x[b,i] - y[b,j]|^2 / 2 - g[b,j],   value[b,i,r] = that cost.
+ * Replaces: KeOps' `.argKmin(k, dim=1)` / `.Kmin_argKmin` on a LazyTensor — k nearest neighbours with g = NULL (SqDist: the squared
+ * distance is 2 value), and the k heaviest entries of every row of a transport plan with g = dual potential + eps log weight, what a
+ * user of the reference extracts from `ot.solve_sample(...).lazy_plan` (ot/_implementations/sample.py:562-617).
+ *   x (B,N,D), y (B,M,D) fp32 | bf16;  g (B,M) fp32 or NULL (= 0);  index (B,N,k) int32;  value (B,N,k) fp32 or NULL.
+ *   Supported: p == 2, 1 <= D <= 4095, dense launches (n_ranges == 0), any B <= 65535, 1 <= k <= glhip_argkmin_max_k() (16); p = 1,
+ *   D > 4095, a larger k and block-sparse ranges return GLHIP_EUNSUPPORTED (the range arguments are there so that block-sparse launches
+ *   can follow without an ABI change); k < 1 is GLHIP_EINVAL.
+ *   The kernel is argmin's — staging, MFMA chain and exponents u_ij of glhip_softmin_xk.h, bit for bit — with another epilogue: every
+ *   lane keeps a sorted list of 4 / 8 / 16 candidates per row in registers (the smallest capacity that holds k), filtered by one
+ *   compare against the list's last entry; lane halves, the workgroup's column halves and the column splits merge k-lists.
+ *   Order: entries are sorted by (u descending, index ascending), u the float32 exponent of the kernel — the rule of glhip_argmin.
+ *   So the result of a call with k is the first k entries of a call with any larger k, k = 1 is glhip_argmin (index and value), bit for
+ *   bit both, and exact duplicates among the columns come in ascending index order.  u_ij does not depend on the tile or split a column
+ *   falls into: the result is the same with any number of column splits, under GLHIP_FLAG_NO_SPLIT, with a short or NULL workspace.
+ *   g[b,j] = -inf marks a column that is never returned; NaN exponents never enter a list; a row with fewer than k admissible columns
+ *   (M < k, masks, M == 0) fills its last ranks with index -1 and value +inf.  N == 0 or B == 0 launches nothing.
+ *   Accuracy: per entry that of glhip_argmin — the cost of the column at rank r is within 2 (NM + 5) 2^-24 (diam^2 + max |g|) of the
+ *   row's (r+1)-th smallest cost, NM = ceil((6 + 6 D) / 16), and value is within that of the same number.
+ *   flags: GLHIP_FLAG_NO_SPLIT; GLHIP_FLAG_F16X2 is accepted and ignored (bf16 x 3 only: no range precondition); others are ignored.
+ *   Workspace: glhip_argkmin_workspace_bytes (<= 1 GiB) holds the k (exponent, index) partials per row of the column splits the launch
+ *   would like; NULL or short means fewer or no splits, with the same results.
+ * glhip_argkmin_supported: host arithmetic only, the predicate the launch itself evaluates — 1 / 0, GLHIP_EINVAL for what the entry
+ * point rejects (negative sizes, D < 1, k < 1, a bad p or dtype).
+ */
+int glhip_argkmin_max_k(void);
+int glhip_argkmin_supported(int B, long N, long M, int D, int k, int p, int dtype, int n_ranges);
+size_t glhip_argkmin_workspace_bytes(int B, int N, int M, int D, int k);
+int glhip_argkmin(const void* x, const void* y, const float* g, int32_t* index, float* value,
+                  int B, int N, int M, int D, int k, int p, int in_dtype,
+                  const int32_t* ranges_i, const int32_t* slices_i, const int32_t* redranges_j, int n_ranges,
+                  void* workspace, size_t workspace_bytes, int flags, void* stream);
 /*
  * The cluster pyramid of the two-scale ("multiscale") backends, on the device.
  *
