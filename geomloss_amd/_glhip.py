@@ -31,6 +31,8 @@ DIST_XK_MAX_DIM = 4095          # ... and under FLAG_XK_DIST the p = 1 soft-min 
 ARGMIN_MAX_DIM = 4095           # argmin takes p = 2 clouds of every dimension up to this one (glhip_argmin_xk.h)
 PLAN_MAX_DIM = 4095             # plan_apply_nd applies p = 2 transport plans to features up to this dimension (17 ... 4095: glhip_plan_apply_xk.h)
 PLAN_P1_MAX_DIM = 4095          # plan_apply_p1 applies p = 1 transport plans to features in every dimension up to this one (glhip_dist_plan_xk.h)
+PLAN_BILINEAR_MAX_DIM = 4095    # plan_bilinear contracts p = 2 plans with <rowfeat_i, colfeat_j> (y_j - x_i) up to this dimension and feature count
+                                # (glhip_plan_bilinear_xk.h)
 # kernel families reported by softmin_fwd_family (GLHIP_FAMILY_* of glhip.h)
 FAMILY_VALU, FAMILY_X32, FAMILY_XD, FAMILY_XK, FAMILY_DIST, FAMILY_GENERIC = 0, 1, 2, 3, 4, 5
 
@@ -77,6 +79,10 @@ SIGNATURES = {
     "glhip_plan_apply_p1_pass_width": (_c_int, []),
     "glhip_plan_apply_p1_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "glhip_plan_apply_p1": (_c_int, [_vp] * 6 + [_c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int] + _RANGES + _TAIL),
+    "glhip_plan_bilinear_supported": (_c_int, [_c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int, _c_int]),
+    "glhip_plan_bilinear_pass_width": (_c_int, []),
+    "glhip_plan_bilinear_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "glhip_plan_bilinear": (_c_int, [_vp] * 8 + [_c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int, _c_int] + _RANGES + _TAIL),
     "glhip_kernel_conv_fwd": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int]
                               + _RANGES + _TAIL),
     "glhip_kernel_conv_bwd_x": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float,
@@ -123,7 +129,9 @@ PERM_HINT_X, PERM_HINT_Y = 1, 2     # perm_flags of glhip_sinkhorn_step_perm (GL
 _SINCE = {"glhip_sinkhorn_step_perm": 134, "glhip_softmin_perm_applies": 134,
           "glhip_plan_apply_p1_supported": 135, "glhip_plan_apply_p1_pass_width": 135, "glhip_plan_apply_p1_workspace_bytes": 135,
           "glhip_plan_apply_p1": 135,
-          "glhip_argkmin_max_k": 138, "glhip_argkmin_supported": 138, "glhip_argkmin_workspace_bytes": 138, "glhip_argkmin": 138}
+          "glhip_argkmin_max_k": 138, "glhip_argkmin_supported": 138, "glhip_argkmin_workspace_bytes": 138, "glhip_argkmin": 138,
+          "glhip_plan_bilinear_supported": 139, "glhip_plan_bilinear_pass_width": 139, "glhip_plan_bilinear_workspace_bytes": 139,
+          "glhip_plan_bilinear": 139}
 
 _lib = None
 

@@ -52,8 +52,9 @@
 // argument (plan_merge_kernel below, one thread per row and feature) — one merge for every chunk count and any V, instead of one
 // MergeOp instantiation per width.
 //
-// Shared pieces (profiles/xk_plan_pieces.txt).  The plan half exists in four __global__ bodies: plan_apply_kernel here, xk_plan_kernel
-// (glhip_plan_apply_xk.h), xk_dist_grad_kernel (glhip_dist_grad_xk.h) and xk_dist_plan_kernel (glhip_dist_plan_xk.h).  What they share as __device__ __forceinline__ pieces is defined
+// Shared pieces (profiles/xk_plan_pieces.txt).  The plan half exists in five __global__ bodies: plan_apply_kernel here, xk_plan_kernel
+// (glhip_plan_apply_xk.h), xk_dist_grad_kernel (glhip_dist_grad_xk.h), xk_dist_plan_kernel (glhip_dist_plan_xk.h) and xk_bilinear_kernel
+// (glhip_plan_bilinear_xk.h).  What they share as __device__ __forceinline__ pieces is defined
 // here — plan_store_pieces (scale, split and store of one staged feature item), plan_rescale (the lazy rescale; this kernel keeps its
 // inline text: the helper costs the four-chunk instantiations 2 VGPRs), plan_split_weights, plan_chunk_mfma (the six MFMAs of a chunk) —
 // next to the register maps reg_column / reg_feature of glhip_klayout.h.  The staging loops, the fold of a fresh accumulator into the running

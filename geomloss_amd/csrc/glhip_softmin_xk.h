@@ -158,7 +158,8 @@ __device__ __forceinline__ void xk_norms(const T* __restrict__ pts, const T* __r
 //             the 4 MFMAs of a chunk, mfma(Y, X, acc) — lane (half, i) ends up with row i for the columns 8 (r / 4) + 4 half + r % 4.
 // Keep this a __forceinline__ function called from a __global__ body.  Moving a whole kernel BODY into a device function behind thin
 // __global__ wrappers was tried for xk_plan_kernel: +30 VGPRs at NCH = 1 and 112-180 bytes of scratch per lane at NCH = 2.
-template <typename T, int L, bool SCHED>
+// CENTRED = false (the weight half of xk_bilinear_kernel, glhip_plan_bilinear_xk.h): the points are taken as they are and `centre` is not read.
+template <typename T, int L, bool SCHED, bool CENTRED = true>
 __device__ __forceinline__ void xk_exponent_blocks(XkLds& lds, const T* __restrict__ xb, const T* __restrict__ yb, const T* __restrict__ centre,
                                                    int D, int NM, int NG, int nr32, int ncg, float xscale, float yscale, bool wave_on, int wr,
                                                    int wc, int half, int l31, int tid, f32x16 (&acc)[kXkRT][kXkCG]) {
@@ -194,7 +195,8 @@ __device__ __forceinline__ void xk_exponent_blocks(XkLds& lds, const T* __restri
 #pragma unroll
                 for (int q = 0; q < kItems / 2; ++q) {
                     const int d = d0 + HALF * (kItems / 2) + q;
-                    val[q] = (d >= 0 && d < D && i >= 0) ? (to_f32<T>(p[d]) - to_f32<T>(centre[d])) * scale : 0.f;
+                    if constexpr (CENTRED) val[q] = (d >= 0 && d < D && i >= 0) ? (to_f32<T>(p[d]) - to_f32<T>(centre[d])) * scale : 0.f;
+                    else val[q] = (d >= 0 && d < D && i >= 0) ? to_f32<T>(p[d]) * scale : 0.f;
                 }
                 if (isrow) xk_pack_half<true, L, HALF>(g == 0, sc, val, w[HALF]);
                 else xk_pack_half<false, L, HALF>(g == 0, sc, val, w[HALF]);

@@ -506,6 +506,31 @@ def plan_apply_p1_raw(xb, yb, hb, fb, eps, flags=0, want_softmin=False, workspac
     return (out, soft) if want_softmin else out
 
 
+def plan_bilinear_raw(xb, yb, hb, fwd, rowfeat, colfeat, eps, flags=0, p=2, ranges=None, workspace=True):
+    """The plan of a p = 2 soft-min contracted with the per-pair weight ``<rowfeat_i, colfeat_j>`` (``glhip_plan_bilinear``, any
+    D, K <= PLAN_BILINEAR_MAX_DIM): xb (B,N,D), yb (B,M,D) fp32|bf16, hb (B,M), fwd (B,N) the saved soft-min, rowfeat (B,N,K),
+    colfeat (B,M,K) fp32 -> out (B,N,D), wsum (B,N) fp32.  ``workspace=False`` passes no workspace: the launch runs without column
+    splits (same results up to summation order)."""
+    lib = load_library()
+    B, N, D = xb.shape
+    M, K = yb.shape[1], rowfeat.shape[2]
+    if is_f64(xb):
+        raise NotImplementedError("glhip_plan_bilinear: float64 clouds are not supported (cast to float32)")
+    if (tuple(rowfeat.shape) != (B, N, K) or tuple(colfeat.shape) != (B, M, K) or tuple(hb.shape) != (B, M) or tuple(fwd.shape) != (B, N)
+            or tuple(yb.shape) != (B, M, D)):
+        raise ValueError(f"glhip_plan_bilinear: expected y {(B, M, D)}, h {(B, M)}, fwd {(B, N)}, rowfeat {(B, N, 'K')}, colfeat {(B, M, 'K')}; got "
+                         f"{tuple(yb.shape)}, {tuple(hb.shape)}, {tuple(fwd.shape)}, {tuple(rowfeat.shape)}, {tuple(colfeat.shape)}")
+    out = torch.empty((B, N, D), dtype=torch.float32, device=xb.device)
+    wsum = torch.empty((B, N), dtype=torch.float32, device=xb.device)
+    with torch.cuda.device(xb.device):
+        ws, ws_args = _scratch(int(lib.glhip_plan_bilinear_workspace_bytes(B, N, M, D, K)) if workspace else 0, xb.device)
+        rc = lib.glhip_plan_bilinear(xb.data_ptr(), yb.data_ptr(), hb.data_ptr(), fwd.data_ptr(), rowfeat.data_ptr(), colfeat.data_ptr(),
+                                     out.data_ptr(), wsum.data_ptr(), B, N, M, D, K, float(eps), int(p), _dtype_code(xb),
+                                     *_range_args(ranges, B), *ws_args, int(flags), _stream(xb))
+    _check(rc, lib)
+    return out, wsum
+
+
 def softmin_fwd_grad_raw(x, y, h, guess, margin, eps, ranges=None, flags=0):
     """Soft-min and d out_i / d x_i in one reduction, given a guess within ``margin`` of the answer (``glhip_softmin_fwd_grad``;
     p = 2, D <= 16) -> (B,N), (B,N,D)."""
@@ -1318,6 +1343,52 @@ def plan_apply_p1(eps, x, y, h, feat, flags=0, want_softmin=False, ranges=None):
         soft = None if soft is None else soft[0]
     out = out[..., 0] if vector else out
     return (out, soft) if want_softmin else out
+
+
+def plan_bilinear_applies(x, ranges=None):
+    """Whether :func:`plan_bilinear` serves clouds like ``x``: dense, D <= PLAN_BILINEAR_MAX_DIM, float32 / bfloat16 compute (p = 2 only)."""
+    return ranges is None and 1 <= x.shape[-1] <= PLAN_BILINEAR_MAX_DIM and x.dtype != torch.float64
+
+
+def plan_bilinear(eps, x, y, h, rowfeat, colfeat, fwd=None, flags=0, p=2, ranges=None):
+    """The plan of a p = 2 soft-min contracted with a bilinear per-pair weight on the matrix cores (``glhip_plan_bilinear``,
+    glhip_plan_bilinear_xk.h), for clouds of any dimension D <= PLAN_BILINEAR_MAX_DIM = 4095 and K <= 4095 features:
+
+        pi_ij = w_ij / sum_j w_ij,    w_ij = exp(h_j - |x_i - y_j|^2 / (2 eps) + fwd_i / eps),    tau_ij = <rowfeat_i, colfeat_j>
+        out[i, :] = sum_j pi_ij tau_ij (y_j - x_i)            wsum[i] = sum_j pi_ij tau_ij
+
+    x: (N,D)|(B,N,D), y: (M,D)|(B,M,D), h: (M,)|(B,M), rowfeat: (N,K)|(B,N,K), colfeat: (M,K)|(B,M,K) -> ``(out, wsum)`` of shapes
+    (N,D)|(B,N,D) and (N,)|(B,N), fp32.  ``fwd`` is ``softmin(eps, x, y, h)`` for the same arguments; it is computed here by one
+    soft-min when not given, and only centres the exponents (the kernel divides by the row mass it recomputes).  This is the one
+    reduction behind the gradients of ``P @ S`` and of the barycentric map (``geomloss_amd.transport``).  One sweep over the pairs per 32
+    coordinates; every sweep evaluates the exponents and tau on the matrix cores.  Features of any finite magnitude are safe: the
+    product is scaled per row.  Rows without mass give 0, a column with ``h = -inf`` weighs exactly 0, results are bit-identical run
+    to run.  NOT an autograd function itself: it runs under ``torch.no_grad()`` and returns tensors without ``grad_fn``.  float64
+    clouds, p != 2, block-sparse ranges and D or K > 4095 raise ``NotImplementedError``; mismatched shapes raise ``ValueError``."""
+    D = x.shape[-1]
+    if x.dtype == torch.float64 or y.dtype == torch.float64:
+        raise NotImplementedError("geomloss_amd.hip.plan_bilinear: float64 clouds are not supported (cast to float32)")
+    lead_x, lead_y = tuple(x.shape[:-1]), tuple(y.shape[:-1])
+    if (x.dim() not in (2, 3) or y.dim() != x.dim() or y.shape[-1] != D or rowfeat.dim() != x.dim() or colfeat.dim() != x.dim()
+            or tuple(rowfeat.shape[:-1]) != lead_x or tuple(colfeat.shape[:-1]) != lead_y or rowfeat.shape[-1] != colfeat.shape[-1]
+            or tuple(h.shape) != lead_y or (fwd is not None and tuple(fwd.shape) != lead_x)):
+        raise ValueError(f"geomloss_amd.hip.plan_bilinear: expected y {lead_y[:-1] + ('M', D)}, h {lead_y}, rowfeat {lead_x + ('K',)}, "
+                         f"colfeat {lead_y + ('K',)}, fwd {lead_x}; got {tuple(y.shape)}, {tuple(h.shape)}, {tuple(rowfeat.shape)}, "
+                         f"{tuple(colfeat.shape)}, {None if fwd is None else tuple(fwd.shape)}")
+    K = rowfeat.shape[-1]
+    if p != 2 or D > PLAN_BILINEAR_MAX_DIM or K > PLAN_BILINEAR_MAX_DIM or ranges is not None:
+        raise NotImplementedError(f"geomloss_amd.hip.plan_bilinear: only p = 2, D and K <= {PLAN_BILINEAR_MAX_DIM}, dense plans (got p = {p}, "
+                                  f"D = {D}, K = {K}, ranges {'given' if ranges is not None else 'None'})")
+    batched = x.dim() == 3
+    with torch.no_grad():
+        xb, yb, hb, _ = _clouds(x, y, _f32(h), detach=True)
+        B, N, M = xb.shape[0], xb.shape[1], yb.shape[1]
+        rf = _f32(rowfeat).to(xb.device).reshape(B, N, K).contiguous()
+        cf = _f32(colfeat).to(xb.device).reshape(B, M, K).contiguous()
+        flags = int(flags) | ENV_FLAGS
+        fwd_b = softmin_fwd_raw(xb, yb, hb, eps, 2, None, flags) if fwd is None else _f32(fwd).reshape(B, -1).contiguous()
+        out, wsum = plan_bilinear_raw(xb, yb, hb.contiguous(), fwd_b, rf, cf, float(eps), flags)
+    return (out, wsum) if batched else (out[0], wsum[0])
 
 
 def fused_step_applies(D, p=2, flags=0, sparse=False):

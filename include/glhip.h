@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 138 /* 0.1.38 */
+#define GLHIP_VERSION 139 /* 0.1.39 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
@@ -739,6 +739,40 @@ int glhip_argkmin(const void* x, const void* y, const float* g, int32_t* index, 
                   int B, int N, int M, int D, int k, int p, int in_dtype,
                   const int32_t* ranges_i, const int32_t* slices_i, const int32_t* redranges_j, int n_ranges,
                   void* workspace, size_t workspace_bytes, int flags, void* stream);
+/*
+ * The plan of a p = 2 soft-min contracted with a bilinear per-pair weight (version 139; glhip_plan_bilinear_xk.h) — the one reduction
+ * behind the gradients of `P @ S` and of the barycentric map with respect to the points and the potentials (geomloss_amd/transport.py):
+ *     w_ij   = exp(h_j - |x_i - y_j|^2 / (2 eps) + fwd_i / eps)
+ *     pi_ij  = w_ij / sum_j w_ij                    (normalised by the recomputed mass, as every plan kernel: fwd only centres the weights)
+ *     tau_ij = <rowfeat[b,i,:], colfeat[b,j,:]>
+ *     out[b,i,:] = sum_j pi_ij tau_ij (y_j - x_i)           wsum[b,i] = sum_j pi_ij tau_ij          (wsum may be NULL)
+ *   x (B,N,D), y (B,M,D) fp32 | bf16;  h (B,M), fwd (B,N) fp32;  rowfeat (B,N,K), colfeat (B,M,K) fp32 always;  out (B,N,D), wsum (B,N) fp32.
+ *   Supported: p == 2, dense launches, any B <= 65535, 1 <= D <= 4095, 0 <= K <= 4095.  ONE kernel for the whole range of D.  p = 1,
+ *   block-sparse ranges (the arguments are in the ABI for later), D or K > 4095 and B > 65535 return GLHIP_EUNSUPPORTED.
+ *   The exponents come from the K-chunked matrix-core chain of glhip_softmin_xk.h (GLHIP_FLAG_F16X2 applies to them alone), tau from a second
+ *   run of that chain over the features (uncentred, always bf16 x 3: float32 accuracy, no range contract), and the product w tau — split
+ *   into two f16 pieces relative to a running per-row maximum of its magnitude, so that features of any finite magnitude neither overflow
+ *   nor flush — meets the centred coordinates in the second MFMA product of glhip_plan_apply.h.  One pass over the columns per
+ *   glhip_plan_bilinear_pass_width() coordinates (32; a remainder is a pass of its own); every pass recomputes both chains.
+ *   Accuracy: within 4 x the error of plain float32 arithmetic on the same expression, relative to the unsigned sums
+ *   max_{i,d} sum_j pi_ij |tau_ij| |y_j[d] - x_i[d]| (out) and max_i sum_j pi_ij |tau_ij| (wsum).
+ *   A row without mass (every h_j = -inf; its fwd is +inf) gets 0 in both outputs, never NaN; a column with h_j = -inf weighs exactly 0
+ *   whatever finite colfeat_j it holds.  No float atomics: results are bit-identical run to run.
+ *   N == 0 or B == 0 launches nothing; M == 0 or K == 0 with N > 0 zeroes out and wsum.
+ *   flags: GLHIP_FLAG_NO_SPLIT, GLHIP_FLAG_F16X2 (the caller vouches for the range of the clouds, as everywhere); others are ignored.
+ * glhip_plan_bilinear_workspace_bytes holds the split partials (T[nv], W, mass, m) only and never asks for more than 1 GiB; 0 for
+ * unsupported or empty shapes; NULL or a short buffer means fewer or no splits, with the same results up to summation order.
+ * glhip_plan_bilinear_supported: host arithmetic only, the predicate the launch itself evaluates — 1, 0 for valid requests without a
+ * kernel, GLHIP_EINVAL for what the entry point rejects (negative sizes, D < 1, K < 0, a bad p or dtype).
+ * Not here: gradients with respect to the weights, second derivatives, float64, a resident-operand variant for D <= 16.
+ */
+int glhip_plan_bilinear_supported(int B, long N, long M, int D, int K, int p, int dtype, int n_ranges);
+int glhip_plan_bilinear_pass_width(void);
+size_t glhip_plan_bilinear_workspace_bytes(int B, int N, int M, int D, int K);
+int glhip_plan_bilinear(const void* x, const void* y, const float* h, const float* fwd, const float* rowfeat, const float* colfeat,
+                        float* out, float* wsum, int B, int N, int M, int D, int K, float eps, int p, int in_dtype,
+                        const int32_t* ranges_i, const int32_t* slices_i, const int32_t* redranges_j, int n_ranges,
+                        void* workspace, size_t workspace_bytes, int flags, void* stream);
 /*
  * The cluster pyramid of the two-scale ("multiscale") backends, on the device.
  *
