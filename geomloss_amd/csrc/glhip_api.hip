@@ -48,6 +48,7 @@ static int sorted_inner(const char* fn, const AutoSort& a, const void* x, const 
         sc.l2.groups = static_cast<const GroupBox*>(a.groups);
         sc.l2.home = a.home;
         sc.l2.t2 = a.t2;
+        sc.l2.list_takes = a.list_takes;
         sc.l2.centre_x = x;
         sc.l2.n_groups = (M + 31) / 32;
         sc.l2.L2 = (float)(prune_L(M) * 1.4426950408889634);

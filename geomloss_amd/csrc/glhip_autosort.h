@@ -51,7 +51,8 @@ constexpr int kSortRowsPerVoxel = 256;
 //   lack of a finite bound or because every block passes it — no second level, no cost of it, for such a slab).
 //   The sweep (library 137).  bf16 x 3: softmin_fwd_x32_p2_kernel, 8 wavefronts on one staged 512-column LDS tile, the test per tile
 //   on its 16 groups.  f16 x 2: one of two kernels, chosen per launch on the device from the records of eight reference slabs
-//   (glhip_list_cursor.h, list_takes_launch) — where the first level keeps at most 30 % of the columns, or no slab has a home block,
+//   (glhip_list_cursor.h, list_takes_launch; library 140: once, by list_decide, which writes one int behind `refs` that both sweeps
+//   read) — where the first level keeps at most 30 % of the columns, or no slab has a home block,
 //   softmin_fwd_list_p2_kernel (glhip_softmin_list.h): one wavefront per tile of 32 rows, no LDS tile and no barrier, one test and
 //   one ballot per batch of up to 64 groups of a piece, the kept groups read straight from the group-major packed columns through
 //   a ring of four operands in registers, the lazy maximum with a batch = one ballot; otherwise the staged kernel on 4 wavefronts
@@ -229,6 +230,7 @@ struct AutoSort {
     float* t2 = nullptr;                    // per tile of 32 rows: the second level's mass-rule threshold; per slab: Mlb and the first
     double *mlb = nullptr, *t1 = nullptr;   // level's threshold.  All three live in the sort scratch, dead once both sorts have run,
     int32_t* refs = nullptr;                // and so do the reference blocks of every slab (the sum reference)
+    int32_t* list_takes = nullptr;          // and the one int behind them: which sweep takes the f16 x 2 launch (Level2::list_takes)
     void* inner_ws = nullptr;
     size_t inner_bytes = 0;
 };
@@ -292,13 +294,14 @@ inline int autosort_prepare(AutoSort& a, const void* x, const void* y, int N, in
                       slabs ? 1 : prune_sort_sub(D), a.hint_y);
     if (rc) return rc;
     if (slabs) slab_ranges(N, M, a.ranges_i, a.slices_i, a.red, st);
-    // (the scratch holds 20 bytes per point of the larger cloud and more: N / 8 + (16 + 4 kPruneRefBlocks) C bytes, 0.7 bytes per
+    // (the scratch holds 20 bytes per point of the larger cloud and more: N / 8 + (16 + 4 kPruneRefBlocks) C + 4 bytes, 0.7 bytes per
     // row, fit many times over)
     static_assert(kPruneRefBlocks <= 256, "the reference lists stay under 4 bytes per row");
     a.mlb = reinterpret_cast<double*>(scratch);
     a.t1 = a.mlb + a.C;
     a.t2 = reinterpret_cast<float*>(a.t1 + a.C);
     a.refs = reinterpret_cast<int32_t*>(a.t2 + (N + 31) / 32);
+    a.list_takes = a.refs + (size_t)a.C * kPruneRefBlocks;
     a.inner_ws = w + off;
     a.inner_bytes = workspace_bytes - off;
     a.on = true;

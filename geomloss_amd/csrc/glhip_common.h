@@ -69,7 +69,14 @@ struct Level2 {
     float L2 = 0.f;                     // L of the bound, in log2 units
     const float* t2 = nullptr;          // per tile of 32 sorted rows: the threshold of the mass rule, in log2 units (prune_tiles_kernel); read
                                         // only by slabs with a home block
+    int32_t* list_takes = nullptr;      // f16 x 2: one int, written once per launch (list_decide) and read by both sweeps —
+                                        // nonzero: the list-driven sweep takes the launch, 0: the staged one
 };
+// Which sweep takes the sorted p = 2 launch on the f16 x 2 layout, once per launch (glhip_prune.hip: one wavefront, behind prune_ranges
+// on the same stream): list_takes_launch (glhip_list_cursor.h) on the emitted intervals and home blocks -> *out (Level2::list_takes);
+// keep_pct: the rule's threshold.
+void list_decide(const int32_t* slices_i, const int32_t* red, const int32_t* home, int n_slabs, int M, int keep_pct, int32_t* out,
+                 hipStream_t st);
 
 // One LDS record per column point: D coordinates (already centred / scaled) + one scalar.
 template <int D> struct alignas(16) Rec { float c[4]; };            // D = 2, 3

@@ -143,7 +143,7 @@ void launch_softmin_mfma_nw(const SoftminParams<T>& prm, const Ranges& rg, int n
     // the second pruning level rides on the workgroup shape the sorted launches get (launch_softmin_mfma): f16 x 2 on 4 wavefronts,
     // bf16 x 3 on 8; its kernel carries no leftover tiles (slabs of 256 rows are whole chunks)
     constexpr bool kP2Shape = (L == XL_F16X2) ? NW == 4 : NW == 8;
-    const bool p2 = kP2Shape && n_ranges > 0 && sc.l2.groups && sc.l2.home && sc.l2.centre_x && sc.l2.t2;
+    const bool p2 = kP2Shape && n_ranges > 0 && sc.l2.groups && sc.l2.home && sc.l2.centre_x && sc.l2.t2 && sc.l2.list_takes;
     const int share = (NW == 4 && L == XL_F16X2 && n_ranges > 0 && !p2) ? 1 : 0;
     SplitLaunch sl(rg, n_ranges, B, N, M, kRowsPerBlock, 2, sc.ws, sc.bytes, sc.cb, st, share);
     const SplitPlan plan = plan_x32_fwd(sl, sc.policy(), NW, NR, share && sl.rgc.chunks);
@@ -168,14 +168,18 @@ void launch_softmin_mfma_nw(const SoftminParams<T>& prm, const Ranges& rg, int n
         if constexpr (SP && kP2Shape) {
             if (use_p2) {
                 // f16 x 2: two sweeps back to back on the same grid, and ONE of them does the launch's work (list_takes_launch,
-                // glhip_list_cursor.h: decided on the device from the records, the same in every workgroup) — the list-driven kernel
-                // (glhip_softmin_list.h) where the first level keeps little or no slab has a home block, the staged one otherwise;
-                // the workgroups of the other return at once.  bf16 x 3: the staged kernel alone (the two arguments are not read).
+                // glhip_list_cursor.h: decided on the device from the records, once, by list_decide in front of them) — the list-driven
+                // kernel (glhip_softmin_list.h) where the first level keeps little or no slab has a home block, the staged one
+                // otherwise; the workgroups of the other return on the int it wrote.  bf16 x 3: the staged kernel alone (the int is
+                // not read).
                 // GLHIP_LIST_KEEP: the rule's threshold in percent (tuning knob, read per launch: 100 = always list-driven, 0 = only without home blocks)
-                const char* knob = getenv("GLHIP_LIST_KEEP");
-                const int keep_pct = knob ? atoi(knob) : kListKeepPct;
-                if constexpr (L == XL_F16X2) hipLaunchKernelGGL((softmin_fwd_list_p2_kernel<D, T>), grid, dim3(NW * 64), 0, st, prm, r, N, M, sl.sp, pk, sc.l2, n_ranges, keep_pct);
-                hipLaunchKernelGGL((softmin_fwd_x32_p2_kernel<D, T, NW, L>), grid, dim3(NW * 64), 0, st, prm, r, N, M, sl.sp, pk, sc.l2, n_ranges, keep_pct);
+                if constexpr (L == XL_F16X2) {
+                    const char* knob = getenv("GLHIP_LIST_KEEP");
+                    const int keep_pct = knob ? atoi(knob) : kListKeepPct;
+                    list_decide(r.slices_i, r.redranges_j, sc.l2.home, n_ranges, M, keep_pct, sc.l2.list_takes, st);
+                    hipLaunchKernelGGL((softmin_fwd_list_p2_kernel<D, T>), grid, dim3(NW * 64), 0, st, prm, r, N, M, sl.sp, pk, sc.l2);
+                }
+                hipLaunchKernelGGL((softmin_fwd_x32_p2_kernel<D, T, NW, L>), grid, dim3(NW * 64), 0, st, prm, r, N, M, sl.sp, pk, sc.l2);
                 return;
             }
         }

@@ -55,9 +55,10 @@ GLHIP_LIST_HD inline ListCursor list_next(const int32_t* redranges_j, int q_end,
 }
 
 // Which sweep takes a launch.  The sorted p = 2 launch on the f16 x 2 layout starts two kernels on one grid, the list-driven sweep
-// (glhip_softmin_list.h) and the staged one (glhip_softmin_x32.h, P2); every workgroup of both evaluates this rule on the same
-// records, and all workgroups of the kernel it does not name return at once.  The list-driven sweep reads one operand per wavefront
-// and group through L2, the staged one per workgroup: four times the L2 traffic (measured: profiles/list_sweep.txt).  That pays where
+// (glhip_softmin_list.h) and the staged one (glhip_softmin_x32.h, P2); one wavefront evaluates this rule in front of them
+// (list_decide, glhip_prune.hip), and all workgroups of the kernel it does not name return at once.  The list-driven sweep reads one
+// operand per wavefront and group through L2, the staged one per workgroup: four times the L2 traffic (measured:
+// profiles/list_sweep.txt).  That pays where
 // the staged kernel's per-tile test and barriers buy little — the first level keeps a small share of the columns, and the second
 // keeps half of a tile's groups — and loses where most groups of a tile are kept anyway.  A launch whose slabs have no home block runs
 // no test in either kernel and all its workgroups sweep the columns in one order (L2 hits): the list-driven sweep wins again.

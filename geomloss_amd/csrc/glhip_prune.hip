@@ -9,6 +9,7 @@
 
 #include "glhip_autosort.h"
 #include "glhip_common.h"
+#include "glhip_list_cursor.h"
 #include "glhip_prune_words.h"
 
 using namespace glhip;
@@ -686,9 +687,36 @@ void prune_ranges_typed(const void* xs_, const void* ys_, const float* h, const 
                        t2);
 }
 
+// Which sweep takes the sorted p = 2 launch on the f16 x 2 layout (glhip_list_cursor.h: list_takes_launch on kListRefSlabs reference
+// slabs), once per launch: one wavefront, after prune_slabs_kernel has written the slots and home blocks the rule reads, writes the
+// int that both sweeps read (Level2::list_takes) — the workgroups of the sweep that is not named return on one load, and no working
+// wavefront scans slabs.
+__global__ void __launch_bounds__(64) list_decide_kernel(const int32_t* __restrict__ slices_i, const int32_t* __restrict__ red,
+                                                         const int32_t* __restrict__ home, int n_slabs, int M, int keep_pct,
+                                                         int32_t* __restrict__ out) {
+    const int lane = threadIdx.x;
+    long long kept = 0;
+    bool all_free = true;
+    for (int k = 0; k < kListRefSlabs; ++k) {
+        const int s = list_ref_slab(k, n_slabs);
+        all_free = all_free && home[s] < 0;
+        // the columns of all the intervals of the slab (disjoint intervals of one cloud: at most M, an int)
+        int cols = 0;
+        for (int q = (s == 0 ? 0 : slices_i[s - 1]) + lane; q < slices_i[s]; q += 64) cols += max(red[2 * q + 1] - red[2 * q], 0);
+        for (int off = 32; off > 0; off >>= 1) cols += __shfl_xor(cols, off, 64);
+        kept += cols;
+    }
+    if (lane == 0) *out = list_takes_launch(all_free, kept, (long long)kListRefSlabs * M, keep_pct) ? 1 : 0;
+}
+
 }  // namespace
 
 namespace glhip {
+
+void list_decide(const int32_t* slices_i, const int32_t* red, const int32_t* home, int n_slabs, int M, int keep_pct, int32_t* out,
+                 hipStream_t st) {
+    hipLaunchKernelGGL(list_decide_kernel, dim3(1), dim3(64), 0, st, slices_i, red, home, n_slabs, M, keep_pct, out);
+}
 
 size_t prune_blocks_bytes(int M) { return (size_t)prune_plan(M).nT * sizeof(ColBlock); }
 size_t prune_groups_bytes(int M) { return (size_t)((M + 31) / 32) * sizeof(GroupBox); }

@@ -20,6 +20,7 @@
 //     newer thr keeps: the exactness argument of glhip_softmin_x32.h holds unchanged.
 //   * the order of summation is a function of the records alone: equal bits on a repeated call.
 //   * every group index that forms an address is clamped to [0, n_groups - 1].
+// Which sweep takes the launch is read from Level2::list_takes, written once per launch in front of both sweeps, before anything else.
 // Precondition (the launcher's): pre-packed GROUPED columns, no gathered tiles (SplitInfo::gather == 0).
 #pragma once
 
@@ -59,7 +60,8 @@ __device__ __forceinline__ void list_drain(u32x4& a0, u32x4& a1, u32x4& a2, u32x
 
 template <int D, typename T>
 __global__ void __launch_bounds__(256, 6)
-softmin_fwd_list_p2_kernel(SoftminParams<T> prm, Ranges rg, int N, int M, SplitInfo sp, PackedCols pk, Level2 l2, int n_slabs, int keep_pct) {
+softmin_fwd_list_p2_kernel(SoftminParams<T> prm, Ranges rg, int N, int M, SplitInfo sp, PackedCols pk, Level2 l2) {
+    if (*l2.list_takes == 0) return;      // the staged kernel's launch (the int: list_decide, glhip_prune.hip)
     constexpr int L = XL_F16X2;
     constexpr int kRowsPerBlock = 128;
     int bx, b, split;
@@ -75,7 +77,6 @@ softmin_fwd_list_p2_kernel(SoftminParams<T> prm, Ranges rg, int N, int M, SplitI
     if (row_begin >= row_end) return;
     const int home = l2.home[(rg.chunks && rg.chunks[0] >= 0) ? rg.chunks[1 + 3 * bx] : bx];      // (workgroup-uniform) -1: first level only
     const int glast = l2.n_groups - 1;
-    if (!list_sweep_takes(rg, l2, n_slabs, M, keep_pct, lane)) return;      // the staged kernel's launch
 
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float centre[D];

@@ -787,25 +787,6 @@ softmin_fwd_x32_kernel(SoftminParams<T> prm, Ranges rg, int N, int M, SplitInfo 
     softmin_fwd_x32_body<D, T, SPARSE, RT, NW, PRE, L>(prm, rg, N, M, sp, pk, bx, b, split, tileX);
 }
 
-// the columns of all the intervals of a slab (wave-uniform; every lane of the wavefront takes part)
-__device__ __forceinline__ long long list_slab_columns(const Ranges& rg, int q_begin, int q_end, int lane) {
-    int kept = 0;      // (disjoint intervals of one cloud: at most M, an int)
-    for (int q = q_begin + lane; q < q_end; q += 64) kept += max(rg.redranges_j[2 * q + 1] - rg.redranges_j[2 * q], 0);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) kept += __shfl_xor(kept, off, 64);
-    return __builtin_amdgcn_readfirstlane(kept);
-}
-// list_takes_launch on the launch's reference slabs (launch-uniform: every wavefront of both sweeps computes the same value)
-__device__ __forceinline__ bool list_sweep_takes(const Ranges& rg, const Level2& l2, int n_slabs, int M, int keep_pct, int lane) {
-    long long kept = 0;
-    bool all_free = true;
-    for (int k = 0; k < kListRefSlabs; ++k) {
-        const int s = list_ref_slab(k, n_slabs);
-        all_free = all_free && l2.home[s] < 0;
-        kept += list_slab_columns(rg, s == 0 ? 0 : rg.slices_i[s - 1], rg.slices_i[s], lane);
-    }
-    return list_takes_launch(all_free, kept, (long long)kListRefSlabs * M, keep_pct);
-}
 // the sorted p = 2 launches: block-sparse, pre-packed columns, with the second pruning level (P2 above)
 // Occupancy as without P2: 5 wavefronts per SIMD for the 4-wavefront f16 x 2 kernel (96 VGPRs, no scratch), 6 for the 8-wavefront
 // bf16 x 3 one — three workgroups per CU; at 5 (two workgroups) it measured 101 against 88 ms where nothing prunes.  The bound of 80
@@ -813,14 +794,14 @@ __device__ __forceinline__ bool list_sweep_takes(const Ranges& rg, const Level2&
 // per tile in the test and in the epilogue, never inside the group loops (profiles/r09_kernel_resources.txt).
 template <int D, typename T, int NW, int L>
 __global__ void __launch_bounds__(NW * 64, NW == 4 ? 5 : (NW == 8 ? 6 : 1))
-softmin_fwd_x32_p2_kernel(SoftminParams<T> prm, Ranges rg, int N, int M, SplitInfo sp, PackedCols pk, Level2 l2, int n_slabs, int keep_pct) {
+softmin_fwd_x32_p2_kernel(SoftminParams<T> prm, Ranges rg, int N, int M, SplitInfo sp, PackedCols pk, Level2 l2) {
     __shared__ uint4 tileX[fwd_tile(NW) * X32Layout<L>::NR];
     __shared__ float2 wbox[NW * 4];
+    if constexpr (L == XL_F16X2) {      // launched next to the list-driven sweep (glhip_softmin_list.h): one of the two takes the launch
+        if (*l2.list_takes != 0) return;
+    }
     int bx, b, split;
     workgroup_coords(sp, bx, b, split);
-    if constexpr (L == XL_F16X2) {      // launched next to the list-driven sweep (glhip_softmin_list.h): one of the two takes the launch
-        if (list_sweep_takes(rg, l2, n_slabs, M, keep_pct, threadIdx.x & 63)) return;
-    }
     softmin_fwd_x32_body<D, T, true, 1, NW, true, L, true>(prm, rg, N, M, sp, pk, bx, b, split, tileX, l2, wbox);
 }
 

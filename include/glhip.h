@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 139 /* 0.1.39 */
+#define GLHIP_VERSION 140 /* 0.1.40 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
@@ -171,6 +171,8 @@ extern "C" {
                                   Version 137: on the f16 x 2 layout the sorted launch is swept by a list-driven kernel (one wavefront per
                                   tile of 32 rows, one keep test per 64 groups, operands straight from the packed columns: csrc/
                                   glhip_softmin_list.h).  Same test, same guarantee; the order of summation differs (profiles/list_sweep.txt).
+                                  Version 140: which of the two sweeps takes a launch is decided once per launch, not by every wavefront
+                                  of both.  Same bits as version 137 (profiles/list_pair.txt).
                                   Here this flag means the dense xd / x32 launch. */
 
 /* Environment variables read ONCE per process by the library itself (test / tuning knobs; everything else is an argument):
