@@ -103,6 +103,7 @@ SIGNATURES = {
     "glhip_argmin_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int]),
     "glhip_argmin": (_c_int, [_vp] * 5 + [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int] + _RANGES + _TAIL),
     "glhip_argkmin_max_k": (_c_int, []),
+    "glhip_argkmin_passes": (_c_int, [_c_int]),
     "glhip_argkmin_supported": (_c_int, [_c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int, _c_int]),
     "glhip_argkmin_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "glhip_argkmin": (_c_int, [_vp] * 5 + [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int] + _RANGES + _TAIL),
@@ -131,7 +132,8 @@ _SINCE = {"glhip_sinkhorn_step_perm": 134, "glhip_softmin_perm_applies": 134,
           "glhip_plan_apply_p1": 135,
           "glhip_argkmin_max_k": 138, "glhip_argkmin_supported": 138, "glhip_argkmin_workspace_bytes": 138, "glhip_argkmin": 138,
           "glhip_plan_bilinear_supported": 139, "glhip_plan_bilinear_pass_width": 139, "glhip_plan_bilinear_workspace_bytes": 139,
-          "glhip_plan_bilinear": 139}
+          "glhip_plan_bilinear": 139,
+          "glhip_argkmin_passes": 141}
 
 _lib = None
 

@@ -1,5 +1,6 @@
 // glhip_argkmin_xk.h — the top-k arg-reduction: for every row the k columns of the smallest dual-shifted cost, best first,
 //   index_i[r] = column of the (r+1)-th smallest  c_ij = |x_i - y_j|^2 / 2 - g_j,   value_i[r] = that cost,      0 <= r < k <= kArgkminMaxK,
+// in one pass up to k = kArgkminCap = 16 and in ceil(k / 16) floored passes beyond (below),
 // p = 2, clouds of dimension 1 <= D <= 4095, float32 / bfloat16, dense and batched launches.  KeOps' argKmin / Kmin_argKmin of SqDist
 // (g = 0: k nearest neighbours) and the k heaviest entries of every row of a transport plan (g = dual potential + eps log weight).
 //
@@ -33,7 +34,11 @@
 //      4    (512, 4)         128     0 B      80640 B        4               2           kXkSlots
 //      8    (512, 2)         199     0 B      80640 B        2               1           kXkTopkSlots
 //     16    (512, 2)         256     0 B      80640 B        2               1           kXkTopkSlots
-//   argkmin_merge_kernel<4 / 8 / 16>: 17 / 25 / 56 VGPRs, 0 B of scratch.
+//   floored (k > 16):
+//      4    (512, 4)         128     0 B      80640 B        4               2           kXkSlots
+//      8    (512, 2)         197     0 B      80640 B        2               1           kXkTopkSlots
+//     16    (512, 2)         256     0 B      80640 B        2               1           kXkTopkSlots
+//   argkmin_merge_kernel<4 / 8 / 16>: 18 / 26 / 56 VGPRs, 0 B of scratch.
 // argmin_xk_kernel has 123 VGPRs under (512, 4) with two registers of state per row tile, and the lists are live across the whole
 // stage loop.  CAP = 4 (16 registers) just fits that budget, with the lean select of argkmin_pick and the opaque shuffle address of the
 // half merge; under the same bounds CAP = 6 / 8 spill 40 / 104 bytes per lane (CAP = 16: 440, with the select tree).  So k <= 4 runs like argmin, two workgroups
@@ -43,6 +48,26 @@
 // but less than the alternative, ceil(k / 4) passes of the CAP = 4 kernel with a floor per row (2 / 4 times argmin for k = 8 / 16),
 // wherever the MFMA chain is long enough to matter (D >= 32).  At low D, where staging is everything, the passes would win (D = 3,
 // k = 8: 3.8 x argmin in one pass against 2 x): see DESIGN.md §9.
+//
+// Floored passes (FLOOR; k > 16).  Pass t writes the ranks r0 = 16 t .. r0 + kc - 1 of a row stride k and admits a candidate (u, j) of
+// row i only strictly behind the row's floor (fu, fj) in the order of the lists: u < fu, or u == fu and j > fj.  The floor is the raw
+// (u, index) of the last rank the pass before wrote, one pair of 32-bit words per row at the head of the workspace — never recomputed
+// from `value` — (+inf, -1) before the first pass (argkmin_floor_fill_kernel) and (-inf, INT_MAX) once a rank is missing, so that the
+// later ranks of the row stay (-1, +inf).  u_ij is the same float32 number in every pass: the union of the passes is exact for any k,
+// the first pass returns the bits of the k = 16 call, and a tie group that straddles a pass boundary continues in ascending index order.
+// Full passes run on CAP = 16 (no scratch, as the table says: no need to fall back to ceil(k / 8) passes of CAP = 8), the last one on
+// the smallest capacity that holds the remainder (k = 20 = 16 + 4: at argmin's occupancy).
+//   Where the floor lives: nowhere across the stage loop.  CAP = 16 and CAP = 4 have no register to spare and the workgroup no 2 KiB of
+//   LDS (2 x 80640 B is what lets two CAP = 4 workgroups share a CU).  The fast path is untouched: one max chain, one ballot, one branch.
+//   Only the slow path needs the floor — it ANDs the lexicographic test into the `todo` set next to `> last` and PARTIAL — so it
+//   fetches the lane's pair there with one 8-byte global load (scalar base + lane offset; the rows of a wavefront are one 256-byte
+//   line of the L1 / L2), from a lane id the compiler cannot see through, else the address is hoisted above the tile loop (12 bytes of
+//   scratch per lane at CAP = 4).  The two registers are dead before the push loop.  In passes >= 1 the at most r0 columns a row has
+//   emitted lie ahead of its floor with exponents above its list's last entry: they send their tile through the slow path, where the
+//   test drops them — at most r0 tiles per row.
+//   Who writes the floor: the last merge of a row — this kernel without splits (every row has one workgroup, which has left the tile
+//   loop by then), argkmin_merge_kernel with splits (the main kernel only reads) — so stream order between the passes is all the
+//   synchronisation there is.  The partial of a pass is 2 kc floats per row and split.
 #pragma once
 
 #include "glhip_softmin_xk.h"
@@ -50,7 +75,8 @@
 
 namespace glhip {
 
-constexpr int kArgkminMaxK = 16;       // the largest list: what glhip_argkmin_max_k() reports
+constexpr int kArgkminCap = 16;        // the largest list: the most ranks one pass writes
+constexpr int kArgkminMaxK = 128;      // what glhip_argkmin_max_k() reports: eight floored passes (a larger k is the same loop; the cap bounds the time of a call)
 // wavefronts per SIMD a capacity's registers allow: 4 = two workgroups per CU like argmin (kXkSlots), 2 = one (kXkTopkSlots, glhip_split_policy.h)
 constexpr int argkmin_occ(int cap) { return cap <= 4 ? 4 : 2; }
 
@@ -61,8 +87,14 @@ struct ArgkminParams {
     const float* g;      // (B,M) or NULL (= 0)
     int32_t* index;      // (B,N,k)
     float* value;        // (B,N,k) or NULL
-    int k;               // 1 <= k <= CAP of the launch
+    int k;               // ranks per row of index / value: their row stride (plain kernel: 1 <= k <= CAP, all written by the launch)
+    // a floored pass (FLOOR; see the header) writes the kc <= CAP ranks r0 .. r0 + kc - 1 and admits only what lies behind the row's floor
+    int r0, kc;
+    int32_t* floor;      // (B N, 2): bits of u and index of the last rank the row has been given so far; (+inf, -1) before the first pass
 };
+
+// the floor of a row whose last rank is missing: nothing lies behind it
+constexpr int kArgkminFloorNoneU = (int)0xff800000u, kArgkminFloorNoneI = 0x7fffffff;
 
 // Element e = 16 cg + r of a lane's 2 x 16 exponents of a row tile, e a run-time number: selects over static subscripts.  LEAN: a chain
 // of 31 compares and selects on one register (the kernels with a 128-VGPR budget); else a tree of 31 selects on 16.
@@ -87,8 +119,23 @@ __device__ __forceinline__ float argkmin_pick(const f32x16 (&a)[kXkCG], int e) {
     }
 }
 
-// CAP: entries per list; OCC: wavefronts per SIMD the register budget is set for (4: two workgroups per CU, 2: one)
-template <typename T, int CAP, int OCC>
+// The next pass's floor of a row from the list its last merge wrote ranks r0 .. r0 + kc - 1 from: the raw (u, index) of entry kc - 1, or the
+// floor nothing lies behind where that rank is missing (so every later rank of the row stays missing).
+template <int CAP>
+__device__ __forceinline__ void topk_store_floor(int32_t* floor, const float (&u)[CAP], const int (&i)[CAP], int kc) {
+    float fu = u[0];
+    int fi = i[0];
+#pragma unroll
+    for (int e = 1; e < CAP; ++e) {
+        fu = (e < kc) ? u[e] : fu;
+        fi = (e < kc) ? i[e] : fi;
+    }
+    floor[0] = fi < 0 ? kArgkminFloorNoneU : __float_as_int(fu);
+    floor[1] = fi < 0 ? kArgkminFloorNoneI : fi;
+}
+
+// CAP: entries per list; OCC: wavefronts per SIMD the register budget is set for (4: two workgroups per CU, 2: one); FLOOR: a floored pass
+template <typename T, int CAP, int OCC, bool FLOOR = false>
 __global__ void __launch_bounds__(kXkThreads, OCC)
 argkmin_xk_kernel(ArgkminParams<T> prm, int N, int M, int D, SplitInfo sp) {
     constexpr int L = XL_BF16X3;
@@ -104,6 +151,7 @@ argkmin_xk_kernel(ArgkminParams<T> prm, int N, int M, int D, SplitInfo sp) {
     const int half = lane >> 5, l31 = lane & 31;
     const int ns = sp.n_splits;
     const int k = prm.k;
+    const int r0 = FLOOR ? prm.r0 : 0, kc = FLOOR ? prm.kc : k;      // the ranks this launch writes
     const int NM = xk_num_mfma(D, L), NG = xk_num_groups(D, L);
     const T* xb = prm.x + (long)b * N * D;
     const T* yb = prm.y + (long)b * M * D;
@@ -169,6 +217,20 @@ argkmin_xk_kernel(ArgkminParams<T> prm, int N, int M, int D, SplitInfo sp) {
                         }
                     }
                     if (__ballot(mx > last) == 0) continue;
+                    // the floor of the lane's row, fetched here and dead before the push loop: (fu, column of the floor - column of element 0)
+                    float fu = 0.f;
+                    int fd = 0;
+                    if constexpr (FLOOR) {
+                        // (the row from a thread id the compiler cannot see through: a loop-invariant address would be hoisted above the tile
+                        // loop and live across it, in registers the 128-VGPR kernel does not have; scalar base + 32-bit lane offset)
+                        int t = threadIdx.x;
+                        asm volatile("" : "+v"(t));
+                        const unsigned rowl = (unsigned)min(row0 + ((t >> 7) * kXkRT + rt) * 32 + (t & 31), row_end - 1) - (unsigned)row0;
+                        static_assert(kXkWC == 2 && kXkThreads == 512, "wr = tid >> 7");
+                        const int2 f = reinterpret_cast<const int2*>(prm.floor + 2 * ((long)b * N + row0))[rowl];
+                        fu = __int_as_float(f.x);
+                        fd = f.y - (j0 + lanecol);
+                    }
                     unsigned todo = 0;
 #pragma unroll
                     for (int cg = 0; cg < kXkCG; ++cg) {
@@ -176,6 +238,7 @@ argkmin_xk_kernel(ArgkminParams<T> prm, int N, int M, int D, SplitInfo sp) {
 #pragma unroll
                             for (int r = 0; r < 16; ++r) {
                                 bool take = acc[rt][cg][r] > last;
+                                if (FLOOR) take = take && (acc[rt][cg][r] < fu || (acc[rt][cg][r] == fu && cg * 32 + 8 * (r / 4) + (r % 4) > fd));
                                 if (PARTIAL) take = take && lds.idx[kXkRows + lanecol + cg * 32 + 8 * (r / 4) + (r % 4)] >= 0;
                                 todo |= take ? (1u << (cg * 16 + r)) : 0u;
                             }
@@ -252,49 +315,61 @@ argkmin_xk_kernel(ArgkminParams<T> prm, int N, int M, int D, SplitInfo sp) {
             if (ns == 1) {
 #pragma unroll
                 for (int e = 0; e < CAP; ++e) {
-                    if (e < k) {
-                        prm.index[row * k + e] = i[e];
-                        if (prm.value) prm.value[row * k + e] = hn - u[e];
+                    if (e < kc) {
+                        prm.index[row * k + r0 + e] = i[e];
+                        if (prm.value) prm.value[row * k + r0 + e] = hn - u[e];
                     }
                 }
+                if constexpr (FLOOR) topk_store_floor<CAP>(prm.floor + 2 * row, u, i, kc);
             } else {
-                float* dst = sp.workspace + split * sp.split_stride + row * (2 * k);
+                float* dst = sp.workspace + split * sp.split_stride + row * (2 * kc);
 #pragma unroll
                 for (int e = 0; e < CAP; ++e) {
-                    if (e < k) {
+                    if (e < kc) {
                         dst[2 * e] = u[e];
                         reinterpret_cast<int*>(dst)[2 * e + 1] = i[e];
                     }
                 }
-                if (split == 0 && prm.value) prm.value[row * k] = hn;      // |xt_i|^2 / 2 is the same in every split: the merge subtracts the exponents
+                if (split == 0 && prm.value) prm.value[row * k + r0] = hn;      // |xt_i|^2 / 2 is the same in every split: the merge subtracts the exponents
             }
         }
     }
 }
 
-// Combines the column splits of every row: one thread per row over the k (u, index) partials of every split, in split order.
+// Combines the column splits of every row: one thread per row over the kc (u, index) partials of every split, in split order; writes
+// the ranks r0 .. r0 + kc - 1 of the row's k and, for a floored pass (floor != NULL), the row's next floor.
 template <int CAP>
 __global__ void __launch_bounds__(kBlock)
-argkmin_merge_kernel(int32_t* __restrict__ index, float* __restrict__ value, long rows, int k, SplitInfo sp) {
+argkmin_merge_kernel(int32_t* __restrict__ index, float* __restrict__ value, long rows, int k, int r0, int kc, int32_t* __restrict__ floor,
+                     SplitInfo sp) {
     const long row = (long)blockIdx.x * kBlock + threadIdx.x;
     if (row >= rows) return;
     float u[CAP];
     int i[CAP];
     topk_clear<CAP>(u, i);
     for (int s = 0; s < sp.n_splits; ++s) {
-        const float* src = sp.workspace + s * sp.split_stride + row * (2 * k);
+        const float* src = sp.workspace + s * sp.split_stride + row * (2 * kc);
 #pragma unroll
         for (int e = 0; e < CAP; ++e)
-            if (e < k) topk_insert_lex<CAP>(u, i, src[2 * e], reinterpret_cast<const int*>(src)[2 * e + 1]);
+            if (e < kc) topk_insert_lex<CAP>(u, i, src[2 * e], reinterpret_cast<const int*>(src)[2 * e + 1]);
     }
-    const float hn = value ? value[row * k] : 0.f;
+    const float hn = value ? value[row * k + r0] : 0.f;
 #pragma unroll
     for (int e = 0; e < CAP; ++e) {
-        if (e < k) {
-            index[row * k + e] = i[e];
-            if (value) value[row * k + e] = hn - u[e];
+        if (e < kc) {
+            index[row * k + r0 + e] = i[e];
+            if (value) value[row * k + r0 + e] = hn - u[e];
         }
     }
+    if (floor) topk_store_floor<CAP>(floor + 2 * row, u, i, kc);
+}
+
+// (+inf, -1) for every row: what the first pass of a k > kArgkminCap call runs behind, everything
+__global__ void __launch_bounds__(kBlock) argkmin_floor_fill_kernel(int32_t* __restrict__ floor, long rows) {
+    const long row = (long)blockIdx.x * kBlock + threadIdx.x;
+    if (row >= rows) return;
+    floor[2 * row] = 0x7f800000;
+    floor[2 * row + 1] = -1;
 }
 
 }  // namespace glhip

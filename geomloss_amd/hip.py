@@ -1764,9 +1764,16 @@ def argmin(x, y, g=None, return_value=False, flags=0, p=2):
 def argkmin_supported(B, N, M, D, k, p=2, dtype=F32, n_ranges=0):
     """Whether ``glhip_argkmin`` serves a launch of this shape (p = 2, dense, 1 <= D <= ARGMIN_MAX_DIM, 1 <= k <= ARGKMIN_MAX_K, fp32 /
     bf16 clouds): the predicate the launch itself evaluates (``glhip_argkmin_supported``), host arithmetic only — no device is touched.
+    ARGKMIN_MAX_K is the library's ``glhip_argkmin_max_k()``: 128, of which k > 16 runs in :func:`argkmin_passes` passes.
     Raises ``ValueError`` for what the entry point rejects (negative sizes, D < 1, k < 1, a bad p or dtype)."""
     return bool(_route_predicate("glhip_argkmin_supported", (B, N, M, D, k, p, dtype, n_ranges),
                                  f"B {B}, N {N}, M {M}, D {D}, k {k}, p {p}, dtype {dtype}, n_ranges {n_ranges}"))
+
+
+def argkmin_passes(k):
+    """Passes of the list kernel a ``glhip_argkmin`` launch with this ``k`` runs (``glhip_argkmin_passes``, host arithmetic only): 1 for
+    k <= 16, else ceil(k / 16) — each pass costs about one k <= 16 call.  ``ValueError`` for k < 1 or k > ARGKMIN_MAX_K."""
+    return _route_predicate("glhip_argkmin_passes", (k,), f"k {k}")
 
 
 def argkmin(x, y, k, g=None, return_value=False, flags=0, p=2):
@@ -1777,7 +1784,9 @@ def argkmin(x, y, k, g=None, return_value=False, flags=0, p=2):
     x: (N,D)|(B,N,D), y: (M,D)|(B,M,D), g: (M,)|(B,M)|None -> int32 (N,k)|(B,N,k); with ``return_value`` also the fp32 costs.
     Entries are sorted by (cost ascending, index ascending) on the kernel's float32 exponents: the first k' < k columns are what a call
     with k' returns, ``k = 1`` is :func:`argmin`, bit for bit both, whatever the launch.  ``g_j = -inf`` excludes column j; ranks a row
-    has no admissible column for (M < k, masks, M = 0) get index -1 and value +inf.  Not recorded by autograd.  float64 clouds, p != 2,
+    has no admissible column for (M < k, masks, M = 0) get index -1 and value +inf.  k > 16 runs ceil(k / 16) passes of the same kernel
+    (:func:`argkmin_passes`), each behind the last entry of the one before: the same statements hold for every k up to
+    ARGKMIN_MAX_K = 128, at about one k = 16 call per pass.  Not recorded by autograd.  float64 clouds, p != 2,
     D > ARGMIN_MAX_DIM = 4095 and k > ARGKMIN_MAX_K raise ``NotImplementedError``, k < 1 ``ValueError``; block-sparse ranges and p = 1
     are out of scope."""
     if x.dtype == torch.float64 or y.dtype == torch.float64:

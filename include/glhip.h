@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 140 /* 0.1.40 */
+#define GLHIP_VERSION 141 /* 0.1.41 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
@@ -714,7 +714,8 @@ int glhip_argmin(const void* x, const void* y, const float* g, int32_t* index, f
  * distance is 2 value), and the k heaviest entries of every row of a transport plan with g = dual potential + eps log weight, what a
  * user of the reference extracts from `ot.solve_sample(...).lazy_plan` (ot/_implementations/sample.py:562-617).
  *   x (B,N,D), y (B,M,D) fp32 | bf16;  g (B,M) fp32 or NULL (= 0);  index (B,N,k) int32;  value (B,N,k) fp32 or NULL.
- *   Supported: p == 2, 1 <= D <= 4095, dense launches (n_ranges == 0), any B <= 65535, 1 <= k <= glhip_argkmin_max_k() (16); p = 1,
+ *   Supported: p == 2, 1 <= D <= 4095, dense launches (n_ranges == 0), any B <= 65535, 1 <= k <= glhip_argkmin_max_k() (128 from
+ *   version 141, 16 before); p = 1,
  *   D > 4095, a larger k and block-sparse ranges return GLHIP_EUNSUPPORTED (the range arguments are there so that block-sparse launches
  *   can follow without an ABI change); k < 1 is GLHIP_EINVAL.
  *   The kernel is argmin's — staging, MFMA chain and exponents u_ij of glhip_softmin_xk.h, bit for bit — with another epilogue: every
@@ -731,10 +732,21 @@ int glhip_argmin(const void* x, const void* y, const float* g, int32_t* index, f
  *   flags: GLHIP_FLAG_NO_SPLIT; GLHIP_FLAG_F16X2 is accepted and ignored (bf16 x 3 only: no range precondition); others are ignored.
  *   Workspace: glhip_argkmin_workspace_bytes (<= 1 GiB) holds the k (exponent, index) partials per row of the column splits the launch
  *   would like; NULL or short means fewer or no splits, with the same results.
+ *   k > 16 (version 141) runs glhip_argkmin_passes(k) = ceil(k / 16) passes of the same kernel, each behind a floor: pass t writes the
+ *   ranks 16 t .. and admits only the columns strictly behind the last entry (u, index) of pass t - 1 in the order above, which it reads
+ *   raw from a buffer of one (u, index) pair per row — exact for any k, and every statement above holds (prefixes, splits, duplicates in
+ *   ascending index order across the pass boundaries, missing ranks).  Passes of 16 ranks use the list of 16, the last one the smallest
+ *   list (4 / 8 / 16) that holds the remainder.  For these calls the workspace is REQUIRED: its head holds the floors, B N pairs of 32-bit
+ *   words rounded up to 256 bytes, and must be 8-byte aligned; glhip_argkmin_workspace_bytes is that plus the largest split area
+ *   (<= 1 GiB) of the passes.  Without at least the head the call returns GLHIP_EINVAL; with the head alone, or under
+ *   GLHIP_FLAG_NO_SPLIT, the passes run unsplit with the same results.  k <= 16 is unchanged: one pass, the sizes and results of 138.
+ * glhip_argkmin_passes (version 141): host arithmetic only — 1 for k <= 16, else the passes the launch runs; GLHIP_EINVAL for k < 1 or
+ * k > glhip_argkmin_max_k().
  * glhip_argkmin_supported: host arithmetic only, the predicate the launch itself evaluates — 1 / 0, GLHIP_EINVAL for what the entry
  * point rejects (negative sizes, D < 1, k < 1, a bad p or dtype).
  */
 int glhip_argkmin_max_k(void);
+int glhip_argkmin_passes(int k);
 int glhip_argkmin_supported(int B, long N, long M, int D, int k, int p, int dtype, int n_ranges);
 size_t glhip_argkmin_workspace_bytes(int B, int N, int M, int D, int k);
 int glhip_argkmin(const void* x, const void* y, const float* g, int32_t* index, float* value,

@@ -15,6 +15,10 @@ evaluation of the same costs.
 Part 2 — one low-dimension line, N = M = --low-n, D = --low-d, k = --low-k: argmin, argkmin, and the torch route timed on ONE chunk of
 rows and scaled to all of them (the line says so).
 
+k > 16 runs in ``hip.argkmin_passes(k)`` floored passes of the k <= 16 kernel (``--ks 16 20 32 64 --low-k 32``): where k = 16 is among the
+timed launches, every larger k is also shown against passes x the k = 16 time of the same shape, what the passes would cost if the floor
+were free; part 2 then times k = 16 as well.
+
 No ratio is asserted: the figures are printed."""
 import argparse
 import os
@@ -40,6 +44,14 @@ def line(D, name, ms, pairs, scale=1.0):
     med, lo = statistics.median(ms), min(ms)
     print(f"  {D:4d} {name:40s} {med:10.3f} {lo:10.3f} {(max(ms) - lo) / med:7.1%} {pairs / (med * 1e-3):10.3e}", flush=True)
     return med, (max(ms) - lo)
+
+
+def print_passes(D, res, ks):
+    """Every k > 16 against passes x the k = 16 launch of the same shape."""
+    if 16 in ks and max(ks) > 16:
+        base = res["glhip_argkmin k = 16"][0]
+        print(f"  {D:4d} argkmin / (passes x argkmin k = 16): " + ", ".join(
+            f"k = {k} ({hip.argkmin_passes(k)} passes): {res[f'glhip_argkmin k = {k}'][0] / (hip.argkmin_passes(k) * base):.3f}" for k in ks if k > 16), flush=True)
 
 
 def chunk_rows(M, mem_gib):
@@ -117,6 +129,7 @@ def main():
         ratios = ", ".join(f"k = {k}: {res[f'glhip_argkmin k = {k}'][0] / base:.3f}" for k in args.ks)
         print(f"  {D:4d} argkmin / argmin: {ratios}; first 256 rows of k = {kt} against float64: {wrong} rows differ, largest cost excess {excess:.2e}",
               flush=True)
+        print_passes(D, res, args.ks)
         if ms[tname]:
             tm, ts = line(D, tname, ms[tname], float(n) * n)
             km, ks_ = res[f"glhip_argkmin k = {kt}"]
@@ -134,6 +147,8 @@ def main():
         x, y = torch.rand(N, D, generator=g).to(dev), torch.rand(N, D, generator=g).to(dev)
         launches = [("glhip_argmin", lambda: hip.argmin(x, y, None, return_value=True)),
                     (f"glhip_argkmin k = {k}", lambda: hip.argkmin(x, y, k, return_value=True))]
+        if k > 16:
+            launches.insert(1, ("glhip_argkmin k = 16", lambda: hip.argkmin(x, y, 16, return_value=True)))
         wrong, excess = check(x, y, k, rows=64)
         for _ in range(args.warmup):
             for _, fn in launches:
@@ -151,6 +166,7 @@ def main():
         km, ks_ = res[f"glhip_argkmin k = {k}"]
         print(f"  {D:4d} argkmin / argmin: k = {k}: {km / res['glhip_argmin'][0]:.3f}; first 64 rows against float64: {wrong} rows differ, "
               f"largest cost excess {excess:.2e}", flush=True)
+        print_passes(D, res, [16, k] if k > 16 else [k])
         if tms:
             tm, ts = line(D, f"torch cdist + topk({k}), one chunk, scaled", tms, float(N) * N, scale=N / chunk)
             verdict = "argkmin is faster by more than both spreads" if tm - km > ts + ks_ else "argkmin is NOT faster by more than the spreads"
