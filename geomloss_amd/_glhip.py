@@ -22,6 +22,7 @@ FLAG_XK_DIST = 2048             # p = 1 soft-min / half-step, laplacian and ener
 FLAG_XK_DIST_GRAD = 4096        # the p = 1 soft-min, laplacian and energy row gradients of 17 <= D <= 4095, dense launches, on the matrix cores
                                 # (glhip_dist_grad_xk.h); glhip_kernel_conv_fwd_grad takes those kinds under it
 DIST_GRAD_OPS = {"softmin_p1": 0, "laplacian": 1, "energy": 2}      # ops of glhip_dist_grad_uses_xk (GLHIP_DIST_GRAD_*)
+FLAG_XD_ARG = 8192              # argmin / argkmin of p = 2, D <= 16, dense launches: the resident-operand kernels (glhip_arg_xd.h)
 FLAG_GRAD_FAMILY = FLAG_XDL16   # kernel products rounded like the product-and-gradient kernel of the same kind (glhip.h)
 XD_MAX_DIM = 16                 # the fused four-softmin iteration / annealing / extrapolation, the one-pass value + gradient and the matrix-core
                                 # gradients stop at this dimension (glhip_softmin_xd.h, glhip_wsum_t32.h)
@@ -107,6 +108,8 @@ SIGNATURES = {
     "glhip_argkmin_supported": (_c_int, [_c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int, _c_int]),
     "glhip_argkmin_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "glhip_argkmin": (_c_int, [_vp] * 5 + [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int] + _RANGES + _TAIL),
+    "glhip_arg_family": (_c_int, [_c_int, _c_long, _c_long] + [_c_int] * 6),
+    "glhip_arg_xd_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "glhip_cluster_workspace_bytes": (_c_size, [_c_int, _c_int]),
     "glhip_grid_cluster": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_float, _c_float] + [_vp] * 7 + [_vp, _c_size, _vp]),
     "glhip_block_ranges": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float] + [_vp] * 6
@@ -133,7 +136,7 @@ _SINCE = {"glhip_sinkhorn_step_perm": 134, "glhip_softmin_perm_applies": 134,
           "glhip_argkmin_max_k": 138, "glhip_argkmin_supported": 138, "glhip_argkmin_workspace_bytes": 138, "glhip_argkmin": 138,
           "glhip_plan_bilinear_supported": 139, "glhip_plan_bilinear_pass_width": 139, "glhip_plan_bilinear_workspace_bytes": 139,
           "glhip_plan_bilinear": 139,
-          "glhip_argkmin_passes": 141}
+          "glhip_argkmin_passes": 141, "glhip_arg_family": 142, "glhip_arg_xd_workspace_bytes": 142}
 
 _lib = None
 

@@ -90,7 +90,7 @@ def kmeans_update(x, labels, centroids, weights=None):
         return new
 
 
-def kmeans(x, K, n_iter=10, init=None, weights=None, generator=None):
+def kmeans(x, K, n_iter=10, init=None, weights=None, generator=None, resident=None):
     """Lloyd's K-means on a GPU cloud, the reference's recipe for cluster labels in dimension D > 3
     (``examples/sinkhorn_multiscale/plot_optimal_transport_cluster.py:154-187``, a KeOps ``generic_argmin`` loop): ``n_iter`` times,
     assign every point to its nearest centroid (:func:`geomloss_amd.hip.argmin`, on the matrix cores, nothing of size N x K is
@@ -104,7 +104,8 @@ def kmeans(x, K, n_iter=10, init=None, weights=None, generator=None):
     from these centroids.  ``weights`` (N,): weighted means.  ``n_iter=0`` only assigns.
     Differences with the tutorial: the centroid update is deterministic (sorted segment sums in float64 instead of
     ``bincount(weights=)`` float atomics: two runs are bit-identical), ties between centroids go to the smallest index, and a
-    cluster that receives no point keeps its previous centroid where the tutorial's 0 / 0 gives NaN.  Not recorded by autograd."""
+    cluster that receives no point keeps its previous centroid where the tutorial's 0 / 0 gives NaN.  Not recorded by autograd.
+    ``resident``: passed to the arg-reduction (``True``: the resident-operand kernels of D <= 16, ``None``: GEOMLOSS_HIP_XD_ARG)."""
     from . import hip
     with torch.no_grad():
         x = x.detach()
@@ -126,21 +127,22 @@ def kmeans(x, K, n_iter=10, init=None, weights=None, generator=None):
             raise ValueError(f"geomloss_amd.kmeans: expected {N} weights, got {w.shape[0]}")
         labels = None
         for _ in range(int(n_iter)):
-            labels = hip.argmin(x, c)
+            labels = hip.argmin(x, c, **hip.resident_kw(resident))
             c = kmeans_update(x, labels, c, w)
         if labels is None:
-            labels = hip.argmin(x, c)
+            labels = hip.argmin(x, c, **hip.resident_kw(resident))
         return labels.int(), c
 
 
-def knn(x, y, k):
+def knn(x, y, k, resident=None):
     """The ``k`` nearest points of ``y`` for every point of ``x``: ``(index, sqdist)``, int32 and fp32 (N,k)|(B,N,k), nearest first —
     KeOps' ``Kmin_argKmin(k, dim=1)`` of ``SqDist(x, y)``, on the matrix cores (:func:`geomloss_amd.hip.argkmin`): nothing of size
     N x M is stored.  x (N,D)|(B,N,D), y (M,D)|(B,M,D) fp32 | bf16 on a GPU, 1 <= D <= 4095, 1 <= k <= ``hip.ARGKMIN_MAX_K``.
     ``sqdist`` is the kernel's float32 ``|x_i - y_j|^2`` (twice its half-squared cost, an exact doubling); equal distances come in
-    ascending index order; with fewer than k points in ``y`` the last ranks are (-1, +inf).  Not recorded by autograd."""
+    ascending index order; with fewer than k points in ``y`` the last ranks are (-1, +inf).  Not recorded by autograd.
+    ``resident``: passed to the arg-reduction (``True``: the resident-operand kernels of D <= 16, ``None``: GEOMLOSS_HIP_XD_ARG)."""
     from . import hip
-    index, value = hip.argkmin(x, y, k, return_value=True)
+    index, value = hip.argkmin(x, y, k, return_value=True, **hip.resident_kw(resident))
     return index, 2.0 * value
 
 

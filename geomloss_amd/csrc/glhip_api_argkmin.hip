@@ -112,6 +112,8 @@ int glhip_argkmin(const void* x, const void* y, const float* g, int32_t* index, 
                     kArgkminMaxK, p, D, k, n_ranges);
     if (B == 0 || N == 0) return GLHIP_OK;   // nothing to write
     if (!index) return fail(GLHIP_EINVAL, "glhip_argkmin: NULL index");
+    if (arg_family(B, N, M, D, k, p, in_dtype, n_ranges, flags) == GLHIP_FAMILY_XD)      // GLHIP_FLAG_XD_ARG: resident operands (glhip_arg_xd.h)
+        return arg_xd_launch("glhip_argkmin", x, y, g, index, value, B, N, M, D, k, in_dtype, workspace, workspace_bytes, flags, stream);
     hipStream_t st = static_cast<hipStream_t>(stream);
     // k > kArgkminCap: the floors of the passes live at the head of the workspace, whatever the flags; the splits take what follows
     int32_t* floor = nullptr;

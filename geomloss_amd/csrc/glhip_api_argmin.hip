@@ -57,6 +57,8 @@ int glhip_argmin(const void* x, const void* y, const float* g, int32_t* index, f
         return fail(GLHIP_EUNSUPPORTED, "glhip_argmin: only p = 2, D <= %d, dense launches (got p %d, D %d, n_ranges %d)", kXkMaxD, p, D, n_ranges);
     if (B == 0 || N == 0) return GLHIP_OK;   // nothing to write
     if (!index) return fail(GLHIP_EINVAL, "glhip_argmin: NULL index");
+    if (arg_family(B, N, M, D, 1, p, in_dtype, n_ranges, flags) == GLHIP_FAMILY_XD)      // GLHIP_FLAG_XD_ARG: resident operands (glhip_arg_xd.h)
+        return arg_xd_launch("glhip_argmin", x, y, g, index, value, B, N, M, D, 1, in_dtype, workspace, workspace_bytes, flags, stream);
     hipStream_t st = static_cast<hipStream_t>(stream);
     // GLHIP_FLAG_F16X2 is accepted and ignored: the kernel has the bf16 x 3 layout only.  M == 0 runs the kernel over no tile: index -1, value +inf.
     const Scratch sc = make_scratch(workspace, workspace_bytes, flags, 0, N);

@@ -365,7 +365,7 @@ argkmin_merge_kernel(int32_t* __restrict__ index, float* __restrict__ value, lon
 }
 
 // (+inf, -1) for every row: what the first pass of a k > kArgkminCap call runs behind, everything
-__global__ void __launch_bounds__(kBlock) argkmin_floor_fill_kernel(int32_t* __restrict__ floor, long rows) {
+static __global__ void __launch_bounds__(kBlock) argkmin_floor_fill_kernel(int32_t* __restrict__ floor, long rows) {
     const long row = (long)blockIdx.x * kBlock + threadIdx.x;
     if (row >= rows) return;
     floor[2 * row] = 0x7f800000;

@@ -102,6 +102,20 @@ inline int conv_family(int kind, int mode, int B, int D, int flags, int n_ranges
     return (D <= kXdMaxD && mfma) ? GLHIP_FAMILY_XD : none;
 }
 
+// ... and of an arg-reduction: THE predicate of glhip_argmin (k = 1) and glhip_argkmin, and what glhip_arg_family reports.
+// GLHIP_FAMILY_XD: the resident-operand kernels of glhip_arg_xd.h, on the caller's word (GLHIP_FLAG_XD_ARG); GLHIP_FAMILY_XK: the
+// K-chunked ones of glhip_argmin_xk.h / glhip_argkmin_xk.h, every other launch they serve.
+constexpr int kArgMaxK = 128;      // = kArgkminMaxK (glhip_argkmin_xk.h; asserted in glhip_api_arg_xd.hip)
+inline int arg_family(int B, long N, long M, int D, int k, int p, int dtype, int n_ranges, int flags) {
+    if (plan_family_bad_args(B, N, M, D, dtype, n_ranges) || (p != 1 && p != 2) || k < 1) return GLHIP_EINVAL;
+    if (p != 2 || n_ranges != 0 || D > kSizedMaxD || B > 65535 || k > kArgMaxK) return GLHIP_EUNSUPPORTED;
+    return ((flags & GLHIP_FLAG_XD_ARG) && D <= kXdMaxD) ? GLHIP_FAMILY_XD : GLHIP_FAMILY_XK;
+}
+// The launch of GLHIP_FAMILY_XD (glhip_api_arg_xd.hip): glhip_argmin (k = 1, index / value of (B,N)) and glhip_argkmin hand their checked
+// arguments over; `fn` names the entry point in messages.  Returns a GLHIP_* code.
+int arg_xd_launch(const char* fn, const void* x, const void* y, const float* g, int32_t* index, float* value, int B, int N, int M, int D, int k,
+                  int in_dtype, void* workspace, size_t workspace_bytes, int flags, void* stream);
+
 // the op of a laplacian / energy gradient (glhip_dist_grad_uses_xk, dist_grad_xk_launch) is its kind
 static_assert(GLHIP_DIST_GRAD_LAPLACIAN == GLHIP_LAPLACIAN && GLHIP_DIST_GRAD_ENERGY == GLHIP_ENERGY, "include/glhip.h");
 

@@ -39,17 +39,19 @@
 
 namespace glhip {
 
-enum XdMode { XD_SOFTMIN = 0, XD_GAUSS = 1 };
+enum XdMode { XD_SOFTMIN = 0, XD_GAUSS = 1, XD_ARG = 2 };
 
 // One column as NBP records `stride` apart starting at `base`; coordinates relative to `centre`.
 //   XD_SOFTMIN: H = log2(e) h_j - s/2 |yt|^2  (h_j through dual_entry: the fused half-step adds pot_j / eps)
 //   XD_GAUSS:   H = -s/2 |yt|^2, and the weight v_j = prm.h[col] goes to *vdst
+//   XD_ARG:     H = g_j - |yt|^2 / 2 with g = prm.h (NULL: 0), no scale (glhip_arg_xd.h); g_j = -inf stays -inf, and a padded column
+//               is -inf too: its exponent never beats anything
 template <int MODE, int D, typename T, int L = XL_BF16X3>
 __device__ __forceinline__ void pack_column_xd(const SoftminParams<T>& prm, long col, bool valid, const float (&centre)[D],
                                                uint4* base, int stride, float* vdst) {
     using S = XdShape<D, L>;
     float yt[D];
-    float H = kNegBig, vj = 0.f;
+    float H = (MODE == XD_ARG) ? -__builtin_inff() : kNegBig, vj = 0.f;
 #pragma unroll
     for (int d = 0; d < D; ++d) yt[d] = 0.f;
     if (valid) {
@@ -63,6 +65,8 @@ __device__ __forceinline__ void pack_column_xd(const SoftminParams<T>& prm, long
         }
         if (MODE == XD_SOFTMIN) {
             H = __builtin_fmaf(-0.5f * prm.s2, n2, dual_entry(prm, col) * kLog2e);
+        } else if (MODE == XD_ARG) {
+            H = __builtin_fmaf(-0.5f, n2, prm.h ? prm.h[col] : 0.f);
         } else {
             H = -0.5f * prm.s2 * n2;
             vj = prm.h[col];

@@ -1716,6 +1716,35 @@ def cmin(x, y, g, p=2, ranges=None, flags=0):
     return out if batched else out.view(-1)
 
 
+# GEOMLOSS_HIP_XD_ARG: what ``resident=None`` of :func:`argmin` / :func:`argkmin` means, read once per process (default 0: the K-chunked
+# kernels; 1: the resident-operand kernels of glhip_arg_xd.h wherever they apply, D <= XD_MAX_DIM)
+_XD_ARG_DEFAULT = os.environ.get("GEOMLOSS_HIP_XD_ARG", "0") != "0"
+
+
+def _resident(name, resident, D):
+    """FLAG_XD_ARG or 0 for a call of ``name`` in dimension D: ``True`` asks for the resident-operand kernels (``NotImplementedError``
+    beyond D = XD_MAX_DIM), ``False`` never sets the flag, ``None`` follows GEOMLOSS_HIP_XD_ARG where they apply."""
+    if resident is None:
+        return FLAG_XD_ARG if (_XD_ARG_DEFAULT and D <= XD_MAX_DIM) else 0
+    if resident and D > XD_MAX_DIM:
+        raise NotImplementedError(f"geomloss_amd.hip.{name}: resident=True serves D <= {XD_MAX_DIM} (got D = {D})")
+    return FLAG_XD_ARG if resident else 0
+
+
+def resident_kw(resident):
+    """The keyword a caller of :func:`argmin` / :func:`argkmin` hands its own ``resident=`` on with: nothing for ``None``, so that the
+    call reads as it did before the keyword existed."""
+    return {} if resident is None else {"resident": resident}
+
+
+def _arg_scratch(lib, flags, sized, B, N, M, D, k, device):
+    """The scratch of an arg-reduction: ``glhip_arg_xd_workspace_bytes`` under FLAG_XD_ARG (ENV_FLAGS may set it too: the library's own
+    predicate decides), else what the entry point's own sizing call says."""
+    if flags & FLAG_XD_ARG and lib.glhip_arg_family(B, N, M, D, k, 2, F32, 0, flags) == FAMILY_XD:
+        return _scratch(int(lib.glhip_arg_xd_workspace_bytes(B, N, M, D, k)), device)
+    return _scratch(int(sized()), device)
+
+
 def argmin_supported(B, N, M, D, p=2, dtype=F32, n_ranges=0):
     """Whether ``glhip_argmin`` serves a launch of this shape (p = 2, dense, 1 <= D <= ARGMIN_MAX_DIM, fp32 / bf16 clouds): the
     predicate the launch itself evaluates (``glhip_argmin_supported``), host arithmetic only — no device is touched.  Raises
@@ -1724,17 +1753,20 @@ def argmin_supported(B, N, M, D, p=2, dtype=F32, n_ranges=0):
                                  f"B {B}, N {N}, M {M}, D {D}, p {p}, dtype {dtype}, n_ranges {n_ranges}"))
 
 
-def argmin(x, y, g=None, return_value=False, flags=0, p=2):
+def argmin(x, y, g=None, return_value=False, flags=0, p=2, resident=None):
     """Arg-reduction on the matrix cores (``glhip_argmin``): ``argmin_j [|x_i - y_j|^2 / 2 - g_j]`` — the nearest column for
     ``g = None``, what KeOps' ``generic_argmin("SqDist(x,y)", ...)`` returns in the reference's K-means recipe; the column a plan row
     sends most of its mass to for g = dual potential + eps log weight.
     x: (N,D)|(B,N,D), y: (M,D)|(B,M,D), g: (M,)|(B,M)|None -> int32 (N,)|(B,N); with ``return_value`` also the fp32 minima.
     Ties go to the smallest index; ``g_j = -inf`` excludes column j; a row without an admissible column (M = 0, every g = -inf) gets
     index -1 and value +inf.  Not recorded by autograd.  float64 clouds, p != 2 and D > ARGMIN_MAX_DIM = 4095 raise
-    ``NotImplementedError``; block-sparse ranges and p = 1 are out of scope; k > 1 neighbours: :func:`argkmin`."""
+    ``NotImplementedError``; block-sparse ranges and p = 1 are out of scope; k > 1 neighbours: :func:`argkmin`.
+    ``resident=True`` (FLAG_XD_ARG, D <= 16 only) runs the resident-operand kernels of glhip_arg_xd.h: both clouds packed once, same
+    semantics, values within rounding of the default route; ``False`` never does; ``None`` follows GEOMLOSS_HIP_XD_ARG (default 0)."""
     if x.dtype == torch.float64 or y.dtype == torch.float64:
         raise NotImplementedError("geomloss_amd.hip.argmin: float64 clouds are not supported (cast to float32)")
     D = x.shape[-1]
+    flags = int(flags) | _resident("argmin", resident, D)
     if p != 2 or D > ARGMIN_MAX_DIM:
         raise NotImplementedError(f"geomloss_amd.hip.argmin: only p = 2, D <= {ARGMIN_MAX_DIM} (got p = {p}, D = {D})")
     lib = load_library()
@@ -1751,9 +1783,10 @@ def argmin(x, y, g=None, return_value=False, flags=0, p=2):
         index = torch.empty((B, N), dtype=torch.int32, device=xb.device)
         value = torch.empty((B, N), dtype=torch.float32, device=xb.device) if return_value else None
         with torch.cuda.device(xb.device):
-            ws, ws_args = _scratch(int(lib.glhip_argmin_workspace_bytes(B, N, M, D)), xb.device)
+            flags |= ENV_FLAGS
+            ws, ws_args = _arg_scratch(lib, flags, lambda: lib.glhip_argmin_workspace_bytes(B, N, M, D), B, N, M, D, 1, xb.device)
             rc = lib.glhip_argmin(xb.data_ptr(), yb.data_ptr(), _ptr(gb), index.data_ptr(), _ptr(value), B, N, M, D, int(p), _dtype_code(xb),
-                                  *_NO_RANGES, *ws_args, int(flags) | ENV_FLAGS, _stream(xb))
+                                  *_NO_RANGES, *ws_args, flags, _stream(xb))
         _check(rc, lib)
     if not batched:
         index = index.view(-1)
@@ -1776,7 +1809,7 @@ def argkmin_passes(k):
     return _route_predicate("glhip_argkmin_passes", (k,), f"k {k}")
 
 
-def argkmin(x, y, k, g=None, return_value=False, flags=0, p=2):
+def argkmin(x, y, k, g=None, return_value=False, flags=0, p=2, resident=None):
     """Top-k arg-reduction on the matrix cores (``glhip_argkmin``): for every row the ``k`` columns of the smallest
     ``|x_i - y_j|^2 / 2 - g_j``, best first — the k nearest columns for ``g = None``, what KeOps' ``LazyTensor.argKmin(k, dim=1)`` of
     ``SqDist`` returns (``Kmin_argKmin`` with ``return_value``: the squared distance is twice the value); the k columns a plan row sends
@@ -1788,10 +1821,12 @@ def argkmin(x, y, k, g=None, return_value=False, flags=0, p=2):
     (:func:`argkmin_passes`), each behind the last entry of the one before: the same statements hold for every k up to
     ARGKMIN_MAX_K = 128, at about one k = 16 call per pass.  Not recorded by autograd.  float64 clouds, p != 2,
     D > ARGMIN_MAX_DIM = 4095 and k > ARGKMIN_MAX_K raise ``NotImplementedError``, k < 1 ``ValueError``; block-sparse ranges and p = 1
-    are out of scope."""
+    are out of scope.  ``resident``: as for :func:`argmin` — ``True`` (D <= 16) runs every capacity and the floored passes on the
+    resident-operand kernels of glhip_arg_xd.h."""
     if x.dtype == torch.float64 or y.dtype == torch.float64:
         raise NotImplementedError("geomloss_amd.hip.argkmin: float64 clouds are not supported (cast to float32)")
     D = x.shape[-1]
+    flags = int(flags) | _resident("argkmin", resident, D)
     k = int(k)
     if k < 1:
         raise ValueError(f"geomloss_amd.hip.argkmin: k must be at least 1, got {k}")
@@ -1812,9 +1847,10 @@ def argkmin(x, y, k, g=None, return_value=False, flags=0, p=2):
         index = torch.empty((B, N, k), dtype=torch.int32, device=xb.device)
         value = torch.empty((B, N, k), dtype=torch.float32, device=xb.device) if return_value else None
         with torch.cuda.device(xb.device):
-            ws, ws_args = _scratch(int(lib.glhip_argkmin_workspace_bytes(B, N, M, D, k)), xb.device)
+            flags |= ENV_FLAGS
+            ws, ws_args = _arg_scratch(lib, flags, lambda: lib.glhip_argkmin_workspace_bytes(B, N, M, D, k), B, N, M, D, k, xb.device)
             rc = lib.glhip_argkmin(xb.data_ptr(), yb.data_ptr(), _ptr(gb), index.data_ptr(), _ptr(value), B, N, M, D, k, int(p), _dtype_code(xb),
-                                   *_NO_RANGES, *ws_args, int(flags) | ENV_FLAGS, _stream(xb))
+                                   *_NO_RANGES, *ws_args, flags, _stream(xb))
         _check(rc, lib)
     if not batched:
         index = index.view(N, k)

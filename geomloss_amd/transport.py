@@ -242,24 +242,25 @@ def barycentric_map(x, y, F, G, blur, b=None, p=2):
         return hip.plan_apply_p1(eps, x, y, h, y.detach().float())
 
 
-def plan_argmax(x, y, F, G, blur, b=None):
+def plan_argmax(x, y, F, G, blur, b=None, resident=None):
     """``argmax_j P_ij`` int32 (N,)|(B,N): the column that receives most of the mass of row i — a hard correspondence where
     :func:`barycentric_map` gives an average.  It is ``argmin_j [|x_i - y_j|^2 / 2 - G_j - blur^2 log b_j]``
     (:func:`geomloss_amd.hip.argmin`); columns of zero weight are never returned, ties go to the smallest index.  Like the
-    barycentric map it does not depend on ``a`` or ``F``; ``F`` is accepted so that the call reads like :func:`apply_plan`."""
+    barycentric map it does not depend on ``a`` or ``F``; ``F`` is accepted so that the call reads like :func:`apply_plan`.
+    ``resident``: passed to the arg-reduction (``True``: the resident-operand kernels of D <= 16, ``None``: GEOMLOSS_HIP_XD_ARG)."""
     eps = float(blur) ** 2
     with torch.no_grad():
         Gf = G.detach().float().reshape(y.shape[:-1])
-        return hip.argmin(x, y, Gf + eps * _log_weights(b, Gf, y.shape[-2]))
+        return hip.argmin(x, y, Gf + eps * _log_weights(b, Gf, y.shape[-2]), **hip.resident_kw(resident))
 
 
-def plan_topk(x, y, F, G, blur, k, a=None, b=None, p=2):
+def plan_topk(x, y, F, G, blur, k, a=None, b=None, p=2, resident=None):
     """The ``k`` heaviest entries of every row of the plan: ``(index, weight)``, int32 and fp32 (N,k)|(B,N,k), heaviest first, with
     ``weight[i, r] = P[i, index[i, r]]``.  One top-k arg-reduction (:func:`geomloss_amd.hip.argkmin`) of
     ``|x_i - y_j|^2 / 2 - G_j - blur^2 log b_j``, whose values give the weights as ``a_i exp((F_i - value_ir) / blur^2)``: nothing of
     size N x M is stored.  Columns of zero weight are never returned; a row with fewer than k columns of positive weight has index -1 and
     weight 0 in its last ranks; equal entries come in ascending column order.  1 <= k <= ``hip.ARGKMIN_MAX_K``; ``p=1`` raises
-    ``NotImplementedError`` (the arg-reduction has the squared cost only).
+    ``NotImplementedError`` (the arg-reduction has the squared cost only).  ``resident``: passed to the arg-reduction (``True``: the resident-operand kernels of D <= 16, ``None``: GEOMLOSS_HIP_XD_ARG).
 
     As a sparse matrix (unbatched, every rank filled)::
 
@@ -277,7 +278,7 @@ def plan_topk(x, y, F, G, blur, k, a=None, b=None, p=2):
     with torch.no_grad():
         Ff = F.detach().float().reshape(x.shape[:-1])
         Gf = G.detach().float().reshape(y.shape[:-1])
-        index, value = hip.argkmin(x, y, k, Gf + eps * _log_weights(b, Gf, y.shape[-2]), return_value=True)
+        index, value = hip.argkmin(x, y, k, Gf + eps * _log_weights(b, Gf, y.shape[-2]), return_value=True, **hip.resident_kw(resident))
         la = _log_weights(a, Ff, x.shape[-2]).to(value.device)
         weight = (la.unsqueeze(-1) + (Ff.to(value.device).unsqueeze(-1) - value) / eps).exp()
         return index, torch.where(index >= 0, weight, torch.zeros_like(weight))

@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 141 /* 0.1.41 */
+#define GLHIP_VERSION 142 /* 0.1.42 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
@@ -131,6 +131,15 @@ extern "C" {
 #define GLHIP_DIST_GRAD_LAPLACIAN 1  /* glhip_kernel_conv_bwd_x / glhip_kernel_conv_fwd_grad, GLHIP_LAPLACIAN */
 #define GLHIP_DIST_GRAD_ENERGY 2     /* ... GLHIP_ENERGY */
 
+#define GLHIP_FLAG_XD_ARG 8192 /* version 142.  glhip_argmin and glhip_argkmin with p == 2, 1 <= D <= 16, dense launches (n_ranges == 0),
+                                  B <= 65535: the resident-operand kernels of csrc/glhip_arg_xd.h — both clouds packed once per call into
+                                  bf16 x 3 records around one centre per launch, tiles copied by LDS-DMA into two buffers, the list filter of
+                                  glhip_argkmin_xk.h as the epilogue — instead of the K-chunked ones.  glhip_arg_family reports
+                                  GLHIP_FAMILY_XD there.  The call then REQUIRES a 16-byte aligned workspace of glhip_arg_xd_workspace_bytes
+                                  (GLHIP_EINVAL otherwise: it never takes the other route silently).  Same semantics inside the family
+                                  (ties, duplicates, -inf, missing ranks, prefixes, k = 1 = argmin, independence of the splits); against
+                                  the other family values differ by rounding (another centre) and indices agree where float64 separates
+                                  the candidates.  Every other entry point, and D > 16, ignore the flag, bit for bit. */
 #define GLHIP_FLAG_NO_SORT 512 /* p = 1 soft-min / half-step, laplacian and energy products: big dense launches (B = 1, D <= 3, N >= 65536,
                                   N M >= 5e8, a workspace of glhip_workspace_bytes) sort both clouds into the workspace themselves — voxel sort along a
                                   boustrophedon path, csrc/glhip_autosort.h — so that the squared distances can come from the matrix cores
@@ -753,6 +762,19 @@ int glhip_argkmin(const void* x, const void* y, const float* g, int32_t* index, 
                   int B, int N, int M, int D, int k, int p, int in_dtype,
                   const int32_t* ranges_i, const int32_t* slices_i, const int32_t* redranges_j, int n_ranges,
                   void* workspace, size_t workspace_bytes, int flags, void* stream);
+/*
+ * The kernel family of an arg-reduction and the workspace of the resident-operand one (version 142; csrc/glhip_arg_xd.h).
+ * glhip_arg_family: host arithmetic only, the predicate glhip_argmin (k = 1) and glhip_argkmin evaluate — GLHIP_FAMILY_XD under
+ * GLHIP_FLAG_XD_ARG for p == 2, 1 <= D <= 16, n_ranges == 0, B <= 65535; GLHIP_FAMILY_XK for every other launch they serve;
+ * GLHIP_EUNSUPPORTED for valid requests without a kernel (p = 1, ranges, D > 4095, B > 65535, k > glhip_argkmin_max_k()); GLHIP_EINVAL
+ * for what the entry points reject (negative sizes, D < 1, k < 1, a bad p or dtype).
+ * glhip_arg_xd_workspace_bytes: what a GLHIP_FLAG_XD_ARG call needs — the floors of a k > 16 call (B N pairs of 32-bit words), the
+ * packed rows and columns (32 NM bytes per point and whole groups of 32 points, NM = ceil(6 (D + 1) / 16)), one float per row and the
+ * (exponent, index) partials of the column splits the launch would like, each part rounded up to 256 bytes.  Non-decreasing in M and
+ * k; 0 for an empty cloud, D > 16 or k beyond the limit.  glhip_argmin_workspace_bytes and glhip_argkmin_workspace_bytes keep their values.
+ */
+int glhip_arg_family(int B, long N, long M, int D, int k, int p, int dtype, int n_ranges, int flags);
+size_t glhip_arg_xd_workspace_bytes(int B, int N, int M, int D, int k);
 /*
  * The plan of a p = 2 soft-min contracted with a bilinear per-pair weight (version 139; glhip_plan_bilinear_xk.h) — the one reduction
  * behind the gradients of `P @ S` and of the barycentric map with respect to the points and the potentials (geomloss_amd/transport.py):
