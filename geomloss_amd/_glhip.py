@@ -80,6 +80,9 @@ SIGNATURES = {
     "glhip_plan_apply_p1_pass_width": (_c_int, []),
     "glhip_plan_apply_p1_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "glhip_plan_apply_p1": (_c_int, [_vp] * 6 + [_c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int] + _RANGES + _TAIL),
+    "glhip_plan_apply_sparse_supported": (_c_int, [_c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int, _c_int]),
+    "glhip_plan_apply_sparse_workspace_bytes": (_c_size, [_c_int] * 6),
+    "glhip_plan_apply_sparse": (_c_int, [_vp] * 7 + [_c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int, _c_int] + _RANGES + _TAIL),
     "glhip_plan_bilinear_supported": (_c_int, [_c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int, _c_int]),
     "glhip_plan_bilinear_pass_width": (_c_int, []),
     "glhip_plan_bilinear_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
@@ -136,7 +139,8 @@ _SINCE = {"glhip_sinkhorn_step_perm": 134, "glhip_softmin_perm_applies": 134,
           "glhip_argkmin_max_k": 138, "glhip_argkmin_supported": 138, "glhip_argkmin_workspace_bytes": 138, "glhip_argkmin": 138,
           "glhip_plan_bilinear_supported": 139, "glhip_plan_bilinear_pass_width": 139, "glhip_plan_bilinear_workspace_bytes": 139,
           "glhip_plan_bilinear": 139,
-          "glhip_argkmin_passes": 141, "glhip_arg_family": 142, "glhip_arg_xd_workspace_bytes": 142}
+          "glhip_argkmin_passes": 141, "glhip_arg_family": 142, "glhip_arg_xd_workspace_bytes": 142,
+          "glhip_plan_apply_sparse_supported": 143, "glhip_plan_apply_sparse_workspace_bytes": 143, "glhip_plan_apply_sparse": 143}
 
 _lib = None
 

@@ -1302,6 +1302,71 @@ def plan_apply_nd(eps, x, y, h, feat, fwd=None, flags=0, p=2, ranges=None):
     return _plan_apply("plan_apply_nd", plan_apply_nd_raw, PLAN_MAX_DIM, eps, x, y, h, feat, fwd, flags, p, ranges)
 
 
+def plan_apply_sparse_raw(x, y, h, fwd, feat, eps, ranges, flags=0, want_mass=False, p=2):
+    """The plan of a p = 2 soft-min applied to features on block-sparse ``ranges`` (``glhip_plan_apply_sparse``, D <= 16): x (1,N,D),
+    y (1,M,D) fp32|bf16 in the order the ranges index, h (1,M), fwd (1,N), feat (1,M,V) fp32 -> (1,N,V) fp32 averages over the kept
+    columns [, (1,N) kept row masses].  Rows outside every range and rows without kept mass come back as 0."""
+    lib = load_library()
+    B, N, D = x.shape
+    M, V = y.shape[1], feat.shape[2]
+    if is_f64(x):
+        raise NotImplementedError("glhip_plan_apply_sparse: float64 clouds are not supported (cast to float32)")
+    if ranges is None:
+        raise ValueError("glhip_plan_apply_sparse: needs block-sparse ranges (dense plans: plan_apply_raw)")
+    if tuple(feat.shape[:2]) != (B, M) or tuple(h.shape) != (B, M) or tuple(fwd.shape) != (B, N) or tuple(y.shape) != (B, M, D):
+        raise ValueError(f"glhip_plan_apply_sparse: expected y {(B, M, D)}, h {(B, M)}, fwd {(B, N)}, feat {(B, M, 'V')}; got "
+                         f"{tuple(y.shape)}, {tuple(h.shape)}, {tuple(fwd.shape)}, {tuple(feat.shape)}")
+    out = torch.empty((B, N, V), dtype=torch.float32, device=x.device)
+    mass = torch.empty((B, N), dtype=torch.float32, device=x.device) if want_mass else None
+    with torch.cuda.device(x.device):
+        n_ranges = int(ranges.ranges_i.shape[0])
+        ws, ws_args = _scratch(int(lib.glhip_plan_apply_sparse_workspace_bytes(B, N, M, D, V, n_ranges)), x.device)
+        rc = lib.glhip_plan_apply_sparse(x.data_ptr(), y.data_ptr(), h.data_ptr(), fwd.data_ptr(), feat.data_ptr(), out.data_ptr(),
+                                         _ptr(mass), B, N, M, D, V, float(eps), int(p), _dtype_code(x),
+                                         *ranges.c_args(), *ws_args, int(flags), _stream(x))
+    _check(rc, lib)
+    return (out, mass) if want_mass else out
+
+
+def plan_apply_sparse_applies(x, ranges, p=2):
+    """Whether :func:`plan_apply_sparse` serves clouds like ``x`` on ``ranges``: p = 2, one un-batched problem with ranges,
+    D <= XD_MAX_DIM, float32 / bfloat16 compute."""
+    return p == 2 and ranges is not None and x.dim() == 2 and x.shape[-1] <= XD_MAX_DIM and x.dtype != torch.float64
+
+
+def plan_apply_sparse(eps, x, y, h, feat, ranges, fwd=None, flags=0, want_mass=False, p=2):
+    """:func:`plan_apply` restricted to the block-sparse pattern ``ranges`` (:class:`BlockRanges`; ``glhip_plan_apply_sparse``):
+
+        out[i, v] = sum_{j in kept(i)} w_ij feat[j, v] / sum_{j in kept(i)} w_ij,     w_ij = exp(h_j - |x_i - y_j|^2 / (2 eps) + fwd_i / eps)
+
+    with kept(i) the columns of the intervals of row i's block.  x: (N,D), y: (M,D) ALREADY in the order the ranges index (cluster-sorted
+    clouds), h: (M,), feat: (M,V)|(M,) -> (N,V)|(N,) fp32.  ``fwd`` defaults to the soft-min on the same ranges, so that the kept mass of a
+    row is 1; ``want_mass=True`` also returns it, (N,).  Rows of an empty slice, rows without kept mass and rows outside every row block
+    give 0 in both.  Nothing is sorted or pruned here: the pattern is the caller's (``transport.plan_ranges`` builds the two-scale
+    solver's).  Numerics and the bit-for-bit one-hot rows are those of :func:`plan_apply`, and so are the pass widths except at D = 2, 3
+    on the default layout and D = 4 under ``FLAG_F16X2``, where a pass carries 64 feature columns; results are bit-identical run to
+    run.  NOT an autograd function.  p = 1, D > 16, float64 clouds and batches raise ``NotImplementedError``."""
+    if x.dtype == torch.float64 or y.dtype == torch.float64:
+        raise NotImplementedError("geomloss_amd.hip.plan_apply_sparse: float64 clouds are not supported (cast to float32)")
+    if ranges is None:
+        raise ValueError("geomloss_amd.hip.plan_apply_sparse: needs block-sparse ranges (dense plans: plan_apply)")
+    if not plan_apply_sparse_applies(x, ranges, p):
+        raise NotImplementedError(f"geomloss_amd.hip.plan_apply_sparse: only p = 2, D <= {XD_MAX_DIM}, one un-batched problem "
+                                  f"(got p = {p}, x of shape {tuple(x.shape)})")
+    M = y.shape[0]
+    vector = feat.dim() == 1
+    if feat.shape[0] != M or feat.dim() not in (1, 2):
+        raise ValueError(f"geomloss_amd.hip.plan_apply_sparse: expected features of shape {(M,)} or {(M, 'V')}, got {tuple(feat.shape)}")
+    with torch.no_grad():
+        xb, yb, hb, _ = _clouds(x, y, _f32(h), detach=True)
+        fb = _f32(feat).to(xb.device).reshape(1, M, -1)
+        flags = int(flags) | ENV_FLAGS
+        fwd_b = softmin_fwd_raw(xb, yb, hb, eps, 2, ranges, _range_flags(flags, ranges)) if fwd is None else _f32(fwd).reshape(1, -1)
+        out, mass = plan_apply_sparse_raw(xb, yb, hb, fwd_b, fb, float(eps), ranges, flags, want_mass=True)
+    out = out[0, :, 0] if vector else out[0]
+    return (out, mass[0]) if want_mass else out
+
+
 def plan_apply_p1_applies(x, ranges=None):
     """Whether :func:`plan_apply_p1` serves clouds like ``x``: dense, D <= PLAN_P1_MAX_DIM, float32 / bfloat16 compute."""
     return ranges is None and 1 <= x.shape[-1] <= PLAN_P1_MAX_DIM and x.dtype != torch.float64

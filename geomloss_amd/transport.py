@@ -45,7 +45,7 @@ import torch
 
 from . import hip
 
-__all__ = ["apply_plan", "barycentric_map", "plan_argmax", "plan_topk"]
+__all__ = ["apply_plan", "barycentric_map", "plan_argmax", "plan_topk", "plan_ranges"]
 
 
 def _log_weights(w, like, count):
@@ -191,7 +191,46 @@ class _BarycentricMap(torch.autograd.Function):
         return dx, dy, dG, None, None
 
 
-def apply_plan(x, y, F, G, feat, blur, a=None, b=None, transpose=False, p=2):
+def plan_ranges(x, y, F, G, blur, truncate=5, cluster_scale=None):
+    """The block-sparse pattern of the plan of ``F``, ``G`` at temperature ``blur ** 2``, from the pieces the two-scale solver uses:
+    voxel clusters of both clouds (``cluster.clusterize_device_many``; ``cluster_scale`` defaults to the solver's, about 2000 cells over
+    the joint bounding box), the potentials averaged per cluster, and the Sinkhorn keep rule on cluster pairs
+    ``F_c + G_c > |x_c - y_c|^2 / 2 - truncate * blur^2`` (``cluster.block_ranges_device``; ``truncate`` = 5 as in ``SamplesLoss``).
+    Returns ``(perm_x, perm_y, ranges)``: ``x[perm_x]``, ``y[perm_y]`` (and ``F[perm_x]``, ``G[perm_y]``, features, weights) are the
+    inputs in the order ``ranges`` indexes, and a result ``T`` of the sorted call goes back with ``out[perm_x] = T``.  Un-batched float32
+    / bfloat16 GPU clouds of dimension <= 3, which is what the device clustering takes (``NotImplementedError`` otherwise; hand-built
+    :class:`geomloss_amd.hip.BlockRanges` serve any D <= 16)."""
+    from . import cluster
+    if not (cluster.native_clustering_applies(x) and cluster.native_clustering_applies(y)):
+        raise NotImplementedError("geomloss_amd.transport.plan_ranges: un-batched float32 / bfloat16 GPU clouds of dimension <= 3")
+    eps = float(blur) ** 2
+    with torch.no_grad():
+        if cluster_scale is None:
+            D = x.shape[1]
+            both = torch.cat([x.detach().float(), y.detach().float()])
+            diameter = float((both.max(0).values - both.min(0).values).norm())
+            cluster_scale = diameter / (math.sqrt(D) * 2000 ** (1 / D))
+        (_, _, x_c, _, ranges_x, perm_x), (_, _, y_c, _, ranges_y, perm_y) = cluster.clusterize_device_many([(None, x), (None, y)], cluster_scale)
+
+        def cluster_mean(pot, perm, ranges):
+            total = torch.cat([pot.new_zeros(1, dtype=torch.float64), pot.detach().reshape(-1)[perm].double().cumsum(0)])
+            lo, hi = ranges[:, 0].long(), ranges[:, 1].long()
+            return ((total[hi] - total[lo]) / (hi - lo).clamp(min=1)).float()
+
+        ranges = cluster.block_ranges_device("dual_slack", x_c, y_c, cluster_mean(F, perm_x, ranges_x), cluster_mean(G, perm_y, ranges_y),
+                                             ranges_x, ranges_y, truncate * eps, p=2)
+    return perm_x, perm_y, ranges
+
+
+def _sparse_guard(name, p, *tensors):
+    """The block-sparse calls: p = 2, no autograd (``NotImplementedError``)."""
+    if p != 2:
+        raise NotImplementedError(f"geomloss_amd.transport.{name}: block-sparse ranges are served for p = 2 only (got p = {p!r})")
+    if any(torch.is_tensor(t) and t.requires_grad for t in tensors):
+        raise NotImplementedError(f"geomloss_amd.transport.{name}: no autograd through block-sparse ranges (detach the inputs)")
+
+
+def apply_plan(x, y, F, G, feat, blur, a=None, b=None, transpose=False, p=2, ranges=None):
     """``sum_j P_ij feat_j`` for the plan of the potentials ``F`` (N,)|(B,N), ``G`` (M,)|(B,M) on the clouds ``x`` (N,D)|(B,N,D),
     ``y`` (M,D)|(B,M,D) with weights ``a``, ``b`` (uniform by default): feat (M,V)|(B,M,V)|(M,) -> (N,V)|(B,N,V)|(N,) fp32.
     ``transpose=True`` applies the transposed plan instead: ``sum_i P_ij feat_i`` for feat on the rows, (N,V) -> (M,V).
@@ -203,10 +242,25 @@ def apply_plan(x, y, F, G, feat, blur, a=None, b=None, transpose=False, p=2):
     :func:`geomloss_amd.hip.plan_bilinear` (at most two launches of it, one transposed soft-min and one transposed application; only
     what the requested gradients need).  The weights ``a``, ``b`` are detached: no gradient flows to them.  The backward pass is
     once-differentiable: no second derivatives.  Otherwise — and always for ``p=1`` — the call runs as before and returns a tensor
-    without ``grad_fn``."""
+    without ``grad_fn``.
+
+    ``ranges`` (a :class:`geomloss_amd.hip.BlockRanges`, e.g. from :func:`plan_ranges`): the plan restricted to that block-sparse
+    pattern, on the kernel of :func:`geomloss_amd.hip.plan_apply_sparse` — ``sum_{j kept} P_ij feat_j``.  Every input must already be in
+    the order the ranges index; un-batched, p = 2, D <= 16, and no input may require grad (``NotImplementedError``).  ``None`` is the
+    dense call above, untouched."""
     if transpose:
-        return apply_plan(y, x, G, F, feat, blur, a=b, b=a, p=p)
+        return apply_plan(y, x, G, F, feat, blur, a=b, b=a, p=p, ranges=None if ranges is None else ranges.t())
     eps = _eps(blur, p)
+    if ranges is not None:
+        _sparse_guard("apply_plan", p, x, y, F, G, feat)
+        with torch.no_grad():
+            Ff = F.detach().float().reshape(x.shape[:-1])
+            Gf = G.detach().float().reshape(y.shape[:-1])
+            h = _log_weights(b, Gf, y.shape[-2]) + Gf / eps
+            fwd = hip.softmin(eps, x, y, h, ranges=ranges)      # the soft-min over the kept columns
+            avg, mass = hip.plan_apply_sparse(eps, x, y, h, feat, ranges, fwd=fwd, want_mass=True)
+            rows = torch.where(mass > 0, (_log_weights(a, Ff, x.shape[-2]) + (Ff - fwd) / eps).exp(), torch.zeros_like(mass))
+            return rows * avg if avg.dim() == rows.dim() else rows.unsqueeze(-1) * avg
     if p == 2:
         if _wants_grad(x, y, F, G, feat):
             return _ApplyPlan.apply(x, y, F, G, feat, eps, a, b)
@@ -221,7 +275,7 @@ def apply_plan(x, y, F, G, feat, blur, a=None, b=None, transpose=False, p=2):
         return rows * avg if avg.dim() == rows.dim() else rows.unsqueeze(-1) * avg
 
 
-def barycentric_map(x, y, F, G, blur, b=None, p=2):
+def barycentric_map(x, y, F, G, blur, b=None, p=2, ranges=None):
     """``T(x_i) = sum_j P_ij y_j / sum_j P_ij`` (N,D)|(B,N,D) fp32: where the plan sends each x_i on average.  The row-normalised
     average does not depend on ``a`` or ``F`` (they scale a whole row); ``F`` is accepted so that the call reads like
     :func:`apply_plan`.  ``p`` as there.
@@ -230,8 +284,16 @@ def barycentric_map(x, y, F, G, blur, b=None, p=2):
     ``(barycentric_map(x, y, F, G, blur) - target).pow(2).sum().backward()`` fills ``x.grad``, ``y.grad`` and ``G.grad`` in the dtype
     of each input (``F`` gets none: the map does not depend on it), for clouds of any dimension D <= 4095, through
     :func:`geomloss_amd.hip.plan_bilinear` with D + 1 features.  ``b`` is detached; the backward pass is once-differentiable.
-    Otherwise — and always for ``p=1`` — the call runs as before and returns a tensor without ``grad_fn``."""
+    Otherwise — and always for ``p=1`` — the call runs as before and returns a tensor without ``grad_fn``.
+
+    ``ranges``: as in :func:`apply_plan` — the average over the kept columns, inputs in the ranges' order, p = 2, no autograd; a row
+    without kept mass maps to 0."""
     eps = _eps(blur, p)
+    if ranges is not None:
+        _sparse_guard("barycentric_map", p, x, y, G)
+        with torch.no_grad():
+            Gf = G.detach().float().reshape(y.shape[:-1])
+            return hip.plan_apply_sparse(eps, x, y, _log_weights(b, Gf, y.shape[-2]) + Gf / eps, y.float(), ranges)
     if p == 2:
         if _wants_grad(x, y, G):
             return _BarycentricMap.apply(x, y, G, eps, b)

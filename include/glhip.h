@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 142 /* 0.1.42 */
+#define GLHIP_VERSION 143 /* 0.1.43 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
@@ -571,6 +571,38 @@ int glhip_plan_apply_p1(const void* x, const void* y, const float* h, const floa
                         int B, int N, int M, int D, int V, float eps, int in_dtype,
                         const int32_t* ranges_i, const int32_t* slices_i, const int32_t* redranges_j, int n_ranges,
                         void* workspace, size_t workspace_bytes, int flags, void* stream);
+
+/*
+ * The plan of a p = 2 soft-min applied to features on the caller's block-sparse ranges (version 143; glhip_plan_apply_sparse.h),
+ * 1 <= D <= 16, float32 / bfloat16 clouds, B = 1 as for every block-sparse entry point.  The arguments of glhip_plan_apply, with
+ * n_ranges >= 1 required; kept(i) = the columns of the intervals redranges_j[slices_i[k-1] : slices_i[k]] of the row block k that holds i:
+ *   mass_i     = sum_{j in kept(i)} w_ij                       w_ij = exp( h_j - C_ij/eps + fwd_i/eps )
+ *   out[i,v]   = sum_{j in kept(i)} w_ij feat[j,v] / mass_i    (0 where mass_i == 0)
+ * fwd is usually glhip_softmin_fwd on the SAME ranges (mass = 1 up to rounding then); with the dense soft-min, mass is the share of the
+ * row's mass that the pattern keeps.  A row whose slice is empty, whose kept columns carry no mass, or that lies in no row block gets
+ * out = 0 and mass = 0, written by the call itself.  Nothing is sorted, pruned or clustered inside: the clouds come in the order the
+ * ranges index.  Row blocks must be disjoint and inside [0, N), intervals inside [0, M).
+ * Numerics are those of glhip_plan_apply (weights relative to the running row maximum, two f16 pieces per side, per-tile feature scales,
+ * features of columns with h = -inf staged as 0): one-hot rows return their features bit for bit, results are bit-identical run to run
+ * (no float atomics).  One workgroup per chunk of at most 256 rows of one row block; a column tile gathers consecutive short intervals
+ * of the slice through an index list in LDS, or takes one piece of a long interval, decided per launch on the host.  Passes of 128 / 64 /
+ * 32 feature columns for D <= 4 / <= 11 / <= 16 as in glhip_plan_apply, except 64 at D = 2, 3 on the bf16 x 3 layout and at D = 4
+ * under GLHIP_FLAG_F16X2, where four chunks would spill registers.
+ *   flags: GLHIP_FLAG_F16X2, GLHIP_FLAG_NO_SPLIT; others are ignored.  N == 0 or V == 0: nothing is launched.
+ *   Workspace: REQUIRED, at least the row-chunk table; glhip_plan_apply_sparse_workspace_bytes is the table plus the partials of the
+ *   column splits a small launch takes (a launch with a chunk per resident workgroup takes none).  A buffer short of the table returns
+ *   GLHIP_EINVAL; one short of the partials means fewer or no splits.
+ * glhip_plan_apply_sparse_supported: host arithmetic only, the predicate the launch itself evaluates: 1, 0 for valid requests without a
+ * kernel (p = 1, D > 16, B != 1, n_ranges == 0), GLHIP_EINVAL for what the entry point rejects.
+ * glhip_plan_apply, glhip_plan_apply_nd and glhip_plan_apply_p1 keep refusing ranges.
+ */
+int glhip_plan_apply_sparse_supported(int B, long N, long M, int D, int V, int p, int dtype, int n_ranges);
+size_t glhip_plan_apply_sparse_workspace_bytes(int B, int N, int M, int D, int V, int n_ranges);
+int glhip_plan_apply_sparse(const void* x, const void* y, const float* h, const float* fwd, const float* feat,
+                            float* out, float* mass,
+                            int B, int N, int M, int D, int V, float eps, int p, int in_dtype,
+                            const int32_t* ranges_i, const int32_t* slices_i, const int32_t* redranges_j, int n_ranges,
+                            void* workspace, size_t workspace_bytes, int flags, void* stream);
 
 /*
  * Kernel-matrix × vector product  out[b,i] = sum_j k(x[b,i], y[b,j]) * v[b,j].
