@@ -23,6 +23,7 @@ FLAG_XK_DIST_GRAD = 4096        # the p = 1 soft-min, laplacian and energy row g
                                 # (glhip_dist_grad_xk.h); glhip_kernel_conv_fwd_grad takes those kinds under it
 DIST_GRAD_OPS = {"softmin_p1": 0, "laplacian": 1, "energy": 2}      # ops of glhip_dist_grad_uses_xk (GLHIP_DIST_GRAD_*)
 FLAG_XD_ARG = 8192              # argmin / argkmin of p = 2, D <= 16, dense launches: the resident-operand kernels (glhip_arg_xd.h)
+FLAG_XD_BILINEAR = 16384        # plan_bilinear of p = 2, D <= 16, K <= 32, dense launches: the resident-operand kernel (glhip_plan_bilinear_xd.h)
 FLAG_GRAD_FAMILY = FLAG_XDL16   # kernel products rounded like the product-and-gradient kernel of the same kind (glhip.h)
 XD_MAX_DIM = 16                 # the fused four-softmin iteration / annealing / extrapolation, the one-pass value + gradient and the matrix-core
                                 # gradients stop at this dimension (glhip_softmin_xd.h, glhip_wsum_t32.h)
@@ -32,6 +33,7 @@ DIST_XK_MAX_DIM = 4095          # ... and under FLAG_XK_DIST the p = 1 soft-min 
 ARGMIN_MAX_DIM = 4095           # argmin takes p = 2 clouds of every dimension up to this one (glhip_argmin_xk.h)
 PLAN_MAX_DIM = 4095             # plan_apply_nd applies p = 2 transport plans to features up to this dimension (17 ... 4095: glhip_plan_apply_xk.h)
 PLAN_P1_MAX_DIM = 4095          # plan_apply_p1 applies p = 1 transport plans to features in every dimension up to this one (glhip_dist_plan_xk.h)
+PLAN_BILINEAR_XD_MAX_K = 32     # ... and FLAG_XD_BILINEAR serves D <= XD_MAX_DIM with at most this many features
 PLAN_BILINEAR_MAX_DIM = 4095    # plan_bilinear contracts p = 2 plans with <rowfeat_i, colfeat_j> (y_j - x_i) up to this dimension and feature count
                                 # (glhip_plan_bilinear_xk.h)
 # kernel families reported by softmin_fwd_family (GLHIP_FAMILY_* of glhip.h)
@@ -86,6 +88,8 @@ SIGNATURES = {
     "glhip_plan_bilinear_supported": (_c_int, [_c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int, _c_int]),
     "glhip_plan_bilinear_pass_width": (_c_int, []),
     "glhip_plan_bilinear_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "glhip_plan_bilinear_family": (_c_int, [_c_int, _c_long, _c_long] + [_c_int] * 6),
+    "glhip_plan_bilinear_xd_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "glhip_plan_bilinear": (_c_int, [_vp] * 8 + [_c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int, _c_int] + _RANGES + _TAIL),
     "glhip_kernel_conv_fwd": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int]
                               + _RANGES + _TAIL),
@@ -140,7 +144,8 @@ _SINCE = {"glhip_sinkhorn_step_perm": 134, "glhip_softmin_perm_applies": 134,
           "glhip_plan_bilinear_supported": 139, "glhip_plan_bilinear_pass_width": 139, "glhip_plan_bilinear_workspace_bytes": 139,
           "glhip_plan_bilinear": 139,
           "glhip_argkmin_passes": 141, "glhip_arg_family": 142, "glhip_arg_xd_workspace_bytes": 142,
-          "glhip_plan_apply_sparse_supported": 143, "glhip_plan_apply_sparse_workspace_bytes": 143, "glhip_plan_apply_sparse": 143}
+          "glhip_plan_apply_sparse_supported": 143, "glhip_plan_apply_sparse_workspace_bytes": 143, "glhip_plan_apply_sparse": 143,
+          "glhip_plan_bilinear_family": 144, "glhip_plan_bilinear_xd_workspace_bytes": 144}
 
 _lib = None
 

@@ -9,10 +9,11 @@ namespace {
 
 constexpr int kXkBilinearWidth = 32 * glhip::kXkBilinearChunks;      // coordinates per pass of xk_bilinear_kernel
 
-// THE predicate of glhip_plan_bilinear, and what glhip_plan_bilinear_supported reports.  Host arithmetic only.
+// What glhip_plan_bilinear_supported reports: whether plan_bilinear_family (glhip_family.h), THE predicate of glhip_plan_bilinear, names a
+// kernel.  Host arithmetic only.
 inline int plan_bilinear_supported(int B, long N, long M, int D, int K, int p, int dtype, int n_ranges) {
-    if (plan_family_bad_args(B, N, M, D, dtype, n_ranges) || K < 0 || (p != 1 && p != 2)) return GLHIP_EINVAL;
-    return (p != 2 || n_ranges > 0 || D > kXkMaxD || K > kXkMaxD || B > 65535) ? 0 : 1;
+    const int fam = plan_bilinear_family(B, N, M, D, K, p, dtype, n_ranges, 0);
+    return fam > 0 ? 1 : fam;
 }
 
 // The passes over the D coordinates, kXkBilinearWidth at a time; the partial of a row and split is (T[nv], W, mass, m): the merge counts
@@ -54,7 +55,7 @@ int glhip_plan_bilinear(const void* x, const void* y, const float* h, const floa
                         void* workspace, size_t workspace_bytes, int flags, void* stream) {
     int rc = check_common("glhip_plan_bilinear", x, y, h, B, N, M, D, in_dtype, ranges_i, slices_i, redranges_j, n_ranges);
     if (rc) return rc;
-    const int ok = plan_bilinear_supported(B, N, M, D, K, p, in_dtype, n_ranges);
+    const int ok = plan_bilinear_family(B, N, M, D, K, p, in_dtype, n_ranges, flags);
     if (ok == GLHIP_EINVAL) return fail(GLHIP_EINVAL, "glhip_plan_bilinear: bad argument (K %d, p %d)", K, p);
     if (ok == 0)
         return fail(GLHIP_EUNSUPPORTED, "glhip_plan_bilinear: only p = 2, D <= %d, K <= %d, dense launches (got p %d, D %d, K %d, n_ranges %d)",
@@ -69,6 +70,8 @@ int glhip_plan_bilinear(const void* x, const void* y, const float* h, const floa
         return check_launch("glhip_plan_bilinear");
     }
     if (!fwd || !rowfeat || !colfeat) return fail(GLHIP_EINVAL, "glhip_plan_bilinear: NULL fwd / rowfeat / colfeat");
+    if (ok == GLHIP_FAMILY_XD)      // GLHIP_FLAG_XD_BILINEAR: resident operands (glhip_plan_bilinear_xd.h)
+        return plan_bilinear_xd_launch(x, y, h, fwd, rowfeat, colfeat, out, wsum, B, N, M, D, K, eps, in_dtype, workspace, workspace_bytes, flags, stream);
     const Scratch sc = make_scratch(workspace, workspace_bytes, flags, 0, N);
     auto run = [&](auto tag) {
         using T = decltype(tag);

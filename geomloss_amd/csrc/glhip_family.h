@@ -116,6 +116,20 @@ inline int arg_family(int B, long N, long M, int D, int k, int p, int dtype, int
 int arg_xd_launch(const char* fn, const void* x, const void* y, const float* g, int32_t* index, float* value, int B, int N, int M, int D, int k,
                   int in_dtype, void* workspace, size_t workspace_bytes, int flags, void* stream);
 
+// ... and of the bilinear plan reduction: THE predicate of glhip_plan_bilinear, and what glhip_plan_bilinear_family reports (0: a valid
+// request without a kernel, as glhip_plan_bilinear_supported).  GLHIP_FAMILY_XD: the resident-operand kernel of glhip_plan_bilinear_xd.h,
+// on the caller's word (GLHIP_FLAG_XD_BILINEAR) for D <= 16 and 1 <= K <= 32; GLHIP_FAMILY_XK: xk_bilinear_kernel, every other launch served.
+constexpr int kPlanBilinearXdMaxK = 32;      // = kXdBilinearMaxK (glhip_plan_bilinear_xd.h; asserted in glhip_api_plan_bilinear_xd.hip)
+inline int plan_bilinear_family(int B, long N, long M, int D, int K, int p, int dtype, int n_ranges, int flags) {
+    if (plan_family_bad_args(B, N, M, D, dtype, n_ranges) || K < 0 || (p != 1 && p != 2)) return GLHIP_EINVAL;
+    if (p != 2 || n_ranges > 0 || D > kSizedMaxD || K > kSizedMaxD || B > 65535) return 0;
+    return ((flags & GLHIP_FLAG_XD_BILINEAR) && D <= kXdMaxD && K >= 1 && K <= kPlanBilinearXdMaxK) ? GLHIP_FAMILY_XD : GLHIP_FAMILY_XK;
+}
+// The launch of GLHIP_FAMILY_XD (glhip_api_plan_bilinear_xd.hip): glhip_plan_bilinear hands its checked arguments over (N, M, K >= 1).
+int plan_bilinear_xd_launch(const void* x, const void* y, const float* h, const float* fwd, const float* rowfeat, const float* colfeat, float* out,
+                            float* wsum, int B, int N, int M, int D, int K, float eps, int in_dtype, void* workspace, size_t workspace_bytes,
+                            int flags, void* stream);
+
 // the op of a laplacian / energy gradient (glhip_dist_grad_uses_xk, dist_grad_xk_launch) is its kind
 static_assert(GLHIP_DIST_GRAD_LAPLACIAN == GLHIP_LAPLACIAN && GLHIP_DIST_GRAD_ENERGY == GLHIP_ENERGY, "include/glhip.h");
 

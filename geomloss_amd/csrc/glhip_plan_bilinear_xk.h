@@ -5,7 +5,8 @@
 //     out[i][:] = sum_j pi_ij tau_ij (y_j - x_i)                      wsum[i] = sum_j pi_ij tau_ij
 //
 // the one reduction behind the gradients of P @ S and of the barycentric map with respect to the points and the potentials
-// (geomloss_amd/transport.py).  ONE kernel for the whole range of D, a __global__ body of its own that joins pieces the tree already has,
+// (geomloss_amd/transport.py).  ONE kernel for the whole range of D (D <= 16 with K <= 32 has a resident-operand kernel of its own behind
+// GLHIP_FLAG_XD_BILINEAR, glhip_plan_bilinear_xd.h), a __global__ body of its own that joins pieces the tree already has,
 // the way xk_dist_grad_kernel (glhip_dist_grad_xk.h) was built; xk_plan_kernel is not touched.  Per column tile:
 //
 //   exponent half = that of xk_plan_kernel (glhip_plan_apply_xk.h): xk_exponent_blocks over (x, y, D), clouds centred on the first row of
@@ -46,8 +47,8 @@
 //   xk_plan_kernel (199-207 / 245-256 VGPRs) and xk_dist_grad_kernel (227-231) keep their figures: the only shared text that changed is
 //   the CENTRED parameter of xk_exponent_blocks, whose default leaves their code as it was.
 //
-// Out of scope: p = 1, block-sparse ranges (the arguments are in the ABI), float64, D or K > 4095, second derivatives, a
-// resident-operand variant for D <= 16, and routing hip._plan_moments (the Cov_i V_i of the p = 2 double backward: the same reduction with
+// Out of scope: p = 1, block-sparse ranges (the arguments are in the ABI), float64, D or K > 4095, second derivatives, and routing
+// hip._plan_moments (the Cov_i V_i of the p = 2 double backward: the same reduction with
 // rowfeat = V, colfeat = y) through this kernel.
 #pragma once
 

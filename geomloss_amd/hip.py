@@ -510,7 +510,9 @@ def plan_bilinear_raw(xb, yb, hb, fwd, rowfeat, colfeat, eps, flags=0, p=2, rang
     """The plan of a p = 2 soft-min contracted with the per-pair weight ``<rowfeat_i, colfeat_j>`` (``glhip_plan_bilinear``, any
     D, K <= PLAN_BILINEAR_MAX_DIM): xb (B,N,D), yb (B,M,D) fp32|bf16, hb (B,M), fwd (B,N) the saved soft-min, rowfeat (B,N,K),
     colfeat (B,M,K) fp32 -> out (B,N,D), wsum (B,N) fp32.  ``workspace=False`` passes no workspace: the launch runs without column
-    splits (same results up to summation order)."""
+    splits (same results up to summation order).  Under FLAG_XD_BILINEAR, where the library's predicate names the resident-operand kernel
+    (D <= 16, K <= 32), ``workspace=True`` sizes the scratch with ``glhip_plan_bilinear_xd_workspace_bytes``; a number of bytes passes a
+    scratch of exactly that size (the library refuses a flagged call whose workspace is short)."""
     lib = load_library()
     B, N, D = xb.shape
     M, K = yb.shape[1], rowfeat.shape[2]
@@ -523,7 +525,11 @@ def plan_bilinear_raw(xb, yb, hb, fwd, rowfeat, colfeat, eps, flags=0, p=2, rang
     out = torch.empty((B, N, D), dtype=torch.float32, device=xb.device)
     wsum = torch.empty((B, N), dtype=torch.float32, device=xb.device)
     with torch.cuda.device(xb.device):
-        ws, ws_args = _scratch(int(lib.glhip_plan_bilinear_workspace_bytes(B, N, M, D, K)) if workspace else 0, xb.device)
+        if workspace is True and N and M and lib.glhip_plan_bilinear_family(B, N, M, D, K, int(p), F32, 0, int(flags)) == FAMILY_XD:
+            nbytes = lib.glhip_plan_bilinear_xd_workspace_bytes(B, N, M, D, K)
+        else:
+            nbytes = lib.glhip_plan_bilinear_workspace_bytes(B, N, M, D, K) if workspace is True else workspace
+        ws, ws_args = _scratch(int(nbytes), xb.device)
         rc = lib.glhip_plan_bilinear(xb.data_ptr(), yb.data_ptr(), hb.data_ptr(), fwd.data_ptr(), rowfeat.data_ptr(), colfeat.data_ptr(),
                                      out.data_ptr(), wsum.data_ptr(), B, N, M, D, K, float(eps), int(p), _dtype_code(xb),
                                      *_range_args(ranges, B), *ws_args, int(flags), _stream(xb))
@@ -1415,7 +1421,7 @@ def plan_bilinear_applies(x, ranges=None):
     return ranges is None and 1 <= x.shape[-1] <= PLAN_BILINEAR_MAX_DIM and x.dtype != torch.float64
 
 
-def plan_bilinear(eps, x, y, h, rowfeat, colfeat, fwd=None, flags=0, p=2, ranges=None):
+def plan_bilinear(eps, x, y, h, rowfeat, colfeat, fwd=None, flags=0, p=2, ranges=None, resident=None):
     """The plan of a p = 2 soft-min contracted with a bilinear per-pair weight on the matrix cores (``glhip_plan_bilinear``,
     glhip_plan_bilinear_xk.h), for clouds of any dimension D <= PLAN_BILINEAR_MAX_DIM = 4095 and K <= 4095 features:
 
@@ -1429,7 +1435,10 @@ def plan_bilinear(eps, x, y, h, rowfeat, colfeat, fwd=None, flags=0, p=2, ranges
     coordinates; every sweep evaluates the exponents and tau on the matrix cores.  Features of any finite magnitude are safe: the
     product is scaled per row.  Rows without mass give 0, a column with ``h = -inf`` weighs exactly 0, results are bit-identical run
     to run.  NOT an autograd function itself: it runs under ``torch.no_grad()`` and returns tensors without ``grad_fn``.  float64
-    clouds, p != 2, block-sparse ranges and D or K > 4095 raise ``NotImplementedError``; mismatched shapes raise ``ValueError``."""
+    clouds, p != 2, block-sparse ranges and D or K > 4095 raise ``NotImplementedError``; mismatched shapes raise ``ValueError``.
+    ``resident=True`` (FLAG_XD_BILINEAR, D <= 16 and 1 <= K <= 32 only, ``NotImplementedError`` beyond) runs the resident-operand kernel of
+    glhip_plan_bilinear_xd.h: everything packed once per call, same contract, values within rounding of the default route; ``False``
+    never does; ``None`` follows GEOMLOSS_HIP_XD_BILINEAR (default 0)."""
     D = x.shape[-1]
     if x.dtype == torch.float64 or y.dtype == torch.float64:
         raise NotImplementedError("geomloss_amd.hip.plan_bilinear: float64 clouds are not supported (cast to float32)")
@@ -1441,6 +1450,7 @@ def plan_bilinear(eps, x, y, h, rowfeat, colfeat, fwd=None, flags=0, p=2, ranges
                          f"colfeat {lead_y + ('K',)}, fwd {lead_x}; got {tuple(y.shape)}, {tuple(h.shape)}, {tuple(rowfeat.shape)}, "
                          f"{tuple(colfeat.shape)}, {None if fwd is None else tuple(fwd.shape)}")
     K = rowfeat.shape[-1]
+    flags = int(flags) | _resident("plan_bilinear", resident, D, FLAG_XD_BILINEAR, _XD_BILINEAR_DEFAULT, K, PLAN_BILINEAR_XD_MAX_K)
     if p != 2 or D > PLAN_BILINEAR_MAX_DIM or K > PLAN_BILINEAR_MAX_DIM or ranges is not None:
         raise NotImplementedError(f"geomloss_amd.hip.plan_bilinear: only p = 2, D and K <= {PLAN_BILINEAR_MAX_DIM}, dense plans (got p = {p}, "
                                   f"D = {D}, K = {K}, ranges {'given' if ranges is not None else 'None'})")
@@ -1784,20 +1794,26 @@ def cmin(x, y, g, p=2, ranges=None, flags=0):
 # GEOMLOSS_HIP_XD_ARG: what ``resident=None`` of :func:`argmin` / :func:`argkmin` means, read once per process (default 0: the K-chunked
 # kernels; 1: the resident-operand kernels of glhip_arg_xd.h wherever they apply, D <= XD_MAX_DIM)
 _XD_ARG_DEFAULT = os.environ.get("GEOMLOSS_HIP_XD_ARG", "0") != "0"
+# GEOMLOSS_HIP_XD_BILINEAR: the same for :func:`plan_bilinear` and, through it, the backward passes of ``geomloss_amd.transport`` (default 0:
+# xk_bilinear_kernel; 1: the resident-operand kernel of glhip_plan_bilinear_xd.h wherever it applies, D <= XD_MAX_DIM and K <= 32)
+_XD_BILINEAR_DEFAULT = os.environ.get("GEOMLOSS_HIP_XD_BILINEAR", "0") != "0"
 
 
-def _resident(name, resident, D):
-    """FLAG_XD_ARG or 0 for a call of ``name`` in dimension D: ``True`` asks for the resident-operand kernels (``NotImplementedError``
-    beyond D = XD_MAX_DIM), ``False`` never sets the flag, ``None`` follows GEOMLOSS_HIP_XD_ARG where they apply."""
+def _resident(name, resident, D, flag=FLAG_XD_ARG, default=None, K=1, max_k=1):
+    """``flag`` (FLAG_XD_ARG, FLAG_XD_BILINEAR) or 0 for a call of ``name`` in dimension D with K features: ``True`` asks for the
+    resident-operand kernels (``NotImplementedError`` beyond D = XD_MAX_DIM or outside 1 <= K <= max_k), ``False`` never sets the flag,
+    ``None`` follows the knob of the flag (``default``; None: GEOMLOSS_HIP_XD_ARG) where they apply."""
+    inside = D <= XD_MAX_DIM and 1 <= K <= max_k
     if resident is None:
-        return FLAG_XD_ARG if (_XD_ARG_DEFAULT and D <= XD_MAX_DIM) else 0
-    if resident and D > XD_MAX_DIM:
-        raise NotImplementedError(f"geomloss_amd.hip.{name}: resident=True serves D <= {XD_MAX_DIM} (got D = {D})")
-    return FLAG_XD_ARG if resident else 0
+        return flag if ((_XD_ARG_DEFAULT if default is None else default) and inside) else 0
+    if resident and not inside:
+        raise NotImplementedError(f"geomloss_amd.hip.{name}: resident=True serves D <= {XD_MAX_DIM}" + (f", 1 <= K <= {max_k}" if max_k > 1 else "")
+                                  + f" (got D = {D}" + (f", K = {K})" if max_k > 1 else ")"))
+    return flag if resident else 0
 
 
 def resident_kw(resident):
-    """The keyword a caller of :func:`argmin` / :func:`argkmin` hands its own ``resident=`` on with: nothing for ``None``, so that the
+    """The keyword a caller of :func:`argmin` / :func:`argkmin` / :func:`plan_bilinear` hands its own ``resident=`` on with: nothing for ``None``, so that the
     call reads as it did before the keyword existed."""
     return {} if resident is None else {"resident": resident}
 

@@ -16,7 +16,7 @@ in a loss.  For a cotangent ``Gb`` of ``P @ S`` the plan is contracted with the 
 
     dL/dx_i = (1/eps) sum_j P_ij tau_ij (y_j - x_i),        dL/dG_j = (1/eps) sum_i P_ij tau_ij,
 
-by ONE matrix-core reduction per side (:func:`geomloss_amd.hip.plan_bilinear`, glhip_plan_bilinear_xk.h) instead of the ``V D``
+by ONE matrix-core reduction per side (:func:`geomloss_amd.hip.plan_bilinear`, glhip_plan_bilinear_xk.h / glhip_plan_bilinear_xd.h) instead of the ``V D``
 feature columns that composing it from :func:`geomloss_amd.hip.plan_apply_nd` would take.  Only the reductions that the requested
 gradients need are launched; gradients come back in the dtype of their input; the backward pass is once-differentiable.  The functions
 reach the kernels through ``hip.softmin``, ``hip.plan_apply_nd`` and ``hip.plan_bilinear`` alone, looked up at call time.  When no input
@@ -98,10 +98,11 @@ class _ApplyPlan(torch.autograd.Function):
     application and two bilinear reductions next to the saved soft-min of the forward pass."""
 
     @staticmethod
-    def forward(ctx, x, y, F, G, feat, eps, a, b):
+    def forward(ctx, x, y, F, G, feat, eps, a, b, resident=None):
         out, h, fwd, rows = _plan_p2(x, y, F, G, feat, eps, a, b)
         ctx.save_for_backward(x, y, F, G, feat, a, b, h, fwd, rows, out)
         ctx.eps = eps
+        ctx.resident = hip.resident_kw(resident)
         return out
 
     @staticmethod
@@ -117,7 +118,7 @@ class _ApplyPlan(torch.autograd.Function):
             Gb, S, out = Gb.unsqueeze(-1), S.unsqueeze(-1), out.unsqueeze(-1)
         dx = dy = dF = dG = dfeat = None
         if need_x:
-            o, _ = hip.plan_bilinear(eps, x, y, h, Gb, S, fwd=fwd)
+            o, _ = hip.plan_bilinear(eps, x, y, h, Gb, S, fwd=fwd, **ctx.resident)
             dx = _like((rows / eps).unsqueeze(-1) * o, x)
         if need_F:
             dF = _like((Gb * out).sum(-1) / eps, F)
@@ -128,7 +129,7 @@ class _ApplyPlan(torch.autograd.Function):
             fwdT = hip.softmin(eps, y.detach(), x.detach(), hT)        # sum_i a_i exp((F_i - C_ij) / eps) = exp(-fwdT_j / eps)
             cols = (_log_weights(b, Gf, y.shape[-2]) + (Gf - fwdT) / eps).exp()
             if need_y or need_G:
-                oT, wT = hip.plan_bilinear(eps, y, x, hT, S, Gb, fwd=fwdT)
+                oT, wT = hip.plan_bilinear(eps, y, x, hT, S, Gb, fwd=fwdT, **ctx.resident)
                 if need_y:
                     dy = _like((cols / eps).unsqueeze(-1) * oT, y)
                 if need_G:
@@ -136,7 +137,7 @@ class _ApplyPlan(torch.autograd.Function):
             if need_feat:
                 dS = cols.unsqueeze(-1) * hip.plan_apply_nd(eps, y, x, hT, Gb, fwd=fwdT)
                 dfeat = _like(dS[..., 0] if vector else dS, feat)
-        return dx, dy, dF, dG, dfeat, None, None, None
+        return dx, dy, dF, dG, dfeat, None, None, None, None
 
 
 def _map_p2(x, y, G, eps, b, want_fwd):
@@ -157,10 +158,11 @@ class _BarycentricMap(torch.autograd.Function):
         (oT, wT) = bil(y, x, fwd/eps; Sf, A)                      dy = pi^T Gd + colsum / eps * oT        dG = colsum / eps * wT"""
 
     @staticmethod
-    def forward(ctx, x, y, G, eps, b):
+    def forward(ctx, x, y, G, eps, b, resident=None):
         T, h, fwd = _map_p2(x, y, G, eps, b, True)
         ctx.save_for_backward(x, y, G, h, fwd, T)
         ctx.eps = eps
+        ctx.resident = hip.resident_kw(resident)
         return T
 
     @staticmethod
@@ -176,19 +178,19 @@ class _BarycentricMap(torch.autograd.Function):
         Sf = torch.cat([yf - cbar, torch.ones_like(yf[..., :1])], -1)
         dx = dy = dG = None
         if need_x:
-            o, w = hip.plan_bilinear(eps, x, y, h, A, Sf, fwd=fwd)
+            o, w = hip.plan_bilinear(eps, x, y, h, A, Sf, fwd=fwd, **ctx.resident)
             dx = _like((o + (x.detach().float() - T) * w.unsqueeze(-1)) / eps, x)
         if need_y or need_G:
             hT = fwd / eps
             fwdT = hip.softmin(eps, y.detach(), x.detach(), hT)        # colsum_j = exp(h_j - fwdT_j / eps)
             colsum = (h - fwdT / eps).exp()
-            oT, wT = hip.plan_bilinear(eps, y, x, hT, Sf, A, fwd=fwdT)
+            oT, wT = hip.plan_bilinear(eps, y, x, hT, Sf, A, fwd=fwdT, **ctx.resident)
             if need_y:
                 direct = colsum.unsqueeze(-1) * hip.plan_apply_nd(eps, y, x, hT, Gd, fwd=fwdT)
                 dy = _like(direct + (colsum / eps).unsqueeze(-1) * oT, y)
             if need_G:
                 dG = _like(colsum / eps * wT, G)
-        return dx, dy, dG, None, None
+        return dx, dy, dG, None, None, None
 
 
 def plan_ranges(x, y, F, G, blur, truncate=5, cluster_scale=None):
@@ -230,7 +232,7 @@ def _sparse_guard(name, p, *tensors):
         raise NotImplementedError(f"geomloss_amd.transport.{name}: no autograd through block-sparse ranges (detach the inputs)")
 
 
-def apply_plan(x, y, F, G, feat, blur, a=None, b=None, transpose=False, p=2, ranges=None):
+def apply_plan(x, y, F, G, feat, blur, a=None, b=None, transpose=False, p=2, ranges=None, resident=None):
     """``sum_j P_ij feat_j`` for the plan of the potentials ``F`` (N,)|(B,N), ``G`` (M,)|(B,M) on the clouds ``x`` (N,D)|(B,N,D),
     ``y`` (M,D)|(B,M,D) with weights ``a``, ``b`` (uniform by default): feat (M,V)|(B,M,V)|(M,) -> (N,V)|(B,N,V)|(N,) fp32.
     ``transpose=True`` applies the transposed plan instead: ``sum_i P_ij feat_i`` for feat on the rows, (N,V) -> (M,V).
@@ -247,9 +249,12 @@ def apply_plan(x, y, F, G, feat, blur, a=None, b=None, transpose=False, p=2, ran
     ``ranges`` (a :class:`geomloss_amd.hip.BlockRanges`, e.g. from :func:`plan_ranges`): the plan restricted to that block-sparse
     pattern, on the kernel of :func:`geomloss_amd.hip.plan_apply_sparse` — ``sum_{j kept} P_ij feat_j``.  Every input must already be in
     the order the ranges index; un-batched, p = 2, D <= 16, and no input may require grad (``NotImplementedError``).  ``None`` is the
-    dense call above, untouched."""
+    dense call above, untouched.
+
+    ``resident``: passed to both bilinear reductions of the backward pass (``True``: the resident-operand kernel of D <= 16 and at most 32
+    feature columns, ``NotImplementedError`` beyond; ``None``: GEOMLOSS_HIP_XD_BILINEAR).  The forward pass does not read it."""
     if transpose:
-        return apply_plan(y, x, G, F, feat, blur, a=b, b=a, p=p, ranges=None if ranges is None else ranges.t())
+        return apply_plan(y, x, G, F, feat, blur, a=b, b=a, p=p, ranges=None if ranges is None else ranges.t(), resident=resident)
     eps = _eps(blur, p)
     if ranges is not None:
         _sparse_guard("apply_plan", p, x, y, F, G, feat)
@@ -263,7 +268,7 @@ def apply_plan(x, y, F, G, feat, blur, a=None, b=None, transpose=False, p=2, ran
             return rows * avg if avg.dim() == rows.dim() else rows.unsqueeze(-1) * avg
     if p == 2:
         if _wants_grad(x, y, F, G, feat):
-            return _ApplyPlan.apply(x, y, F, G, feat, eps, a, b)
+            return _ApplyPlan.apply(x, y, F, G, feat, eps, a, b, resident)
         return _plan_p2(x, y, F, G, feat, eps, a, b)[0]
     with torch.no_grad():
         N, M = x.shape[-2], y.shape[-2]
@@ -275,7 +280,7 @@ def apply_plan(x, y, F, G, feat, blur, a=None, b=None, transpose=False, p=2, ran
         return rows * avg if avg.dim() == rows.dim() else rows.unsqueeze(-1) * avg
 
 
-def barycentric_map(x, y, F, G, blur, b=None, p=2, ranges=None):
+def barycentric_map(x, y, F, G, blur, b=None, p=2, ranges=None, resident=None):
     """``T(x_i) = sum_j P_ij y_j / sum_j P_ij`` (N,D)|(B,N,D) fp32: where the plan sends each x_i on average.  The row-normalised
     average does not depend on ``a`` or ``F`` (they scale a whole row); ``F`` is accepted so that the call reads like
     :func:`apply_plan`.  ``p`` as there.
@@ -287,7 +292,10 @@ def barycentric_map(x, y, F, G, blur, b=None, p=2, ranges=None):
     Otherwise — and always for ``p=1`` — the call runs as before and returns a tensor without ``grad_fn``.
 
     ``ranges``: as in :func:`apply_plan` — the average over the kept columns, inputs in the ranges' order, p = 2, no autograd; a row
-    without kept mass maps to 0."""
+    without kept mass maps to 0.
+
+    ``resident``: passed to both bilinear reductions of the backward pass (``True``: the resident-operand kernel, D <= 16 — its D + 1
+    features fit at D = 16 —, ``NotImplementedError`` beyond; ``None``: GEOMLOSS_HIP_XD_BILINEAR).  The forward pass does not read it."""
     eps = _eps(blur, p)
     if ranges is not None:
         _sparse_guard("barycentric_map", p, x, y, G)
@@ -296,7 +304,7 @@ def barycentric_map(x, y, F, G, blur, b=None, p=2, ranges=None):
             return hip.plan_apply_sparse(eps, x, y, _log_weights(b, Gf, y.shape[-2]) + Gf / eps, y.float(), ranges)
     if p == 2:
         if _wants_grad(x, y, G):
-            return _BarycentricMap.apply(x, y, G, eps, b)
+            return _BarycentricMap.apply(x, y, G, eps, b, resident)
         return _map_p2(x, y, G, eps, b, False)[0]
     with torch.no_grad():
         Gf = G.detach().float().reshape(y.shape[:-1])

@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 143 /* 0.1.43 */
+#define GLHIP_VERSION 144 /* 0.1.44 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
@@ -140,6 +140,16 @@ extern "C" {
                                   (ties, duplicates, -inf, missing ranks, prefixes, k = 1 = argmin, independence of the splits); against
                                   the other family values differ by rounding (another centre) and indices agree where float64 separates
                                   the candidates.  Every other entry point, and D > 16, ignore the flag, bit for bit. */
+#define GLHIP_FLAG_XD_BILINEAR 16384 /* version 144.  glhip_plan_bilinear with p == 2, 1 <= D <= 16, 1 <= K <= 32, dense launches
+                                  (n_ranges == 0), B <= 65535: the resident-operand kernel of csrc/glhip_plan_bilinear_xd.h — rows, row
+                                  features, columns, column features and the centred column coordinates packed once per call around one
+                                  centre per launch, tiles copied by LDS-DMA into two buffers, one 32 x 32 block per wavefront at a time —
+                                  instead of the K-chunked one.  glhip_plan_bilinear_family reports GLHIP_FAMILY_XD there.  The call then
+                                  REQUIRES a 16-byte aligned workspace of glhip_plan_bilinear_xd_workspace_bytes (GLHIP_EINVAL otherwise: it
+                                  never takes the other route silently).  Same contract as the other family (two running maxima, columns
+                                  and rows without mass, features of any common scale, no float atomics); values differ by rounding.
+                                  GLHIP_FLAG_F16X2 is accepted and ignored there (bf16 x 3 exponents only).  Every other entry point, and
+                                  D > 16 or K > 32, ignore the flag, bit for bit. */
 #define GLHIP_FLAG_NO_SORT 512 /* p = 1 soft-min / half-step, laplacian and energy products: big dense launches (B = 1, D <= 3, N >= 65536,
                                   N M >= 5e8, a workspace of glhip_workspace_bytes) sort both clouds into the workspace themselves — voxel sort along a
                                   boustrophedon path, csrc/glhip_autosort.h — so that the squared distances can come from the matrix cores
@@ -832,10 +842,20 @@ size_t glhip_arg_xd_workspace_bytes(int B, int N, int M, int D, int k);
  * unsupported or empty shapes; NULL or a short buffer means fewer or no splits, with the same results up to summation order.
  * glhip_plan_bilinear_supported: host arithmetic only, the predicate the launch itself evaluates — 1, 0 for valid requests without a
  * kernel, GLHIP_EINVAL for what the entry point rejects (negative sizes, D < 1, K < 0, a bad p or dtype).
- * Not here: gradients with respect to the weights, second derivatives, float64, a resident-operand variant for D <= 16.
+ * Not here: gradients with respect to the weights, second derivatives, float64.
+ * Version 144, GLHIP_FLAG_XD_BILINEAR: the resident-operand kernel of csrc/glhip_plan_bilinear_xd.h for 1 <= D <= 16, 1 <= K <= 32.
+ * glhip_plan_bilinear_family: host arithmetic only, the predicate the launch evaluates — GLHIP_FAMILY_XD under the flag inside that
+ * domain (p == 2, n_ranges == 0, B <= 65535), GLHIP_FAMILY_XK for every other launch glhip_plan_bilinear serves, 0 for valid requests
+ * without a kernel, GLHIP_EINVAL as glhip_plan_bilinear_supported.
+ * glhip_plan_bilinear_xd_workspace_bytes: what a flagged call in the domain needs — the packed rows and row features, one centred
+ * float per row and coordinate, the packed columns (exponent records, column-feature records, 4 KiB of coordinate pieces per group of
+ * 32 columns), one scale per group and the (T[D], W, mass, m) partials of the column splits the launch would like, each part rounded
+ * up to 256 bytes.  Non-decreasing in M and K; 0 for an empty cloud or outside 1 <= D <= 16, 1 <= K <= 32.
  */
 int glhip_plan_bilinear_supported(int B, long N, long M, int D, int K, int p, int dtype, int n_ranges);
 int glhip_plan_bilinear_pass_width(void);
+int glhip_plan_bilinear_family(int B, long N, long M, int D, int K, int p, int dtype, int n_ranges, int flags);
+size_t glhip_plan_bilinear_xd_workspace_bytes(int B, int N, int M, int D, int K);
 size_t glhip_plan_bilinear_workspace_bytes(int B, int N, int M, int D, int K);
 int glhip_plan_bilinear(const void* x, const void* y, const float* h, const float* fwd, const float* rowfeat, const float* colfeat,
                         float* out, float* wsum, int B, int N, int M, int D, int K, float eps, int p, int in_dtype,

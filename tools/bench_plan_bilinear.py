@@ -3,10 +3,13 @@ numbers without it, and the wall time of ``barycentric_map`` forward and forward
 
     python tools/bench_plan_bilinear.py [--n 200000] [--shapes 3,3 3,32 32,32 64,64 128,128] [--rounds 5] [--warmup 1]
                                         [--route-cols 1024] [--route-rounds 3] [--map-dims 3 64] [--out profiles/plan_bilinear.txt]
+                                        [--resident]
 
 Part 1 — float32 clouds (x uniform in the unit cube, y in its middle), N = M = --n, eps = 0.1 D / 3, standard-normal features, the
 saved soft-min given to every launch.  Per (D, K), alternated in one process on one GPU, each call between two HIP events:
-  (i)   ``hip.plan_bilinear``;
+  (i)   ``hip.plan_bilinear`` (``resident=False``: xk_bilinear_kernel);
+  (i')  with --resident, where D <= 16 and K <= 32: ``hip.plan_bilinear(..., resident=True)``, the resident-operand kernel
+        (glhip_plan_bilinear_xd.h), packing included; profiles/plan_bilinear_xd.txt is such a run;
   (ii)  one ``hip.plan_apply_nd`` of K feature columns: the "one pass" yardstick;
   (iii) the route without the kernel: ``hip.plan_apply_nd`` on the K D columns ``colfeat (x) (y - c)``, contracted with ``rowfeat`` in
         torch.  The columns are built and applied --route-cols at a time (K D floats per point do not fit otherwise); when K D exceeds
@@ -15,7 +18,8 @@ Medians, minima, the spread (max - min) / median; then (i) / (ii) and (iii) / (i
 against float64.  No ratio is asserted: the figures are printed.
 
 Part 2 — ``barycentric_map`` at N = M = --n for every D of --map-dims: wall time (host clock around a synchronised call) of the forward
-pass without a graph, and of forward + backward of ``(T - target)^2`` with x and y requiring grad."""
+pass without a graph, and of forward + backward of ``(T - target)^2`` with x and y requiring grad; with --resident and D <= 16 the
+latter also with ``resident=True``, alternated with the default."""
 import argparse
 import os
 import statistics
@@ -50,9 +54,9 @@ def line(tag, name, ms, scale=1.0):
     return med
 
 
-def check(eps, x, y, h, rf, cf, fwd, rows=128):
+def check(eps, x, y, h, rf, cf, fwd, rows=128, resident=False):
     """Largest error of the first rows against float64, relative to the unsigned sums."""
-    out, wsum = hip.plan_bilinear(eps, x, y, h, rf, cf, fwd=fwd)
+    out, wsum = hip.plan_bilinear(eps, x, y, h, rf, cf, fwd=fwd, resident=resident)
     xd, yd, hd, rd, cd = (t.double() for t in (x[:rows], y, h, rf[:rows], cf))
     E = hd[None, :] - torch.cdist(xd, yd) ** 2 / (2 * eps)
     q = torch.softmax(E, 1) * (rd @ cd.T)
@@ -81,6 +85,7 @@ def main():
     ap.add_argument("--route-cols", type=int, default=1024)
     ap.add_argument("--route-rounds", type=int, default=3)
     ap.add_argument("--map-dims", type=int, nargs="*", default=[3, 64])
+    ap.add_argument("--resident", action="store_true", help="also time resident=True where D <= 16 and K <= 32")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "plan_bilinear.txt"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -107,8 +112,11 @@ def main():
         cols = K * D
         c1 = min(cols, args.route_cols)
         scale = cols / c1
-        launches = [("(i)   plan_bilinear", lambda: hip.plan_bilinear(eps, x, y, h, rf, cf, fwd=fwd)),
+        launches = [("(i)   plan_bilinear", lambda: hip.plan_bilinear(eps, x, y, h, rf, cf, fwd=fwd, resident=False)),
                     (f"(ii)  plan_apply_nd, V = {K}", lambda: hip.plan_apply_nd(eps, x, y, h, cf, fwd=fwd))]
+        xd = args.resident and D <= hip.XD_MAX_DIM and K <= hip.PLAN_BILINEAR_XD_MAX_K
+        if xd:
+            launches.append(("(i')  plan_bilinear, resident=True", lambda: hip.plan_bilinear(eps, x, y, h, rf, cf, fwd=fwd, resident=True)))
         rname = f"(iii) plan_apply_nd on {cols} columns + contraction" + (f" [one slice of {c1}, x {scale:.1f}]" if scale > 1 else "")
         eo, ew = check(eps, x, y, h, rf, cf, fwd)
         for _ in range(args.warmup):
@@ -130,6 +138,10 @@ def main():
             rmed = line(tag, rname, rms, scale)
             text += f";  (iii) / (i) = {rmed / med[0]:.2f}"
         say(text + f";  first 128 rows against float64: out {eo:.2e}, wsum {ew:.2e} of the unsigned sums")
+        if xd:
+            xo, xw = check(eps, x, y, h, rf, cf, fwd, resident=True)
+            say(f"  {tag:>9s} (i') / (i) = {med[2] / med[0]:.2f};  (i') / (ii) = {med[2] / med[1]:.2f}" + (f";  (i') / (iii) = {med[2] / rmed:.2f}" if rms else "")
+                + f";  first 128 rows against float64: out {xo:.2e}, wsum {xw:.2e}")
         del x, y, h, rf, cf, fwd, yc
         torch.cuda.empty_cache()
 
@@ -147,20 +159,24 @@ def main():
             with torch.no_grad():
                 barycentric_map(x, y, F, G, blur)
 
-        def both():
+        def both(resident=False):
             xg, yg = x.clone().requires_grad_(True), y.clone().requires_grad_(True)
-            (barycentric_map(xg, yg, F, G, blur) - target).pow(2).sum().backward()
+            (barycentric_map(xg, yg, F, G, blur, resident=resident) - target).pow(2).sum().backward()
 
-        for name, fn in (("forward", forward), ("forward + backward (x, y)", both)):
-            ts = []
-            for r in range(args.warmup + args.rounds):
+        cases = [("forward", forward), ("forward + backward (x, y)", both)]
+        if args.resident and D <= hip.XD_MAX_DIM:
+            cases.append(("forward + backward, resident", lambda: both(True)))
+        ts = {name: [] for name, _ in cases}
+        for r in range(args.warmup + args.rounds):      # alternated
+            for name, fn in cases:
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 fn()
                 torch.cuda.synchronize()
                 if r >= args.warmup:
-                    ts.append((time.perf_counter() - t0) * 1e3)
-            say(f"  D = {D:4d} barycentric_map {name:28s} {statistics.median(ts):10.3f} {min(ts):10.3f}")
+                    ts[name].append((time.perf_counter() - t0) * 1e3)
+        for name, _ in cases:
+            say(f"  D = {D:4d} barycentric_map {name:28s} {statistics.median(ts[name]):10.3f} {min(ts[name]):10.3f} {(max(ts[name]) - min(ts[name])) / statistics.median(ts[name]):7.1%}")
     say("# not timed: bfloat16 clouds, batches, D > 128, gradients of apply_plan")
     with open(args.out, "w") as f:
         f.write("\n".join(LINES) + "\n")
