@@ -24,6 +24,7 @@ FLAG_XK_DIST_GRAD = 4096        # the p = 1 soft-min, laplacian and energy row g
 DIST_GRAD_OPS = {"softmin_p1": 0, "laplacian": 1, "energy": 2}      # ops of glhip_dist_grad_uses_xk (GLHIP_DIST_GRAD_*)
 FLAG_XD_ARG = 8192              # argmin / argkmin of p = 2, D <= 16, dense launches: the resident-operand kernels (glhip_arg_xd.h)
 FLAG_XD_BILINEAR = 16384        # plan_bilinear of p = 2, D <= 16, K <= 32, dense launches: the resident-operand kernel (glhip_plan_bilinear_xd.h)
+FLAG_XD_PLAN_P1 = 32768         # plan_apply_p1 of D <= 16, dense launches: the resident-operand kernel (glhip_dist_plan_xd.h)
 FLAG_GRAD_FAMILY = FLAG_XDL16   # kernel products rounded like the product-and-gradient kernel of the same kind (glhip.h)
 XD_MAX_DIM = 16                 # the fused four-softmin iteration / annealing / extrapolation, the one-pass value + gradient and the matrix-core
                                 # gradients stop at this dimension (glhip_softmin_xd.h, glhip_wsum_t32.h)
@@ -81,6 +82,9 @@ SIGNATURES = {
     "glhip_plan_apply_p1_supported": (_c_int, [_c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int]),
     "glhip_plan_apply_p1_pass_width": (_c_int, []),
     "glhip_plan_apply_p1_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "glhip_plan_apply_p1_family": (_c_int, [_c_int, _c_long, _c_long] + [_c_int] * 5),
+    "glhip_plan_apply_p1_xd_pass_width": (_c_int, [_c_int]),
+    "glhip_plan_apply_p1_xd_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "glhip_plan_apply_p1": (_c_int, [_vp] * 6 + [_c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int] + _RANGES + _TAIL),
     "glhip_plan_apply_sparse_supported": (_c_int, [_c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int, _c_int]),
     "glhip_plan_apply_sparse_workspace_bytes": (_c_size, [_c_int] * 6),
@@ -145,7 +149,8 @@ _SINCE = {"glhip_sinkhorn_step_perm": 134, "glhip_softmin_perm_applies": 134,
           "glhip_plan_bilinear": 139,
           "glhip_argkmin_passes": 141, "glhip_arg_family": 142, "glhip_arg_xd_workspace_bytes": 142,
           "glhip_plan_apply_sparse_supported": 143, "glhip_plan_apply_sparse_workspace_bytes": 143, "glhip_plan_apply_sparse": 143,
-          "glhip_plan_bilinear_family": 144, "glhip_plan_bilinear_xd_workspace_bytes": 144}
+          "glhip_plan_bilinear_family": 144, "glhip_plan_bilinear_xd_workspace_bytes": 144,
+          "glhip_plan_apply_p1_family": 145, "glhip_plan_apply_p1_xd_pass_width": 145, "glhip_plan_apply_p1_xd_workspace_bytes": 145}
 
 _lib = None
 

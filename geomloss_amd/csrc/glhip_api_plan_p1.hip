@@ -1,7 +1,8 @@
 // glhip_api_plan_p1.hip — C-ABI part 14: the plan of a p = 1 soft-min applied to features, 1 <= D <= 4095 (glhip_plan_apply_p1):
 // xk_dist_plan_kernel (glhip_dist_plan_xk.h), the exponent half of xk_dist_kernel joined with the plan half of xk_plan_kernel.  It
-// normalises itself and returns the soft-min on the side, so no saved forward value comes in.  A translation unit of its own: the parallel
-// build does not get longer.
+// normalises itself and returns the soft-min on the side, so no saved forward value comes in.  Under GLHIP_FLAG_XD_PLAN_P1, 1 <= D <= 16 go
+// to the resident-operand kernel of glhip_dist_plan_xd.h (plan_p1_family, glhip_family.h; its launch: glhip_api_plan_p1_xd.hip).  A
+// translation unit of its own: the parallel build does not get longer.
 #include "glhip_launch_plan.h"
 #include "glhip_dist_plan_xk.h"
 
@@ -67,6 +68,8 @@ int glhip_plan_apply_p1(const void* x, const void* y, const float* h, const floa
         return check_launch("glhip_plan_apply_p1");
     }
     if (V > 0 && !feat) return fail(GLHIP_EINVAL, "glhip_plan_apply_p1: NULL feat");
+    if (plan_p1_family(B, N, M, D, V, in_dtype, n_ranges, flags) == GLHIP_FAMILY_XD)      // GLHIP_FLAG_XD_PLAN_P1: resident operands (glhip_dist_plan_xd.h)
+        return plan_p1_xd_launch(x, y, h, feat, out, softmin, B, N, M, D, V, eps, in_dtype, workspace, workspace_bytes, flags, stream);
     // GLHIP_FLAG_F16X2 is ignored: a squared distance needs all 24 bits
     const Scratch sc = make_scratch(workspace, workspace_bytes, V == 0 ? (flags | GLHIP_FLAG_NO_SPLIT) : flags, 0, N);
     auto run = [&](auto tag) {

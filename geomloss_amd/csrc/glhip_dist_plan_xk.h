@@ -25,8 +25,8 @@
 // that depends on timing: bit-identical run to run.  Rows that no column reached, rows whose duals are all -inf (Z == 0), padded columns
 // and columns with h = -inf write / contribute 0, never NaN; the soft-min of a row without mass is +inf.
 //
-// ONE kernel for 1 <= D <= 4095: below D = 17 the chain is a single stage (NM = 1 at D = 1, 6 = one whole stage at D = 15); a
-// resident-operand variant for D <= 16 is a follow-up.
+// ONE kernel for 1 <= D <= 4095: below D = 17 the chain is a single stage (NM = 1 at D = 1, 6 = one whole stage at D = 15); the
+// resident-operand variant for D <= 16 is xd_dist_plan_kernel (glhip_dist_plan_xd.h), behind GLHIP_FLAG_XD_PLAN_P1.
 //
 // Width of a pass: TWO chunks of 32 features (kXkDistPlanChunks = 2), a pass of <= 32 features runs the one-chunk instantiation; wider
 // feature matrices take further passes (launch_plan_passes), a remainder is a pass of its own.  Next to the state of xk_plan_kernel a

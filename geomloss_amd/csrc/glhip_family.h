@@ -130,6 +130,19 @@ int plan_bilinear_xd_launch(const void* x, const void* y, const float* h, const 
                             float* wsum, int B, int N, int M, int D, int K, float eps, int in_dtype, void* workspace, size_t workspace_bytes,
                             int flags, void* stream);
 
+// ... and of the p = 1 plan: THE predicate of glhip_plan_apply_p1, and what glhip_plan_apply_p1_family reports (0: a valid request without
+// a kernel, as glhip_plan_apply_p1_supported).  GLHIP_FAMILY_XD: the resident-operand kernel of glhip_dist_plan_xd.h, on the caller's word
+// (GLHIP_FLAG_XD_PLAN_P1) for D <= 16; GLHIP_FAMILY_XK: xk_dist_plan_kernel, every other launch served.
+inline int plan_p1_family(int B, long N, long M, int D, int V, int dtype, int n_ranges, int flags) {
+    if (plan_family_bad_args(B, N, M, D, dtype, n_ranges) || V < 0) return GLHIP_EINVAL;
+    if (n_ranges > 0 || D > kSizedMaxD || B > 65535) return 0;
+    return ((flags & GLHIP_FLAG_XD_PLAN_P1) && D <= kXdMaxD) ? GLHIP_FAMILY_XD : GLHIP_FAMILY_XK;
+}
+// The launch of GLHIP_FAMILY_XD (glhip_api_plan_p1_xd.hip): glhip_plan_apply_p1 hands its checked arguments over (B, N, M >= 1; V == 0 only
+// with a soft-min wanted).
+int plan_p1_xd_launch(const void* x, const void* y, const float* h, const float* feat, float* out, float* softmin, int B, int N, int M, int D,
+                      int V, float eps, int in_dtype, void* workspace, size_t workspace_bytes, int flags, void* stream);
+
 // the op of a laplacian / energy gradient (glhip_dist_grad_uses_xk, dist_grad_xk_launch) is its kind
 static_assert(GLHIP_DIST_GRAD_LAPLACIAN == GLHIP_LAPLACIAN && GLHIP_DIST_GRAD_ENERGY == GLHIP_ENERGY, "include/glhip.h");
 

@@ -488,7 +488,9 @@ def plan_apply_p1_raw(xb, yb, hb, fb, eps, flags=0, want_softmin=False, workspac
     """The plan of a p = 1 soft-min applied to features (``glhip_plan_apply_p1``, any D <= PLAN_P1_MAX_DIM): xb (B,N,D), yb (B,M,D)
     fp32|bf16, hb (B,M), fb (B,M,V) fp32 -> (B,N,V) fp32 row-normalised averages [, (B,N) the soft-min computed on the side].  The kernel
     normalises itself: no saved forward value comes in.  ``workspace=False`` passes no workspace: the launch runs without column splits
-    (same results up to summation order)."""
+    (same results up to summation order).  Under FLAG_XD_PLAN_P1, where the library's predicate names the resident-operand kernel
+    (D <= 16), ``workspace=True`` sizes the scratch with ``glhip_plan_apply_p1_xd_workspace_bytes``; a number of bytes passes a scratch
+    of exactly that size (the library refuses a flagged call whose workspace is short)."""
     lib = load_library()
     B, N, D = xb.shape
     M, V = yb.shape[1], fb.shape[2]
@@ -499,7 +501,13 @@ def plan_apply_p1_raw(xb, yb, hb, fb, eps, flags=0, want_softmin=False, workspac
     out = torch.empty((B, N, V), dtype=torch.float32, device=xb.device)
     soft = torch.empty((B, N), dtype=torch.float32, device=xb.device) if want_softmin else None
     with torch.cuda.device(xb.device):
-        ws, ws_args = _scratch(int(lib.glhip_plan_apply_p1_workspace_bytes(B, N, M, D, V)) if workspace else 0, xb.device)
+        if workspace is True and N and M and lib.glhip_plan_apply_p1_family(B, N, M, D, V, F32, 0, int(flags)) == FAMILY_XD:
+            nbytes = lib.glhip_plan_apply_p1_xd_workspace_bytes(B, N, M, D, V)
+        elif workspace is True:
+            nbytes = lib.glhip_plan_apply_p1_workspace_bytes(B, N, M, D, V)
+        else:
+            nbytes = workspace or 0
+        ws, ws_args = _scratch(int(nbytes), xb.device)
         rc = lib.glhip_plan_apply_p1(xb.data_ptr(), yb.data_ptr(), hb.data_ptr(), fb.data_ptr(), out.data_ptr(), _ptr(soft),
                                      B, N, M, D, V, float(eps), _dtype_code(xb), *_NO_RANGES, *ws_args, int(flags), _stream(xb))
     _check(rc, lib)
@@ -1378,7 +1386,7 @@ def plan_apply_p1_applies(x, ranges=None):
     return ranges is None and 1 <= x.shape[-1] <= PLAN_P1_MAX_DIM and x.dtype != torch.float64
 
 
-def plan_apply_p1(eps, x, y, h, feat, flags=0, want_softmin=False, ranges=None):
+def plan_apply_p1(eps, x, y, h, feat, flags=0, want_softmin=False, ranges=None, resident=None):
     """Row-normalised application of the plan of a p = 1 soft-min to a feature matrix on the matrix cores (``glhip_plan_apply_p1``,
     glhip_dist_plan_xk.h), for clouds of any dimension D <= PLAN_P1_MAX_DIM = 4095:
 
@@ -1391,10 +1399,15 @@ def plan_apply_p1(eps, x, y, h, feat, flags=0, want_softmin=False, ranges=None):
     ``glhip_plan_apply_p1_pass_width()`` feature columns; a remainder is a pass of its own.  One-hot plan rows return their features bit
     for bit, rows without mass give 0 (soft-min +inf), results are bit-identical run to run.  NOT an autograd function: it runs under
     ``torch.no_grad()`` and returns tensors without ``grad_fn``.  float64 clouds, D > 4095 and block-sparse ranges raise
-    ``NotImplementedError``."""
+    ``NotImplementedError``.
+    ``resident=True`` (FLAG_XD_PLAN_P1, D <= 16 only, ``NotImplementedError`` beyond) runs the resident-operand kernel of
+    glhip_dist_plan_xd.h: both clouds packed once per call, the features once per pass of ``glhip_plan_apply_p1_xd_pass_width(D)``
+    columns, same contract, values within rounding of the default route; ``False`` never does; ``None`` follows GEOMLOSS_HIP_XD_PLAN_P1
+    (default 0)."""
     D = x.shape[-1]
     if x.dtype == torch.float64 or y.dtype == torch.float64:
         raise NotImplementedError("geomloss_amd.hip.plan_apply_p1: float64 clouds are not supported (cast to float32)")
+    flags = int(flags) | _resident("plan_apply_p1", resident, D, FLAG_XD_PLAN_P1, _XD_PLAN_P1_DEFAULT)
     if D > PLAN_P1_MAX_DIM or ranges is not None:
         raise NotImplementedError(f"geomloss_amd.hip.plan_apply_p1: only D <= {PLAN_P1_MAX_DIM}, dense plans (got D = {D}, "
                                   f"ranges {'given' if ranges is not None else 'None'})")
@@ -1797,10 +1810,13 @@ _XD_ARG_DEFAULT = os.environ.get("GEOMLOSS_HIP_XD_ARG", "0") != "0"
 # GEOMLOSS_HIP_XD_BILINEAR: the same for :func:`plan_bilinear` and, through it, the backward passes of ``geomloss_amd.transport`` (default 0:
 # xk_bilinear_kernel; 1: the resident-operand kernel of glhip_plan_bilinear_xd.h wherever it applies, D <= XD_MAX_DIM and K <= 32)
 _XD_BILINEAR_DEFAULT = os.environ.get("GEOMLOSS_HIP_XD_BILINEAR", "0") != "0"
+# GEOMLOSS_HIP_XD_PLAN_P1: the same for :func:`plan_apply_p1` and, through it, the p = 1 forward passes of ``geomloss_amd.transport`` (default 0:
+# xk_dist_plan_kernel; 1: the resident-operand kernel of glhip_dist_plan_xd.h wherever it applies, D <= XD_MAX_DIM)
+_XD_PLAN_P1_DEFAULT = os.environ.get("GEOMLOSS_HIP_XD_PLAN_P1", "0") != "0"
 
 
 def _resident(name, resident, D, flag=FLAG_XD_ARG, default=None, K=1, max_k=1):
-    """``flag`` (FLAG_XD_ARG, FLAG_XD_BILINEAR) or 0 for a call of ``name`` in dimension D with K features: ``True`` asks for the
+    """``flag`` (FLAG_XD_ARG, FLAG_XD_BILINEAR, FLAG_XD_PLAN_P1) or 0 for a call of ``name`` in dimension D with K features: ``True`` asks for the
     resident-operand kernels (``NotImplementedError`` beyond D = XD_MAX_DIM or outside 1 <= K <= max_k), ``False`` never sets the flag,
     ``None`` follows the knob of the flag (``default``; None: GEOMLOSS_HIP_XD_ARG) where they apply."""
     inside = D <= XD_MAX_DIM and 1 <= K <= max_k
@@ -1813,7 +1829,7 @@ def _resident(name, resident, D, flag=FLAG_XD_ARG, default=None, K=1, max_k=1):
 
 
 def resident_kw(resident):
-    """The keyword a caller of :func:`argmin` / :func:`argkmin` / :func:`plan_bilinear` hands its own ``resident=`` on with: nothing for ``None``, so that the
+    """The keyword a caller of :func:`argmin` / :func:`argkmin` / :func:`plan_bilinear` / :func:`plan_apply_p1` hands its own ``resident=`` on with: nothing for ``None``, so that the
     call reads as it did before the keyword existed."""
     return {} if resident is None else {"resident": resident}
 

@@ -252,7 +252,9 @@ def apply_plan(x, y, F, G, feat, blur, a=None, b=None, transpose=False, p=2, ran
     dense call above, untouched.
 
     ``resident``: passed to both bilinear reductions of the backward pass (``True``: the resident-operand kernel of D <= 16 and at most 32
-    feature columns, ``NotImplementedError`` beyond; ``None``: GEOMLOSS_HIP_XD_BILINEAR).  The forward pass does not read it."""
+    feature columns, ``NotImplementedError`` beyond; ``None``: GEOMLOSS_HIP_XD_BILINEAR).  The forward pass of ``p=2`` does not read it;
+    that of ``p=1`` hands it to :func:`geomloss_amd.hip.plan_apply_p1` (``True``: the resident-operand kernel of glhip_dist_plan_xd.h, D <= 16,
+    ``NotImplementedError`` beyond; ``None``: GEOMLOSS_HIP_XD_PLAN_P1), ``transpose=True`` included."""
     if transpose:
         return apply_plan(y, x, G, F, feat, blur, a=b, b=a, p=p, ranges=None if ranges is None else ranges.t(), resident=resident)
     eps = _eps(blur, p)
@@ -275,7 +277,7 @@ def apply_plan(x, y, F, G, feat, blur, a=None, b=None, transpose=False, p=2, ran
         Ff = F.detach().float().reshape(x.shape[:-1])
         Gf = G.detach().float().reshape(y.shape[:-1])
         h = _log_weights(b, Gf, M) + Gf / eps
-        avg, fwd = hip.plan_apply_p1(eps, x, y, h, feat, want_softmin=True)      # sum_j b_j exp((G_j - C_ij) / eps) = exp(-fwd_i / eps)
+        avg, fwd = hip.plan_apply_p1(eps, x, y, h, feat, want_softmin=True, **hip.resident_kw(resident))      # sum_j b_j exp((G_j - C_ij) / eps) = exp(-fwd_i / eps)
         rows = (_log_weights(a, Ff, N) + (Ff - fwd) / eps).exp()                  # sum_j P_ij
         return rows * avg if avg.dim() == rows.dim() else rows.unsqueeze(-1) * avg
 
@@ -295,7 +297,9 @@ def barycentric_map(x, y, F, G, blur, b=None, p=2, ranges=None, resident=None):
     without kept mass maps to 0.
 
     ``resident``: passed to both bilinear reductions of the backward pass (``True``: the resident-operand kernel, D <= 16 — its D + 1
-    features fit at D = 16 —, ``NotImplementedError`` beyond; ``None``: GEOMLOSS_HIP_XD_BILINEAR).  The forward pass does not read it."""
+    features fit at D = 16 —, ``NotImplementedError`` beyond; ``None``: GEOMLOSS_HIP_XD_BILINEAR).  The forward pass of ``p=2`` does not read
+    it; that of ``p=1`` hands it to :func:`geomloss_amd.hip.plan_apply_p1` (``True``: the resident-operand kernel of D <= 16; ``None``:
+    GEOMLOSS_HIP_XD_PLAN_P1)."""
     eps = _eps(blur, p)
     if ranges is not None:
         _sparse_guard("barycentric_map", p, x, y, G)
@@ -309,7 +313,7 @@ def barycentric_map(x, y, F, G, blur, b=None, p=2, ranges=None, resident=None):
     with torch.no_grad():
         Gf = G.detach().float().reshape(y.shape[:-1])
         h = _log_weights(b, Gf, y.shape[-2]) + Gf / eps
-        return hip.plan_apply_p1(eps, x, y, h, y.detach().float())
+        return hip.plan_apply_p1(eps, x, y, h, y.detach().float(), **hip.resident_kw(resident))
 
 
 def plan_argmax(x, y, F, G, blur, b=None, resident=None):

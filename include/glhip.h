@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 144 /* 0.1.44 */
+#define GLHIP_VERSION 145 /* 0.1.45 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
@@ -150,6 +150,17 @@ extern "C" {
                                   and rows without mass, features of any common scale, no float atomics); values differ by rounding.
                                   GLHIP_FLAG_F16X2 is accepted and ignored there (bf16 x 3 exponents only).  Every other entry point, and
                                   D > 16 or K > 32, ignore the flag, bit for bit. */
+#define GLHIP_FLAG_XD_PLAN_P1 32768 /* version 145.  glhip_plan_apply_p1 with 1 <= D <= 16, dense launches (n_ranges == 0), B <= 65535: the
+                                  resident-operand kernel of csrc/glhip_dist_plan_xd.h — rows and columns packed once per call into the
+                                  bf16 x 3 distance records around one centre per launch, the features of a pass packed once per pass as
+                                  f16 x 2 pieces under a power-of-two scale per group of 32 columns, tiles copied by LDS-DMA into two
+                                  buffers, one 32 x 32 block per wavefront at a time — instead of the K-chunked one.
+                                  glhip_plan_apply_p1_family reports GLHIP_FAMILY_XD there.  The call then REQUIRES a 16-byte aligned
+                                  workspace of glhip_plan_apply_p1_xd_workspace_bytes (GLHIP_EINVAL otherwise: it never takes the other
+                                  route silently).  Same contract as the other family (self-normalising, one-hot rows bit for bit, rows
+                                  and columns without mass, no float atomics); values differ by rounding (another centre, another
+                                  feature scale).  GLHIP_FLAG_NO_SPLIT is honoured, GLHIP_FLAG_F16X2 ignored.  Every other entry point,
+                                  and D > 16, ignore the flag, bit for bit. */
 #define GLHIP_FLAG_NO_SORT 512 /* p = 1 soft-min / half-step, laplacian and energy products: big dense launches (B = 1, D <= 3, N >= 65536,
                                   N M >= 5e8, a workspace of glhip_workspace_bytes) sort both clouds into the workspace themselves — voxel sort along a
                                   boustrophedon path, csrc/glhip_autosort.h — so that the squared distances can come from the matrix cores
@@ -573,7 +584,22 @@ int glhip_plan_apply_nd(const void* x, const void* y, const float* h, const floa
  * glhip_plan_apply_p1_supported: host arithmetic only, the predicate the launch itself evaluates — 1, 0 for valid requests without a
  * kernel, GLHIP_EINVAL for what the entry point rejects (negative sizes, D < 1, bad dtype).
  * glhip_plan_apply and glhip_plan_apply_nd keep refusing p = 1.
+ * Version 145, GLHIP_FLAG_XD_PLAN_P1: the resident-operand kernel of csrc/glhip_dist_plan_xd.h for 1 <= D <= 16; the edge cases above
+ * (M == 0, V == 0, N == 0, B == 0) behave the same under the flag.
+ * glhip_plan_apply_p1_family: host arithmetic only, the predicate the launch evaluates — GLHIP_FAMILY_XD under the flag inside that
+ * domain (n_ranges == 0, B <= 65535), GLHIP_FAMILY_XK wherever glhip_plan_apply_p1_supported is 1 otherwise, 0 for valid requests
+ * without a kernel, GLHIP_EINVAL as glhip_plan_apply_p1_supported.
+ * glhip_plan_apply_p1_xd_pass_width: feature columns one pass of that kernel carries in dimension D (a multiple of 32; a remainder is
+ * a pass of its own), 0 outside 1 <= D <= 16.
+ * glhip_plan_apply_p1_xd_workspace_bytes: what a flagged call in the domain needs — the packed rows and one float per row, the packed
+ * columns and one float per column, the feature pieces (128 bytes per column and chunk of 32 features) and scales of the widest pass,
+ * min(V, pass width) features, and the (sums[nv], Z, m) partials of the column splits the launch would like, each part rounded up to
+ * 256 bytes.  Non-decreasing in N, M and min(V, pass width); V == 0 (the soft-min alone) is sized as one chunk without splits; 0 for an
+ * empty cloud, V < 0 or outside 1 <= D <= 16.
  */
+int glhip_plan_apply_p1_family(int B, long N, long M, int D, int V, int dtype, int n_ranges, int flags);
+int glhip_plan_apply_p1_xd_pass_width(int D);
+size_t glhip_plan_apply_p1_xd_workspace_bytes(int B, int N, int M, int D, int V);
 int glhip_plan_apply_p1_supported(int B, long N, long M, int D, int V, int dtype, int n_ranges);
 int glhip_plan_apply_p1_pass_width(void);
 size_t glhip_plan_apply_p1_workspace_bytes(int B, int N, int M, int D, int V);

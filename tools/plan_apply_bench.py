@@ -13,6 +13,9 @@ V = 32 product at --big (1e6: 3 calls after 1).  Medians over --launches calls a
     python tools/plan_apply_bench.py --p 1 --dims 3 32 128 --widths 3 32 128 --legacy --budget-ms 4000
                                                      # the p = 1 product (glhip_plan_apply_p1), one p = 1 forward reduction and, with
                                                      # --legacy, the loop of 2 V reductions it replaces, alternated in one process
+    python tools/plan_apply_bench.py --p 1 --resident --dims 3 8 16 --widths 3 32 128 --budget-ms 4000
+                                                     # per shape, in turns in one process: the default route (flag off), the
+                                                     # resident-operand route (FLAG_XD_PLAN_P1, packing included) and one p = 1 forward
 
 The solve itself is not timed: the potentials are a few Sinkhorn iterations at a moderate temperature, enough for a well-formed plan."""
 import argparse
@@ -47,6 +50,26 @@ def timed(fn, launches, warmup, budget_ms=0.0):
         ms.append(a.elapsed_time(b))
     med = statistics.median(ms)
     return med, min(ms), (max(ms) - min(ms)) / med
+
+
+def alternated(fns, launches, warmup, budget_ms=0.0):
+    """`timed` for several callables taken in turns — one call of each per round — so that drift of the clocks hits them alike."""
+    for fn in fns:
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    ms = [[] for _ in fns]
+    for r in range(launches):
+        for k, fn in enumerate(fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            ms[k].append(a.elapsed_time(b))
+        if budget_ms > 0 and r >= 2 and sum(sum(m) for m in ms) > budget_ms:      # at least 3 rounds
+            break
+    return [(statistics.median(m), min(m), (max(m) - min(m)) / statistics.median(m)) for m in ms]
 
 
 def features(n, V, g, dev):
@@ -88,7 +111,8 @@ def run_p1(args, lib, dev):
     ``hip.softmin(p=1)`` forward reduction of the same shape and, with --legacy, the log-domain loop the product replaces — 2 V forward
     reductions, the positive and the negative part of every column — alternated with it in the same process.  FLAG_XK_DIST where D > 16;
     eps = 0.05 sqrt(D).  The loop is timed with one warm-up call."""
-    print(f"# libgeomloss_hip {lib.glhip_version()}; p = 1; float32; pass width {lib.glhip_plan_apply_p1_pass_width()}; median (min, spread) "
+    print(f"# libgeomloss_hip {lib.glhip_version()}; p = 1; float32; pass width {lib.glhip_plan_apply_p1_pass_width()}"
+          + (f" (resident: {lib.glhip_plan_apply_p1_xd_pass_width(3)})" if args.resident else "") + f"; median (min, spread) "
           f"of up to {args.launches} calls after {args.warmup}; {torch.cuda.get_device_name(0)}")
     n = args.n
     for D in args.dims if args.dims is not None else [3]:
@@ -100,7 +124,16 @@ def run_p1(args, lib, dev):
         xb, yb, hb = x[None].contiguous(), y[None].contiguous(), h[None].contiguous()
         fwd_ms, lo, spread = timed(lambda: hip.softmin(eps, x, y, h, p=1, flags=flags), args.launches, args.warmup, args.budget_ms)
         print(f"hip.softmin p=1     D={D:4d} N=M={n:8d}         {fwd_ms:10.3f} ms (min {lo:10.3f}, spread {spread:5.1%})", flush=True)
-        for V in args.widths:
+        for V in args.widths if args.resident else []:
+            Sb = features(n, V, g, dev)[None].contiguous()
+            (off, off_lo, off_sp), (on, on_lo, on_sp), (fw, fw_lo, fw_sp) = alternated(
+                [lambda: hip.plan_apply_p1_raw(xb, yb, hb, Sb, eps, 0, want_softmin=True),
+                 lambda: hip.plan_apply_p1_raw(xb, yb, hb, Sb, eps, hip.FLAG_XD_PLAN_P1, want_softmin=True),
+                 lambda: hip.softmin(eps, x, y, h, p=1, flags=flags)], args.launches, args.warmup, args.budget_ms)
+            print(f"glhip_plan_apply_p1 D={D:4d} N=M={n:8d} V={V:4d}  default {off:10.3f} ms (min {off_lo:10.3f}, spread {off_sp:5.1%}) = "
+                  f"{off / fw:5.2f} forwards;  resident {on:10.3f} ms (min {on_lo:10.3f}, spread {on_sp:5.1%}) = {on / fw:5.2f} forwards;  "
+                  f"forward {fw:10.3f} ms (spread {fw_sp:5.1%});  default / resident {off / on:5.2f}", flush=True)
+        for V in [] if args.resident else args.widths:
             S = features(n, V, g, dev)
             Sb = S[None].contiguous()
             med, lo, spread = timed(lambda: hip.plan_apply_p1_raw(xb, yb, hb, Sb, eps, 0, want_softmin=True), args.launches, args.warmup,
@@ -131,6 +164,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--widths", type=int, nargs="*", default=[1, 2, 3, 32, 128])
     ap.add_argument("--legacy", action="store_true", help="log-domain path: 2 V forward reductions per product")
+    ap.add_argument("--resident", action="store_true", help="--p 1, D <= 16: alternate the default route, FLAG_XD_PLAN_P1 and one forward")
     ap.add_argument("--dims", type=int, nargs="*", default=None, help="cloud dimensions (default: 3, as ever); eps = 0.1 D / 3 from D = 4 on")
     ap.add_argument("--budget-ms", type=float, default=0.0, help="fewer calls (at least 3) for products longer than this / --launches")
     args = ap.parse_args()
