@@ -26,8 +26,9 @@ FLAG_XD_ARG = 8192              # argmin / argkmin of p = 2, D <= 16, dense laun
 FLAG_XD_BILINEAR = 16384        # plan_bilinear of p = 2, D <= 16, K <= 32, dense launches: the resident-operand kernel (glhip_plan_bilinear_xd.h)
 FLAG_XD_PLAN_P1 = 32768         # plan_apply_p1 of D <= 16, dense launches: the resident-operand kernel (glhip_dist_plan_xd.h)
 FLAG_GRAD_FAMILY = FLAG_XDL16   # kernel products rounded like the product-and-gradient kernel of the same kind (glhip.h)
-XD_MAX_DIM = 16                 # the fused four-softmin iteration / annealing / extrapolation, the one-pass value + gradient and the matrix-core
-                                # gradients stop at this dimension (glhip_softmin_xd.h, glhip_wsum_t32.h)
+XD_MAX_DIM = 16                 # the fused extrapolation, the p = 1 iteration / annealing, the one-pass value + gradient and the matrix-core
+                                # gradients stop at this dimension (glhip_softmin_xd.h, glhip_wsum_t32.h); the p = 2 iteration / annealing
+                                # goes on to MFMA_FWD_MAX_DIM on pre-packed operands (glhip_softmin_xkp.h, version 146)
 MFMA_FWD_MAX_DIM = 4095         # p = 2 soft-min forward / half-step and gaussian product run on the matrix cores up to this dimension
                                 # (17 ... 4095: the K-chunked kernel of glhip_softmin_xk.h; kept in step with the library by tests/test_anyd_kernels_gpu.py)
 DIST_XK_MAX_DIM = 4095          # ... and under FLAG_XK_DIST the p = 1 soft-min / half-step and the laplacian / energy products too (glhip_dist_xk.h)
@@ -62,6 +63,7 @@ SIGNATURES = {
     "glhip_softmin_perm_applies": (_c_int, [_c_int, _c_long, _c_long, _c_int, _c_int, _c_int, _c_int, _c_int]),
     "glhip_sinkhorn_iter4": (_c_int, [_vp] * 12 + [_c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _c_int, _c_int, _c_int]
                              + _TAIL),
+    "glhip_sinkhorn_iter4_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "glhip_sinkhorn_anneal": (_c_int, [_vp] * 6 + [_c_int] * 4 + [_vp, _vp, _c_int, _c_int, _c_int, _vp, _c_size, _c_int, _c_float, _vp]),
     "glhip_sinkhorn_extrapolate4": (_c_int, [_vp] * 14 + [_c_int] * 6 + [_c_float, _c_float, _c_int, _c_int] + _TAIL),
     "glhip_softmin_bwd_x": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int,
@@ -150,7 +152,8 @@ _SINCE = {"glhip_sinkhorn_step_perm": 134, "glhip_softmin_perm_applies": 134,
           "glhip_argkmin_passes": 141, "glhip_arg_family": 142, "glhip_arg_xd_workspace_bytes": 142,
           "glhip_plan_apply_sparse_supported": 143, "glhip_plan_apply_sparse_workspace_bytes": 143, "glhip_plan_apply_sparse": 143,
           "glhip_plan_bilinear_family": 144, "glhip_plan_bilinear_xd_workspace_bytes": 144,
-          "glhip_plan_apply_p1_family": 145, "glhip_plan_apply_p1_xd_pass_width": 145, "glhip_plan_apply_p1_xd_workspace_bytes": 145}
+          "glhip_plan_apply_p1_family": 145, "glhip_plan_apply_p1_xd_pass_width": 145, "glhip_plan_apply_p1_xd_workspace_bytes": 145,
+          "glhip_sinkhorn_iter4_workspace_bytes": 146}
 
 _lib = None
 

@@ -2,6 +2,7 @@
 // (glhip_softmin_fwd, glhip_sinkhorn_step, glhip_sinkhorn_step_perm, glhip_sinkhorn_iter4, glhip_sinkhorn_anneal, glhip_sinkhorn_extrapolate4).  gfx950 only.
 #include "glhip_autosort.h"
 #include "glhip_launch.h"
+#include "glhip_softmin_xkp.h"
 
 namespace glhip {
 thread_local char g_err[512] = "";
@@ -12,6 +13,24 @@ thread_local char g_err[512] = "";
 static const int kXdNBP[] = {GL_NBP(4), GL_NBP(5), GL_NBP(6), GL_NBP(7), GL_NBP(8), GL_NBP(9), GL_NBP(10), GL_NBP(11), GL_NBP(12), GL_NBP(13), GL_NBP(14), GL_NBP(15), GL_NBP(16)};
 #undef GL_NBP
 static_assert(sizeof kXdNBP / sizeof kXdNBP[0] == kXdMaxD - 3, "one entry per dimension of the xd kernels");
+
+// glhip_sinkhorn_iter4 / _anneal for p = 2 clouds of 17 <= D <= 4095: the half-steps as ONE launch on the operands xkp_pack left in the
+// workspace (glhip_softmin_xkp.h), or, where the workspace did not hold them (`packed` false), as two or four launches of xk_fwd_kernel —
+// the launches of glhip_sinkhorn_step, on whatever workspace there is.  bf16 x 3 only.
+template <typename T>
+static void iter4_xk_typed(const void* x, const void* y, const float* a_log, const float* b_log, float const* const* src, float* const* dst, int B,
+                           int N, int M, int D, float eps, float damping, int first, bool packed, void* workspace, size_t workspace_bytes, int flags,
+                           hipStream_t st) {
+    SoftminMulti<T> m = iter4_problems<T>(x, y, a_log, b_log, src[0], src[1], src[2], src[3], dst[0], dst[1], dst[2], dst[3], N, M, eps, damping, 2, first);
+    if (packed) {
+        xkp_reduce(m, B, N, M, D, workspace, workspace_bytes, (flags & GLHIP_FLAG_NO_SPLIT) == 0, st);
+        return;
+    }
+    const Scratch sc = make_scratch(workspace, workspace_bytes, flags & ~(GLHIP_FLAG_PREPACK | GLHIP_FLAG_F16X2), 0, N);
+    for (int k = 0; k < m.count; ++k)
+        launch_xk_l<XD_SOFTMIN, T, SoftminFwdOp<1, 2, false, 1, T>, XL_BF16X3>(m.p[k], m.p[k], Ranges{nullptr, nullptr, nullptr, nullptr}, 0, B, m.N[k],
+                                                                                  m.M[k], D, sc, st);
+}
 
 extern "C" {
 
@@ -182,7 +201,8 @@ int glhip_sinkhorn_iter4(const void* x, const void* y, const float* a_log, const
                          int in_dtype, int first, void* workspace, size_t workspace_bytes, int flags, void* stream) {
     int rc = check_common("glhip_sinkhorn_iter4", x, y, b_log, B, N, M, D, in_dtype, nullptr, nullptr, nullptr, 0);
     if (rc) return rc;
-    if ((p != 1 && p != 2) || D > kXdMaxD) return fail(GLHIP_EUNSUPPORTED, "glhip_sinkhorn_iter4: only p = 1, 2 and D <= 16 (got p = %d, D = %d)", p, D);
+    if ((p != 1 && p != 2) || D > kXkMaxD || (p == 1 && D > kXdMaxD))
+        return fail(GLHIP_EUNSUPPORTED, "glhip_sinkhorn_iter4: only p = 1 with D <= 16 and p = 2 with D <= 4095 (got p = %d, D = %d)", p, D);
     if (flags & (GLHIP_FLAG_DIRECT | GLHIP_FLAG_NO_MFMA | GLHIP_FLAG_F32_MFMA | GLHIP_FLAG_XDL16))
         return fail(GLHIP_EUNSUPPORTED, "glhip_sinkhorn_iter4: runs on the default 32x32x16 kernel only (flags = %d)", flags);
     if (B == 0 || N == 0 || M == 0) return GLHIP_OK;
@@ -195,6 +215,14 @@ int glhip_sinkhorn_iter4(const void* x, const void* y, const float* a_log, const
         return fail(GLHIP_EINVAL, "glhip_sinkhorn_iter4: outputs must not alias inputs (updates are simultaneous)");
     if (!(eps > 0.f)) return fail(GLHIP_EINVAL, "glhip_sinkhorn_iter4: eps must be > 0");
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if (D > kXdMaxD) {      // 17 <= D <= 4095: pre-packed operands (glhip_softmin_xkp.h)
+        const float* src[4] = {f_ba, g_ab, f_aa, g_bb};
+        float* dst[4] = {f_ba_out, g_ab_out, f_aa_out, g_bb_out};
+        const bool packed = xkp_pack(x, y, B, N, M, D, in_dtype, workspace, workspace_bytes, st);
+        if (in_dtype == GLHIP_F32) iter4_xk_typed<float>(x, y, a_log, b_log, src, dst, B, N, M, D, eps, damping, first, packed, workspace, workspace_bytes, flags, st);
+        else iter4_xk_typed<bf16_t>(x, y, a_log, b_log, src, dst, B, N, M, D, eps, damping, first, packed, workspace, workspace_bytes, flags, st);
+        return check_launch("glhip_sinkhorn_iter4");
+    }
     const Scratch sc = make_scratch(workspace, workspace_bytes, flags & ~GLHIP_FLAG_PREPACK, 0, N);
     rc = (in_dtype == GLHIP_F32)
              ? iter4_typed<float>(x, y, a_log, b_log, f_ba, g_ab, f_aa, g_bb, f_ba_out, g_ab_out, f_aa_out, g_bb_out, B, N, M, D, eps, damping, p, first, sc, st)
@@ -208,7 +236,8 @@ int glhip_sinkhorn_anneal(const void* x, const void* y, const float* a_log, cons
     const char* fn = "glhip_sinkhorn_anneal";
     int rc = check_common(fn, x, y, b_log, B, N, M, D, in_dtype, nullptr, nullptr, nullptr, 0);
     if (rc) return rc;
-    if ((p != 1 && p != 2) || D > kXdMaxD) return fail(GLHIP_EUNSUPPORTED, "%s: only p = 1, 2 and D <= 16 (got p = %d, D = %d)", fn, p, D);
+    if ((p != 1 && p != 2) || D > kXkMaxD || (p == 1 && D > kXdMaxD))
+        return fail(GLHIP_EUNSUPPORTED, "%s: only p = 1 with D <= 16 and p = 2 with D <= 4095 (got p = %d, D = %d)", fn, p, D);
     if (flags & (GLHIP_FLAG_DIRECT | GLHIP_FLAG_NO_MFMA | GLHIP_FLAG_F32_MFMA | GLHIP_FLAG_XDL16))
         return fail(GLHIP_EUNSUPPORTED, "%s: runs on the default 32x32x16 kernel only (flags = %d)", fn, flags);
     if (n_eps < 1 || !eps || !damping) return fail(GLHIP_EINVAL, "%s: needs n_eps >= 1 temperatures and dampings (n_eps = %d)", fn, n_eps);
@@ -228,7 +257,16 @@ int glhip_sinkhorn_anneal(const void* x, const void* y, const float* a_log, cons
     for (int i = 0; i < n_eps; ++i)
         if (!(eps[i] > 0.f)) return fail(GLHIP_EINVAL, "%s: eps[%d] must be > 0", fn, i);
     hipStream_t st = static_cast<hipStream_t>(stream);
+    // 17 <= D <= 4095: the clouds are packed ONCE for the initialisation and every temperature (glhip_softmin_xkp.h)
+    const bool packed = D > kXdMaxD && xkp_pack(x, y, B, N, M, D, in_dtype, workspace, workspace_bytes, st);
     auto one = [&](int i, int first, float* const* src, float* const* dst) {
+        if (D > kXdMaxD) {
+            const float* none[4] = {nullptr, nullptr, nullptr, nullptr};
+            float const* const* from = src ? src : none;
+            if (in_dtype == GLHIP_F32) iter4_xk_typed<float>(x, y, a_log, b_log, from, dst, B, N, M, D, eps[i], damping[i], first, packed, workspace, workspace_bytes, flags, st);
+            else iter4_xk_typed<bf16_t>(x, y, a_log, b_log, from, dst, B, N, M, D, eps[i], damping[i], first, packed, workspace, workspace_bytes, flags, st);
+            return (int)GLHIP_OK;
+        }
         int fl = flags & ~GLHIP_FLAG_PREPACK;
         if (!(eps[i] >= f16x2_min_eps)) fl &= ~GLHIP_FLAG_F16X2;
         const Scratch sc = make_scratch(workspace, workspace_bytes, fl, 0, N);

@@ -648,10 +648,11 @@ int multi_dispatch(SoftminMulti<T>& m, int B, int D, int p, const Scratch& sc, h
     return GLHIP_OK;
 }
 
+// the two or four half-steps of an iteration as the problems of a multi launch
 template <typename T>
-int iter4_typed(const void* x, const void* y, const float* a_log, const float* b_log, const float* f_ba, const float* g_ab,
-                const float* f_aa, const float* g_bb, float* f_ba_out, float* g_ab_out, float* f_aa_out, float* g_bb_out,
-                int B, int N, int M, int D, float eps, float damping, int p, int first, const Scratch& sc, hipStream_t st) {
+SoftminMulti<T> iter4_problems(const void* x, const void* y, const float* a_log, const float* b_log, const float* f_ba, const float* g_ab,
+                               const float* f_aa, const float* g_bb, float* f_ba_out, float* g_ab_out, float* f_aa_out, float* g_bb_out,
+                               int N, int M, float eps, float damping, int p, int first) {
     // first = 0: averaged update;  1: initial potentials (no pot, no prev);  2: plain extrapolation (pot, no prev)
     const float alpha = first ? damping : 0.5f * damping, beta = 0.5f;
     auto one = [&](const void* rows, const void* cols, const float* logw, const float* pot, const float* prev, float* out) {
@@ -665,6 +666,14 @@ int iter4_typed(const void* x, const void* y, const float* a_log, const float* b
         m.p[2] = one(x, x, a_log, f_aa, f_aa, f_aa_out); m.N[2] = N; m.M[2] = N;
         m.p[3] = one(y, y, b_log, g_bb, g_bb, g_bb_out); m.N[3] = M; m.M[3] = M;
     }
+    return m;
+}
+
+template <typename T>
+int iter4_typed(const void* x, const void* y, const float* a_log, const float* b_log, const float* f_ba, const float* g_ab,
+                const float* f_aa, const float* g_bb, float* f_ba_out, float* g_ab_out, float* f_aa_out, float* g_bb_out,
+                int B, int N, int M, int D, float eps, float damping, int p, int first, const Scratch& sc, hipStream_t st) {
+    SoftminMulti<T> m = iter4_problems<T>(x, y, a_log, b_log, f_ba, g_ab, f_aa, g_bb, f_ba_out, g_ab_out, f_aa_out, g_bb_out, N, M, eps, damping, p, first);
     return multi_dispatch<T>(m, B, D, p, sc, st);
 }
 

@@ -184,11 +184,15 @@ class _HipSoftmin:
 
     def _iter4_plan(self, C_xy, a_log, b_log, debias, create):
         """The hip.Iter4Plan of the loop being run, (re)built when the inputs change; None when the one-launch-per-iteration
-        path does not apply: block-sparse levels, D > 16, and problems big enough for every soft-min to fill the GPU
+        path does not apply: block-sparse levels, D > 16 (but see below), and problems big enough for every soft-min to fill the GPU
         on its own (those run faster as separate launches with pre-packed columns).  The coarse level of the multiscale
-        backend (dense, ~2e3 clusters with their own weights) qualifies: its 7 x 4 soft-mins become 7 launches."""
+        backend (dense, ~2e3 clusters with their own weights) qualifies: its 7 x 4 soft-mins become 7 launches.
+        Online p = 2 clouds of 16 < D <= hip.MFMA_FWD_MAX_DIM qualify under `_XK_ITER` (the pre-packed operands of glhip_softmin_xkp.h),
+        up to `_XK_ITER_MAX_PAIRS` pairs per soft-min."""
         x, y = C_xy[0], C_xy[1]
-        if self.p not in (1, 2) or x.shape[-1] > hip.XD_MAX_DIM or not _fuse_iterations or x.dtype == torch.float64:
+        D = x.shape[-1]
+        xk = _XK_ITER and self.p == 2 and not self.multiscale and hip.XD_MAX_DIM < D <= hip.MFMA_FWD_MAX_DIM
+        if self.p not in (1, 2) or (D > hip.XD_MAX_DIM and not xk) or not _fuse_iterations or x.dtype == torch.float64:
             return None
         if self.p == 1 and (hip.autosort_applies(x, y) or hip.autosort_applies(y, x)):
             return None     # big p = 1 clouds: one voxel-sorted launch per soft-min (glhip_dist_x32.h) beats the fused iteration
@@ -197,7 +201,7 @@ class _HipSoftmin:
         if self.multiscale and C_xy[4] is not None:     # truncated fine level: block-sparse launches
             return None
         B = 1 if x.dim() == 2 else x.shape[0]
-        if float(B) * x.shape[-2] * y.shape[-2] >= _ITER4_MAX_PAIRS:
+        if float(B) * x.shape[-2] * y.shape[-2] >= (_XK_ITER_MAX_PAIRS if xk else _ITER4_MAX_PAIRS):
             return None
         plan = self._plan
         if plan is None or plan[0] is not x or plan[1] is not a_log or plan[2] is not b_log or plan[3] != debias:
@@ -261,6 +265,12 @@ _anneal_in_library = True   # the iterations of a level queued by one library ca
 _fuse_iterations = True   # one launch per Sinkhorn iteration (small / mid-size clouds); set_iteration_fusion(False): four half-steps
 # ... up to this many pairs per soft-min; bigger problems fill the GPU with one soft-min per launch (pre-packed columns, XCD grids)
 _ITER4_MAX_PAIRS = 4e9   # measured: B x 4096^2 with B = 32..128 and N = 3e4 gain 5-13 %, 7e4+ lose
+# ... and online p = 2 clouds of 17 <= D <= 4095 on operands packed once per annealing (glhip_softmin_xkp.h, library version 146):
+# on by default, GEOMLOSS_HIP_XK_ITER=0 keeps the four half-step launches per temperature.  Measured (profiles/iter4_xk.txt): losses at
+# N = 512 ... 8000, D = 32 ... 512 run 1.4-6.3 x faster, one raw iteration 6.2 / 1.8 / 1.9 x the four launches at N = M = 2000 / 8000 / 30000
+# (9e8 pairs, the largest point timed: separate launches won nowhere, so the threshold is where the measurements end)
+_XK_ITER = os.environ.get("GEOMLOSS_HIP_XK_ITER", "1") != "0"
+_XK_ITER_MAX_PAIRS = 1e9
 _graphs = hip.GraphCache()
 
 

@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 145 /* 0.1.45 */
+#define GLHIP_VERSION 146 /* 0.1.46 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
@@ -382,6 +382,13 @@ int glhip_softmin_perm_applies(int B, long N, long M, int D, int p, int dtype, i
  * of glhip_dist_xd.h) (GLHIP_EUNSUPPORTED otherwise: issue four
  * glhip_sinkhorn_step calls instead); meant for small and mid-size problems, where four separate launches
  * leave the chip under-filled.  Workspace: 4 * glhip_workspace_bytes(B, max(N,M), max(N,M), D, 0).
+ * Version 146: p = 2 clouds of 17 <= D <= 4095 as well (float32 / bfloat16, B <= 65535, dense), on the kernels of
+ * csrc/glhip_softmin_xkp.h: one launch packs both clouds, centred on x[b, 0, :], into temperature-free bf16 x 3 MFMA records in the
+ * workspace, one launch runs the two or four half-steps on them (+ one merge launch where the columns are split; GLHIP_FLAG_NO_SPLIT
+ * is honoured).  GLHIP_FLAG_F16X2 is ignored there (bf16 x 3 only); the kernel-selection flags that are refused for D <= 16 are
+ * refused alike.  Workspace: glhip_sinkhorn_iter4_workspace_bytes.  With a NULL or shorter workspace the call runs its half-steps as
+ * two or four launches of the kernel of glhip_sinkhorn_step instead: same results up to rounding.  p = 1 with D > 16 and D > 4095
+ * stay GLHIP_EUNSUPPORTED.
  */
 int glhip_sinkhorn_iter4(const void* x, const void* y, const float* a_log, const float* b_log,
                          const float* f_ba, const float* g_ab, const float* f_aa, const float* g_bb,
@@ -402,10 +409,21 @@ int glhip_sinkhorn_iter4(const void* x, const void* y, const float* a_log, const
  *   range vouching is per temperature; pass 0 to apply it everywhere, a huge value or no flag for never).
  * Dense, D <= 16, p = 1 or 2, n_eps >= 1; workspace as glhip_sinkhorn_iter4.  Used for single-scale losses and for the coarse level of
  * the two-scale ones (everything up to the jump).
+ * Version 146: p = 2 clouds of 17 <= D <= 4095 as glhip_sinkhorn_iter4; the clouds are packed ONCE for the whole call, then the
+ * initialisation and one reducing (+ merge) launch per temperature are queued.  flags' GLHIP_FLAG_F16X2 and f16x2_min_eps are ignored there.
  */
 int glhip_sinkhorn_anneal(const void* x, const void* y, const float* a_log, const float* b_log, float* const* set0, float* const* set1,
                           int B, int N, int M, int D, const float* eps, const float* damping, int n_eps, int p, int in_dtype,
                           void* workspace, size_t workspace_bytes, int flags, float f16x2_min_eps, void* stream);
+
+/*
+ * Version 146.  The workspace glhip_sinkhorn_iter4 / glhip_sinkhorn_anneal are sized for (host arithmetic, no GPU).  D <= 16: exactly
+ * 4 * glhip_workspace_bytes(B, max(N, M), max(N, M), D, 0).  p = 2, 17 <= D <= 4095: both clouds packed in both operand roles
+ * (ceil(n / 32) * ceil(D / 8) * 3072 bytes per cloud, role and batch item), their squared norms, and the split partials of the four
+ * problems, each part rounded up to 256 bytes; non-decreasing in N, M and D.  0 for an empty cloud and for a request without a kernel
+ * (p = 1 with D > 16, D > 4095, p outside {1, 2}).
+ */
+size_t glhip_sinkhorn_iter4_workspace_bytes(int B, int N, int M, int D, int p);
 
 /*
  * The coarse-to-fine jump of the two-scale loop in ONE launch (+ one merge launch): the four extrapolations of
