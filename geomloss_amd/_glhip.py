@@ -25,6 +25,8 @@ DIST_GRAD_OPS = {"softmin_p1": 0, "laplacian": 1, "energy": 2}      # ops of glh
 FLAG_XD_ARG = 8192              # argmin / argkmin of p = 2, D <= 16, dense launches: the resident-operand kernels (glhip_arg_xd.h)
 FLAG_XD_BILINEAR = 16384        # plan_bilinear of p = 2, D <= 16, K <= 32, dense launches: the resident-operand kernel (glhip_plan_bilinear_xd.h)
 FLAG_XD_PLAN_P1 = 32768         # plan_apply_p1 of D <= 16, dense launches: the resident-operand kernel (glhip_dist_plan_xd.h)
+FLAG_XK_ITER_DIST = 65536       # sinkhorn_iter4 / Iter4Plan with p = 1, 17 <= D <= 4095: the one-launch iteration on pre-packed operands with
+                                # the distance epilogue of glhip_dist_xkp.h (version 147); opt-in
 FLAG_GRAD_FAMILY = FLAG_XDL16   # kernel products rounded like the product-and-gradient kernel of the same kind (glhip.h)
 XD_MAX_DIM = 16                 # the fused extrapolation, the p = 1 iteration / annealing, the one-pass value + gradient and the matrix-core
                                 # gradients stop at this dimension (glhip_softmin_xd.h, glhip_wsum_t32.h); the p = 2 iteration / annealing
@@ -64,6 +66,7 @@ SIGNATURES = {
     "glhip_sinkhorn_iter4": (_c_int, [_vp] * 12 + [_c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _c_int, _c_int, _c_int]
                              + _TAIL),
     "glhip_sinkhorn_iter4_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "glhip_sinkhorn_iter4_dist_workspace_bytes": (_c_size, [_c_int, _c_int, _c_int, _c_int]),
     "glhip_sinkhorn_anneal": (_c_int, [_vp] * 6 + [_c_int] * 4 + [_vp, _vp, _c_int, _c_int, _c_int, _vp, _c_size, _c_int, _c_float, _vp]),
     "glhip_sinkhorn_extrapolate4": (_c_int, [_vp] * 14 + [_c_int] * 6 + [_c_float, _c_float, _c_int, _c_int] + _TAIL),
     "glhip_softmin_bwd_x": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int,
@@ -153,7 +156,7 @@ _SINCE = {"glhip_sinkhorn_step_perm": 134, "glhip_softmin_perm_applies": 134,
           "glhip_plan_apply_sparse_supported": 143, "glhip_plan_apply_sparse_workspace_bytes": 143, "glhip_plan_apply_sparse": 143,
           "glhip_plan_bilinear_family": 144, "glhip_plan_bilinear_xd_workspace_bytes": 144,
           "glhip_plan_apply_p1_family": 145, "glhip_plan_apply_p1_xd_pass_width": 145, "glhip_plan_apply_p1_xd_workspace_bytes": 145,
-          "glhip_sinkhorn_iter4_workspace_bytes": 146}
+          "glhip_sinkhorn_iter4_workspace_bytes": 146, "glhip_sinkhorn_iter4_dist_workspace_bytes": 147}
 
 _lib = None
 

@@ -17,19 +17,30 @@ static_assert(sizeof kXdNBP / sizeof kXdNBP[0] == kXdMaxD - 3, "one entry per di
 // glhip_sinkhorn_iter4 / _anneal for p = 2 clouds of 17 <= D <= 4095: the half-steps as ONE launch on the operands xkp_pack left in the
 // workspace (glhip_softmin_xkp.h), or, where the workspace did not hold them (`packed` false), as two or four launches of xk_fwd_kernel —
 // the launches of glhip_sinkhorn_step, on whatever workspace there is.  bf16 x 3 only.
+// p = 1 (GLHIP_FLAG_XK_ITER_DIST, version 147): the same on the distance epilogue of glhip_dist_xkp.h; the fall-back launches are those of
+// xk_dist_kernel, what glhip_sinkhorn_step makes with p = 1 under GLHIP_FLAG_XK_DIST.
 template <typename T>
 static void iter4_xk_typed(const void* x, const void* y, const float* a_log, const float* b_log, float const* const* src, float* const* dst, int B,
-                           int N, int M, int D, float eps, float damping, int first, bool packed, void* workspace, size_t workspace_bytes, int flags,
-                           hipStream_t st) {
-    SoftminMulti<T> m = iter4_problems<T>(x, y, a_log, b_log, src[0], src[1], src[2], src[3], dst[0], dst[1], dst[2], dst[3], N, M, eps, damping, 2, first);
+                           int N, int M, int D, float eps, float damping, int p, int first, bool packed, void* workspace, size_t workspace_bytes,
+                           int flags, hipStream_t st) {
+    SoftminMulti<T> m = iter4_problems<T>(x, y, a_log, b_log, src[0], src[1], src[2], src[3], dst[0], dst[1], dst[2], dst[3], N, M, eps, damping, p, first);
     if (packed) {
-        xkp_reduce(m, B, N, M, D, workspace, workspace_bytes, (flags & GLHIP_FLAG_NO_SPLIT) == 0, st);
+        xkp_reduce(m, B, N, M, D, p, workspace, workspace_bytes, (flags & GLHIP_FLAG_NO_SPLIT) == 0, st);
         return;
     }
     const Scratch sc = make_scratch(workspace, workspace_bytes, flags & ~(GLHIP_FLAG_PREPACK | GLHIP_FLAG_F16X2), 0, N);
-    for (int k = 0; k < m.count; ++k)
-        launch_xk_l<XD_SOFTMIN, T, SoftminFwdOp<1, 2, false, 1, T>, XL_BF16X3>(m.p[k], m.p[k], Ranges{nullptr, nullptr, nullptr, nullptr}, 0, B, m.N[k],
-                                                                                  m.M[k], D, sc, st);
+    for (int k = 0; k < m.count; ++k) {
+        if (p == 1)
+            launch_xk_dist<DM_SOFTMIN_P1, T, SoftminFwdOp<1, 1, true, 1, T>>(dist_params(m.p[k]), m.p[k], B, m.N[k], m.M[k], D, sc, st);
+        else
+            launch_xk_l<XD_SOFTMIN, T, SoftminFwdOp<1, 2, false, 1, T>, XL_BF16X3>(m.p[k], m.p[k], Ranges{nullptr, nullptr, nullptr, nullptr}, 0, B,
+                                                                                      m.N[k], m.M[k], D, sc, st);
+    }
+}
+
+// p = 1 beyond D = 16 is served under GLHIP_FLAG_XK_ITER_DIST only
+static bool iter4_unsupported(int D, int p, int flags) {
+    return (p != 1 && p != 2) || D > kXkMaxD || (p == 1 && D > kXdMaxD && !(flags & GLHIP_FLAG_XK_ITER_DIST));
 }
 
 extern "C" {
@@ -201,7 +212,7 @@ int glhip_sinkhorn_iter4(const void* x, const void* y, const float* a_log, const
                          int in_dtype, int first, void* workspace, size_t workspace_bytes, int flags, void* stream) {
     int rc = check_common("glhip_sinkhorn_iter4", x, y, b_log, B, N, M, D, in_dtype, nullptr, nullptr, nullptr, 0);
     if (rc) return rc;
-    if ((p != 1 && p != 2) || D > kXkMaxD || (p == 1 && D > kXdMaxD))
+    if (iter4_unsupported(D, p, flags))
         return fail(GLHIP_EUNSUPPORTED, "glhip_sinkhorn_iter4: only p = 1 with D <= 16 and p = 2 with D <= 4095 (got p = %d, D = %d)", p, D);
     if (flags & (GLHIP_FLAG_DIRECT | GLHIP_FLAG_NO_MFMA | GLHIP_FLAG_F32_MFMA | GLHIP_FLAG_XDL16))
         return fail(GLHIP_EUNSUPPORTED, "glhip_sinkhorn_iter4: runs on the default 32x32x16 kernel only (flags = %d)", flags);
@@ -219,8 +230,8 @@ int glhip_sinkhorn_iter4(const void* x, const void* y, const float* a_log, const
         const float* src[4] = {f_ba, g_ab, f_aa, g_bb};
         float* dst[4] = {f_ba_out, g_ab_out, f_aa_out, g_bb_out};
         const bool packed = xkp_pack(x, y, B, N, M, D, in_dtype, workspace, workspace_bytes, st);
-        if (in_dtype == GLHIP_F32) iter4_xk_typed<float>(x, y, a_log, b_log, src, dst, B, N, M, D, eps, damping, first, packed, workspace, workspace_bytes, flags, st);
-        else iter4_xk_typed<bf16_t>(x, y, a_log, b_log, src, dst, B, N, M, D, eps, damping, first, packed, workspace, workspace_bytes, flags, st);
+        if (in_dtype == GLHIP_F32) iter4_xk_typed<float>(x, y, a_log, b_log, src, dst, B, N, M, D, eps, damping, p, first, packed, workspace, workspace_bytes, flags, st);
+        else iter4_xk_typed<bf16_t>(x, y, a_log, b_log, src, dst, B, N, M, D, eps, damping, p, first, packed, workspace, workspace_bytes, flags, st);
         return check_launch("glhip_sinkhorn_iter4");
     }
     const Scratch sc = make_scratch(workspace, workspace_bytes, flags & ~GLHIP_FLAG_PREPACK, 0, N);
@@ -236,7 +247,7 @@ int glhip_sinkhorn_anneal(const void* x, const void* y, const float* a_log, cons
     const char* fn = "glhip_sinkhorn_anneal";
     int rc = check_common(fn, x, y, b_log, B, N, M, D, in_dtype, nullptr, nullptr, nullptr, 0);
     if (rc) return rc;
-    if ((p != 1 && p != 2) || D > kXkMaxD || (p == 1 && D > kXdMaxD))
+    if (iter4_unsupported(D, p, flags))
         return fail(GLHIP_EUNSUPPORTED, "%s: only p = 1 with D <= 16 and p = 2 with D <= 4095 (got p = %d, D = %d)", fn, p, D);
     if (flags & (GLHIP_FLAG_DIRECT | GLHIP_FLAG_NO_MFMA | GLHIP_FLAG_F32_MFMA | GLHIP_FLAG_XDL16))
         return fail(GLHIP_EUNSUPPORTED, "%s: runs on the default 32x32x16 kernel only (flags = %d)", fn, flags);
@@ -263,8 +274,8 @@ int glhip_sinkhorn_anneal(const void* x, const void* y, const float* a_log, cons
         if (D > kXdMaxD) {
             const float* none[4] = {nullptr, nullptr, nullptr, nullptr};
             float const* const* from = src ? src : none;
-            if (in_dtype == GLHIP_F32) iter4_xk_typed<float>(x, y, a_log, b_log, from, dst, B, N, M, D, eps[i], damping[i], first, packed, workspace, workspace_bytes, flags, st);
-            else iter4_xk_typed<bf16_t>(x, y, a_log, b_log, from, dst, B, N, M, D, eps[i], damping[i], first, packed, workspace, workspace_bytes, flags, st);
+            if (in_dtype == GLHIP_F32) iter4_xk_typed<float>(x, y, a_log, b_log, from, dst, B, N, M, D, eps[i], damping[i], p, first, packed, workspace, workspace_bytes, flags, st);
+            else iter4_xk_typed<bf16_t>(x, y, a_log, b_log, from, dst, B, N, M, D, eps[i], damping[i], p, first, packed, workspace, workspace_bytes, flags, st);
             return (int)GLHIP_OK;
         }
         int fl = flags & ~GLHIP_FLAG_PREPACK;

@@ -37,8 +37,13 @@
 // LDS: 2 x 24 KiB + 1 KiB of H_j + 2 KiB of (max, sum) = 51 KiB: three workgroups per CU, 3 wavefronts per SIMD (<= 168 VGPRs).  At
 // N = M = 2048 with four problems the launch is 16 row blocks x 4 splits x 4 = 256 workgroups.  Resources as the compiler reports them
 // (the translation unit prints them with every build): DESIGN.md §4.
+//
+// Version 147: the body takes the metric as a template parameter.  P = 2 is everything above; P = 1 (GLHIP_FLAG_XK_ITER_DIST) keeps the
+// operands, the grid and the stage loop and swaps the epilogue for the distance one of glhip_dist_xkp.h (S_j and N_j in LDS, near-pair
+// repair, clamp, square root, one FMA per pair).  Every P = 1 line sits under `if constexpr`: the P = 2 report above did not move.
 #pragma once
 
+#include "glhip_dist_xkp.h"
 #include "glhip_softmin_xk.h"
 
 namespace glhip {
@@ -81,6 +86,7 @@ struct XkpOperands {
     const uint4* crec[4];     // packed columns
     const float* rn2[4];      // |xt_i|^2 of its rows, (B, N[k])
     const float* cn2[4];      // |yt_j|^2 of its columns, (B, M[k])
+    float guard;              // P = 1: the near-pair rule of glhip_dist_xkp.h (GLHIP_DIST_GUARD)
 };
 
 // Both clouds of a call as records, in both roles, and their squared norms.  grid = (blocks of 256 points of the longer cloud, B,
@@ -133,11 +139,12 @@ xkp_pack_kernel(const T* __restrict__ x, const T* __restrict__ y, int N, int M, 
     }
 }
 
-template <typename T>
+// P = 2: the dot-product epilogue described above.  P = 1: the distance epilogue of glhip_dist_xkp.h (Hs[2 ..] holds N_j of the tile).
+template <typename T, int P = 2>
 __global__ void __launch_bounds__(kXkpThreads, 3)
 xkp_fwd_multi_kernel(SoftminMulti<T> m, XkpOperands ops, int D, SplitInfo sp) {
     __shared__ uint4 stageBuf[2][kXkpGroups * kXkpStageRecs];
-    __shared__ __attribute__((aligned(16))) float Hs[2][kXkpCols];
+    __shared__ __attribute__((aligned(16))) float Hs[P == 1 ? 4 : 2][kXkpCols];
     __shared__ float mrg[2][kXkpRows][2];
 
     const int ns = sp.n_splits;
@@ -192,8 +199,16 @@ xkp_fwd_multi_kernel(SoftminMulti<T> m, XkpOperands ops, int D, SplitInfo sp) {
     const bool rows_on = wr * 2 < nrg;
     f32x16 acc[2][2];
     float mx[2], ssum[2];
+    // P = 1: n_i of this lane's rows and their near-pair thresholds; -inf for a row past the cloud: its group may not even be staged, and
+    // nothing its accumulators hold is ever below it
+    [[maybe_unused]] float rn[2], thr[2];
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt) {
+        if constexpr (P == 1) {
+            const int row = row0 + wr * 64 + rt * 32 + l31;
+            rn[rt] = ops.rn2[k][(long)b * N + min(row, N - 1)];
+            thr[rt] = (row < N && ops.guard > 0.f) ? fmaxf(ops.guard * rn[rt], 4.f * kXkpDistClamp2) : -__builtin_inff();
+        }
         mx[rt] = kMinusHuge;
         ssum[rt] = 0.f;
 #pragma unroll
@@ -209,12 +224,16 @@ xkp_fwd_multi_kernel(SoftminMulti<T> m, XkpOperands ops, int D, SplitInfo sp) {
         const int n = min(kXkpCols, je - j0);
         const int ncg = (n + 31) >> 5;
         if (s == 0 && tid < kXkpCols) {      // H_j of the tile; read after the last stage's barrier, rewritten two tiles on
-            float H = kNegBig;
-            if (tid < n) {
-                const long col = (long)b * M + j0 + tid;
-                H = __builtin_fmaf(-0.5f * s2, ops.cn2[k][col], dual_entry(prm, col) * kLog2e);
+            if constexpr (P == 1) {
+                xkp_dist_columns<T>(prm, ops.cn2[k], (long)b * M + j0 + tid, tid < n, &Hs[t & 1][tid], &Hs[2 + (t & 1)][tid]);
+            } else {
+                float H = kNegBig;
+                if (tid < n) {
+                    const long col = (long)b * M + j0 + tid;
+                    H = __builtin_fmaf(-0.5f * s2, ops.cn2[k][col], dual_entry(prm, col) * kLog2e);
+                }
+                Hs[t & 1][tid] = H;
             }
-            Hs[t & 1][tid] = H;
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wavefront's share of step q has landed ...
         __syncthreads();                                      // ... and so has everybody's; step q - 1 is consumed
@@ -240,21 +259,29 @@ xkp_fwd_multi_kernel(SoftminMulti<T> m, XkpOperands ops, int D, SplitInfo sp) {
             }
             if (s == NS - 1) {
                 // ---- epilogue: lane (half, i) holds row i of a block against the columns 8 (e / 4) + 4 half + e % 4 ----
-                f32x16 H[2];
-#pragma unroll
-                for (int cg = 0; cg < 2; ++cg)
-#pragma unroll
-                    for (int g4 = 0; g4 < 4; ++g4) {
-                        const float4 v = *reinterpret_cast<const float4*>(&Hs[t & 1][(wc * 2 + cg) * 32 + g4 * 8 + half * 4]);
-                        H[cg][4 * g4] = v.x; H[cg][4 * g4 + 1] = v.y; H[cg][4 * g4 + 2] = v.z; H[cg][4 * g4 + 3] = v.w;
-                    }
-                const bool cg1 = wc * 2 + 1 < ncg;      // (the wavefront's second column group may lie past the tile)
-#pragma unroll
-                for (int rt = 0; rt < 2; ++rt) {
+                [[maybe_unused]] f32x16 H[2];
+                if constexpr (P == 2) {
 #pragma unroll
                     for (int cg = 0; cg < 2; ++cg)
 #pragma unroll
-                        for (int e = 0; e < 16; ++e) acc[rt][cg][e] = __builtin_fmaf(s2, acc[rt][cg][e], H[cg][e]);
+                        for (int g4 = 0; g4 < 4; ++g4) {
+                            const float4 v = *reinterpret_cast<const float4*>(&Hs[t & 1][(wc * 2 + cg) * 32 + g4 * 8 + half * 4]);
+                            H[cg][4 * g4] = v.x; H[cg][4 * g4 + 1] = v.y; H[cg][4 * g4 + 2] = v.z; H[cg][4 * g4 + 3] = v.w;
+                        }
+                }
+                const bool cg1 = wc * 2 + 1 < ncg;      // (the wavefront's second column group may lie past the tile)
+#pragma unroll
+                for (int rt = 0; rt < 2; ++rt) {
+                    if constexpr (P == 1) {
+                        xkp_dist_exponents<T>(acc[rt], &Hs[t & 1][wc * 64], &Hs[2 + (t & 1)][wc * 64], rn[rt], thr[rt], s2, cg1,
+                                              prm.x + (long)b * N * D, prm.y + (long)b * M * D, row0 + wr * 64 + rt * 32, N, j0 + wc * 64, je,
+                                              half, D);
+                    } else {
+#pragma unroll
+                        for (int cg = 0; cg < 2; ++cg)
+#pragma unroll
+                            for (int e = 0; e < 16; ++e) acc[rt][cg][e] = __builtin_fmaf(s2, acc[rt][cg][e], H[cg][e]);
+                    }
                     float um = fmaxf(kMinusHuge, max16(acc[rt][0]));
                     if (cg1) um = fmaxf(um, max16(acc[rt][1]));
                     um = fmaxf(um, __shfl_xor(um, 32, 64));
@@ -290,7 +317,7 @@ xkp_fwd_multi_kernel(SoftminMulti<T> m, XkpOperands ops, int D, SplitInfo sp) {
         const float mn = fmaxf(m0, m1);
         const float sum = mrg[0][tid][1] * fast_exp2(m0 - mn) + mrg[1][tid][1] * fast_exp2(m1 - mn);
         const long idx = (long)b * N + row0 + tid;
-        const float mtot = __builtin_fmaf(-0.5f * s2, ops.rn2[k][idx], mn);      // r_i + max
+        const float mtot = P == 1 ? mn : __builtin_fmaf(-0.5f * s2, ops.rn2[k][idx], mn);      // r_i + max (P = 1: no row constant)
         if (ns == 1) {
             prm.out[idx] = finish_value(prm, idx, mtot + fast_log2(sum));
         } else {
@@ -307,7 +334,8 @@ xkp_fwd_multi_kernel(SoftminMulti<T> m, XkpOperands ops, int D, SplitInfo sp) {
 bool xkp_pack(const void* x, const void* y, int B, int N, int M, int D, int in_dtype, void* ws, size_t bytes, hipStream_t st);
 // The problems of `m` (rows / columns of problem k: x / y, y / x, x / x, y / y) on the operands xkp_pack left in `ws`: one launch, and
 // the merge of its column splits where the rest of the workspace holds some.
-void xkp_reduce(SoftminMulti<float>& m, int B, int N, int M, int D, void* ws, size_t bytes, bool allow_split, hipStream_t st);
-void xkp_reduce(SoftminMulti<bf16_t>& m, int B, int N, int M, int D, void* ws, size_t bytes, bool allow_split, hipStream_t st);
+// p = 2: the dot-product epilogue; p = 1: the distance epilogue (glhip_dist_xkp.h), `m` built with p = 1.
+void xkp_reduce(SoftminMulti<float>& m, int B, int N, int M, int D, int p, void* ws, size_t bytes, bool allow_split, hipStream_t st);
+void xkp_reduce(SoftminMulti<bf16_t>& m, int B, int N, int M, int D, int p, void* ws, size_t bytes, bool allow_split, hipStream_t st);
 
 }  // namespace glhip

@@ -141,7 +141,10 @@ def _workspace(lib, x, B, N, M, D, ranges):
 def _iter4_scratch(lib, x, B, rows, cols, D, clouds=None):
     """Scratch buffer of the launches that run four reductions side by side (iteration, annealing, extrapolation): four times that of one
     dense reduction of ``rows`` x ``cols``.  ``clouds`` = (N, M, p) of an iteration / annealing: the library's own size where it has the
-    symbol (version 146) — the same for D <= 16, the packed clouds of glhip_softmin_xkp.h beyond."""
+    symbol (version 146) — the same for D <= 16, the packed clouds of glhip_softmin_xkp.h beyond.  ``clouds`` = (N, M, p, flags) with
+    FLAG_XK_ITER_DIST, p = 1 and D > 16: the size of that route (``glhip_sinkhorn_iter4_dist_workspace_bytes``, version 147)."""
+    if clouds is not None and len(clouds) > 3 and clouds[3] & FLAG_XK_ITER_DIST and clouds[2] == 1 and D > XD_MAX_DIM:
+        return _scratch(int(lib.glhip_sinkhorn_iter4_dist_workspace_bytes(B, clouds[0], clouds[1], D)), x.device)
     if clouds is not None and hasattr(lib, "glhip_sinkhorn_iter4_workspace_bytes"):
         return _scratch(int(lib.glhip_sinkhorn_iter4_workspace_bytes(B, clouds[0], clouds[1], D, clouds[2])), x.device)
     return _scratch(4 * int(lib.glhip_workspace_bytes(B, rows, cols, D, 0)), x.device)
@@ -355,7 +358,7 @@ def _launch(stem, x, ranges, out_shape, head, dims, scalars, flags, routes=None,
 
 def sinkhorn_iter4_raw(x, y, a_log, b_log, pots, eps, damping, debias=True, flags=0, p=2):
     """The 4 (or 2) simultaneous updates of one Sinkhorn iteration in one launch (p = 1, 2 with D <= 16; p = 2 up to D = MFMA_FWD_MAX_DIM
-    on operands packed once per call, glhip_softmin_xkp.h).
+    on operands packed once per call, glhip_softmin_xkp.h; p = 1 up to that dimension under ``FLAG_XK_ITER_DIST``, glhip_dist_xkp.h).
 
     x (B,N,D), y (B,M,D); a_log (B,N), b_log (B,M); ``pots`` = None (initialisation) or the old potentials
     ``(f_ba, g_ab, f_aa, g_bb)`` / ``(f_ba, g_ab)`` as (B,N) / (B,M) fp32.  Returns the new ones, same arity."""
@@ -367,7 +370,7 @@ def sinkhorn_iter4_raw(x, y, a_log, b_log, pots, eps, damping, debias=True, flag
     old = [None] * 4 if first else list(pots) + [None] * (4 - len(pots))
     new = outs + [None] * (4 - len(outs))
     with torch.cuda.device(x.device):
-        ws, ws_args = _iter4_scratch(lib, x, B, max(N, M), max(N, M), D, (N, M, int(p)))
+        ws, ws_args = _iter4_scratch(lib, x, B, max(N, M), max(N, M), D, (N, M, int(p), int(flags)))
         rc = lib.glhip_sinkhorn_iter4(x.data_ptr(), y.data_ptr(), a_log.data_ptr(), b_log.data_ptr(),
                                       *[_ptr(t) for t in old], *[_ptr(t) for t in new], B, N, M, D, float(eps), float(damping),
                                       int(p), _dtype_code(x), int(first), *ws_args, int(flags), _stream(x))
@@ -1074,7 +1077,7 @@ def softmin_value_and_grad(eps, x, y, h, guess, margin, ranges=None, flags=0):
 
 def sinkhorn_iter4(eps, x, y, a_log, b_log, pots, damping, debias=True, flags=0, p=2):
     """One whole iteration of the symmetric Sinkhorn loop on the GPU, non-differentiable (dense; p = 1 or 2 with D <= 16, p = 2 up to
-    D = MFMA_FWD_MAX_DIM).
+    D = MFMA_FWD_MAX_DIM, p = 1 up to that dimension with ``flags=FLAG_XK_ITER_DIST``).
 
     x: (N,D)|(B,N,D), y: (M,D)|(B,M,D); a_log: (N,)|(1,N)|(B,N), b_log likewise; ``pots`` None (initial potentials)
     or the old ``(f_ba, g_ab, f_aa, g_bb)`` / ``(f_ba, g_ab)``.  Returns the new potentials, shaped like a_log / b_log."""
@@ -1108,7 +1111,8 @@ class Iter4Plan:
     validated contiguous inputs, the scratch buffer, two sets of output buffers (an iteration reads the potentials the
     previous one wrote, and outputs may not alias inputs).  At N ~ 1e3 the per-call Python work (checks, allocations,
     device guard) costs more than the kernels; the plan leaves one ctypes call per iteration.  Dimensions as :func:`sinkhorn_iter4`;
-    for p = 2 clouds of D > 16 every :meth:`run` packs the clouds again and :meth:`anneal` packs them once for all its temperatures."""
+    for p = 2 clouds of D > 16 (and p = 1 ones under ``FLAG_XK_ITER_DIST``) every :meth:`run` packs the clouds again and :meth:`anneal`
+    packs them once for all its temperatures."""
 
     def __init__(self, x, y, a_log, b_log, debias=True, flags=0, p=2):
         self.lib = load_library()
@@ -1126,7 +1130,7 @@ class Iter4Plan:
         dev = xb.device
         self.device = dev
         with torch.cuda.device(dev):
-            self.ws, self.ws_args = _iter4_scratch(self.lib, xb, B, max(N, M), max(N, M), D, (N, M, self.p))
+            self.ws, self.ws_args = _iter4_scratch(self.lib, xb, B, max(N, M), max(N, M), D, (N, M, self.p, self.flags))
             self.sets = []
             for _ in range(2):
                 flat = torch.empty(B * sum(sizes), dtype=torch.float32, device=dev)

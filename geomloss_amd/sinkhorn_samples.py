@@ -188,10 +188,11 @@ class _HipSoftmin:
         on its own (those run faster as separate launches with pre-packed columns).  The coarse level of the multiscale
         backend (dense, ~2e3 clusters with their own weights) qualifies: its 7 x 4 soft-mins become 7 launches.
         Online p = 2 clouds of 16 < D <= hip.MFMA_FWD_MAX_DIM qualify under `_XK_ITER` (the pre-packed operands of glhip_softmin_xkp.h),
-        up to `_XK_ITER_MAX_PAIRS` pairs per soft-min."""
+        up to `_XK_ITER_MAX_PAIRS` pairs per soft-min; online p = 1 clouds of those dimensions under `_XK_ITER_P1` (off by default), with
+        hip.FLAG_XK_ITER_DIST on the plan (the distance epilogue of glhip_dist_xkp.h)."""
         x, y = C_xy[0], C_xy[1]
         D = x.shape[-1]
-        xk = _XK_ITER and self.p == 2 and not self.multiscale and hip.XD_MAX_DIM < D <= hip.MFMA_FWD_MAX_DIM
+        xk = ((_XK_ITER and self.p == 2) or (_XK_ITER_P1 and self.p == 1)) and not self.multiscale and hip.XD_MAX_DIM < D <= hip.MFMA_FWD_MAX_DIM
         if self.p not in (1, 2) or (D > hip.XD_MAX_DIM and not xk) or not _fuse_iterations or x.dtype == torch.float64:
             return None
         if self.p == 1 and (hip.autosort_applies(x, y) or hip.autosort_applies(y, x)):
@@ -207,7 +208,8 @@ class _HipSoftmin:
         if plan is None or plan[0] is not x or plan[1] is not a_log or plan[2] is not b_log or plan[3] != debias:
             if not create:
                 return None
-            plan = self._plan = (x, a_log, b_log, debias, hip.Iter4Plan(x, y, a_log, b_log, debias, p=self.p))
+            flags = hip.FLAG_XK_ITER_DIST if (xk and self.p == 1) else 0
+            plan = self._plan = (x, a_log, b_log, debias, hip.Iter4Plan(x, y, a_log, b_log, debias, flags=flags, p=self.p))
         return plan[4]
 
     def iter4(self, eps, C_xy, a_log, b_log, pots, damping, debias):
@@ -271,6 +273,9 @@ _ITER4_MAX_PAIRS = 4e9   # measured: B x 4096^2 with B = 32..128 and N = 3e4 gai
 # (9e8 pairs, the largest point timed: separate launches won nowhere, so the threshold is where the measurements end)
 _XK_ITER = os.environ.get("GEOMLOSS_HIP_XK_ITER", "1") != "0"
 _XK_ITER_MAX_PAIRS = 1e9
+# ... and online p = 1 clouds of those dimensions on the same operands (glhip_dist_xkp.h, library version 147, hip.FLAG_XK_ITER_DIST):
+# GEOMLOSS_HIP_XK_ITER_P1=1 opts in, same pair cap; off by default (measurements: profiles/iter4_xk_p1.txt)
+_XK_ITER_P1 = os.environ.get("GEOMLOSS_HIP_XK_ITER_P1", "0") == "1"
 _graphs = hip.GraphCache()
 
 

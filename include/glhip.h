@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GLHIP_VERSION 146 /* 0.1.46 */
+#define GLHIP_VERSION 147 /* 0.1.47 */
 
 /* element type of the point clouds x, y */
 #define GLHIP_F32 0
@@ -161,6 +161,14 @@ extern "C" {
                                   and columns without mass, no float atomics); values differ by rounding (another centre, another
                                   feature scale).  GLHIP_FLAG_NO_SPLIT is honoured, GLHIP_FLAG_F16X2 ignored.  Every other entry point,
                                   and D > 16, ignore the flag, bit for bit. */
+#define GLHIP_FLAG_XK_ITER_DIST 65536 /* version 147.  glhip_sinkhorn_iter4 / glhip_sinkhorn_anneal with p == 1 and 17 <= D <= 4095 (float32 /
+                                  bfloat16, dense, B <= 65535): the one-launch iteration on the pre-packed operands of version 146 with the
+                                  distance epilogue of csrc/glhip_dist_xkp.h — d2 = |xt_i|^2 + |yt_j|^2 - 2 <xt_i, yt_j> from the packed,
+                                  temperature-free records, near pairs re-evaluated on explicit differences of the caller's points
+                                  (the rule of GLHIP_FLAG_XK_DIST), the clamp of utils.py:61, a square root and one FMA per pair.
+                                  Workspace: glhip_sinkhorn_iter4_dist_workspace_bytes; NULL or shorter: two or four launches of the
+                                  half-step kernel of GLHIP_FLAG_XK_DIST instead, same results up to rounding.  Without the flag those
+                                  calls stay GLHIP_EUNSUPPORTED.  No effect for p == 2 or D <= 16; every other entry point ignores the bit. */
 #define GLHIP_FLAG_NO_SORT 512 /* p = 1 soft-min / half-step, laplacian and energy products: big dense launches (B = 1, D <= 3, N >= 65536,
                                   N M >= 5e8, a workspace of glhip_workspace_bytes) sort both clouds into the workspace themselves — voxel sort along a
                                   boustrophedon path, csrc/glhip_autosort.h — so that the squared distances can come from the matrix cores
@@ -389,6 +397,7 @@ int glhip_softmin_perm_applies(int B, long N, long M, int D, int p, int dtype, i
  * refused alike.  Workspace: glhip_sinkhorn_iter4_workspace_bytes.  With a NULL or shorter workspace the call runs its half-steps as
  * two or four launches of the kernel of glhip_sinkhorn_step instead: same results up to rounding.  p = 1 with D > 16 and D > 4095
  * stay GLHIP_EUNSUPPORTED.
+ * Version 147: p = 1 with 17 <= D <= 4095 under GLHIP_FLAG_XK_ITER_DIST (see there); unsupported without the flag, as before.
  */
 int glhip_sinkhorn_iter4(const void* x, const void* y, const float* a_log, const float* b_log,
                          const float* f_ba, const float* g_ab, const float* f_aa, const float* g_bb,
@@ -424,6 +433,14 @@ int glhip_sinkhorn_anneal(const void* x, const void* y, const float* a_log, cons
  * (p = 1 with D > 16, D > 4095, p outside {1, 2}).
  */
 size_t glhip_sinkhorn_iter4_workspace_bytes(int B, int N, int M, int D, int p);
+
+/*
+ * Version 147.  The workspace of glhip_sinkhorn_iter4 / glhip_sinkhorn_anneal with p == 1 under GLHIP_FLAG_XK_ITER_DIST: the packed
+ * operands and split partials of the p = 2 sizing above (the records are the same).  0 outside 17 <= D <= 4095 and for an empty
+ * cloud; non-decreasing in N, M and D.  (glhip_sinkhorn_iter4_workspace_bytes keeps answering 0 for p = 1 beyond D = 16: the route is
+ * opt-in.)
+ */
+size_t glhip_sinkhorn_iter4_dist_workspace_bytes(int B, int N, int M, int D);
 
 /*
  * The coarse-to-fine jump of the two-scale loop in ONE launch (+ one merge launch): the four extrapolations of

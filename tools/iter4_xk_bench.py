@@ -5,7 +5,12 @@
 Part 1: online SamplesLoss("sinkhorn", p=2, blur=0.3), float32, forward and forward + backward: the parent build (four half-step launches
 per temperature) against this build with GEOMLOSS_HIP_XK_ITER on, alternated in one process, `--reps` repetitions of a window of at least
 `--window` seconds each; median and spread (max - min) per point.
-Part 2: one raw iteration (hip.Iter4Plan.run: pack + one launch + merge) against the four hip.sinkhorn_step launches it replaces, this build."""
+Part 2: one raw iteration (hip.Iter4Plan.run: pack + one launch + merge) against the four hip.sinkhorn_step launches it replaces, this build.
+
+    python tools/iter4_xk_bench.py --p 1 [--out FILE]      -> profiles/iter4_xk_p1.txt
+
+The same two parts for p = 1 (glhip_dist_xkp.h): GEOMLOSS_HIP_XK_ITER_P1 off (four half-step launches of xk_dist_kernel per temperature,
+the default) against on, both from THIS build's library, alternated in one process."""
 
 import argparse
 import os
@@ -43,26 +48,33 @@ def stats(ts):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--parent", required=True)
+    ap.add_argument("--parent", default=None, help="p = 2: the parent commit's library")
+    ap.add_argument("--p", type=int, default=2, choices=(1, 2))
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.25)
     ap.add_argument("--quick", action="store_true", help="two small shapes only (rehearsal)")
     a = ap.parse_args()
+    if a.p == 2 and not a.parent:
+        ap.error("--p 2 needs --parent")
+    p = a.p
     out = open(a.out, "w") if a.out else sys.stdout
     say = lambda s: (print(s, file=out, flush=True), print(s, flush=True) if a.out else None)      # noqa: E731
     dev = torch.device("cuda:0")
     say(f"# {' '.join(sys.argv)}\n# {torch.cuda.get_device_name(0)}; {a.reps} repetitions of >= {a.window} s windows, builds alternated; ms per call: median (max - min)")
 
-    builds = {"parent": (a.parent, False), "packed": (_glhip.LIB_PATH, True)}
+    builds = {"parent": (a.parent if p == 2 else _glhip.LIB_PATH, False), "packed": (_glhip.LIB_PATH, True)}      # p = 1: "parent" = knob off
 
     def use(name):
         path, on = builds[name]
         _glhip.load_library(path)
-        ss._XK_ITER = on
+        if p == 2:
+            ss._XK_ITER = on
+        else:
+            ss._XK_ITER_P1 = on
 
-    say("\n## online SamplesLoss('sinkhorn', p=2, blur=0.3), float32\n# B N D | forward: parent, packed, ratio | forward + backward: parent, packed, ratio")
-    L = SamplesLoss("sinkhorn", p=2, blur=0.3, backend="online")
+    say(f"\n## online SamplesLoss('sinkhorn', p={p}, blur=0.3), float32\n# B N D | forward: {'parent' if p == 2 else 'knob off'}, packed, ratio | forward + backward: likewise")
+    L = SamplesLoss("sinkhorn", p=p, blur=0.3, backend="online")
     shapes = [(None, N, D) for N in (512, 2000, 8000) for D in (32, 64, 128, 512)] + [(32, 1024, 64)]
     if a.quick:
         shapes = [(None, 512, 32), (2, 300, 64)]
@@ -92,17 +104,17 @@ def main():
 
     say("\n## one raw iteration, float32, debias: four sinkhorn_step launches | Iter4Plan.run (pack + launch + merge) | ratio | pairs per soft-min")
     use("packed")
-    raw = [(N, D) for N in (2000, 8000, 30000) for D in (64, 128)]
+    raw = [(N, D) for N in (2000, 8000, 30000) for D in ((64, 128) if p == 2 else (64,))]
     if a.quick:
         raw = [(2000, 64)]
     for N, D in raw:
         torch.manual_seed(0)
         x, y = torch.rand(N, D, device=dev), torch.rand(N, D, device=dev)
         lw = torch.full((N,), -float(torch.log(torch.tensor(float(N)))), device=dev)
-        eps, damp = 0.3**2, 1.0
+        eps, damp = 0.3**p, 1.0
         pots = tuple(0.1 * torch.rand(N, device=dev) for _ in range(4))
-        plan = hip.Iter4Plan(x, y, lw, lw, True)
-        step = lambda r, c, pot, prev: hip.sinkhorn_step(eps, r, c, lw, pot, prev, damp, p=2)      # noqa: E731
+        plan = hip.Iter4Plan(x, y, lw, lw, True, flags=hip.FLAG_XK_ITER_DIST if p == 1 else 0, p=p)
+        step = lambda r, c, pot, prev: hip.sinkhorn_step(eps, r, c, lw, pot, prev, damp, p=p, flags=hip.FLAG_XK_DIST if p == 1 else 0)      # noqa: E731
         four = lambda: (step(x, y, pots[1], pots[0]), step(y, x, pots[0], pots[1]), step(x, x, pots[2], pots[2]), step(y, y, pots[3], pots[3]))  # noqa: E731
         one = lambda: plan.run(eps, damp, pots)                                                                                                      # noqa: E731
         t4, t1 = [], []
